@@ -1,23 +1,32 @@
 #!/usr/bin/env python3
 """Headline benchmark: env-steps/s of the batched reset/step/mask/reward hot path.
 
-    python bench.py --gpus N --steps K --warmup W [--config c3] [--reward centroid] [--envs 4096]
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR] [--config c3] [--reward centroid] [--envs 4096]
 
 A "step" is one batched transition of all environments on a GPU, one kernel launch: on-device uniform
 sampling of a legal action, the transition (place + legal mask + observations + the terminal routing
 reward) and, after a terminal transition, the reset inside the same launch.  The headline replays a
-queue of instances filled before the timed region from reference-exact RNG streams (as in round 1);
-`fresh_instances` in the line is the same loop where every reset takes a NEW instance of the
-environment's stream, generated on the GPU while the steps run (the reference's reset() semantics,
-`--instances device`), `rollout` the persistent kernel that runs 16 steps per launch and keeps every
-step's tensors (trajectory layout).  Environments shard
-by global index over ranks with no data-path collective (weak scaling); `python bench.py --gpus N`
-starts the N ranks itself.
+queue of instances filled before the timed region from reference-exact RNG streams (as in round 1).
+Environments shard by global index over ranks with no data-path collective (weak scaling);
+`python bench.py --gpus N` starts the N ranks itself.
 
-One JSON line on rank 0: metric/value (whole-job env-steps/s), `roofline` for the dominant kernel
-(k_step: algorithmic bytes per launch / mean launch duration from HIP events on the launch stream), and
-`cpu_baseline` (the oracle restatement of the reference, timed on this box's host cores over a bounded
-sample of the same instances and the same action stream, with a parity check of rewards/dones).
+One JSON line on rank 0: metric/value (whole-job env-steps/s over exactly --steps timed steps) and
+ms_per_step.  A plain run does only that.  With --full the line also carries what takes runs of its own:
+`ms_per_step_repeats` (further timed regions), `roofline` for the dominant kernel (k_step: algorithmic
+bytes per launch / mean launch duration from HIP events on the launch stream, next to measured copy and
+fill ceilings), `cpu_baseline` (the oracle restatement of the reference, timed on the host cores over a
+bounded sample of the same instances and the same action stream, with a parity check of rewards/dones),
+`fresh_instances` (the same loop where every reset takes a NEW instance of the environment's stream,
+generated on the GPU while the steps run: the reference's reset() semantics, `--instances device`),
+`external_actions_staggered`, `rollout` (the persistent kernel that runs 16 steps per launch and keeps
+every step's tensors, trajectory layout) and, for N > 1, `north_star_config4`.
+
+--dump-outputs DIR: after the timed region, rank 0 writes what the last timed step returned to its caller
+(observations, reward, done, info, actions) as DIR/<name>.npy, float32 or float64, every value finite: an
+info value the reference leaves out is 0 in info_<key>.npy and 0 in info_<key>_present.npy.  Per-environment
+scalars cover every environment; the observation tensors cover a fixed, seeded sample of environments
+(`obs_env_index.npy`) kept under 48 MB.  Inputs depend only on the arguments, so two builds can be
+compared output for output.
 """
 import argparse
 import json
@@ -283,6 +292,29 @@ def cpu_baseline(cfg, run_seed, sample_envs, sample_steps, queue_depth):
     return out
 
 
+def dump_outputs(dirname, env, actions):
+    """What the last step returned to its caller -> dirname/<name>.npy (float32 for integer tensors, float64 kept).
+    Observation tensors: a fixed, seeded sample of environments, at most 256 and 48 MB.  Every value written is finite."""
+    os.makedirs(dirname, exist_ok=True)
+    B = env.num_envs
+
+    def host(t):
+        t = t.detach()
+        return (t if t.dtype == torch.float64 else t.to(torch.float32)).cpu().numpy()
+    per_env = sum(v[0].numel() * (8 if v.dtype == torch.float64 else 4) for v in env.obs.values())
+    n = max(1, min(B, 256, (48 << 20) // max(1, per_env)))
+    idx = np.sort(np.random.default_rng(0).choice(B, n, replace=False))
+    idx_t = torch.from_numpy(idx).to(env.device)
+    out = {"obs_env_index": idx.astype(np.float64), "reward": host(env.reward), "done": host(env.done), "actions": host(actions)}
+    for k, v in env.info.items():  # NaN where the reference's info dict is empty: written as 0 next to a presence mask
+        present = ~torch.isnan(v)
+        out["info_" + k] = host(torch.where(present, v, torch.zeros_like(v)))
+        out["info_" + k + "_present"] = host(present)
+    out.update({"obs_" + k: host(v.index_select(0, idx_t)) for k, v in env.obs.items()})
+    for k, v in out.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -313,18 +345,29 @@ def main():
                     help="N > 1 (default there): every 16 steps all-gather + standardise a [16*B] float32 advantage tensor "
                          "(the PPO-side collective, 256 KiB per rank at 4 096 envs) over RCCL")
     ap.add_argument("--no-adv-allgather", dest="adv_allgather", action="store_false")
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each; `value` comes from the first, the spread of all is reported")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: repeats, roofline + copy/fill ceilings, CPU baseline, the "
+                         "fresh-instance, staggered and rollout legs, config 4 for N > 1 (the --no-* options below trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each; `value` comes from the first, the spread of all is reported "
+                         "(default 5 with --full, else 1)")
     ap.add_argument("--rollout-steps", type=int, default=16,
-                    help="also time the persistent rollout kernel with this many steps per launch in the trajectory layout "
+                    help="--full: also time the persistent rollout kernel with this many steps per launch in the trajectory layout "
                          "(reported as `rollout`; 0 = skip)")
-    ap.add_argument("--no-fresh-leg", action="store_true", help="skip the extra leg with a fresh on-device instance at every reset")
-    ap.add_argument("--no-staggered-leg", action="store_true", help="skip the extra leg with external actions and staggered episode phases")
+    ap.add_argument("--no-fresh-leg", action="store_true", help="--full: skip the extra leg with a fresh on-device instance at every reset")
+    ap.add_argument("--no-staggered-leg", action="store_true", help="--full: skip the extra leg with external actions and staggered episode phases")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-events", action="store_true")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start N fresh ranks (one per GPU) and relay rank 0's line.
         # Nothing in this process has touched the GPU (importing torch does not), and it is not replaced: the ranks
@@ -450,13 +493,16 @@ def main():
 
     own, region_ms = timed_region(args.warmup)
     elapsed, per_rank_s = over_ranks(own)
+    if args.dump_outputs and rank == 0:  # before the repeats: the same step with and without --full
+        last = (args.steps - 1) % chunk
+        dump_outputs(args.dump_outputs, env, chunk_actions[last] if chunk > 1 else actions)
     repeats_ms = [elapsed / args.steps * 1e3]
     for r in range(1, max(1, args.repeats)):  # the spread: further regions of the same length, not part of `value`
         own_r, _ = timed_region(args.warmup + r * args.steps)
         repeats_ms.append(over_ranks(own_r)[0] / args.steps * 1e3)
     steps_done = args.warmup + max(1, args.repeats) * args.steps
     step_kernel_ms = None
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         if args.loop == "fused" and cfg.reward_type == "centroid":
             step_kernel_ms = region_ms / args.steps
         elif args.event_steps > 0:
@@ -471,7 +517,7 @@ def main():
     # N > 1: BASELINE.json's config 4 (pin_spatial 64x64, 4 096 environments per GPU, sharded) next to the headline workload,
     # which stays c3 for every N so that the per-N values of one scaling run are comparable
     config4 = None
-    if dist and args.config == "c3" and not args.incremental:
+    if args.full and dist and args.config == "c3" and not args.incremental:
         cfg4 = named_config("c4", args.reward)
         env4 = BatchedPlacementEnv(cfg4, B, device=f"cuda:{dev_index}", queue_depth=args.queue_depth, run_seed=args.run_seed,
                                    first_env_index=rank * B, auto_reset=True, threads_per_env=args.threads_per_env)
@@ -490,13 +536,13 @@ def main():
         config4 = {"workload": "c4: pin_spatial 64x64, 16 components, 48 pins", "envs_per_gpu": B, "steps": n4,
                    "value": round(world * B * n4 / t4, 1), "unit": "env-steps/s (all ranks)", "ms_per_step": round(t4 / n4 * 1e3, 5)}
     staggered = None
-    if args.loop == "fused" and not args.incremental and cfg.kind != 0 and not args.no_staggered_leg:
+    if args.full and args.loop == "fused" and not args.incremental and cfg.kind != 0 and not args.no_staggered_leg:
         staggered = external_actions_staggered_leg(cfg, args, B, dev_index, rank)
     fresh = None
-    if args.instances == "replay" and args.loop == "fused" and not args.incremental and cfg.kind != 0 and not args.no_fresh_leg:
+    if args.full and args.instances == "replay" and args.loop == "fused" and not args.incremental and cfg.kind != 0 and not args.no_fresh_leg:
         fresh = fresh_instances_leg(cfg, args, B, dev_index, rank)
     rollout = None
-    if args.rollout_steps > 0 and not args.incremental and args.config != "c1":
+    if args.full and args.rollout_steps > 0 and not args.incremental and args.config != "c1":
         if dist:
             dist.barrier()
         rollout = rollout_leg(cfg, args, B, dev_index, rank, args.rollout_steps)
@@ -535,7 +581,7 @@ def main():
                     "algorithmic_bytes_per_env_step": b_alg, "units_per_launch": B,
                     "kernel_ms": round(step_kernel_ms, 5)}
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             sample_envs, sample_steps = {"c2": (4096, 128), "c3": (2048, 64), "c4": (2048, 48), "c5": (256, 64)}.get(args.config, (64, 64))
             res = cpu_baseline(cfg, args.run_seed, sample_envs, sample_steps, args.queue_depth)
             nthr = max(res)
@@ -567,7 +613,7 @@ def main():
                 "terminal_launches_note": (f"episodes are {L} steps and in lock-step: a region of {args.steps} steps from step {args.warmup} holds "
                                            f"{term_in_region} terminal launches (reward + reset of every environment), {args.steps / L:.2f} on average") if lockstep else None,
                 "adv_allgather_bytes_per_rank": (16 * B * 4 if adv is not None else 0),
-                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64",
+                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64", "full": args.full,
                 "data": "synthetic (reference-exact instance streams, seeds 1000003*run_seed+env" + (", generated on the GPU, a new instance at every reset" if args.instances == "device" else ", queued once and replayed") + "; uniform legal actions drawn on device)",
                 "config": {"workload": f"{args.config}: {cfg.height}x{cfg.width} grid, {cfg.max_num_components} components, "
                                        f"{cfg.max_total_pins} pins, reward={args.reward}", "envs_per_gpu": B,

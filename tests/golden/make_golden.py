@@ -20,7 +20,8 @@ action-independent.  Per case it stores, in `tests/golden/<case>.npz`:
 
 Also written: `spaces.json` (the gym spaces every reference constructor declares), `model_config_spatial.json` (the
 shipped hyper-parameters of the spatial policy, a data file of the reference), `adapter_views.npz` (`env.components`
-with all pin coordinates after whole episodes), `norm2.npz` (np.linalg.norm of length-2 vectors in this container's
+with all pin coordinates after whole episodes), `episode_export.npz` (the reference's Pin / Component objects of one
+episode, before and after placement), `norm2.npz` (np.linalg.norm of length-2 vectors in this container's
 NumPy/OpenBLAS -- SURVEY.md trap T1) and `setorder.npz` (CPython iteration order of
 `set(points) - visited` -- trap T2).  The files are data only; no reference source
 text is stored.
@@ -259,6 +260,40 @@ def record_adapter_views():
     np.savez_compressed(os.path.join(HERE, "adapter_views.npz"), **data)
 
 
+def record_episode_export():
+    """What utils/visualization/csv_utils.py:11-25 pickles (`components` + `actions`) for one finished episode of
+    spatial_small_centroid, built with the reference's own Pin / Component (keyword arguments) and placed with its own
+    `place_component`: the parameter names of both constructors, the attributes right after construction and after
+    placement (`tests/golden/episode_export.npz`; pcbenv.io.episode_to_reference_objects is checked against it by
+    tests/test_host_logic.py)."""
+    import inspect
+    sys.path[:0] = [os.path.dirname(HERE), os.path.join(REPO, "rl-environment-for-component-placement_amd")]
+    from golden_util import load_case
+    from environment.dummy_env_rectangular_pin_spatial import Component, Pin
+    name = "spatial_small_centroid"
+    _, _, eps = load_case(name)
+    e = next(ep for ep in eps if ep.done[len(ep.actions) - 2] and not np.isnan(ep.info[len(ep.actions) - 2, 0]) and len(ep.actions) > 3)
+    ins = e.instance
+    pin_params = [p for p in inspect.signature(Pin.__init__).parameters if p != "self"]
+    comp_params = [p for p in inspect.signature(Component.__init__).parameters if p != "self"]
+    pins = [[] for _ in range(ins.num_components)]
+    for k in range(len(ins.pin_id)):
+        pins[int(ins.pin_comp[k])].append(Pin(relative_x=int(ins.pin_rel_x[k]), relative_y=int(ins.pin_rel_y[k]), pin_id=int(ins.pin_id[k]),
+                                              component_id=int(ins.pin_comp[k]), net_id=int(ins.pin_net[k])))
+    comps = [Component(h=int(ins.comp_h[i]), w=int(ins.comp_w[i]), comp_id=i, pins=pins[i]) for i in range(ins.num_components)]
+    data = {"meta": np.array(json.dumps({"case": name, "seed": int(e.seed), "ep": int(e.ep)})),
+            "pin_params": np.array(pin_params), "comp_params": np.array(comp_params),
+            "pin_ctor": np.array([[getattr(p, n) for n in pin_params] for c in comps for p in c.pins], np.int16),
+            "comp_ctor": np.array([[c.h, c.w, c.comp_id, len(c.pins)] for c in comps], np.int16)}
+    actions = e.actions[:ins.num_components]
+    for c, (o, x, y) in zip(comps, actions):
+        c.place_component(int(o), int(x), int(y))
+    data["actions"] = np.array(actions, np.int16)
+    data["comp_position"] = np.array([c.position for c in comps], np.int16)
+    data["pin_placed"] = np.array([[p.pin_id, p.relative_x, p.relative_y, p.absolute_x, p.absolute_y] for c in comps for p in c.pins], np.int16)
+    np.savez_compressed(os.path.join(HERE, "episode_export.npz"), **data)
+
+
 def record_model_config():
     """The hyper-parameters the reference ships for the spatial policy (`agent/config/rectangle_pin_spatial_model.json`,
     a data file): `tests/golden/model_config_spatial.json`, compared with pcbenv/policy.py's defaults by
@@ -273,6 +308,9 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "model_config":  # only the (tiny) model-config fixture
         record_model_config()
         raise SystemExit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "episode_export":  # only the (tiny) episode-export fixture
+        record_episode_export()
+        raise SystemExit(0)
     total = 0
     for case in CASES:
         sz = record_case(*case)
@@ -282,5 +320,6 @@ if __name__ == "__main__":
     record_setorder()
     record_spaces()
     record_adapter_views()
+    record_episode_export()
     record_model_config()
     print(f"total {total / 1024:.1f} KiB")

@@ -1,10 +1,11 @@
-"""bench.py's output contract (one JSON line with the driver's keys + roofline + cpu_baseline) and its multi-rank
+"""bench.py's output contract (one JSON line with the driver's keys; roofline + cpu_baseline with --full) and its multi-rank
 path, rehearsed with two gloo ranks sharing the one GPU of the box."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,7 +23,7 @@ def _last_json(out: str):
 
 @gpu
 def test_single_gpu_line():
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "48", "--warmup", "8", "--envs", "512"],
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "48", "--warmup", "8", "--envs", "512", "--full"],
                          capture_output=True, text=True, timeout=600, cwd=REPO)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _last_json(out.stdout)
@@ -36,6 +37,35 @@ def test_single_gpu_line():
     rep = d["ms_per_step_repeats"]
     assert rep["n"] == 5 and rep["min"] <= rep["median"] <= rep["max"] and rep["min"] <= d["ms_per_step"] <= rep["max"]
     assert d["world_size_observed"] == 1 and d["per_rank_env_steps_per_sec"] == [d["value"]]
+
+
+@gpu
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run times exactly --steps steps and measures nothing else; --dump-outputs writes the last step's outputs
+    as float32 / float64 .npy files, identical from run to run with the same arguments."""
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "24", "--warmup", "4", "--envs", "512",
+                              "--config", "c4", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=REPO)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = _last_json(out.stdout)
+        assert REQUIRED <= set(line) and line["full"] is False and line["steps"] == 24 and line["warmup"] == 4
+        assert line["roofline"] is None and line["cpu_baseline"] is None and line["rollout"] is None
+        assert line["fresh_instances"] is None and line["external_actions_staggered"] is None and line["ms_per_step_repeats"]["n"] == 1
+        assert abs(line["value"] - 512 * 24 / (line["ms_per_step"] * 24e-3)) / line["value"] < 0.02
+        files = {f.name: np.load(f) for f in sorted(d.iterdir())}
+        assert {"reward.npy", "done.npy", "actions.npy", "obs_env_index.npy", "obs_grid.npy", "obs_action_mask.npy",
+                "info_wirelength.npy", "info_wirelength_present.npy", "info_num_intersections.npy"} <= set(files)
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert all(np.isfinite(a).all() for a in files.values()), [k for k, a in files.items() if not np.isfinite(a).all()]
+        assert sum(a.nbytes for a in files.values()) <= 64 << 20
+        assert files["reward.npy"].shape == (512,) and files["actions.npy"].shape == (512, 3)
+        assert files["obs_grid.npy"].shape[0] == len(files["obs_env_index.npy"])
+        dumps.append(files)
+    assert set(dumps[0]) == set(dumps[1])
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
 
 
 @gpu

@@ -132,33 +132,46 @@ def test_instance_file_roundtrip(tmp_path):
         io.load_instances(p)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/environment"), reason="reference tree not present (build container only)")
 def test_episode_export_builds_reference_components():
-    """utils/visualization/csv_utils.py:11-25 pickles `components` + `actions`; the export rebuilds those objects
-    with the reference's own classes and must land every pin where the oracle's features say it is."""
-    import sys
-    sys.dont_write_bytecode = True
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path[:0] = [os.path.join(repo, "oracle", "refshim"), "/root/reference"]
-    try:
-        from environment.dummy_env_rectangular_pin_spatial import Component, Pin
-    finally:
-        del sys.path[:2]
+    """utils/visualization/csv_utils.py:11-25 pickles `components` + `actions`; the export rebuilds those objects with
+    the reference's own classes.  tests/golden/episode_export.npz holds what the reference's Pin / Component carried
+    for this episode when built with keyword arguments, and after their own `place_component`: the export must call
+    the constructors and `place_component` with exactly those values, and every placed pin must land where the
+    oracle's features say it is."""
+    from golden_util import GOLDEN_DIR
     from oracle import oracle as orc
     from pcbenv import io
-    meta, cfg, eps = load_case("spatial_small_centroid")
+    g = np.load(os.path.join(GOLDEN_DIR, "episode_export.npz"))
+    meta = json.loads(str(g["meta"]))
+    _, cfg, eps = load_case(meta["case"])
     e = next(ep for ep in eps if ep.done[len(ep.actions) - 2] and not np.isnan(ep.info[len(ep.actions) - 2, 0]) and len(ep.actions) > 3)
+    assert (e.seed, e.ep) == (meta["seed"], meta["ep"])
     valid_actions = e.actions[:e.instance.num_components]
+
+    class Pin:  # records the arguments under the reference constructor's parameter names
+        def __init__(self, *args):
+            self.args = {str(n): v for n, v in zip(g["pin_params"], args)}
+
+    class Component:
+        def __init__(self, *args):
+            self.args = {str(n): v for n, v in zip(g["comp_params"], args)}
+            self.placed_with = None
+
+        def place_component(self, orientation, x, y):
+            self.placed_with = (orientation, x, y)
     comps, acts = io.episode_to_reference_objects(e.instance, valid_actions, Component, Pin)
+    assert [[c.args["h"], c.args["w"], c.args["comp_id"], len(c.args["pins"])] for c in comps] == g["comp_ctor"].tolist()
+    assert [[p.args[str(n)] for n in g["pin_params"]] for c in comps for p in c.args["pins"]] == g["pin_ctor"].tolist()
+    assert acts == [tuple(a) for a in g["actions"].tolist()] and [c.placed_with for c in comps] == acts
     env = orc.OracleEnv(cfg)
     env.reset(instance=e.instance)
     for a in valid_actions:
         obs, _, _, _ = env.step(a)
     feats = obs["all_pins_num_feature"]
-    for c in comps:
-        assert tuple(c.position) == (obs["all_components_feature"][c.comp_id, 2], obs["all_components_feature"][c.comp_id, 3])
-        for pin in c.pins:
-            assert list(feats[pin.pin_id]) == [pin.relative_x, pin.relative_y, pin.absolute_x, pin.absolute_y]
+    for comp_id, pos in enumerate(g["comp_position"].tolist()):
+        assert tuple(pos) == (obs["all_components_feature"][comp_id, 2], obs["all_components_feature"][comp_id, 3])
+    for pin_id, rx, ry, ax, ay in g["pin_placed"].tolist():
+        assert list(feats[pin_id]) == [rx, ry, ax, ay]
 
 
 def test_expand_compact_features_is_the_reference_arithmetic():

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Copy the judged summaries from gpurun_out/<round>/ into profiles/<round>/ and derive profiles/traffic_<cfg>.json
+"""Copy the judged summaries from prof_out/<round>/ (tools/profile_all.sh) into profiles/<round>/ and derive profiles/traffic_<cfg>.json
 (HBM bytes per k_step launch from the PMC passes; KiB units, gfx950 FETCH_SIZE x2 correction per MI355X_MICROARCH.md)."""
 import csv
 import glob
@@ -9,7 +9,7 @@ import shutil
 import sys
 
 R = sys.argv[1] if len(sys.argv) > 1 else "r2"
-src, dst = f"gpurun_out/{R}", f"profiles/{R}"
+src, dst = f"prof_out/{R}", f"profiles/{R}"
 os.makedirs(dst, exist_ok=True)
 for f in glob.glob(f"{src}/*_bench.json"):
     lines = [l for l in open(f) if l.startswith("{")]
