@@ -25,6 +25,8 @@
  *   pcbenv_sample_actions, pcbenv_step_sampled
  *                          the uniform-random valid-action policy and its simulate() loop body
  *                            agent/random/random_policy_square.py:11-23 (and siblings)
+ *   pcbenv_gather          no counterpart: the closest is copy.deepcopy(env) of a reference env object, which a
+ *                          caller uses to fork an episode (lookahead, beam search, population resampling)
  *
  * Observations are written into caller-owned device buffers (pcbenv_buffers)
  * and updated in place by the next call; the library owns only the handle, the
@@ -282,6 +284,25 @@ int pcbenv_queue_cursors(pcbenv *env, uint32_t *min_out, uint32_t *max_out, void
 int64_t pcbenv_state_bytes(const pcbenv *env);
 int pcbenv_get_state(pcbenv *env, void *host_dst, void *stream);
 int pcbenv_set_state(pcbenv *env, const void *host_src, void *stream);
+
+/* Fork / reorder episodes on the device.  Environment i of dst continues the episode in progress of environment
+ * src_index[i] of src (src == NULL or src == dst: the same handle; any permutation or repetition is allowed).
+ * src_index: int32 [dst num_envs] on the device; -1 = keep this environment's episode.  Any other out-of-range value
+ * also keeps the episode, and if errors_dev is not NULL it ORs 1 into *errors_dev.  The two handles must have equal
+ * environment definitions: every pcbenv_config field from kind through weight_num_intersections.  The batch fields
+ * (num_envs, queue_depth, flags, threads_per_env) may differ.  Both handles must be on one device with buffers bound.
+ * Asynchronous on `stream`, one kernel launch (and, within one handle, a 25-byte-per-environment device-to-device
+ * snapshot of reward / done / info before it); the caller orders src's last launch before it.  Not capturable into a
+ * hipGraph (PCBENV_ESTATE).
+ * What moves is the episode: the state block (occupancy and legal-mask bit rows, component and pin records, the
+ * current component) and, in the destination's selected slot, every bound tensor (pcbenv_buffers, the compact feature
+ * tensors, the mask marginals) -- written whole -- and reward / done / info, copied from the source's selected slot.
+ * Afterwards every tensor row of i is bit-identical to what src_index[i] showed, and every later step of i matches
+ * what src_index[i] would have done.
+ * What stays the destination's own -- the one deliberate difference from copy.deepcopy -- is its instance stream: the
+ * queue cursor, the episode count, the queue and the on-device generator's state.  The next reset of i takes i's own
+ * next instance, as it would have without the gather. */
+int pcbenv_gather(pcbenv *dst, const pcbenv *src, const int32_t *src_index_dev, uint32_t *errors_dev, void *stream);
 
 /* Bit-packed legal-action mask of the current component, library-owned device
  * memory: uint64 [B, 2, H, ceil(W/64)] (orientation 0/1; pin kinds: 2 = 0, 3 = 1;

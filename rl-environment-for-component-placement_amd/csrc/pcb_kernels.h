@@ -1,7 +1,8 @@
-// pcb_kernels.h -- the __global__ kernels: k_reset, k_step, k_sample, k_cursor_range
+// pcb_kernels.h -- the __global__ kernels: k_reset, k_gather, k_step, k_sample, k_cursor_range
 // Part of libpcbenv.so (CDNA4 / gfx950 only).
 #pragma once
 #include "pcb_team.h"
+#include "pcb_launch.h"
 
 // Workgroups go to the eight XCDs round-robin (blockIdx.x % 8).  Environment of workgroup `block` (the environments'
 // workgroups follow `head` others): XCD * B/8 + turn, so that each XCD -- each L2 -- owns a contiguous eighth of every
@@ -32,6 +33,62 @@ __global__ __launch_bounds__(64 * NW) void k_reset(DevParams p, const unsigned c
         p.buf.reward[row] = 0.0;
         p.buf.done[row] = 0;
         if (p.buf.info) { p.buf.info[2 * (size_t)row] = nan(""); p.buf.info[2 * (size_t)row + 1] = nan(""); }
+    }
+    T::store_state(smem, p, e, lane);
+}
+
+// pcbenv_gather: environment e of the destination continues the episode in progress of environment j = src_index[e] of the
+// source (same handle or another one with the same definition).  One team per destination environment, like k_reset:
+// the source's block of the CURRENT state set -> LDS, the header patched, the block written to the destination's OTHER
+// set (the host swaps the sets afterwards, as after a step launch: a permutation inside one handle reads nothing this
+// launch writes), and every bound tensor of the destination's selected slot written whole from LDS -- the emission of a
+// trajectory slot, where nothing may be assumed about what the destination holds.  Rows with j == -1 or j out of
+// range keep their episode: their block is copied as it is, and none of their tensors is touched.
+// What the header must not take over from the source:
+//   qcursor, episode  the destination's instance stream: its next reset takes its own next record.  feat_cache_valid
+//                     compares the cache tag with `episode`, so the spatial cache is refilled below under that tag;
+//   term_seq / pos    a copied terminal-list mark would claim the source's list entry in the next step launch
+//                     (MODE_DELEGATED waiting for helpers that work on another environment): not listed;
+//   pre_action        drawn from the source's mask for the source's global index: cleared;
+//   feat_gen          the destination's bind generation: its pin-feature rows are written whole here.
+template <int KIND, int WW, int NW>
+__global__ __launch_bounds__(64 * NW) void k_gather(DevParams p, GatherArgs g) {
+    typedef Team<64 * NW> T;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int e = xcd_contiguous_env((int)blockIdx.x, 0, p.B), lane = threadIdx.x;
+    const int j = __builtin_amdgcn_readfirstlane(g.src_index[e]);
+    const bool take = (unsigned)j < (unsigned)g.src_B;  // checked before it addresses anything
+    if (!take && j != -1 && g.errors && lane == 0) atomicOr(g.errors, 1u);
+    const unsigned char *own = p.state + (size_t)e * p.stateStride;
+    T::load_state_from(smem, take ? g.src_state + (size_t)j * p.stateStride : own, p, lane);
+    typename T::Lds l = T::carve(smem, p);
+    if (take) {
+        if (lane == 0) {
+            const EnvHdr *oh = (const EnvHdr *)own;
+            l.hdr->qcursor = oh->qcursor; l.hdr->episode = oh->episode;
+            l.hdr->term_seq = 0u; l.hdr->term_pos = 0u;
+            l.hdr->pre_action = 0u;
+            if (KIND == PCBENV_PIN || KIND == PCBENV_SPATIAL) l.hdr->feat_gen = p.bind_gen;
+        }
+        T::lds_sync();
+        const int row = T::out_row(p, p.slot, e);
+        if (KIND == PCBENV_SPATIAL) T::build_pin_tables(p, l, lane);
+        T::template emit_features_full<KIND>(p, l, row, lane);
+        if (KIND == PCBENV_SPATIAL) {
+            T::emit_component_grid(p, l, row, lane);  // from the pin tables (unrotated coordinates)
+            T::feat_cache_fill(p, l, e, lane);        // trajectory layout: what this episode's steps copy, tagged with `episode`
+            T::lds_sync();                            // the tables share their zone with the class map of emit_pin_grid
+        }
+        T::template mask_and_emit<KIND, WW>(p, l, row, lane, true, 0, p.H);
+        if (KIND == PCBENV_SPATIAL) T::template emit_pin_grid<WW>(p, l, row, lane, 0, p.H);
+        if (lane == 0) {
+            p.buf.reward[row] = g.reward[j];
+            p.buf.done[row] = g.done[j];
+            if (p.buf.info) {
+                p.buf.info[2 * (size_t)row] = g.info ? g.info[2 * (size_t)j] : nan("");
+                p.buf.info[2 * (size_t)row + 1] = g.info ? g.info[2 * (size_t)j + 1] : nan("");
+            }
+        }
     }
     T::store_state(smem, p, e, lane);
 }

@@ -2,7 +2,7 @@
 // including pcb_kind_<name>[_<part>].hip).  Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (one IEEE operation
 // per written operator; the only fused multiply-add is the explicit __fma_rn in norm2).
 // The pin kinds are split into PARTS, one translation unit each, so that the build is as long as its slowest part:
-//   0 = reset + launch switch + k_step without routes (in-place and rollout builds), 1 = k_step without routes, one
+//   0 = reset + gather + launch switch + k_step without routes (in-place and rollout builds), 1 = k_step without routes, one
 //   transition into a trajectory slot, 2 / 3 = k_step with beam / both routes on one / four wavefronts;
 // PCB_PART undefined = a kind without routes (square, rect), everything in one unit.
 // (The slot build has a unit of its own for its code, not only for the build time: next to the rollout build every
@@ -44,6 +44,13 @@ int PCB_FN(pcb_launch_reset)(const ResetLaunch &a) {
 #define LAUNCH_RESET(WW_, NW_) hipLaunchKernelGGL((k_reset<KIND, WW_, NW_>), dim3(d.B), dim3(64 * NW_), d.ldsBytes, a.stream, d, a.mask)
     if (d.WW == 1) { if (a.threads == 64) LAUNCH_RESET(1, 1); else LAUNCH_RESET(1, 4); }
     else { if (a.threads == 64) LAUNCH_RESET(2, 1); else LAUNCH_RESET(2, 4); }
+    return 0;
+}
+int PCB_FN(pcb_launch_gather)(const GatherLaunch &a) {
+    const DevParams &d = a.d;
+#define LAUNCH_GATHER(WW_, NW_) hipLaunchKernelGGL((k_gather<KIND, WW_, NW_>), dim3(d.B), dim3(64 * NW_), d.ldsBytes, a.stream, d, a.g)
+    if (d.WW == 1) { if (a.threads == 64) LAUNCH_GATHER(1, 1); else LAUNCH_GATHER(1, 4); }
+    else { if (a.threads == 64) LAUNCH_GATHER(2, 1); else LAUNCH_GATHER(2, 4); }
     return 0;
 }
 int PCB_FN(pcb_step_plain)(const StepLaunch &a) {

@@ -14,6 +14,19 @@ struct StepLaunch {
     hipStream_t stream;
 };
 struct ResetLaunch { DevParams d; const unsigned char *mask; int threads; hipStream_t stream; };
+// pcbenv_gather: d is the destination's parameter block (d.state = its current state set, d.state_out = the other one);
+// the source's current state set and the rows of its selected slot (or, source == destination, the snapshot of them
+// taken before the launch) travel in GatherArgs.
+struct GatherArgs {
+    const unsigned char *src_state;
+    const int *src_index;
+    unsigned *errors;
+    const double *reward, *info;  // row j of the source = element j (info: 2 j, 2 j + 1); info may be null
+    const unsigned char *done;
+    int src_B;
+};
+struct GatherLaunch { DevParams d; GatherArgs g; int threads; hipStream_t stream; };
 
-#define PCB_DECLARE_KIND(name) int pcb_launch_step_##name(const StepLaunch &a); int pcb_launch_reset_##name(const ResetLaunch &a);
+#define PCB_DECLARE_KIND(name) int pcb_launch_step_##name(const StepLaunch &a); int pcb_launch_reset_##name(const ResetLaunch &a); \
+    int pcb_launch_gather_##name(const GatherLaunch &a);
 PCB_DECLARE_KIND(square) PCB_DECLARE_KIND(rect) PCB_DECLARE_KIND(pin) PCB_DECLARE_KIND(spatial)

@@ -23,8 +23,9 @@ static __device__ inline Lds carve(unsigned char *smem, const DevParams &p) {
     l.seg = (double *)(smem + p.ldsSeg);
     return l;
 }
-static __device__ inline void load_state(unsigned char *smem, const DevParams &p, int e, int lane) {
-    const uint4 *src = (const uint4 *)(p.state + (size_t)e * p.stateStride);
+// State block at `block` (one of p.stateStride bytes) -> LDS.
+static __device__ inline void load_state_from(unsigned char *smem, const unsigned char *block, const DevParams &p, int lane) {
+    const uint4 *src = (const uint4 *)block;
     uint4 *dst = (uint4 *)smem;
     const int n = (int)(p.stateStride / 16);
     if (n <= NT) {  // small blocks (c2): one chunk per lane
@@ -41,6 +42,9 @@ static __device__ inline void load_state(unsigned char *smem, const DevParams &p
         for (int i = lane + 4 * NT; i < n; i += NT) dst[i] = src[i];
     }
     lds_sync();
+}
+static __device__ inline void load_state(unsigned char *smem, const DevParams &p, int e, int lane) {
+    load_state_from(smem, p.state + (size_t)e * p.stateStride, p, lane);
 }
 static __device__ inline void store_state(const unsigned char *smem, const DevParams &p, int e, int lane) {
     lds_sync();

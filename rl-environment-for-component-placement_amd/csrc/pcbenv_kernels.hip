@@ -17,6 +17,7 @@
 // written operator; the only fused multiply-add is the explicit __fma_rn in norm2).
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -58,6 +59,7 @@ struct pcbenv {
     unsigned *term_seen_host;     // mapped host memory the step kernel reports its list length to (DevParams::term_seen)
     unsigned char *state_buf[2];  // double-buffered state blocks: dp.state is the current one, a step launch writes the other
     int state_cur;
+    unsigned char *gather_snap;   // pcbenv_gather within one handle: reward | info | done of the selected slot before the launch
     char err[256];
 };
 
@@ -306,6 +308,7 @@ extern "C" void pcbenv_destroy(pcbenv *env) {
     if (env->dp.feat_cache_tag) hipFree(env->dp.feat_cache_tag);
     if (env->term_seen_host) hipHostFree(env->term_seen_host);
     if (env->scratch) hipFree(env->scratch);
+    if (env->gather_snap) hipFree(env->gather_snap);
     delete env;
 }
 
@@ -377,6 +380,10 @@ extern "C" int pcbenv_bind_buffers_slots(pcbenv *env, const pcbenv_buffers *b, i
         DEVICE_GUARD(env);
         if (hipMalloc((void **)&d.feat_cache, (size_t)d.featCacheStride * d.B) != hipSuccess || hipMalloc((void **)&d.feat_cache_tag, 4 * (size_t)d.B) != hipSuccess)
             return fail(env, PCBENV_EHIP, "hipMalloc failed");
+    }
+    if (!env->gather_snap) {  // pcbenv_gather's snapshot (25 bytes per environment), allocated here and not per call
+        DEVICE_GUARD(env);
+        if (hipMalloc((void **)&env->gather_snap, 25 * (size_t)env->dp.B) != hipSuccess) return fail(env, PCBENV_EHIP, "hipMalloc failed");
     }
     if (env->dp.feat_cache_tag) hipMemset(env->dp.feat_cache_tag, 0xFF, 4 * (size_t)env->dp.B);  // no episode has that number: nothing cached yet
     env->dp.bind_gen += 1;  // feature tensors of these buffers are uninitialised: the next reset of each env fills them
@@ -817,6 +824,61 @@ extern "C" int pcbenv_rollout_sampled(pcbenv *env, int32_t *actions_out_dev, int
         gen_after_launch(env, auto_reset ? num_steps : 0, (hipStream_t)stream);
     }
     HIP_TRY(env, hipGetLastError());
+    return PCBENV_OK;
+}
+
+// ---- pcbenv_gather ------------------------------------------------------------------------------------------
+// The environment definition is every pcbenv_config field from kind through weight_num_intersections.
+static_assert(offsetof(pcbenv_config, weight_num_intersections) + sizeof(double) == offsetof(pcbenv_config, num_envs),
+              "the definition fields end where the batch fields begin");
+extern "C" int pcbenv_gather(pcbenv *dst, const pcbenv *src, const int32_t *src_index_dev, uint32_t *errors_dev, void *stream) {
+    if (!dst) return fail(0, PCBENV_EINVAL, "null handle");
+    if (!src) src = dst;
+    if (!src_index_dev) return fail(dst, PCBENV_EINVAL, "null src_index");
+    if (src != dst) {
+        if (src->device != dst->device) return fail(dst, PCBENV_EINVAL, "the two handles are on different devices");
+        if (memcmp(&src->cfg, &dst->cfg, offsetof(pcbenv_config, num_envs)) != 0)
+            return fail(dst, PCBENV_EINVAL, "the two handles have different environment definitions");
+    }
+    if (!dst->bound || !src->bound) return fail(dst, PCBENV_ESTATE, "pcbenv_bind_buffers has not been called");
+    DEVICE_GUARD(dst);
+    hipStream_t s = (hipStream_t)stream;
+    // A captured launch would be replayed with the state sets of the capture: the second replay would read a stale set.
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+        return fail(dst, PCBENV_ESTATE, "pcbenv_gather cannot be captured into a graph");
+    GatherLaunch a;
+    a.d = dst->dp;
+    DevParams &d = a.d;
+    a.threads = dst->threads; a.stream = s;
+    // the store policy a trajectory-layout step launch would use (dispatch_step)
+    if (d.num_slots > 1) d.stream_stores = dst->cell_bytes_per_env * d.B * d.num_slots > dst->stream_threshold;
+    d.state = dst->state_buf[dst->state_cur];
+    d.state_out = dst->state_buf[dst->state_cur ^ 1];
+    const DevParams &sp = src->dp;
+    const size_t r0 = (size_t)sp.slot * sp.B;  // first row of the source's selected slot
+    GatherArgs &g = a.g;
+    g.src_state = sp.state; g.src_index = src_index_dev; g.errors = (unsigned *)errors_dev; g.src_B = sp.B;
+    if (src == dst) {
+        // another team may overwrite row j of reward / done / info before the team that reads it runs: read a snapshot
+        const size_t B = (size_t)d.B;
+        unsigned char *snap = dst->gather_snap;
+        HIP_TRY(dst, hipMemcpyAsync(snap, sp.buf.reward + r0, 8 * B, hipMemcpyDeviceToDevice, s));
+        if (sp.buf.info) HIP_TRY(dst, hipMemcpyAsync(snap + 8 * B, sp.buf.info + 2 * r0, 16 * B, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(dst, hipMemcpyAsync(snap + 24 * B, sp.buf.done + r0, B, hipMemcpyDeviceToDevice, s));
+        g.reward = (const double *)snap; g.info = sp.buf.info ? (const double *)(snap + 8 * B) : 0; g.done = snap + 24 * B;
+    } else {
+        g.reward = sp.buf.reward + r0; g.info = sp.buf.info ? sp.buf.info + 2 * r0 : 0; g.done = sp.buf.done + r0;
+    }
+    switch (dst->cfg.kind) {
+    case PCBENV_SQUARE: pcb_launch_gather_square(a); break;
+    case PCBENV_RECT: pcb_launch_gather_rect(a); break;
+    case PCBENV_PIN: pcb_launch_gather_pin(a); break;
+    default: pcb_launch_gather_spatial(a); break;
+    }
+    HIP_TRY(dst, hipGetLastError());
+    dst->state_cur ^= 1;
+    dst->dp.state = dst->dp.state_out = dst->state_buf[dst->state_cur];
     return PCBENV_OK;
 }
 

@@ -369,6 +369,34 @@ class BatchedPlacementEnv:
             int(step_index0), self._stream()), self._h)
         return out
 
+    def gather_(self, index: torch.Tensor, source: Optional["BatchedPlacementEnv"] = None, check: bool = False) -> Dict[str, torch.Tensor]:
+        """Fork / reorder episodes on the device (`pcbenv_gather`, one kernel launch, no host round trip): environment i
+        continues the episode in progress of environment `index[i]` of `source` (default: this environment batch; any
+        permutation or repetition), `-1` keeps i's own episode.  `source` needs an equal definition (the same EnvConfig;
+        num_envs, queue_depth, flags may differ) on the same device.  Every observation tensor, reward, done and info row of i
+        (selected slot) then equals what `index[i]` showed, and later steps of i go as those of `index[i]` would have.  The
+        instance stream stays i's own: its next reset takes its own next instance (the one difference from
+        `copy.deepcopy` of a reference env).  check=True raises IndexError if an index was out of range (such rows keep
+        their episode); it synchronises the host, so it is off by default."""
+        src = self if source is None else source
+        idx = index.to(device=self.device, dtype=torch.int32).contiguous()
+        if tuple(idx.shape) != (self.num_envs,):
+            raise ValueError(f"index must have shape [{self.num_envs}], got {tuple(idx.shape)}")
+        err = torch.zeros(1, dtype=torch.int32, device=self.device) if check else None
+        # reset_done() reads _last_done: the kernel carries `done` of the selected slots over; where _last_done lives in
+        # another slot (either side), the forked rows' flags are taken from the source's _last_done here, before the launch
+        in_slot = (self._last_done.data_ptr() == self.done.data_ptr() and src._last_done.data_ptr() == src.done.data_ptr())
+        if not in_slot:
+            taken = (idx >= 0) & (idx < src.num_envs)
+            forked = src._last_done[idx.long().clamp(0, src.num_envs - 1)]
+        _lib.check(self._L.pcbenv_gather(self._h, None if src is self else src._h, idx.data_ptr(),
+                                         None if err is None else err.data_ptr(), self._stream()), self._h)
+        if not in_slot:
+            self._last_done = torch.where(taken, forked, self._last_done)
+        if check and int(err.item()) != 0:
+            raise IndexError(f"gather_: an index is outside [-1, {src.num_envs}) (those environments kept their episode)")
+        return self.obs
+
     def queue_cursors(self):
         """(min, max) over the environments of the number of resets performed so far (synchronises)."""
         lo, hi = C.c_uint32(), C.c_uint32()

@@ -1,0 +1,370 @@
+"""pcbenv_gather on the GPU: fork / reorder episodes on the device, through the C ABI (BatchedPlacementEnv.gather_ and
+direct calls), bit for bit.  The oracle for destination row i after a gather is OracleBatch.reset_packed with the
+source's current instance record followed by a replay of the source's actions since its last reset; later resets of i
+take the destination's own queue records.  Right after a gather every tensor row of i must equal the pre-gather
+snapshot of the source row; every later step must equal the oracle (identical bytes, identical float64 bit patterns)."""
+import numpy as np
+import pytest
+import torch
+
+from pcbenv import _lib, env_seed, named_config
+from pcbenv.batched_env import BatchedPlacementEnv
+from pcbenv.config import KIND_PIN, KIND_SPATIAL, KIND_SQUARE
+
+pytestmark = pytest.mark.gpu
+
+
+def _bytes_equal(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+
+
+class Run:
+    """A BatchedPlacementEnv next to its CPU oracle and, per row, what the oracle needs to rebuild it: the instance
+    record of the current episode, the actions since its last reset and the number of resets (the queue cursor)."""
+
+    def __init__(self, cfg, B, run_seed=3, queue_depth=3, device_instances=False, max_resets=64, **kw):
+        from oracle import oracle as orc
+        self.cfg, self.B, self.Q = cfg, B, queue_depth
+        self.env = BatchedPlacementEnv(cfg, B, queue_depth=queue_depth, run_seed=run_seed, **kw)
+        self.square = cfg.kind == KIND_SQUARE
+        self.fresh = self.packed = None
+        if device_instances:
+            from pcbenv.instances import NativeInstanceStreams
+            self.env.enable_device_instances()
+            host = NativeInstanceStreams(cfg, [env_seed(run_seed, i) for i in range(B)])
+            self.fresh = [host.next_packed() for _ in range(max_resets)]
+        elif not self.square:
+            self.packed = self.env.generate_instances()
+        self.ob = orc.OracleBatch(cfg, B)
+        self.cursor = np.zeros(B, np.int64)
+        self.inst = [None] * B
+        self.hist = [[] for _ in range(B)]
+        self.last_done = np.zeros(B, np.uint8)
+        self.S = self.env.num_slots
+        self.env.reset()
+        self.oracle_reset(np.ones(B, np.uint8))
+
+    def record(self, i):
+        c = int(self.cursor[i])
+        return self.fresh[c][i] if self.fresh is not None else self.packed[c % self.Q][i]
+
+    def oracle_reset(self, mask):
+        mask = np.asarray(mask).astype(bool)
+        if self.square:
+            for i in np.flatnonzero(mask):
+                self.ob.env(int(i)).reset()
+        else:
+            rec = np.stack([self.record(i) for i in range(self.B)])
+            self.ob.reset_packed(rec, mask.astype(np.uint8))
+            for i in np.flatnonzero(mask):
+                self.inst[i] = rec[i]
+        for i in np.flatnonzero(mask):
+            self.hist[i] = []
+        self.cursor[mask] += 1
+
+    def host_obs(self, f64=False):
+        e = self.env
+        out = {k: v.cpu().numpy() for k, v in (e.obs_f64() if f64 else e.obs).items()}
+        if not f64:
+            out.update({"marginal_" + k: v.cpu().numpy() for k, v in e.mask_marginals.items()})
+            out.update(reward=e.reward.cpu().numpy(), done=e.done.cpu().numpy(), info=e.info_raw.cpu().numpy())
+        return out
+
+    def compare_oracle(self, tag):
+        obs = self.host_obs(f64=True)
+        for k, v in obs.items():
+            bad = self.ob.first_mismatch(k, v)
+            assert bad < 0, (tag, k, bad)
+        m = self.env.mask_marginals
+        if m:  # marginals against the mask they summarise
+            am = self.env.obs["action_mask"].reshape(self.B, -1, self.cfg.height, self.cfg.width)
+            assert torch.equal(m["rows"], am.amax(dim=3)), tag
+            assert torch.equal(m["orientation"], am.amax(dim=(2, 3))), tag
+
+    def gather(self, idx, src=None, check_snapshot=True):
+        """gather_ on the device; the snapshot and oracle bookkeeping on the host.  Returns the rows taken."""
+        src = src or self
+        idx = np.asarray(idx, np.int64)
+        take = (idx >= 0) & (idx < src.B)
+        before_src = src.host_obs()
+        before_own = before_src if src is self else self.host_obs()
+        self.env.gather_(torch.from_numpy(idx).to(self.env.device), source=None if src is self else src.env)
+        after = self.host_obs()
+        if check_snapshot:
+            for k, v in after.items():
+                want = before_own[k].copy()
+                want[take] = before_src[k][idx[take]]
+                assert _bytes_equal(v, want), ("snapshot", k, np.flatnonzero([not _bytes_equal(v[i], want[i]) for i in range(self.B)])[:5])
+        inst = [src.inst[j] for j in idx.clip(0, src.B - 1)]
+        hist = [list(src.hist[j]) for j in idx.clip(0, src.B - 1)]
+        last_done = src.last_done[idx.clip(0, src.B - 1)]
+        if self.square:
+            for i in np.flatnonzero(take):
+                self.ob.env(int(i)).reset()
+        else:
+            rec = np.stack([inst[i] if take[i] else self.inst[i] for i in range(self.B)])
+            self.ob.reset_packed(rec, take.astype(np.uint8))
+        for i in np.flatnonzero(take):
+            e = self.ob.env(int(i))
+            for a in hist[i]:
+                e.step_raw(a)
+            self.inst[i], self.hist[i], self.last_done[i] = inst[i], hist[i], last_done[i]
+        self.compare_oracle("after gather")
+        return take
+
+    def step(self, t, fused=True, p_bad=0.0, rng=None):
+        e = self.env
+        if self.S > 1:
+            e.select_slot(t + 1)
+        if fused:
+            want = e.sample_actions(t).cpu().numpy()  # k_sample draws from the mask alone: a stale presample would differ
+            _, r, d, _, a_dev = e.rollout_step(t)
+            a = a_dev.cpu().numpy()
+            assert np.array_equal(a, want), ("fused action", t)
+        else:
+            a = e.sample_actions(t).cpu().numpy()
+            if p_bad:
+                bad = rng.rand(self.B) < p_bad
+                a[bad] = rng.randint(-1, 70, size=(int(bad.sum()), 3))
+            _, r, d, _ = e.step(torch.from_numpy(a))
+        rr, dd, ii = self.ob.step(a)
+        for i in range(self.B):
+            self.hist[i].append(a[i].copy())
+        self.last_done = dd.copy()
+        if e.auto_reset:
+            self.oracle_reset(dd)
+        assert np.array_equal(d.cpu().numpy(), dd), ("done", t)
+        assert _bytes_equal(r.cpu().numpy(), rr), ("reward", t)
+        if self.cfg.kind in (KIND_PIN, KIND_SPATIAL):
+            inf = e.info_raw.cpu().numpy()
+            has = ~np.isnan(inf[:, 0])
+            assert _bytes_equal(inf[has], ii[has]), ("info", t)
+        self.compare_oracle(("step", t))
+        return dd
+
+    def reset_done(self):
+        self.env.reset_done()
+        self.oracle_reset(self.last_done)
+        self.last_done[:] = 0
+
+    def close(self):
+        self.env.close()
+
+
+def _perm_with_repeats(rng, B, src_B=None):
+    src_B = src_B or B
+    idx = rng.randint(0, src_B, size=B)
+    idx[rng.rand(B) < 0.1] = -1
+    return idx
+
+
+@pytest.mark.parametrize("name", ["c2", "c3", "c4"])
+def test_identity_and_keep_change_nothing(name):
+    """arange and all -1: every tensor unchanged, and later steps equal those of a twin handle that never gathered."""
+    cfg = named_config(name)
+    a, b = (BatchedPlacementEnv(cfg, 32, queue_depth=2, run_seed=4, auto_reset=True) for _ in range(2))
+    for e in (a, b):
+        e.generate_instances()
+        e.reset()
+
+    def tensors(e):
+        d = {k: v.cpu().numpy() for k, v in e.obs.items()}
+        d.update(reward=e.reward.cpu().numpy(), done=e.done.cpu().numpy(), info=e.info_raw.cpu().numpy())
+        return d
+    for t in range(3 * cfg.max_num_components):
+        if t % 5 == 2:
+            before = tensors(a)
+            idx = torch.arange(32, device=a.device) if t % 2 else torch.full((32,), -1, dtype=torch.int64, device=a.device)
+            a.gather_(idx)
+            after = tensors(a)
+            for k in before:
+                assert _bytes_equal(before[k], after[k]), (t, k)
+        ra = a.rollout_step(t)[-1].cpu().numpy()
+        rb = b.rollout_step(t)[-1].cpu().numpy()
+        assert np.array_equal(ra, rb), t
+        ta, tb = tensors(a), tensors(b)
+        for k in ta:
+            assert _bytes_equal(ta[k], tb[k]), (t, k)
+    a.close(); b.close()
+
+
+@pytest.mark.parametrize("name,reward", [("c1", "centroid"), ("c2", "centroid"), ("c3", "centroid"), ("c4", "centroid"),
+                                         ("c3", "beam"), ("c3", "both")])
+def test_permutation_with_repeats_mid_episode(name, reward):
+    """A random index with repeats and -1 in the middle of episodes, same handle; then two episodes of device-sampled
+    actions with auto-reset against the oracle -- and the explicit loop, gathering between step and reset_done."""
+    cfg = named_config(name, reward) if name in ("c3", "c4") else named_config(name)
+    rng = np.random.RandomState(11)
+    L = max(cfg.max_num_components, 6)
+    run = Run(cfg, 48, auto_reset=True)
+    for t in range(4):
+        run.step(t)
+    run.gather(_perm_with_repeats(rng, 48))
+    for t in range(4, 4 + 2 * L + 2):
+        run.step(t)
+        if t % 7 == 0:
+            run.gather(_perm_with_repeats(rng, 48))
+    run.close()
+    run = Run(cfg, 32, auto_reset=False)
+    pr = np.random.RandomState(2)
+    for t in range(2 * L):
+        run.step(t, fused=False, p_bad=0.03, rng=pr)
+        if t % 3 == 1:
+            run.gather(_perm_with_repeats(rng, 32))  # between the step and reset_done: reset_done acts on the forked flags
+            assert np.array_equal(run.env._last_done.cpu().numpy(), run.last_done)
+        run.reset_done()
+    run.close()
+
+
+def test_cross_handle_gather_and_errors():
+    cfg = named_config("c3")
+    rng = np.random.RandomState(5)
+    src = Run(cfg, 64, run_seed=8, auto_reset=True)
+    dst = Run(cfg, 256, run_seed=9, queue_depth=2, auto_reset=True)
+    for t in range(5):
+        src.step(t)
+        dst.step(t)
+    idx = _perm_with_repeats(rng, 256, 64)
+    dst.gather(idx, src=src)
+    for t in range(5, 5 + 2 * cfg.max_num_components):
+        dst.step(t)
+        src.step(t)
+        if t % 6 == 0:
+            dst.gather(_perm_with_repeats(rng, 256, 64), src=src)
+    # out-of-range indices keep the row and set the error word
+    bad = np.arange(256) % 64
+    bad[[3, 70, 200]] = [64, -2, 100000]
+    dst.env.gather_(torch.from_numpy(bad).to(dst.env.device), source=src.env)  # (rows checked below through the oracle)
+    take = (bad >= 0) & (bad < 64)
+    keep_hist = {i: list(dst.hist[i]) for i in np.flatnonzero(~take)}
+    dst_inst = {i: dst.inst[i] for i in np.flatnonzero(~take)}
+    rec = np.stack([src.inst[j] if take[i] else dst.inst[i] for i, j in enumerate(bad.clip(0, 63))])
+    dst.ob.reset_packed(rec, take.astype(np.uint8))
+    for i in np.flatnonzero(take):
+        e = dst.ob.env(int(i))
+        for a in src.hist[bad[i]]:
+            e.step_raw(a)
+        dst.inst[i], dst.hist[i] = src.inst[bad[i]], list(src.hist[bad[i]])
+    for i in keep_hist:
+        assert dst.inst[i] is dst_inst[i]
+    dst.compare_oracle("out of range")
+    err = torch.zeros(1, dtype=torch.int32, device=dst.env.device)
+    idx_dev = torch.from_numpy(bad.astype(np.int32)).to(dst.env.device)
+    L = dst.env._L
+    assert L.pcbenv_gather(dst.env._h, src.env._h, idx_dev.data_ptr(), err.data_ptr(), dst.env._stream()) == _lib.PCBENV_OK
+    assert int(err.item()) == 1
+    with pytest.raises(IndexError):
+        dst.env.gather_(idx_dev, source=src.env, check=True)
+    dst.env.gather_(torch.full((256,), -1, device=dst.env.device), check=True)  # nothing out of range: no error
+    assert L.pcbenv_gather(dst.env._h, src.env._h, None, None, dst.env._stream()) == _lib.PCBENV_EINVAL
+    # a different definition
+    other = BatchedPlacementEnv(named_config("c3", "both"), 64, queue_depth=1)
+    other.generate_instances(); other.reset()
+    with pytest.raises(ValueError):
+        dst.env.gather_(idx_dev, source=other)
+    assert L.pcbenv_gather(dst.env._h, other._h, idx_dev.data_ptr(), None, dst.env._stream()) == _lib.PCBENV_EINVAL
+    other.close()
+    # batch fields may differ: flags (no auto-reset on the source) and queue depth
+    plain = BatchedPlacementEnv(cfg, 16, queue_depth=1, run_seed=1)
+    plain.generate_instances(); plain.reset()
+    dst.env.gather_(torch.full((256,), -1, device=dst.env.device), source=plain)
+    plain.close()
+    src.close(); dst.close()
+
+
+@pytest.mark.parametrize("name,kw", [
+    ("c2", dict(num_slots=5)), ("c4", dict(num_slots=5)), ("c4", dict(num_slots=5, compact_features=True)),
+    ("c3", dict(num_slots=4, compact_features=True, mask_marginals=True)), ("c2", dict(mask_marginals=True)),
+    ("c3", dict(incremental_obs=True)), ("c4", dict(incremental_obs=True)),
+    ("c3", dict(threads_per_env=256)), ("c4", dict(threads_per_env=256)), ("c4", dict(threads_per_env=64, num_slots=3)),
+    ("c5", dict()), ("c5", dict(num_slots=3))])
+def test_layouts(name, kw):
+    cfg = named_config(name)
+    B = 8 if name == "c5" else 32
+    rng = np.random.RandomState(3)
+    run = Run(cfg, B, auto_reset=True, **kw)
+    steps = cfg.max_num_components + 6 if name != "c5" else 12
+    for t in range(steps):
+        run.step(t)
+        if t % 4 == 1:  # (trajectory layout: into the selected slot, the one the step just wrote)
+            run.gather(_perm_with_repeats(rng, B))
+    run.close()
+
+
+@pytest.mark.parametrize("name,B", [("c3", 512), ("c4", 256)])
+def test_staggered_episodes_with_helper_teams(name, B):
+    """Episode phases spread over the batch (1 / L of it terminal in every launch, helper teams on): gathers while
+    environments sit on the terminal list must still match the oracle."""
+    cfg = named_config(name)
+    L = cfg.max_num_components
+    rng = np.random.RandomState(9)
+    run = Run(cfg, B, auto_reset=True)
+    for t in range(3 * L):
+        run.step(t, fused=bool(t % 2))
+        if t < L:
+            m = (np.arange(B) % L == t).astype(np.uint8)
+            run.env.reset(torch.from_numpy(m))
+            run.oracle_reset(m)
+        if t % 3 == 2:
+            run.gather(_perm_with_repeats(rng, B), check_snapshot=(t % 6 == 2))
+    run.close()
+
+
+@pytest.mark.parametrize("name", ["c3", "c4"])
+def test_device_generator_streams_stay_the_destinations(name):
+    cfg = named_config(name)
+    B = 64
+    rng = np.random.RandomState(4)
+    run = Run(cfg, B, queue_depth=8, device_instances=True, auto_reset=True, max_resets=16)
+    for t in range(3 * cfg.max_num_components):
+        run.step(t)
+        if t % 5 == 3:
+            before = run.env.queue_cursors()
+            run.gather(_perm_with_repeats(rng, B))
+            assert run.env.queue_cursors() == before
+    assert run.env.device_instance_errors() == 0 and int(run.cursor.max()) < len(run.fresh)
+    run.close()
+
+
+def test_fused_sampler_right_after_a_gather():
+    """The presampled action is cleared by a gather: the fused launch right after it draws what k_sample draws from the
+    new mask (Run.step asserts it), and the results equal the oracle -- same handle and across handles with equal seeds."""
+    cfg = named_config("c3")
+    rng = np.random.RandomState(1)
+    a = Run(cfg, 32, run_seed=5, auto_reset=True)
+    b = Run(cfg, 32, run_seed=5, auto_reset=True)
+    for t in range(20):
+        a.step(t)
+        b.step(t)
+        a.gather(rng.permutation(32))
+        a.gather(rng.randint(0, 32, 32), src=b)
+    a.close(); b.close()
+
+
+def test_best_of_k_vs_oracle():
+    from oracle import oracle as orc
+    from pcbenv.search import best_of_k
+    cfg = named_config("c3")
+    P, k = 8, 6
+    root = Run(cfg, P, run_seed=6, auto_reset=False)
+    for t in range(3):
+        root.step(t)
+    planner = BatchedPlacementEnv(cfg, P * k, queue_depth=1, run_seed=7)
+    planner.generate_instances(); planner.reset()
+    res = best_of_k(root.env, planner, k, step_index=1000)
+    reward, child, acts, length, all_r = (x.cpu().numpy() for x in (res.reward, res.child, res.actions, res.length, res.child_rewards))
+    assert _bytes_equal(reward, all_r.max(axis=1)) and np.array_equal(child // k, np.arange(P))
+    assert _bytes_equal(all_r[np.arange(P), child % k], reward)
+    ob = orc.OracleBatch(cfg, 1)
+    for p in range(P):
+        ob.reset_packed(root.inst[p][None])
+        e = ob.env(0)
+        assert length[p] >= 1
+        for a in root.hist[p]:
+            e.step_raw(a)
+        for s in range(int(length[p])):
+            r, d, _ = e.step_raw(acts[s, p])
+            assert d == (s == length[p] - 1), (p, s)
+        assert np.float64(r).tobytes() == np.float64(reward[p]).tobytes(), (p, r, reward[p])
+    planner.close(); root.close()

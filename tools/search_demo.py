@@ -1,0 +1,76 @@
+"""Receding-horizon Monte-Carlo lookahead with pcbenv.search.best_of_k against the plain uniform-random policy, c3.
+python tools/search_demo.py [--roots 256] [--k 16]
+
+Both play the same instances (one episode per root environment).  The search forks every root k times into a planner
+batch (one device-side gather), plays every child to its end with the on-device sampler, and applies the best child's
+first action to the root, then searches again.  Reports mean final reward of both policies and the search rate in
+planner env-steps/s (wall time of the best_of_k calls)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "rl-environment-for-component-placement_amd"))
+import torch  # noqa: E402
+
+from pcbenv import named_config  # noqa: E402
+from pcbenv.batched_env import BatchedPlacementEnv  # noqa: E402
+from pcbenv.search import best_of_k  # noqa: E402
+
+
+def final_rewards(env, act, T):
+    """Steps every root until its first done; `act(t)` issues step t and returns (reward, done)."""
+    final = torch.zeros(env.num_envs, dtype=torch.float64, device=env.device)
+    finished = torch.zeros(env.num_envs, dtype=torch.bool, device=env.device)
+    for t in range(T):
+        r, d = act(t)
+        first = d.bool() & ~finished
+        final = torch.where(first, r, final)
+        finished |= first
+    assert bool(finished.all())
+    return final
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--roots", type=int, default=256)
+    ap.add_argument("--k", type=int, default=16)
+    ap.add_argument("--config", default="c3")
+    a = ap.parse_args()
+    cfg = named_config(a.config)
+    P, k, T = a.roots, a.k, cfg.max_num_components
+
+    def make(n, seed):
+        e = BatchedPlacementEnv(cfg, n, queue_depth=1, run_seed=seed)
+        e.generate_instances()
+        e.reset()
+        return e
+    rand_root, search_root, planner = make(P, 11), make(P, 11), make(P * k, 12)
+
+    random_final = final_rewards(rand_root, lambda t: rand_root.rollout_step(t)[1:3], T)
+    torch.cuda.synchronize()
+    spent, planner_steps = 0.0, 0
+
+    def search_step(t):
+        nonlocal spent, planner_steps
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = best_of_k(search_root, planner, k, step_index=1000 + t * T)
+        torch.cuda.synchronize()
+        spent += time.perf_counter() - t0
+        planner_steps += P * k * T
+        _, r, d, _ = search_root.step(res.actions[0])
+        return r, d
+    search_final = final_rewards(search_root, search_step, T)
+    out = {"config": a.config, "roots": P, "k": k,
+           "random_policy_mean_final_reward": float(random_final.mean()),
+           "best_of_k_mean_final_reward": float(search_final.mean()),
+           "search_env_steps_per_sec": round(planner_steps / spent), "search_seconds": round(spent, 3)}
+    print(json.dumps(out), flush=True)
+    for e in (rand_root, search_root, planner):
+        e.close()
+
+
+if __name__ == "__main__":
+    main()
