@@ -25,6 +25,11 @@
  *   pcbenv_sample_actions, pcbenv_step_sampled
  *                          the uniform-random valid-action policy and its simulate() loop body
  *                            agent/random/random_policy_square.py:11-23 (and siblings)
+ *   pcbenv_sample_logits   the masked Categorical of every reference model: the logits masked with
+ *                          `logits += max(log(action_mask), float32.min)`
+ *                            agent/models/square_model.py:137-139, rectangle_pin_spatial_model.py:268-270 (and siblings)
+ *                          and RLlib's Categorical sample / deterministic_sample / logp / entropy
+ *                            utils/agent/factorized_action_distributions.py:21-91
  *   pcbenv_gather          no counterpart: the closest is copy.deepcopy(env) of a reference env object, which a
  *                          caller uses to fork an episode (lookahead, beam search, population resampling)
  *
@@ -303,6 +308,37 @@ int pcbenv_set_state(pcbenv *env, const void *host_src, void *stream);
  * queue cursor, the episode count, the queue and the on-device generator's state.  The next reset of i takes i's own
  * next instance, as it would have without the gather. */
 int pcbenv_gather(pcbenv *dst, const pcbenv *src, const int32_t *src_index_dev, uint32_t *errors_dev, void *stream);
+
+/* Masked categorical draw from a policy's logits, on the device, one kernel launch on `stream`.
+ * logits_dev: C-contiguous [num_envs, A], A = O*H*W (square: H*W), in the flat action order of PCBENV_ACTION_FLAT
+ * (a = o*H*W + x*W + y: what a Dense(action_space.n) head emits), float32 or bf16, aligned to its element size.
+ * L_e, the legal set of environment e, is what action_mask shows, read from the bit rows of the current state set (as
+ * pcbenv_sample_actions reads them; pin kinds: orientations 2 and 3 use mask planes 0 and 1).  An illegal logit is never
+ * read: it may hold anything (NaN, or the already-masked logit + float32.min), so masked and unmasked logits give
+ * identical results.  With M = max over L_e of l_i, w_i = exp(l_i - M), Z = sum over L_e of w_i, p_i = w_i / Z on L_e:
+ *   PCBENV_DRAW_SAMPLE  u = hi32(rnd) / 2^32, rnd = mix64(mix64(seed ^ GOLDEN*(genv+1)) + step_index) -- the value
+ *                       pcbenv_sample_actions uses, genv = first_env_index + e -- and the action is the first legal i in
+ *                       flat order whose prefix sum C_i = sum over legal j <= i of w_j exceeds u*Z (up to float32
+ *                       rounding of the partial sums, never an illegal action; the threshold and the sums across
+ *                       segments of 64 columns are float64).  Constant logits draw bit for bit what pcbenv_sample_actions
+ *                       draws.
+ *   PCBENV_DRAW_GREEDY  argmax of l_i over L_e, the lowest flat index on ties (deterministic_sample; torch.argmax of the
+ *                       masked logits).
+ * In both modes log_prob[e] = l_a - M - log Z and entropy[e] = log Z - sum over L_e of p_i (l_i - M) (float32; the
+ * reference's formula, factorized_action_distributions.py:49-59).  log_prob_dev, entropy_dev, errors_dev may be NULL.
+ * No legal action: action 0, log_prob = entropy = 0 (data, not an error).  A legal logit that is NaN or +inf (bit 0 of
+ * *errors_dev), or every legal logit -inf (bit 1): the draw is the uniform one of pcbenv_sample_actions,
+ * log_prob = -log n, entropy = log n (n legal flat actions), and the bit is ORed into *errors_dev.
+ * Writes nothing the library owns (state blocks, the fused sampler's presampled action, terminal list, queue): a later
+ * pcbenv_step* behaves exactly as without the call.  PCBENV_EINVAL (checked before any device call): null handle, logits
+ * or actions, unknown dtype, mode or format, misaligned logits.  PCBENV_ESTATE: buffers not bound, or `stream` is being
+ * captured into a hipGraph (as pcbenv_gather). */
+enum pcbenv_logits_dtype { PCBENV_LOGITS_F32 = 0, PCBENV_LOGITS_BF16 = 1 };
+enum pcbenv_draw_mode { PCBENV_DRAW_SAMPLE = 0, PCBENV_DRAW_GREEDY = 1 };
+int pcbenv_sample_logits(pcbenv *env, const void *logits_dev, int32_t logits_dtype, int32_t mode,
+                         int32_t *actions_dev, int32_t action_format, float *log_prob_dev, float *entropy_dev,
+                         uint32_t *errors_dev, uint64_t seed, uint64_t first_env_index, uint64_t step_index,
+                         void *stream);
 
 /* Bit-packed legal-action mask of the current component, library-owned device
  * memory: uint64 [B, 2, H, ceil(W/64)] (orientation 0/1; pin kinds: 2 = 0, 3 = 1;

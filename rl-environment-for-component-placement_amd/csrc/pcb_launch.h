@@ -27,6 +27,18 @@ struct GatherArgs {
 };
 struct GatherLaunch { DevParams d; GatherArgs g; int threads; hipStream_t stream; };
 
+// pcbenv_sample_logits (pcb_policy.hip): d is the handle's parameter block with d.state = the current state set
+struct SampleLogitsArgs {
+    const void *logits;  // [B, O*H*W], float32 or bf16
+    int *actions;
+    float *log_prob, *entropy;  // may be null
+    unsigned *errors;           // may be null
+    u64 seed, first_env, step_index;
+    int fmt, greedy;
+};
+struct SampleLogitsLaunch { DevParams d; SampleLogitsArgs g; int dtype; hipStream_t stream; };
+int pcb_launch_sample_logits(const SampleLogitsLaunch &a);
+
 #define PCB_DECLARE_KIND(name) int pcb_launch_step_##name(const StepLaunch &a); int pcb_launch_reset_##name(const ResetLaunch &a); \
     int pcb_launch_gather_##name(const GatherLaunch &a);
 PCB_DECLARE_KIND(square) PCB_DECLARE_KIND(rect) PCB_DECLARE_KIND(pin) PCB_DECLARE_KIND(spatial)

@@ -1,0 +1,283 @@
+// pcb_policy.hip -- k_sample_logits: a policy's masked categorical draw from its logits (pcbenv_sample_logits).
+// Part of libpcbenv.so (CDNA4 / gfx950 only); a translation unit of its own, so that nothing here can change the
+// builds of k_step / k_reset / k_gather / k_sample.
+//
+// The reference's models mask their logits (`logits += max(log(action_mask), float32.min)`,
+// agent/models/square_model.py:137-139) and hand them to RLlib's Categorical
+// (utils/agent/factorized_action_distributions.py:21-91): sample / deterministic_sample, logp, entropy.  Here the legal
+// set is read from the state block's bit rows instead of the uint8 action_mask, and a logit is read only where its
+// action is legal: a 16-byte chunk with no legal bit issues no load, so the cache lines of an occupied board are never
+// fetched.
+//
+// One workgroup per environment (xcd_contiguous_env: each XCD streams a contiguous share of the logits), four
+// wavefronts when A = O*H*W >= 4096, otherwise one.
+//   segment   (o, x, 64-column word w): the up to 64 logits one mask word governs, flat [(o*H + x)*W + 64 w, + len).
+//             There are O*H*WW of them (c3 256, c5 1024).
+//   pass 1    a 16-lane DPP row per segment, 4 logits per lane, U segments' loads in flight per lane before the first
+//             use; per segment (m = max, s = sum exp(l - m), t = sum exp(l - m) (l - m), first index of the max) -> LDS.
+//   pick      wavefront 0 combines the segments in float64 (M, Z, the prefix, sum p (l - M)), finds the segment J that
+//             holds u*Z, re-reads J (<= 256 bytes, just fetched) and selects the element; one lane writes the results.
+// Weights are exp2((l - m) * log2 e) in float32, computed by one function in both passes, so the re-read of J sees
+// exactly the weights its sum was made of.
+#include <hip/hip_runtime.h>
+#include <limits.h>
+
+#include "pcbenv.h"
+#include "pcb_kernels.h"
+#include "pcb_launch.h"
+
+namespace {
+
+constexpr float LOG2E = 1.44269504088896340736f;
+constexpr int SEG_LANES = 16;  // lanes per segment in pass 1: one DPP row, 4 logits each
+// Segments per lane whose loads are issued before the first is used, and the smallest A launched with four wavefronts.
+// (-D overrides for A/B builds only: c3 x 4096 fp32 measured 67 us with 4 / four wavefronts -- 60 VGPRs, 8 waves per
+// SIMD -- against 79 us with 8 (103 VGPRs, 4 waves per SIMD) and 77 us with one wavefront per environment;
+// profiles/sample_logits_ab.txt.)
+#ifndef PCB_SL_UNROLL
+#define PCB_SL_UNROLL 4
+#endif
+#ifndef PCB_SL_NW4_MIN_A
+#define PCB_SL_NW4_MIN_A 4096
+#endif
+constexpr int UNROLL = PCB_SL_UNROLL;
+
+typedef unsigned short bf16_bits;
+__device__ inline float to_f32(float v) { return v; }
+__device__ inline float to_f32(bf16_bits v) { return __uint_as_float((unsigned)v << 16); }
+
+// four consecutive logits from a 16-byte (float) / 8-byte (bf16) aligned address
+__device__ inline void load4(const float *p, float v[4]) {
+    const float4 q = *(const float4 *)p;
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+}
+__device__ inline void load4(const bf16_bits *p, float v[4]) {
+    const uint2 q = *(const uint2 *)p;
+    v[0] = __uint_as_float(q.x << 16); v[1] = __uint_as_float(q.x & 0xFFFF0000u);
+    v[2] = __uint_as_float(q.y << 16); v[3] = __uint_as_float(q.y & 0xFFFF0000u);
+}
+
+// weight of a legal logit relative to its segment's maximum (the one place it is computed)
+__device__ inline float seg_weight(float l, float m) { return exp2f((l - m) * LOG2E); }
+
+// all-reduce over the 16 lanes of a DPP row (row_ror 8, 4, 2, 1); every lane must be active
+template <int CTRL> __device__ inline float dpp_f(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false)); }
+template <int CTRL> __device__ inline int dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, false); }
+__device__ inline float row_max(float v) {
+    v = fmaxf(v, dpp_f<0x128>(v)); v = fmaxf(v, dpp_f<0x124>(v)); v = fmaxf(v, dpp_f<0x122>(v)); v = fmaxf(v, dpp_f<0x121>(v));
+    return v;
+}
+__device__ inline float row_sum(float v) {
+    v += dpp_f<0x128>(v); v += dpp_f<0x124>(v); v += dpp_f<0x122>(v); v += dpp_f<0x121>(v);
+    return v;
+}
+__device__ inline int row_min(int v) {
+    v = min(v, dpp_i<0x128>(v)); v = min(v, dpp_i<0x124>(v)); v = min(v, dpp_i<0x122>(v)); v = min(v, dpp_i<0x121>(v));
+    return v;
+}
+__device__ inline float wave_max(float v) { for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o)); return v; }
+__device__ inline int wave_min(int v) { for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o)); return v; }
+__device__ inline double wave_sum(double v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o); return v; }
+template <typename V> __device__ inline V wave_scan(V v, int lane) {  // inclusive, in lane order
+    for (int d = 1; d < WAVE; d <<= 1) { const V t = __shfl_up(v, d); if (lane >= d) v += t; }
+    return v;
+}
+
+__host__ __device__ inline int seg_slot(int j) { return j + (j >> 4); }  // one pad word per 16: wave 0 reads runs of 16
+__host__ __device__ inline int seg_pad(int S) { return seg_slot(S) + 1; }
+__host__ __device__ inline size_t lds_bytes(int H, int WW, int S) { return (size_t)16 * H * WW + (size_t)16 * seg_pad(S) + 16; }
+
+// segment j -> first flat index, valid columns and its mask word (bit y - 64 w of word = column y legal)
+struct Seg { int a0, len, o, x, w; };
+__device__ inline Seg segment(int j, int H, int W, int WW) {
+    Seg g;
+    g.w = WW == 1 ? 0 : (j & 1);
+    const int ox = WW == 1 ? j : j >> 1;
+    g.o = (ox >= H) + (ox >= 2 * H) + (ox >= 3 * H);  // O <= 4: no integer division
+    g.x = ox - g.o * H;
+    g.len = min(64, W - 64 * g.w);
+    g.a0 = ox * W + 64 * g.w;
+    return g;
+}
+__device__ inline u64 seg_word(const u64 *vm, const Seg &g, int H, int WW) { return vm[(g.o & 1) * H * WW + g.x * WW + g.w]; }
+
+// VEC: W % 4 == 0 and the logits 4-element aligned (every chunk of 4 is one vector load); otherwise one load per legal logit
+template <typename T, bool VEC, int NW>
+__global__ __launch_bounds__(64 * NW) void k_sample_logits(DevParams p, SampleLogitsArgs g) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int e = xcd_contiguous_env((int)blockIdx.x, 0, p.B), tid = threadIdx.x, lane = tid & (WAVE - 1);
+    const int H = p.H, W = p.W, WW = p.WW, HW = H * W, S = p.O * H * WW;
+    const int nwords = (p.kind == PCBENV_SQUARE ? 1 : 2) * H * WW;
+    const u64 *vm = (const u64 *)(p.state + (size_t)e * p.stateStride + p.offVm);
+    u64 *vml = (u64 *)smem;  // the bit rows, [planes][H][WW]
+    const int pad = seg_pad(S);
+    float *sm_m = (float *)(vml + 2 * H * WW), *sm_s = sm_m + pad, *sm_t = sm_s + pad;
+    int *sm_i = (int *)(sm_t + pad), *bad_flag = sm_i + pad;
+    for (int i = tid; i < nwords; i += 64 * NW) vml[i] = vm[i];
+    if (tid == 0) *bad_flag = 0;
+    __syncthreads();
+
+    const T *row = (const T *)g.logits + (size_t)e * (size_t)(p.O * HW);
+    const int sub = lane & (SEG_LANES - 1), grp = tid >> 4;  // grp: this row's segment within a round
+    constexpr int G = 64 * NW / SEG_LANES;                       // segments per round
+    const bool greedy = g.greedy != 0;
+    bool bad = false;
+    for (int s0 = 0; s0 < S; s0 += G * UNROLL) {
+        float v[UNROLL][4];
+        unsigned nib[UNROLL];
+        int a0[UNROLL];
+        #pragma unroll
+        for (int u = 0; u < UNROLL; u++) {
+            const int j = s0 + u * G + grp;
+            nib[u] = 0u; a0[u] = 0;
+            if (j < S) {
+                const Seg sg = segment(j, H, W, WW);
+                const int rem = sg.len - 4 * sub;
+                const unsigned word4 = (unsigned)(seg_word(vml, sg, H, WW) >> (4 * sub)) & 15u;
+                nib[u] = rem <= 0 ? 0u : rem >= 4 ? word4 : word4 & ((1u << rem) - 1u);
+                a0[u] = sg.a0 + 4 * sub;
+            }
+            if (VEC) {
+                if (nib[u]) load4(row + a0[u], v[u]);
+            } else {
+                #pragma unroll
+                for (int i = 0; i < 4; i++)
+                    if ((nib[u] >> i) & 1u) v[u][i] = to_f32(row[a0[u] + i]);
+            }
+        }
+        #pragma unroll
+        for (int u = 0; u < UNROLL; u++) {
+            float lm = -INFINITY;
+            #pragma unroll
+            for (int i = 0; i < 4; i++)
+                if ((nib[u] >> i) & 1u) { bad |= !(v[u][i] < INFINITY); lm = fmaxf(lm, v[u][i]); }
+            const float m = row_max(lm);
+            float sw = 0.f, st = 0.f;
+            int first = INT_MAX;
+            if (m > -INFINITY) {
+                #pragma unroll
+                for (int i = 3; i >= 0; i--) {
+                    const float l = v[u][i];
+                    if (((nib[u] >> i) & 1u) && l > -INFINITY) {
+                        const float d = l - m, w = seg_weight(l, m);
+                        sw += w; st += w * d;
+                        if (l == m) first = a0[u] + i;
+                    }
+                }
+            }
+            sw = row_sum(sw); st = row_sum(st);
+            if (greedy) first = row_min(first);
+            const int j = s0 + u * G + grp;
+            if (sub == 0 && j < S) { const int k = seg_slot(j); sm_m[k] = m; sm_s[k] = sw; sm_t[k] = st; sm_i[k] = first; }
+        }
+    }
+    if (bad) *bad_flag = 1;
+    __syncthreads();
+    if (tid >= WAVE) return;
+
+    // ---- wavefront 0: the legal count, M, Z, the pick, the outputs
+    int cnt = 0;
+    for (int i = lane; i < nwords; i += WAVE) cnt += __popcll(vml[i]);
+    const int total = __builtin_amdgcn_readlane(wave_inclusive_scan(cnt, lane), WAVE - 1);
+    const bool mirrored = p.kind == PCBENV_PIN || p.kind == PCBENV_SPATIAL;  // orientations 2, 3 reuse planes 0, 1
+    const int n = mirrored ? 2 * total : total;
+    const int per = (S + WAVE - 1) / WAVE, j0 = min(lane * per, S), j1 = min(j0 + per, S);
+    float lm = -INFINITY;
+    for (int j = j0; j < j1; j++) lm = fmaxf(lm, sm_m[seg_slot(j)]);
+    const float M = wave_max(lm);
+    const unsigned bits = n == 0 ? 0u : *bad_flag ? 1u : M == -INFINITY ? 2u : 0u;
+    int a = 0;
+    double logp = 0.0, ent = 0.0;
+    if (n > 0 && bits) {
+        // not a distribution: exactly the uniform draw of pcbenv_sample_actions
+        int o, x, y;
+        Team<64>::sample_action(vm, p, (int)g.first_env + e, lane, g.seed, g.step_index, &o, &x, &y);
+        a = o * HW + x * W + y;
+        logp = -log((double)n); ent = log((double)n);
+    } else if (n > 0) {
+        double mine = 0.0, tl = 0.0;
+        for (int j = j0; j < j1; j++) {
+            const int k = seg_slot(j);
+            const float s = sm_s[k];
+            if (s > 0.f) {
+                const float m = sm_m[k], sc = seg_weight(m, M);
+                mine += (double)s * (double)sc;
+                tl += (double)sc * ((double)sm_t[k] + (double)s * ((double)m - (double)M));
+            }
+        }
+        const double incl = wave_scan(mine, lane), Z = __shfl(incl, WAVE - 1);
+        double excl = __shfl_up(incl, 1);
+        if (lane == 0) excl = 0.0;
+        const double tsum = wave_sum(tl), logZ = log(Z);
+        ent = logZ - tsum / Z;
+        if (greedy) {
+            int cand = INT_MAX;
+            for (int j = j0; j < j1; j++)
+                if (sm_m[seg_slot(j)] == M) { cand = sm_i[seg_slot(j)]; break; }
+            a = wave_min(cand);
+            logp = -logZ;
+        } else {
+            const u64 rnd = Team<64>::mix64(Team<64>::mix64(g.seed ^ 0x9E3779B97F4A7C15ull * ((u64)((int)g.first_env + e) + 1)) + g.step_index);
+            const double uz = (double)(unsigned)(rnd >> 32) * 0x1p-32 * Z;
+            // the lane whose run of segments holds u*Z (rounding can leave none: then the last lane with weight)
+            const u64 owners = __ballot(mine > 0.0 && excl <= uz && uz < incl);
+            const int ol = owners ? __ffsll((long long)owners) - 1 : 63 - __clzll((long long)__ballot(mine > 0.0));
+            int J = -1;
+            double rloc = 0.0;
+            if (lane == ol) {
+                double acc = excl;
+                for (int j = j0; j < j1; j++) {
+                    const int k = seg_slot(j);
+                    const float s = sm_s[k];
+                    if (s > 0.f) {
+                        const float sc = seg_weight(sm_m[k], M);
+                        const double sj = (double)s * (double)sc;
+                        J = j; rloc = (uz - acc) / (double)sc;  // threshold in units of the segment's own weights
+                        if (acc + sj > uz) break;
+                        acc += sj;
+                    }
+                }
+            }
+            J = __shfl(J, ol); rloc = __shfl(rloc, ol);
+            // re-read segment J: lane k holds column 64 w + k
+            const Seg sg = segment(J, H, W, WW);
+            const u64 word = seg_word(vml, sg, H, WW);
+            const bool legal = lane < sg.len && ((word >> lane) & 1ull);
+            const float l = legal ? to_f32(row[sg.a0 + lane]) : -INFINITY;
+            const float w = legal && l > -INFINITY ? seg_weight(l, sm_m[seg_slot(J)]) : 0.f;
+            const float c = wave_scan(w, lane);
+            const u64 hit = __ballot(w > 0.f && (double)c > rloc);
+            // rounding can leave no element above the threshold: the segment's last legal element with weight
+            const int k = hit ? __ffsll((long long)hit) - 1 : 63 - __clzll((long long)__ballot(w > 0.f));
+            a = sg.a0 + k;
+            logp = (double)__shfl(l, k) - (double)M - logZ;
+        }
+    }
+    if (lane == 0) {
+        const int o = a / HW, x = (a - o * HW) / W, y = a - o * HW - x * W;
+        if (g.fmt == PCBENV_ACTION_FLAT) g.actions[e] = a;
+        else { g.actions[3 * e] = o; g.actions[3 * e + 1] = x; g.actions[3 * e + 2] = y; }
+        if (g.log_prob) g.log_prob[e] = (float)logp;
+        if (g.entropy) g.entropy[e] = (float)ent;
+        if (bits && g.errors) atomicOr(g.errors, bits);
+    }
+}
+
+template <typename T, bool VEC>
+void launch(const SampleLogitsLaunch &a, size_t lds) {
+    const DevParams &d = a.d;
+    if (d.O * d.H * d.W >= PCB_SL_NW4_MIN_A) hipLaunchKernelGGL((k_sample_logits<T, VEC, 4>), dim3(d.B), dim3(256), lds, a.stream, d, a.g);
+    else hipLaunchKernelGGL((k_sample_logits<T, VEC, 1>), dim3(d.B), dim3(64), lds, a.stream, d, a.g);
+}
+
+}  // namespace
+
+int pcb_launch_sample_logits(const SampleLogitsLaunch &a) {
+    const DevParams &d = a.d;
+    const size_t lds = lds_bytes(d.H, d.WW, d.O * d.H * d.WW);
+    const bool f32 = a.dtype == PCBENV_LOGITS_F32;
+    const bool vec = d.W % 4 == 0 && (uintptr_t)a.g.logits % (f32 ? 16 : 8) == 0;
+    if (f32) { if (vec) launch<float, true>(a, lds); else launch<float, false>(a, lds); }
+    else { if (vec) launch<bf16_bits, true>(a, lds); else launch<bf16_bits, false>(a, lds); }
+    return 0;
+}

@@ -3,8 +3,8 @@
 // One environment per workgroup: one wavefront (64 lanes) up to 64x64 cells, four wavefronts for the 128x128
 // spatial configuration (template parameter NW).  Kernels: k_reset, k_step (transition + legal mask +
 // observations + terminal routing reward + optional in-launch reset and action sampling), k_sample,
-// k_cursor_range.  The occupancy grid lives bit-packed (one row = WW 64-bit words) in a compact
-// per-environment state block in HBM that is staged through LDS; the legal
+// k_cursor_range, and k_sample_logits in pcb_policy.hip.  The occupancy grid lives bit-packed (one row = WW 64-bit
+// words) in a compact per-environment state block in HBM that is staged through LDS; the legal
 // placement mask is OR-folds of row words (horizontal: shifts; vertical: LDS
 // neighbours); the observation tensors the policy consumes (uint8 cells) are a
 // pure coalesced 16-byte-per-lane write stream, which is what bounds the kernel.
@@ -879,6 +879,41 @@ extern "C" int pcbenv_gather(pcbenv *dst, const pcbenv *src, const int32_t *src_
     HIP_TRY(dst, hipGetLastError());
     dst->state_cur ^= 1;
     dst->dp.state = dst->dp.state_out = dst->state_buf[dst->state_cur];
+    return PCBENV_OK;
+}
+
+// ---- pcbenv_sample_logits ------------------------------------------------------------------------------------
+// The argument checks come before anything touches a device (a null handle included), so that every one of them can be
+// exercised without a GPU.  Nothing the library owns is written: no state block, presampled action, terminal list or
+// queue, and no generator interaction (nothing is consumed).
+extern "C" int pcbenv_sample_logits(pcbenv *env, const void *logits_dev, int32_t logits_dtype, int32_t mode,
+                                    int32_t *actions_dev, int32_t fmt, float *log_prob_dev, float *entropy_dev,
+                                    uint32_t *errors_dev, uint64_t seed, uint64_t first_env_index, uint64_t step_index,
+                                    void *stream) {
+    if (!logits_dev) return fail(env, PCBENV_EINVAL, "null logits");
+    if (!actions_dev) return fail(env, PCBENV_EINVAL, "null actions");
+    if (logits_dtype != PCBENV_LOGITS_F32 && logits_dtype != PCBENV_LOGITS_BF16) return fail(env, PCBENV_EINVAL, "unknown logits dtype");
+    if (mode != PCBENV_DRAW_SAMPLE && mode != PCBENV_DRAW_GREEDY) return fail(env, PCBENV_EINVAL, "unknown draw mode");
+    if (fmt != PCBENV_ACTION_TUPLE && fmt != PCBENV_ACTION_FLAT) return fail(env, PCBENV_EINVAL, "unknown action format");
+    if ((uintptr_t)logits_dev % (logits_dtype == PCBENV_LOGITS_F32 ? 4 : 2) != 0)
+        return fail(env, PCBENV_EINVAL, "logits pointer not aligned to its element size");
+    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
+    if (!env->bound) return fail(env, PCBENV_ESTATE, "pcbenv_bind_buffers has not been called");
+    DEVICE_GUARD(env);
+    hipStream_t s = (hipStream_t)stream;
+    // A captured launch would keep reading the state set that was current at capture time (as pcbenv_gather).
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+        return fail(env, PCBENV_ESTATE, "pcbenv_sample_logits cannot be captured into a graph");
+    SampleLogitsLaunch a;
+    a.d = env->dp;  // d.state: the current state set, as k_sample reads it
+    a.dtype = logits_dtype; a.stream = s;
+    SampleLogitsArgs &g = a.g;
+    g.logits = logits_dev; g.actions = actions_dev; g.log_prob = log_prob_dev; g.entropy = entropy_dev;
+    g.errors = (unsigned *)errors_dev; g.seed = (u64)seed; g.first_env = (u64)first_env_index; g.step_index = (u64)step_index;
+    g.fmt = fmt; g.greedy = mode == PCBENV_DRAW_GREEDY;
+    pcb_launch_sample_logits(a);
+    HIP_TRY(env, hipGetLastError());
     return PCBENV_OK;
 }
 

@@ -347,6 +347,45 @@ class BatchedPlacementEnv:
             self.first_env_index, int(step_index), self._stream()), self._h)
         return out
 
+    def sample_logits(self, logits: torch.Tensor, step_index: int, greedy: bool = False, flat: bool = False,
+                      out: Optional[torch.Tensor] = None, check: bool = False):
+        """A policy's masked categorical draw on the device (`pcbenv_sample_logits`, one kernel launch): the reference
+        models' `logits += max(log(action_mask), float32.min)` followed by RLlib's Categorical `sample()` (or
+        `deterministic_sample()` with greedy=True), `logp` and `entropy`.  logits: float32 or bfloat16 `[B, A]` or
+        `[B, O, H, W]` (A = O*H*W in the flat action order), C-contiguous, on `self.device`; illegal entries are never
+        read (raw or already-masked logits give identical results).  The legal set is the current `action_mask`.  The
+        draw uses `run_seed` and `first_env_index` as `sample_actions` does; constant logits draw exactly what
+        `sample_actions(step_index)` draws.  Returns (actions int32 [B, 3] or [B] (flat), log_prob float32 [B],
+        entropy float32 [B]).  check=True synchronises and raises if a legal logit was NaN / +inf or every legal logit
+        -inf (those environments then took the uniform draw)."""
+        B, A = self.num_envs, self.cfg.num_orientations * self.cfg.height * self.cfg.width
+        if not isinstance(logits, torch.Tensor) or logits.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("logits must be a float32 or bfloat16 tensor")
+        if logits.device != self.device and not (logits.device.type == "cuda" and self.device.index is None
+                                                 and logits.device.index == torch.cuda.current_device()):
+            raise ValueError(f"logits must be on {self.device}, got {logits.device}")
+        shapes = ((B, A), (B, self.cfg.num_orientations, self.cfg.height, self.cfg.width))
+        if tuple(logits.shape) not in shapes:
+            raise ValueError(f"logits must have shape {list(shapes[0])} or {list(shapes[1])}, got {list(logits.shape)}")
+        if not logits.is_contiguous():
+            raise ValueError("logits must be C-contiguous (no copy is made)")
+        if out is None:
+            out = torch.empty((B,) if flat else (B, 3), dtype=torch.int32, device=self.device)
+        log_prob = torch.empty(B, dtype=torch.float32, device=self.device)
+        entropy = torch.empty(B, dtype=torch.float32, device=self.device)
+        err = torch.zeros(1, dtype=torch.int32, device=self.device) if check else None
+        _lib.check(self._L.pcbenv_sample_logits(
+            self._h, logits.data_ptr(), _lib.LOGITS_F32 if logits.dtype == torch.float32 else _lib.LOGITS_BF16,
+            _lib.DRAW_GREEDY if greedy else _lib.DRAW_SAMPLE, out.data_ptr(), _lib.ACTION_FLAT if flat else _lib.ACTION_TUPLE,
+            log_prob.data_ptr(), entropy.data_ptr(), None if err is None else err.data_ptr(), self.run_seed,
+            self.first_env_index, int(step_index), self._stream()), self._h)
+        if check:
+            bits = int(err.item())
+            if bits:
+                raise FloatingPointError(f"sample_logits: error bits {bits:#x} (1: a legal logit was NaN or +inf, 2: every "
+                                         "legal logit was -inf); those environments took the uniform draw")
+        return out, log_prob, entropy
+
     def rollout_step(self, step_index: int, flat: bool = False, out: Optional[torch.Tensor] = None):
         """`sample_actions` + `step` in one kernel launch (the body of the reference's random-policy
         `simulate()` loop, agent/random/random_policy_square.py:38-56); `out` receives the actions taken."""

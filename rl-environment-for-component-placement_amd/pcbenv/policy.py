@@ -130,10 +130,13 @@ class SpatialPolicy(nn.Module):
         enc = torch.cat([g.flatten(1), p.flatten(1), comp.flatten(1)], dim=1)
         return enc, {"processed_grid": g, "processed_pin_grid": p, "components_encodings": comp_in, "component_attn_output": comp}
 
-    def forward(self, obs):
-        """obs: the BatchedPlacementEnv observation dict (device tensors) -> (masked logits [B, O*H*W], value [B])."""
+    def forward(self, obs, mask: bool = True):
+        """obs: the BatchedPlacementEnv observation dict (device tensors) -> (masked logits [B, O*H*W], value [B]).
+        mask=False returns the raw logits, for `BatchedPlacementEnv.sample_logits`, which reads only the legal ones."""
         enc, _ = self.encode(obs)
         logits = self.logits(enc)
+        if not mask:
+            return logits, self.value(enc).squeeze(-1)
         mask = obs["action_mask"].reshape(enc.shape[0], -1).float()
         logits = logits + torch.clamp(torch.log(mask), min=torch.finfo(torch.float32).min)
         return logits, self.value(enc).squeeze(-1)

@@ -30,6 +30,10 @@ class PPOConfig:
     ent_coef: float = 0.01
     lr: float = 3e-4
     adv_mode: str = "all_gather"
+    # collect() draws with env.sample_logits (the masked categorical in one kernel launch, logp from the kernel) instead of
+    # torch's Categorical; update() keeps torch's masked Categorical (it needs gradients).  Off by default: the torch path
+    # keeps existing runs' random stream.
+    device_sampler: bool = False
 
 
 def _allreduce_grads(model):
@@ -49,6 +53,7 @@ class PPOTrainer:
         # byte is copied.  (With fewer slots every observation is copied once per step, as in round 1.)
         self.in_place = getattr(env, "num_slots", 1) >= cfg.rollout_steps + 1
         self.timing = {"collect_s": 0.0, "update_s": 0.0, "env_steps": 0}
+        self.draws = 0  # step index of the device sampler's next draw: every collect() draws differently
 
     @torch.no_grad()
     def collect(self) -> Dict[str, torch.Tensor]:
@@ -73,10 +78,16 @@ class PPOTrainer:
             if not self.in_place:
                 for k in self.obs_keys:
                     buf[k][t].copy_(obs[k])
-            logits, v = self.policy(obs)
-            d = torch.distributions.Categorical(logits=logits)
-            a = d.sample()
-            act[t], logp[t], val[t] = a, d.log_prob(a), v
+            if self.cfg.device_sampler:
+                logits, v = self.policy(obs, mask=False)
+                a, lp, _ = env.sample_logits(logits.contiguous(), self.draws, flat=True)
+                self.draws += 1
+                act[t], logp[t], val[t] = a, lp, v
+            else:
+                logits, v = self.policy(obs)
+                d = torch.distributions.Categorical(logits=logits)
+                a = d.sample()
+                act[t], logp[t], val[t] = a, d.log_prob(a), v
             if self.in_place:
                 env.select_slot(t + 1)
             env.step(a.to(torch.int32))

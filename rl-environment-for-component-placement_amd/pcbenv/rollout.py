@@ -4,7 +4,9 @@
 Trajectories stay on the device as `[T, B, ...]` tensors.  With `policy=None` every step is ONE kernel launch
 (`pcbenv_step_sampled`: uniform draw over the legal actions + transition, plus the in-launch reset when the
 environment was created with `auto_reset=True`); with a policy callable the action comes from
-`policy(obs) -> int tensor [B] (flat) or [B, 3]`.
+`policy(obs) -> int tensor [B] (flat) or [B, 3]`; with a logits callable (`logits_policy(obs) -> [B, O*H*W]` float32 /
+bfloat16 logits, raw or masked) the draw is `env.sample_logits` (`pcbenv_sample_logits`: the masked categorical on the
+device), and the trajectory also keeps each draw's log-probability and the entropy of its distribution.
 """
 from __future__ import annotations
 
@@ -21,6 +23,8 @@ class Trajectory:
     dones: torch.Tensor        # [T, B] uint8
     info: Optional[torch.Tensor]  # [T, B, 2] float64 (wirelength, num_intersections; NaN when absent) or None
     obs: Dict[str, torch.Tensor]  # requested observation keys, [T, B, ...] (observation BEFORE the step)
+    log_prob: Optional[torch.Tensor] = None  # [T, B] float32, collect(logits_policy=...) only
+    entropy: Optional[torch.Tensor] = None   # [T, B] float32, collect(logits_policy=...) only
 
     def episode_returns(self):
         """List of per-environment lists of completed-episode returns (sum of rewards up to each done)."""
@@ -38,9 +42,16 @@ class Trajectory:
 
 
 def collect(env, num_steps: int, policy: Optional[Callable] = None, t0: int = 0,
-            store_obs: Sequence[str] = ()) -> Trajectory:
+            store_obs: Sequence[str] = (), logits_policy: Optional[Callable] = None, greedy: bool = False) -> Trajectory:
+    """logits_policy: step t draws `env.sample_logits(logits_policy(obs), t0 + t, greedy)`; not together with policy."""
+    if policy is not None and logits_policy is not None:
+        raise ValueError("collect: pass either policy or logits_policy, not both")
     B, dev = env.num_envs, env.device
     actions = torch.zeros((num_steps, B, 3), dtype=torch.int32, device=dev)
+    log_prob = entropy = None
+    if logits_policy is not None:
+        log_prob = torch.zeros((num_steps, B), dtype=torch.float32, device=dev)
+        entropy = torch.zeros((num_steps, B), dtype=torch.float32, device=dev)
     rewards = torch.zeros((num_steps, B), dtype=torch.float64, device=dev)
     dones = torch.zeros((num_steps, B), dtype=torch.uint8, device=dev)
     info = torch.zeros((num_steps, B, 2), dtype=torch.float64, device=dev) if env.info else None
@@ -49,7 +60,10 @@ def collect(env, num_steps: int, policy: Optional[Callable] = None, t0: int = 0,
     for t in range(num_steps):
         for k in store_obs:
             obs[k][t].copy_(env.obs[k])
-        if policy is None:
+        if logits_policy is not None:
+            _, log_prob[t], entropy[t] = env.sample_logits(logits_policy(env.obs), t0 + t, greedy=greedy, out=actions[t])
+            env.step(actions[t])
+        elif policy is None:
             env.rollout_step(t0 + t, out=actions[t])
         else:
             a = policy(env.obs)
@@ -68,7 +82,7 @@ def collect(env, num_steps: int, policy: Optional[Callable] = None, t0: int = 0,
             info[t].copy_(env.info_raw)
         if not env.auto_reset:
             env.reset_done()
-    return Trajectory(actions, rewards, dones, info, obs)
+    return Trajectory(actions, rewards, dones, info, obs, log_prob, entropy)
 
 
 def masked_logits(logits: torch.Tensor, action_mask: torch.Tensor) -> torch.Tensor:
