@@ -30,6 +30,10 @@
  *                            agent/models/square_model.py:137-139, rectangle_pin_spatial_model.py:268-270 (and siblings)
  *                          and RLlib's Categorical sample / deterministic_sample / logp / entropy
  *                            utils/agent/factorized_action_distributions.py:21-91
+ *   pcbenv_evaluate_logits, pcbenv_evaluate_logits_backward
+ *                          RLlib's Categorical logp / entropy of the same masked logits for stored actions, and their
+ *                          gradient with respect to the logits (what a PPO update back-propagates)
+ *                            utils/agent/factorized_action_distributions.py:21-91
  *   pcbenv_gather          no counterpart: the closest is copy.deepcopy(env) of a reference env object, which a
  *                          caller uses to fork an episode (lookahead, beam search, population resampling)
  *
@@ -339,6 +343,44 @@ int pcbenv_sample_logits(pcbenv *env, const void *logits_dev, int32_t logits_dty
                          int32_t *actions_dev, int32_t action_format, float *log_prob_dev, float *entropy_dev,
                          uint32_t *errors_dev, uint64_t seed, uint64_t first_env_index, uint64_t step_index,
                          void *stream);
+
+/* The update half of the same masked categorical: log-probability and entropy of stored actions, and their gradient
+ * with respect to the logits.  One kernel launch each on `stream`.
+ * Rows are independent and num_rows is arbitrary (a minibatch of stored steps, not the handle's num_envs).  The handle
+ * supplies the geometry (kind, O, H, W) and the device only: neither call reads or writes anything the library owns, so
+ * neither needs bound buffers.
+ * logits_dev: C-contiguous [num_rows, A] float32 or bf16 in flat action order, aligned to its element size, as for
+ * pcbenv_sample_logits.  mask_bits_dev: dense uint64 [num_rows, 2, H, ceil(W/64)], the layout pcbenv_mask_bits
+ * documents (orientation o reads plane o & 1, square reads plane 0 only; bits of columns >= W are ignored).  An illegal
+ * logit is never read: it may hold NaN or an already-masked value, so masked and unmasked logits give identical results.
+ * actions_dev: int32 [num_rows] (PCBENV_ACTION_FLAT) or [num_rows, 3] (PCBENV_ACTION_TUPLE).
+ * stats_dev: float32 [num_rows, 4] = (M, log Z, entropy, row status), 16-byte aligned; the forward call writes it and
+ * the backward call consumes it, so that backward is one pass.  It may be NULL in forward when no gradient is wanted.
+ * Forward, with L, M, w_i, Z, p_i as above: log_prob = l_a - M - log Z, entropy = log Z - sum over L of p_i (l_i - M)
+ * (a legal -inf logit contributes 0).  log_prob_dev, entropy_dev, errors_dev may be NULL.
+ * Backward writes EVERY element of grad_logits_dev [num_rows, A] in the logits' dtype (bf16: round to nearest even); the
+ * caller passes uninitialised memory.  With log p_i = l_i - M - log Z and Hrow the row's entropy:
+ *   g_i = g_lp (1[i = a] - p_i) - g_H p_i (log p_i + Hrow)   for i in L   (p_i = 0: the second term is 0, never NaN)
+ *   g_i = 0                                                   for i not in L
+ * grad_log_prob_dev (g_lp) and grad_entropy_dev (g_H) are float32 [num_rows]; either may be NULL, which means zero.
+ * Edge cases are data:
+ *   no legal action in a row         log_prob = entropy = 0, gradient row zero (what pcbenv_sample_logits reports)
+ *   a legal NaN or +inf              bit 0 of *errors_dev; log_prob = -log n, entropy = log n, gradient row zero
+ *   every legal logit -inf           bit 1; the same outputs
+ *   the stored action out of range or not legal, in a row with legal actions and neither of the two cases above
+ *                                    bit 2; log_prob = 0, the entropy as usual, the one-hot term dropped in backward
+ * The bits are ORed into *errors_dev by the forward call.
+ * PCBENV_EINVAL (checked before any device call): null handle, logits, mask bits, actions or (backward) stats or grad
+ * logits; unknown dtype or format; misaligned logits, mask bits, stats or grad logits; num_rows < 0.  num_rows == 0 is a
+ * no-op success.  Neither call is meant to be captured into a hipGraph. */
+int pcbenv_evaluate_logits(const pcbenv *env, const void *logits_dev, int32_t logits_dtype,
+                           const uint64_t *mask_bits_dev, const int32_t *actions_dev, int32_t action_format,
+                           int64_t num_rows, float *log_prob_dev, float *entropy_dev, float *stats_dev,
+                           uint32_t *errors_dev, void *stream);
+int pcbenv_evaluate_logits_backward(const pcbenv *env, const void *logits_dev, int32_t logits_dtype,
+                           const uint64_t *mask_bits_dev, const int32_t *actions_dev, int32_t action_format,
+                           int64_t num_rows, const float *stats_dev, const float *grad_log_prob_dev,
+                           const float *grad_entropy_dev, void *grad_logits_dev, void *stream);
 
 /* Bit-packed legal-action mask of the current component, library-owned device
  * memory: uint64 [B, 2, H, ceil(W/64)] (orientation 0/1; pin kinds: 2 = 0, 3 = 1;

@@ -39,6 +39,30 @@ struct SampleLogitsArgs {
 struct SampleLogitsLaunch { DevParams d; SampleLogitsArgs g; int dtype; hipStream_t stream; };
 int pcb_launch_sample_logits(const SampleLogitsLaunch &a);
 
+// pcbenv_evaluate_logits / pcbenv_evaluate_logits_backward (pcb_policy_eval.hip): the handle gives the geometry only;
+// the rows are the caller's (a minibatch of stored steps), with their own bit rows [rows, 2, H, WW]
+struct EvalGeom { int O, H, W, WW, rows; };
+struct EvalLogitsArgs {
+    const void *logits;  // [rows, O*H*W], float32 or bf16
+    const u64 *mask_bits;
+    const int *actions;
+    float *log_prob, *entropy, *stats;  // may be null; stats: [rows, 4] = (M, log Z, entropy, row status)
+    unsigned *errors;                   // may be null
+    int fmt;
+};
+struct EvalLogitsLaunch { EvalGeom q; EvalLogitsArgs g; int dtype; hipStream_t stream; };
+struct EvalLogitsBackwardArgs {
+    const void *logits;
+    const u64 *mask_bits;
+    const int *actions;
+    const float *stats, *grad_log_prob, *grad_entropy;  // the two gradients may be null (zero)
+    void *grad_logits;  // [rows, O*H*W] in the logits' dtype, written whole
+    int fmt;
+};
+struct EvalLogitsBackwardLaunch { EvalGeom q; EvalLogitsBackwardArgs g; int dtype; hipStream_t stream; };
+int pcb_launch_evaluate_logits(const EvalLogitsLaunch &a);
+int pcb_launch_evaluate_logits_backward(const EvalLogitsBackwardLaunch &a);
+
 #define PCB_DECLARE_KIND(name) int pcb_launch_step_##name(const StepLaunch &a); int pcb_launch_reset_##name(const ResetLaunch &a); \
     int pcb_launch_gather_##name(const GatherLaunch &a);
 PCB_DECLARE_KIND(square) PCB_DECLARE_KIND(rect) PCB_DECLARE_KIND(pin) PCB_DECLARE_KIND(spatial)

@@ -3,7 +3,8 @@
 // One environment per workgroup: one wavefront (64 lanes) up to 64x64 cells, four wavefronts for the 128x128
 // spatial configuration (template parameter NW).  Kernels: k_reset, k_step (transition + legal mask +
 // observations + terminal routing reward + optional in-launch reset and action sampling), k_sample,
-// k_cursor_range, and k_sample_logits in pcb_policy.hip.  The occupancy grid lives bit-packed (one row = WW 64-bit
+// k_cursor_range, k_sample_logits in pcb_policy.hip and k_evaluate_logits* in pcb_policy_eval.hip.
+// The occupancy grid lives bit-packed (one row = WW 64-bit
 // words) in a compact per-environment state block in HBM that is staged through LDS; the legal
 // placement mask is OR-folds of row words (horizontal: shifts; vertical: LDS
 // neighbours); the observation tensors the policy consumes (uint8 cells) are a
@@ -913,6 +914,73 @@ extern "C" int pcbenv_sample_logits(pcbenv *env, const void *logits_dev, int32_t
     g.errors = (unsigned *)errors_dev; g.seed = (u64)seed; g.first_env = (u64)first_env_index; g.step_index = (u64)step_index;
     g.fmt = fmt; g.greedy = mode == PCBENV_DRAW_GREEDY;
     pcb_launch_sample_logits(a);
+    HIP_TRY(env, hipGetLastError());
+    return PCBENV_OK;
+}
+
+// ---- pcbenv_evaluate_logits / pcbenv_evaluate_logits_backward ------------------------------------------------------
+// As pcbenv_sample_logits: the argument checks come before anything touches a device.  The handle gives the geometry
+// and the device; nothing the library owns is read or written, so no buffers need to be bound.
+static int evaluate_checks(pcbenv *env, const void *logits_dev, int32_t logits_dtype, const uint64_t *mask_bits_dev,
+                           const int32_t *actions_dev, int32_t fmt, int64_t num_rows) {
+    if (!logits_dev) return fail(env, PCBENV_EINVAL, "null logits");
+    if (!mask_bits_dev) return fail(env, PCBENV_EINVAL, "null mask bits");
+    if (!actions_dev) return fail(env, PCBENV_EINVAL, "null actions");
+    if (logits_dtype != PCBENV_LOGITS_F32 && logits_dtype != PCBENV_LOGITS_BF16) return fail(env, PCBENV_EINVAL, "unknown logits dtype");
+    if (fmt != PCBENV_ACTION_TUPLE && fmt != PCBENV_ACTION_FLAT) return fail(env, PCBENV_EINVAL, "unknown action format");
+    if ((uintptr_t)logits_dev % (logits_dtype == PCBENV_LOGITS_F32 ? 4 : 2) != 0)
+        return fail(env, PCBENV_EINVAL, "logits pointer not aligned to its element size");
+    if ((uintptr_t)mask_bits_dev % 8 != 0) return fail(env, PCBENV_EINVAL, "mask bits pointer not aligned to 8 bytes");
+    if (num_rows < 0 || num_rows > INT32_MAX) return fail(env, PCBENV_EINVAL, "num_rows out of range");
+    return PCBENV_OK;
+}
+static EvalGeom eval_geom(const pcbenv *env, int64_t num_rows) {
+    const DevParams &d = env->dp;
+    return EvalGeom{d.O, d.H, d.W, d.WW, (int)num_rows};
+}
+
+extern "C" int pcbenv_evaluate_logits(const pcbenv *cenv, const void *logits_dev, int32_t logits_dtype,
+                                      const uint64_t *mask_bits_dev, const int32_t *actions_dev, int32_t fmt,
+                                      int64_t num_rows, float *log_prob_dev, float *entropy_dev, float *stats_dev,
+                                      uint32_t *errors_dev, void *stream) {
+    pcbenv *env = const_cast<pcbenv *>(cenv);  // the error text only
+    const int rc = evaluate_checks(env, logits_dev, logits_dtype, mask_bits_dev, actions_dev, fmt, num_rows);
+    if (rc != PCBENV_OK) return rc;
+    if ((uintptr_t)stats_dev % 16 != 0) return fail(env, PCBENV_EINVAL, "stats pointer not aligned to 16 bytes");
+    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
+    if (num_rows == 0) return PCBENV_OK;
+    DEVICE_GUARD(env);
+    EvalLogitsLaunch a;
+    a.q = eval_geom(env, num_rows); a.dtype = logits_dtype; a.stream = (hipStream_t)stream;
+    EvalLogitsArgs &g = a.g;
+    g.logits = logits_dev; g.mask_bits = (const u64 *)mask_bits_dev; g.actions = actions_dev; g.log_prob = log_prob_dev;
+    g.entropy = entropy_dev; g.stats = stats_dev; g.errors = (unsigned *)errors_dev; g.fmt = fmt;
+    pcb_launch_evaluate_logits(a);
+    HIP_TRY(env, hipGetLastError());
+    return PCBENV_OK;
+}
+
+extern "C" int pcbenv_evaluate_logits_backward(const pcbenv *cenv, const void *logits_dev, int32_t logits_dtype,
+                                               const uint64_t *mask_bits_dev, const int32_t *actions_dev, int32_t fmt,
+                                               int64_t num_rows, const float *stats_dev, const float *grad_log_prob_dev,
+                                               const float *grad_entropy_dev, void *grad_logits_dev, void *stream) {
+    pcbenv *env = const_cast<pcbenv *>(cenv);  // the error text only
+    const int rc = evaluate_checks(env, logits_dev, logits_dtype, mask_bits_dev, actions_dev, fmt, num_rows);
+    if (rc != PCBENV_OK) return rc;
+    if (!stats_dev) return fail(env, PCBENV_EINVAL, "null stats");
+    if ((uintptr_t)stats_dev % 16 != 0) return fail(env, PCBENV_EINVAL, "stats pointer not aligned to 16 bytes");
+    if (!grad_logits_dev) return fail(env, PCBENV_EINVAL, "null grad logits");
+    if ((uintptr_t)grad_logits_dev % (logits_dtype == PCBENV_LOGITS_F32 ? 4 : 2) != 0)
+        return fail(env, PCBENV_EINVAL, "grad logits pointer not aligned to its element size");
+    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
+    if (num_rows == 0) return PCBENV_OK;
+    DEVICE_GUARD(env);
+    EvalLogitsBackwardLaunch a;
+    a.q = eval_geom(env, num_rows); a.dtype = logits_dtype; a.stream = (hipStream_t)stream;
+    EvalLogitsBackwardArgs &g = a.g;
+    g.logits = logits_dev; g.mask_bits = (const u64 *)mask_bits_dev; g.actions = actions_dev; g.stats = stats_dev;
+    g.grad_log_prob = grad_log_prob_dev; g.grad_entropy = grad_entropy_dev; g.grad_logits = grad_logits_dev; g.fmt = fmt;
+    pcb_launch_evaluate_logits_backward(a);
     HIP_TRY(env, hipGetLastError());
     return PCBENV_OK;
 }

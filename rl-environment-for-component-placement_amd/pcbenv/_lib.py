@@ -16,6 +16,8 @@ ABI_VERSION = 3
 OPT_STREAM_THRESHOLD_BYTES, OPT_TERMINAL_TEAMS, OPT_GEN_GRID, OPT_GEN_LANES = 1, 2, 3, 4
 LOGITS_F32, LOGITS_BF16 = 0, 1
 DRAW_SAMPLE, DRAW_GREEDY = 0, 1
+EVAL_ERR_NONFINITE, EVAL_ERR_ALL_NEG_INF, EVAL_ERR_ACTION = 1, 2, 4  # bits of pcbenv_evaluate_logits' *errors_dev
+EVAL_ROW_OK, EVAL_ROW_ZERO, EVAL_ROW_NO_ONE_HOT = 0, 1, 2  # row status, stats[:, 3]
 
 EXPORTS = ("pcbenv_abi_version", "pcbenv_create", "pcbenv_destroy", "pcbenv_last_error",
            "pcbenv_instance_stride", "pcbenv_max_total_pins", "pcbenv_set_option", "pcbenv_bind_buffers", "pcbenv_bind_buffers_slots", "pcbenv_bind_compact_features", "pcbenv_select_slot",
@@ -23,7 +25,7 @@ EXPORTS = ("pcbenv_abi_version", "pcbenv_create", "pcbenv_destroy", "pcbenv_last
            "pcbenv_mask_bits", "pcbenv_state_bytes", "pcbenv_get_state", "pcbenv_set_state", "pcbenv_queue_cursors",
            "pcbenv_instgen_device_enable", "pcbenv_instgen_device_status", "pcbenv_get_instances",
            "pcbenv_instgen_create", "pcbenv_instgen_destroy", "pcbenv_instgen_next", "pcbenv_instgen_next_batch",
-           "pcbenv_gather", "pcbenv_sample_logits")
+           "pcbenv_gather", "pcbenv_sample_logits", "pcbenv_evaluate_logits", "pcbenv_evaluate_logits_backward")
 
 
 class PcbenvConfig(C.Structure):
@@ -100,6 +102,10 @@ def load():
     L.pcbenv_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pcbenv_sample_logits.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.pcbenv_evaluate_logits.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pcbenv_evaluate_logits_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pcbenv_mask_bits.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.pcbenv_mask_bits.restype = C.c_void_p
     if L.pcbenv_abi_version() != ABI_VERSION:

@@ -386,6 +386,74 @@ class BatchedPlacementEnv:
                                          "legal logit was -inf); those environments took the uniform draw")
         return out, log_prob, entropy
 
+    def _check_eval_args(self, logits, mask_bits, actions):
+        """Shapes, dtypes and devices of an evaluate_logits call -> (num_rows, flat)."""
+        cfg = self.cfg
+        A, H, WW = cfg.num_orientations * cfg.height * cfg.width, cfg.height, (cfg.width + 63) // 64
+        if not isinstance(logits, torch.Tensor) or logits.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("logits must be a float32 or bfloat16 tensor")
+        if logits.dim() != 2 or logits.shape[1] != A:
+            raise ValueError(f"logits must have shape [N, {A}], got {list(logits.shape)}")
+        N = logits.shape[0]
+        if mask_bits.dtype != torch.int64 or tuple(mask_bits.shape) != (N, 2, H, WW):
+            raise ValueError(f"mask_bits must be int64 [{N}, 2, {H}, {WW}], got {mask_bits.dtype} {list(mask_bits.shape)}")
+        if actions.dtype != torch.int32 or tuple(actions.shape) not in ((N,), (N, 3)):
+            raise ValueError(f"actions must be int32 [{N}] (flat) or [{N}, 3], got {actions.dtype} {list(actions.shape)}")
+        for name, t in (("logits", logits), ("mask_bits", mask_bits), ("actions", actions)):
+            if t.device.type != self.device.type or (self.device.index is not None and t.device.index != self.device.index):
+                raise ValueError(f"{name} must be on {self.device}, got {t.device}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be C-contiguous (no copy is made)")
+        return N, actions.dim() == 1
+
+    def evaluate_logits_forward(self, logits, mask_bits, actions, stats: Optional[torch.Tensor] = None,
+                                errors: Optional[torch.Tensor] = None):
+        """`pcbenv_evaluate_logits`, one kernel launch: (log_prob, entropy) float32 [N] of the stored `actions` under the
+        masked categorical of `logits` [N, A] with the legal sets `mask_bits` [N, 2, H, WW] (what `mask_bits()` returned
+        when the rows were stored).  stats: float32 [N, 4] the backward call needs, or None.  errors: int32 [1] the error
+        bits are ORed into, or None."""
+        N, flat = self._check_eval_args(logits, mask_bits, actions)
+        log_prob = torch.empty(N, dtype=torch.float32, device=logits.device)
+        entropy = torch.empty(N, dtype=torch.float32, device=logits.device)
+        if N == 0:  # torch gives empty tensors a null pointer
+            return log_prob, entropy
+        _lib.check(self._L.pcbenv_evaluate_logits(
+            self._h, logits.data_ptr(), _lib.LOGITS_F32 if logits.dtype == torch.float32 else _lib.LOGITS_BF16,
+            mask_bits.data_ptr(), actions.data_ptr(), _lib.ACTION_FLAT if flat else _lib.ACTION_TUPLE, N,
+            log_prob.data_ptr(), entropy.data_ptr(), None if stats is None else stats.data_ptr(),
+            None if errors is None else errors.data_ptr(), self._stream()), self._h)
+        return log_prob, entropy
+
+    def evaluate_logits_backward(self, logits, mask_bits, actions, stats, grad_log_prob, grad_entropy,
+                                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`pcbenv_evaluate_logits_backward`, one kernel launch: the gradient with respect to `logits`, every element
+        written (into `out`, or a fresh `torch.empty_like(logits)`).  grad_log_prob / grad_entropy: float32 [N] or None
+        (zero)."""
+        N, flat = self._check_eval_args(logits, mask_bits, actions)
+        if out is None:
+            out = torch.empty_like(logits)
+        for name, t, shape in (("stats", stats, (N, 4)), ("grad_log_prob", grad_log_prob, (N,)), ("grad_entropy", grad_entropy, (N,))):
+            if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != logits.device):
+                raise ValueError(f"{name} must be a C-contiguous float32 tensor {list(shape)} on {logits.device}")
+        if out.dtype != logits.dtype or out.shape != logits.shape or not out.is_contiguous() or out.device != logits.device:
+            raise ValueError("out must match logits in dtype, shape and device and be C-contiguous")
+        if N == 0:
+            return out
+        _lib.check(self._L.pcbenv_evaluate_logits_backward(
+            self._h, logits.data_ptr(), _lib.LOGITS_F32 if logits.dtype == torch.float32 else _lib.LOGITS_BF16,
+            mask_bits.data_ptr(), actions.data_ptr(), _lib.ACTION_FLAT if flat else _lib.ACTION_TUPLE, N,
+            None if stats is None else stats.data_ptr(), None if grad_log_prob is None else grad_log_prob.data_ptr(),
+            None if grad_entropy is None else grad_entropy.data_ptr(), out.data_ptr(), self._stream()), self._h)
+        return out
+
+    @torch.no_grad()
+    def evaluate_logits(self, logits, mask_bits, actions, errors: Optional[torch.Tensor] = None):
+        """Log-probability and entropy of stored actions under the masked categorical of `logits` (the reference's
+        RLlib `Categorical.logp` / `entropy` of the masked logits), without a gradient: `(log_prob, entropy)` float32
+        [N].  N is arbitrary (a minibatch of stored steps).  `pcbenv.masked_categorical.evaluate` is the differentiable
+        form."""
+        return self.evaluate_logits_forward(logits, mask_bits, actions, None, errors)
+
     def rollout_step(self, step_index: int, flat: bool = False, out: Optional[torch.Tensor] = None):
         """`sample_actions` + `step` in one kernel launch (the body of the reference's random-policy
         `simulate()` loop, agent/random/random_policy_square.py:38-56); `out` receives the actions taken."""
@@ -477,14 +545,22 @@ class BatchedPlacementEnv:
         if "last_done" in d:
             self._last_done.copy_(d["last_done"])
 
-    def mask_bits(self) -> torch.Tensor:
-        """Bit-packed legal-action mask, int64 [B, 2, H, ceil(W/64)] (a copy; bit y of word [b, o, x, y // 64])."""
+    def mask_bits(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Bit-packed legal-action mask, int64 [B, 2, H, ceil(W/64)] (a copy; bit y of word [b, o, x, y // 64]).
+        out: a C-contiguous int64 tensor of that shape on `self.device` to write into instead (for example one step's
+        row of a [T, B, 2, H, WW] trajectory tensor); it is returned."""
         stride = C.c_int64()
         ptr = self._L.pcbenv_mask_bits(self._h, C.byref(stride))
         H, WW = self.cfg.height, (self.cfg.width + 63) // 64
         nbytes = stride.value * self.num_envs
         raw = _as_tensor(ptr, nbytes, self.device)  # library-owned block, wrapped without taking ownership
-        return raw.view(self.num_envs, stride.value)[:, :2 * H * WW * 8].contiguous().view(torch.int64).view(self.num_envs, 2, H, WW)
+        rows = raw.view(self.num_envs, stride.value)[:, :2 * H * WW * 8]
+        if out is None:
+            return rows.contiguous().view(torch.int64).view(self.num_envs, 2, H, WW)
+        if out.dtype != torch.int64 or tuple(out.shape) != (self.num_envs, 2, H, WW) or not out.is_contiguous() or out.device.type != self.device.type:
+            raise ValueError(f"mask_bits: out must be a C-contiguous int64 tensor [{self.num_envs}, 2, {H}, {WW}] on {self.device}")
+        out.view(torch.uint8).view(self.num_envs, 2 * H * WW * 8).copy_(rows)
+        return out
 
     # reference-style attribute access
     @property

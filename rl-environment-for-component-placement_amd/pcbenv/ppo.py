@@ -31,9 +31,13 @@ class PPOConfig:
     lr: float = 3e-4
     adv_mode: str = "all_gather"
     # collect() draws with env.sample_logits (the masked categorical in one kernel launch, logp from the kernel) instead of
-    # torch's Categorical; update() keeps torch's masked Categorical (it needs gradients).  Off by default: the torch path
-    # keeps existing runs' random stream.
+    # torch's Categorical; update() keeps torch's masked Categorical unless device_evaluator is on.  Off by default: the
+    # torch path keeps existing runs' random stream.
     device_sampler: bool = False
+    # update() evaluates log-probability and entropy with masked_categorical.evaluate (one kernel launch forward, one
+    # backward, from the raw logits and each step's bit-packed legal set, which collect() then keeps) instead of the
+    # masked logits and torch's Categorical.  With device_sampler as well nothing reads "action_mask": obs_keys may omit it.
+    device_evaluator: bool = False
 
 
 def _allreduce_grads(model):
@@ -71,6 +75,9 @@ class PPOTrainer:
         val = torch.zeros((T + 1, B), device=env.device)
         rew = torch.zeros((T, B), device=env.device)
         done = torch.zeros((T, B), device=env.device)
+        bits = None
+        if self.cfg.device_evaluator:
+            bits = torch.empty((T, B, 2, env.cfg.height, (env.cfg.width + 63) // 64), dtype=torch.int64, device=env.device)
         self.policy.eval()
         finished = []
         for t in range(T):
@@ -78,6 +85,8 @@ class PPOTrainer:
             if not self.in_place:
                 for k in self.obs_keys:
                     buf[k][t].copy_(obs[k])
+            if bits is not None:
+                env.mask_bits(out=bits[t])
             if self.cfg.device_sampler:
                 logits, v = self.policy(obs, mask=False)
                 a, lp, _ = env.sample_logits(logits.contiguous(), self.draws, flat=True)
@@ -97,7 +106,7 @@ class PPOTrainer:
             if fin.any():
                 finished.append(self._ep_ret[fin].clone())
                 self._ep_ret[fin] = 0
-        _, val[T] = self.policy(env.obs)
+        _, val[T] = self.policy(env.obs, mask=False) if self.cfg.device_evaluator and self.cfg.device_sampler else self.policy(env.obs)
         if finished:
             self.returns.append(float(torch.cat(finished).mean()))
         adv = torch.zeros((T, B), device=env.device)
@@ -107,7 +116,10 @@ class PPOTrainer:
             delta = rew[t] + self.cfg.gamma * val[t + 1] * nonterm - val[t]
             last = delta + self.cfg.gamma * self.cfg.lam * nonterm * last
             adv[t] = last
-        return {"obs": buf, "act": act, "logp": logp, "adv": adv, "ret": adv + val[:T]}
+        batch = {"obs": buf, "act": act, "logp": logp, "adv": adv, "ret": adv + val[:T]}
+        if bits is not None:
+            batch["mask_bits"] = bits
+        return batch
 
     def update(self, batch) -> Dict[str, float]:
         T, B = batch["act"].shape
@@ -122,13 +134,23 @@ class PPOTrainer:
         with torch.no_grad():
             self.policy.train()
             ridx = torch.randperm(N, device=act.device)[:max(1, N // self.cfg.minibatches)]
-            self.policy({k: o[ridx] for k, o in flat_obs.items()})
+            if "mask_bits" in batch:
+                self.policy({k: o[ridx] for k, o in flat_obs.items()}, mask=False)  # the statistics do not depend on the mask
+            else:
+                self.policy({k: o[ridx] for k, o in flat_obs.items()})
             allreduce_mean_([b for b in self.policy.buffers() if b.is_floating_point()])
         self.policy.eval()
         stats = {}
+        bits = act32 = None
+        if "mask_bits" in batch:  # PPOConfig.device_evaluator
+            bits = batch["mask_bits"].reshape((N,) + tuple(batch["mask_bits"].shape[2:]))
+            act32 = act.to(torch.int32)
         for _ in range(self.cfg.epochs):
             perm = torch.randperm(N, device=act.device)
             for idx in perm.chunk(self.cfg.minibatches):
+                if bits is not None:
+                    stats = self._minibatch_device(flat_obs, bits, act32, idx, logp0, adv, ret)
+                    continue
                 logits, v = self.policy({k: o[idx] for k, o in flat_obs.items()})
                 d = torch.distributions.Categorical(logits=logits)
                 ratio = torch.exp(d.log_prob(act[idx]) - logp0[idx])
@@ -143,6 +165,23 @@ class PPOTrainer:
                 self.opt.step()
                 stats = {"loss": float(loss.detach()), "pg": float(pg.detach()), "vf": float(vf.detach()), "entropy": float(ent.detach())}
         return stats
+
+    def _minibatch_device(self, flat_obs, bits, act32, idx, logp0, adv, ret):
+        """One minibatch step of update() with the device evaluator: raw logits, `masked_categorical.evaluate`."""
+        from .masked_categorical import evaluate
+        logits, v = self.policy({k: o[idx] for k, o in flat_obs.items()}, mask=False)
+        logp, entropy = evaluate(self.env, logits, bits[idx], act32[idx])
+        ratio = torch.exp(logp - logp0[idx])
+        pg = -torch.min(ratio * adv[idx], torch.clamp(ratio, 1 - self.cfg.clip, 1 + self.cfg.clip) * adv[idx]).mean()
+        vf = 0.5 * (v - ret[idx]).pow(2).mean()
+        ent = entropy.mean()
+        loss = pg + self.cfg.vf_coef * vf - self.cfg.ent_coef * ent
+        self.opt.zero_grad(set_to_none=True)
+        loss.backward()
+        _allreduce_grads(self.policy)
+        torch.nn.utils.clip_grad_norm_(self.policy.parameters(), 1.0)
+        self.opt.step()
+        return {"loss": float(loss.detach()), "pg": float(pg.detach()), "vf": float(vf.detach()), "entropy": float(ent.detach())}
 
     def train(self, iterations: int, log=None):
         import time

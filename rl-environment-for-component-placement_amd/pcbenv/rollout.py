@@ -25,6 +25,7 @@ class Trajectory:
     obs: Dict[str, torch.Tensor]  # requested observation keys, [T, B, ...] (observation BEFORE the step)
     log_prob: Optional[torch.Tensor] = None  # [T, B] float32, collect(logits_policy=...) only
     entropy: Optional[torch.Tensor] = None   # [T, B] float32, collect(logits_policy=...) only
+    mask_bits: Optional[torch.Tensor] = None  # [T, B, 2, H, WW] int64 (legal set BEFORE the step), collect(store_mask_bits=True) only
 
     def episode_returns(self):
         """List of per-environment lists of completed-episode returns (sum of rewards up to each done)."""
@@ -42,8 +43,10 @@ class Trajectory:
 
 
 def collect(env, num_steps: int, policy: Optional[Callable] = None, t0: int = 0,
-            store_obs: Sequence[str] = (), logits_policy: Optional[Callable] = None, greedy: bool = False) -> Trajectory:
-    """logits_policy: step t draws `env.sample_logits(logits_policy(obs), t0 + t, greedy)`; not together with policy."""
+            store_obs: Sequence[str] = (), logits_policy: Optional[Callable] = None, greedy: bool = False,
+            store_mask_bits: bool = False) -> Trajectory:
+    """logits_policy: step t draws `env.sample_logits(logits_policy(obs), t0 + t, greedy)`; not together with policy.
+    store_mask_bits: keep every step's bit-packed legal set (`env.mask_bits`), what `masked_categorical.evaluate` reads."""
     if policy is not None and logits_policy is not None:
         raise ValueError("collect: pass either policy or logits_policy, not both")
     B, dev = env.num_envs, env.device
@@ -57,9 +60,12 @@ def collect(env, num_steps: int, policy: Optional[Callable] = None, t0: int = 0,
     info = torch.zeros((num_steps, B, 2), dtype=torch.float64, device=dev) if env.info else None
     obs = {k: torch.zeros((num_steps,) + tuple(env.obs[k].shape), dtype=env.obs[k].dtype, device=dev) for k in store_obs}
     H, W = env.cfg.height, env.cfg.width
+    mask_bits = torch.empty((num_steps, B, 2, H, (W + 63) // 64), dtype=torch.int64, device=dev) if store_mask_bits else None
     for t in range(num_steps):
         for k in store_obs:
             obs[k][t].copy_(env.obs[k])
+        if mask_bits is not None:
+            env.mask_bits(out=mask_bits[t])
         if logits_policy is not None:
             _, log_prob[t], entropy[t] = env.sample_logits(logits_policy(env.obs), t0 + t, greedy=greedy, out=actions[t])
             env.step(actions[t])
@@ -82,7 +88,7 @@ def collect(env, num_steps: int, policy: Optional[Callable] = None, t0: int = 0,
             info[t].copy_(env.info_raw)
         if not env.auto_reset:
             env.reset_done()
-    return Trajectory(actions, rewards, dones, info, obs, log_prob, entropy)
+    return Trajectory(actions, rewards, dones, info, obs, log_prob, entropy, mask_bits)
 
 
 def masked_logits(logits: torch.Tensor, action_mask: torch.Tensor) -> torch.Tensor:
