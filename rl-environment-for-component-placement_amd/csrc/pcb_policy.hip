@@ -17,6 +17,8 @@
 //             use; per segment (m = max, s = sum exp(l - m), t = sum exp(l - m) (l - m), first index of the max) -> LDS.
 //   pick      wavefront 0 combines the segments in float64 (M, Z, the prefix, sum p (l - M)), finds the segment J that
 //             holds u*Z, re-reads J (<= 256 bytes, just fetched) and selects the element; one lane writes the results.
+// Pass 1, the chunk loads, the legal count and the combine's per-lane partials are those of k_evaluate_logits
+// (pcb_policy_common.h); the scan that gives the prefix and Z, and the pick, are this kernel's own.
 // Weights are exp2((l - m) * log2 e) in float32, computed by one function in both passes, so the re-read of J sees
 // exactly the weights its sum was made of.
 #include <hip/hip_runtime.h>
@@ -41,91 +43,28 @@ namespace {
 #endif
 constexpr int UNROLL = PCB_SL_UNROLL;
 
-// VEC: W % 4 == 0 and the logits 4-element aligned (every chunk of 4 is one vector load); otherwise one load per legal logit
 template <typename T, bool VEC, int NW>
 __global__ __launch_bounds__(64 * NW) void k_sample_logits(DevParams p, SampleLogitsArgs g) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int e = xcd_contiguous_env((int)blockIdx.x, 0, p.B), tid = threadIdx.x, lane = tid & (WAVE - 1);
+    const EvalGeom q{p.O, p.H, p.W, p.WW, p.B};
     const int H = p.H, W = p.W, WW = p.WW, HW = H * W, S = p.O * H * WW;
-    const int nwords = (p.kind == PCBENV_SQUARE ? 1 : 2) * H * WW;
     const u64 *vm = (const u64 *)(p.state + (size_t)e * p.stateStride + p.offVm);
-    u64 *vml = (u64 *)smem;  // the bit rows, [planes][H][WW]
-    const int pad = seg_pad(S);
-    float *sm_m = (float *)(vml + 2 * H * WW), *sm_s = sm_m + pad, *sm_t = sm_s + pad;
-    int *sm_i = (int *)(sm_t + pad), *bad_flag = sm_i + pad;
-    for (int i = tid; i < nwords; i += 64 * NW) vml[i] = vm[i];
-    if (tid == 0) *bad_flag = 0;
+    const PolicyLds lds = carve_lds(smem, q);
+    stage_bits(lds.vml, vm, q, tid, 64 * NW);
+    if (tid == 0) *lds.bad = 0;
     __syncthreads();
 
     const T *row = (const T *)g.logits + (size_t)e * (size_t)(p.O * HW);
-    const int sub = lane & (SEG_LANES - 1), grp = tid >> 4;  // grp: this row's segment within a round
-    constexpr int G = 64 * NW / SEG_LANES;                       // segments per round
     const bool greedy = g.greedy != 0;
-    bool bad = false;
-    for (int s0 = 0; s0 < S; s0 += G * UNROLL) {
-        float v[UNROLL][4];
-        unsigned nib[UNROLL];
-        int a0[UNROLL];
-        #pragma unroll
-        for (int u = 0; u < UNROLL; u++) {
-            const int j = s0 + u * G + grp;
-            nib[u] = 0u; a0[u] = 0;
-            if (j < S) {
-                const Seg sg = segment(j, H, W, WW);
-                const int rem = sg.len - 4 * sub;
-                const unsigned word4 = (unsigned)(seg_word(vml, sg, H, WW) >> (4 * sub)) & 15u;
-                nib[u] = rem <= 0 ? 0u : rem >= 4 ? word4 : word4 & ((1u << rem) - 1u);
-                a0[u] = sg.a0 + 4 * sub;
-            }
-            if (VEC) {
-                if (nib[u]) load4(row + a0[u], v[u]);
-            } else {
-                #pragma unroll
-                for (int i = 0; i < 4; i++)
-                    if ((nib[u] >> i) & 1u) v[u][i] = to_f32(row[a0[u] + i]);
-            }
-        }
-        #pragma unroll
-        for (int u = 0; u < UNROLL; u++) {
-            float lm = -INFINITY;
-            #pragma unroll
-            for (int i = 0; i < 4; i++)
-                if ((nib[u] >> i) & 1u) { bad |= !(v[u][i] < INFINITY); lm = fmaxf(lm, v[u][i]); }
-            const float m = row_max(lm);
-            float sw = 0.f, st = 0.f;
-            int first = INT_MAX;
-            if (m > -INFINITY) {
-                #pragma unroll
-                for (int i = 3; i >= 0; i--) {
-                    const float l = v[u][i];
-                    if (((nib[u] >> i) & 1u) && l > -INFINITY) {
-                        const float d = l - m, w = seg_weight(l, m);
-                        sw += w; st += w * d;
-                        if (l == m) first = a0[u] + i;
-                    }
-                }
-            }
-            sw = row_sum(sw); st = row_sum(st);
-            if (greedy) first = row_min(first);
-            const int j = s0 + u * G + grp;
-            if (sub == 0 && j < S) { const int k = seg_slot(j); sm_m[k] = m; sm_s[k] = sw; sm_t[k] = st; sm_i[k] = first; }
-        }
-    }
-    if (bad) *bad_flag = 1;
+    if (pass1<T, VEC, NW, UNROLL, true>(row, lds, q, tid, greedy)) *lds.bad = 1;
     __syncthreads();
     if (tid >= WAVE) return;
 
     // ---- wavefront 0: the legal count, M, Z, the pick, the outputs
-    int cnt = 0;
-    for (int i = lane; i < nwords; i += WAVE) cnt += __popcll(vml[i]);
-    const int total = __builtin_amdgcn_readlane(wave_inclusive_scan(cnt, lane), WAVE - 1);
-    const bool mirrored = p.kind == PCBENV_PIN || p.kind == PCBENV_SPATIAL;  // orientations 2, 3 reuse planes 0, 1
-    const int n = mirrored ? 2 * total : total;
-    const int per = (S + WAVE - 1) / WAVE, j0 = min(lane * per, S), j1 = min(j0 + per, S);
-    float lm = -INFINITY;
-    for (int j = j0; j < j1; j++) lm = fmaxf(lm, sm_m[seg_slot(j)]);
-    const float M = wave_max(lm);
-    const unsigned bits = n == 0 ? 0u : *bad_flag ? 1u : M == -INFINITY ? 2u : 0u;
+    int j0, j1;
+    lane_run(S, lane, &j0, &j1);
+    const auto [n, M, bits] = row_head(lds, q, j0, j1, lane);
     int a = 0;
     double logp = 0.0, ent = 0.0;
     if (n > 0 && bits) {
@@ -136,15 +75,7 @@ __global__ __launch_bounds__(64 * NW) void k_sample_logits(DevParams p, SampleLo
         logp = -log((double)n); ent = log((double)n);
     } else if (n > 0) {
         double mine = 0.0, tl = 0.0;
-        for (int j = j0; j < j1; j++) {
-            const int k = seg_slot(j);
-            const float s = sm_s[k];
-            if (s > 0.f) {
-                const float m = sm_m[k], sc = seg_weight(m, M);
-                mine += (double)s * (double)sc;
-                tl += (double)sc * ((double)sm_t[k] + (double)s * ((double)m - (double)M));
-            }
-        }
+        combine_partials(lds, j0, j1, M, &mine, &tl);
         const double incl = wave_scan(mine, lane), Z = __shfl(incl, WAVE - 1);
         double excl = __shfl_up(incl, 1);
         if (lane == 0) excl = 0.0;
@@ -153,7 +84,7 @@ __global__ __launch_bounds__(64 * NW) void k_sample_logits(DevParams p, SampleLo
         if (greedy) {
             int cand = INT_MAX;
             for (int j = j0; j < j1; j++)
-                if (sm_m[seg_slot(j)] == M) { cand = sm_i[seg_slot(j)]; break; }
+                if (lds.m[seg_slot(j)] == M) { cand = lds.first[seg_slot(j)]; break; }
             a = wave_min(cand);
             logp = -logZ;
         } else {
@@ -168,9 +99,9 @@ __global__ __launch_bounds__(64 * NW) void k_sample_logits(DevParams p, SampleLo
                 double acc = excl;
                 for (int j = j0; j < j1; j++) {
                     const int k = seg_slot(j);
-                    const float s = sm_s[k];
+                    const float s = lds.s[k];
                     if (s > 0.f) {
-                        const float sc = seg_weight(sm_m[k], M);
+                        const float sc = seg_weight(lds.m[k], M);
                         const double sj = (double)s * (double)sc;
                         J = j; rloc = (uz - acc) / (double)sc;  // threshold in units of the segment's own weights
                         if (acc + sj > uz) break;
@@ -181,10 +112,10 @@ __global__ __launch_bounds__(64 * NW) void k_sample_logits(DevParams p, SampleLo
             J = __shfl(J, ol); rloc = __shfl(rloc, ol);
             // re-read segment J: lane k holds column 64 w + k
             const Seg sg = segment(J, H, W, WW);
-            const u64 word = seg_word(vml, sg, H, WW);
+            const u64 word = seg_word(lds.vml, sg, H, WW);
             const bool legal = lane < sg.len && ((word >> lane) & 1ull);
             const float l = legal ? to_f32(row[sg.a0 + lane]) : -INFINITY;
-            const float w = legal && l > -INFINITY ? seg_weight(l, sm_m[seg_slot(J)]) : 0.f;
+            const float w = legal && l > -INFINITY ? seg_weight(l, lds.m[seg_slot(J)]) : 0.f;
             const float c = wave_scan(w, lane);
             const u64 hit = __ballot(w > 0.f && (double)c > rloc);
             // rounding can leave no element above the threshold: the segment's last legal element with weight
@@ -203,21 +134,13 @@ __global__ __launch_bounds__(64 * NW) void k_sample_logits(DevParams p, SampleLo
     }
 }
 
-template <typename T, bool VEC>
-void launch(const SampleLogitsLaunch &a, size_t lds) {
-    const DevParams &d = a.d;
-    if (d.O * d.H * d.W >= PCB_SL_NW4_MIN_A) hipLaunchKernelGGL((k_sample_logits<T, VEC, 4>), dim3(d.B), dim3(256), lds, a.stream, d, a.g);
-    else hipLaunchKernelGGL((k_sample_logits<T, VEC, 1>), dim3(d.B), dim3(64), lds, a.stream, d, a.g);
-}
-
 }  // namespace
 
 int pcb_launch_sample_logits(const SampleLogitsLaunch &a) {
     const DevParams &d = a.d;
-    const size_t lds = lds_bytes(d.H, d.WW, d.O * d.H * d.WW);
-    const bool f32 = a.dtype == PCBENV_LOGITS_F32;
-    const bool vec = d.W % 4 == 0 && (uintptr_t)a.g.logits % (f32 ? 16 : 8) == 0;
-    if (f32) { if (vec) launch<float, true>(a, lds); else launch<float, false>(a, lds); }
-    else { if (vec) launch<bf16_bits, true>(a, lds); else launch<bf16_bits, false>(a, lds); }
+    const EvalGeom q{d.O, d.H, d.W, d.WW, d.B};
+    select_launch(a.dtype, d.W, (uintptr_t)a.g.logits, d.O * d.H * d.W, PCB_SL_NW4_MIN_A, [&](auto t, auto vec, auto nw) {
+        hipLaunchKernelGGL((k_sample_logits<typename decltype(t)::type, vec, nw>), dim3(d.B), dim3(64 * nw), lds_bytes(q), a.stream, d, a.g);
+    });
     return 0;
 }

@@ -10,15 +10,15 @@
 // where its action is legal, as in k_sample_logits.
 //
 // One workgroup per row (xcd_contiguous_env: each XCD streams a contiguous share of the logits and of the gradient),
-// four wavefronts when A = O*H*W >= 4096, otherwise one.  Segments (the up to 64 logits one mask word governs) and the
-// 16-lane DPP rows that reduce them are those of k_sample_logits (pcb_policy_common.h).
+// four wavefronts when A = O*H*W >= 4096, otherwise one.  Segments (the up to 64 logits one mask word governs), the
+// chunk loads, pass 1, the legal count and the combine's per-lane partials are those of k_sample_logits
+// (pcb_policy_common.h).
 //   forward   per segment (m = max, s = sum exp(l - m), t = sum exp(l - m) (l - m)) -> LDS; wavefront 0 combines them
 //             in float64 (M, Z, sum p (l - M)) and counts the legal bits; the stored action's logit is read directly and
 //             its bit checked.  (M, log Z, entropy, row status) go to `stats` for the backward kernel.
 //   backward  one pass: a chunk of 4 with no legal bit stores zeros without loading; otherwise
 //             p = exp2((l - M - log Z) log2 e), g = g_lp (1[i = a] - p) - g_H p (log p + Hrow), whole vectors stored.
 #include <hip/hip_runtime.h>
-#include <limits.h>
 
 #include "pcbenv.h"
 #include "pcb_kernels.h"
@@ -61,23 +61,6 @@ __device__ inline void store4(bf16_bits *p, const float v[4]) {
 __device__ inline void store1(float *p, float v) { *p = v; }
 __device__ inline void store1(bf16_bits *p, float v) { *p = to_bf16(v); }
 
-// the bit rows of row e -> LDS ([planes][H][WW]; square: plane 0 only)
-__device__ inline void load_mask(u64 *vml, const EvalGeom &q, const u64 *mask_bits, int e, int tid, int nthreads) {
-    const u64 *vm = mask_bits + (size_t)e * (size_t)(2 * q.H * q.WW);
-    const int nwords = (q.O == 1 ? 1 : 2) * q.H * q.WW;
-    for (int i = tid; i < nwords; i += nthreads) vml[i] = vm[i];
-}
-// this lane's 4 columns of segment j: the first flat index, how many of them exist (0 beyond the segment's length or the
-// last segment) and the legal bits of those
-__device__ inline unsigned lane_nibble(const u64 *vml, const EvalGeom &q, int j, int S, int sub, int *a0, int *cols) {
-    *a0 = 0; *cols = 0;
-    if (j >= S) return 0u;
-    const Seg sg = segment(j, q.H, q.W, q.WW);
-    const unsigned word4 = (unsigned)(seg_word(vml, sg, q.H, q.WW) >> (4 * sub)) & 15u;
-    *a0 = sg.a0 + 4 * sub;
-    *cols = max(0, min(4, sg.len - 4 * sub));
-    return word4 & ((1u << *cols) - 1u);
-}
 // flat action of row e, or -1 when it is out of range; *legal: its bit
 __device__ inline int stored_action(const u64 *vml, const EvalGeom &q, const int *actions, int fmt, int e, bool *legal) {
     const int HW = q.H * q.W;
@@ -94,99 +77,34 @@ __device__ inline int stored_action(const u64 *vml, const EvalGeom &q, const int
     return o * HW + x * q.W + y;
 }
 
-// VEC: W % 4 == 0 and the logits 4-element aligned (every chunk of 4 is one vector load); otherwise one load per legal logit
 template <typename T, bool VEC, int NW>
 __global__ __launch_bounds__(64 * NW) void k_evaluate_logits(EvalGeom q, EvalLogitsArgs g) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int e = xcd_contiguous_env((int)blockIdx.x, 0, q.rows), tid = threadIdx.x, lane = tid & (WAVE - 1);
-    const int H = q.H, W = q.W, WW = q.WW, S = q.O * H * WW;
-    u64 *vml = (u64 *)smem;
-    const int pad = seg_pad(S);
-    float *sm_m = (float *)(vml + 2 * H * WW), *sm_s = sm_m + pad, *sm_t = sm_s + pad;
-    int *bad_flag = (int *)(sm_t + pad);
-    load_mask(vml, q, g.mask_bits, e, tid, 64 * NW);
-    if (tid == 0) *bad_flag = 0;
+    const PolicyLds lds = carve_lds(smem, q);
+    stage_bits(lds.vml, g.mask_bits + (size_t)e * (size_t)(2 * q.H * q.WW), q, tid, 64 * NW);
+    if (tid == 0) *lds.bad = 0;
     __syncthreads();
 
-    const T *row = (const T *)g.logits + (size_t)e * (size_t)(q.O * H * W);
+    const T *row = (const T *)g.logits + (size_t)e * (size_t)(q.O * q.H * q.W);
     // the stored action's logit, in flight under pass 1
     bool a_legal = false;
     int a = -1;
     float la = 0.f;
     if (tid == 0) {
-        a = stored_action(vml, q, g.actions, g.fmt, e, &a_legal);
+        a = stored_action(lds.vml, q, g.actions, g.fmt, e, &a_legal);
         if (a_legal) la = to_f32(row[a]);
     }
-    const int sub = lane & (SEG_LANES - 1), grp = tid >> 4;
-    constexpr int G = 64 * NW / SEG_LANES;  // segments per round
-    bool bad = false;
-    for (int s0 = 0; s0 < S; s0 += G * UNROLL) {
-        float v[UNROLL][4];
-        unsigned nib[UNROLL];
-        #pragma unroll
-        for (int u = 0; u < UNROLL; u++) {
-            int a0, cols;
-            nib[u] = lane_nibble(vml, q, s0 + u * G + grp, S, sub, &a0, &cols);
-            if (VEC) {
-                if (nib[u]) load4(row + a0, v[u]);
-            } else {
-                #pragma unroll
-                for (int i = 0; i < 4; i++)
-                    if ((nib[u] >> i) & 1u) v[u][i] = to_f32(row[a0 + i]);
-            }
-        }
-        #pragma unroll
-        for (int u = 0; u < UNROLL; u++) {
-            float lm = -INFINITY;
-            #pragma unroll
-            for (int i = 0; i < 4; i++)
-                if ((nib[u] >> i) & 1u) { bad |= !(v[u][i] < INFINITY); lm = fmaxf(lm, v[u][i]); }
-            const float m = row_max(lm);
-            float sw = 0.f, st = 0.f;
-            if (m > -INFINITY) {
-                #pragma unroll
-                for (int i = 3; i >= 0; i--) {
-                    const float l = v[u][i];
-                    if (((nib[u] >> i) & 1u) && l > -INFINITY) {
-                        const float d = l - m, w = seg_weight(l, m);
-                        sw += w; st += w * d;
-                    }
-                }
-            }
-            sw = row_sum(sw); st = row_sum(st);
-            const int j = s0 + u * G + grp;
-            if (sub == 0 && j < S) { const int k = seg_slot(j); sm_m[k] = m; sm_s[k] = sw; sm_t[k] = st; }
-        }
-    }
-    if (bad) *bad_flag = 1;
+    if (pass1<T, VEC, NW, UNROLL, false>(row, lds, q, tid, false)) *lds.bad = 1;
     __syncthreads();
     if (tid >= WAVE) return;
 
-    // ---- wavefront 0: the legal count (columns beyond W never count), M, Z, the outputs
-    const int per = (S + WAVE - 1) / WAVE, j0 = min(lane * per, S), j1 = min(j0 + per, S);
-    int cnt = 0;
-    float lm = -INFINITY;
-    for (int j = j0; j < j1; j++) {
-        const Seg sg = segment(j, H, W, WW);
-        const u64 word = seg_word(vml, sg, H, WW);
-        cnt += __popcll(sg.len == 64 ? word : word & ((1ull << sg.len) - 1ull));
-        lm = fmaxf(lm, sm_m[seg_slot(j)]);
-    }
-    const int n = __builtin_amdgcn_readlane(wave_inclusive_scan(cnt, lane), WAVE - 1);
-    const float M = wave_max(lm);
-    const unsigned bad_bits = n == 0 ? 0u : *bad_flag ? 1u : M == -INFINITY ? 2u : 0u;
+    // ---- wavefront 0: the legal count, M, Z, the outputs
+    int j0, j1;
+    lane_run(q.O * q.H * q.WW, lane, &j0, &j1);
+    const auto [n, M, bad_bits] = row_head(lds, q, j0, j1, lane);
     double mine = 0.0, tl = 0.0;
-    if (n > 0 && !bad_bits) {
-        for (int j = j0; j < j1; j++) {
-            const int k = seg_slot(j);
-            const float s = sm_s[k];
-            if (s > 0.f) {
-                const float m = sm_m[k], sc = seg_weight(m, M);
-                mine += (double)s * (double)sc;
-                tl += (double)sc * ((double)sm_t[k] + (double)s * ((double)m - (double)M));
-            }
-        }
-    }
+    if (n > 0 && !bad_bits) combine_partials(lds, j0, j1, M, &mine, &tl);
     const double Z = wave_sum(mine), tsum = wave_sum(tl);
     if (lane != 0) return;
     unsigned bits = bad_bits;
@@ -223,9 +141,9 @@ template <typename T, bool VEC, int NW>
 __global__ __launch_bounds__(64 * NW) void k_evaluate_logits_backward(EvalGeom q, EvalLogitsBackwardArgs g) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int e = xcd_contiguous_env((int)blockIdx.x, 0, q.rows), tid = threadIdx.x, lane = tid & (WAVE - 1);
-    const int H = q.H, W = q.W, WW = q.WW, S = q.O * H * WW;
+    const int S = q.O * q.H * q.WW;
     u64 *vml = (u64 *)smem;
-    load_mask(vml, q, g.mask_bits, e, tid, 64 * NW);
+    stage_bits(vml, g.mask_bits + (size_t)e * (size_t)(2 * q.H * q.WW), q, tid, 64 * NW);
     const float4 st = *(const float4 *)(g.stats + 4 * (size_t)e);
     const float M = st.x, logZ = st.y, Hrow = st.z;
     const bool zero_row = st.w == ROW_ZERO;
@@ -236,7 +154,7 @@ __global__ __launch_bounds__(64 * NW) void k_evaluate_logits_backward(EvalGeom q
         bool legal;
         a = stored_action(vml, q, g.actions, g.fmt, e, &legal);
     }
-    const size_t base = (size_t)e * (size_t)(q.O * H * W);
+    const size_t base = (size_t)e * (size_t)(q.O * q.H * q.W);
     const T *row = (const T *)g.logits + base;
     T *out = (T *)g.grad_logits + base;
     const int sub = lane & (SEG_LANES - 1), grp = tid >> 4;
@@ -246,17 +164,7 @@ __global__ __launch_bounds__(64 * NW) void k_evaluate_logits_backward(EvalGeom q
         unsigned nib[UNROLL];
         int a0[UNROLL], cols[UNROLL];  // cols: how many of this lane's 4 columns exist (all of them get a gradient)
         #pragma unroll
-        for (int u = 0; u < UNROLL; u++) {
-            nib[u] = lane_nibble(vml, q, s0 + u * G + grp, S, sub, &a0[u], &cols[u]);
-            if (zero_row) nib[u] = 0u;
-            if (VEC) {
-                if (nib[u]) load4(row + a0[u], v[u]);
-            } else {
-                #pragma unroll
-                for (int i = 0; i < 4; i++)
-                    if ((nib[u] >> i) & 1u) v[u][i] = to_f32(row[a0[u] + i]);
-            }
-        }
+        for (int u = 0; u < UNROLL; u++) nib[u] = load_chunk<T, VEC>(row, vml, q, s0 + u * G + grp, S, sub, zero_row, v[u], &a0[u], &cols[u]);
         #pragma unroll
         for (int u = 0; u < UNROLL; u++) {
             float gr[4];
@@ -274,37 +182,23 @@ __global__ __launch_bounds__(64 * NW) void k_evaluate_logits_backward(EvalGeom q
     }
 }
 
-size_t eval_lds_bytes(const EvalGeom &q) { return lds_bytes(q.H, q.WW, q.O * q.H * q.WW); }
-
-template <typename T, bool VEC>
-void launch_forward(const EvalLogitsLaunch &a) {
-    const EvalGeom &q = a.q;
-    if (q.O * q.H * q.W >= PCB_EV_NW4_MIN_A) hipLaunchKernelGGL((k_evaluate_logits<T, VEC, 4>), dim3(q.rows), dim3(256), eval_lds_bytes(q), a.stream, q, a.g);
-    else hipLaunchKernelGGL((k_evaluate_logits<T, VEC, 1>), dim3(q.rows), dim3(64), eval_lds_bytes(q), a.stream, q, a.g);
-}
-template <typename T, bool VEC>
-void launch_backward(const EvalLogitsBackwardLaunch &a) {
-    const EvalGeom &q = a.q;
-    const size_t lds = (size_t)16 * q.H * q.WW;
-    if (q.O * q.H * q.W >= PCB_EV_NW4_MIN_A) hipLaunchKernelGGL((k_evaluate_logits_backward<T, VEC, 4>), dim3(q.rows), dim3(256), lds, a.stream, q, a.g);
-    else hipLaunchKernelGGL((k_evaluate_logits_backward<T, VEC, 1>), dim3(q.rows), dim3(64), lds, a.stream, q, a.g);
-}
-
 }  // namespace
 
 int pcb_launch_evaluate_logits(const EvalLogitsLaunch &a) {
-    const bool f32 = a.dtype == PCBENV_LOGITS_F32;
-    const bool vec = a.q.W % 4 == 0 && (uintptr_t)a.g.logits % (f32 ? 16 : 8) == 0;
-    if (f32) { if (vec) launch_forward<float, true>(a); else launch_forward<float, false>(a); }
-    else { if (vec) launch_forward<bf16_bits, true>(a); else launch_forward<bf16_bits, false>(a); }
+    const EvalGeom &q = a.q;
+    select_launch(a.dtype, q.W, (uintptr_t)a.g.logits, q.O * q.H * q.W, PCB_EV_NW4_MIN_A, [&](auto t, auto vec, auto nw) {
+        hipLaunchKernelGGL((k_evaluate_logits<typename decltype(t)::type, vec, nw>), dim3(q.rows), dim3(64 * nw), lds_bytes(q), a.stream, q, a.g);
+    });
     return 0;
 }
 
+// the gradient is stored with the same vectors as the logits are loaded: both pointers aligned; LDS: the bit rows alone
 int pcb_launch_evaluate_logits_backward(const EvalLogitsBackwardLaunch &a) {
-    const bool f32 = a.dtype == PCBENV_LOGITS_F32;
+    const EvalGeom &q = a.q;
     const uintptr_t both = (uintptr_t)a.g.logits | (uintptr_t)a.g.grad_logits;
-    const bool vec = a.q.W % 4 == 0 && both % (f32 ? 16 : 8) == 0;
-    if (f32) { if (vec) launch_backward<float, true>(a); else launch_backward<float, false>(a); }
-    else { if (vec) launch_backward<bf16_bits, true>(a); else launch_backward<bf16_bits, false>(a); }
+    select_launch(a.dtype, q.W, both, q.O * q.H * q.W, PCB_EV_NW4_MIN_A, [&](auto t, auto vec, auto nw) {
+        hipLaunchKernelGGL((k_evaluate_logits_backward<typename decltype(t)::type, vec, nw>), dim3(q.rows), dim3(64 * nw),
+                           (size_t)16 * q.H * q.WW, a.stream, q, a.g);
+    });
     return 0;
 }

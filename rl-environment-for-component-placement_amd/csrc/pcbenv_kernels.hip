@@ -476,6 +476,10 @@ static int launch_reset(pcbenv *env, const uint8_t *mask, hipStream_t s) {
     default: return pcb_launch_reset_spatial(a);
     }
 }
+static bool stream_capturing(hipStream_t s) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+}
 // Every step launch has a number (DevParams::seq); see k_step_mixed for what the terminal list is.
 static int dispatch_step(pcbenv *env, int *actions, int fmt, int sampled, u64 seed, u64 first_env, u64 step_index, int num_steps, hipStream_t s) {
     StepLaunch a;
@@ -495,8 +499,7 @@ static int dispatch_step(pcbenv *env, int *actions, int fmt, int sampled, u64 se
     d.seq = env->seq;
     // A launch that is being captured into a hipGraph will be replayed with these very arguments: no launch number,
     // no buffer swap -- it runs without helpers, keeps no list and works on the state blocks in place.
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const bool capturing = hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+    const bool capturing = stream_capturing(s);
     d.term_wgs = 0;
     if (num_steps == 1 && !capturing && env->term_wgs > 0) {  // reward helpers: one transition per launch only
         // as many entries' helpers as the lists have lately been long (k_step reports it: + 25 %, + 2 per shard; never none:
@@ -845,9 +848,7 @@ extern "C" int pcbenv_gather(pcbenv *dst, const pcbenv *src, const int32_t *src_
     DEVICE_GUARD(dst);
     hipStream_t s = (hipStream_t)stream;
     // A captured launch would be replayed with the state sets of the capture: the second replay would read a stale set.
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-        return fail(dst, PCBENV_ESTATE, "pcbenv_gather cannot be captured into a graph");
+    if (stream_capturing(s)) return fail(dst, PCBENV_ESTATE, "pcbenv_gather cannot be captured into a graph");
     GatherLaunch a;
     a.d = dst->dp;
     DevParams &d = a.d;
@@ -887,25 +888,30 @@ extern "C" int pcbenv_gather(pcbenv *dst, const pcbenv *src, const int32_t *src_
 // The argument checks come before anything touches a device (a null handle included), so that every one of them can be
 // exercised without a GPU.  Nothing the library owns is written: no state block, presampled action, terminal list or
 // queue, and no generator interaction (nothing is consumed).
+static int logits_elem_bytes(int32_t logits_dtype) { return logits_dtype == PCBENV_LOGITS_F32 ? 4 : 2; }
+// the checks pcbenv_sample_logits and pcbenv_evaluate_logits[_backward] share
+static int logits_checks(pcbenv *env, const void *logits_dev, int32_t logits_dtype, const int32_t *actions_dev, int32_t fmt) {
+    if (!logits_dev) return fail(env, PCBENV_EINVAL, "null logits");
+    if (!actions_dev) return fail(env, PCBENV_EINVAL, "null actions");
+    if (logits_dtype != PCBENV_LOGITS_F32 && logits_dtype != PCBENV_LOGITS_BF16) return fail(env, PCBENV_EINVAL, "unknown logits dtype");
+    if (fmt != PCBENV_ACTION_TUPLE && fmt != PCBENV_ACTION_FLAT) return fail(env, PCBENV_EINVAL, "unknown action format");
+    if ((uintptr_t)logits_dev % logits_elem_bytes(logits_dtype) != 0)
+        return fail(env, PCBENV_EINVAL, "logits pointer not aligned to its element size");
+    return PCBENV_OK;
+}
 extern "C" int pcbenv_sample_logits(pcbenv *env, const void *logits_dev, int32_t logits_dtype, int32_t mode,
                                     int32_t *actions_dev, int32_t fmt, float *log_prob_dev, float *entropy_dev,
                                     uint32_t *errors_dev, uint64_t seed, uint64_t first_env_index, uint64_t step_index,
                                     void *stream) {
-    if (!logits_dev) return fail(env, PCBENV_EINVAL, "null logits");
-    if (!actions_dev) return fail(env, PCBENV_EINVAL, "null actions");
-    if (logits_dtype != PCBENV_LOGITS_F32 && logits_dtype != PCBENV_LOGITS_BF16) return fail(env, PCBENV_EINVAL, "unknown logits dtype");
+    const int rc = logits_checks(env, logits_dev, logits_dtype, actions_dev, fmt);
+    if (rc != PCBENV_OK) return rc;
     if (mode != PCBENV_DRAW_SAMPLE && mode != PCBENV_DRAW_GREEDY) return fail(env, PCBENV_EINVAL, "unknown draw mode");
-    if (fmt != PCBENV_ACTION_TUPLE && fmt != PCBENV_ACTION_FLAT) return fail(env, PCBENV_EINVAL, "unknown action format");
-    if ((uintptr_t)logits_dev % (logits_dtype == PCBENV_LOGITS_F32 ? 4 : 2) != 0)
-        return fail(env, PCBENV_EINVAL, "logits pointer not aligned to its element size");
     if (!env) return fail(0, PCBENV_EINVAL, "null handle");
     if (!env->bound) return fail(env, PCBENV_ESTATE, "pcbenv_bind_buffers has not been called");
     DEVICE_GUARD(env);
     hipStream_t s = (hipStream_t)stream;
     // A captured launch would keep reading the state set that was current at capture time (as pcbenv_gather).
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-        return fail(env, PCBENV_ESTATE, "pcbenv_sample_logits cannot be captured into a graph");
+    if (stream_capturing(s)) return fail(env, PCBENV_ESTATE, "pcbenv_sample_logits cannot be captured into a graph");
     SampleLogitsLaunch a;
     a.d = env->dp;  // d.state: the current state set, as k_sample reads it
     a.dtype = logits_dtype; a.stream = s;
@@ -923,13 +929,9 @@ extern "C" int pcbenv_sample_logits(pcbenv *env, const void *logits_dev, int32_t
 // and the device; nothing the library owns is read or written, so no buffers need to be bound.
 static int evaluate_checks(pcbenv *env, const void *logits_dev, int32_t logits_dtype, const uint64_t *mask_bits_dev,
                            const int32_t *actions_dev, int32_t fmt, int64_t num_rows) {
-    if (!logits_dev) return fail(env, PCBENV_EINVAL, "null logits");
+    const int rc = logits_checks(env, logits_dev, logits_dtype, actions_dev, fmt);
+    if (rc != PCBENV_OK) return rc;
     if (!mask_bits_dev) return fail(env, PCBENV_EINVAL, "null mask bits");
-    if (!actions_dev) return fail(env, PCBENV_EINVAL, "null actions");
-    if (logits_dtype != PCBENV_LOGITS_F32 && logits_dtype != PCBENV_LOGITS_BF16) return fail(env, PCBENV_EINVAL, "unknown logits dtype");
-    if (fmt != PCBENV_ACTION_TUPLE && fmt != PCBENV_ACTION_FLAT) return fail(env, PCBENV_EINVAL, "unknown action format");
-    if ((uintptr_t)logits_dev % (logits_dtype == PCBENV_LOGITS_F32 ? 4 : 2) != 0)
-        return fail(env, PCBENV_EINVAL, "logits pointer not aligned to its element size");
     if ((uintptr_t)mask_bits_dev % 8 != 0) return fail(env, PCBENV_EINVAL, "mask bits pointer not aligned to 8 bytes");
     if (num_rows < 0 || num_rows > INT32_MAX) return fail(env, PCBENV_EINVAL, "num_rows out of range");
     return PCBENV_OK;
@@ -970,7 +972,7 @@ extern "C" int pcbenv_evaluate_logits_backward(const pcbenv *cenv, const void *l
     if (!stats_dev) return fail(env, PCBENV_EINVAL, "null stats");
     if ((uintptr_t)stats_dev % 16 != 0) return fail(env, PCBENV_EINVAL, "stats pointer not aligned to 16 bytes");
     if (!grad_logits_dev) return fail(env, PCBENV_EINVAL, "null grad logits");
-    if ((uintptr_t)grad_logits_dev % (logits_dtype == PCBENV_LOGITS_F32 ? 4 : 2) != 0)
+    if ((uintptr_t)grad_logits_dev % logits_elem_bytes(logits_dtype) != 0)
         return fail(env, PCBENV_EINVAL, "grad logits pointer not aligned to its element size");
     if (!env) return fail(0, PCBENV_EINVAL, "null handle");
     if (num_rows == 0) return PCBENV_OK;

@@ -72,6 +72,13 @@ def _as_tensor(ptr: int, nbytes: int, device) -> torch.Tensor:
     return torch.as_tensor(_ExternalBlock(ptr, nbytes), device=device)
 
 
+def _logits_dtype(logits) -> int:
+    """The library's code (`_lib.LOGITS_*`) for a float32 or bfloat16 tensor of logits; ValueError otherwise."""
+    if not isinstance(logits, torch.Tensor) or logits.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("logits must be a float32 or bfloat16 tensor")
+    return _lib.LOGITS_F32 if logits.dtype == torch.float32 else _lib.LOGITS_BF16
+
+
 class BatchedPlacementEnv:
     is_batched = True
 
@@ -359,8 +366,7 @@ class BatchedPlacementEnv:
         entropy float32 [B]).  check=True synchronises and raises if a legal logit was NaN / +inf or every legal logit
         -inf (those environments then took the uniform draw)."""
         B, A = self.num_envs, self.cfg.num_orientations * self.cfg.height * self.cfg.width
-        if not isinstance(logits, torch.Tensor) or logits.dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError("logits must be a float32 or bfloat16 tensor")
+        dtype = _logits_dtype(logits)
         if logits.device != self.device and not (logits.device.type == "cuda" and self.device.index is None
                                                  and logits.device.index == torch.cuda.current_device()):
             raise ValueError(f"logits must be on {self.device}, got {logits.device}")
@@ -375,8 +381,8 @@ class BatchedPlacementEnv:
         entropy = torch.empty(B, dtype=torch.float32, device=self.device)
         err = torch.zeros(1, dtype=torch.int32, device=self.device) if check else None
         _lib.check(self._L.pcbenv_sample_logits(
-            self._h, logits.data_ptr(), _lib.LOGITS_F32 if logits.dtype == torch.float32 else _lib.LOGITS_BF16,
-            _lib.DRAW_GREEDY if greedy else _lib.DRAW_SAMPLE, out.data_ptr(), _lib.ACTION_FLAT if flat else _lib.ACTION_TUPLE,
+            self._h, logits.data_ptr(), dtype, _lib.DRAW_GREEDY if greedy else _lib.DRAW_SAMPLE, out.data_ptr(),
+            _lib.ACTION_FLAT if flat else _lib.ACTION_TUPLE,
             log_prob.data_ptr(), entropy.data_ptr(), None if err is None else err.data_ptr(), self.run_seed,
             self.first_env_index, int(step_index), self._stream()), self._h)
         if check:
@@ -387,11 +393,10 @@ class BatchedPlacementEnv:
         return out, log_prob, entropy
 
     def _check_eval_args(self, logits, mask_bits, actions):
-        """Shapes, dtypes and devices of an evaluate_logits call -> (num_rows, flat)."""
+        """Shapes, dtypes and devices of an evaluate_logits call -> (num_rows, flat, logits dtype code)."""
         cfg = self.cfg
         A, H, WW = cfg.num_orientations * cfg.height * cfg.width, cfg.height, (cfg.width + 63) // 64
-        if not isinstance(logits, torch.Tensor) or logits.dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError("logits must be a float32 or bfloat16 tensor")
+        dtype = _logits_dtype(logits)
         if logits.dim() != 2 or logits.shape[1] != A:
             raise ValueError(f"logits must have shape [N, {A}], got {list(logits.shape)}")
         N = logits.shape[0]
@@ -404,7 +409,7 @@ class BatchedPlacementEnv:
                 raise ValueError(f"{name} must be on {self.device}, got {t.device}")
             if not t.is_contiguous():
                 raise ValueError(f"{name} must be C-contiguous (no copy is made)")
-        return N, actions.dim() == 1
+        return N, actions.dim() == 1, dtype
 
     def evaluate_logits_forward(self, logits, mask_bits, actions, stats: Optional[torch.Tensor] = None,
                                 errors: Optional[torch.Tensor] = None):
@@ -412,14 +417,13 @@ class BatchedPlacementEnv:
         masked categorical of `logits` [N, A] with the legal sets `mask_bits` [N, 2, H, WW] (what `mask_bits()` returned
         when the rows were stored).  stats: float32 [N, 4] the backward call needs, or None.  errors: int32 [1] the error
         bits are ORed into, or None."""
-        N, flat = self._check_eval_args(logits, mask_bits, actions)
+        N, flat, dtype = self._check_eval_args(logits, mask_bits, actions)
         log_prob = torch.empty(N, dtype=torch.float32, device=logits.device)
         entropy = torch.empty(N, dtype=torch.float32, device=logits.device)
         if N == 0:  # torch gives empty tensors a null pointer
             return log_prob, entropy
         _lib.check(self._L.pcbenv_evaluate_logits(
-            self._h, logits.data_ptr(), _lib.LOGITS_F32 if logits.dtype == torch.float32 else _lib.LOGITS_BF16,
-            mask_bits.data_ptr(), actions.data_ptr(), _lib.ACTION_FLAT if flat else _lib.ACTION_TUPLE, N,
+            self._h, logits.data_ptr(), dtype, mask_bits.data_ptr(), actions.data_ptr(), _lib.ACTION_FLAT if flat else _lib.ACTION_TUPLE, N,
             log_prob.data_ptr(), entropy.data_ptr(), None if stats is None else stats.data_ptr(),
             None if errors is None else errors.data_ptr(), self._stream()), self._h)
         return log_prob, entropy
@@ -429,7 +433,7 @@ class BatchedPlacementEnv:
         """`pcbenv_evaluate_logits_backward`, one kernel launch: the gradient with respect to `logits`, every element
         written (into `out`, or a fresh `torch.empty_like(logits)`).  grad_log_prob / grad_entropy: float32 [N] or None
         (zero)."""
-        N, flat = self._check_eval_args(logits, mask_bits, actions)
+        N, flat, dtype = self._check_eval_args(logits, mask_bits, actions)
         if out is None:
             out = torch.empty_like(logits)
         for name, t, shape in (("stats", stats, (N, 4)), ("grad_log_prob", grad_log_prob, (N,)), ("grad_entropy", grad_entropy, (N,))):
@@ -440,8 +444,7 @@ class BatchedPlacementEnv:
         if N == 0:
             return out
         _lib.check(self._L.pcbenv_evaluate_logits_backward(
-            self._h, logits.data_ptr(), _lib.LOGITS_F32 if logits.dtype == torch.float32 else _lib.LOGITS_BF16,
-            mask_bits.data_ptr(), actions.data_ptr(), _lib.ACTION_FLAT if flat else _lib.ACTION_TUPLE, N,
+            self._h, logits.data_ptr(), dtype, mask_bits.data_ptr(), actions.data_ptr(), _lib.ACTION_FLAT if flat else _lib.ACTION_TUPLE, N,
             None if stats is None else stats.data_ptr(), None if grad_log_prob is None else grad_log_prob.data_ptr(),
             None if grad_entropy is None else grad_entropy.data_ptr(), out.data_ptr(), self._stream()), self._h)
         return out
