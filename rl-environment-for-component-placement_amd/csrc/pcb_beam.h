@@ -1,5 +1,5 @@
 // pcb_beam.h -- beam-search routes with the model of CPython's set iteration order
-// Part of libpcbenv.so's single translation unit (included by pcbenv_kernels.hip); CDNA4 / gfx950 only.
+// Included by pcb_team.h inside Team<>, so by every unit that includes pcb_kernels.h (pcb_kind_*.hip, pcbenv_api.hip); CDNA4 / gfx950 only.
 
 // ---- beam-search routing (S:1273-1286 pin_outlier, S:1303-1369 beam_search, S:1371-1406) -----------------
 // beam_search keeps, per popped path, the beam_width nearest unvisited points of

@@ -1,5 +1,5 @@
 // pcb_device.h -- device-side parameter block, state-block records, LDS barrier, bit rows, 16-byte plane emission, wave scan
-// Part of libpcbenv.so's single translation unit (included by pcbenv_kernels.hip); CDNA4 / gfx950 only.
+// Included by every unit of libpcbenv.so that launches or defines a kernel (through pcb_launch.h, pcb_team.h or pcb_host.h); CDNA4 / gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -44,7 +44,7 @@ struct DevParams {
     int num_slots, slot;
     // on-device instance generator (pcb_geninst.h), null when the host feeds the queue: records generated so far per
     // environment, and a sticky error word a reset raises if it ever finds its record missing (it never should:
-    // the host-side bookkeeping of pcbenv_kernels.hip orders every fill before the launches that can consume it)
+    // the host-side bookkeeping of pcb_gen.hip orders every fill before the launches that can consume it)
     unsigned *gen_produced, *gen_errors;
     // Queue cursor of every environment, published with agent-scope (write-through) stores at each reset.  The copy
     // in the state block is written back lazily and only ever re-read on the environment's own XCD; a kernel on

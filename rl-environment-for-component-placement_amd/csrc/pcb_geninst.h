@@ -1,5 +1,5 @@
 // pcb_geninst.h -- on-device instance generator: the reference's generate_instances() as a kernel, one lane per stream
-// Part of libpcbenv.so's single translation unit (included by pcbenv_kernels.hip); CDNA4 / gfx950 only.
+// Included by pcb_gen.hip, the one unit of libpcbenv.so that compiles it (and by tools/gen_harness.hip); CDNA4 / gfx950 only.
 //
 // The reference draws a fresh placement problem at EVERY reset (S:1487-1549 -> generate_instances S:960-989 and
 // helpers :931-1212, :1408-1443, sample_truncated_multinomial :250-287; P:1006-1265; R:253-273) from the global

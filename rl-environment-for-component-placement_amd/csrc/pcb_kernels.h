@@ -169,7 +169,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(4, 8))) __launch_bounds__(64 * NW)
                                                            num_steps, role, part, pos);
 }
 
-#ifdef PCB_HOST_TU  // plain (non-template) kernels: defined once, in pcbenv_kernels.hip
+#ifdef PCB_HOST_TU  // plain (non-template) kernels: defined once, in pcbenv_api.hip
 __global__ __launch_bounds__(WAVE) void k_sample(DevParams p, int *__restrict__ actions, int fmt, u64 seed,
                                                  u64 first_env, u64 step_index) {
     const int e = blockIdx.x, lane = threadIdx.x;

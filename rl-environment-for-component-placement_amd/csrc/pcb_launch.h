@@ -1,4 +1,4 @@
-// pcb_launch.h -- what the host side (pcbenv_kernels.hip) and the per-kind kernel translation units (pcb_kind_*.hip)
+// pcb_launch.h -- what the host side (pcbenv_api.hip) and the per-kind kernel translation units (pcb_kind_*.hip)
 // share: one launch entry per environment kind, so that the kernel instantiations of the four kinds compile in parallel.
 #pragma once
 #include "pcb_device.h"

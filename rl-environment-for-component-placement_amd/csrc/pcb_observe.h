@@ -1,5 +1,5 @@
 // pcb_observe.h -- state block staging through LDS, legal-mask fold + observation emission, pin_grid, feature rows, terminal reward
-// Part of libpcbenv.so's single translation unit (included by pcbenv_kernels.hip); CDNA4 / gfx950 only.
+// Included by pcb_team.h inside Team<>, so by every unit that includes pcb_kernels.h (pcb_kind_*.hip, pcbenv_api.hip); CDNA4 / gfx950 only.
 
 // ----------------------------------------------------------------------------------------------
 // shared pieces of reset / step

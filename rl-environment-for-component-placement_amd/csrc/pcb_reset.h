@@ -1,5 +1,5 @@
 // pcb_reset.h -- reset of one environment from the instance queue (k_reset and the in-launch reset of k_step)
-// Part of libpcbenv.so's single translation unit (included by pcbenv_kernels.hip); CDNA4 / gfx950 only.
+// Included by pcb_team.h inside Team<>, so by every unit that includes pcb_kernels.h (pcb_kind_*.hip, pcbenv_api.hip); CDNA4 / gfx950 only.
 
 // ----------------------------------------------------------------------------------------------
 // reset (R:310-351, P:1544-1597, S:1487-1549, Q:74-113): header is in LDS; builds the new episode's state in

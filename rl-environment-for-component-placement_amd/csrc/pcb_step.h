@@ -1,5 +1,5 @@
 // pcb_step.h -- the step kernel (transition, mask, observations, terminal reward, optional reset and next-action draw) and the queue-cursor reduction
-// Part of libpcbenv.so's single translation unit (included by pcbenv_kernels.hip); CDNA4 / gfx950 only.
+// Included by pcb_team.h inside Team<>, so by every unit that includes pcb_kernels.h (pcb_kind_*.hip, pcbenv_api.hip); CDNA4 / gfx950 only.
 
 // ----------------------------------------------------------------------------------------------
 // step kernel (R:353-432, P:1599-1710, S:1551-1661, Q:115-153)

@@ -3,7 +3,7 @@
 //
 // A team is the set of threads that work on one environment: one wavefront (TN = 64) for grids up to 64 x 64, four
 // (TN = 256) for the 128 x 128 spatial configuration -- and, since round 3, four for the environments of a launch that
-// are certain to end their episode in it, next to one-wavefront teams for the others in the same kernel (k_step_mixed).
+// are certain to end their episode in it, next to one-wavefront teams for the others in the same kernel (see Team<>::run_env).
 // The team size decides the lane stride of every loop, whether a phase boundary needs an s_barrier (a one-wavefront
 // team's LDS traffic executes in program order) and how work is dealt to wavefronts, so it is a compile-time
 // property: the sections below are textually included inside the class template, where NT is TN.  They hold the

@@ -4,7 +4,7 @@
 // (s_waitcnt vmcnt(0)), which would serialise the observation write stream between kernel phases.
 // A team of ONE wavefront needs no s_barrier: its LDS traffic executes in program order, only the compiler (and the
 // lgkmcnt wait the fence emits) stand between a write and a read of another lane -- and it MUST not execute one when
-// four independent one-wavefront teams share a workgroup (k_step_mixed), where their barrier counts differ.
+// four independent one-wavefront teams share a workgroup (see Team<>::run_env), where their barrier counts differ.
 static __device__ inline void lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
     if (NT > WAVE) __builtin_amdgcn_s_barrier(); else __builtin_amdgcn_wave_barrier();

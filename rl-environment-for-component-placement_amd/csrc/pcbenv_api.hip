@@ -1,0 +1,607 @@
+// pcbenv_api.hip -- host side of libpcbenv.so's C ABI (include/pcbenv.h): create / destroy / options / bind / load,
+// reset / step / rollout / sample, checkpoint, gather and the logits entry points, plus the two plain kernels k_sample
+// and k_cursor_range.  The environment kernels are instantiated per kind in pcb_kind_*.hip and the policy kernels in
+// pcb_policy*.hip (both reached through pcb_launch.h); pcb_config.hip derives the layout from a configuration and
+// pcb_gen.hip owns the on-device instance generator (pcb_host.h declares what the three share).
+//
+// Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (one IEEE operation per
+// written operator; the only fused multiply-add is the explicit __fma_rn in norm2).
+#include <stdlib.h>
+
+#include <vector>
+
+#include "pcb_host.h"
+#define PCB_HOST_TU
+#include "pcb_kernels.h"  // k_sample, k_cursor_range (the per-kind kernels are instantiated in pcb_kind_*.hip)
+#include "pcb_launch.h"
+
+static char g_err[256] = "";
+int fail(pcbenv *env, int code, const char *fmt, const char *detail) {
+    char *dst = env ? env->err : g_err;
+    snprintf(dst, 256, fmt, detail);
+    if (env) snprintf(g_err, 256, "%s", dst);
+    return code;
+}
+
+extern "C" int pcbenv_abi_version(void) { return PCBENV_ABI_VERSION; }
+
+extern "C" const char *pcbenv_last_error(const pcbenv *env) { return env ? env->err : g_err; }
+
+// The launch functions of an environment kind (pcb_kind_*.hip), indexed by pcbenv_config::kind.
+struct KindLaunch {
+    int (*step)(const StepLaunch &);
+    int (*reset)(const ResetLaunch &);
+    int (*gather)(const GatherLaunch &);
+};
+#define PCB_KIND_LAUNCH(name) {pcb_launch_step_##name, pcb_launch_reset_##name, pcb_launch_gather_##name}
+static const KindLaunch kind_launch[] = {PCB_KIND_LAUNCH(square), PCB_KIND_LAUNCH(rect), PCB_KIND_LAUNCH(pin), PCB_KIND_LAUNCH(spatial)};
+static_assert(PCBENV_SQUARE == 0 && PCBENV_RECT == 1 && PCBENV_PIN == 2 && PCBENV_SPATIAL == 3, "kind_launch is indexed by kind");
+
+// validate, derive, allocate, zero
+extern "C" int pcbenv_create(const pcbenv_config *cfg, int device, pcbenv **out) {
+    if (out) *out = 0;
+    if (!cfg || !out) return fail(0, PCBENV_EINVAL, "null argument");
+    int rc = validate(cfg);
+    if (rc != PCBENV_OK) return rc;
+    pcbenv *env = new pcbenv();
+    memset(env, 0, sizeof(*env));
+    env->cfg = *cfg;
+    env->device = device;
+    if (is_pin_kind(cfg->kind)) {  // P:467-468 / S:450-451: clipped after validation
+        env->cfg.net_distribution = cfg->net_distribution < 0 ? 0 : cfg->net_distribution > 9 ? 9 : cfg->net_distribution;
+        env->cfg.pin_spread = cfg->pin_spread < 0 ? 0 : cfg->pin_spread > 9 ? 9 : cfg->pin_spread;
+    }
+    derive_layout(env->cfg, env);
+    DevParams &d = env->dp;
+    DeviceGuard guard_(device);
+    if (!guard_.ok) { int r = fail(0, PCBENV_EHIP, "hipSetDevice failed (no such device?)"); delete env; return r; }
+    const size_t sbytes = (size_t)d.stateStride * d.B, qbytes = (size_t)d.instStride * d.B * d.Q;
+    const struct { void **ptr; size_t bytes; } zeroed[] = {
+        {(void **)&env->state_buf[0], sbytes}, {(void **)&env->state_buf[1], sbytes}, {(void **)&d.queue, qbytes ? qbytes : 16},
+        {(void **)&d.cursor_pub, 4 * (size_t)d.B}, {(void **)&d.term_list, TERM_LIST_BYTES}, {(void **)&d.term_cnt, TERM_CNT_BYTES},
+        {(void **)&d.term_arrive, TERM_ARRIVE_BYTES}};
+    const char *what = 0;
+    for (const auto &z : zeroed) {
+        if (!what && hipMalloc(z.ptr, z.bytes) != hipSuccess) what = "hipMalloc failed";
+        if (!what && hipMemset(*z.ptr, 0, z.bytes) != hipSuccess) what = "hipMemset failed";
+    }
+    if (!what && (hipHostMalloc((void **)&env->term_seen_host, 64, hipHostMallocMapped) != hipSuccess ||
+                  hipHostGetDevicePointer((void **)&d.term_seen, env->term_seen_host, 0) != hipSuccess)) what = "hipMalloc failed";
+    if (!what && hipDeviceSynchronize() != hipSuccess) what = "hipMemset failed";
+    if (what) {
+        int r = fail(0, PCBENV_EHIP, what);
+        pcbenv_destroy(env);
+        return r;
+    }
+#ifdef PCBENV_STAMPS
+    { const char *ev = getenv("PCBENV_STAMPS"); if (ev && ev[0] == '1') { hipMalloc((void **)&d.dbg, (size_t)(d.B + PCBENV_TERM_CAP_MAX * (REWARD_PARTS + 1)) * 32 * 8); hipMemset(d.dbg, 0, (size_t)(d.B + PCBENV_TERM_CAP_MAX * (REWARD_PARTS + 1)) * 32 * 8); } }
+#endif
+    env->state_cur = 0;
+    d.state = d.state_out = env->state_buf[0];
+    *env->term_seen_host = 0u;
+    *out = env;
+    return PCBENV_OK;
+}
+
+// Releases whatever the handle holds: create zero-fills it, so a pointer, stream or event is either null or owned.
+extern "C" void pcbenv_destroy(pcbenv *env) {
+    if (!env) return;
+    DeviceGuard guard_(env->device);
+    gen_release(env);
+    if (env->state_buf[0]) hipFree(env->state_buf[0]);
+    if (env->state_buf[1]) hipFree(env->state_buf[1]);
+    if (env->dp.queue) hipFree(env->dp.queue);
+    if (env->dp.cursor_pub) hipFree(env->dp.cursor_pub);
+    if (env->dp.term_list) hipFree(env->dp.term_list);
+    if (env->dp.term_cnt) hipFree(env->dp.term_cnt);
+    if (env->dp.term_arrive) hipFree(env->dp.term_arrive);
+    if (env->dp.feat_cache) hipFree(env->dp.feat_cache);
+    if (env->dp.feat_cache_tag) hipFree(env->dp.feat_cache_tag);
+    if (env->term_seen_host) hipHostFree(env->term_seen_host);
+    if (env->scratch) hipFree(env->scratch);
+    if (env->gather_snap) hipFree(env->gather_snap);
+    delete env;
+}
+
+extern "C" int pcbenv_set_option(pcbenv *env, int32_t option, int64_t value) {
+    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
+    switch (option) {
+    case PCBENV_OPT_STREAM_THRESHOLD_BYTES:
+        if (value < 0) return fail(env, PCBENV_EINVAL, "threshold must not be negative");
+        env->stream_threshold = value;
+        env->dp.stream_stores = stream_stores(env, 1);
+        return PCBENV_OK;
+    case PCBENV_OPT_TERMINAL_TEAMS:
+        if (value < 0 || value > PCBENV_TERM_CAP_MAX) return fail(env, PCBENV_EINVAL, "terminal-list entries must be in [0, 4096]");
+        if (value > 0 && !is_pin_kind(env->cfg.kind))
+            return fail(env, PCBENV_EINVAL, "reward helpers need an environment kind with a routing reward");
+        value = (value + TERM_SHARDS - 1) & ~(long long)(TERM_SHARDS - 1);
+        {   // The lists built so far were laid out for the old capacity: drop them (counters to zero once everything enqueued
+            // has run; no mark matches the next launch's number).  A rare call: it may synchronise.
+            DEVICE_GUARD(env);
+            HIP_TRY(env, hipDeviceSynchronize());
+            HIP_TRY(env, hipMemset(env->dp.term_cnt, 0, TERM_CNT_BYTES));
+            *env->term_seen_host = 0u;
+        }
+        env->term_wgs = (int)value;
+        env->dp.term_cap = (int)value;
+        env->seq += 2;
+        return PCBENV_OK;
+    case PCBENV_OPT_GEN_GRID:
+        if (value < 1) return fail(env, PCBENV_EINVAL, "generator grid must be at least 1");
+        env->gen_grid = (int)value;
+        return PCBENV_OK;
+    case PCBENV_OPT_GEN_LANES:
+        if (env->gen_on) return fail(env, PCBENV_ESTATE, "set the generator's group width before enabling it");
+        if (value != 0 && value != 16 && value != 32 && value != 64) return fail(env, PCBENV_EINVAL, "generator lanes per environment: 0, 16, 32 or 64");
+        env->gen_lanes = (int)value;
+        return PCBENV_OK;
+    }
+    return fail(env, PCBENV_EINVAL, "unknown option");
+}
+
+extern "C" int pcbenv_bind_buffers_slots(pcbenv *env, const pcbenv_buffers *b, int32_t num_slots);
+extern "C" int pcbenv_bind_buffers(pcbenv *env, const pcbenv_buffers *b) { return pcbenv_bind_buffers_slots(env, b, 1); }
+
+extern "C" int pcbenv_select_slot(pcbenv *env, int32_t slot) {
+    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
+    if (slot < 0 || slot >= env->dp.num_slots) return fail(env, PCBENV_EINVAL, "slot out of range");
+    env->dp.slot = slot;
+    return PCBENV_OK;
+}
+
+extern "C" int pcbenv_bind_buffers_slots(pcbenv *env, const pcbenv_buffers *b, int32_t num_slots) {
+    if (!env || !b) return fail(env, PCBENV_EINVAL, "null argument");
+    if (num_slots < 1 || num_slots > 4096) return fail(env, PCBENV_EINVAL, "num_slots must be in [1, 4096]");
+    if (num_slots > 1 && (env->cfg.flags & PCBENV_FLAG_INCREMENTAL_OBS))
+        return fail(env, PCBENV_EINVAL, "PCBENV_FLAG_INCREMENTAL_OBS needs the in-place layout (num_slots = 1)");
+    if ((long long)num_slots * env->dp.B > 0x7fffffffll / 8) return fail(env, PCBENV_ELIMIT, "num_slots * num_envs too large");
+    if (!b->reward || !b->done) return fail(env, PCBENV_EINVAL, "reward and done buffers are required");
+    // Everything that can fail comes first: a refused bind leaves the previous binding as it was.
+    DEVICE_GUARD(env);
+    DevParams &d = env->dp;
+    const int k = env->cfg.kind;
+    if (k == PCBENV_SPATIAL && num_slots > 1 && !d.feat_cache) {  // the episode-constant bytes a trajectory step copies
+        const int cg = align16(2ll * d.C * d.F), stride = align16((long long)cg + (long long)d.C * d.mh * d.mw * d.K);
+        if (hipMalloc((void **)&d.feat_cache, (size_t)stride * d.B) != hipSuccess || hipMalloc((void **)&d.feat_cache_tag, 4 * (size_t)d.B) != hipSuccess) {
+            if (d.feat_cache) hipFree(d.feat_cache);  // both or neither: the next bind tries again
+            d.feat_cache = 0; d.feat_cache_tag = 0;
+            return fail(env, PCBENV_EHIP, "hipMalloc failed");
+        }
+        d.featCacheCg = cg; d.featCacheStride = stride;
+    }
+    // pcbenv_gather's snapshot (25 bytes per environment), allocated here and not per call
+    if (!env->gather_snap && hipMalloc((void **)&env->gather_snap, 25 * (size_t)d.B) != hipSuccess) {
+        env->gather_snap = 0;
+        return fail(env, PCBENV_EHIP, "hipMalloc failed");
+    }
+    if (d.feat_cache_tag) hipMemset(d.feat_cache_tag, 0xFF, 4 * (size_t)d.B);  // no episode has that number: nothing cached yet
+    d.num_slots = num_slots; d.slot = 0;
+    d.buf = *b;
+    if (k != PCBENV_SPATIAL) { d.buf.pin_grid = 0; d.buf.component_grid = 0; }
+    if (!is_pin_kind(k)) { d.buf.all_pins_num_feature = 0; d.buf.all_pins_cat_feature = 0; d.buf.info = 0; }
+    if (k != PCBENV_RECT) d.buf.component_mask = 0;
+    if (k == PCBENV_SQUARE) { d.buf.all_components_feature = 0; d.buf.placement_mask = 0; }
+    d.bind_gen += 1;  // feature tensors of these buffers are uninitialised: the next reset of each env fills them
+    memset(&d.cbuf, 0, sizeof(d.cbuf));  // compact tensors belong to a binding: bind them again
+    env->bound = true;
+    return PCBENV_OK;
+}
+
+extern "C" int pcbenv_bind_compact_features(pcbenv *env, const pcbenv_compact_features *f) {
+    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
+    if (!env->bound) return fail(env, PCBENV_ESTATE, "pcbenv_bind_buffers has not been called");
+    memset(&env->dp.cbuf, 0, sizeof(env->dp.cbuf));
+    if (!f) return PCBENV_OK;
+    if (env->dp.num_slots < 2) return fail(env, PCBENV_EINVAL, "compact feature tensors need the trajectory layout (pcbenv_bind_buffers_slots with num_slots > 1)");
+    if (env->dp.H > 128 || env->dp.W > 128) return fail(env, PCBENV_ELIMIT, "coordinates do not fit the compact pin tensors");
+    env->dp.cbuf = *f;
+    const int k = env->cfg.kind;
+    if (!is_pin_kind(k)) { env->dp.cbuf.all_pins_num_feature = 0; env->dp.cbuf.all_pins_cat_feature = 0; }
+    if (k != PCBENV_RECT) env->dp.cbuf.component_mask = 0;
+    if (k == PCBENV_SQUARE) memset(&env->dp.cbuf, 0, sizeof(env->dp.cbuf));
+    return PCBENV_OK;
+}
+
+extern "C" int pcbenv_load_instances(pcbenv *env, const int32_t *env_ids, int32_t n, int32_t slot,
+                                     const void *host_tables, void *stream) {
+    if (!env || !host_tables) return fail(env, PCBENV_EINVAL, "null argument");
+    const DevParams &d = env->dp;
+    if (env->cfg.kind == PCBENV_SQUARE) return PCBENV_OK;  // the square env has no instance
+    // refused before anything is copied: the generator owns the records, and k_gen_fill may be writing this very slot
+    if (env->gen_on) return fail(env, PCBENV_ESTATE, "the on-device generator owns the queue (pcbenv_instgen_device_enable)");
+    if (slot < 0 || slot >= d.Q || n < 0 || n > d.B) return fail(env, PCBENV_EINVAL, "slot or count out of range");
+    DEVICE_GUARD(env);
+    int rc = check_records(env, host_tables, n);
+    if (rc != PCBENV_OK) return rc;
+    const long long src_stride = pcbenv_instance_stride(&env->cfg);
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned char *src = (const unsigned char *)host_tables;
+    unsigned char *base = d.queue + (size_t)slot * d.B * d.instStride;
+    if (!env_ids && src_stride == d.instStride) {
+        HIP_TRY(env, hipMemcpyAsync(base, src, (size_t)n * src_stride, hipMemcpyHostToDevice, s));
+    } else {
+        for (int i = 0; i < n; i++) {
+            int id = env_ids ? env_ids[i] : i;
+            if (id < 0 || id >= d.B) return fail(env, PCBENV_EINVAL, "environment id out of range");
+            HIP_TRY(env, hipMemcpyAsync(base + (size_t)id * d.instStride, src + (size_t)i * src_stride, (size_t)src_stride, hipMemcpyHostToDevice, s));
+        }
+    }
+    HIP_TRY(env, hipStreamSynchronize(s));
+    if (!env_ids && n == d.B) env->loaded_slots[slot >> 6] |= 1ull << (slot & 63);  // partial loads: caller's responsibility
+    return PCBENV_OK;
+}
+
+static int launch_reset(pcbenv *env, const uint8_t *mask, hipStream_t s) {
+    ResetLaunch a{env->dp, mask, env->threads, s};
+    a.d.seq = env->seq;  // the next step launch is seq + 1: a reset takes its environments off that launch's terminal list
+    return kind_launch[env->cfg.kind].reset(a);
+}
+// Every step launch has a number (DevParams::seq); see Team<>::run_env for what the terminal list is.
+static int dispatch_step(pcbenv *env, int *actions, int fmt, int sampled, u64 seed, u64 first_env, u64 step_index, int num_steps, hipStream_t s) {
+    StepLaunch a;
+    a.d = env->dp;
+    DevParams &d = a.d;
+    a.actions = actions; a.fmt = fmt; a.sampled = sampled; a.seed = seed; a.first_env = first_env; a.step_index = step_index;
+    a.num_steps = num_steps; a.threads = env->threads; a.stream = s;
+    // in-place build (one transition, store policy compiled in) or the trajectory layout's: one transition into a slot / the rollout loop
+    a.traj = d.num_slots > 1 || num_steps > 1;
+    // The trajectory layout cycles through num_slots slots: the store policy is chosen on the bytes of all of them (a slot is
+    // next written num_slots steps later; one launch per step into a [17, B, ...] trajectory measured + 14 % at c3, + 3 % at
+    // c4 with streaming stores).  In place, the steps overwrite the same lines and the per-transition choice of
+    // pcbenv_create stands.
+    if (a.traj && d.num_slots > 1) d.stream_stores = stream_stores(env, d.num_slots);
+    a.routes = is_pin_kind(env->cfg.kind) && env->cfg.reward_type != PCBENV_REWARD_CENTROID;
+    if (++env->seq == 0u) env->seq = 1u;  // 0 is "not listed" in the marks
+    d.seq = env->seq;
+    // A launch that is being captured into a hipGraph will be replayed with these very arguments: no launch number,
+    // no buffer swap -- it runs without helpers, keeps no list and works on the state blocks in place.
+    const bool capturing = stream_capturing(s);
+    d.term_wgs = 0;
+    if (num_steps == 1 && !capturing && env->term_wgs > 0) {  // reward helpers: one transition per launch only
+        // as many entries' helpers as the lists have lately been long (k_step reports it: + 25 %, + 2 per shard; never none:
+        // a shard's first entry)
+        const unsigned seen = *(volatile unsigned *)env->term_seen_host;
+        const long long want = (long long)TERM_SHARDS * ((long long)seen + seen / 4 + 2);
+        d.term_wgs = (int)(want < env->term_wgs ? want : env->term_wgs);
+    }
+    if (capturing) d.term_cap = 0;
+    // double-buffered state blocks: read the current ones, write the others
+    d.state = env->state_buf[env->state_cur];
+    d.state_out = env->state_buf[env->state_cur ^ (capturing ? 0 : 1)];
+    const int rc = kind_launch[env->cfg.kind].step(a);
+    if (!capturing) env->state_cur ^= 1;
+    env->dp.state = env->dp.state_out = env->state_buf[env->state_cur];  // what k_reset / k_sample / get_state work on, in place
+    return rc;
+}
+
+static int check_queue(pcbenv *env) {
+    if (env->cfg.kind == PCBENV_SQUARE || env->gen_on) return PCBENV_OK;
+    for (int s = 0; s < env->dp.Q; s++)
+        if (!(env->loaded_slots[s >> 6] >> (s & 63) & 1ull))
+            return fail(env, PCBENV_ESTATE, "every queue slot must be loaded (pcbenv_load_instances for all environments) first");
+    return PCBENV_OK;
+}
+
+// The one path of every launch that may consume instance records (pcb_gen.hip has the protocol).  `checks` holds the entry
+// point's own argument checks and says what it is going to launch; it runs on the handle's device, before anything of
+// the generator is touched.
+struct LaunchPlan {
+    int consumes = 0;  // records per environment one launch may consume
+    int launches = 1;
+};
+template <class Checks, class Launch>
+static int consuming_launch(pcbenv *env, void *stream, Checks checks, Launch launch) {
+    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
+    if (!env->bound) return fail(env, PCBENV_ESTATE, "pcbenv_bind_buffers has not been called");
+    DEVICE_GUARD(env);
+    LaunchPlan plan;
+    int rc = checks(plan);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    for (int t = 0; t < plan.launches; t++) {
+        rc = gen_before_launch(env, plan.consumes, s);
+        if (rc) return rc;
+        launch(t, s);
+        if (t == plan.launches - 1) HIP_TRY(env, hipGetLastError());
+        gen_after_launch(env, plan.consumes, s);
+    }
+    return PCBENV_OK;
+}
+// one transition per launch: a record per environment at most, and only where episodes restart in the launch
+static int step_consumes(const pcbenv *env) { return (env->cfg.flags & PCBENV_FLAG_AUTO_RESET) ? 1 : 0; }
+static int step_checks(pcbenv *env, const void *actions_dev, int fmt, LaunchPlan &plan) {
+    if (!actions_dev) return fail(env, PCBENV_EINVAL, "null actions");
+    CHECK_ACTION_FORMAT(env, fmt);
+    plan.consumes = step_consumes(env);
+    return PCBENV_OK;
+}
+
+extern "C" int pcbenv_reset(pcbenv *env, const uint8_t *mask_dev, void *stream) {
+    return consuming_launch(
+        env, stream, [&](LaunchPlan &plan) { plan.consumes = 1; return check_queue(env); },
+        [&](int, hipStream_t s) { launch_reset(env, mask_dev, s); });
+}
+
+extern "C" int pcbenv_get_instances(pcbenv *env, int32_t slot, void *host_dst, void *stream) {
+    if (!env || !host_dst) return fail(env, PCBENV_EINVAL, "null argument");
+    if (slot < 0 || slot >= env->dp.Q) return fail(env, PCBENV_EINVAL, "slot out of range");
+    DEVICE_GUARD(env);
+    const DevParams &d = env->dp;
+    const long long dst_stride = pcbenv_instance_stride(&env->cfg);
+    // the copy runs on the stream that last wrote the queue (the generator's, if it is on): in order behind its kernels
+    hipStream_t s = env->gen_on ? env->gen_stream : (hipStream_t)stream;
+    HIP_TRY(env, hipStreamSynchronize((hipStream_t)stream));
+    HIP_TRY(env, hipMemcpy2DAsync(host_dst, (size_t)dst_stride, d.queue + (size_t)slot * d.B * d.instStride, (size_t)d.instStride,
+                                  (size_t)dst_stride, (size_t)d.B, hipMemcpyDeviceToHost, s));
+    HIP_TRY(env, hipStreamSynchronize(s));
+    return PCBENV_OK;
+}
+
+extern "C" int pcbenv_step(pcbenv *env, const int32_t *actions_dev, int32_t fmt, void *stream) {
+    return consuming_launch(
+        env, stream, [&](LaunchPlan &plan) { return step_checks(env, actions_dev, fmt, plan); },
+        [&](int, hipStream_t s) { dispatch_step(env, (int *)actions_dev, fmt, 0, 0, 0, 0, 1, s); });
+}
+
+extern "C" int pcbenv_step_sampled(pcbenv *env, int32_t *actions_out_dev, int32_t fmt, uint64_t seed,
+                                   uint64_t first_env_index, uint64_t step_index, void *stream) {
+    return consuming_launch(
+        env, stream, [&](LaunchPlan &plan) { return step_checks(env, actions_out_dev, fmt, plan); },
+        [&](int, hipStream_t s) { dispatch_step(env, actions_out_dev, fmt, 1, seed, first_env_index, step_index, 1, s); });
+}
+
+// num_steps transitions: one launch of the persistent rollout kernel, every step of which may end an episode, or, with the
+// row-incremental tensors, one launch per step as before
+extern "C" int pcbenv_rollout_sampled(pcbenv *env, int32_t *actions_out_dev, int32_t fmt, int32_t num_steps,
+                                      uint64_t seed, uint64_t first_env_index, uint64_t step_index0, void *stream) {
+    bool per_step = false;
+    return consuming_launch(
+        env, stream,
+        [&](LaunchPlan &plan) -> int {
+            if (!actions_out_dev || num_steps < 0) return fail(env, PCBENV_EINVAL, "bad rollout arguments");
+            CHECK_ACTION_FORMAT(env, fmt);
+            per_step = (env->cfg.flags & PCBENV_FLAG_INCREMENTAL_OBS) != 0;
+            plan.launches = per_step ? num_steps : num_steps > 0;
+            plan.consumes = step_consumes(env) * (per_step ? 1 : num_steps);
+            return PCBENV_OK;
+        },
+        [&](int t, hipStream_t s) {
+            if (!per_step) { dispatch_step(env, actions_out_dev, fmt, 1, seed, first_env_index, step_index0, num_steps, s); return; }
+            const size_t actions_per_step = (size_t)env->dp.B * (fmt == PCBENV_ACTION_TUPLE ? 3 : 1);
+            dispatch_step(env, actions_out_dev + actions_per_step * (size_t)t, fmt, 1, seed, first_env_index, step_index0 + (uint64_t)t, 1, s);
+        });
+}
+
+extern "C" int pcbenv_sample_actions(pcbenv *env, int32_t *actions_dev, int32_t fmt, uint64_t seed,
+                                     uint64_t first_env_index, uint64_t step_index, void *stream) {
+    if (!env || !actions_dev) return fail(env, PCBENV_EINVAL, "null argument");
+    CHECK_ACTION_FORMAT(env, fmt);
+    DEVICE_GUARD(env);
+    hipLaunchKernelGGL(k_sample, dim3(env->dp.B), dim3(WAVE), 0, (hipStream_t)stream, env->dp, actions_dev, fmt,
+                       (u64)seed, (u64)first_env_index, (u64)step_index);
+    HIP_TRY(env, hipGetLastError());
+    return PCBENV_OK;
+}
+
+extern "C" const uint64_t *pcbenv_mask_bits(const pcbenv *env, int64_t *env_stride_bytes) {
+    if (!env) return 0;
+    if (env_stride_bytes) *env_stride_bytes = env->dp.stateStride;
+    return (const uint64_t *)(env->dp.state + env->dp.offVm);
+}
+
+// Checkpoint layout: [state blocks, B x stateStride] and, once the on-device generator is enabled, its section behind
+// them (gen_section_bytes).
+static size_t state_section_bytes(const pcbenv *env) { return (size_t)env->dp.stateStride * env->dp.B; }
+extern "C" int64_t pcbenv_state_bytes(const pcbenv *env) {
+    return env ? (int64_t)(state_section_bytes(env) + gen_section_bytes(env)) : 0;
+}
+extern "C" int pcbenv_get_state(pcbenv *env, void *host_dst, void *stream) {
+    if (!env || !host_dst) return fail(env, PCBENV_EINVAL, "null argument");
+    DEVICE_GUARD(env);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t sb = state_section_bytes(env);
+    unsigned char *dst = (unsigned char *)host_dst;
+    HIP_TRY(env, hipMemcpyAsync(dst, env->dp.state, sb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(env, hipStreamSynchronize(s));
+    return gen_save(env, dst + sb, s);
+}
+extern "C" int pcbenv_set_state(pcbenv *env, const void *host_src, void *stream) {
+    if (!env || !host_src) return fail(env, PCBENV_EINVAL, "null argument");
+    DEVICE_GUARD(env);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t sb = state_section_bytes(env), B = (size_t)env->dp.B;
+    // The terminal-list marks in a checkpoint refer to lists of the run that wrote it: restored environments are not listed.
+    std::vector<unsigned char> blob((const unsigned char *)host_src, (const unsigned char *)host_src + sb);
+    std::vector<unsigned> cur(B);  // the published copy of the queue cursors follows the restored headers
+    for (size_t i = 0; i < B; i++) {
+        EnvHdr *hd = (EnvHdr *)(blob.data() + i * env->dp.stateStride);
+        hd->term_seq = 0u;
+        cur[i] = hd->qcursor;
+    }
+    if (env->gen_on) {  // nothing of the generator may be in flight while its state is replaced
+        HIP_TRY(env, hipStreamSynchronize(s));
+        HIP_TRY(env, hipStreamSynchronize(env->gen_stream));
+    }
+    HIP_TRY(env, hipMemcpyAsync(env->dp.state, blob.data(), sb, hipMemcpyHostToDevice, s));
+    HIP_TRY(env, hipMemcpyAsync(env->dp.cursor_pub, cur.data(), 4 * B, hipMemcpyHostToDevice, s));
+    if (env->dp.feat_cache_tag) HIP_TRY(env, hipMemsetAsync(env->dp.feat_cache_tag, 0xFF, 4 * B, s));  // the cached bytes are another episode's
+    const int rc = gen_restore(env, (const unsigned char *)host_src + sb, s);
+    if (rc != PCBENV_OK) return rc;
+    HIP_TRY(env, hipStreamSynchronize(s));
+    return PCBENV_OK;
+}
+
+// ---- pcbenv_gather ------------------------------------------------------------------------------------------
+// The environment definition is every pcbenv_config field from kind through weight_num_intersections.
+static_assert(offsetof(pcbenv_config, weight_num_intersections) + sizeof(double) == offsetof(pcbenv_config, num_envs),
+              "the definition fields end where the batch fields begin");
+extern "C" int pcbenv_gather(pcbenv *dst, const pcbenv *src, const int32_t *src_index_dev, uint32_t *errors_dev, void *stream) {
+    if (!dst) return fail(0, PCBENV_EINVAL, "null handle");
+    if (!src) src = dst;
+    if (!src_index_dev) return fail(dst, PCBENV_EINVAL, "null src_index");
+    if (src != dst) {
+        if (src->device != dst->device) return fail(dst, PCBENV_EINVAL, "the two handles are on different devices");
+        if (memcmp(&src->cfg, &dst->cfg, offsetof(pcbenv_config, num_envs)) != 0)
+            return fail(dst, PCBENV_EINVAL, "the two handles have different environment definitions");
+    }
+    if (!dst->bound || !src->bound) return fail(dst, PCBENV_ESTATE, "pcbenv_bind_buffers has not been called");
+    DEVICE_GUARD(dst);
+    hipStream_t s = (hipStream_t)stream;
+    // A captured launch would be replayed with the state sets of the capture: the second replay would read a stale set.
+    if (stream_capturing(s)) return fail(dst, PCBENV_ESTATE, "pcbenv_gather cannot be captured into a graph");
+    GatherLaunch a;
+    a.d = dst->dp;
+    DevParams &d = a.d;
+    a.threads = dst->threads; a.stream = s;
+    // the store policy a trajectory-layout step launch would use (dispatch_step)
+    if (d.num_slots > 1) d.stream_stores = stream_stores(dst, d.num_slots);
+    d.state = dst->state_buf[dst->state_cur];
+    d.state_out = dst->state_buf[dst->state_cur ^ 1];
+    const DevParams &sp = src->dp;
+    const size_t r0 = (size_t)sp.slot * sp.B;  // first row of the source's selected slot
+    GatherArgs &g = a.g;
+    g.src_state = sp.state; g.src_index = src_index_dev; g.errors = (unsigned *)errors_dev; g.src_B = sp.B;
+    if (src == dst) {
+        // another team may overwrite row j of reward / done / info before the team that reads it runs: read a snapshot
+        const size_t B = (size_t)d.B;
+        unsigned char *snap = dst->gather_snap;
+        HIP_TRY(dst, hipMemcpyAsync(snap, sp.buf.reward + r0, 8 * B, hipMemcpyDeviceToDevice, s));
+        if (sp.buf.info) HIP_TRY(dst, hipMemcpyAsync(snap + 8 * B, sp.buf.info + 2 * r0, 16 * B, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(dst, hipMemcpyAsync(snap + 24 * B, sp.buf.done + r0, B, hipMemcpyDeviceToDevice, s));
+        g.reward = (const double *)snap; g.info = sp.buf.info ? (const double *)(snap + 8 * B) : 0; g.done = snap + 24 * B;
+    } else {
+        g.reward = sp.buf.reward + r0; g.info = sp.buf.info ? sp.buf.info + 2 * r0 : 0; g.done = sp.buf.done + r0;
+    }
+    kind_launch[dst->cfg.kind].gather(a);
+    HIP_TRY(dst, hipGetLastError());
+    dst->state_cur ^= 1;
+    dst->dp.state = dst->dp.state_out = dst->state_buf[dst->state_cur];
+    return PCBENV_OK;
+}
+
+// ---- pcbenv_sample_logits ------------------------------------------------------------------------------------
+// The argument checks come before anything touches a device (a null handle included), so that every one of them can be
+// exercised without a GPU.  Nothing the library owns is written: no state block, presampled action, terminal list or
+// queue, and no generator interaction (nothing is consumed).
+static int logits_elem_bytes(int32_t logits_dtype) { return logits_dtype == PCBENV_LOGITS_F32 ? 4 : 2; }
+// the checks pcbenv_sample_logits and pcbenv_evaluate_logits[_backward] share
+static int logits_checks(pcbenv *env, const void *logits_dev, int32_t logits_dtype, const int32_t *actions_dev, int32_t fmt) {
+    if (!logits_dev) return fail(env, PCBENV_EINVAL, "null logits");
+    if (!actions_dev) return fail(env, PCBENV_EINVAL, "null actions");
+    if (logits_dtype != PCBENV_LOGITS_F32 && logits_dtype != PCBENV_LOGITS_BF16) return fail(env, PCBENV_EINVAL, "unknown logits dtype");
+    CHECK_ACTION_FORMAT(env, fmt);
+    if ((uintptr_t)logits_dev % logits_elem_bytes(logits_dtype) != 0)
+        return fail(env, PCBENV_EINVAL, "logits pointer not aligned to its element size");
+    return PCBENV_OK;
+}
+extern "C" int pcbenv_sample_logits(pcbenv *env, const void *logits_dev, int32_t logits_dtype, int32_t mode,
+                                    int32_t *actions_dev, int32_t fmt, float *log_prob_dev, float *entropy_dev,
+                                    uint32_t *errors_dev, uint64_t seed, uint64_t first_env_index, uint64_t step_index,
+                                    void *stream) {
+    const int rc = logits_checks(env, logits_dev, logits_dtype, actions_dev, fmt);
+    if (rc != PCBENV_OK) return rc;
+    if (mode != PCBENV_DRAW_SAMPLE && mode != PCBENV_DRAW_GREEDY) return fail(env, PCBENV_EINVAL, "unknown draw mode");
+    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
+    if (!env->bound) return fail(env, PCBENV_ESTATE, "pcbenv_bind_buffers has not been called");
+    DEVICE_GUARD(env);
+    hipStream_t s = (hipStream_t)stream;
+    // A captured launch would keep reading the state set that was current at capture time (as pcbenv_gather).
+    if (stream_capturing(s)) return fail(env, PCBENV_ESTATE, "pcbenv_sample_logits cannot be captured into a graph");
+    SampleLogitsLaunch a;
+    a.d = env->dp;  // d.state: the current state set, as k_sample reads it
+    a.dtype = logits_dtype; a.stream = s;
+    SampleLogitsArgs &g = a.g;
+    g.logits = logits_dev; g.actions = actions_dev; g.log_prob = log_prob_dev; g.entropy = entropy_dev;
+    g.errors = (unsigned *)errors_dev; g.seed = (u64)seed; g.first_env = (u64)first_env_index; g.step_index = (u64)step_index;
+    g.fmt = fmt; g.greedy = mode == PCBENV_DRAW_GREEDY;
+    pcb_launch_sample_logits(a);
+    HIP_TRY(env, hipGetLastError());
+    return PCBENV_OK;
+}
+
+// ---- pcbenv_evaluate_logits / pcbenv_evaluate_logits_backward ------------------------------------------------------
+// As pcbenv_sample_logits: the argument checks come before anything touches a device.  The handle gives the geometry
+// and the device; nothing the library owns is read or written, so no buffers need to be bound.
+static int evaluate_checks(pcbenv *env, const void *logits_dev, int32_t logits_dtype, const uint64_t *mask_bits_dev,
+                           const int32_t *actions_dev, int32_t fmt, int64_t num_rows) {
+    const int rc = logits_checks(env, logits_dev, logits_dtype, actions_dev, fmt);
+    if (rc != PCBENV_OK) return rc;
+    if (!mask_bits_dev) return fail(env, PCBENV_EINVAL, "null mask bits");
+    if ((uintptr_t)mask_bits_dev % 8 != 0) return fail(env, PCBENV_EINVAL, "mask bits pointer not aligned to 8 bytes");
+    if (num_rows < 0 || num_rows > INT32_MAX) return fail(env, PCBENV_EINVAL, "num_rows out of range");
+    return PCBENV_OK;
+}
+static EvalGeom eval_geom(const pcbenv *env, int64_t num_rows) {
+    const DevParams &d = env->dp;
+    return EvalGeom{d.O, d.H, d.W, d.WW, (int)num_rows};
+}
+
+extern "C" int pcbenv_evaluate_logits(const pcbenv *cenv, const void *logits_dev, int32_t logits_dtype,
+                                      const uint64_t *mask_bits_dev, const int32_t *actions_dev, int32_t fmt,
+                                      int64_t num_rows, float *log_prob_dev, float *entropy_dev, float *stats_dev,
+                                      uint32_t *errors_dev, void *stream) {
+    pcbenv *env = const_cast<pcbenv *>(cenv);  // the error text only
+    const int rc = evaluate_checks(env, logits_dev, logits_dtype, mask_bits_dev, actions_dev, fmt, num_rows);
+    if (rc != PCBENV_OK) return rc;
+    if ((uintptr_t)stats_dev % 16 != 0) return fail(env, PCBENV_EINVAL, "stats pointer not aligned to 16 bytes");
+    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
+    if (num_rows == 0) return PCBENV_OK;
+    DEVICE_GUARD(env);
+    EvalLogitsLaunch a;
+    a.q = eval_geom(env, num_rows); a.dtype = logits_dtype; a.stream = (hipStream_t)stream;
+    EvalLogitsArgs &g = a.g;
+    g.logits = logits_dev; g.mask_bits = (const u64 *)mask_bits_dev; g.actions = actions_dev; g.log_prob = log_prob_dev;
+    g.entropy = entropy_dev; g.stats = stats_dev; g.errors = (unsigned *)errors_dev; g.fmt = fmt;
+    pcb_launch_evaluate_logits(a);
+    HIP_TRY(env, hipGetLastError());
+    return PCBENV_OK;
+}
+
+extern "C" int pcbenv_evaluate_logits_backward(const pcbenv *cenv, const void *logits_dev, int32_t logits_dtype,
+                                               const uint64_t *mask_bits_dev, const int32_t *actions_dev, int32_t fmt,
+                                               int64_t num_rows, const float *stats_dev, const float *grad_log_prob_dev,
+                                               const float *grad_entropy_dev, void *grad_logits_dev, void *stream) {
+    pcbenv *env = const_cast<pcbenv *>(cenv);  // the error text only
+    const int rc = evaluate_checks(env, logits_dev, logits_dtype, mask_bits_dev, actions_dev, fmt, num_rows);
+    if (rc != PCBENV_OK) return rc;
+    if (!stats_dev) return fail(env, PCBENV_EINVAL, "null stats");
+    if ((uintptr_t)stats_dev % 16 != 0) return fail(env, PCBENV_EINVAL, "stats pointer not aligned to 16 bytes");
+    if (!grad_logits_dev) return fail(env, PCBENV_EINVAL, "null grad logits");
+    if ((uintptr_t)grad_logits_dev % logits_elem_bytes(logits_dtype) != 0)
+        return fail(env, PCBENV_EINVAL, "grad logits pointer not aligned to its element size");
+    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
+    if (num_rows == 0) return PCBENV_OK;
+    DEVICE_GUARD(env);
+    EvalLogitsBackwardLaunch a;
+    a.q = eval_geom(env, num_rows); a.dtype = logits_dtype; a.stream = (hipStream_t)stream;
+    EvalLogitsBackwardArgs &g = a.g;
+    g.logits = logits_dev; g.mask_bits = (const u64 *)mask_bits_dev; g.actions = actions_dev; g.stats = stats_dev;
+    g.grad_log_prob = grad_log_prob_dev; g.grad_entropy = grad_entropy_dev; g.grad_logits = grad_logits_dev; g.fmt = fmt;
+    pcb_launch_evaluate_logits_backward(a);
+    HIP_TRY(env, hipGetLastError());
+    return PCBENV_OK;
+}
+
+extern "C" int pcbenv_queue_cursors(pcbenv *env, uint32_t *min_out, uint32_t *max_out, void *stream) {
+    if (!env || !min_out || !max_out) return fail(env, PCBENV_EINVAL, "null argument");
+    DEVICE_GUARD(env);
+    if (!env->scratch) HIP_TRY(env, hipMalloc((void **)&env->scratch, 16));
+    hipLaunchKernelGGL(k_cursor_range, dim3(1), dim3(256), 0, (hipStream_t)stream, env->dp, env->scratch);
+    unsigned host[2] = {0, 0};
+    HIP_TRY(env, hipMemcpyAsync(host, env->scratch, 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(env, hipStreamSynchronize((hipStream_t)stream));
+    *min_out = host[0]; *max_out = host[1];
+    return PCBENV_OK;
+}
+
+#ifdef PCBENV_STAMPS
+extern "C" int pcbenv_debug_stamps(pcbenv *env, unsigned long long *host) {  // diagnostic build only
+    if (!env || !env->dp.dbg) return -1;
+    hipDeviceSynchronize();
+    const size_t rows = (size_t)env->dp.B + (size_t)env->dp.term_cap * (REWARD_PARTS + 1);  // environments, then the helpers
+    const int rc = hipMemcpy(host, env->dp.dbg, rows * 32 * 8, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -3;
+    hipMemset(env->dp.dbg, 0, rows * 32 * 8);
+    return rc;
+}
+#endif

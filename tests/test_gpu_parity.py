@@ -229,7 +229,8 @@ def test_auto_reset_with_beam_routes():
                                                  ("c3", 1024, 0, False), ("c5", 256, None, False), ("c3_256threads", 256, None, True)])
 def test_terminal_teams_with_staggered_episodes(name, B, teams, fused):
     """One launch per step, episode phases spread over the batch (1 / L of it terminal in every launch): the
-    environments on the terminal list run on four-wavefront teams of k_step_mixed, the others on one wavefront each --
+    environments on the terminal list get the helper teams of Team<>::run_env (shares of the routing reward, the
+    feature half of the reset), the others run on their own team alone --
     every tensor of every environment at every step vs the oracle, with corrupted actions (terminal at once, off the
     list), lists longer than the teams' capacity (teams = 3 / 5 / 7: the rest falls back to its own wavefront) and
     the plain kernel (teams = 0)."""
