@@ -357,7 +357,8 @@ int pcbenv_sample_logits(pcbenv *env, const void *logits_dev, int32_t logits_dty
  * stats_dev: float32 [num_rows, 4] = (M, log Z, entropy, row status), 16-byte aligned; the forward call writes it and
  * the backward call consumes it, so that backward is one pass.  It may be NULL in forward when no gradient is wanted.
  * Forward, with L, M, w_i, Z, p_i as above: log_prob = l_a - M - log Z, entropy = log Z - sum over L of p_i (l_i - M)
- * (a legal -inf logit contributes 0).  log_prob_dev, entropy_dev, errors_dev may be NULL.
+ * (a legal logit whose weight is 0 contributes 0: -inf, or finite and so far below M that the weight underflows or
+ * l_i - M is itself no float32).  log_prob_dev, entropy_dev, errors_dev may be NULL.
  * Backward writes EVERY element of grad_logits_dev [num_rows, A] in the logits' dtype (bf16: round to nearest even); the
  * caller passes uninitialised memory.  With log p_i = l_i - M - log Z and Hrow the row's entropy:
  *   g_i = g_lp (1[i = a] - p_i) - g_H p_i (log p_i + Hrow)   for i in L   (p_i = 0: the second term is 0, never NaN)

@@ -154,7 +154,7 @@ __device__ inline bool pass1(const T *row, const PolicyLds &l, const EvalGeom &q
                     const float lv = v[u][i];
                     if (((nib[u] >> i) & 1u) && lv > -INFINITY) {
                         const float d = lv - m, w = seg_weight(lv, m);
-                        sw += w; st += w * d;
+                        sw += w; st += w > 0.f ? w * d : 0.f;  // a zero weight contributes 0: l - m may be -inf, and 0 * -inf is NaN
                         if (FIRST && lv == m) first = a0[u] + i;
                     }
                 }

@@ -18,7 +18,7 @@ from pcbenv.masked_categorical import evaluate, evaluate_torch, unpack_mask_bits
 from pcbenv.rollout import masked_logits
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHAPES = [(1, 8, 8), (2, 6, 6), (4, 10, 10), (4, 16, 64), (4, 5, 128)]
+SHAPES = [(1, 8, 8), (2, 6, 6), (4, 10, 10), (4, 16, 64), (4, 5, 128), (4, 7, 100), (2, 33, 65), (1, 3, 128), (4, 100, 9)]
 
 
 def _header():

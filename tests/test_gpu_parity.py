@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from golden_util import case_names, load_case, pad_component_grid
+from logits_cases import RAGGED
 from pcbenv import EnvConfig, InstanceStream, env_seed, named_config, pack_instances
 from pcbenv.batched_env import BatchedPlacementEnv
 from pcbenv.config import KIND_PIN, KIND_SPATIAL, KIND_SQUARE
@@ -817,8 +818,9 @@ def test_sampler_definition():
     legal actions in (orientation, row, column) order -- checked here against a host computation from mask_bits(),
     independently of how the kernel scans and selects."""
     M = (1 << 64) - 1
-    for name, first in (("c1", 0), ("c2", 7), ("c4", 1000), ("c5", 3)):
-        cfg = named_config(name)
+    for name, first in (("c1", 0), ("c2", 7), ("c4", 1000), ("c5", 3),
+                        ("spatial_7x100", 11), ("pin_100x9", 2), ("rect_33x65", 5), ("square_3x128", 9)):
+        cfg = RAGGED[name]() if name in RAGGED else named_config(name)
         B = 12
         env = BatchedPlacementEnv(cfg, B, queue_depth=1, run_seed=5, first_env_index=first)
         env.generate_instances(); env.reset()

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import sampling_contract as sc
+from logits_cases import RAGGED, SAMPLER_RAGGED
 from pcbenv import EnvConfig, _lib, named_config
 from pcbenv.batched_env import BatchedPlacementEnv
 from pcbenv.config import KIND_SQUARE
@@ -16,6 +17,8 @@ pytestmark = pytest.mark.gpu
 CONFIGS = {"c1": lambda: named_config("c1"), "c2": lambda: named_config("c2"), "c3": lambda: named_config("c3"),
            "c4": lambda: named_config("c4"), "c5": lambda: named_config("c5"),
            "rect_6x6": lambda: EnvConfig.rect(6, 6, 2, 4, 2, 4, 4, 2), "square_5x5": lambda: EnvConfig.square(5, 5, 2)}
+# ragged grids (H != W, a partial second mask word, one load per logit with one and with four wavefronts): whole episodes
+CONFIGS.update({name: RAGGED[name] for name in SAMPLER_RAGGED})
 SEED = 7
 
 
