@@ -224,7 +224,16 @@ int pcbenv_reset(pcbenv *env, const uint8_t *mask_dev, void *stream);
 
 /* step(): one transition of every environment with the given actions.
  * (A launch issued while `stream` is being captured into a hipGraph will be replayed with the very same arguments: it
- * then runs without the helper wavefronts of the terminal list and updates the state blocks in place -- same results.) */
+ * then runs without the helper wavefronts of the terminal list and updates the state blocks in place -- same results.
+ * The graph may be replayed at any later time, in any order with eager calls on the same handle (pcbenv_step*,
+ * pcbenv_rollout_sampled, pcbenv_reset, pcbenv_gather, pcbenv_set_state, pcbenv_set_option): a replay steps the state
+ * the latest call left.  To keep that true, from the first captured launch on EVERY step launch of the handle works
+ * in place on the set the graph was captured on -- no swap of the double-buffered state blocks, no helpers -- and
+ * pcbenv_gather copies its result back into that set.  This holds for the rest of the handle's life:
+ * PCBENV_OPT_TERMINAL_TEAMS is still accepted but starts no helpers on such a handle, because the library cannot know
+ * whether a graph is still alive and a replay after a re-armed swap would silently step a stale set.  Create a new
+ * handle to get helper launches back.  What stays frozen in a captured launch are its arguments: the actions pointer,
+ * the selected trajectory slot, the store policy.) */
 int pcbenv_step(pcbenv *env, const int32_t *actions_dev, int32_t action_format, void *stream);
 
 /* Uniform draw over the currently legal actions of every environment

@@ -41,6 +41,9 @@ struct pcbenv {
     unsigned *term_seen_host;     // mapped host memory the step kernel reports its list length to (DevParams::term_seen)
     unsigned char *state_buf[2];  // double-buffered state blocks: dp.state is the current one, a step launch writes the other
     int state_cur;
+    // Set by the first step launch captured into a hipGraph, for the rest of the handle's life: the graph works on
+    // state_buf[state_cur] in place, so from then on every launch does (no buffer swap, no helpers) -- see dispatch_step.
+    bool in_place;
     unsigned char *gather_snap;   // pcbenv_gather within one handle: reward | info | done of the selected slot before the launch
     char err[256];
 };

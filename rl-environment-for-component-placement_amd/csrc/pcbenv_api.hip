@@ -255,22 +255,27 @@ static int dispatch_step(pcbenv *env, int *actions, int fmt, int sampled, u64 se
     if (++env->seq == 0u) env->seq = 1u;  // 0 is "not listed" in the marks
     d.seq = env->seq;
     // A launch that is being captured into a hipGraph will be replayed with these very arguments: no launch number,
-    // no buffer swap -- it runs without helpers, keeps no list and works on the state blocks in place.
-    const bool capturing = stream_capturing(s);
+    // no buffer swap -- it runs without helpers, keeps no list and works on the state blocks in place.  The graph may be
+    // replayed at any later time, between eager calls, and must then find the current state where it was captured: from
+    // the first capture on, every launch of the handle works in place on that same set (pcbenv_gather copies back).
+    // The library cannot tell whether a graph is still alive, so nothing re-arms the swap: a replay after that would
+    // silently step a stale set.
+    if (stream_capturing(s)) env->in_place = true;
+    const bool in_place = env->in_place;
     d.term_wgs = 0;
-    if (num_steps == 1 && !capturing && env->term_wgs > 0) {  // reward helpers: one transition per launch only
+    if (num_steps == 1 && !in_place && env->term_wgs > 0) {  // reward helpers: one transition per launch only
         // as many entries' helpers as the lists have lately been long (k_step reports it: + 25 %, + 2 per shard; never none:
         // a shard's first entry)
         const unsigned seen = *(volatile unsigned *)env->term_seen_host;
         const long long want = (long long)TERM_SHARDS * ((long long)seen + seen / 4 + 2);
         d.term_wgs = (int)(want < env->term_wgs ? want : env->term_wgs);
     }
-    if (capturing) d.term_cap = 0;
+    if (in_place) d.term_cap = 0;
     // double-buffered state blocks: read the current ones, write the others
     d.state = env->state_buf[env->state_cur];
-    d.state_out = env->state_buf[env->state_cur ^ (capturing ? 0 : 1)];
+    d.state_out = env->state_buf[env->state_cur ^ (in_place ? 0 : 1)];
     const int rc = kind_launch[env->cfg.kind].step(a);
-    if (!capturing) env->state_cur ^= 1;
+    if (!in_place) env->state_cur ^= 1;
     env->dp.state = env->dp.state_out = env->state_buf[env->state_cur];  // what k_reset / k_sample / get_state work on, in place
     return rc;
 }
@@ -475,6 +480,10 @@ extern "C" int pcbenv_gather(pcbenv *dst, const pcbenv *src, const int32_t *src_
     }
     kind_launch[dst->cfg.kind].gather(a);
     HIP_TRY(dst, hipGetLastError());
+    if (dst->in_place) {  // a captured graph works on the current set (dispatch_step): the gathered blocks go back into it
+        HIP_TRY(dst, hipMemcpyAsync(d.state, d.state_out, state_section_bytes(dst), hipMemcpyDeviceToDevice, s));
+        return PCBENV_OK;
+    }
     dst->state_cur ^= 1;
     dst->dp.state = dst->dp.state_out = dst->state_buf[dst->state_cur];
     return PCBENV_OK;

@@ -543,6 +543,10 @@ class BatchedPlacementEnv:
         self.reward.copy_(d["reward"]); self.done.copy_(d["done"]); self.info_raw.copy_(d["info"])
         for k, v in self.obs.items():
             v.copy_(d["obs/" + k])
+        if self.mask_marginals:  # not part of a checkpoint: they summarise the mask that has just been restored
+            am = self.obs["action_mask"].reshape(self.num_envs, -1, self.cfg.height, self.cfg.width)
+            self.mask_marginals["rows"].copy_(am.amax(dim=3))
+            self.mask_marginals["orientation"].copy_(am.amax(dim=(2, 3)))
         # `done` of the latest step: restored into the selected slot's tensor (where reset_done() will look)
         self._last_done = self.done
         if "last_done" in d:

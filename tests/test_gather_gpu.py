@@ -11,145 +11,9 @@ from pcbenv import _lib, env_seed, named_config
 from pcbenv.batched_env import BatchedPlacementEnv
 from pcbenv.config import KIND_PIN, KIND_SPATIAL, KIND_SQUARE
 
+from handle_model import Run, _bytes_equal  # the environment next to its host model (shared with the call-sequence tests)
+
 pytestmark = pytest.mark.gpu
-
-
-def _bytes_equal(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
-class Run:
-    """A BatchedPlacementEnv next to its CPU oracle and, per row, what the oracle needs to rebuild it: the instance
-    record of the current episode, the actions since its last reset and the number of resets (the queue cursor)."""
-
-    def __init__(self, cfg, B, run_seed=3, queue_depth=3, device_instances=False, max_resets=64, **kw):
-        from oracle import oracle as orc
-        self.cfg, self.B, self.Q = cfg, B, queue_depth
-        self.env = BatchedPlacementEnv(cfg, B, queue_depth=queue_depth, run_seed=run_seed, **kw)
-        self.square = cfg.kind == KIND_SQUARE
-        self.fresh = self.packed = None
-        if device_instances:
-            from pcbenv.instances import NativeInstanceStreams
-            self.env.enable_device_instances()
-            host = NativeInstanceStreams(cfg, [env_seed(run_seed, i) for i in range(B)])
-            self.fresh = [host.next_packed() for _ in range(max_resets)]
-        elif not self.square:
-            self.packed = self.env.generate_instances()
-        self.ob = orc.OracleBatch(cfg, B)
-        self.cursor = np.zeros(B, np.int64)
-        self.inst = [None] * B
-        self.hist = [[] for _ in range(B)]
-        self.last_done = np.zeros(B, np.uint8)
-        self.S = self.env.num_slots
-        self.env.reset()
-        self.oracle_reset(np.ones(B, np.uint8))
-
-    def record(self, i):
-        c = int(self.cursor[i])
-        return self.fresh[c][i] if self.fresh is not None else self.packed[c % self.Q][i]
-
-    def oracle_reset(self, mask):
-        mask = np.asarray(mask).astype(bool)
-        if self.square:
-            for i in np.flatnonzero(mask):
-                self.ob.env(int(i)).reset()
-        else:
-            rec = np.stack([self.record(i) for i in range(self.B)])
-            self.ob.reset_packed(rec, mask.astype(np.uint8))
-            for i in np.flatnonzero(mask):
-                self.inst[i] = rec[i]
-        for i in np.flatnonzero(mask):
-            self.hist[i] = []
-        self.cursor[mask] += 1
-
-    def host_obs(self, f64=False):
-        e = self.env
-        out = {k: v.cpu().numpy() for k, v in (e.obs_f64() if f64 else e.obs).items()}
-        if not f64:
-            out.update({"marginal_" + k: v.cpu().numpy() for k, v in e.mask_marginals.items()})
-            out.update(reward=e.reward.cpu().numpy(), done=e.done.cpu().numpy(), info=e.info_raw.cpu().numpy())
-        return out
-
-    def compare_oracle(self, tag):
-        obs = self.host_obs(f64=True)
-        for k, v in obs.items():
-            bad = self.ob.first_mismatch(k, v)
-            assert bad < 0, (tag, k, bad)
-        m = self.env.mask_marginals
-        if m:  # marginals against the mask they summarise
-            am = self.env.obs["action_mask"].reshape(self.B, -1, self.cfg.height, self.cfg.width)
-            assert torch.equal(m["rows"], am.amax(dim=3)), tag
-            assert torch.equal(m["orientation"], am.amax(dim=(2, 3))), tag
-
-    def gather(self, idx, src=None, check_snapshot=True):
-        """gather_ on the device; the snapshot and oracle bookkeeping on the host.  Returns the rows taken."""
-        src = src or self
-        idx = np.asarray(idx, np.int64)
-        take = (idx >= 0) & (idx < src.B)
-        before_src = src.host_obs()
-        before_own = before_src if src is self else self.host_obs()
-        self.env.gather_(torch.from_numpy(idx).to(self.env.device), source=None if src is self else src.env)
-        after = self.host_obs()
-        if check_snapshot:
-            for k, v in after.items():
-                want = before_own[k].copy()
-                want[take] = before_src[k][idx[take]]
-                assert _bytes_equal(v, want), ("snapshot", k, np.flatnonzero([not _bytes_equal(v[i], want[i]) for i in range(self.B)])[:5])
-        inst = [src.inst[j] for j in idx.clip(0, src.B - 1)]
-        hist = [list(src.hist[j]) for j in idx.clip(0, src.B - 1)]
-        last_done = src.last_done[idx.clip(0, src.B - 1)]
-        if self.square:
-            for i in np.flatnonzero(take):
-                self.ob.env(int(i)).reset()
-        else:
-            rec = np.stack([inst[i] if take[i] else self.inst[i] for i in range(self.B)])
-            self.ob.reset_packed(rec, take.astype(np.uint8))
-        for i in np.flatnonzero(take):
-            e = self.ob.env(int(i))
-            for a in hist[i]:
-                e.step_raw(a)
-            self.inst[i], self.hist[i], self.last_done[i] = inst[i], hist[i], last_done[i]
-        self.compare_oracle("after gather")
-        return take
-
-    def step(self, t, fused=True, p_bad=0.0, rng=None):
-        e = self.env
-        if self.S > 1:
-            e.select_slot(t + 1)
-        if fused:
-            want = e.sample_actions(t).cpu().numpy()  # k_sample draws from the mask alone: a stale presample would differ
-            _, r, d, _, a_dev = e.rollout_step(t)
-            a = a_dev.cpu().numpy()
-            assert np.array_equal(a, want), ("fused action", t)
-        else:
-            a = e.sample_actions(t).cpu().numpy()
-            if p_bad:
-                bad = rng.rand(self.B) < p_bad
-                a[bad] = rng.randint(-1, 70, size=(int(bad.sum()), 3))
-            _, r, d, _ = e.step(torch.from_numpy(a))
-        rr, dd, ii = self.ob.step(a)
-        for i in range(self.B):
-            self.hist[i].append(a[i].copy())
-        self.last_done = dd.copy()
-        if e.auto_reset:
-            self.oracle_reset(dd)
-        assert np.array_equal(d.cpu().numpy(), dd), ("done", t)
-        assert _bytes_equal(r.cpu().numpy(), rr), ("reward", t)
-        if self.cfg.kind in (KIND_PIN, KIND_SPATIAL):
-            inf = e.info_raw.cpu().numpy()
-            has = ~np.isnan(inf[:, 0])
-            assert _bytes_equal(inf[has], ii[has]), ("info", t)
-        self.compare_oracle(("step", t))
-        return dd
-
-    def reset_done(self):
-        self.env.reset_done()
-        self.oracle_reset(self.last_done)
-        self.last_done[:] = 0
-
-    def close(self):
-        self.env.close()
 
 
 def _perm_with_repeats(rng, B, src_B=None):

@@ -899,6 +899,59 @@ def test_step_is_graph_capturable_with_a_policy():
     a.close(); b.close()
 
 
+def test_graph_replays_interleave_with_eager_calls():
+    """A replay of a captured step launch between eager steps, a gather and a masked reset: every replay works on the
+    state the latest call left (an eager call used to swap the double-buffered state blocks under the graph, which kept
+    stepping the set it was captured on: stale observations, rewards and dones).  The twin makes the same calls eagerly."""
+    cfg = named_config("c3")
+    B = 64
+
+    def make():
+        env = BatchedPlacementEnv(cfg, B, queue_depth=2, auto_reset=True, run_seed=6)
+        env.generate_instances(); env.reset()
+        return env
+
+    a, b = make(), make()
+    rng = np.random.RandomState(3)
+    static = torch.zeros((B, 3), dtype=torch.int32, device="cuda")
+    for env in (a, b):  # an eager step before the capture: the graph is captured on a handle that has swapped once
+        env.step(env.sample_actions(0))
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        b.step(static)
+
+    def same(tag):
+        torch.cuda.synchronize()
+        bad = ((a.reward != b.reward) | (a.done != b.done)).nonzero().flatten()
+        assert len(bad) == 0, (tag, "reward / done", bad[:8].tolist())
+        for k in a.obs:
+            assert torch.equal(a.obs[k], b.obs[k]), (tag, k)
+        assert torch.equal(a.info_raw.nan_to_num(-1.0), b.info_raw.nan_to_num(-1.0)), (tag, "info")
+        assert torch.equal(a.mask_bits(), b.mask_bits()), (tag, "mask_bits")
+
+    t = 1
+    for rnd in range(3 * cfg.max_num_components):
+        kind = rnd % 5
+        if kind in (0, 2):    # a replay: the twin takes the same actions eagerly
+            a.sample_actions(t, out=static)
+            a.step(static)
+            g.replay()
+            t += 1
+        elif kind == 1:       # ONE eager step on both: an odd number of swaps between two replays
+            act = a.sample_actions(t)
+            a.step(act); b.step(act)
+            t += 1
+        elif kind == 3:
+            idx = torch.from_numpy(rng.randint(-1, B, size=B)).cuda()
+            a.gather_(idx); b.gather_(idx)
+        else:
+            mask = torch.from_numpy((rng.rand(B) < 0.3).astype(np.uint8))
+            a.reset(mask); b.reset(mask)
+        same((rnd, kind))
+    a.close(); b.close()
+
+
 def test_presampled_action_is_never_stale():
     """The fused sampler draws the action of step t+1 at the end of the launch of step t and keeps it in the state
     header; whatever happens in between -- jumps in the step index, another seed, an explicit step, a masked reset,
