@@ -283,8 +283,10 @@ int pcbenv_instgen_next_batch(pcbenv_instgen *const *streams, int32_t n, void *r
  * 2-4x the records one launch can consume keeps the generator off the critical path (queue_depth <= 256).
  * pcbenv_instgen_device_status brings the queue fully up to date (queue_depth records ahead of every cursor),
  * synchronises, and reports 0 unless a reset ever found its record missing (bit 0; it never should) or a stream hit
- * a draw the reference itself fails on / this library does not support (bit 1).  pcbenv_get_instances copies one queue slot (num_envs packed
- * records) to the host, e.g. to replay an episode on the CPU. */
+ * a draw the reference itself fails on / this library does not support (bit 1).  Such a stream has stopped: the records
+ * before the failing one are queued and valid, none follows, and once they are consumed its environment must not be
+ * reset again (the other environments' streams carry on unaffected).  pcbenv_get_instances copies one queue slot
+ * (num_envs packed records) to the host, e.g. to replay an episode on the CPU. */
 int pcbenv_instgen_device_enable(pcbenv *env, const uint32_t *seeds_host, void *stream);
 int pcbenv_instgen_device_status(pcbenv *env, uint32_t *errors_out, void *stream);
 int pcbenv_get_instances(pcbenv *env, int32_t slot, void *host_dst, void *stream);

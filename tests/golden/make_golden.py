@@ -23,8 +23,9 @@ shipped hyper-parameters of the spatial policy, a data file of the reference), `
 with all pin coordinates after whole episodes), `episode_export.npz` (the reference's Pin / Component objects of one
 episode, before and after placement), `norm2.npz` (np.linalg.norm of length-2 vectors in this container's
 NumPy/OpenBLAS -- SURVEY.md trap T1) and `setorder.npz` (CPython iteration order of
-`set(points) - visited` -- trap T2).  The files are data only; no reference source
-text is stored.
+`set(points) - visited` -- trap T2) and `generator_tables.npz` (the instance tables of eight resets per stream for the
+configurations of tests/generator_cases.py, with the reset and exception class where the reference raised).  The files
+are data only; no reference source text is stored.
 """
 import json
 import os
@@ -194,6 +195,62 @@ def record_setorder():
                         order=np.array(orders), tuple_hash=np.array(hashes, np.uint64))
 
 
+def record_generator_tables():
+    """The generator's configuration space (`tests/generator_cases.py`): per case and seed, seeded like record_case,
+    RESETS reset()s of the reference and the tables of each; where reset() raised, the index of that reset and the
+    exception's class name instead, and nothing after it.  `tests/golden/generator_tables.npz`, per case:
+    seeds [S], fail_at [S] (-1: none), fail_exc [S], ncomp / nnets / npins [S, RESETS] (-1: no record), comp_hw = (h, w)
+    of all components and pins = (rel_x, rel_y, net, component, pin_id) of all pins, record after record.  The archive
+    is written with fixed member dates, so regenerating it gives the same bytes."""
+    import io
+    import zipfile
+    sys.path[:0] = [os.path.dirname(HERE), os.path.join(REPO, "rl-environment-for-component-placement_amd")]
+    import generator_cases as gc
+    big = [n for n, (_k, _a, g) in gc.CASES.items() if g == 64]
+    data = {}
+    for name, (kind, args, _g) in gc.CASES.items():
+        seeds = list(range(3)) if name in big else list(range(24)) if name in gc.FAIL_CASES else list(range(8))
+        S, R = len(seeds), gc.RESETS
+        fail_at, fail_exc = np.full(S, -1, np.int16), [""] * S
+        counts = np.full((3, S, R), -1, np.int16)
+        comp_rows, pin_rows = [], []
+        for si, seed in enumerate(seeds):
+            np.random.seed(seed)
+            random.seed(seed)
+            env = REF[kind](*args)
+            for r in range(R):
+                try:
+                    env.reset()
+                except Exception as exc:  # the stream stops here: generate_instances cannot draw this record
+                    fail_at[si], fail_exc[si] = r, type(exc).__name__
+                    break
+                t = tables(env, kind)
+                counts[0, si, r] = len(t["comp_h"])
+                comp_rows.append(np.stack([t["comp_h"], t["comp_w"]], axis=1))
+                if kind != "rect":
+                    counts[1, si, r], counts[2, si, r] = int(t["num_nets"]), len(t["pin_id"])
+                    pin_rows.append(np.stack([t[k] for k in gc.PIN_FIELDS], axis=1))
+                else:
+                    counts[1, si, r] = counts[2, si, r] = 0
+        if name in gc.FAIL_CASES:  # streams that stop and streams that do not
+            assert (fail_at >= 0).any() and (fail_at < 0).any(), (name, fail_at)
+        else:
+            assert (fail_at < 0).all(), (name, fail_at)
+        data.update({name + "/seeds": np.array(seeds, np.int64), name + "/fail_at": fail_at, name + "/fail_exc": np.array(fail_exc),
+                     name + "/ncomp": counts[0], name + "/nnets": counts[1], name + "/npins": counts[2],
+                     name + "/comp_hw": np.concatenate(comp_rows).astype(np.uint8),
+                     name + "/pins": (np.concatenate(pin_rows) if pin_rows else np.zeros((0, 5))).astype(np.int16)})
+    path = os.path.join(HERE, "generator_tables.npz")
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as zf:
+        for key, arr in data.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.ascontiguousarray(arr), allow_pickle=False)
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            zf.writestr(info, buf.getvalue())
+    return os.path.getsize(path)
+
+
 def _describe_space(sp):
     """JSON summary of one of the reference's space objects (the stand-in gym classes keep the ctor arguments)."""
     from gym import spaces as gs
@@ -311,6 +368,9 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "episode_export":  # only the (tiny) episode-export fixture
         record_episode_export()
         raise SystemExit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "generator_tables":  # only the generator's configuration space
+        print(f"generator_tables {record_generator_tables() / 1024:.1f} KiB")
+        raise SystemExit(0)
     total = 0
     for case in CASES:
         sz = record_case(*case)
@@ -322,4 +382,5 @@ if __name__ == "__main__":
     record_adapter_views()
     record_episode_export()
     record_model_config()
+    record_generator_tables()
     print(f"total {total / 1024:.1f} KiB")

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import generator_cases
 from golden_util import case_names, load_case, pad_component_grid
 from logits_cases import RAGGED
 from pcbenv import EnvConfig, InstanceStream, env_seed, named_config, pack_instances
@@ -664,6 +665,9 @@ GEN_CASES = {
     "small_pin": lambda: EnvConfig.pin(10, 10, 3, 4, 2, 4, 2, 4, 6, 1, 2, 4, 5, 2, "centroid", 2, 0.5),
     "mid_spatial": lambda: EnvConfig.spatial(12, 12, 5, 5, 2, 5, 2, 5, 8, 6, 3, 5, 7, 2, "centroid", 2, 0.25),
     "rect_6x6": lambda: EnvConfig.rect(6, 6, 2, 4, 2, 4, 4, 2),
+    # from the generator's configuration space (tests/generator_cases.py): the knobs at 0, 1x1 / fully pinned components, the pin kind at G = 32
+    "pin_knobs00": lambda: generator_cases.make_cfg("pin_knobs00"), "pin_tiny_full": lambda: generator_cases.make_cfg("pin_tiny_full"),
+    "pin_g32": lambda: generator_cases.make_cfg("pin_g32"),
 }
 
 
@@ -703,7 +707,8 @@ def test_device_instance_generator_equals_the_host_streams(name, B, lanes, monke
 
 
 @pytest.mark.parametrize("name,B,mode", [("c3", 256, "fused"), ("c4", 128, "fused"), ("c2", 256, "explicit"), ("small_spatial", 256, "fused"),
-                                         ("small_pin", 256, "explicit"), ("mid_spatial", 128, "fused")])
+                                         ("small_pin", 256, "explicit"), ("mid_spatial", 128, "fused"),
+                                         ("pin_knobs00", 128, "fused"), ("pin_tiny_full", 256, "fused"), ("pin_g32", 64, "explicit")])
 def test_fresh_instances_every_reset_vs_oracle(name, B, mode):
     """The reference's reset() semantics at full speed: every episode of every environment on a NEW instance from its
     stream (on-device generator, queue refilled on the side stream while the steps run); every tensor, reward, done

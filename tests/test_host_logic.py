@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import generator_cases as gc
 from golden_util import case_names, load_case
 from pcbenv import (EnvConfig, InstanceStream, config_from_env_config, env_seed, flat_to_tuple, instance_stride,
                     named_config, pack_instances, tuple_to_flat)
@@ -23,6 +24,29 @@ def test_instance_stream_reproduces_reference_tables(name):
         for f in ("comp_h", "comp_w", "pin_rel_x", "pin_rel_y", "pin_net", "pin_comp", "pin_id"):
             assert np.array_equal(getattr(got, f), getattr(want, f)), (name, e.seed, e.ep, f)
         assert got.num_nets == want.num_nets
+
+
+@pytest.mark.parametrize("name", list(gc.CASES))
+def test_instance_stream_reproduces_the_generator_fixture(name):
+    """The generator's configuration space (tests/generator_cases.py): every record of every recorded stream, and where
+    the reference raised, InstanceStream raises the same exception class at the same reset."""
+    cfg = gc.make_cfg(name)
+    cfg.check_device_limits()
+    assert gc.group_lanes(cfg) == gc.CASES[name][2]
+    streams = gc.load_fixture(name)
+    if name in gc.FAIL_CASES:
+        stopped = sum(fail_at != gc.NEVER for _, _, fail_at, _ in streams)
+        assert 0 < stopped < len(streams)
+    for seed, recs, fail_at, exc in streams:
+        st = InstanceStream(cfg, seed)
+        for r, want in enumerate(recs):
+            assert gc.same_tables(gc.instance_tables(st.next()), want), (name, seed, r)
+        if fail_at != gc.NEVER:
+            with pytest.raises(Exception) as ei:
+                st.next()
+            assert type(ei.value).__name__ == exc, (name, seed, fail_at, ei.value)
+        else:
+            assert len(recs) == gc.RESETS and exc == ""
 
 
 def test_constructor_validation_mirrors_reference():
