@@ -1,5 +1,5 @@
 // pcb_beam.h -- beam-search routes with the model of CPython's set iteration order
-// Included by pcb_team.h inside Team<>, so by every unit that includes pcb_kernels.h (pcb_kind_*.hip, pcbenv_api.hip); CDNA4 / gfx950 only.
+// Included by pcb_team.h inside Team<>, so by every unit that includes pcb_kernels.h (pcb_kind_*.hip, pcb_sample.hip, pcb_policy*.hip); CDNA4 / gfx950 only.
 
 // ---- beam-search routing (S:1273-1286 pin_outlier, S:1303-1369 beam_search, S:1371-1406) -----------------
 // beam_search keeps, per popped path, the beam_width nearest unvisited points of
@@ -30,8 +30,8 @@ struct BsEntry {
     }
 };
 static_assert(sizeof(BsEntry) == 32 && sizeof(CSet) == 48, "beam LDS records");
-#define BEAM_LDS_PER_NET(k) (64 * (k) * (k) + 16 * 8 + 16 + 2 * 48 + 16 * 4)
-#define BEAM_LDS_BYTES(nets, k) ((nets) * BEAM_LDS_PER_NET(k))
+// BEAM_LDS_PER_NET / BEAM_LDS_BYTES: pcb_layout.h (the host sizes the zone by the same formulas)
+static_assert(PCBENV_MAX_PINS_PER_NET <= 16, "BsEntry::meta / p0 / p1: 16 visited bits, 16 path bytes; dist, order and hs of beam_route_lanes: 16 entries");
 
 // points to visit of one net: the net's pins without the start pin `st`
 struct NetPts {  // coordinates packed one byte each into registers (<= 15 points): no LDS round trip per access
@@ -206,6 +206,8 @@ static __device__ inline int cs_small_difference_order(const CSet *A, const unsi
 // Same results as round 1's one-lane-per-net search (git history): same pop order (first index among fully equal
 // entries), same children in the same queue order.
 #define BEAM_LANES_PER_NET PCBENV_MAX_BEAM_WIDTH
+static_assert(BEAM_LANES_PER_NET == PCBENV_MAX_BEAM_WIDTH && (BEAM_LANES_PER_NET & (BEAM_LANES_PER_NET - 1)) == 0 && WAVE % BEAM_LANES_PER_NET == 0,
+              "route_beam: lane = group * BEAM_LANES_PER_NET + turn (lane & (BEAM_LANES_PER_NET - 1)), a lane per heappop of a level");
 #if defined(PCBENV_STAMPS) && defined(PCBENV_STAMPS_BEAM)  // phase cycles of the search, accumulated by lane 0 into stamp slots 26..29
 #define BEAM_T0() unsigned long long bt0_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(bt0_) :: "memory")
 #define BEAM_ACC(k) do { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); if (threadIdx.x == 0 && beam_dbg) beam_dbg[(size_t)blockIdx.x * 32 + (k)] += t_ - bt0_; bt0_ = t_; } while (0)

@@ -4,8 +4,7 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include "pcb_host.h"
-#include "pcb_team.h"  // the LDS zone sizes the kernels expect: BEAM_LDS_BYTES, SEG_LDS_BYTES, REWARD_PARTS
+#include "pcb_host.h"  // with pcb_layout.h: the state-block and LDS layout the kernels index by
 
 extern "C" int32_t pcbenv_max_total_pins(const pcbenv_config *c) {
     if (!c || !is_pin_kind(c->kind)) return 0;
@@ -77,7 +76,7 @@ static double mean2(int a, int b) { return (double)(a + b) / 2.0; }
 // per environment, state-block offsets, LDS zones, store policy and terminal-list capacity.
 void derive_layout(const pcbenv_config &c, pcbenv *env) {
     DevParams &d = env->dp;
-    d.kind = c.kind; d.H = c.height; d.W = c.width; d.WW = (c.width + 63) / 64;
+    d.kind = c.kind; d.H = c.height; d.W = c.width; d.WW = (c.width + 63) / 64;  // (= pcb_layout::Layout::WW)
     d.O = c.kind == PCBENV_SQUARE ? 1 : c.kind == PCBENV_RECT ? 2 : 4;
     d.C = c.kind == PCBENV_SQUARE ? 0 : c.max_num_components;
     d.P = pcbenv_max_total_pins(&c);
@@ -111,40 +110,18 @@ void derive_layout(const pcbenv_config &c, pcbenv *env) {
     // threads per environment: one wave up to 64x64 cells of output per plane, four waves above
     env->threads = c.threads_per_env == 64 || c.threads_per_env == 256 ? c.threads_per_env
                    : ((long long)c.height * c.width * (c.kind == PCBENV_SPATIAL ? d.K + 5 : 5) > 64 * 1024 ? 256 : 64);
-    // state block: header | occ | vm | comps | pins
-    d.offOcc = HDR_BYTES;
-    d.offVm = d.offOcc + d.H * d.WW * 8;
-    d.offComps = d.offVm + 2 * d.H * d.WW * 8;
-    d.offPins = d.offComps + 8 * d.C;
-    d.offRank = d.offPins + 8 * d.P;  // rank of each pin inside its component (spatial env)
-    d.stateStride = align16((long long)d.offRank + (c.kind == PCBENV_SPATIAL ? d.P : 0));
+    // the state block and the LDS zones behind its mirror: pcb_layout.h, which the kernels compile too
+    const pcb_layout::Geometry g{c.kind, d.H, d.W, d.C, d.P, d.N, d.mh, d.mw, env->threads, c.reward_type, c.reward_beam_width};
+    const pcb_layout::Layout l = pcb_layout::state_layout(g);
+    d.offOcc = l.offOcc; d.offVm = l.offVm; d.offComps = l.offComps; d.offPins = l.offPins; d.offRank = l.offRank;
+    d.stateStride = l.stateStride;
+    d.ldsHf = l.ldsHf; d.ldsHfWords = l.ldsHfWords; d.ldsCls = l.ldsCls; d.ldsSeg = l.ldsSeg; d.ldsBytes = l.ldsBytes;
     d.num_slots = 1; d.slot = 0;
     d.instStride = align16(pcbenv_instance_stride(&c));
-    // LDS scratch behind the state mirror: the folded rows of window_mask where it stages them in LDS (not the one-row-
-    // per-lane cross-lane fold of one-wavefront teams up to 64 rows), doubling as the pin env's row-membership bit map
-    d.ldsHf = (int)d.stateStride;
-    {
-#ifdef PCBENV_FOLD_LDS
-        const bool fold_in_lds = true;
-#else
-        const bool fold_in_lds = !(d.WW == 1 && env->threads == 64 && d.H <= 64);
-#endif
-        const int fold_words = fold_in_lds ? d.H * d.WW : 0, member_words = c.kind == PCBENV_PIN ? (d.C * d.mp + 63) / 64 : 0;
-        d.ldsHfWords = fold_words > member_words ? fold_words : member_words;
-    }
-    // the class map (pin_grid emission) and the route segments (terminal reward) are never live together
-    d.ldsCls = align16(d.ldsHf + d.ldsHfWords * 8);
-    d.ldsSeg = d.ldsCls;
-    {
-        const int beam = (is_pin_kind(c.kind) && c.reward_type != PCBENV_REWARD_CENTROID) ? BEAM_LDS_BYTES(c.max_num_nets, c.reward_beam_width) : 0;
-        // class map of emit_pin_grid; at a reset the same zone holds the pin-id and net-mask tables (2 + 4 bytes per component cell)
-        int cls = c.kind == PCBENV_SPATIAL ? (d.H * d.W > d.C * d.mp * 6 + 4 ? d.H * d.W : d.C * d.mp * 6 + 4) : 0, seg = is_pin_kind(c.kind) ? SEG_LDS_BYTES(d.P, d.N, env->threads / 64, beam) : 0;
-        d.ldsBytes = align16(d.ldsCls + (cls > seg ? cls : seg));
-    }
 #ifdef PCBENV_EXPERIMENTS
     { const char *ev = getenv("PCBENV_LDS_MIN"); if (ev && atoi(ev) > d.ldsBytes) d.ldsBytes = align16(atoi(ev)); }  // occupancy experiments
 #endif
-    // Terminal list: on for one-wavefront teams with instances (Team<>::run_env); B / 8 entries cover twice the
+    // Terminal list: on for the kinds with a routing reward (Team<>::run_env); B / 8 entries cover twice the
     // 1 / max_num_components of the batch that ends an episode per launch when the phases are spread evenly over a
     // 16-component episode (PCBENV_OPT_TERMINAL_TEAMS changes or disables it).
     env->seq = 0;

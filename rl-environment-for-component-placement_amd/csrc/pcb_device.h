@@ -1,5 +1,6 @@
 // pcb_device.h -- device-side parameter block, state-block records, LDS barrier, bit rows, 16-byte plane emission, wave scan
 // Included by every unit of libpcbenv.so that launches or defines a kernel (through pcb_launch.h, pcb_team.h or pcb_host.h); CDNA4 / gfx950 only.
+// The host units (pcbenv_api.hip, pcb_config.hip) take the parameter block and the records from here and call no device function.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -8,18 +9,17 @@
 #include <type_traits>
 
 #include "pcbenv.h"
+#include "pcb_layout.h"  // WAVE, HDR_BYTES, TERM_*: every size and offset the host side and the kernels share
 
 typedef unsigned long long u64;
 
-#define WAVE 64
-#define MAX_NT 256
-#define HDR_BYTES 64
-#define TERM_CNT_STRIDE 32u  // unsigned words between the shard counters of the terminal list: one 128-byte line each
-#define TERM_SHARD_BITS 4
-#define TERM_SHARDS (1u << TERM_SHARD_BITS)
-
 // ----------------------------------------------------------------------------------------------
 // device-side parameter block (kernel argument, by value)
+// The layout fields (offOcc ... ldsHfWords) are pcb_layout::Layout's, copied by derive_layout (pcb_config.hip).
+// The kernel-argument offsets of the fields must stay put: every wavefront starts by loading the fields it needs from
+// the kernel-argument segment with scalar loads the compiler groups by offset, so adding, removing or moving a field
+// regroups those loads and shifts the register allocation of every kernel -- a change to be measured like a kernel
+// change, never a side effect of tidying the host side.
 // ----------------------------------------------------------------------------------------------
 struct DevParams {
     int kind, H, W, WW, O, C, P, N, K, mp, mh, mw, F, pinRows, catW, B, Q;
@@ -112,12 +112,17 @@ struct __attribute__((aligned(16))) EnvHdr {
     unsigned term_seq, term_pos;
 };
 static_assert(sizeof(EnvHdr) == HDR_BYTES, "header size");
+static_assert(PCBENV_MAX_SIDE <= 128, "EnvHdr::pre_action: x and y in 8 bits each; CompRec::px / py, PinRec::abs_x / abs_y: signed char");
 
 // 8-byte records (state block and instance wire format share the pin layout up to abs_x/abs_y)
 struct CompRec { unsigned char h, w; signed char px, py; unsigned char o, pad[3]; };  // o = orientation it was placed with
 struct PinRec { unsigned char rel_x, rel_y; signed char abs_x, abs_y; unsigned char net, comp; unsigned short id; };
 #define PIN_ID_MASK 0x7FFF
 #define PIN_LOSER 0x8000  // pin env quirk Q1: a later pin of the same component shares this feature row
+// PinRec::id is a row of the pin feature tensors (spatial: the global pin id; pin: the id inside the component) and
+// PinTables::pid keeps one in 16 bits with 0xFFFF for "none": the largest pinRows (spatial: C * mp + 1) stays below both
+static_assert(PCBENV_MAX_COMPONENTS * PCBENV_MAX_PINS_PER_COMPONENT + 1 <= PIN_ID_MASK && PIN_ID_MASK < 0xFFFF, "PinRec::id & PIN_ID_MASK, PinTables::pid");
+static_assert(PCBENV_MAX_COMPONENTS <= 0xFF && PCBENV_MAX_NETS <= 0xFF, "PinRec::comp / net: unsigned char, 0xFF = no pin in this slot (reset_env)");
 
 // ----------------------------------------------------------------------------------------------
 // bit rows

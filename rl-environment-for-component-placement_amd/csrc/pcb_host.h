@@ -67,8 +67,8 @@ struct DeviceGuard {
 };
 #define DEVICE_GUARD(env) DeviceGuard guard_((env)->device); if (!guard_.ok) return fail(env, PCBENV_EHIP, "hipSetDevice failed")
 
-static inline int align16(long long v) { return (int)((v + 15) & ~15ll); }
-static inline bool is_pin_kind(int k) { return k == PCBENV_PIN || k == PCBENV_SPATIAL; }
+using pcb_layout::align16;
+using pcb_layout::is_pin_kind;
 static inline bool action_format_ok(int fmt) { return fmt == PCBENV_ACTION_TUPLE || fmt == PCBENV_ACTION_FLAT; }
 #define CHECK_ACTION_FORMAT(env, fmt) do { if (!action_format_ok(fmt)) return fail(env, PCBENV_EINVAL, "unknown action format"); } while (0)
 static inline bool stream_capturing(hipStream_t s) {
@@ -81,12 +81,6 @@ static inline bool stream_capturing(hipStream_t s) {
 static inline int stream_stores(const pcbenv *env, int slots) {
     return env->cell_bytes_per_env * env->dp.B * slots > env->stream_threshold;
 }
-
-// Terminal list (DevParams::term_*): four rings.  The allocations are sized for the largest capacity an option can ask for.
-#define PCBENV_TERM_CAP_MAX 4096  // entries per ring of the terminal list = the most terminal workgroups of a launch
-#define TERM_LIST_BYTES ((size_t)4 * PCBENV_TERM_CAP_MAX * sizeof(int))               // DevParams::term_list
-#define TERM_CNT_BYTES ((size_t)4 * TERM_SHARDS * TERM_CNT_STRIDE * sizeof(unsigned) + 32)  // DevParams::term_cnt: a line per shard counter
-#define TERM_ARRIVE_BYTES ((size_t)PCBENV_TERM_CAP_MAX * sizeof(u64))                 // DevParams::term_arrive
 
 // ---- pcb_config.hip --------------------------------------------------------------------------------------------
 int validate(const pcbenv_config *c);                      // the reference constructors' checks, then this library's limits

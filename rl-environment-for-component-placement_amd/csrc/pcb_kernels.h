@@ -1,4 +1,4 @@
-// pcb_kernels.h -- the __global__ kernels: k_reset, k_gather, k_step, k_sample, k_cursor_range
+// pcb_kernels.h -- the __global__ kernel templates of the environment kinds: k_reset, k_gather, k_step
 // Part of libpcbenv.so (CDNA4 / gfx950 only).
 #pragma once
 #include "pcb_team.h"
@@ -145,7 +145,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(4, 8))) __launch_bounds__(64 * NW)
         // last: on gfx9 a wavefront's loads and stores retire through one in-order counter, so a load issued behind a
         // store waits for that store's acknowledgement -- microseconds while the chip is saturated with stores, and this
         // wavefront has a whole transition to do afterwards (0.3 us per launch on the lock-step loop).
-        unsigned *hist = p.term_cnt + 4u * TERM_SHARDS * TERM_CNT_STRIDE;  // behind the counters: four launches' figures, then the one the host was last told
+        unsigned *hist = p.term_cnt + TERM_HIST_OFFSET;  // behind the counters, TERM_HIST_WORDS words: four launches' figures, then the one the host was last told
         unsigned longest = load_agent(p.term_cnt + (((p.seq & 3u) * TERM_SHARDS + threadIdx.x) * TERM_CNT_STRIDE));
         const unsigned h1 = hist[(p.seq + 1u) & 3u], h2 = hist[(p.seq + 2u) & 3u], h3 = hist[(p.seq + 3u) & 3u], told = hist[4];
         for (int o = TERM_SHARDS / 2; o > 0; o >>= 1) longest = max(longest, (unsigned)__shfl_xor((int)longest, o, TERM_SHARDS));
@@ -168,34 +168,3 @@ __global__ __attribute__((amdgpu_waves_per_eu(4, 8))) __launch_bounds__(64 * NW)
     Team<64 * NW>::template run_env<KIND, WW, ROUTES, TRAJ>(p, smem, e, threadIdx.x, actions, fmt, sampled, seed, first_env, step_index,
                                                            num_steps, role, part, pos);
 }
-
-#ifdef PCB_HOST_TU  // plain (non-template) kernels: defined once, in pcbenv_api.hip
-__global__ __launch_bounds__(WAVE) void k_sample(DevParams p, int *__restrict__ actions, int fmt, u64 seed,
-                                                 u64 first_env, u64 step_index) {
-    const int e = blockIdx.x, lane = threadIdx.x;
-    const u64 *vm = (const u64 *)(p.state + (size_t)e * p.stateStride + p.offVm);
-    int o, x, y;
-    Team<64>::sample_action(vm, p, (int)first_env + e, lane, seed, step_index, &o, &x, &y);
-    if (lane == 0) {
-        if (fmt == PCBENV_ACTION_FLAT) actions[e] = o * p.H * p.W + x * p.W + y;
-        else { actions[3 * e] = o; actions[3 * e + 1] = x; actions[3 * e + 2] = y; }
-    }
-}
-
-// min / max of the per-environment queue cursors (one small workgroup; B <= a few thousand headers)
-__global__ __launch_bounds__(256) void k_cursor_range(DevParams p, unsigned *out) {
-    unsigned lo = 0xFFFFFFFFu, hi = 0u;
-    for (int e = threadIdx.x; e < p.B; e += 256) {
-        const unsigned c = load_agent(p.cursor_pub + e);  // not the state block: that copy is only coherent on its own XCD
-        lo = min(lo, c); hi = max(hi, c);
-    }
-    for (int o = 32; o > 0; o >>= 1) { lo = min(lo, (unsigned)__shfl_xor((int)lo, o)); hi = max(hi, (unsigned)__shfl_xor((int)hi, o)); }
-    __shared__ unsigned slo[4], shi[4];
-    if ((threadIdx.x & 63) == 0) { slo[threadIdx.x >> 6] = lo; shi[threadIdx.x >> 6] = hi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; w++) { lo = min(lo, slo[w]); hi = max(hi, shi[w]); }
-        out[0] = lo; out[1] = hi;
-    }
-}
-#endif

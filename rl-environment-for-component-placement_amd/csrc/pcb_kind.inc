@@ -38,34 +38,44 @@ int PCB_FN(pcb_step_routed4)(const StepLaunch &a);
 #define LAUNCH_STEP_ROUTED(WW_, NW_) do { \
     if (a.traj && a.num_steps == 1) LAUNCH_STEP_(WW_, NW_, true, STEP_BUILD_SLOT); else LAUNCH_STEP_INPLACE_OR_ROLLOUT(WW_, NW_, true); } while (0)
 
+// The run-time shape of a launch as compile-time constants: f(ww) / f(ww, nw) get std::integral_constants for the
+// 64-bit words per bit row (1 / 2) and the wavefronts per team (1 / 4), so a generic lambda names its kernel by them.
+typedef std::integral_constant<int, 1> int1_t;
+typedef std::integral_constant<int, 2> int2_t;
+typedef std::integral_constant<int, 4> int4_t;
+template <class F> static inline void with_row_words(int WW, F f) { if (WW == 1) f(int1_t{}); else f(int2_t{}); }
+template <class F> static inline void with_team_shape(int WW, int threads, F f) {
+    with_row_words(WW, [&](auto ww) { if (pcb_layout::wavefronts(threads) == 1) f(ww, int1_t{}); else f(ww, int4_t{}); });
+}
+#define WW_OF(ww) decltype(ww)::value
+#define NW_OF(nw) decltype(nw)::value
+
 #if PCB_HAS(0)
 int PCB_FN(pcb_launch_reset)(const ResetLaunch &a) {
     const DevParams &d = a.d;
-#define LAUNCH_RESET(WW_, NW_) hipLaunchKernelGGL((k_reset<KIND, WW_, NW_>), dim3(d.B), dim3(64 * NW_), d.ldsBytes, a.stream, d, a.mask)
-    if (d.WW == 1) { if (a.threads == 64) LAUNCH_RESET(1, 1); else LAUNCH_RESET(1, 4); }
-    else { if (a.threads == 64) LAUNCH_RESET(2, 1); else LAUNCH_RESET(2, 4); }
+    with_team_shape(d.WW, a.threads, [&](auto ww, auto nw) {
+        hipLaunchKernelGGL((k_reset<KIND, WW_OF(ww), NW_OF(nw)>), dim3(d.B), dim3(64 * NW_OF(nw)), d.ldsBytes, a.stream, d, a.mask);
+    });
     return 0;
 }
 int PCB_FN(pcb_launch_gather)(const GatherLaunch &a) {
     const DevParams &d = a.d;
-#define LAUNCH_GATHER(WW_, NW_) hipLaunchKernelGGL((k_gather<KIND, WW_, NW_>), dim3(d.B), dim3(64 * NW_), d.ldsBytes, a.stream, d, a.g)
-    if (d.WW == 1) { if (a.threads == 64) LAUNCH_GATHER(1, 1); else LAUNCH_GATHER(1, 4); }
-    else { if (a.threads == 64) LAUNCH_GATHER(2, 1); else LAUNCH_GATHER(2, 4); }
+    with_team_shape(d.WW, a.threads, [&](auto ww, auto nw) {
+        hipLaunchKernelGGL((k_gather<KIND, WW_OF(ww), NW_OF(nw)>), dim3(d.B), dim3(64 * NW_OF(nw)), d.ldsBytes, a.stream, d, a.g);
+    });
     return 0;
 }
 int PCB_FN(pcb_step_plain)(const StepLaunch &a) {
     const DevParams &d = a.d;
     if (a.traj && a.num_steps == 1) return PCB_FN(pcb_step_slot)(a);
-    if (d.WW == 1) { if (a.threads == 64) LAUNCH_STEP_INPLACE_OR_ROLLOUT(1, 1, false); else LAUNCH_STEP_INPLACE_OR_ROLLOUT(1, 4, false); }
-    else { if (a.threads == 64) LAUNCH_STEP_INPLACE_OR_ROLLOUT(2, 1, false); else LAUNCH_STEP_INPLACE_OR_ROLLOUT(2, 4, false); }
+    with_team_shape(d.WW, a.threads, [&](auto ww, auto nw) { LAUNCH_STEP_INPLACE_OR_ROLLOUT(WW_OF(ww), NW_OF(nw), false); });
     return 0;
 }
 #endif
 #if PCB_HAS(1)
 int PCB_FN(pcb_step_slot)(const StepLaunch &a) {
     const DevParams &d = a.d;
-    if (d.WW == 1) { if (a.threads == 64) LAUNCH_STEP_(1, 1, false, STEP_BUILD_SLOT); else LAUNCH_STEP_(1, 4, false, STEP_BUILD_SLOT); }
-    else { if (a.threads == 64) LAUNCH_STEP_(2, 1, false, STEP_BUILD_SLOT); else LAUNCH_STEP_(2, 4, false, STEP_BUILD_SLOT); }
+    with_team_shape(d.WW, a.threads, [&](auto ww, auto nw) { LAUNCH_STEP_(WW_OF(ww), NW_OF(nw), false, STEP_BUILD_SLOT); });
     return 0;
 }
 #endif
@@ -82,14 +92,14 @@ int PCB_FN(pcb_launch_step)(const StepLaunch &a) {
 #if PCB_HAS(2)
 int PCB_FN(pcb_step_routed1)(const StepLaunch &a) {
     const DevParams &d = a.d;
-    if (d.WW == 1) LAUNCH_STEP_ROUTED(1, 1); else LAUNCH_STEP_ROUTED(2, 1);
+    with_row_words(d.WW, [&](auto ww) { LAUNCH_STEP_ROUTED(WW_OF(ww), 1); });
     return 0;
 }
 #endif
 #if PCB_HAS(3)
 int PCB_FN(pcb_step_routed4)(const StepLaunch &a) {
     const DevParams &d = a.d;
-    if (d.WW == 1) LAUNCH_STEP_ROUTED(1, 4); else LAUNCH_STEP_ROUTED(2, 4);
+    with_row_words(d.WW, [&](auto ww) { LAUNCH_STEP_ROUTED(WW_OF(ww), 4); });
     return 0;
 }
 #endif

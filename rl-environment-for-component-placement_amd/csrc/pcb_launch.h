@@ -1,5 +1,6 @@
-// pcb_launch.h -- what the host side (pcbenv_api.hip) and the per-kind kernel translation units (pcb_kind_*.hip)
-// share: one launch entry per environment kind, so that the kernel instantiations of the four kinds compile in parallel.
+// pcb_launch.h -- what the host side (pcbenv_api.hip) and the kernel translation units (pcb_kind_*.hip, pcb_sample.hip,
+// pcb_policy*.hip) share: one launch entry per kernel family and environment kind, so that the host side compiles no
+// device code and the kernel instantiations of the four kinds compile in parallel.
 #pragma once
 #include "pcb_device.h"
 
@@ -26,6 +27,11 @@ struct GatherArgs {
     int src_B;
 };
 struct GatherLaunch { DevParams d; GatherArgs g; int threads; hipStream_t stream; };
+
+// pcbenv_sample_actions and pcbenv_queue_cursors (pcb_sample.hip): d.state = the current state set; out = two words, min and max
+struct SampleLaunch { DevParams d; int *actions; int fmt; u64 seed, first_env, step_index; hipStream_t stream; };
+int pcb_launch_sample(const SampleLaunch &a);
+int pcb_launch_cursor_range(const DevParams &d, unsigned *out, hipStream_t stream);
 
 // pcbenv_sample_logits (pcb_policy.hip): d is the handle's parameter block with d.state = the current state set
 struct SampleLogitsArgs {

@@ -1,0 +1,134 @@
+// pcb_layout.h -- the layout contract between the host side and the kernels of libpcbenv.so, stated once: every size,
+// offset and predicate that pcb_config.hip / pcbenv_api.hip allocate by and the kernels index by.  Plain C++17 (it
+// includes only pcbenv.h and <stdint.h>): the host units, the kernel units and tools/layout_check.cpp -- a CPU program
+// that sweeps the geometry and asserts that no zone is smaller than what its user indexes -- compile the same text.
+#pragma once
+#include <stdint.h>
+
+#include "pcbenv.h"
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define PCB_HD __host__ __device__
+#else
+#define PCB_HD
+#endif
+
+#define WAVE 64
+#define MAX_NT 256
+#define HDR_BYTES 64  // sizeof(EnvHdr), pcb_device.h
+
+// ---- terminal list (DevParams::term_*, Team<>::run_env): four rings of TERM_SHARDS shards ------------------------
+#define TERM_CNT_STRIDE 32u  // unsigned words between the shard counters of the terminal list: one 128-byte line each
+#define TERM_SHARD_BITS 4
+#define TERM_SHARDS (1u << TERM_SHARD_BITS)
+// The allocations are sized for the largest capacity an option can ask for.
+#define PCBENV_TERM_CAP_MAX 4096  // entries per ring of the terminal list = the most terminal workgroups of a launch
+#define TERM_LIST_BYTES ((size_t)4 * PCBENV_TERM_CAP_MAX * sizeof(int))  // DevParams::term_list
+// DevParams::term_cnt: a line per shard counter, then k_step's history of list lengths -- hist[0..3] = the longest shard
+// of the last four launches, hist[4] = the figure the host was last told
+#define TERM_HIST_OFFSET (4u * TERM_SHARDS * TERM_CNT_STRIDE)  // in unsigned words: behind the counters of the four rings
+#define TERM_HIST_WORDS 5
+#define TERM_CNT_BYTES ((size_t)TERM_HIST_OFFSET * sizeof(unsigned) + 32)
+#define TERM_ARRIVE_BYTES ((size_t)PCBENV_TERM_CAP_MAX * sizeof(uint64_t))  // DevParams::term_arrive
+static_assert(TERM_HIST_WORDS * sizeof(unsigned) <= 32, "TERM_CNT_BYTES: the history words behind the counters");
+static_assert(PCBENV_TERM_CAP_MAX % TERM_SHARDS == 0 && TERM_SHARDS <= WAVE, "a ring is TERM_SHARDS equal shards, one lane of k_step each");
+
+// ---- terminal reward: LDS zones (pcb_reward.h seg_view, pcb_beam.h) ------------------------------------------------
+#define REWARD_PARTS 2  // reward helpers per listed environment (+ one feature helper with PCBENV_FLAG_AUTO_RESET)
+// compaction buffer of candidate (i, j) pairs, per wavefront: a dense batch is two candidates per lane (128), a
+// sweep step appends at most 4 * 64 to a partial batch (< 128), and what does not fill a batch is moved to the front
+#define PAIR_ENTRIES_PER_WAVE 384
+// [segments X1 Y1 X2 Y2 D | centroids | act nstart total nsum] then a zone used only by the pair count
+// (A DX DY bbox pairs), which the beam search -- finished before the count starts -- overlays with its per-net scratch.
+// (the per-net tables are sized by the configuration's max_num_nets N, not by PCBENV_MAX_NETS: at c3 / c4 that and a fold
+// scratch sized by need bring a workgroup's LDS from 7.8 to 6.6 KB -- 24 instead of 20 one-wavefront workgroups per CU,
+// the headroom the reward helpers start in)
+#define SEG_INTS(P, N) ((P) + ((N) + 1) + 3 + 2 * (N))
+#define SEG_FIXED_BYTES(P, N) ((5 * (P) + 2 * (N)) * 8 + SEG_INTS(P, N) * 4)
+#define SEG_COUNT_BYTES(P, NW) (3 * (P) * 8 + (P) * 4 + PAIR_ENTRIES_PER_WAVE * 2 * (NW))
+#define SEG_LDS_BYTES(P, N, NW, beam) (((SEG_FIXED_BYTES(P, N) + 7) & ~7) + ((beam) > SEG_COUNT_BYTES(P, NW) ? (beam) : SEG_COUNT_BYTES(P, NW)))
+// per net of a beam search of width k (beam_route_lanes): two queues of k * k BsEntry (32 bytes), 16 distances, 16
+// order bytes, two CSet (48 bytes), 16 tuple hashes
+#define BEAM_LDS_PER_NET(k) (64 * (k) * (k) + 16 * 8 + 16 + 2 * 48 + 16 * 4)
+#define BEAM_LDS_BYTES(nets, k) ((nets) * BEAM_LDS_PER_NET(k))
+
+namespace pcb_layout {
+
+PCB_HD constexpr int align16(long long v) { return (int)((v + 15) & ~15ll); }
+PCB_HD constexpr int imax(int a, int b) { return a > b ? a : b; }
+PCB_HD constexpr bool is_pin_kind(int k) { return k == PCBENV_PIN || k == PCBENV_SPATIAL; }
+// threads per environment (64 / 256) -> wavefronts of a team: Team<64 * NW>
+PCB_HD constexpr int wavefronts(int threads) { return threads / WAVE; }
+
+// Whether window_mask (pcb_team_io.h) folds its rows across the lanes of a one-wavefront team, one row per lane, and
+// never touches hf -- `threads` is the team size, NT in the kernels -- or stages the folded rows in LDS at hf.
+// -DPCBENV_FOLD_LDS (A/B builds) stages them always.
+PCB_HD constexpr bool fold_across_lanes(int WW, int threads, int H) {
+#ifdef PCBENV_FOLD_LDS
+    return false;
+#else
+    return WW == 1 && threads == WAVE && H <= WAVE;
+#endif
+}
+PCB_HD constexpr bool fold_in_lds(int WW, int threads, int H) { return !fold_across_lanes(WW, threads, H); }
+PCB_HD constexpr int fold_words(int WW, int threads, int H) { return fold_in_lds(WW, threads, H) ? H * WW : 0; }
+// 64-bit words of the pin kind's row-membership bit map at hf: one bit per row [component, pin_id] of the pin feature
+// tensors (pinRows == C * mp for that kind), so emit_features_* and reset_env index it by any row without a test.
+PCB_HD constexpr int member_words(int kind, int C, int mp) { return kind == PCBENV_PIN ? (C * mp + 63) / 64 : 0; }
+
+// Pin tables of the spatial kind in the class-map zone (pcb_observe.h pin_tables): pid, 2 bytes per component cell, at
+// 0; netmask, 4 bytes per component cell, at the next multiple of 4.
+PCB_HD constexpr int pin_table_netmask_offset(int comp_cells) { return (comp_cells * 2 + 3) & ~3; }
+PCB_HD constexpr int pin_table_bytes(int comp_cells) { return comp_cells * 6 + 4; }
+// The class-map zone: a byte per grid cell for emit_pin_grid; at a reset the same zone holds the pin tables.
+PCB_HD constexpr int class_map_bytes(int kind, int H, int W, int C, int mp) {
+    return kind == PCBENV_SPATIAL ? imax(H * W, pin_table_bytes(C * mp)) : 0;
+}
+
+// Per-episode feature cache of the spatial kind (pcb_observe.h feat_cache_*), per environment: the compact
+// all_components_feature, C x F int16, then component_grid at a 16-byte boundary; feat_cache_emit reads the latter in
+// whole 16-byte chunks, so the stride pads it to whole chunks.
+PCB_HD constexpr int feat_cache_grid_bytes(int C, int mp, int K) { return C * mp * K; }
+PCB_HD constexpr int feat_cache_grid_offset(int C, int F) { return align16(2ll * C * F); }
+PCB_HD constexpr int feat_cache_stride(int C, int F, int mp, int K) {
+    return align16((long long)feat_cache_grid_offset(C, F) + (long long)feat_cache_grid_bytes(C, mp, K));
+}
+
+// What the layout follows from.  C, P, N are the configuration's maxima (0 for a kind without them), threads the team size.
+struct Geometry { int kind, H, W, C, P, N, mh, mw, threads, reward_type, beam_width; };
+// A state block in HBM -- header | occ | vm (both orientations) | comps | pins | rank, padded to 16 bytes -- which a
+// team mirrors at the start of its LDS, and the LDS scratch zones behind the mirror.  All byte offsets; DevParams
+// carries them under the same names.
+struct Layout {
+    int WW;
+    int offOcc, offVm, offComps, offPins, offRank;
+    long long stateStride;
+    int ldsHf, ldsHfWords;  // fold scratch of window_mask, doubling as the pin kind's row-membership bit map
+    int ldsCls, ldsSeg;     // the class map (pin_grid emission) and the route segments (terminal reward) are never live together
+    int ldsBytes;
+};
+PCB_HD constexpr int beam_bytes(const Geometry &g) {
+    return is_pin_kind(g.kind) && g.reward_type != PCBENV_REWARD_CENTROID ? BEAM_LDS_BYTES(g.N, g.beam_width) : 0;
+}
+PCB_HD constexpr int seg_bytes(const Geometry &g) {
+    return is_pin_kind(g.kind) ? SEG_LDS_BYTES(g.P, g.N, wavefronts(g.threads), beam_bytes(g)) : 0;
+}
+PCB_HD constexpr Layout state_layout(const Geometry &g) {
+    Layout l{};
+    l.WW = (g.W + 63) / 64;
+    const int mp = g.mh * g.mw;
+    l.offOcc = HDR_BYTES;
+    l.offVm = l.offOcc + g.H * l.WW * 8;
+    l.offComps = l.offVm + 2 * g.H * l.WW * 8;
+    l.offPins = l.offComps + 8 * g.C;
+    l.offRank = l.offPins + 8 * g.P;  // rank of each pin inside its component (spatial env)
+    l.stateStride = align16((long long)l.offRank + (g.kind == PCBENV_SPATIAL ? g.P : 0));
+    l.ldsHf = (int)l.stateStride;
+    l.ldsHfWords = imax(fold_words(l.WW, g.threads, g.H), member_words(g.kind, g.C, mp));
+    l.ldsCls = align16(l.ldsHf + l.ldsHfWords * 8);
+    l.ldsSeg = l.ldsCls;
+    l.ldsBytes = align16(l.ldsCls + imax(class_map_bytes(g.kind, g.H, g.W, g.C, mp), seg_bytes(g)));
+    return l;
+}
+
+}  // namespace pcb_layout

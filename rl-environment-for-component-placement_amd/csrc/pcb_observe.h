@@ -1,5 +1,5 @@
 // pcb_observe.h -- state block staging through LDS, legal-mask fold + observation emission, pin_grid, feature rows, terminal reward
-// Included by pcb_team.h inside Team<>, so by every unit that includes pcb_kernels.h (pcb_kind_*.hip, pcbenv_api.hip); CDNA4 / gfx950 only.
+// Included by pcb_team.h inside Team<>, so by every unit that includes pcb_kernels.h (pcb_kind_*.hip, pcb_sample.hip, pcb_policy*.hip); CDNA4 / gfx950 only.
 
 // ----------------------------------------------------------------------------------------------
 // shared pieces of reset / step
@@ -211,9 +211,10 @@ struct PinTables { unsigned short *pid; unsigned *netmask; };
 static __device__ inline PinTables pin_tables(const DevParams &p, Lds &l) {
     PinTables t;
     t.pid = (unsigned short *)l.cls;
-    t.netmask = (unsigned *)(l.cls + ((p.C * p.mp * 2 + 3) & ~3));
+    t.netmask = (unsigned *)(l.cls + pcb_layout::pin_table_netmask_offset(p.C * p.mp));
     return t;
 }
+static_assert(PCBENV_MAX_NETS <= 32, "PinTables::netmask: 1u << pr.net (build_pin_tables); emit_component_grid_to: a cell's field = netmask << 1 | exists, in 64 bits");
 static __device__ inline void build_pin_tables(const DevParams &p, Lds &l, int lane) {
     const PinTables t = pin_tables(p, l);
     const int np = l.hdr->npins;
@@ -328,7 +329,7 @@ static __device__ inline void feat_cache_emit(const DevParams &p, Lds &l, int e,
     if (p.buf.component_grid) {
         const int total = p.C * p.mh * p.mw * p.K;
         unsigned char *cg = p.buf.component_grid + (size_t)row * total;
-        const uint4 *src = (const uint4 *)(base + p.featCacheCg);  // (16-byte aligned, and padded to whole chunks)
+        const uint4 *src = (const uint4 *)(base + p.featCacheCg);  // (16-byte aligned, and padded to whole chunks: pcb_layout::feat_cache_stride)
         if ((total & 3) == 0 && (((uintptr_t)cg) & 3) == 0) {
             const ObsDst d = obs_dst(cg, total);
             for (int c16 = lane; c16 < (total + 15) / 16; c16 += NT) store16_or_tail(d, cg, c16 * 16, total, src[c16], p.stream_stores);
@@ -396,7 +397,7 @@ template <int KIND> static __device__ inline void emit_features_compact(const De
                 if (fn) fn[r] = quad(pr);
                 if (fc) ((unsigned short *)fc)[r] = (unsigned short)(pr.net | (pr.comp << 8));
             }
-        } else {  // pin env: rows [component, pin_id] through the membership bit map (always large enough for this kind)
+        } else {  // pin env: rows [component, pin_id] through the membership bit map (a bit per row: pcb_layout::member_words)
             u64 *rowbits = l.hf;
             lds_sync();
             for (int i = lane; i < p.ldsHfWords; i += NT) rowbits[i] = 0ull;
@@ -499,7 +500,11 @@ template <int KIND> static __device__ inline void emit_features_full(const DevPa
                 if (fc) fc[r] = pr.net;
             }
             lds_sync();
-        } else {  // more rows than the bit map holds (tiny grids with large components): zero everything, then the rows
+        } else {
+            // Unreachable: pcb_layout::member_words gives the pin kind a bit per row, so the test above is always true
+            // (tools/layout_check.cpp asserts it over the geometry).  The branch stays because without it the compiler
+            // spills up to 109 more scalar registers in PCBENV_PIN instantiations of k_step (the trajectory-slot build
+            // on one wavefront: 164 -> 273, profiles/layout_contract_refactor.txt); it zeroes everything, then writes the rows.
             for (int i = lane; i < p.pinRows * 4; i += NT) if (fn) fn[i] = 0.0;
             for (int i = lane; i < p.pinRows; i += NT) if (fc) fc[i] = 0.0;
             store_drain_sync();
@@ -534,6 +539,7 @@ static __device__ __forceinline__ void terminal_reward(const DevParams &p, Lds &
         else route_beam_or_both(p, l.hdr, l.pins, l.seg, lane, part, nparts, wsum, cnt);
         if (nparts > 1) {
             if (lane != 0) return;  // one lane carries the shares; nobody else writes anything below
+            static_assert(REWARD_PARTS < 256 && PCBENV_MAX_PINS * (PCBENV_MAX_PINS - 1) / 2 < (1 << 28), "`mine`: 8 bits of arrivals, 28 bits per count of segment pairs");
             const u64 mine = 1ull | ((u64)(unsigned)cnt[0] << 8) | ((u64)(unsigned)cnt[1] << 36);
             const u64 before = atomicAdd((unsigned long long *)(p.term_arrive + pos), (unsigned long long)mine);
             if ((int)(before & 0xFFull) != nparts - 1) return;  // not the last: the totals are somebody else's to write

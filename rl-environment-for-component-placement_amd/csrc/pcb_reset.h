@@ -1,5 +1,5 @@
 // pcb_reset.h -- reset of one environment from the instance queue (k_reset and the in-launch reset of k_step)
-// Included by pcb_team.h inside Team<>, so by every unit that includes pcb_kernels.h (pcb_kind_*.hip, pcbenv_api.hip); CDNA4 / gfx950 only.
+// Included by pcb_team.h inside Team<>, so by every unit that includes pcb_kernels.h (pcb_kind_*.hip, pcb_sample.hip, pcb_policy*.hip); CDNA4 / gfx950 only.
 
 // ----------------------------------------------------------------------------------------------
 // reset (R:310-351, P:1544-1597, S:1487-1549, Q:74-113): header is in LDS; builds the new episode's state in
@@ -7,6 +7,8 @@
 // ----------------------------------------------------------------------------------------------
 // The next queued instance of environment e: header and 8-byte records, all loads issued together.
 struct InstRegs { int nc, nn, np; u64 comp; u64 pin[4]; };
+static_assert(PCBENV_MAX_PINS <= 4 * WAVE, "InstRegs::pin[4]: pin q = lane + r * NT of fetch_instance, NT >= WAVE");
+static_assert(PCBENV_MAX_COMPONENTS <= WAVE, "InstRegs::comp: the record of component `lane` (lane < p.C), NT >= WAVE");
 static __device__ inline void fetch_instance(const DevParams &p, unsigned qcursor, int e, int lane, InstRegs &ir) {
     const unsigned slot = qcursor % (unsigned)p.Q;
     const unsigned char *rec = p.queue + ((size_t)slot * p.B + e) * p.instStride;
@@ -42,6 +44,9 @@ template <int KIND, int WW, bool TRAJ> static __device__ inline void reset_env(c
         if (owner && p.gen_produced && lane == 0 && load_agent(p.gen_produced + e) <= l.hdr->qcursor) atomicOr(p.gen_errors, 1u);
     }
     bool rows_cleared = false;
+    // (The last clause is always true: pcb_layout::member_words gives the pin kind a bit per row.  It stays, like the
+    // unreachable branch of emit_features_full, because without the two nine PCBENV_PIN instantiations of k_step and
+    // one of k_reset spill more scalar registers: profiles/layout_contract_refactor.txt.)
     if (feats && (KIND == PCBENV_PIN || KIND == PCBENV_SPATIAL) && !full && l.hdr->feat_gen == p.bind_gen &&
         (KIND == PCBENV_SPATIAL || p.C * p.mp <= p.ldsHfWords * 64)) {
         u64 *rowbits = l.hf;

@@ -1,5 +1,5 @@
 // pcb_reward.h -- float64 geometry of the routing reward: centroid routes, exact extent pre-filter, intersection count, wirelength
-// Included by pcb_team.h inside Team<>, so by every unit that includes pcb_kernels.h (pcb_kind_*.hip, pcbenv_api.hip); CDNA4 / gfx950 only.
+// Included by pcb_team.h inside Team<>, so by every unit that includes pcb_kernels.h (pcb_kind_*.hip, pcb_sample.hip, pcb_policy*.hip); CDNA4 / gfx950 only.
 
 // ----------------------------------------------------------------------------------------------
 // float64 geometry of the reward (one IEEE operation per operator, see file header)
@@ -23,18 +23,7 @@ static __device__ inline bool is_intersect(double x1, double y1, double x2, doub
 // A route is kept as one segment slot per pin q (slots of net n are nstart[n]..nstart[n+1]-1, so slots are
 // net-major like the reference's route lists); act[q] = 1 if the slot carries a segment.
 struct SegView { double *X1, *Y1, *X2, *Y2, *D, *A, *DX, *DY, *cen; int *act, *nstart, *nsum; unsigned *bbox; unsigned short *pairs; unsigned char *beam; int N; };  // N = max_num_nets: the per-net tables' size
-// compaction buffer of candidate (i, j) pairs, per wavefront: a dense batch is two candidates per lane (128), a
-// sweep step appends at most 4 * 64 to a partial batch (< 128), and what does not fill a batch is moved to the front
-#define PAIR_ENTRIES_PER_WAVE 384
-// [segments X1 Y1 X2 Y2 D | centroids | act nstart total nsum] then a zone used only by the pair count
-// (A DX DY bbox pairs), which the beam search -- finished before the count starts -- overlays with its per-net scratch.
-// (the per-net tables are sized by the configuration's max_num_nets N, not by PCBENV_MAX_NETS: at c3 / c4 that and a fold
-// scratch sized by need bring a workgroup's LDS from 7.8 to 6.6 KB -- 24 instead of 20 one-wavefront workgroups per CU,
-// the headroom the reward helpers start in)
-#define SEG_INTS(P, N) ((P) + ((N) + 1) + 3 + 2 * (N))
-#define SEG_FIXED_BYTES(P, N) ((5 * (P) + 2 * (N)) * 8 + SEG_INTS(P, N) * 4)
-#define SEG_COUNT_BYTES(P, NW) (3 * (P) * 8 + (P) * 4 + PAIR_ENTRIES_PER_WAVE * 2 * (NW))
-#define SEG_LDS_BYTES(P, N, NW, beam) (((SEG_FIXED_BYTES(P, N) + 7) & ~7) + ((beam) > SEG_COUNT_BYTES(P, NW) ? (beam) : SEG_COUNT_BYTES(P, NW)))
+// PAIR_ENTRIES_PER_WAVE and the zone sizes SEG_*: pcb_layout.h (the host sizes the zone by the same formulas)
 static __device__ inline SegView seg_view(double *seg, int P, int N) {
     SegView v;
     v.N = N;

@@ -1,5 +1,5 @@
 // pcb_sampler.h -- uniform legal-action sampler (k_sample and the fused sampler of k_step)
-// Included by pcb_team.h inside Team<>, so by every unit that includes pcb_kernels.h (pcb_kind_*.hip, pcbenv_api.hip); CDNA4 / gfx950 only.
+// Included by pcb_team.h inside Team<>, so by every unit that includes pcb_kernels.h (pcb_kind_*.hip, pcb_sample.hip, pcb_policy*.hip); CDNA4 / gfx950 only.
 
 // ----------------------------------------------------------------------------------------------
 // uniform legal-action sampler (rollout driver; agent/random/random_policy_*.py counterpart)

@@ -1,5 +1,5 @@
 // pcb_step.h -- the step kernel (transition, mask, observations, terminal reward, optional reset and next-action draw) and the queue-cursor reduction
-// Included by pcb_team.h inside Team<>, so by every unit that includes pcb_kernels.h (pcb_kind_*.hip, pcbenv_api.hip); CDNA4 / gfx950 only.
+// Included by pcb_team.h inside Team<>, so by every unit that includes pcb_kernels.h (pcb_kind_*.hip, pcb_sample.hip, pcb_policy*.hip); CDNA4 / gfx950 only.
 
 // ----------------------------------------------------------------------------------------------
 // step kernel (R:353-432, P:1599-1710, S:1551-1661, Q:115-153)
@@ -39,7 +39,7 @@ static __device__ inline void presample_next(const DevParams &p, Lds &l, int sam
 #define MODE_DELEGATED 1
 #define MODE_REWARD 2
 #define MODE_FEATURES 3
-#define REWARD_PARTS 2  // reward helpers per listed environment (+ one feature helper with PCBENV_FLAG_AUTO_RESET)
+// REWARD_PARTS, the reward helpers per listed environment: pcb_layout.h (the host sizes the helper grid by it)
 
 // One transition of environment e with action (o, x, y): validate_action, update_grid, place_component, features,
 // legal mask + observation stream, done, terminal reward, and -- PCBENV_FLAG_AUTO_RESET -- the reset that follows a

@@ -2,8 +2,10 @@
 // Part of libpcbenv.so (CDNA4 / gfx950 only).
 //
 // A team is the set of threads that work on one environment: one wavefront (TN = 64) for grids up to 64 x 64, four
-// (TN = 256) for the 128 x 128 spatial configuration -- and, since round 3, four for the environments of a launch that
-// are certain to end their episode in it, next to one-wavefront teams for the others in the same kernel (see Team<>::run_env).
+// (TN = 256) for the 128 x 128 spatial configuration.  A team is one workgroup.  For an environment that is certain to
+// end its episode in a step launch, k_step starts helper workgroups next to the environment's own -- REWARD_PARTS
+// teams of the same size that share the routing reward and, with PCBENV_FLAG_AUTO_RESET, one that writes the feature
+// half of the reset -- each with its own LDS copy of the state block (see Team<>::run_env).
 // The team size decides the lane stride of every loop, whether a phase boundary needs an s_barrier (a one-wavefront
 // team's LDS traffic executes in program order) and how work is dealt to wavefronts, so it is a compile-time
 // property: the sections below are textually included inside the class template, where NT is TN.  They hold the

@@ -3,8 +3,9 @@
 // Team barrier that waits for LDS traffic only.  __syncthreads() also drains the global stores in flight
 // (s_waitcnt vmcnt(0)), which would serialise the observation write stream between kernel phases.
 // A team of ONE wavefront needs no s_barrier: its LDS traffic executes in program order, only the compiler (and the
-// lgkmcnt wait the fence emits) stand between a write and a read of another lane -- and it MUST not execute one when
-// four independent one-wavefront teams share a workgroup (see Team<>::run_env), where their barrier counts differ.
+// lgkmcnt wait the fence emits) stand between a write and a read of another lane.  (A team is a workgroup of its own,
+// also the helper teams k_step starts for an environment on the terminal list: they share nothing in LDS with the
+// environment's own team and meet it only in term_arrive.)
 static __device__ inline void lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
     if (NT > WAVE) __builtin_amdgcn_s_barrier(); else __builtin_amdgcn_wave_barrier();
@@ -86,8 +87,7 @@ static __device__ inline void emit_zero(unsigned char *dst, long long bytes, int
 // Returns (wave-uniform) whether any bit is set.
 template <int WW>
 static __device__ inline bool window_mask(const u64 *occ, u64 *hf, u64 *vm, int H, int W, int ph, int pw, int lane, unsigned *flag) {
-#ifndef PCBENV_FOLD_LDS
-    if (WW == 1 && NT == WAVE && H <= WAVE) {
+    if (pcb_layout::fold_across_lanes(WW, NT, H)) {  // the predicate that sizes hf: here hf may have no word at all
         // One row per lane: the vertical OR over ph rows by log-step doubling across lanes, like the horizontal one across
         // bits -- no staging of the folded rows in LDS, no barrier, at most three cross-lane steps for ph <= 8.
         u64 a = lane < H ? hfold<1>(Row<1>::load(occ + lane), pw).a : 0ull;
@@ -98,7 +98,6 @@ static __device__ inline bool window_mask(const u64 *occ, u64 *hf, u64 *vm, int 
         if (lane < H) vm[lane] = v;
         return __any(v != 0ull);
     }
-#endif
     for (int r = lane; r < H; r += NT) hfold<WW>(Row<WW>::load(occ + r * WW), pw).store(hf + r * WW);
     lds_sync();
     bool any = false;

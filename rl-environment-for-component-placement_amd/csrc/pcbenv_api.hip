@@ -1,18 +1,13 @@
 // pcbenv_api.hip -- host side of libpcbenv.so's C ABI (include/pcbenv.h): create / destroy / options / bind / load,
-// reset / step / rollout / sample, checkpoint, gather and the logits entry points, plus the two plain kernels k_sample
-// and k_cursor_range.  The environment kernels are instantiated per kind in pcb_kind_*.hip and the policy kernels in
-// pcb_policy*.hip (both reached through pcb_launch.h); pcb_config.hip derives the layout from a configuration and
-// pcb_gen.hip owns the on-device instance generator (pcb_host.h declares what the three share).
-//
-// Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (one IEEE operation per
-// written operator; the only fused multiply-add is the explicit __fma_rn in norm2).
+// reset / step / rollout / sample, checkpoint, gather and the logits entry points.  No kernel is defined here: the
+// environment kernels are instantiated per kind in pcb_kind_*.hip, k_sample and k_cursor_range in pcb_sample.hip and the
+// policy kernels in pcb_policy*.hip (all reached through pcb_launch.h); pcb_config.hip derives the layout from a
+// configuration and pcb_gen.hip owns the on-device instance generator (pcb_host.h declares what the three share).
 #include <stdlib.h>
 
 #include <vector>
 
 #include "pcb_host.h"
-#define PCB_HOST_TU
-#include "pcb_kernels.h"  // k_sample, k_cursor_range (the per-kind kernels are instantiated in pcb_kind_*.hip)
 #include "pcb_launch.h"
 
 static char g_err[256] = "";
@@ -162,7 +157,7 @@ extern "C" int pcbenv_bind_buffers_slots(pcbenv *env, const pcbenv_buffers *b, i
     DevParams &d = env->dp;
     const int k = env->cfg.kind;
     if (k == PCBENV_SPATIAL && num_slots > 1 && !d.feat_cache) {  // the episode-constant bytes a trajectory step copies
-        const int cg = align16(2ll * d.C * d.F), stride = align16((long long)cg + (long long)d.C * d.mh * d.mw * d.K);
+        const int cg = pcb_layout::feat_cache_grid_offset(d.C, d.F), stride = pcb_layout::feat_cache_stride(d.C, d.F, d.mp, d.K);
         if (hipMalloc((void **)&d.feat_cache, (size_t)stride * d.B) != hipSuccess || hipMalloc((void **)&d.feat_cache_tag, 4 * (size_t)d.B) != hipSuccess) {
             if (d.feat_cache) hipFree(d.feat_cache);  // both or neither: the next bind tries again
             d.feat_cache = 0; d.feat_cache_tag = 0;
@@ -383,8 +378,7 @@ extern "C" int pcbenv_sample_actions(pcbenv *env, int32_t *actions_dev, int32_t 
     if (!env || !actions_dev) return fail(env, PCBENV_EINVAL, "null argument");
     CHECK_ACTION_FORMAT(env, fmt);
     DEVICE_GUARD(env);
-    hipLaunchKernelGGL(k_sample, dim3(env->dp.B), dim3(WAVE), 0, (hipStream_t)stream, env->dp, actions_dev, fmt,
-                       (u64)seed, (u64)first_env_index, (u64)step_index);
+    pcb_launch_sample(SampleLaunch{env->dp, actions_dev, fmt, (u64)seed, (u64)first_env_index, (u64)step_index, (hipStream_t)stream});
     HIP_TRY(env, hipGetLastError());
     return PCBENV_OK;
 }
@@ -596,7 +590,7 @@ extern "C" int pcbenv_queue_cursors(pcbenv *env, uint32_t *min_out, uint32_t *ma
     if (!env || !min_out || !max_out) return fail(env, PCBENV_EINVAL, "null argument");
     DEVICE_GUARD(env);
     if (!env->scratch) HIP_TRY(env, hipMalloc((void **)&env->scratch, 16));
-    hipLaunchKernelGGL(k_cursor_range, dim3(1), dim3(256), 0, (hipStream_t)stream, env->dp, env->scratch);
+    pcb_launch_cursor_range(env->dp, env->scratch, (hipStream_t)stream);
     unsigned host[2] = {0, 0};
     HIP_TRY(env, hipMemcpyAsync(host, env->scratch, 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIP_TRY(env, hipStreamSynchronize((hipStream_t)stream));

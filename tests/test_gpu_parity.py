@@ -592,6 +592,16 @@ def test_trajectory_slots_every_tensor(name, mode):
                         num_slots=5, max_steps=60, compact=True)
 
 
+@pytest.mark.parametrize("threads", [0, 256])
+def test_pin_kind_trajectory_rows_through_the_bit_map(threads):
+    """The pin kind's float64 and compact pin-feature tensors of a trajectory slot go through the row-membership bit map
+    at hf, which csrc/pcb_layout.h sizes with a bit per row: on a 10 x 10 grid the default one-wavefront team folds
+    across lanes, so the bit map's 2 words are all of hf; threads_per_env = 256 stages the fold's 10 rows in the same words."""
+    cfg = EnvConfig.pin(10, 10, 1, 1, 2, 4, 2, 4, 6, 1, 2, 4, 5, 2, "both", 2, 0.5)
+    for compact in (False, True):
+        _oracle_rollout(cfg, 8, episodes=2, num_slots=3, threads=threads, compact=compact)
+
+
 @pytest.mark.parametrize("name,B,T,S,compact", [("c3", 512, 40, 41, False), ("c4", 256, 36, 37, False), ("c2", 512, 20, 7, False), ("c5", 64, 40, 41, False),
                                                 ("small_spatial", 256, 30, 31, False), ("c1", 64, 12, 13, False),
                                                 # BASELINE batches, one episode + the reset behind it, every tensor of every slot

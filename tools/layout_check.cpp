@@ -1,0 +1,143 @@
+// layout_check.cpp -- CPU guard of the host/kernel layout contract (csrc/pcb_layout.h, the only header included).
+// Sweeps the geometry -- all four kinds, grid sides around the 64-column word and the one-wavefront fold, both team
+// sizes, components / pins per component / nets at their minima and at the PCBENV_MAX_* limits, the three reward types,
+// beam widths 1-4 -- and asserts, with the indexing of each zone's user written out here independently of the header's
+// size functions, that every zone holds what its user indexes and that zones live together do not overlap.
+// Build and run (tests/test_layout_contract.py does that):
+//   g++ -std=c++17 -fsanitize=address,undefined -Iinclude -Irl-environment-for-component-placement_amd/csrc
+//       -o layout_check tools/layout_check.cpp && ./layout_check
+#include "pcb_layout.h"
+
+#include <stdio.h>
+#include <stdlib.h>
+
+using namespace pcb_layout;
+
+static long long g_checks = 0;
+static Geometry g_now;
+#define CHECK(cond)                                                                                                     \
+    do {                                                                                                                \
+        g_checks++;                                                                                                     \
+        if (!(cond)) {                                                                                                  \
+            fprintf(stderr, "layout_check: %s fails (line %d) for kind %d H %d W %d C %d P %d N %d mh %d mw %d threads %d reward %d beam %d\n", \
+                    #cond, __LINE__, g_now.kind, g_now.H, g_now.W, g_now.C, g_now.P, g_now.N, g_now.mh, g_now.mw,       \
+                    g_now.threads, g_now.reward_type, g_now.beam_width);                                                \
+            exit(1);                                                                                                    \
+        }                                                                                                               \
+    } while (0)
+
+// last byte + 1 that seg_view's arrays (pcb_reward.h) and the beam search's per-net scratch (pcb_beam.h
+// beam_route_lanes) reach from the start of the segment zone
+static long long seg_zone_end(int P, int N, int NW, bool routes, int k) {
+    long long off = 0;
+    off += 5ll * P * 8;            // X1 Y1 X2 Y2 D
+    off += 2ll * N * 8;            // cen: cx[N], cy[N]
+    off += 4ll * P;                // act[P]
+    off += 4ll * (N + 1 + 3);      // nstart[N + 1], 3 spare words
+    off += 4ll * 2 * N;            // nsum[2 N]
+    const long long fixed_end = off;
+    const long long overlay = (off + 7) & ~7ll;  // v.beam: the zone the pair count and the beam search take in turn
+    long long count_end = overlay + 3ll * P * 8;                  // A DX DY
+    count_end += 4ll * P;                                         // bbox[P]
+    count_end += 2ll * PAIR_ENTRIES_PER_WAVE * NW;                // pairs, per wavefront
+    long long beam_end = overlay;
+    if (routes) {
+        const long long per_net = 2ll * k * k * 32 + 16 * 8 + 16 + 2 * 48 + 16 * 4;  // queue, next | dist | order | A, R | hs
+        CHECK(BEAM_LDS_PER_NET(k) >= per_net);                    // the stride between two nets' scratch
+        beam_end = overlay + (long long)(N - 1) * BEAM_LDS_PER_NET(k) + per_net;
+    }
+    const long long end = count_end > beam_end ? count_end : beam_end;
+    return end > fixed_end ? end : fixed_end;
+}
+
+static int g_max_lds = 0;
+static void check_one(const Geometry &g) {
+    g_now = g;
+    const Layout l = state_layout(g);
+    const int mp = g.mh * g.mw, K = g.N + 1, WW = l.WW, NW = wavefronts(g.threads);
+    const bool spatial = g.kind == PCBENV_SPATIAL, pins = is_pin_kind(g.kind);
+    CHECK(WW == 1 || WW == 2);
+    CHECK(NW == 1 || NW == 4);
+    CHECK(WW * 64 >= g.W);
+    // ---- the state block: header | occ | vm | comps | pins | rank, mirrored at the start of LDS -----------------
+    CHECK(l.offOcc >= HDR_BYTES);
+    CHECK(l.offVm >= l.offOcc + 8 * g.H * WW);           // occ[r * WW + w], r < H
+    CHECK(l.offComps >= l.offVm + 8 * 2 * g.H * WW);      // vm[o * H * WW + r * WW + w], o < 2
+    CHECK(l.offPins >= l.offComps + 8 * g.C);             // comps[c], c < C
+    CHECK(l.offRank >= l.offPins + 8 * g.P);              // pins[q], q < P
+    CHECK(l.stateStride >= l.offRank + (spatial ? g.P : 0));  // rank[q], q < P
+    CHECK(l.offOcc % 8 == 0 && l.offVm % 8 == 0 && l.offComps % 8 == 0 && l.offPins % 8 == 0);  // 64-bit words and records
+    CHECK(l.stateStride % 16 == 0);                       // load_state / store_state move 16-byte chunks
+    // ---- hf: the folded rows of window_mask, or the pin kind's row-membership bit map (never live together) ------
+    CHECK(l.ldsHf >= l.stateStride && l.ldsHf % 8 == 0);
+    if (fold_in_lds(WW, g.threads, g.H)) CHECK(l.ldsHfWords >= g.H * WW);  // hf[r * WW + w], r < H
+    if (g.kind == PCBENV_PIN) {
+        const int pin_rows = g.C * mp;                    // DevParams::pinRows of the pin kind
+        CHECK(l.ldsHfWords >= (pin_rows - 1) / 64 + 1);   // rowbits[r >> 6], r < pinRows
+    }
+    // ---- behind hf: the class map / pin tables and the route segments share one zone (never live together) ------
+    CHECK(l.ldsCls >= l.ldsHf + 8 * l.ldsHfWords);
+    CHECK(l.ldsSeg >= l.ldsHf + 8 * l.ldsHfWords);
+    CHECK(l.ldsCls % 16 == 0 && l.ldsSeg % 8 == 0);       // emit_pin_grid writes the class map 16 bytes at a time; doubles
+    if (spatial) {
+        CHECK(l.ldsBytes - l.ldsCls >= g.H * g.W);        // cls[cell], cell < H * W
+        const int cells = g.C * mp, nm = pin_table_netmask_offset(cells);
+        CHECK(nm >= 2 * cells && nm % 4 == 0);            // pid[i], i < C * mp (16-bit); netmask is 32-bit words
+        CHECK(l.ldsBytes - l.ldsCls >= nm + 4 * cells);   // netmask[i], i < C * mp
+        CHECK(pin_table_bytes(cells) >= nm + 4 * cells);
+        CHECK(class_map_bytes(g.kind, g.H, g.W, g.C, mp) <= l.ldsBytes - l.ldsCls);
+    }
+    if (pins) {
+        const bool routes = g.reward_type != PCBENV_REWARD_CENTROID;
+        const long long end = seg_zone_end(g.P, g.N, NW, routes, g.beam_width);
+        CHECK(SEG_LDS_BYTES(g.P, g.N, NW, routes ? BEAM_LDS_BYTES(g.N, g.beam_width) : 0) >= end);
+        CHECK(l.ldsBytes - l.ldsSeg >= end);
+    }
+    CHECK(l.ldsBytes % 16 == 0 && l.ldsBytes >= l.ldsCls);
+    if (l.ldsBytes > g_max_lds) g_max_lds = l.ldsBytes;
+    // ---- the per-episode feature cache (spatial, trajectory layout) ------------------------------------------------
+    if (spatial) {
+        const int F = 5 + mp, total = g.C * mp * K;       // bytes of one environment's component_grid
+        const int cg = feat_cache_grid_offset(g.C, F), stride = feat_cache_stride(g.C, F, mp, K);
+        CHECK(cg >= 2 * g.C * F && cg % 16 == 0);         // cf[i], i < C * F (int16); the grid is read as uint4
+        CHECK(stride >= cg + 16 * ((total + 15) / 16));   // src[c16], c16 < ceil(total / 16): whole 16-byte chunks
+        CHECK(stride % 16 == 0);                          // every environment's block starts on a chunk boundary
+        CHECK(feat_cache_grid_bytes(g.C, mp, K) == total);
+    }
+}
+
+int main() {
+    // the terminal list's allocations against what k_step and run_env index
+    {
+        g_now = Geometry{};
+        const unsigned last_counter = ((3u * TERM_SHARDS) + (TERM_SHARDS - 1u)) * TERM_CNT_STRIDE;  // term_cnt[(ring * TERM_SHARDS + shard) * TERM_CNT_STRIDE]
+        CHECK(last_counter < TERM_HIST_OFFSET);
+        CHECK(TERM_CNT_BYTES >= (TERM_HIST_OFFSET + TERM_HIST_WORDS) * sizeof(unsigned));           // hist[0 .. TERM_HIST_WORDS)
+        CHECK(TERM_LIST_BYTES >= 4u * PCBENV_TERM_CAP_MAX * sizeof(int));                            // term_list[ring * term_cap + pos]
+        CHECK(TERM_ARRIVE_BYTES >= PCBENV_TERM_CAP_MAX * sizeof(uint64_t));                          // term_arrive[pos]
+    }
+    static const int sides[] = {1, 5, 16, 63, 64, 65, 100, PCBENV_MAX_SIDE};
+    static const int team[] = {WAVE, MAX_NT};
+    long long geometries = 0;
+    for (int kind = PCBENV_SQUARE; kind <= PCBENV_SPATIAL; kind++)
+    for (int H : sides) for (int W : sides) for (int threads : team) {
+        const int shorter = H < W ? H : W;
+        if (kind == PCBENV_SQUARE) { check_one(Geometry{kind, H, W, 0, 0, 0, 0, 0, threads, 0, 0}); geometries++; continue; }
+        const int big = shorter < 8 ? shorter : 8;  // 8 x 8 = PCBENV_MAX_PINS_PER_COMPONENT, where the grid allows it
+        const int comps[] = {1, PCBENV_MAX_COMPONENTS < H * W ? PCBENV_MAX_COMPONENTS : H * W};
+        const int comp_side[] = {1, big};
+        for (int C : comps) for (int mh : comp_side) for (int mw : comp_side) {
+            if (!is_pin_kind(kind)) { check_one(Geometry{kind, H, W, C, 0, 0, mh, mw, threads, 0, 0}); geometries++; continue; }
+            const int nets[] = {1, PCBENV_MAX_NETS}, per_net[] = {2, PCBENV_MAX_PINS_PER_NET};
+            for (int N : nets) for (int ppn : per_net) {
+                const int a = ppn * N, b = C * mh * mw;  // pcbenv_max_total_pins
+                int P = a < b ? a : b;
+                if (P > PCBENV_MAX_PINS) P = PCBENV_MAX_PINS;  // (validate refuses more: the limit itself is the case to check)
+                for (int reward = PCBENV_REWARD_BEAM; reward <= PCBENV_REWARD_BOTH; reward++)
+                    for (int k = 1; k <= PCBENV_MAX_BEAM_WIDTH; k++) { check_one(Geometry{kind, H, W, C, P, N, mh, mw, threads, reward, k}); geometries++; }
+            }
+        }
+    }
+    printf("layout_check ok: %lld geometries, %lld checks, largest LDS block %d bytes\n", geometries, g_checks, g_max_lds);
+    return 0;
+}
