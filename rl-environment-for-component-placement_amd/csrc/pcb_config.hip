@@ -121,7 +121,7 @@ void derive_layout(const pcbenv_config &c, pcbenv *env) {
 #ifdef PCBENV_EXPERIMENTS
     { const char *ev = getenv("PCBENV_LDS_MIN"); if (ev && atoi(ev) > d.ldsBytes) d.ldsBytes = align16(atoi(ev)); }  // occupancy experiments
 #endif
-    // Terminal list: on for the kinds with a routing reward (Team<>::run_env); B / 8 entries cover twice the
+    // Terminal list: on for the kinds with a routing reward (run_env, pcb_step.h); B / 8 entries cover twice the
     // 1 / max_num_components of the batch that ends an episode per launch when the phases are spread evenly over a
     // 16-component episode (PCBENV_OPT_TERMINAL_TEAMS changes or disables it).
     env->seq = 0;

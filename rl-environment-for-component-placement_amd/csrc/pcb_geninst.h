@@ -82,17 +82,6 @@ template <int G> __device__ inline int grl(int v, int idx, int lane) {
 template <int G> __device__ inline double grl(double v, int idx, int lane) {
     return __hiloint2double(grl<G>(__double2hiint(v), idx, lane), grl<G>(__double2loint(v), idx, lane));
 }
-template <int G> __device__ inline int gscan(int x, int lane) {  // inclusive prefix sum inside the group (DPP)
-    const int row = lane & 15;
-    int t;
-    t = __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, false); if (row >= 1) x += t;   // row_shr:1
-    t = __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, false); if (row >= 2) x += t;   // row_shr:2
-    t = __builtin_amdgcn_update_dpp(0, x, 0x114, 0xF, 0xF, false); if (row >= 4) x += t;   // row_shr:4
-    t = __builtin_amdgcn_update_dpp(0, x, 0x118, 0xF, 0xF, false); if (row >= 8) x += t;   // row_shr:8
-    if (G >= 32) { t = __builtin_amdgcn_update_dpp(0, x, 0x142, 0xF, 0xF, false); if ((lane & 31) >= 16) x += t; }  // row_bcast:15
-    if (G == 64) { t = __builtin_amdgcn_update_dpp(0, x, 0x143, 0xF, 0xF, false); if (lane >= 32) x += t; }         // row_bcast:31
-    return x;
-}
 template <int G> __device__ inline u64 gballot(bool pred, int lane) {  // the group's bits of the ballot, at bit 0
     const u64 b = __ballot(pred);
     if (G == WAVE) return b;
@@ -116,7 +105,7 @@ template <int G> __device__ inline void mt_regenerate(LdsU32 mt, int gl) {  // m
 }
 // One generator state between HBM and LDS, ten words of a lane in flight at a time (through the volatile LDS pointer
 // every element would otherwise wait for the one before).
-template <int G> __device__ inline void mt_to_lds(LdsU32 dst, const unsigned *src, int gl) {
+template <int G, typename Dst, typename Src> __device__ inline void mt_copy(Dst dst, Src src, int gl) {
     for (int b0 = 0; b0 < 624; b0 += 10 * G) {
         unsigned t[10];
         #pragma unroll
@@ -125,14 +114,9 @@ template <int G> __device__ inline void mt_to_lds(LdsU32 dst, const unsigned *sr
         for (int r = 0; r < 10; r++) if (b0 + r * G + gl < 624) dst[b0 + r * G + gl] = t[r];
     }
 }
-template <int G> __device__ inline void mt_from_lds(unsigned *dst, LdsU32 src, int gl) {
-    for (int b0 = 0; b0 < 624; b0 += 10 * G) {
-        unsigned t[10];
-        #pragma unroll
-        for (int r = 0; r < 10; r++) t[r] = b0 + r * G + gl < 624 ? src[b0 + r * G + gl] : 0u;
-        #pragma unroll
-        for (int r = 0; r < 10; r++) if (b0 + r * G + gl < 624) dst[b0 + r * G + gl] = t[r];
-    }
+__device__ inline unsigned mt_temper(unsigned v) {  // mt19937ar.c genrand_int32's output transform
+    v ^= (v >> 11); v ^= (v << 7) & 0x9d2c5680u; v ^= (v << 15) & 0xefc60000u;
+    return v ^ (v >> 18);
 }
 // The stream of tempered words, G at a time in a register (group lane i holds word base + i): a draw is one
 // cross-lane read instead of an LDS round trip.
@@ -146,12 +130,7 @@ template <int G> struct MtReader {
         if (pos >= 624) { mt_regenerate<G>(mt, gl); pos = 0; base = -1; }
         if (base < 0 || pos >= base + G) {
             base = pos;
-            unsigned v = base + gl < 624 ? mt[base + gl] : 0u;
-            v ^= (v >> 11);
-            v ^= (v << 7) & 0x9d2c5680u;
-            v ^= (v << 15) & 0xefc60000u;
-            v ^= (v >> 18);
-            cache = v;
+            cache = mt_temper(base + gl < 624 ? mt[base + gl] : 0u);
         }
         const unsigned out = (unsigned)grl<G>((int)cache, pos - base, lane);
         pos++;
@@ -274,7 +253,7 @@ template <int G> struct NpStream {  // NumPy legacy RandomState pieces
         const double pp_l = upper_l ? 1.0 - P_l : P_l, qq_l = 1.0 - pp_l, lg_l = log(qq_l);
         const bool bin_l = gl < d - 1, draws_l = bin_l && P_l != 0.0;   // random_binomial returns 0 without a draw for p == 0
         if (rd.pos >= 624) { mt_regenerate<G>(rd.mt, gl); rd.pos = 0; rd.base = -1; }
-        const int incl = gscan<G>(draws_l ? 1 : 0, lane);
+        const int incl = group_inclusive_scan<G>(draws_l ? 1 : 0, lane);
         const int ndraw = grl<G>(incl, G - 1, lane);
         bool fast = n <= 15 && rd.pos + 2 * ndraw <= 624;
 #ifdef GEN_COUNT_FALLBACK
@@ -285,9 +264,7 @@ template <int G> struct NpStream {  // NumPy legacy RandomState pieces
             bool bad_l = false;
             if (draws_l) {
                 const int w0 = rd.pos + 2 * (incl - 1);
-                unsigned a = rd.mt[w0], b = rd.mt[w0 + 1];
-                a ^= (a >> 11); a ^= (a << 7) & 0x9d2c5680u; a ^= (a << 15) & 0xefc60000u; a ^= (a >> 18);
-                b ^= (b >> 11); b ^= (b << 7) & 0x9d2c5680u; b ^= (b << 15) & 0xefc60000u; b ^= (b >> 18);
+                const unsigned a = mt_temper(rd.mt[w0]), b = mt_temper(rd.mt[w0 + 1]);
                 const double U0 = ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) / 9007199254740992.0;
                 for (int m = 1; m <= n; m++) {  // legacy_random_binomial_inversion(m, pp) on this bin's variate
                     if (!(pp_l * (double)m <= 30.0)) { bad_l = true; break; }
@@ -446,21 +423,21 @@ template <int G> __device__ inline int gen_record(const GenParams &c, const GrpL
         }
         int k;
         {   // the first k >= kcomp positions with enough room for the net (the reference grows k one by one)
-            const int cum = gscan<G>(gl < ncomp ? a_s : 0, lane);
+            const int cum = group_inclusive_scan<G>(gl < ncomp ? a_s : 0, lane);
             const u64 enough = gballot<G>(gl >= kcomp - 1 && gl < ncomp && cum >= unassigned, lane);
             if (!enough) return PCBENV_EINVAL;
             k = __ffsll((long long)enough);
         }
         int pin_in_net = 0;
         while (unassigned > 0) {
-            const int cum = gscan<G>(gl < k ? a_s : 0, lane);
+            const int cum = group_inclusive_scan<G>(gl < k ? a_s : 0, lane);
             const int tot = grl<G>(cum, k - 1, lane);
             const double prob_l = (double)a_s / (double)tot;
             const int cnt_l = rs.multinomial(unassigned, prob_l, k, &ok);
             if (!ok) return PCBENV_ELIMIT;
             const int m_l = gl < k ? min(cnt_l, a_s) : 0;
             a_s -= m_l;
-            const int incl = gscan<G>(m_l, lane);
+            const int incl = group_inclusive_scan<G>(m_l, lane);
             const int assigned = grl<G>(incl, G - 1, lane);
             for (int t = 0; t < m_l; t++) {
                 // creation id of the pi-th pin of net n (spatial); index in this batch (pin env, quirk Q1)
@@ -476,8 +453,8 @@ template <int G> __device__ inline int gen_record(const GenParams &c, const GrpL
     }
     GSTAMP(4);
     // NumPy's generator leaves LDS, CPython's comes in
-    mt_from_lds<G>(g->np_mt, L.mt, gl);
-    mt_to_lds<G>(L.mt, g->py_mt, gl);
+    mt_copy<G>(g->np_mt, L.mt, gl);
+    mt_copy<G>(L.mt, g->py_mt, gl);
     GSTAMP(5);
     rs.rd.base = -1;  // (the words in LDS are CPython's now; NumPy's come back with the next record)
     MtReader<G> py{L.mt, py_pos_, -1, 0u};
@@ -503,7 +480,7 @@ template <int G> __device__ inline int gen_record(const GenParams &c, const GrpL
                 unsigned r;
                 do { r = py.next(lane) >> (32 - kbits); } while ((int)r >= ncell);  // _randbelow_with_getrandbits
                 int cell = 0, k = (int)r;
-                {   // position of the k-th set bit: binary search on popcounts
+                {   // position of the k-th set bit: select_bit (pcb_sampler.h) written out -- through the call k_gen_fill<16|32|64> schedule differently
                     u64 wbits = cells;
                     #pragma unroll
                     for (int width = 32; width >= 1; width >>= 1) {
@@ -522,7 +499,7 @@ template <int G> __device__ inline int gen_record(const GenParams &c, const GrpL
     #pragma unroll
     for (int ch = 0; ch < 4; ch++) if (ch * G + gl < total) prec[ch * G + gl] = rec_r[ch];
     if (gl == 0) { hdr[1] = nn; hdr[2] = total; }
-    mt_from_lds<G>(g->py_mt, L.mt, gl);
+    mt_copy<G>(g->py_mt, L.mt, gl);
     GSTAMP(7);
     py_pos_ = py.pos;
     return PCBENV_OK;
@@ -566,14 +543,14 @@ __global__ __attribute__((amdgpu_waves_per_eu(4, 8))) __launch_bounds__(WAVE) vo
         NpStream<G> rs{MtReader<G>{L.mt, g->np_pos, -1, 0u}, lane, g->has_gauss, g->gauss};
         int py_pos = g->py_pos, status = 0;
         while (produced - cursor < (unsigned)c.Q) {
-            mt_to_lds<G>(L.mt, g->np_mt, gl);
+            mt_copy<G>(L.mt, g->np_mt, gl);
             rs.rd.base = -1;
             status = gen_record<G>(c, L, g, rs, py_pos, lane);
             if (status != PCBENV_OK) break;  // (the stream stops here; its state is not needed any more)
             unsigned long long *dst = (unsigned long long *)(c.queue + ((size_t)(produced % (unsigned)c.Q) * c.B + e) * c.instStride);
             for (int i = gl; i < words; i += G) dst[i] = L.rec[i];
             produced++;
-            if (c.kind == PCBENV_RECT) mt_from_lds<G>(g->np_mt, L.mt, gl);  // (the others swapped it out before step 10)
+            if (c.kind == PCBENV_RECT) mt_copy<G>(g->np_mt, L.mt, gl);  // (the others swapped it out before step 10)
         }
         if (gl == 0) { g->np_pos = rs.rd.pos; g->py_pos = py_pos; g->has_gauss = rs.has_gauss; g->gauss = rs.gauss; g->status = status; }
         __threadfence();  // the records before the count

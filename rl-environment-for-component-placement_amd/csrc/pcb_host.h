@@ -9,7 +9,7 @@
 #include <string.h>
 
 #include "pcbenv.h"
-#include "pcb_device.h"
+#include "pcb_records.h"
 
 #pragma GCC visibility push(hidden)  // internal to the library: only include/pcbenv.h is exported from these units
 
@@ -35,7 +35,7 @@ struct pcbenv {
     hipEvent_t ev_snap, ev_fill;
     long long since_waited, since_outstanding;
     int gen_lanes;      // PCBENV_OPT_GEN_LANES: 0 = the narrowest group the configuration allows
-    // terminal list (Team<>::run_env): launch counter, list entries that get helper teams per launch (0 = none)
+    // terminal list (run_env, pcb_step.h): launch counter, list entries that get helper teams per launch (0 = none)
     unsigned seq;
     int term_wgs;
     unsigned *term_seen_host;     // mapped host memory the step kernel reports its list length to (DevParams::term_seen)

@@ -4,19 +4,6 @@
 #include "pcb_team.h"
 #include "pcb_launch.h"
 
-// Workgroups go to the eight XCDs round-robin (blockIdx.x % 8).  Environment of workgroup `block` (the environments'
-// workgroups follow `head` others): XCD * B/8 + turn, so that each XCD -- each L2 -- owns a contiguous eighth of every
-// tensor.  Rows smaller than a cache line (reward, done, info, actions, the compact features) and the ends of the
-// others then share their lines with neighbours under the SAME L2, which merges them into whole-line writes; with
-// environment = blockIdx.x every such line went to memory in up to eight pieces (c3: 19.65 -> 19.1 us per launch, c4
-// 44.8 -> 44.3, same-box A/B in profiles/r3/ab_xcd_contiguous_environments.txt).  Any bijection serves: the
-// environments are independent, and nothing else depends on which workgroup runs which.
-__device__ inline int xcd_contiguous_env(int block, int head, int B) {
-    if (B & 7) return block - head;
-    const int x = block & 7, first = head + ((x - head) & 7);  // first: the XCD's first environment workgroup
-    return x * (B >> 3) + (block - first) / 8;
-}
-
 template <int KIND, int WW, int NW>
 __global__ __launch_bounds__(64 * NW) void k_reset(DevParams p, const unsigned char *__restrict__ mask) {
     typedef Team<64 * NW> T;
@@ -24,8 +11,8 @@ __global__ __launch_bounds__(64 * NW) void k_reset(DevParams p, const unsigned c
     const int e = xcd_contiguous_env((int)blockIdx.x, 0, p.B), lane = threadIdx.x;
     if (mask && !mask[e]) return;
     T::load_state(smem, p, e, lane);  // cursor / episode survive; the old pins tell which feature rows to clear
-    typename T::Lds l = T::carve(smem, p);
-    const int row = T::out_row(p, p.slot, e);
+    Lds l = carve(smem, p);
+    const int row = out_row(p, p.slot, e);
     T::template reset_env<KIND, WW, true>(p, l, e, row, lane);
     if (lane == 0) {
         l.hdr->pre_action = 0u;  // the mask changed under any presampled action
@@ -61,7 +48,7 @@ __global__ __launch_bounds__(64 * NW) void k_gather(DevParams p, GatherArgs g) {
     if (!take && j != -1 && g.errors && lane == 0) atomicOr(g.errors, 1u);
     const unsigned char *own = p.state + (size_t)e * p.stateStride;
     T::load_state_from(smem, take ? g.src_state + (size_t)j * p.stateStride : own, p, lane);
-    typename T::Lds l = T::carve(smem, p);
+    Lds l = carve(smem, p);
     if (take) {
         if (lane == 0) {
             const EnvHdr *oh = (const EnvHdr *)own;
@@ -71,7 +58,7 @@ __global__ __launch_bounds__(64 * NW) void k_gather(DevParams p, GatherArgs g) {
             if (KIND == PCBENV_PIN || KIND == PCBENV_SPATIAL) l.hdr->feat_gen = p.bind_gen;
         }
         T::lds_sync();
-        const int row = T::out_row(p, p.slot, e);
+        const int row = out_row(p, p.slot, e);
         if (KIND == PCBENV_SPATIAL) T::build_pin_tables(p, l, lane);
         T::template emit_features_full<KIND>(p, l, row, lane);
         if (KIND == PCBENV_SPATIAL) {

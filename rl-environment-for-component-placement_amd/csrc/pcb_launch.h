@@ -2,7 +2,9 @@
 // pcb_policy*.hip) share: one launch entry per kernel family and environment kind, so that the host side compiles no
 // device code and the kernel instantiations of the four kinds compile in parallel.
 #pragma once
-#include "pcb_device.h"
+#include <hip/hip_runtime.h>
+
+#include "pcb_records.h"
 
 struct StepLaunch {
     DevParams d;

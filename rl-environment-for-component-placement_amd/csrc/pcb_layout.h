@@ -9,13 +9,15 @@
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define PCB_HD __host__ __device__
+#define PCB_UNROLL _Pragma("unroll")  // (`#pragma unroll` is unknown to a host compiler)
 #else
 #define PCB_HD
+#define PCB_UNROLL
 #endif
 
 #define WAVE 64
 #define MAX_NT 256
-#define HDR_BYTES 64  // sizeof(EnvHdr), pcb_device.h
+#define HDR_BYTES 64  // sizeof(EnvHdr), pcb_records.h
 
 // ---- terminal list (DevParams::term_*, Team<>::run_env): four rings of TERM_SHARDS shards ------------------------
 #define TERM_CNT_STRIDE 32u  // unsigned words between the shard counters of the terminal list: one 128-byte line each
@@ -33,7 +35,7 @@
 static_assert(TERM_HIST_WORDS * sizeof(unsigned) <= 32, "TERM_CNT_BYTES: the history words behind the counters");
 static_assert(PCBENV_TERM_CAP_MAX % TERM_SHARDS == 0 && TERM_SHARDS <= WAVE, "a ring is TERM_SHARDS equal shards, one lane of k_step each");
 
-// ---- terminal reward: LDS zones (pcb_reward.h seg_view, pcb_beam.h) ------------------------------------------------
+// ---- terminal reward: LDS zones (pcb_geometry.h seg_view, pcb_routing.h beam_route_lanes) ------------------------------------------------
 #define REWARD_PARTS 2  // reward helpers per listed environment (+ one feature helper with PCBENV_FLAG_AUTO_RESET)
 // compaction buffer of candidate (i, j) pairs, per wavefront: a dense batch is two candidates per lane (128), a
 // sweep step appends at most 4 * 64 to a partial batch (< 128), and what does not fill a batch is moved to the front
@@ -76,7 +78,7 @@ PCB_HD constexpr int fold_words(int WW, int threads, int H) { return fold_in_lds
 // tensors (pinRows == C * mp for that kind), so emit_features_* and reset_env index it by any row without a test.
 PCB_HD constexpr int member_words(int kind, int C, int mp) { return kind == PCBENV_PIN ? (C * mp + 63) / 64 : 0; }
 
-// Pin tables of the spatial kind in the class-map zone (pcb_observe.h pin_tables): pid, 2 bytes per component cell, at
+// Pin tables of the spatial kind in the class-map zone (pcb_env_lds.h pin_tables): pid, 2 bytes per component cell, at
 // 0; netmask, 4 bytes per component cell, at the next multiple of 4.
 PCB_HD constexpr int pin_table_netmask_offset(int comp_cells) { return (comp_cells * 2 + 3) & ~3; }
 PCB_HD constexpr int pin_table_bytes(int comp_cells) { return comp_cells * 6 + 4; }

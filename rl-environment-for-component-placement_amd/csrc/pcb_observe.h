@@ -1,28 +1,5 @@
 // pcb_observe.h -- state block staging through LDS, legal-mask fold + observation emission, pin_grid, feature rows, terminal reward
-// Included by pcb_team.h inside Team<>, so by every unit that includes pcb_kernels.h (pcb_kind_*.hip, pcb_sample.hip, pcb_policy*.hip); CDNA4 / gfx950 only.
-
-// ----------------------------------------------------------------------------------------------
-// shared pieces of reset / step
-// ----------------------------------------------------------------------------------------------
-struct Lds {
-    EnvHdr *hdr; u64 *occ, *vm; CompRec *comps; PinRec *pins; unsigned char *rank;
-    u64 *hf; unsigned char *cls; double *seg;
-};
-// Row of environment e in the [num_slots, B, ...] output tensors for the slot a step writes (DevParams::slot).
-static __device__ inline int out_row(const DevParams &p, int slot, int e) { return slot * p.B + e; }
-static __device__ inline Lds carve(unsigned char *smem, const DevParams &p) {
-    Lds l;
-    l.hdr = (EnvHdr *)smem;
-    l.occ = (u64 *)(smem + p.offOcc);
-    l.vm = (u64 *)(smem + p.offVm);
-    l.comps = (CompRec *)(smem + p.offComps);
-    l.pins = (PinRec *)(smem + p.offPins);
-    l.rank = smem + p.offRank;  // rank[q] = position of pin q among the pins of its component (self.pins order)
-    l.hf = (u64 *)(smem + p.ldsHf);
-    l.cls = smem + p.ldsCls;
-    l.seg = (double *)(smem + p.ldsSeg);
-    return l;
-}
+// Class section, not a header: included INSIDE Team<TN> (pcb_team.h), because it strides by NT lanes or meets the team in lds_sync / store_drain_sync / block_any.
 // State block at `block` (one of p.stateStride bytes) -> LDS.
 static __device__ inline void load_state_from(unsigned char *smem, const unsigned char *block, const DevParams &p, int lane) {
     const uint4 *src = (const uint4 *)block;
@@ -191,30 +168,6 @@ template <int WW> static __device__ inline void emit_pin_grid(const DevParams &p
     }
 }
 
-// Feature rows of one pin (P:72-103 / S:70-104 Pin.calculate_feature): [rel_x, rel_y, abs_x, abs_y]
-template <int KIND> static __device__ inline void write_pin_num(const DevParams &p, int row_, const PinRec &pr) {
-    if (!p.buf.all_pins_num_feature) return;
-    int row;
-    if (KIND == PCBENV_SPATIAL) row = pr.id & PIN_ID_MASK;
-    else { if (pr.id & PIN_LOSER) return; row = pr.comp * p.mp + (pr.id & PIN_ID_MASK); }
-    double *f = p.buf.all_pins_num_feature + ((size_t)row_ * p.pinRows + row) * 4;
-    f[0] = pr.rel_x; f[1] = pr.rel_y; f[2] = pr.abs_x; f[3] = pr.abs_y;
-}
-
-// Scratch tables in the class-map zone (free between two emit_pin_grid calls), spatial env only:
-// pid[c][k] = global id of the k-th pin of component c in self.pins order (0xFFFF = none) -- the tail of
-// all_components_feature (S:203-239); netmask[c][rel_x][rel_y] = nets with a pin on that cell of the component at
-// its UNROTATED relative coordinates -- draw_components (S:1677-1697) runs at reset only, so component_grid never
-// shows the in-place rotation of place_component (quirk Q4): for a placed component the rotation is undone here
-// with the orientation kept in its record.
-struct PinTables { unsigned short *pid; unsigned *netmask; };
-static __device__ inline PinTables pin_tables(const DevParams &p, Lds &l) {
-    PinTables t;
-    t.pid = (unsigned short *)l.cls;
-    t.netmask = (unsigned *)(l.cls + pcb_layout::pin_table_netmask_offset(p.C * p.mp));
-    return t;
-}
-static_assert(PCBENV_MAX_NETS <= 32, "PinTables::netmask: 1u << pr.net (build_pin_tables); emit_component_grid_to: a cell's field = netmask << 1 | exists, in 64 bits");
 static __device__ inline void build_pin_tables(const DevParams &p, Lds &l, int lane) {
     const PinTables t = pin_tables(p, l);
     const int np = l.hdr->npins;
@@ -238,13 +191,6 @@ static __device__ inline void build_pin_tables(const DevParams &p, Lds &l, int l
 }
 // S:1677-1697 draw_components from the tables above: byte (cell, ch) = ch == 0 ? component exists : net ch-1 has a
 // pin on the cell; each byte written once.
-// chunk [bb, bb + 16) of a `total`-byte tensor row (total a multiple of 4): whole, or -- the last one -- the dwords inside the row
-static __device__ inline void store16_or_tail(const ObsDst &d, unsigned char *dst, int bb, int total, uint4 v, bool stream) {
-    if (bb + 16 <= total) { STORE16_dyn(d, (unsigned)bb, v, stream); return; }
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-    #pragma unroll
-    for (int j = 0; j < 4; j++) if (bb + 4 * j < total) *(unsigned *)(dst + bb + 4 * j) = w[j];
-}
 static __device__ inline void emit_component_grid_to(const DevParams &p, Lds &l, unsigned char *cg, int lane) {
     const PinTables t = pin_tables(p, l);
     const int nc = l.hdr->ncomp;
@@ -279,13 +225,6 @@ static __device__ inline void emit_component_grid(const DevParams &p, Lds &l, in
     emit_component_grid_to(p, l, p.buf.component_grid + (size_t)row * p.C * p.mh * p.mw * p.K, lane);
 }
 
-// The episode-constant part of a spatial environment's trajectory slot, kept per environment in library memory so that a
-// step of the trajectory layout copies it instead of rebuilding the pin tables: [compact all_components_feature, C x F
-// int16 with x = y = -1 | component_grid].  Written by the reset that starts the episode (tagged with the episode number;
-// a restored checkpoint invalidates the tags), used by steps whose slot takes no float64 all_components_feature.
-static __device__ inline bool feat_cache_valid(const DevParams &p, const Lds &l, int e) {
-    return p.feat_cache && !p.buf.all_components_feature && p.feat_cache_tag[e] == l.hdr->episode;
-}
 static __device__ inline void feat_cache_fill(const DevParams &p, Lds &l, int e, int lane) {  // spatial, build_pin_tables() has run
     if (!p.feat_cache) return;
     unsigned char *base = p.feat_cache + (size_t)e * p.featCacheStride;

@@ -25,7 +25,7 @@
 #include <limits.h>
 
 #include "pcbenv.h"
-#include "pcb_kernels.h"
+#include "pcb_sampler.h"
 #include "pcb_launch.h"
 #include "pcb_policy_common.h"
 
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(64 * NW) void k_sample_logits(DevParams p, SampleLo
     if (n > 0 && bits) {
         // not a distribution: exactly the uniform draw of pcbenv_sample_actions
         int o, x, y;
-        Team<64>::sample_action(vm, p, (int)g.first_env + e, lane, g.seed, g.step_index, &o, &x, &y);
+        sample_action(vm, p, (int)g.first_env + e, lane, g.seed, g.step_index, &o, &x, &y);
         a = o * HW + x * W + y;
         logp = -log((double)n); ent = log((double)n);
     } else if (n > 0) {
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(64 * NW) void k_sample_logits(DevParams p, SampleLo
             a = wave_min(cand);
             logp = -logZ;
         } else {
-            const u64 rnd = Team<64>::mix64(Team<64>::mix64(g.seed ^ 0x9E3779B97F4A7C15ull * ((u64)((int)g.first_env + e) + 1)) + g.step_index);
+            const u64 rnd = draw_bits(g.seed, (int)g.first_env + e, g.step_index);
             const double uz = (double)(unsigned)(rnd >> 32) * 0x1p-32 * Z;
             // the lane whose run of segments holds u*Z (rounding can leave none: then the last lane with weight)
             const u64 owners = __ballot(mine > 0.0 && excl <= uz && uz < incl);

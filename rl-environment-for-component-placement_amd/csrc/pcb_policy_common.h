@@ -193,7 +193,7 @@ __device__ inline RowHead row_head(const PolicyLds &l, const EvalGeom &q, int j0
         lm = fmaxf(lm, l.m[seg_slot(j)]);
     }
     RowHead h;
-    h.n = __builtin_amdgcn_readlane(wave_inclusive_scan(cnt, lane), WAVE - 1);
+    h.n = __builtin_amdgcn_readlane(group_inclusive_scan<WAVE>(cnt, lane), WAVE - 1);
     h.M = wave_max(lm);
     h.bits = h.n == 0 ? 0u : *l.bad ? 1u : h.M == -INFINITY ? 2u : 0u;
     return h;

@@ -21,7 +21,6 @@
 #include <hip/hip_runtime.h>
 
 #include "pcbenv.h"
-#include "pcb_kernels.h"
 #include "pcb_launch.h"
 #include "pcb_policy_common.h"
 

@@ -1,14 +1,7 @@
 // pcb_reset.h -- reset of one environment from the instance queue (k_reset and the in-launch reset of k_step)
-// Included by pcb_team.h inside Team<>, so by every unit that includes pcb_kernels.h (pcb_kind_*.hip, pcb_sample.hip, pcb_policy*.hip); CDNA4 / gfx950 only.
-
-// ----------------------------------------------------------------------------------------------
+// Class section, not a header: included INSIDE Team<TN> (pcb_team.h), because it strides by NT lanes or meets the team in lds_sync / store_drain_sync / block_any.
 // reset (R:310-351, P:1544-1597, S:1487-1549, Q:74-113): header is in LDS; builds the new episode's state in
 // LDS from the next queued instance and rewrites every observation tensor of environment e.
-// ----------------------------------------------------------------------------------------------
-// The next queued instance of environment e: header and 8-byte records, all loads issued together.
-struct InstRegs { int nc, nn, np; u64 comp; u64 pin[4]; };
-static_assert(PCBENV_MAX_PINS <= 4 * WAVE, "InstRegs::pin[4]: pin q = lane + r * NT of fetch_instance, NT >= WAVE");
-static_assert(PCBENV_MAX_COMPONENTS <= WAVE, "InstRegs::comp: the record of component `lane` (lane < p.C), NT >= WAVE");
 static __device__ inline void fetch_instance(const DevParams &p, unsigned qcursor, int e, int lane, InstRegs &ir) {
     const unsigned slot = qcursor % (unsigned)p.Q;
     const unsigned char *rec = p.queue + ((size_t)slot * p.B + e) * p.instStride;
@@ -257,5 +250,3 @@ template <int KIND, int WW, bool TRAJ> static __device__ inline void reset_env(c
     }
     lds_sync();
 }
-
-

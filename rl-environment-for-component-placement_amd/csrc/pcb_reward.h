@@ -1,44 +1,5 @@
-// pcb_reward.h -- float64 geometry of the routing reward: centroid routes, exact extent pre-filter, intersection count, wirelength
-// Included by pcb_team.h inside Team<>, so by every unit that includes pcb_kernels.h (pcb_kind_*.hip, pcb_sample.hip, pcb_policy*.hip); CDNA4 / gfx950 only.
-
-// ----------------------------------------------------------------------------------------------
-// float64 geometry of the reward (one IEEE operation per operator, see file header)
-// ----------------------------------------------------------------------------------------------
-// S:1288-1301 euclidean_distance == np.linalg.norm == sqrt(ddot): sqrt(fma(dy, dy, dx*dx))
-static __device__ inline double norm2(double dx, double dy) { return __dsqrt_rn(__fma_rn(dy, dy, __dmul_rn(dx, dx))); }
-
-// S:653-702 is_intersect
-static __device__ inline bool is_intersect(double x1, double y1, double x2, double y2, double x3, double y3, double x4, double y4) {
-    if ((x1 == x3 && y1 == y3) || (x1 == x4 && y1 == y4) || (x2 == x3 && y2 == y3) || (x2 == x4 && y2 == y4)) return true;
-    double det = (x1 - x2) * (y3 - y4) - (y1 - y2) * (x3 - x4);
-    if (det == 0) return false;
-    double a = x1 * y2 - y1 * x2, b = x3 * y4 - y3 * x4;
-    double x = (a * (x3 - x4) - (x1 - x2) * b) / det;
-    double y = (a * (y3 - y4) - (y1 - y2) * b) / det;
-    return fmin(x1, x2) <= x && x <= fmax(x1, x2) && fmin(x3, x4) <= x && x <= fmax(x3, x4) &&
-           fmin(y1, y2) <= y && y <= fmax(y1, y2) && fmin(y3, y4) <= y && y <= fmax(y3, y4);
-}
-
-// ---- routes -------------------------------------------------------------------------------------
-// A route is kept as one segment slot per pin q (slots of net n are nstart[n]..nstart[n+1]-1, so slots are
-// net-major like the reference's route lists); act[q] = 1 if the slot carries a segment.
-struct SegView { double *X1, *Y1, *X2, *Y2, *D, *A, *DX, *DY, *cen; int *act, *nstart, *nsum; unsigned *bbox; unsigned short *pairs; unsigned char *beam; int N; };  // N = max_num_nets: the per-net tables' size
-// PAIR_ENTRIES_PER_WAVE and the zone sizes SEG_*: pcb_layout.h (the host sizes the zone by the same formulas)
-static __device__ inline SegView seg_view(double *seg, int P, int N) {
-    SegView v;
-    v.N = N;
-    v.X1 = seg; v.Y1 = seg + P; v.X2 = seg + 2 * P; v.Y2 = seg + 3 * P; v.D = seg + 4 * P;
-    v.cen = seg + 5 * P;                              // cx[N], cy[N]
-    v.act = (int *)(v.cen + 2 * N);                   // [P]
-    v.nstart = v.act + P;                             // [N + 1], then 3 spare words (nstart[N + 1] = pair counter)
-    v.nsum = v.nstart + N + 1 + 3;                    // [2 * N] integer coordinate sums per net
-    v.beam = (unsigned char *)seg + ((SEG_FIXED_BYTES(P, N) + 7) & ~7);
-    v.A = (double *)v.beam; v.DX = v.A + P; v.DY = v.A + 2 * P;  // per segment: x1*y2 - y1*x2, x1 - x2, y1 - y2
-    v.bbox = (unsigned *)(v.A + 3 * P);               // [P] integer extents (x_lo, x_hi, y_lo, y_hi), one byte each
-    v.pairs = (unsigned short *)(v.bbox + P);         // [PAIR_ENTRIES_PER_WAVE] per wavefront
-    return v;
-}
-
+// pcb_reward.h -- the team's sweeps of the routing reward: net offsets and centroids, centroid routes, pair count, wirelength
+// Class section, not a header: included INSIDE Team<TN> (pcb_team.h), because it strides by NT lanes or meets the team in lds_sync / store_drain_sync / block_any.
 // net_pins offsets (self.pins is net-major) and S:1229-1241 get_centroid per net: np.mean of an integer array =
 // (exact integer sum, as float64) / n -- the sums are gathered with LDS integer atomics (order-free because exact).
 static __device__ inline void net_offsets_and_centroids(const SegView &v, const EnvHdr *hdr, const PinRec *pins, int lane) {
@@ -77,54 +38,6 @@ static __device__ inline void build_centroid_segments(const SegView &v, const En
     lds_sync();
 }
 
-// is_intersect (S:653-702) on two slots, with the per-segment terms hoisted: the operations and their order are
-// exactly the reference's -- (x1*y2 - y1*x2), (x1 - x2), (y1 - y2) are sub-expressions of its formulas.
-// Written without branches so that several candidates per lane can be in flight at once (the count is bound by
-// the LDS and float64 division latency of one wavefront, not by issue slots): det == 0 gives inf / NaN
-// coordinates, which is harmless and masked by the explicit test.
-static __device__ inline bool slots_intersect(const SegView &v, int i, int j) {
-    const double x1 = v.X1[i], y1 = v.Y1[i], x2 = v.X2[i], y2 = v.Y2[i];
-    const double x3 = v.X1[j], y3 = v.Y1[j], x4 = v.X2[j], y4 = v.Y2[j];
-    const double dxi = v.DX[i], dyi = v.DY[i], dxj = v.DX[j], dyj = v.DY[j];
-    const double a = v.A[i], b = v.A[j];
-    const bool shared = ((x1 == x3) & (y1 == y3)) | ((x1 == x4) & (y1 == y4)) | ((x2 == x3) & (y2 == y3)) | ((x2 == x4) & (y2 == y4));
-    const double det = dxi * dyj - dyi * dxj;
-    const double x = (a * dxj - dxi * b) / det;
-    const double y = (a * dyj - dyi * b) / det;
-    const bool inside = (fmin(x1, x2) <= x) & (x <= fmax(x1, x2)) & (fmin(x3, x4) <= x) & (x <= fmax(x3, x4)) &
-                        (fmin(y1, y2) <= y) & (y <= fmax(y1, y2)) & (fmin(y3, y4) <= y) & (y <= fmax(y3, y4));
-    return shared | ((det != 0) & inside);
-}
-// Exact pre-filter: if the closed x- (or y-) extents of the two segments are disjoint, no x (y) can lie in both,
-// so the reference's final range test fails whatever the computed intersection point is (a shared end point,
-// its only early "True", puts a common point in both extents).  The extents are kept as conservatively rounded
-// integers (floor of the minimum, ceil of the maximum; coordinates are in [0, 127]), four bytes per segment, so
-// the filter is one LDS word per segment and a few integer compares; a pair it lets through is decided by the
-// full float64 test, a pair it rejects has disjoint real extents.  Saves the two float64 divisions.
-static __device__ inline unsigned pack_extents(double x1, double y1, double x2, double y2) {
-    const unsigned xl = (unsigned)floor(fmin(x1, x2)), xh = (unsigned)ceil(fmax(x1, x2));
-    const unsigned yl = (unsigned)floor(fmin(y1, y2)), yh = (unsigned)ceil(fmax(y1, y2));
-    return xl | (xh << 8) | (yl << 16) | (yh << 24) | 0x80000000u;  // bit 31 = slot carries a segment
-}
-static __device__ inline bool extents_overlap(unsigned a, unsigned b) {  // branch-free
-    const unsigned xl = max(a & 0xFFu, b & 0xFFu), xh = min((a >> 8) & 0xFFu, (b >> 8) & 0xFFu);
-    const unsigned yl = max((a >> 16) & 0xFFu, (b >> 16) & 0xFFu), yh = min((a >> 24) & 0x7Fu, (b >> 24) & 0x7Fu);
-    return ((a & b & 0x80000000u) != 0) & (xl <= xh) & (yl <= yh);
-}
-
-// Full test on candidates [0, n) of a wavefront's buffer, two per lane and step so that their LDS reads and
-// divisions overlap.
-typedef __attribute__((address_space(3))) unsigned short lds_u16;  // keeps the buffer accesses ds_* instead of flat_*
-static __device__ inline int count_candidates(const SegView &v, const volatile lds_u16 *buf, int n, int wl_lane) {
-    int cnt = 0;
-    for (int base = 0; base < n; base += 2 * WAVE) {
-        const int i0 = base + wl_lane, i1 = i0 + WAVE;
-        const unsigned short p0 = i0 < n ? buf[i0] : (unsigned short)0, p1 = i1 < n ? buf[i1] : (unsigned short)0;
-        const bool r0 = slots_intersect(v, p0 & 0xFF, p0 >> 8), r1 = slots_intersect(v, p1 & 0xFF, p1 >> 8);
-        cnt += ((i0 < n) & r0) + ((i1 < n) & r1);
-    }
-    return cnt;
-}
 
 // S:629-651 find_num_intersection + S:704-722 find_wirelength over the slots.
 // Slots are net-major, so the partners "segment of an earlier net" of the slots of net n are the slots
@@ -138,11 +51,7 @@ static __device__ inline int count_candidates(const SegView &v, const volatile l
 // count_prepare reads the pins, count_finish only the segment zone.
 static __device__ inline void count_prepare(const SegView &v, int np, int lane) {
     int *total_cnt = v.nstart + v.N + 1;  // spare slot behind nstart[0..MAX_NETS]
-    for (int q = lane; q < np; q += NT) {
-        const double x1 = v.X1[q], y1 = v.Y1[q], x2 = v.X2[q], y2 = v.Y2[q];
-        v.A[q] = x1 * y2 - y1 * x2; v.DX[q] = x1 - x2; v.DY[q] = y1 - y2;
-        v.bbox[q] = v.act[q] ? pack_extents(x1, y1, x2, y2) : 0u;
-    }
+    for (int q = lane; q < np; q += NT) prepare_slot(v, q);
     if (lane == 0) *total_cnt = 0;
     lds_sync();
 }
@@ -245,4 +154,3 @@ static __device__ inline void route_centroid(const DevParams &p, const EnvHdr *h
     count_finish(p, v, hdr->npins, hdr->nnets, lane, part, nparts, wirelength, nintersections);
     STAMP(8);
 }
-

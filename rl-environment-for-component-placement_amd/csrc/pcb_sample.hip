@@ -1,7 +1,7 @@
 // pcb_sample.hip -- the two plain (non-template) kernels of libpcbenv.so that serve every environment kind: k_sample
 // (pcbenv_sample_actions: one uniformly drawn legal action per environment) and k_cursor_range (pcbenv_queue_cursors).
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off, like the per-kind units.
-#include "pcb_kernels.h"
+#include "pcb_sampler.h"
 #include "pcb_launch.h"
 
 __global__ __launch_bounds__(WAVE) void k_sample(DevParams p, int *__restrict__ actions, int fmt, u64 seed,
@@ -9,7 +9,7 @@ __global__ __launch_bounds__(WAVE) void k_sample(DevParams p, int *__restrict__ 
     const int e = blockIdx.x, lane = threadIdx.x;
     const u64 *vm = (const u64 *)(p.state + (size_t)e * p.stateStride + p.offVm);
     int o, x, y;
-    Team<64>::sample_action(vm, p, (int)first_env + e, lane, seed, step_index, &o, &x, &y);
+    sample_action(vm, p, (int)first_env + e, lane, seed, step_index, &o, &x, &y);
     if (lane == 0) {
         if (fmt == PCBENV_ACTION_FLAT) actions[e] = o * p.H * p.W + x * p.W + y;
         else { actions[3 * e] = o; actions[3 * e + 1] = x; actions[3 * e + 2] = y; }

@@ -1,11 +1,8 @@
-// pcb_step.h -- the step kernel (transition, mask, observations, terminal reward, optional reset and next-action draw) and the queue-cursor reduction
-// Included by pcb_team.h inside Team<>, so by every unit that includes pcb_kernels.h (pcb_kind_*.hip, pcb_sample.hip, pcb_policy*.hip); CDNA4 / gfx950 only.
-
-// ----------------------------------------------------------------------------------------------
+// pcb_step.h -- the step kernel (transition, mask, observations, terminal reward, optional reset and next-action draw)
+// Class section, not a header: included INSIDE Team<TN> (pcb_team.h), because it strides by NT lanes or meets the team in lds_sync / store_drain_sync / block_any.
 // step kernel (R:353-432, P:1599-1710, S:1551-1661, Q:115-153)
 //   sampled != 0: the action is drawn here (same generator as k_sample) and written to `actions`
 //   PCBENV_FLAG_AUTO_RESET: a terminal transition is followed, in the same launch, by the reset
-// ----------------------------------------------------------------------------------------------
 // Draw the next fused-sampler action from the mask now in l.vm (see EnvHdr::pre_action), or clear a stale one.
 static __device__ inline void presample_next(const DevParams &p, Lds &l, int sampled, int genv, u64 seed, u64 next_step, int lane) {
     if (lane >= WAVE) return;

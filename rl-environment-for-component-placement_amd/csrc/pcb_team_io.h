@@ -1,5 +1,5 @@
 // pcb_team_io.h -- team-size dependent basics: LDS barrier, workgroup any(), 16-byte plane emission, the legal-mask window fold
-// Textually included INSIDE `template <int TN> struct Team` (pcb_team.h): NT == TN threads work on one environment.
+// Class section, not a header: included INSIDE Team<TN> (pcb_team.h), because it strides by NT lanes or meets the team in lds_sync / store_drain_sync / block_any.
 // Team barrier that waits for LDS traffic only.  __syncthreads() also drains the global stores in flight
 // (s_waitcnt vmcnt(0)), which would serialise the observation write stream between kernel phases.
 // A team of ONE wavefront needs no s_barrier: its LDS traffic executes in program order, only the compiler (and the
@@ -113,4 +113,3 @@ static __device__ inline bool window_mask(const u64 *occ, u64 *hf, u64 *vm, int 
     }
     return block_any(any, flag);
 }
-

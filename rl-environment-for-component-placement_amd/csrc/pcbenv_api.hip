@@ -232,7 +232,7 @@ static int launch_reset(pcbenv *env, const uint8_t *mask, hipStream_t s) {
     a.d.seq = env->seq;  // the next step launch is seq + 1: a reset takes its environments off that launch's terminal list
     return kind_launch[env->cfg.kind].reset(a);
 }
-// Every step launch has a number (DevParams::seq); see Team<>::run_env for what the terminal list is.
+// Every step launch has a number (DevParams::seq); see run_env (pcb_step.h) for what the terminal list is.
 static int dispatch_step(pcbenv *env, int *actions, int fmt, int sampled, u64 seed, u64 first_env, u64 step_index, int num_steps, hipStream_t s) {
     StepLaunch a;
     a.d = env->dp;

@@ -26,7 +26,7 @@ static Geometry g_now;
         }                                                                                                               \
     } while (0)
 
-// last byte + 1 that seg_view's arrays (pcb_reward.h) and the beam search's per-net scratch (pcb_beam.h
+// last byte + 1 that seg_view's arrays (pcb_geometry.h) and the beam search's per-net scratch (pcb_routing.h
 // beam_route_lanes) reach from the start of the segment zone
 static long long seg_zone_end(int P, int N, int NW, bool routes, int k) {
     long long off = 0;
