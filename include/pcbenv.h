@@ -188,8 +188,12 @@ enum pcbenv_option {
                                               episodes end at different times steps as fast as one in lock-step; default
                                               num_envs / 8 for the pin kinds, 0 = off */
     PCBENV_OPT_GEN_GRID = 3,               /* workgroups of a refill launch of the on-device generator (default 2 048) */
-    PCBENV_OPT_GEN_LANES = 4               /* lanes per environment of the generator kernel: 0 = narrowest the
+    PCBENV_OPT_GEN_LANES = 4,              /* lanes per environment of the generator kernel: 0 = narrowest the
                                               configuration allows, 32 / 64 force a wider group; before enabling it */
+    PCBENV_OPT_FIXED_GEOMETRY = 5          /* 1 (default): a step launch of a pin kind on the 64 x 64 grid -- one wavefront
+                                              per environment, no routes, in-place layout, one transition, cell tensors
+                                              bound at 16-byte boundaries -- runs the build of the step kernel with that
+                                              grid compiled in; 0: always the build that reads the grid at run time */
 };
 int pcbenv_set_option(pcbenv *env, int32_t option, int64_t value);
 

@@ -44,6 +44,9 @@ struct pcbenv {
     // Set by the first step launch captured into a hipGraph, for the rest of the handle's life: the graph works on
     // state_buf[state_cur] in place, so from then on every launch does (no buffer swap, no helpers) -- see dispatch_step.
     bool in_place;
+    // The geometry-fixed build of k_step (pcb_layout::fixed_geometry_applies): PCBENV_OPT_FIXED_GEOMETRY, and whether every
+    // cell tensor of the current binding starts at a 16-byte boundary (pcbenv_bind_buffers_slots looks once).
+    bool fixed_geometry, cells_aligned16;
     unsigned char *gather_snap;   // pcbenv_gather within one handle: reward | info | done of the selected slot before the launch
     char err[256];
 };

@@ -101,12 +101,29 @@ __global__ __launch_bounds__(64 * NW) void k_gather(DevParams p, GatherArgs g) {
 #define STEP_BUILD_INPLACE_STREAM 1
 #define STEP_BUILD_SLOT 2
 #define STEP_BUILD_ROLLOUT 3
-template <int KIND, int WW, int NW, bool ROUTES, int BUILD>
+// GEO: the grid shape as a compile-time fact of the launch.  STEP_GEO_RUNTIME: H, W, O come with the parameter block;
+// STEP_GEO_64: the 64 x 64 grid of a pin kind (pcb_layout::fixed_geometry), for launches pcb_layout::fixed_geometry_applies
+// admits -- the in-place builds on one wavefront without routes only (pcb_kind_*_4.hip).  The routed, slot and rollout
+// builds, k_reset and k_gather keep the run-time geometry: none of them is on the path of a step of the lock-step loop.
+#define STEP_GEO_RUNTIME 0
+#define STEP_GEO_64 1
+template <int KIND, int WW, int NW, bool ROUTES, int BUILD, int GEO = STEP_GEO_RUNTIME>
 __global__ __attribute__((amdgpu_waves_per_eu(4, 8))) __launch_bounds__(64 * NW) void k_step(DevParams p, int *__restrict__ actions, int fmt, int sampled,
                                                u64 seed, u64 first_env, u64 step_index, int num_steps_) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr bool TRAJ = BUILD == STEP_BUILD_SLOT || BUILD == STEP_BUILD_ROLLOUT;
     if (!TRAJ) p.stream_stores = BUILD == STEP_BUILD_INPLACE_STREAM;  // the launch's choice as a compile-time constant: only one store policy is compiled in
+    if (GEO == STEP_GEO_64) {  // likewise the geometry, before anything reads it: what the host put there are these very values
+        static_assert(GEO == STEP_GEO_RUNTIME || (pcb_layout::is_pin_kind(KIND) && WW == 1 && NW == 1 && !ROUTES && !TRAJ), "pcb_layout::fixed_geometry_applies");
+        constexpr pcb_layout::FixedGeometry g = pcb_layout::fixed_geometry(KIND);
+        p.H = g.H; p.W = g.W; p.O = g.O; p.WW = g.WW;
+        p.offOcc = g.offOcc; p.offVm = g.offVm; p.offComps = g.offComps;
+        // The bound cell tensors start at 16-byte boundaries (checked when they were bound): with the low bits masked
+        // the compiler knows it too, and the byte paths of emit_plane_* / emit_pin_grid are not compiled in.
+        p.buf.grid = (uint8_t *)((uintptr_t)p.buf.grid & ~(uintptr_t)15);
+        p.buf.action_mask = (uint8_t *)((uintptr_t)p.buf.action_mask & ~(uintptr_t)15);
+        p.buf.pin_grid = (uint8_t *)((uintptr_t)p.buf.pin_grid & ~(uintptr_t)15);
+    }
     const int num_steps = BUILD == STEP_BUILD_ROLLOUT ? num_steps_ : 1;
     // above the generator's wavefronts (priority 0) when both share a SIMD: the step kernel is the latency-critical one
     __builtin_amdgcn_s_setprio(3);

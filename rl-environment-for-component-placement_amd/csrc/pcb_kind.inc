@@ -3,7 +3,8 @@
 // per written operator; the only fused multiply-add is the explicit __fma_rn in norm2).
 // The pin kinds are split into PARTS, one translation unit each, so that the build is as long as its slowest part:
 //   0 = reset + gather + launch switch + k_step without routes (in-place and rollout builds), 1 = k_step without routes, one
-//   transition into a trajectory slot, 2 / 3 = k_step with beam / both routes on one / four wavefronts;
+//   transition into a trajectory slot, 2 / 3 = k_step with beam / both routes on one / four wavefronts, 4 = the in-place
+//   k_step without routes on one wavefront with the 64 x 64 grid compiled in (STEP_GEO_64);
 // PCB_PART undefined = a kind without routes (square, rect), everything in one unit.
 // (The slot build has a unit of its own for its code, not only for the build time: next to the rollout build every
 // function only the trajectory layout uses has two callers instead of one and is no longer inlined -- 437 instead of
@@ -27,6 +28,7 @@ int PCB_FN(pcb_step_plain)(const StepLaunch &a);
 int PCB_FN(pcb_step_slot)(const StepLaunch &a);
 int PCB_FN(pcb_step_routed1)(const StepLaunch &a);
 int PCB_FN(pcb_step_routed4)(const StepLaunch &a);
+int PCB_FN(pcb_step_fixed)(const StepLaunch &a);
 
 // the build of the launch (pcb_kernels.h STEP_BUILD_*): in-place layout with the store policy compiled in, one transition
 // into a trajectory slot, or the persistent rollout
@@ -68,6 +70,9 @@ int PCB_FN(pcb_launch_gather)(const GatherLaunch &a) {
 int PCB_FN(pcb_step_plain)(const StepLaunch &a) {
     const DevParams &d = a.d;
     if (a.traj && a.num_steps == 1) return PCB_FN(pcb_step_slot)(a);
+#if PCB_ROUTES
+    if (pcb_layout::fixed_geometry_applies(step_shape(a))) return PCB_FN(pcb_step_fixed)(a);
+#endif
     with_team_shape(d.WW, a.threads, [&](auto ww, auto nw) { LAUNCH_STEP_INPLACE_OR_ROLLOUT(WW_OF(ww), NW_OF(nw), false); });
     return 0;
 }
@@ -89,6 +94,15 @@ int PCB_FN(pcb_launch_step)(const StepLaunch &a) {
 #endif
 
 #if PCB_ROUTES
+#if PCB_HAS(4)
+// only for launches pcb_layout::fixed_geometry_applies admits (pcb_step_plain asks): one wavefront, one word per bit row, in place
+int PCB_FN(pcb_step_fixed)(const StepLaunch &a) {
+    const DevParams &d = a.d;
+    if (d.stream_stores) hipLaunchKernelGGL((k_step<KIND, 1, 1, false, STEP_BUILD_INPLACE_STREAM, STEP_GEO_64>), dim3(d.B + d.term_wgs * d.term_hpe), dim3(64), d.ldsBytes, a.stream, d, a.actions, a.fmt, a.sampled, a.seed, a.first_env, a.step_index, a.num_steps);
+    else hipLaunchKernelGGL((k_step<KIND, 1, 1, false, STEP_BUILD_INPLACE, STEP_GEO_64>), dim3(d.B + d.term_wgs * d.term_hpe), dim3(64), d.ldsBytes, a.stream, d, a.actions, a.fmt, a.sampled, a.seed, a.first_env, a.step_index, a.num_steps);
+    return 0;
+}
+#endif
 #if PCB_HAS(2)
 int PCB_FN(pcb_step_routed1)(const StepLaunch &a) {
     const DevParams &d = a.d;

@@ -14,8 +14,14 @@ struct StepLaunch {
     int num_steps;
     int threads;        // threads per environment of the plain kernels (64 / 256)
     bool routes, traj;  // beam / both routes compiled in; trajectory layout or persistent rollout
+    bool cells_aligned16, fixed_geometry;  // of the binding / PCBENV_OPT_FIXED_GEOMETRY: pcb_layout::StepShape, step_shape() below
     hipStream_t stream;
 };
+// what pcb_layout::fixed_geometry_applies is asked about a launch
+static inline pcb_layout::StepShape step_shape(const StepLaunch &a) {
+    const DevParams &d = a.d;
+    return pcb_layout::StepShape{d.kind, d.H, d.W, d.O, d.WW, a.threads, d.num_slots, a.num_steps, a.routes, a.cells_aligned16, a.fixed_geometry};
+}
 struct ResetLaunch { DevParams d; const unsigned char *mask; int threads; hipStream_t stream; };
 // pcbenv_gather: d is the destination's parameter block (d.state = its current state set, d.state_out = the other one);
 // the source's current state set and the rows of its selected slot (or, source == destination, the snapshot of them

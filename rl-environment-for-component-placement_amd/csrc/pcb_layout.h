@@ -133,4 +133,33 @@ PCB_HD constexpr Layout state_layout(const Geometry &g) {
     return l;
 }
 
+// ---- the geometry-fixed build of k_step (pcb_kernels.h STEP_GEO_64) ------------------------------------------------
+// The grid shape of a handle never changes, and every shipped 64 x 64 configuration (c3, c4) has this one: a build of
+// the in-place step kernel that overwrites the geometry fields of its parameter block with these constants -- H, W, O
+// and what is a pure function of them: WW and the offsets of occ, vm and comps inside a state block -- so that every
+// division by W, every "is W a power of two", the LDS-staged fold, the flat-action decode's divisions and the byte paths
+// of the plane emission fold away.
+#define FIXED_GEO_SIDE 64
+#define FIXED_GEO_ORIENTATIONS 4  // DevParams::O of the pin kinds
+struct FixedGeometry { int H, W, O, WW, offOcc, offVm, offComps; };
+PCB_HD constexpr FixedGeometry fixed_geometry(int kind) {
+    const Layout l = state_layout(Geometry{kind, FIXED_GEO_SIDE, FIXED_GEO_SIDE, 0, 0, 0, 0, 0, WAVE, PCBENV_REWARD_CENTROID, 0});
+    return FixedGeometry{FIXED_GEO_SIDE, FIXED_GEO_SIDE, FIXED_GEO_ORIENTATIONS, l.WW, l.offOcc, l.offVm, l.offComps};
+}
+// What a step launch is, as far as the choice of its build goes.  cells_aligned16: every bound cell tensor (grid,
+// action_mask, pin_grid) starts at a 16-byte boundary -- checked once, when the buffers are bound -- so that the fixed
+// build needs no byte path in emit_plane_* / emit_pin_grid; enabled: PCBENV_OPT_FIXED_GEOMETRY.
+struct StepShape {
+    int kind, H, W, O, WW, threads, num_slots, num_steps;
+    bool routes, cells_aligned16, enabled;
+};
+// The one predicate that says when the fixed build applies (the launch switch of pcb_kind.inc uses nothing else): a
+// pin kind without routes on the 64 x 64 grid, one wavefront per environment, in-place layout, one transition per launch.
+PCB_HD constexpr bool fixed_geometry_applies(const StepShape &s) {
+    return s.enabled && is_pin_kind(s.kind) && !s.routes && s.H == FIXED_GEO_SIDE && s.W == FIXED_GEO_SIDE &&
+           s.O == FIXED_GEO_ORIENTATIONS && s.WW == 1 && wavefronts(s.threads) == 1 && s.num_slots == 1 && s.num_steps == 1 &&
+           s.cells_aligned16;
+}
+PCB_HD inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }  // (a null pointer -- tensor not bound -- is)
+
 }  // namespace pcb_layout

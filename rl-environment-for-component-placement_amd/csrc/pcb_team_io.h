@@ -59,6 +59,21 @@ template <int WW, bool STREAM> static __device__ inline void emit_plane2_(unsign
     if ((W & 15) == 0 && (((uintptr_t)dst) & 15) == 0 && (((uintptr_t)dst2) & 15) == 0) {
         const ObsDst d = obs_dst(dst, (long long)H * W), d2 = obs_dst(dst2, (long long)H * W);
         const int sh = (W & (W - 1)) == 0 ? __ffs(W) - 1 : -1;
+        // The geometry-fixed build (k_step's STEP_GEO_64): the plane is a compile-time number of whole trips of the team, so
+        // the trips are written out -- no loop counter, no exec mask, immediate offsets -- in the same order read ->
+        // expand -> store per trip (c3 221 -> 224 M env-steps/s, profiles/fixed_geometry_ab.txt).  Any other build: H * W is not
+        // a constant, the test folds to false and the loop below is all there is (same device code as without it).
+        if (__builtin_constant_p(H * W) && __builtin_constant_p(W) && (H * W / 16) % NT == 0 && H * W / 16 / NT <= 8) {
+            PCB_UNROLL
+            for (int k = 0; k < H * W / 16 / NT; k++) {
+                const int cell = (lane + k * NT) * 16, r = sh >= 0 ? cell >> sh : cell / W, col = cell - r * W;
+                unsigned b = (unsigned)(bits[r * WW + (col >> 6)] >> (col & 63)) & 0xFFFFu;
+                const uint4 v = expand16(b);
+                STORE16<STREAM>(d, (unsigned)cell, v);
+                STORE16<STREAM>(d2, (unsigned)cell, v);
+            }
+            return;
+        }
         for (int c = lane; c < H * W / 16; c += NT) {
             int cell = c * 16, r = sh >= 0 ? cell >> sh : cell / W, col = cell - r * W;
             unsigned b = (unsigned)(bits[r * WW + (col >> 6)] >> (col & 63)) & 0xFFFFu;

@@ -72,6 +72,7 @@ extern "C" int pcbenv_create(const pcbenv_config *cfg, int device, pcbenv **out)
     { const char *ev = getenv("PCBENV_STAMPS"); if (ev && ev[0] == '1') { hipMalloc((void **)&d.dbg, (size_t)(d.B + PCBENV_TERM_CAP_MAX * (REWARD_PARTS + 1)) * 32 * 8); hipMemset(d.dbg, 0, (size_t)(d.B + PCBENV_TERM_CAP_MAX * (REWARD_PARTS + 1)) * 32 * 8); } }
 #endif
     env->state_cur = 0;
+    env->fixed_geometry = true;  // PCBENV_OPT_FIXED_GEOMETRY
     d.state = d.state_out = env->state_buf[0];
     *env->term_seen_host = 0u;
     *out = env;
@@ -131,6 +132,10 @@ extern "C" int pcbenv_set_option(pcbenv *env, int32_t option, int64_t value) {
         if (value != 0 && value != 16 && value != 32 && value != 64) return fail(env, PCBENV_EINVAL, "generator lanes per environment: 0, 16, 32 or 64");
         env->gen_lanes = (int)value;
         return PCBENV_OK;
+    case PCBENV_OPT_FIXED_GEOMETRY:
+        if (value != 0 && value != 1) return fail(env, PCBENV_EINVAL, "fixed geometry: 0 or 1");
+        env->fixed_geometry = value != 0;
+        return PCBENV_OK;
     }
     return fail(env, PCBENV_EINVAL, "unknown option");
 }
@@ -177,6 +182,7 @@ extern "C" int pcbenv_bind_buffers_slots(pcbenv *env, const pcbenv_buffers *b, i
     if (!is_pin_kind(k)) { d.buf.all_pins_num_feature = 0; d.buf.all_pins_cat_feature = 0; d.buf.info = 0; }
     if (k != PCBENV_RECT) d.buf.component_mask = 0;
     if (k == PCBENV_SQUARE) { d.buf.all_components_feature = 0; d.buf.placement_mask = 0; }
+    env->cells_aligned16 = pcb_layout::aligned16(d.buf.grid) && pcb_layout::aligned16(d.buf.action_mask) && pcb_layout::aligned16(d.buf.pin_grid);
     d.bind_gen += 1;  // feature tensors of these buffers are uninitialised: the next reset of each env fills them
     memset(&d.cbuf, 0, sizeof(d.cbuf));  // compact tensors belong to a binding: bind them again
     env->bound = true;
@@ -247,6 +253,7 @@ static int dispatch_step(pcbenv *env, int *actions, int fmt, int sampled, u64 se
     // pcbenv_create stands.
     if (a.traj && d.num_slots > 1) d.stream_stores = stream_stores(env, d.num_slots);
     a.routes = is_pin_kind(env->cfg.kind) && env->cfg.reward_type != PCBENV_REWARD_CENTROID;
+    a.cells_aligned16 = env->cells_aligned16; a.fixed_geometry = env->fixed_geometry;
     if (++env->seq == 0u) env->seq = 1u;  // 0 is "not listed" in the marks
     d.seq = env->seq;
     // A launch that is being captured into a hipGraph will be replayed with these very arguments: no launch number,

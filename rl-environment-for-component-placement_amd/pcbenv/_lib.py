@@ -13,7 +13,7 @@ ACTION_TUPLE, ACTION_FLAT = 0, 1
 FLAG_INCREMENTAL_OBS = 1
 FLAG_AUTO_RESET = 2
 ABI_VERSION = 3
-OPT_STREAM_THRESHOLD_BYTES, OPT_TERMINAL_TEAMS, OPT_GEN_GRID, OPT_GEN_LANES = 1, 2, 3, 4
+OPT_STREAM_THRESHOLD_BYTES, OPT_TERMINAL_TEAMS, OPT_GEN_GRID, OPT_GEN_LANES, OPT_FIXED_GEOMETRY = 1, 2, 3, 4, 5
 LOGITS_F32, LOGITS_BF16 = 0, 1
 DRAW_SAMPLE, DRAW_GREEDY = 0, 1
 EVAL_ERR_NONFINITE, EVAL_ERR_ALL_NEG_INF, EVAL_ERR_ACTION = 1, 2, 4  # bits of pcbenv_evaluate_logits' *errors_dev

@@ -91,7 +91,7 @@ class BatchedPlacementEnv:
         `self.traj_reward`, ...), `select_slot(s)` chooses the slot the next reset / step writes and `self.obs`,
         `self.reward`, `self.done`, `self.info_raw` are views of that slot (pcbenv_bind_buffers_slots).
         options: tuning knobs of the handle, `pcbenv_set_option` (include/pcbenv.h): "stream_threshold_bytes",
-        "terminal_teams", "gen_grid", "gen_lanes" -- none changes a result.
+        "terminal_teams", "gen_grid", "gen_lanes", "fixed_geometry" -- none changes a result.
         compact_features (trajectory layout only): the feature tensors are kept as int16 / int8 / uint8
         (`pcbenv_bind_compact_features`: 8x fewer feature bytes per step) under the same keys of `traj` / `obs`;
         `obs_f64()` / `expand_compact_features` give the reference's float64 tensors, bit for bit.
@@ -183,7 +183,7 @@ class BatchedPlacementEnv:
 
     def set_option(self, name: str, value: int):
         code = {"stream_threshold_bytes": _lib.OPT_STREAM_THRESHOLD_BYTES, "terminal_teams": _lib.OPT_TERMINAL_TEAMS,
-                "gen_grid": _lib.OPT_GEN_GRID, "gen_lanes": _lib.OPT_GEN_LANES}[name]
+                "gen_grid": _lib.OPT_GEN_GRID, "gen_lanes": _lib.OPT_GEN_LANES, "fixed_geometry": _lib.OPT_FIXED_GEOMETRY}[name]
         _lib.check(self._L.pcbenv_set_option(self._h, code, int(value)), self._h)
 
     def _stream(self):
