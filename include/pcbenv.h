@@ -34,6 +34,10 @@
  *                          RLlib's Categorical logp / entropy of the same masked logits for stored actions, and their
  *                          gradient with respect to the logits (what a PPO update back-propagates)
  *                            utils/agent/factorized_action_distributions.py:21-91
+ *   pcbenv_sample_axis, pcbenv_evaluate_axis, pcbenv_evaluate_axis_backward
+ *                          one stage of the factorised distributions p(o) p(x|o) p(y|o,x) and p(x) p(y|x) p(o|x,y): the
+ *                          stage's mask (reduce_max / gather of action_mask), its masked Categorical and the gradient
+ *                            utils/agent/factorized_action_distributions.py:107-818
  *   pcbenv_gather          no counterpart: the closest is copy.deepcopy(env) of a reference env object, which a
  *                          caller uses to fork an episode (lookahead, beam search, population resampling)
  *
@@ -397,6 +401,64 @@ int pcbenv_evaluate_logits_backward(const pcbenv *env, const void *logits_dev, i
                            const uint64_t *mask_bits_dev, const int32_t *actions_dev, int32_t action_format,
                            int64_t num_rows, const float *stats_dev, const float *grad_log_prob_dev,
                            const float *grad_entropy_dev, void *grad_logits_dev, void *stream);
+
+/* One stage of a factorised policy: a masked categorical over ONE action coordinate, given some of the others.  One
+ * kernel launch each on `stream`; a policy p(o) p(x|o) p(y|o,x) draws with three pcbenv_sample_axis calls and is
+ * updated with three pcbenv_evaluate_axis + three pcbenv_evaluate_axis_backward calls.  Nothing reads action_mask.
+ * Axes: 0 = orientation (n = O), 1 = x (n = H), 2 = y (n = W).  `given` is a bit set (1u << axis) of the OTHER axes whose
+ * values are already fixed.  The legal set of a row for target axis t is
+ *   L = { v in [0, n) : some legal (o, x, y) has coordinate t equal to v and every given coordinate equal to its value }
+ * with (o, x, y) legal when o < O and bit y of word [o & 1, x, y / 64] of the row's bit rows is set (bits of columns >= W
+ * never count; the square kind never reads plane 1).  pcbenv_sample_axis reads the bit rows of the current state set (as
+ * pcbenv_sample_logits does: row e = environment e, num_envs rows); the evaluate calls read the caller's dense uint64
+ * [num_rows, 2, H, ceil(W/64)] (the layout pcbenv_mask_bits documents), for any num_rows.
+ * logits_dev: C-contiguous [rows, n], float32 or bf16, aligned to its element size.  A logit outside L is never read: it
+ * may hold NaN or an already-masked value, so raw and masked logits give identical results.
+ * actions_dev: int32 [rows, 3] = (o, x, y).  The columns named in `given` are read; the sampler writes column `axis` and
+ * the evaluate calls read the stored value there; the remaining column is neither read nor written.
+ * With M = max over L of l_v, w_v = exp(l_v - M), Z = sum over L of w_v, p_v = w_v / Z, as for pcbenv_sample_logits:
+ *   log_prob = l_a - M - log Z        entropy = log Z - sum over L of p_v (l_v - M)     (a zero weight contributes 0)
+ *   PCBENV_DRAW_SAMPLE  rnd = the value pcbenv_sample_actions uses for (seed, first_env_index + e, step_index),
+ *                       rnd_axis = mix64(rnd + GOLDEN * (axis + 1)) -- the salt keeps the three stages of one step
+ *                       independent -- u = hi32(rnd_axis) / 2^32, and the draw is the first v in L, in increasing v, whose
+ *                       prefix sum exceeds u * Z (the threshold is float64, the partial sums carry float32 rounding); never
+ *                       a value outside L, never one of weight 0.  Constant logits draw exactly member number
+ *                       (hi32(rnd_axis) * |L|) >> 32 of L.
+ *   PCBENV_DRAW_GREEDY  the lowest argmax over L.
+ * Backward writes EVERY element of grad_logits_dev [num_rows, n] in the logits' dtype (bf16: round to nearest even); it
+ * recomputes M and Z from the logits, so there is no statistics buffer.  With log p_v = l_v - M - log Z, Hrow the entropy:
+ *   g_v = g_lp (1[v = a] - p_v) - g_H p_v (log p_v + Hrow)   for v in L   (p_v = 0: the second term is 0, never NaN)
+ *   g_v = 0                                                   elsewhere
+ * grad_log_prob_dev (g_lp) and grad_entropy_dev (g_H) are float32 [num_rows]; either may be NULL, which means zero.
+ * Edge cases are data:
+ *   L empty (no legal action at all, or a given combination with no legal completion)
+ *                                    the value 0, log_prob = entropy = 0, gradient row zero; no error bit
+ *   a NaN or +inf in L               bit 0 of *errors_dev; the sampler takes the uniform pick above (in both modes),
+ *                                    log_prob = -log |L|, entropy = log |L|, gradient row zero
+ *   every logit of L -inf            bit 1; the same outputs
+ *   (evaluate) the stored value out of range or not in L, L not empty and neither of the two cases above
+ *                                    bit 2; log_prob = 0, the entropy as usual, the one-hot term dropped in backward
+ *   a given value out of range for its axis
+ *                                    bit 3; otherwise treated as L empty
+ * The bits are ORed into *errors_dev by the sampler and by the evaluate forward; errors_dev, log_prob_dev and entropy_dev
+ * may be NULL.
+ * PCBENV_EINVAL (checked before any device call, in this order): null logits or actions; unknown dtype, mode or axis;
+ * `given` with a bit above 4 or containing 1u << axis; misaligned logits; null or misaligned mask bits; num_rows < 0; null
+ * or misaligned grad logits; null handle.  PCBENV_ESTATE (sampler): buffers not bound, or `stream` is being captured into
+ * a hipGraph (as pcbenv_sample_logits).  num_rows == 0 is a no-op success.
+ * The sampler writes nothing the library owns; the evaluate calls use the handle for geometry and device only and need
+ * no bound buffers. */
+enum pcbenv_axis { PCBENV_AXIS_ORIENTATION = 0, PCBENV_AXIS_X = 1, PCBENV_AXIS_Y = 2 };
+int pcbenv_sample_axis(pcbenv *env, int32_t axis, uint32_t given, const void *logits_dev, int32_t logits_dtype,
+                       int32_t mode, int32_t *actions_dev, float *log_prob_dev, float *entropy_dev,
+                       uint32_t *errors_dev, uint64_t seed, uint64_t first_env_index, uint64_t step_index, void *stream);
+int pcbenv_evaluate_axis(const pcbenv *env, int32_t axis, uint32_t given, const void *logits_dev, int32_t logits_dtype,
+                         const uint64_t *mask_bits_dev, const int32_t *actions_dev, int64_t num_rows,
+                         float *log_prob_dev, float *entropy_dev, uint32_t *errors_dev, void *stream);
+int pcbenv_evaluate_axis_backward(const pcbenv *env, int32_t axis, uint32_t given, const void *logits_dev,
+                         int32_t logits_dtype, const uint64_t *mask_bits_dev, const int32_t *actions_dev,
+                         int64_t num_rows, const float *grad_log_prob_dev, const float *grad_entropy_dev,
+                         void *grad_logits_dev, void *stream);
 
 /* Bit-packed legal-action mask of the current component, library-owned device
  * memory: uint64 [B, 2, H, ceil(W/64)] (orientation 0/1; pin kinds: 2 = 0, 3 = 1;

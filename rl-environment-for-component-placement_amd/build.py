@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 UNITS = (["pcb_kind_square.hip", "pcb_kind_rect.hip"] + [f"pcb_kind_{k}_{p}.hip" for p in (2, 3, 0, 4, 1) for k in ("spatial", "pin")]  # slowest first
-         + ["pcb_policy.hip", "pcb_policy_eval.hip", "pcb_gen.hip", "pcb_sample.hip", "pcbenv_api.hip", "pcb_config.hip", "instance_gen.cpp"])
+         + ["pcb_policy.hip", "pcb_policy_eval.hip", "pcb_policy_axis.hip", "pcb_gen.hip", "pcb_sample.hip", "pcbenv_api.hip", "pcb_config.hip", "instance_gen.cpp"])
 SRC = [os.path.join(CSRC, u) for u in UNITS]
 DEPS = SRC + [os.path.join(REPO, "include", "pcbenv.h")] + sorted(
     os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc")))

@@ -77,6 +77,38 @@ struct EvalLogitsBackwardLaunch { EvalGeom q; EvalLogitsBackwardArgs g; int dtyp
 int pcb_launch_evaluate_logits(const EvalLogitsLaunch &a);
 int pcb_launch_evaluate_logits_backward(const EvalLogitsBackwardLaunch &a);
 
+// pcbenv_sample_axis / pcbenv_evaluate_axis / pcbenv_evaluate_axis_backward (pcb_policy_axis.hip): one stage of a
+// factorised policy.  The sampler reads the bit rows of d.state (the current state set), the evaluate calls the caller's.
+struct AxisStage { int axis; unsigned given; };
+struct SampleAxisArgs {
+    const void *logits;  // [B, n], n = O, H or W by the axis; float32 or bf16
+    int *actions;        // [B, 3]: the given columns are read, column `axis` is written
+    float *log_prob, *entropy;  // may be null
+    unsigned *errors;           // may be null
+    u64 seed, first_env, step_index;
+    int greedy;
+};
+struct SampleAxisLaunch { DevParams d; AxisStage s; SampleAxisArgs g; int dtype; hipStream_t stream; };
+struct EvalAxisArgs {
+    const void *logits;  // [rows, n]
+    const u64 *mask_bits;
+    const int *actions;  // [rows, 3]: the given columns and the stored value in column `axis`
+    float *log_prob, *entropy;  // may be null
+    unsigned *errors;           // may be null
+};
+struct EvalAxisLaunch { EvalGeom q; AxisStage s; EvalAxisArgs g; int dtype; hipStream_t stream; };
+struct EvalAxisBackwardArgs {
+    const void *logits;
+    const u64 *mask_bits;
+    const int *actions;
+    const float *grad_log_prob, *grad_entropy;  // may be null (zero)
+    void *grad_logits;  // [rows, n] in the logits' dtype, written whole
+};
+struct EvalAxisBackwardLaunch { EvalGeom q; AxisStage s; EvalAxisBackwardArgs g; int dtype; hipStream_t stream; };
+int pcb_launch_sample_axis(const SampleAxisLaunch &a);
+int pcb_launch_evaluate_axis(const EvalAxisLaunch &a);
+int pcb_launch_evaluate_axis_backward(const EvalAxisBackwardLaunch &a);
+
 #define PCB_DECLARE_KIND(name) int pcb_launch_step_##name(const StepLaunch &a); int pcb_launch_reset_##name(const ResetLaunch &a); \
     int pcb_launch_gather_##name(const GatherLaunch &a);
 PCB_DECLARE_KIND(square) PCB_DECLARE_KIND(rect) PCB_DECLARE_KIND(pin) PCB_DECLARE_KIND(spatial)

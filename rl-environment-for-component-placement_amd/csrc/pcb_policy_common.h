@@ -1,7 +1,8 @@
 // pcb_policy_common.h -- what the kernels that read a policy's logits through the legal-action bit rows share
 // (k_sample_logits in pcb_policy.hip; k_evaluate_logits and its backward in pcb_policy_eval.hip): the segment
 // addressing, the bit-row staging, the chunk loads, the weight of a logit, pass 1 of the forward kernels, the pieces of
-// their wavefront-0 combine, the DPP row / wavefront reductions and the launch selection.
+// their wavefront-0 combine, the DPP row / wavefront reductions and the launch selection.  The axis kernels
+// (pcb_policy_axis.hip) take the weight, the wavefront reductions and the gradient of one logit from here.
 // Part of libpcbenv.so (CDNA4 / gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -34,6 +35,21 @@ __device__ inline void load4(const bf16_bits *p, float v[4]) {
 
 // weight of a legal logit relative to its segment's maximum (the one place it is computed)
 __device__ inline float seg_weight(float l, float m) { return exp2f((l - m) * LOG2E); }
+
+// what the backward kernels share: the gradient's bf16 rounding, its scalar store and the gradient of one logit
+__device__ inline bf16_bits to_bf16(float v) {  // round to nearest even; v is finite
+    const unsigned u = __float_as_uint(v);
+    return (bf16_bits)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+__device__ inline void store1(float *p, float v) { *p = v; }
+__device__ inline void store1(bf16_bits *p, float v) { *p = to_bf16(v); }
+// gradient of one legal logit.  c = M + log Z split as (M, log Z): lp = (l - M) - log Z keeps the cancellation in the
+// first, exact-or-nearly-exact difference.  p = 0 (a legal -inf logit, or underflow): the entropy term is 0, never NaN.
+__device__ inline float grad_one(float l, float M, float logZ, float Hrow, float glp, float gH, bool is_action) {
+    const float lp = (l - M) - logZ, p = exp2f(lp * LOG2E);
+    const float ge = p > 0.f ? gH * (p * (lp + Hrow)) : 0.f;
+    return glp * ((is_action ? 1.f : 0.f) - p) - ge;
+}
 
 // all-reduce over the 16 lanes of a DPP row (row_ror 8, 4, 2, 1); every lane must be active
 template <int CTRL> __device__ inline float dpp_f(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false)); }

@@ -40,10 +40,6 @@ constexpr int UNROLL = PCB_EV_UNROLL;
 // row status in stats[4 r + 3]
 constexpr float ROW_OK = 0.f, ROW_ZERO = 1.f, ROW_NO_ONE_HOT = 2.f;
 
-__device__ inline bf16_bits to_bf16(float v) {  // round to nearest even; v is finite
-    const unsigned u = __float_as_uint(v);
-    return (bf16_bits)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
 template <typename V> __device__ inline void store_vec(V *p, V v) {
 #ifdef PCB_EV_NT_STORES
     __builtin_nontemporal_store(v, p);
@@ -57,8 +53,6 @@ __device__ inline void store4(float *p, const float v[4]) { store_vec((f32x4 *)p
 __device__ inline void store4(bf16_bits *p, const float v[4]) {
     store_vec((u32x2 *)p, u32x2{(unsigned)to_bf16(v[0]) | ((unsigned)to_bf16(v[1]) << 16), (unsigned)to_bf16(v[2]) | ((unsigned)to_bf16(v[3]) << 16)});
 }
-__device__ inline void store1(float *p, float v) { *p = v; }
-__device__ inline void store1(bf16_bits *p, float v) { *p = to_bf16(v); }
 
 // flat action of row e, or -1 when it is out of range; *legal: its bit
 __device__ inline int stored_action(const u64 *vml, const EvalGeom &q, const int *actions, int fmt, int e, bool *legal) {
@@ -126,14 +120,6 @@ __global__ __launch_bounds__(64 * NW) void k_evaluate_logits(EvalGeom q, EvalLog
         *(float4 *)(g.stats + 4 * (size_t)e) = st;
     }
     if (bits && g.errors) atomicOr(g.errors, bits);
-}
-
-// gradient of one legal logit.  c = M + log Z split as (M, log Z): lp = (l - M) - log Z keeps the cancellation in the
-// first, exact-or-nearly-exact difference.  p = 0 (a legal -inf logit, or underflow): the entropy term is 0, never NaN.
-__device__ inline float grad_one(float l, float M, float logZ, float Hrow, float glp, float gH, bool is_action) {
-    const float lp = (l - M) - logZ, p = exp2f(lp * LOG2E);
-    const float ge = p > 0.f ? gH * (p * (lp + Hrow)) : 0.f;
-    return glp * ((is_action ? 1.f : 0.f) - p) - ge;
 }
 
 template <typename T, bool VEC, int NW>

@@ -593,6 +593,99 @@ extern "C" int pcbenv_evaluate_logits_backward(const pcbenv *cenv, const void *l
     return PCBENV_OK;
 }
 
+// ---- pcbenv_sample_axis / pcbenv_evaluate_axis / pcbenv_evaluate_axis_backward --------------------------------------
+// One stage of a factorised policy.  As the logits entry points: the argument checks come before anything touches a
+// device, in the order of logits_checks; nothing the library owns is written.
+static int axis_checks(pcbenv *env, int32_t axis, uint32_t given, const void *logits_dev, int32_t logits_dtype, int32_t mode,
+                       const int32_t *actions_dev) {
+    if (!logits_dev) return fail(env, PCBENV_EINVAL, "null logits");
+    if (!actions_dev) return fail(env, PCBENV_EINVAL, "null actions");
+    if (logits_dtype != PCBENV_LOGITS_F32 && logits_dtype != PCBENV_LOGITS_BF16) return fail(env, PCBENV_EINVAL, "unknown logits dtype");
+    if (mode != PCBENV_DRAW_SAMPLE && mode != PCBENV_DRAW_GREEDY) return fail(env, PCBENV_EINVAL, "unknown draw mode");
+    if (axis != PCBENV_AXIS_ORIENTATION && axis != PCBENV_AXIS_X && axis != PCBENV_AXIS_Y) return fail(env, PCBENV_EINVAL, "unknown axis");
+    if (given & ~7u) return fail(env, PCBENV_EINVAL, "given has a bit above 4");
+    if (given & (1u << axis)) return fail(env, PCBENV_EINVAL, "given contains the axis itself");
+    if ((uintptr_t)logits_dev % logits_elem_bytes(logits_dtype) != 0)
+        return fail(env, PCBENV_EINVAL, "logits pointer not aligned to its element size");
+    return PCBENV_OK;
+}
+static int evaluate_axis_checks(pcbenv *env, int32_t axis, uint32_t given, const void *logits_dev, int32_t logits_dtype,
+                                const uint64_t *mask_bits_dev, const int32_t *actions_dev, int64_t num_rows) {
+    const int rc = axis_checks(env, axis, given, logits_dev, logits_dtype, PCBENV_DRAW_SAMPLE, actions_dev);
+    if (rc != PCBENV_OK) return rc;
+    if (!mask_bits_dev) return fail(env, PCBENV_EINVAL, "null mask bits");
+    if ((uintptr_t)mask_bits_dev % 8 != 0) return fail(env, PCBENV_EINVAL, "mask bits pointer not aligned to 8 bytes");
+    if (num_rows < 0 || num_rows > INT32_MAX) return fail(env, PCBENV_EINVAL, "num_rows out of range");
+    return PCBENV_OK;
+}
+
+extern "C" int pcbenv_sample_axis(pcbenv *env, int32_t axis, uint32_t given, const void *logits_dev, int32_t logits_dtype,
+                                  int32_t mode, int32_t *actions_dev, float *log_prob_dev, float *entropy_dev,
+                                  uint32_t *errors_dev, uint64_t seed, uint64_t first_env_index, uint64_t step_index,
+                                  void *stream) {
+    const int rc = axis_checks(env, axis, given, logits_dev, logits_dtype, mode, actions_dev);
+    if (rc != PCBENV_OK) return rc;
+    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
+    if (!env->bound) return fail(env, PCBENV_ESTATE, "pcbenv_bind_buffers has not been called");
+    DEVICE_GUARD(env);
+    hipStream_t s = (hipStream_t)stream;
+    // A captured launch would keep reading the state set that was current at capture time (as pcbenv_sample_logits).
+    if (stream_capturing(s)) return fail(env, PCBENV_ESTATE, "pcbenv_sample_axis cannot be captured into a graph");
+    SampleAxisLaunch a;
+    a.d = env->dp;  // d.state: the current state set, as k_sample_logits reads it
+    a.s = AxisStage{axis, given}; a.dtype = logits_dtype; a.stream = s;
+    SampleAxisArgs &g = a.g;
+    g.logits = logits_dev; g.actions = actions_dev; g.log_prob = log_prob_dev; g.entropy = entropy_dev;
+    g.errors = (unsigned *)errors_dev; g.seed = (u64)seed; g.first_env = (u64)first_env_index; g.step_index = (u64)step_index;
+    g.greedy = mode == PCBENV_DRAW_GREEDY;
+    pcb_launch_sample_axis(a);
+    HIP_TRY(env, hipGetLastError());
+    return PCBENV_OK;
+}
+
+extern "C" int pcbenv_evaluate_axis(const pcbenv *cenv, int32_t axis, uint32_t given, const void *logits_dev,
+                                    int32_t logits_dtype, const uint64_t *mask_bits_dev, const int32_t *actions_dev,
+                                    int64_t num_rows, float *log_prob_dev, float *entropy_dev, uint32_t *errors_dev,
+                                    void *stream) {
+    pcbenv *env = const_cast<pcbenv *>(cenv);  // the error text only
+    const int rc = evaluate_axis_checks(env, axis, given, logits_dev, logits_dtype, mask_bits_dev, actions_dev, num_rows);
+    if (rc != PCBENV_OK) return rc;
+    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
+    if (num_rows == 0) return PCBENV_OK;
+    DEVICE_GUARD(env);
+    EvalAxisLaunch a;
+    a.q = eval_geom(env, num_rows); a.s = AxisStage{axis, given}; a.dtype = logits_dtype; a.stream = (hipStream_t)stream;
+    EvalAxisArgs &g = a.g;
+    g.logits = logits_dev; g.mask_bits = (const u64 *)mask_bits_dev; g.actions = actions_dev; g.log_prob = log_prob_dev;
+    g.entropy = entropy_dev; g.errors = (unsigned *)errors_dev;
+    pcb_launch_evaluate_axis(a);
+    HIP_TRY(env, hipGetLastError());
+    return PCBENV_OK;
+}
+
+extern "C" int pcbenv_evaluate_axis_backward(const pcbenv *cenv, int32_t axis, uint32_t given, const void *logits_dev,
+                                             int32_t logits_dtype, const uint64_t *mask_bits_dev, const int32_t *actions_dev,
+                                             int64_t num_rows, const float *grad_log_prob_dev, const float *grad_entropy_dev,
+                                             void *grad_logits_dev, void *stream) {
+    pcbenv *env = const_cast<pcbenv *>(cenv);  // the error text only
+    const int rc = evaluate_axis_checks(env, axis, given, logits_dev, logits_dtype, mask_bits_dev, actions_dev, num_rows);
+    if (rc != PCBENV_OK) return rc;
+    if (!grad_logits_dev) return fail(env, PCBENV_EINVAL, "null grad logits");
+    if ((uintptr_t)grad_logits_dev % logits_elem_bytes(logits_dtype) != 0)
+        return fail(env, PCBENV_EINVAL, "grad logits pointer not aligned to its element size");
+    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
+    if (num_rows == 0) return PCBENV_OK;
+    DEVICE_GUARD(env);
+    EvalAxisBackwardLaunch a;
+    a.q = eval_geom(env, num_rows); a.s = AxisStage{axis, given}; a.dtype = logits_dtype; a.stream = (hipStream_t)stream;
+    EvalAxisBackwardArgs &g = a.g;
+    g.logits = logits_dev; g.mask_bits = (const u64 *)mask_bits_dev; g.actions = actions_dev;
+    g.grad_log_prob = grad_log_prob_dev; g.grad_entropy = grad_entropy_dev; g.grad_logits = grad_logits_dev;
+    pcb_launch_evaluate_axis_backward(a);
+    HIP_TRY(env, hipGetLastError());
+    return PCBENV_OK;
+}
+
 extern "C" int pcbenv_queue_cursors(pcbenv *env, uint32_t *min_out, uint32_t *max_out, void *stream) {
     if (!env || !min_out || !max_out) return fail(env, PCBENV_EINVAL, "null argument");
     DEVICE_GUARD(env);

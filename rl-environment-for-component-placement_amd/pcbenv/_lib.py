@@ -18,6 +18,8 @@ LOGITS_F32, LOGITS_BF16 = 0, 1
 DRAW_SAMPLE, DRAW_GREEDY = 0, 1
 EVAL_ERR_NONFINITE, EVAL_ERR_ALL_NEG_INF, EVAL_ERR_ACTION = 1, 2, 4  # bits of pcbenv_evaluate_logits' *errors_dev
 EVAL_ROW_OK, EVAL_ROW_ZERO, EVAL_ROW_NO_ONE_HOT = 0, 1, 2  # row status, stats[:, 3]
+AXIS_ORIENTATION, AXIS_X, AXIS_Y = 0, 1, 2
+AXIS_ERR_NONFINITE, AXIS_ERR_ALL_NEG_INF, AXIS_ERR_VALUE, AXIS_ERR_GIVEN = 1, 2, 4, 8  # bits of the axis entry points' *errors_dev
 
 EXPORTS = ("pcbenv_abi_version", "pcbenv_create", "pcbenv_destroy", "pcbenv_last_error",
            "pcbenv_instance_stride", "pcbenv_max_total_pins", "pcbenv_set_option", "pcbenv_bind_buffers", "pcbenv_bind_buffers_slots", "pcbenv_bind_compact_features", "pcbenv_select_slot",
@@ -25,7 +27,8 @@ EXPORTS = ("pcbenv_abi_version", "pcbenv_create", "pcbenv_destroy", "pcbenv_last
            "pcbenv_mask_bits", "pcbenv_state_bytes", "pcbenv_get_state", "pcbenv_set_state", "pcbenv_queue_cursors",
            "pcbenv_instgen_device_enable", "pcbenv_instgen_device_status", "pcbenv_get_instances",
            "pcbenv_instgen_create", "pcbenv_instgen_destroy", "pcbenv_instgen_next", "pcbenv_instgen_next_batch",
-           "pcbenv_gather", "pcbenv_sample_logits", "pcbenv_evaluate_logits", "pcbenv_evaluate_logits_backward")
+           "pcbenv_gather", "pcbenv_sample_logits", "pcbenv_evaluate_logits", "pcbenv_evaluate_logits_backward",
+           "pcbenv_sample_axis", "pcbenv_evaluate_axis", "pcbenv_evaluate_axis_backward")
 
 
 class PcbenvConfig(C.Structure):
@@ -106,6 +109,12 @@ def load():
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pcbenv_evaluate_logits_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pcbenv_sample_axis.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.pcbenv_evaluate_axis.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pcbenv_evaluate_axis_backward.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pcbenv_mask_bits.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.pcbenv_mask_bits.restype = C.c_void_p
     if L.pcbenv_abi_version() != ABI_VERSION:

@@ -457,6 +457,105 @@ class BatchedPlacementEnv:
         form."""
         return self.evaluate_logits_forward(logits, mask_bits, actions, None, errors)
 
+    # -- factorised policies: one action coordinate at a time ---------------------------------------------------
+    def _axis_stage(self, axis, given):
+        """(axis, given) of a stage -> (axis code, `given` bit set, n); `given` is a bit set or a sequence of axes."""
+        axis = int(axis)
+        if axis not in (_lib.AXIS_ORIENTATION, _lib.AXIS_X, _lib.AXIS_Y):
+            raise ValueError(f"axis must be 0 (orientation), 1 (x) or 2 (y), got {axis}")
+        bits = int(given) if isinstance(given, int) else sum({1 << int(a) for a in given})
+        if bits & ~7 or bits & (1 << axis):
+            raise ValueError(f"given must name axes 0..2 other than the stage's own ({axis}), got {given}")
+        return axis, bits, (self.cfg.num_orientations, self.cfg.height, self.cfg.width)[axis]
+
+    def _check_axis_tensors(self, n, logits, actions, mask_bits=None):
+        """Shapes, dtypes, devices and contiguity of an axis call -> (rows, logits dtype code)."""
+        dtype = _logits_dtype(logits)
+        if logits.dim() != 2 or logits.shape[1] != n:
+            raise ValueError(f"logits must have shape [N, {n}], got {list(logits.shape)}")
+        N = logits.shape[0]
+        if actions.dtype != torch.int32 or tuple(actions.shape) != (N, 3):
+            raise ValueError(f"actions must be int32 [{N}, 3], got {actions.dtype} {list(actions.shape)}")
+        tensors = [("logits", logits), ("actions", actions)]
+        if mask_bits is not None:
+            H, WW = self.cfg.height, (self.cfg.width + 63) // 64
+            if mask_bits.dtype != torch.int64 or tuple(mask_bits.shape) != (N, 2, H, WW):
+                raise ValueError(f"mask_bits must be int64 [{N}, 2, {H}, {WW}], got {mask_bits.dtype} {list(mask_bits.shape)}")
+            tensors.append(("mask_bits", mask_bits))
+        for name, t in tensors:
+            # as sample_logits: the handle's device, or -- where it was named without an index -- the current one
+            if t.device != self.device and not (t.device.type == "cuda" and self.device.type == "cuda" and self.device.index is None
+                                                and t.device.index == torch.cuda.current_device()):
+                raise ValueError(f"{name} must be on {self.device}, got {t.device}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be C-contiguous (no copy is made)")
+        return N, dtype
+
+    def sample_axis(self, axis, logits: torch.Tensor, step_index: int, actions: torch.Tensor, given=(),
+                    greedy: bool = False, check: bool = False):
+        """One stage of a factorised policy on the device (`pcbenv_sample_axis`, one kernel launch): the masked
+        categorical over ONE action coordinate -- axis 0 orientation, 1 x, 2 y -- given the coordinates named in `given`
+        (a sequence of axes, or the bit set), which are read from `actions` int32 [B, 3]; the drawn value is written into
+        column `axis` of `actions` and the remaining column is left alone.  logits: float32 or bfloat16 [B, n] with
+        n = O, H or W, C-contiguous; entries outside the stage's legal set are never read.  The legal set comes from the
+        current state's bit rows (the reference's reduce_max / gather of `action_mask`,
+        utils/agent/factorized_action_distributions.py:107-818).  Returns (log_prob, entropy) float32 [B].  check=True
+        synchronises and raises if a logit of a legal set was NaN / +inf, every one -inf, or a given value out of range."""
+        axis, bits, n = self._axis_stage(axis, given)
+        N, dtype = self._check_axis_tensors(n, logits, actions)
+        if N != self.num_envs:
+            raise ValueError(f"logits must have shape [{self.num_envs}, {n}], got {list(logits.shape)}")
+        log_prob = torch.empty(N, dtype=torch.float32, device=self.device)
+        entropy = torch.empty(N, dtype=torch.float32, device=self.device)
+        err = torch.zeros(1, dtype=torch.int32, device=self.device) if check else None
+        _lib.check(self._L.pcbenv_sample_axis(
+            self._h, axis, bits, logits.data_ptr(), dtype, _lib.DRAW_GREEDY if greedy else _lib.DRAW_SAMPLE,
+            actions.data_ptr(), log_prob.data_ptr(), entropy.data_ptr(), None if err is None else err.data_ptr(),
+            self.run_seed, self.first_env_index, int(step_index), self._stream()), self._h)
+        if check:
+            e = int(err.item())
+            if e:
+                raise FloatingPointError(f"sample_axis: error bits {e:#x} (1: a logit of a legal set was NaN or +inf, 2: every "
+                                         "one was -inf -- those rows took the uniform pick; 8: a given value out of range)")
+        return log_prob, entropy
+
+    def evaluate_axis_forward(self, axis, given, logits, mask_bits, actions, errors: Optional[torch.Tensor] = None):
+        """`pcbenv_evaluate_axis`, one kernel launch: (log_prob, entropy) float32 [N] of the values stored in column
+        `axis` of `actions` int32 [N, 3] under the stage's masked categorical of `logits` [N, n], with the legal sets
+        derived from `mask_bits` int64 [N, 2, H, WW] and the given columns of `actions`.  errors: int32 [1] the error bits
+        are ORed into, or None."""
+        axis, bits, n = self._axis_stage(axis, given)
+        N, dtype = self._check_axis_tensors(n, logits, actions, mask_bits)
+        log_prob = torch.empty(N, dtype=torch.float32, device=logits.device)
+        entropy = torch.empty(N, dtype=torch.float32, device=logits.device)
+        if N == 0:  # torch gives empty tensors a null pointer
+            return log_prob, entropy
+        _lib.check(self._L.pcbenv_evaluate_axis(
+            self._h, axis, bits, logits.data_ptr(), dtype, mask_bits.data_ptr(), actions.data_ptr(), N, log_prob.data_ptr(),
+            entropy.data_ptr(), None if errors is None else errors.data_ptr(), self._stream()), self._h)
+        return log_prob, entropy
+
+    def evaluate_axis_backward(self, axis, given, logits, mask_bits, actions, grad_log_prob, grad_entropy,
+                               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`pcbenv_evaluate_axis_backward`, one kernel launch: the gradient with respect to `logits`, every element written
+        (into `out`, or a fresh `torch.empty_like(logits)`).  grad_log_prob / grad_entropy: float32 [N] or None (zero)."""
+        axis, bits, n = self._axis_stage(axis, given)
+        N, dtype = self._check_axis_tensors(n, logits, actions, mask_bits)
+        if out is None:
+            out = torch.empty_like(logits)
+        for name, t in (("grad_log_prob", grad_log_prob), ("grad_entropy", grad_entropy)):
+            if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (N,) or not t.is_contiguous() or t.device != logits.device):
+                raise ValueError(f"{name} must be a C-contiguous float32 tensor [{N}] on {logits.device}")
+        if out.dtype != logits.dtype or out.shape != logits.shape or not out.is_contiguous() or out.device != logits.device:
+            raise ValueError("out must match logits in dtype, shape and device and be C-contiguous")
+        if N == 0:
+            return out
+        _lib.check(self._L.pcbenv_evaluate_axis_backward(
+            self._h, axis, bits, logits.data_ptr(), dtype, mask_bits.data_ptr(), actions.data_ptr(), N,
+            None if grad_log_prob is None else grad_log_prob.data_ptr(),
+            None if grad_entropy is None else grad_entropy.data_ptr(), out.data_ptr(), self._stream()), self._h)
+        return out
+
     def rollout_step(self, step_index: int, flat: bool = False, out: Optional[torch.Tensor] = None):
         """`sample_actions` + `step` in one kernel launch (the body of the reference's random-policy
         `simulate()` loop, agent/random/random_policy_square.py:38-56); `out` receives the actions taken."""

@@ -6,7 +6,9 @@ Trajectories stay on the device as `[T, B, ...]` tensors.  With `policy=None` ev
 environment was created with `auto_reset=True`); with a policy callable the action comes from
 `policy(obs) -> int tensor [B] (flat) or [B, 3]`; with a logits callable (`logits_policy(obs) -> [B, O*H*W]` float32 /
 bfloat16 logits, raw or masked) the draw is `env.sample_logits` (`pcbenv_sample_logits`: the masked categorical on the
-device), and the trajectory also keeps each draw's log-probability and the entropy of its distribution.
+device), and the trajectory also keeps each draw's log-probability and the entropy of its distribution; with a
+factorised policy (`factorised_policy.act(env, obs, step_index, greedy, out)`, `pcbenv.factorised.FactorisedPolicy`) the
+draw is three `env.sample_axis` launches and the trajectory keeps their summed log-probability and entropy.
 """
 from __future__ import annotations
 
@@ -23,8 +25,8 @@ class Trajectory:
     dones: torch.Tensor        # [T, B] uint8
     info: Optional[torch.Tensor]  # [T, B, 2] float64 (wirelength, num_intersections; NaN when absent) or None
     obs: Dict[str, torch.Tensor]  # requested observation keys, [T, B, ...] (observation BEFORE the step)
-    log_prob: Optional[torch.Tensor] = None  # [T, B] float32, collect(logits_policy=...) only
-    entropy: Optional[torch.Tensor] = None   # [T, B] float32, collect(logits_policy=...) only
+    log_prob: Optional[torch.Tensor] = None  # [T, B] float32, collect(logits_policy=...) / collect(factorised_policy=...) only
+    entropy: Optional[torch.Tensor] = None   # [T, B] float32, collect(logits_policy=...) / collect(factorised_policy=...) only
     mask_bits: Optional[torch.Tensor] = None  # [T, B, 2, H, WW] int64 (legal set BEFORE the step), collect(store_mask_bits=True) only
 
     def episode_returns(self):
@@ -44,15 +46,19 @@ class Trajectory:
 
 def collect(env, num_steps: int, policy: Optional[Callable] = None, t0: int = 0,
             store_obs: Sequence[str] = (), logits_policy: Optional[Callable] = None, greedy: bool = False,
-            store_mask_bits: bool = False) -> Trajectory:
+            store_mask_bits: bool = False, factorised_policy=None) -> Trajectory:
     """logits_policy: step t draws `env.sample_logits(logits_policy(obs), t0 + t, greedy)`; not together with policy.
+    factorised_policy: step t calls `factorised_policy.act(env, env.obs, t0 + t, greedy, out=actions[t])`; not together
+    with policy or logits_policy.
     store_mask_bits: keep every step's bit-packed legal set (`env.mask_bits`), what `masked_categorical.evaluate` reads."""
     if policy is not None and logits_policy is not None:
         raise ValueError("collect: pass either policy or logits_policy, not both")
+    if factorised_policy is not None and (policy is not None or logits_policy is not None):
+        raise ValueError("collect: factorised_policy excludes policy and logits_policy")
     B, dev = env.num_envs, env.device
     actions = torch.zeros((num_steps, B, 3), dtype=torch.int32, device=dev)
     log_prob = entropy = None
-    if logits_policy is not None:
+    if logits_policy is not None or factorised_policy is not None:
         log_prob = torch.zeros((num_steps, B), dtype=torch.float32, device=dev)
         entropy = torch.zeros((num_steps, B), dtype=torch.float32, device=dev)
     rewards = torch.zeros((num_steps, B), dtype=torch.float64, device=dev)
@@ -68,6 +74,9 @@ def collect(env, num_steps: int, policy: Optional[Callable] = None, t0: int = 0,
             env.mask_bits(out=mask_bits[t])
         if logits_policy is not None:
             _, log_prob[t], entropy[t] = env.sample_logits(logits_policy(env.obs), t0 + t, greedy=greedy, out=actions[t])
+            env.step(actions[t])
+        elif factorised_policy is not None:
+            _, log_prob[t], entropy[t] = factorised_policy.act(env, env.obs, t0 + t, greedy, out=actions[t])
             env.step(actions[t])
         elif policy is None:
             env.rollout_step(t0 + t, out=actions[t])
