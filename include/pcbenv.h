@@ -40,6 +40,9 @@
  *                            utils/agent/factorized_action_distributions.py:107-818
  *   pcbenv_gather          no counterpart: the closest is copy.deepcopy(env) of a reference env object, which a
  *                          caller uses to fork an episode (lookahead, beam search, population resampling)
+ *   pcbenv_playout         copy.deepcopy(env) of a reference env object followed by the random policy's simulate() loop
+ *                          on the copy, played per fork
+ *                            agent/random/random_policy_square.py:25-58 (and siblings)
  *
  * Observations are written into caller-owned device buffers (pcbenv_buffers)
  * and updated in place by the next call; the library owns only the handle, the
@@ -331,6 +334,49 @@ int pcbenv_set_state(pcbenv *env, const void *host_src, void *stream);
  * queue cursor, the episode count, the queue and the on-device generator's state.  The next reset of i takes i's own
  * next instance, as it would have without the gather. */
 int pcbenv_gather(pcbenv *dst, const pcbenv *src, const int32_t *src_index_dev, uint32_t *errors_dev, void *stream);
+
+/* Play forked episodes to their end on the device, without observations: the rollout-policy primitive of a search.  One
+ * kernel launch on `stream`, one team per playout; the root's state block is read once and the episode then lives in
+ * LDS until it ends -- no observation tensor, no second handle, no launch per step.
+ * The identity.  Playout i starts from the episode in progress of environment r = root_index_dev[i] of env (state read
+ * from the current state set, as pcbenv_sample_actions reads it) and applies transitions t = 0, 1, ... until the first
+ * `done` or until max_steps transitions, whichever comes first.  Transition t draws what
+ * pcbenv_step_sampled(seed, first_env_index, step_index0 + t) would draw for environment i of a handle of num_playouts
+ * environments without PCBENV_FLAG_AUTO_RESET after pcbenv_gather had put root r's episode there -- the uniform legal
+ * draw keyed by (seed, first_env_index + i, step_index0 + t) -- and the transition is that handle's transition, bit for
+ * bit.  That also covers a root whose episode is already over: one transition, as that handle would do it.
+ * root_index_dev: int32 [num_playouts] on the device, or NULL: num_playouts must then be a multiple of num_envs and
+ * playout i plays root i / (num_playouts / num_envs).
+ * first_actions_dev: NULL, or int32 [num_playouts, 3] / [num_playouts] per action_format: transition 0 applies that
+ * action instead of a draw; an illegal or out-of-range action is data -- a terminal transition with the worst-case
+ * reward, as in pcbenv_step.  Later transitions draw.
+ * Outputs (device pointers; only reward_dev is required, the others may be NULL):
+ *   reward_dev[i]       float64: the value the reward tensor would show at the last transition played.  Not a sum
+ *                       (square / rect: the return is length - 1 + reward).
+ *   done_dev[i]         uint8: 0 when the playout was cut at max_steps
+ *   length_dev[i]       int32: the number of transitions played
+ *   info_dev[i, 2]      float64 (wirelength, num_intersections) of that last transition, NaN where the reference's info
+ *                       dict is empty.  Pin kinds only (ignored otherwise).
+ *   actions_out_dev     int32 [actions_steps, num_playouts, 3] or [actions_steps, num_playouts]: rows
+ *                       t < min(length, actions_steps) are written (row 0 of a forced action: the action as given), the
+ *                       others are untouched.  actions_steps is in 0 ... max_steps: a receding-horizon caller keeps
+ *                       only the first action.
+ * A root_index outside [0, num_envs) is checked before it addresses anything: bit 0 is ORed into *errors_dev (if not
+ * NULL) and that playout reports length = 0, done = 0, reward = 0.0 and NaN info.
+ * Writes nothing the library owns and nothing bound -- state blocks, the fused sampler's presampled action, the terminal
+ * list and its marks, queue, cursors, observation tensors: a later call on the handle behaves exactly as without it.
+ * PCBENV_FLAG_AUTO_RESET is ignored (a playout never resets and never consumes an instance), as are the trajectory
+ * layout, the selected slot, helper marks in the root's header and its presampled action.
+ * PCBENV_EINVAL (checked before any device call, in this order): null reward_dev; unknown format; max_steps < 1;
+ * actions_steps outside [0, max_steps], or > 0 with null actions_out_dev; num_playouts < 0; null root_index_dev with
+ * num_playouts not a multiple of num_envs; null handle.  num_playouts == 0 is a no-op success.  PCBENV_ESTATE: buffers
+ * not bound, no episode in the handle yet (no reset, gather or restored state), or `stream` is being captured into a
+ * hipGraph (the current-set pointer alternates; as pcbenv_sample_logits). */
+int pcbenv_playout(const pcbenv *env, const int32_t *root_index_dev, int64_t num_playouts,
+                   const int32_t *first_actions_dev, int32_t action_format, int32_t max_steps,
+                   double *reward_dev, uint8_t *done_dev, int32_t *length_dev, double *info_dev,
+                   int32_t *actions_out_dev, int32_t actions_steps, uint32_t *errors_dev,
+                   uint64_t seed, uint64_t first_env_index, uint64_t step_index0, void *stream);
 
 /* Masked categorical draw from a policy's logits, on the device, one kernel launch on `stream`.
  * logits_dev: C-contiguous [num_envs, A], A = O*H*W (square: H*W), in the flat action order of PCBENV_ACTION_FLAT

@@ -48,6 +48,7 @@ struct pcbenv {
     // cell tensor of the current binding starts at a 16-byte boundary (pcbenv_bind_buffers_slots looks once).
     bool fixed_geometry, cells_aligned16;
     unsigned char *gather_snap;   // pcbenv_gather within one handle: reward | info | done of the selected slot before the launch
+    bool has_episode;  // a reset, a gather or a restored checkpoint has put episodes into the state blocks (pcbenv_playout asks)
     char err[256];
 };
 

@@ -36,6 +36,23 @@ struct GatherArgs {
 };
 struct GatherLaunch { DevParams d; GatherArgs g; int threads; hipStream_t stream; };
 
+// pcbenv_playout (pcb_playout_*.hip): d is the root handle's parameter block with d.state = the current state set,
+// buf.reward / buf.info repointed at the playout's rows and everything else a playout must not touch taken out (every
+// other tensor null, flags 0, no terminal list); the rest travels in PlayoutArgs.
+struct PlayoutArgs {
+    const int *root_index;     // [n] or null: playout i plays root i / per_root
+    const int *first_actions;  // [n, 3] / [n] or null: the action of transition 0
+    double *reward;            // [n]
+    unsigned char *done;       // [n], may be null
+    int *length;               // [n], may be null
+    double *info;              // [n, 2], may be null (pin kinds only)
+    int *actions_out;          // [actions_steps, n, 3] / [actions_steps, n], null if actions_steps == 0
+    unsigned *errors;          // may be null
+    int n, per_root, fmt, max_steps, actions_steps;
+    u64 seed, first_env, step_index0;
+};
+struct PlayoutLaunch { DevParams d; PlayoutArgs g; int threads; bool routes; hipStream_t stream; };
+
 // pcbenv_sample_actions and pcbenv_queue_cursors (pcb_sample.hip): d.state = the current state set; out = two words, min and max
 struct SampleLaunch { DevParams d; int *actions; int fmt; u64 seed, first_env, step_index; hipStream_t stream; };
 int pcb_launch_sample(const SampleLaunch &a);
@@ -110,5 +127,5 @@ int pcb_launch_evaluate_axis(const EvalAxisLaunch &a);
 int pcb_launch_evaluate_axis_backward(const EvalAxisBackwardLaunch &a);
 
 #define PCB_DECLARE_KIND(name) int pcb_launch_step_##name(const StepLaunch &a); int pcb_launch_reset_##name(const ResetLaunch &a); \
-    int pcb_launch_gather_##name(const GatherLaunch &a);
+    int pcb_launch_gather_##name(const GatherLaunch &a); int pcb_launch_playout_##name(const PlayoutLaunch &a);
 PCB_DECLARE_KIND(square) PCB_DECLARE_KIND(rect) PCB_DECLARE_KIND(pin) PCB_DECLARE_KIND(spatial)

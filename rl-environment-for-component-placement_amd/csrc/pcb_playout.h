@@ -1,0 +1,140 @@
+// pcb_playout.h -- k_playout, the kernel of pcbenv_playout: forked episodes played to their end without observations.
+// Part of libpcbenv.so (CDNA4 / gfx950 only).  Instantiated in translation units of its own (pcb_playout.inc), never next
+// to k_step: the step kernels' inlining depends on every function having one caller in their units (pcb_kind.inc).
+//
+// One team per playout, the team size of the handle (the state layout and the fold staging depend on it).  The root's
+// state block of the CURRENT state set -> LDS, then a loop of at most max_steps transitions, each exactly the transition
+// a handle without PCBENV_FLAG_AUTO_RESET would make after pcbenv_gather had put the root's episode into its environment
+// i (Team<>::transition in MODE_ALL, pcb_step.h): draw (sample_action on l.vm, keyed by (seed, first_env + i,
+// step_index0 + t)) or, at t = 0, the caller's forced action -> validate -> placement update -> legal mask without
+// emission -> done -> reward.  The state never leaves LDS: no store_state, no observation byte, nothing the library owns
+// is written.  What a playout writes is its row of the caller's outputs, each element by one lane, once:
+// reward / done / length / info after the last transition and the action of every recorded step.
+//
+// The placement update is restated here instead of calling Team<>::transition: that function stores done and reward rows
+// at every transition (the playout's done row is optional and its reward is the LAST transition's only) and carries the
+// reset and every emission under run-time flags, which this kernel would compile in and hold registers for.  What
+// is shared is everything with a result in it: window_mask through mask_and_emit(emit = false), sample_action and
+// terminal_reward -- the latter through the parameter block, whose buf.reward / buf.info the host points at the
+// playout's rows (every other tensor null, flags and the terminal list zeroed: pcbenv_playout).
+#pragma once
+#include "pcb_team.h"
+#include "pcb_launch.h"
+
+template <int KIND, int WW, int NW, bool ROUTES>
+__global__ __attribute__((amdgpu_waves_per_eu(4, 8))) __launch_bounds__(64 * NW) void k_playout(DevParams p, PlayoutArgs g) {
+    typedef Team<64 * NW> T;
+    constexpr int NT = 64 * NW;
+    constexpr bool PINS = KIND == PCBENV_PIN || KIND == PCBENV_SPATIAL;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    // the children of one root are neighbours in i: with an XCD's playouts contiguous the root block is fetched once per L2
+    const int i = xcd_contiguous_env((int)blockIdx.x, 0, g.n), lane0 = threadIdx.x;
+    const int H = p.H, W = p.W, HW = H * W, plane = H * WW;
+    const int r = __builtin_amdgcn_readfirstlane(g.root_index ? g.root_index[i] : i / g.per_root);
+    if ((unsigned)r >= (unsigned)p.B) {  // checked before it addresses anything (team-uniform: nobody meets a barrier below)
+        if (lane0 == 0) {
+            if (g.errors) atomicOr(g.errors, 1u);
+            g.reward[i] = 0.0;
+            if (g.done) g.done[i] = 0;
+            if (g.length) g.length[i] = 0;
+            if (PINS && g.info) { g.info[2 * (size_t)i] = nan(""); g.info[2 * (size_t)i + 1] = nan(""); }
+        }
+        return;
+    }
+    T::load_state_from(smem, p.state + (size_t)r * p.stateStride, p, lane0);
+    Lds l = carve(smem, p);
+    const int genv = (int)g.first_env + i;
+    const size_t per_step = (size_t)g.n * (g.fmt == PCBENV_ACTION_TUPLE ? 3 : 1);
+    bool done = false, valid = false;
+    int length = 0;
+    // (a `for` bounded by the host's max_steps: no data on the device can keep a team here)
+    for (int t = 0; t < g.max_steps; t++) {
+        // every iteration sees the lane index as a fresh value (run_env: keeps per-lane addressing out of the loop's live set)
+        int lane = lane0;
+        asm volatile("" : "+v"(lane));
+        int o = 0, x = 0, y = 0, given = 0;
+        const bool forced = t == 0 && g.first_actions;
+        if (forced) {  // as run_env reads a caller's action: out of range is data (an invalid action), checked before use below
+            if (g.fmt == PCBENV_ACTION_FLAT) {
+                const int a = g.first_actions[i];
+                given = a;
+                if (a < 0 || a >= p.O * HW) { o = -1; x = y = 0; }
+                else { o = a / HW; const int rem = a - o * HW; x = rem / W; y = rem - x * W; }
+            } else {
+                o = g.first_actions[3 * (size_t)i]; x = g.first_actions[3 * (size_t)i + 1]; y = g.first_actions[3 * (size_t)i + 2];
+                if (KIND == PCBENV_SQUARE) o = 0;
+            }
+        } else {
+            if (lane < WAVE) {  // wavefront 0 draws (the result is wave-uniform), the others take it from LDS
+                sample_action(l.vm, p, genv, lane, g.seed, g.step_index0 + (u64)t, &o, &x, &y);
+                if (NT > WAVE && lane == 0) { l.hdr->pad[0] = (unsigned)o; l.hdr->pad[1] = (unsigned)x; l.hdr->flag = (unsigned)y; }
+            }
+            if (NT > WAVE) {
+                T::lds_sync();
+                o = (int)l.hdr->pad[0]; x = (int)l.hdr->pad[1]; y = (int)l.hdr->flag;
+            }
+        }
+        if (lane == 0 && t < g.actions_steps) {
+            int *act = g.actions_out + per_step * (size_t)t;
+            if (g.fmt == PCBENV_ACTION_FLAT) act[i] = forced ? given : o * HW + x * W + y;
+            else { act[3 * (size_t)i] = o; act[3 * (size_t)i + 1] = x; act[3 * (size_t)i + 2] = y; }
+        }
+        // validate_action (S:1699-1723), as Team<>::transition: anything out of range is invalid
+        const int cur = l.hdr->cur, ncomp = l.hdr->ncomp, npins = l.hdr->npins;
+        valid = o >= 0 && o < p.O && x >= 0 && x < H && y >= 0 && y < W && (KIND == PCBENV_SQUARE || cur >= 0);
+        if (valid) valid = (l.vm[(o & 1) * plane + x * WW + (y >> 6)] >> (y & 63)) & 1ull;
+        if (NT > WAVE) T::lds_sync();  // every wavefront has read the cursor and the mask bit before anything below changes them
+        done = true;  // an invalid action is a terminal transition with the state unchanged (quirk Q8 iii)
+        if (valid) {
+            int ph, pw;
+            CompRec cr = CompRec();
+            if (KIND == PCBENV_SQUARE) ph = pw = p.component_n;
+            else {
+                cr = l.comps[cur];
+                ph = (o & 1) ? cr.w : cr.h;  // S:1742-1747 update_grid
+                pw = (o & 1) ? cr.h : cr.w;
+            }
+            for (int rr = x + lane; rr < x + ph && rr < H; rr += NT) {
+                for (int w = 0; w < WW; w++) {
+                    const int lo = max(y, 64 * w) - 64 * w, hi = min(y + pw, 64 * w + 64) - 64 * w;  // bit range in word w
+                    if (hi > lo) l.occ[rr * WW + w] |= ((hi - lo) >= 64 ? ~0ull : ((1ull << (hi - lo)) - 1ull)) << lo;
+                }
+            }
+            if (KIND != PCBENV_SQUARE) {
+                if (lane == 0) { l.comps[cur].px = (signed char)x; l.comps[cur].py = (signed char)y; l.comps[cur].o = (unsigned char)o; }
+                if (PINS) {
+                    const int ch = cr.h, cw = cr.w;
+                    for (int q = lane; q < npins; q += NT) {  // S:149-190 place_component
+                        PinRec pr = l.pins[q];
+                        if (pr.comp != cur) continue;
+                        const int rx = pr.rel_x, ry = pr.rel_y;
+                        if (o == 1) { pr.rel_x = ry; pr.rel_y = ch - rx - 1; }
+                        else if (o == 2) { pr.rel_x = ch - rx - 1; pr.rel_y = cw - ry - 1; }
+                        else if (o == 3) { pr.rel_x = cw - ry - 1; pr.rel_y = rx; }
+                        pr.abs_x = (signed char)(x + pr.rel_x); pr.abs_y = (signed char)(y + pr.rel_y);
+                        l.pins[q] = pr;
+                    }
+                }
+                if (lane == 0) l.hdr->cur = (short)(cur + 1 < ncomp ? cur + 1 : -1);
+            }
+            T::lds_sync();
+            const bool any = T::template mask_and_emit<KIND, WW>(p, l, i, lane, false, 0, 0);  // team-uniform (block_any)
+            done = KIND == PCBENV_SQUARE ? !any : (l.hdr->cur < 0 || !any);  // S:1856-1869
+        }
+        length = t + 1;
+        // `done` is team-uniform: valid, cur and `any` are functions of LDS words every wavefront read behind a barrier
+        if (done) break;
+        T::lds_sync();
+    }
+    // the outputs of the last transition played (Team<>::transition's reward rules)
+    if (lane0 == 0) {
+        if (g.done) g.done[i] = done ? 1 : 0;
+        if (g.length) g.length[i] = length;
+    }
+    if (PINS && done) {  // routed if everything is placed, else the worst case (S:853-863): reward and info of row i
+        T::template terminal_reward<KIND, ROUTES>(p, l, i, lane0, 0, 1, 0u);
+    } else if (lane0 == 0) {
+        g.reward[i] = PINS ? 0.0 : (valid ? 1.0 : 0.0);  // R:424-432
+        if (PINS && g.info) { g.info[2 * (size_t)i] = nan(""); g.info[2 * (size_t)i + 1] = nan(""); }
+    }
+}

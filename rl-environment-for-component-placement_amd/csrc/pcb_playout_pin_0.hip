@@ -1,0 +1,7 @@
+// pcb_playout_pin_0.hip -- k_playout of the pin environment, part 0 (pcb_playout.inc lists the parts; one translation unit each: they compile in parallel)
+#include <hip/hip_runtime.h>
+#include "pcbenv.h"
+#define PCB_KIND PCBENV_PIN
+#define PCB_KIND_NAME pin
+#define PCB_PART 0
+#include "pcb_playout.inc"

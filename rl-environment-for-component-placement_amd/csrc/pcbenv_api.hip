@@ -1,5 +1,5 @@
 // pcbenv_api.hip -- host side of libpcbenv.so's C ABI (include/pcbenv.h): create / destroy / options / bind / load,
-// reset / step / rollout / sample, checkpoint, gather and the logits entry points.  No kernel is defined here: the
+// reset / step / rollout / sample, checkpoint, gather, playout and the logits entry points.  No kernel is defined here: the
 // environment kernels are instantiated per kind in pcb_kind_*.hip, k_sample and k_cursor_range in pcb_sample.hip and the
 // policy kernels in pcb_policy*.hip (all reached through pcb_launch.h); pcb_config.hip derives the layout from a
 // configuration and pcb_gen.hip owns the on-device instance generator (pcb_host.h declares what the three share).
@@ -27,8 +27,9 @@ struct KindLaunch {
     int (*step)(const StepLaunch &);
     int (*reset)(const ResetLaunch &);
     int (*gather)(const GatherLaunch &);
+    int (*playout)(const PlayoutLaunch &);
 };
-#define PCB_KIND_LAUNCH(name) {pcb_launch_step_##name, pcb_launch_reset_##name, pcb_launch_gather_##name}
+#define PCB_KIND_LAUNCH(name) {pcb_launch_step_##name, pcb_launch_reset_##name, pcb_launch_gather_##name, pcb_launch_playout_##name}
 static const KindLaunch kind_launch[] = {PCB_KIND_LAUNCH(square), PCB_KIND_LAUNCH(rect), PCB_KIND_LAUNCH(pin), PCB_KIND_LAUNCH(spatial)};
 static_assert(PCBENV_SQUARE == 0 && PCBENV_RECT == 1 && PCBENV_PIN == 2 && PCBENV_SPATIAL == 3, "kind_launch is indexed by kind");
 
@@ -325,9 +326,11 @@ static int step_checks(pcbenv *env, const void *actions_dev, int fmt, LaunchPlan
 }
 
 extern "C" int pcbenv_reset(pcbenv *env, const uint8_t *mask_dev, void *stream) {
-    return consuming_launch(
+    const int rc = consuming_launch(
         env, stream, [&](LaunchPlan &plan) { plan.consumes = 1; return check_queue(env); },
         [&](int, hipStream_t s) { launch_reset(env, mask_dev, s); });
+    if (rc == PCBENV_OK) env->has_episode = true;
+    return rc;
 }
 
 extern "C" int pcbenv_get_instances(pcbenv *env, int32_t slot, void *host_dst, void *stream) {
@@ -435,6 +438,7 @@ extern "C" int pcbenv_set_state(pcbenv *env, const void *host_src, void *stream)
     const int rc = gen_restore(env, (const unsigned char *)host_src + sb, s);
     if (rc != PCBENV_OK) return rc;
     HIP_TRY(env, hipStreamSynchronize(s));
+    env->has_episode = true;
     return PCBENV_OK;
 }
 
@@ -481,12 +485,65 @@ extern "C" int pcbenv_gather(pcbenv *dst, const pcbenv *src, const int32_t *src_
     }
     kind_launch[dst->cfg.kind].gather(a);
     HIP_TRY(dst, hipGetLastError());
+    dst->has_episode = true;
     if (dst->in_place) {  // a captured graph works on the current set (dispatch_step): the gathered blocks go back into it
         HIP_TRY(dst, hipMemcpyAsync(d.state, d.state_out, state_section_bytes(dst), hipMemcpyDeviceToDevice, s));
         return PCBENV_OK;
     }
     dst->state_cur ^= 1;
     dst->dp.state = dst->dp.state_out = dst->state_buf[dst->state_cur];
+    return PCBENV_OK;
+}
+
+// ---- pcbenv_playout ------------------------------------------------------------------------------------------
+// As pcbenv_sample_logits: the argument checks come before anything touches a device (the null handle last), and nothing
+// the library owns is written -- the kernel gets a parameter block in which nothing but the playout's own reward / info
+// rows can be stored to.
+extern "C" int pcbenv_playout(const pcbenv *cenv, const int32_t *root_index_dev, int64_t num_playouts,
+                              const int32_t *first_actions_dev, int32_t fmt, int32_t max_steps, double *reward_dev,
+                              uint8_t *done_dev, int32_t *length_dev, double *info_dev, int32_t *actions_out_dev,
+                              int32_t actions_steps, uint32_t *errors_dev, uint64_t seed, uint64_t first_env_index,
+                              uint64_t step_index0, void *stream) {
+    pcbenv *env = const_cast<pcbenv *>(cenv);  // the error text only
+    if (!reward_dev) return fail(env, PCBENV_EINVAL, "null reward");
+    CHECK_ACTION_FORMAT(env, fmt);
+    if (max_steps < 1) return fail(env, PCBENV_EINVAL, "max_steps must be at least 1");
+    if (actions_steps < 0 || actions_steps > max_steps) return fail(env, PCBENV_EINVAL, "actions_steps must be in [0, max_steps]");
+    if (actions_steps > 0 && !actions_out_dev) return fail(env, PCBENV_EINVAL, "null actions_out with actions_steps > 0");
+    if (num_playouts < 0) return fail(env, PCBENV_EINVAL, "num_playouts must not be negative");
+    if (env && !root_index_dev && num_playouts % env->dp.B != 0)
+        return fail(env, PCBENV_EINVAL, "without root_index, num_playouts must be a multiple of num_envs");
+    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
+    if (num_playouts > 0x7fffffffll / 8) return fail(env, PCBENV_ELIMIT, "num_playouts too large");
+    if (num_playouts == 0) return PCBENV_OK;
+    if (!env->bound) return fail(env, PCBENV_ESTATE, "pcbenv_bind_buffers has not been called");
+    if (!env->has_episode) return fail(env, PCBENV_ESTATE, "no episode to play: reset the environments first");
+    DEVICE_GUARD(env);
+    hipStream_t s = (hipStream_t)stream;
+    // A captured launch would keep reading the state set that was current at capture time (as pcbenv_sample_logits).
+    if (stream_capturing(s)) return fail(env, PCBENV_ESTATE, "pcbenv_playout cannot be captured into a graph");
+    PlayoutLaunch a;
+    a.d = env->dp;  // d.state: the current state set, as k_sample reads it
+    DevParams &d = a.d;
+    const bool pins = is_pin_kind(env->cfg.kind);
+    // nothing bound and nothing of the library's can be reached through the block: terminal_reward writes row i of these two
+    memset(&d.buf, 0, sizeof(d.buf));
+    memset(&d.cbuf, 0, sizeof(d.cbuf));
+    d.buf.reward = reward_dev; d.buf.info = pins ? info_dev : 0;
+    d.flags = 0u; d.num_slots = 1; d.slot = 0; d.stream_stores = 0;
+    d.queue = 0; d.feat_cache = 0; d.feat_cache_tag = 0; d.gen_produced = 0; d.gen_errors = 0; d.cursor_pub = 0;
+    d.seq = 0u; d.term_wgs = 0; d.term_cap = 0; d.term_hpe = 0; d.term_list = 0; d.term_cnt = 0; d.term_arrive = 0; d.term_seen = 0;
+    d.state_out = 0; d.dbg = 0;
+    a.threads = env->threads; a.stream = s;
+    a.routes = pins && env->cfg.reward_type != PCBENV_REWARD_CENTROID;
+    PlayoutArgs &g = a.g;
+    g.root_index = root_index_dev; g.first_actions = first_actions_dev; g.reward = reward_dev; g.done = done_dev;
+    g.length = length_dev; g.info = pins ? info_dev : 0; g.actions_out = actions_out_dev; g.errors = (unsigned *)errors_dev;
+    g.n = (int)num_playouts; g.per_root = root_index_dev ? 1 : (int)(num_playouts / d.B);
+    g.fmt = fmt; g.max_steps = max_steps; g.actions_steps = actions_steps;
+    g.seed = (u64)seed; g.first_env = (u64)first_env_index; g.step_index0 = (u64)step_index0;
+    kind_launch[env->cfg.kind].playout(a);
+    HIP_TRY(env, hipGetLastError());
     return PCBENV_OK;
 }
 

@@ -28,7 +28,7 @@ EXPORTS = ("pcbenv_abi_version", "pcbenv_create", "pcbenv_destroy", "pcbenv_last
            "pcbenv_instgen_device_enable", "pcbenv_instgen_device_status", "pcbenv_get_instances",
            "pcbenv_instgen_create", "pcbenv_instgen_destroy", "pcbenv_instgen_next", "pcbenv_instgen_next_batch",
            "pcbenv_gather", "pcbenv_sample_logits", "pcbenv_evaluate_logits", "pcbenv_evaluate_logits_backward",
-           "pcbenv_sample_axis", "pcbenv_evaluate_axis", "pcbenv_evaluate_axis_backward")
+           "pcbenv_sample_axis", "pcbenv_evaluate_axis", "pcbenv_evaluate_axis_backward", "pcbenv_playout")
 
 
 class PcbenvConfig(C.Structure):
@@ -115,6 +115,8 @@ def load():
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pcbenv_evaluate_axis_backward.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pcbenv_playout.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     L.pcbenv_mask_bits.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.pcbenv_mask_bits.restype = C.c_void_p
     if L.pcbenv_abi_version() != ABI_VERSION:

@@ -11,6 +11,7 @@ kernels on the current torch stream; nothing here touches observation data.
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -59,6 +60,23 @@ def obs_spec(cfg: EnvConfig) -> Dict[str, tuple]:
             "action_mask": ((4, H, W), u8), "all_components_feature": ((Cc, 5 + mp), f64),
             "placement_mask": ((Cc,), f64), "all_pins_num_feature": ((Cc * mp + 1, 4), f64),
             "all_pins_cat_feature": ((Cc * mp + 1, 2), f64)}
+
+
+@dataclass
+class Playout:
+    """What `BatchedPlacementEnv.playout` returns, one row per playout (n = number of playouts)."""
+    reward: torch.Tensor            # [n] float64: the reward of the last transition played (not a sum)
+    done: torch.Tensor              # [n] uint8: 0 where the playout was cut at max_steps
+    length: torch.Tensor            # [n] int32: transitions played
+    info: Optional[torch.Tensor]    # [n, 2] float64 (wirelength, num_intersections), NaN where empty; None for square / rect
+    actions: Optional[torch.Tensor] # [actions_steps, n, 3] int32, rows t >= length are zero; None if actions_steps == 0
+
+
+def default_max_steps(cfg: EnvConfig) -> int:
+    """The most transitions an episode can have: one per component (square: one per n x n tile of the grid)."""
+    if cfg.kind == KIND_SQUARE:
+        return (cfg.height // cfg.component_n) * (cfg.width // cfg.component_n)
+    return cfg.max_num_components
 
 
 class _ExternalBlock:
@@ -605,6 +623,58 @@ class BatchedPlacementEnv:
         if check and int(err.item()) != 0:
             raise IndexError(f"gather_: an index is outside [-1, {src.num_envs}) (those environments kept their episode)")
         return self.obs
+
+    def playout(self, k: Optional[int] = None, index: Optional[torch.Tensor] = None, step_index: int = 0,
+                first_actions: Optional[torch.Tensor] = None, max_steps: Optional[int] = None,
+                actions_steps: Optional[int] = None, first_env_index: int = 0, check: bool = False) -> Playout:
+        """Play forked episodes to their end on the device without observations (`pcbenv_playout`, one kernel launch, no
+        second handle): playout i starts from the episode in progress of environment `index[i]` -- or, with `k`,
+        environment i // k (k playouts per environment) -- and takes uniformly drawn legal actions until its first
+        `done` or `max_steps` transitions (default: the most an episode can have).  Transition t draws what
+        `rollout_step(step_index + t)` draws for environment i of a handle with `first_env_index`, this handle's
+        `run_seed` and auto_reset=False after `gather_` had forked the roots into it, and the transition is that
+        handle's, bit for bit.  first_actions: int32 [n, 3] or flat [n]: the action of transition 0 instead of a draw (an
+        illegal one ends the playout with the worst-case reward, as `step` would).  actions_steps (default max_steps):
+        how many leading actions to record.  Nothing of this environment batch changes.  check=True synchronises and
+        raises IndexError if an index was out of range (those rows report length 0)."""
+        if (k is None) == (index is None):
+            raise ValueError("playout: give either k (playouts per environment) or index (the root of every playout)")
+        idx = None
+        if index is not None:
+            idx = index.to(device=self.device, dtype=torch.int32).contiguous()
+            if idx.dim() != 1:
+                raise ValueError(f"index must be one-dimensional, got {tuple(idx.shape)}")
+            n = idx.shape[0]
+        else:
+            if int(k) < 1:
+                raise ValueError("k must be at least 1")
+            n = self.num_envs * int(k)
+        T = default_max_steps(self.cfg) if max_steps is None else int(max_steps)
+        A = T if actions_steps is None else int(actions_steps)
+        fmt, fa = _lib.ACTION_TUPLE, None
+        if first_actions is not None:
+            fa = first_actions.to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(fa.shape) not in ((n,), (n, 3)):
+                raise ValueError(f"first_actions must have shape [{n}] (flat) or [{n}, 3], got {tuple(fa.shape)}")
+            if fa.dim() == 1:
+                fmt = _lib.ACTION_FLAT
+        pins = self.cfg.kind in (KIND_PIN, KIND_SPATIAL)
+        dev = self.device
+        reward = torch.empty(n, dtype=torch.float64, device=dev)
+        done = torch.empty(n, dtype=torch.uint8, device=dev)
+        length = torch.empty(n, dtype=torch.int32, device=dev)
+        info = torch.empty((n, 2), dtype=torch.float64, device=dev) if pins else None
+        actions = torch.zeros((A, n) if fmt == _lib.ACTION_FLAT else (A, n, 3), dtype=torch.int32, device=dev) if A > 0 else None
+        err = torch.zeros(1, dtype=torch.int32, device=dev) if check else None
+        if n == 0:  # torch gives empty tensors a null pointer
+            return Playout(reward, done, length, info, actions)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(self._L.pcbenv_playout(
+            self._h, ptr(idx), n, ptr(fa), fmt, T, reward.data_ptr(), done.data_ptr(), length.data_ptr(), ptr(info),
+            ptr(actions), A, ptr(err), self.run_seed, int(first_env_index), int(step_index), self._stream()), self._h)
+        if check and int(err.item()) != 0:
+            raise IndexError(f"playout: an index is outside [0, {self.num_envs}) (those playouts report length 0)")
+        return Playout(reward, done, length, info, actions)
 
     def queue_cursors(self):
         """(min, max) over the environments of the number of resets performed so far (synchronises)."""
