@@ -1,6 +1,6 @@
-"""The instance generator's configuration space: twelve configurations that reach what c2 .. c5 and the small grids do
+"""The instance generator's configuration space: sixteen configurations that reach what c2 .. c5 and the small grids do
 not (64-lane groups chosen by the configuration, the knobs at their ends, 16-pin nets, 1x1 and fully pinned components,
-streams the reference itself stops on), the fixture the reference recorded for them
+different w and h ranges on non-square grids, streams the reference itself stops on), the fixture the reference recorded for them
 (tests/golden/generator_tables.npz, written by make_golden.record_generator_tables) and the host twin driven stream by
 stream.  Shared by the CPU tests (test_host_logic.py, test_instance_gen_native.py) and tests/test_device_generator_gpu.py.
 A plain module: nothing here touches a device."""
@@ -27,9 +27,15 @@ CASES = {
     "fail_pin": ("pin", (10, 10, 5, 5, 2, 4, 2, 4, 4, 1, 1, 3, 6, 4) + TAIL, 16),               # about half of the streams stop
     "fail_spatial_1x1": ("spatial", (8, 8, 5, 5, 1, 2, 1, 2, 3, 1, 1, 2, 3, 1) + TAIL, 16),     # streams stop on num_nets < 1
     "fail_nets16": ("spatial", (24, 24, 5, 5, 2, 4, 2, 4, 12, 6, 2, 3, 16, 16) + TAIL, 16),     # about 15 % stop; 16-pin nets
+    # different w and h ranges on H != W (arguments: ..., min_w, max_w, min_h, max_h, ...): a swapped axis shows here
+    "pin_asym_40x72": ("pin", (40, 72, 5, 5, 2, 8, 2, 4, 12, 8, 4, 6, 6, 3) + TAIL, 16),
+    "spatial_asym_72x40": ("spatial", (72, 40, 5, 5, 2, 4, 2, 8, 12, 8, 4, 6, 6, 3) + TAIL, 16),
+    "spatial_asym_9x14": ("spatial", (9, 14, 3, 4, 2, 5, 1, 3, 6, 2, 2, 4, 5, 2) + TAIL, 16),
+    "rect_asym_12x7": ("rect", (12, 7, 2, 3, 1, 5, 6, 2), 16),
 }
 FAIL_CASES = tuple(n for n in CASES if n.startswith("fail_"))
 OK_CASES = tuple(n for n in CASES if not n.startswith("fail_"))
+ASYM_CASES = tuple(n for n in CASES if "_asym_" in n)
 RESETS = 8            # records per stream in the fixture
 NEVER = 1 << 30       # fail_at of a stream that does not stop
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "generator_tables.npz")

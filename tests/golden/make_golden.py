@@ -4,6 +4,7 @@
 Run in the build container only (needs /root/reference, which never travels):
 
     PYTHONDONTWRITEBYTECODE=1 python3 tests/golden/make_golden.py
+    PYTHONDONTWRITEBYTECODE=1 python3 tests/golden/make_golden.py cases NAME [NAME ...]   # only these episode cases
 
 It imports `/root/reference/environment/dummy_env_*.py` with the stand-in `gym`
 package of oracle/refshim first on sys.path (gym is used by those files only for
@@ -74,6 +75,22 @@ CASES += [
     ("spatial_mid_both_k4", "spatial", MID + ("both", 4, 0.25), list(range(6)), 3, 0.03),
     ("pin_mid_beam_k1", "pin", MID + ("beam", 1, 0.25), list(range(6)), 3, 0.03),
 ]
+# H != W with different w and h ranges (arguments: height, width, ..., min_w, max_w, min_h, max_h, ...): the reference
+# validates max_component_w against the height, rotation swaps h and w, and an action is (o, x, y) over (H, W).  The
+# last two are the first with two mask words per row (40x72) and with more rows than a wavefront has lanes (72x40).
+ASYM = (3, 4, 2, 5, 1, 3, 6, 2, 2, 4, 5, 2)
+ASYM_T = (3, 4, 1, 3, 2, 5, 6, 2, 2, 4, 5, 2)
+CASES += [
+    ("rect_7x12", "rect", (7, 12, 1, 5, 2, 3, 6, 2), list(range(6)), 3, 0.05),
+    ("rect_12x7", "rect", (12, 7, 2, 3, 1, 5, 6, 2), list(range(6)), 3, 0.05),
+    ("pin_9x14_both", "pin", (9, 14) + ASYM + ("both", 2, 0.5), list(range(6)), 3, 0.05),
+    ("pin_14x9_beam", "pin", (14, 9) + ASYM_T + ("beam", 2, 0.5), list(range(6)), 3, 0.05),
+    ("spatial_9x14_both", "spatial", (9, 14) + ASYM + ("both", 2, 0.5), list(range(6)), 3, 0.05),
+    ("spatial_14x9_cent", "spatial", (14, 9) + ASYM_T + ("centroid", 2, 0.5), list(range(6)), 3, 0.05),
+    ("pin_40x72_cent", "pin", (40, 72, 5, 5, 2, 8, 2, 4, 12, 8, 4, 6, 6, 3, "centroid", 2, 0.5), [0, 1], 2, 0.02),
+    ("spatial_72x40_both", "spatial", (72, 40, 5, 5, 2, 4, 2, 8, 12, 8, 4, 6, 6, 3, "both", 3, 0.25), [0, 1], 2, 0.02),
+]
+ASYMMETRIC = tuple(c[0] for c in CASES[-8:])
 
 
 def tables(env, kind):
@@ -91,6 +108,21 @@ def tables(env, kind):
         flat = [p for n in range(len(env.net_pins)) for p in env.net_pins[n]]
         assert all(a is b for a, b in zip(flat, pins)) and len(flat) == len(pins)
     return out
+
+
+def write_npz(path, data):
+    """An .npz with fixed member dates: recording the same data again gives the same bytes."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as zf:
+        for key, arr in data.items():
+            buf = io.BytesIO()
+            arr = np.asarray(arr)
+            np.lib.format.write_array(buf, arr if arr.ndim == 0 else np.ascontiguousarray(arr), allow_pickle=False)
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            zf.writestr(info, buf.getvalue())
+    return os.path.getsize(path)
 
 
 def record_case(name, kind, args, seeds, episodes, p_random):
@@ -142,9 +174,7 @@ def record_case(name, kind, args, seeds, episodes, p_random):
                     data[pre + "obs_" + k + "_bits"] = np.packbits(stack.astype(np.uint8).ravel())
                 else:
                     data[pre + "obs_" + k] = stack
-    path = os.path.join(HERE, name + ".npz")
-    np.savez_compressed(path, **data)
-    return os.path.getsize(path)
+    return write_npz(os.path.join(HERE, name + ".npz"), data)
 
 
 def record_norm2():
@@ -202,8 +232,6 @@ def record_generator_tables():
     seeds [S], fail_at [S] (-1: none), fail_exc [S], ncomp / nnets / npins [S, RESETS] (-1: no record), comp_hw = (h, w)
     of all components and pins = (rel_x, rel_y, net, component, pin_id) of all pins, record after record.  The archive
     is written with fixed member dates, so regenerating it gives the same bytes."""
-    import io
-    import zipfile
     sys.path[:0] = [os.path.dirname(HERE), os.path.join(REPO, "rl-environment-for-component-placement_amd")]
     import generator_cases as gc
     big = [n for n, (_k, _a, g) in gc.CASES.items() if g == 64]
@@ -240,15 +268,7 @@ def record_generator_tables():
                      name + "/ncomp": counts[0], name + "/nnets": counts[1], name + "/npins": counts[2],
                      name + "/comp_hw": np.concatenate(comp_rows).astype(np.uint8),
                      name + "/pins": (np.concatenate(pin_rows) if pin_rows else np.zeros((0, 5))).astype(np.int16)})
-    path = os.path.join(HERE, "generator_tables.npz")
-    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as zf:
-        for key, arr in data.items():
-            buf = io.BytesIO()
-            np.lib.format.write_array(buf, np.ascontiguousarray(arr), allow_pickle=False)
-            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
-            info.compress_type = zipfile.ZIP_DEFLATED
-            zf.writestr(info, buf.getvalue())
-    return os.path.getsize(path)
+    return write_npz(os.path.join(HERE, "generator_tables.npz"), data)
 
 
 def _describe_space(sp):
@@ -370,6 +390,14 @@ if __name__ == "__main__":
         raise SystemExit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "generator_tables":  # only the generator's configuration space
         print(f"generator_tables {record_generator_tables() / 1024:.1f} KiB")
+        raise SystemExit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "spaces":  # only the declared spaces of every case (existing entries do not change)
+        record_spaces()
+        raise SystemExit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "cases":  # only the named episode cases: `make_golden.py cases NAME ...`
+        by_name = {c[0]: c for c in CASES}
+        for n in sys.argv[2:]:
+            print(f"{n:28s} {record_case(*by_name[n]) / 1024:8.1f} KiB")
         raise SystemExit(0)
     total = 0
     for case in CASES:

@@ -10,6 +10,9 @@ from pcbenv import EnvConfig, Instance
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 BINARY_KEYS = ("grid", "action_mask", "pin_grid", "component_grid")
+# the cases at H != W with different w and h ranges (make_golden.ASYMMETRIC)
+ASYMMETRIC = ("rect_7x12", "rect_12x7", "pin_9x14_both", "pin_14x9_beam", "spatial_9x14_both", "spatial_14x9_cent",
+              "pin_40x72_cent", "spatial_72x40_both")
 MAKE = {"square": EnvConfig.square, "rect": EnvConfig.rect, "pin": EnvConfig.pin, "spatial": EnvConfig.spatial}
 
 

@@ -235,6 +235,19 @@ class Run:
             out.update(reward=e.reward.cpu().numpy(), done=e.done.cpu().numpy(), info=e.info_raw.cpu().numpy())
         return out
 
+    def host_rows(self):
+        """host_obs() in the form two handles of one definition share whatever their layouts: the feature tensors as
+        float64 (a compact layout expanded), reward / done / info, and the mask marginals where this handle binds them."""
+        e = self.env
+        out = self.host_obs(f64=True)
+        out.update({"marginal_" + k: v.cpu().numpy() for k, v in e.mask_marginals.items()})
+        out.update(reward=e.reward.cpu().numpy(), done=e.done.cpu().numpy(), info=e.info_raw.cpu().numpy())
+        return out
+
+    def same_layout(self, other):
+        a, b = self.env, other.env
+        return a.compact_features == b.compact_features and bool(a.mask_marginals) == bool(b.mask_marginals)
+
     def compare_oracle(self, tag):
         import torch
         obs = self.host_obs(f64=True)
@@ -248,18 +261,26 @@ class Run:
             assert torch.equal(m["orientation"], am.amax(dim=(2, 3))), tag
 
     def gather(self, idx, src=None, check_snapshot=True):
-        """gather_ on the device; the snapshot and oracle bookkeeping on the host.  Returns the rows taken."""
+        """gather_ on the device; the snapshot and oracle bookkeeping on the host.  Returns the rows taken.  Between
+        two handles whose tensors differ (compact against float64 features, marginals bound on one side only) the rows
+        are compared as host_rows() gives them, key by key where the source has the key; marginals the source does not
+        bind are checked against the mask by compare_oracle."""
         import torch
         src = src or self
         idx = np.asarray(idx, np.int64)
         take = (idx >= 0) & (idx < src.B)
-        before_src = src.host_obs()
-        before_own = before_src if src is self else self.host_obs()
+        rows = Run.host_obs if self.same_layout(src) else Run.host_rows
+        before_src = rows(src)
+        before_own = before_src if src is self else rows(self)
         self.env.gather_(torch.from_numpy(idx).to(self.env.device), source=None if src is self else src.env)
-        after = self.host_obs()
+        after = rows(self)
         if check_snapshot:
+            assert set(after) - set(before_src) <= {"marginal_orientation", "marginal_rows"}
             for k, v in after.items():
                 want = before_own[k].copy()
+                if k not in before_src:  # marginals of a source that binds none: the rows kept must stay, the taken ones follow the mask
+                    assert _bytes_equal(v[~take], want[~take]), ("snapshot", k, "a kept row changed")
+                    continue
                 want[take] = before_src[k][idx[take]]
                 assert _bytes_equal(v, want), ("snapshot", k, np.flatnonzero([not _bytes_equal(v[i], want[i]) for i in range(self.B)])[:5])
         self.model.gather(idx, None if src is self else src.model)

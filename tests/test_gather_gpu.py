@@ -7,11 +7,12 @@ import numpy as np
 import pytest
 import torch
 
-from pcbenv import _lib, env_seed, named_config
+from pcbenv import EnvConfig, _lib, env_seed, named_config
 from pcbenv.batched_env import BatchedPlacementEnv
 from pcbenv.config import KIND_PIN, KIND_SPATIAL, KIND_SQUARE
 
 from handle_model import Run, _bytes_equal  # the environment next to its host model (shared with the call-sequence tests)
+from logits_cases import RAGGED
 
 pytestmark = pytest.mark.gpu
 
@@ -154,6 +155,72 @@ def test_layouts(name, kw):
         if t % 4 == 1:  # (trajectory layout: into the selected slot, the one the step just wrote)
             run.gather(_perm_with_repeats(rng, B))
     run.close()
+
+
+def _spatial_max():
+    return EnvConfig.spatial(128, 128, 9, 9, 2, 8, 2, 8, 64, 40, 8, 16, 16, 4, "both", 4, 0.5)
+
+
+EDGE_CONFIGS = dict(RAGGED, spatial_max=_spatial_max)
+
+
+@pytest.mark.parametrize("name,kw", [
+    ("spatial_7x100", dict()), ("spatial_7x100", dict(threads_per_env=256)), ("pin_100x9", dict()), ("rect_33x65", dict()),
+    ("pin_40x48", dict(num_slots=3, compact_features=True)), ("spatial_max", dict(threads_per_env=64))],
+    ids=["spatial_7x100", "spatial_7x100-t256", "pin_100x9", "rect_33x65", "pin_40x48-slots3-compact", "spatial_max-t64"])
+def test_edge_shapes(name, kw):
+    """test_layouts at the ragged and maximal shapes: two mask words per row with padding bits behind W on one and on four
+    wavefronts, more rows than lanes, one valid bit in word 1, H != W with compact features, and 128 rows, 64 components
+    and up to 256 pins on 64 lanes."""
+    cfg = EDGE_CONFIGS[name]()
+    B = 4 if name == "spatial_max" else 16
+    rng = np.random.RandomState(3)
+    run = Run(cfg, B, auto_reset=True, **kw)
+    steps = cfg.max_num_components + 6 if name != "spatial_max" else 12
+    moved = 0
+    for t in range(steps):
+        run.step(t)
+        if t % 4 == 1:  # (trajectory layout: into the selected slot, the one the step just wrote)
+            idx = _perm_with_repeats(rng, B)
+            moved += int((run.gather(idx) & (idx != np.arange(B))).sum())
+    assert moved >= B  # (on the host alone: the indices are not all -1 or the identity)
+    run.close()
+
+
+@pytest.mark.parametrize("name,src_kw,dst_kw", [
+    ("c3", dict(threads_per_env=64), dict(threads_per_env=256)),
+    ("c3", dict(threads_per_env=256), dict(threads_per_env=64)),
+    ("c4", dict(), dict(num_slots=4, compact_features=True)),
+    ("c4", dict(num_slots=4, compact_features=True), dict()),
+    ("c3", dict(incremental_obs=True), dict(mask_marginals=True)),
+    ("spatial_7x100", dict(threads_per_env=64), dict(threads_per_env=256)),
+    ("c3", dict(auto_reset=False), dict(auto_reset=True, queue_depth=5))],
+    ids=["c3-t64-to-t256", "c3-t256-to-t64", "c4-inplace-to-slots4-compact", "c4-slots4-compact-to-inplace",
+         "c3-incremental-to-marginals", "spatial_7x100-t64-to-t256", "c3-manual-to-auto-reset-q5"])
+def test_cross_handle_rows_move(name, src_kw, dst_kw):
+    """What the header promises of two handles of one definition -- num_envs, queue_depth, flags and threads_per_env may
+    differ -- with rows that move: 16 source environments after 3 launches, 32 destination environments of another run
+    seed after 7, an index with repeats and some -1.  Every taken row equals the source's pre-gather snapshot (Run.gather:
+    compact features after expansion, marginals against the mask where only the destination binds them), then one more
+    episode of the destination against the oracle."""
+    cfg = named_config(name) if name in ("c3", "c4") else RAGGED[name]()
+    rng = np.random.RandomState(13)
+    src = Run(cfg, 16, run_seed=8, **dict(dict(auto_reset=True), **src_kw))
+    dst = Run(cfg, 32, run_seed=9, **dict(dict(auto_reset=True), **dst_kw))
+    for t in range(3):
+        src.step(t)
+    for t in range(7):
+        dst.step(t)
+    idx = _perm_with_repeats(rng, 32, 16)
+    assert ((idx >= 0).sum() >= 16) and (idx < 0).any() and len(set(idx[idx >= 0])) < (idx >= 0).sum()
+    take = dst.gather(idx, src=src)
+    assert take.sum() >= 16
+    for i in np.flatnonzero(take):  # the rows did move: the destination's episodes are the source's, three transitions old
+        assert len(dst.hist[i]) == len(src.hist[idx[i]]) and dst.inst[i] is src.inst[idx[i]]
+    for t in range(7, 7 + cfg.max_num_components + 1):
+        dst.step(t)
+    src.step(3)  # the source goes on as if nothing had happened
+    src.close(); dst.close()
 
 
 @pytest.mark.parametrize("name,B", [("c3", 512), ("c4", 256)])

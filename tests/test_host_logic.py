@@ -49,6 +49,18 @@ def test_instance_stream_reproduces_the_generator_fixture(name):
             assert len(recs) == gc.RESETS and exc == ""
 
 
+@pytest.mark.parametrize("name", gc.ASYM_CASES)
+def test_asymmetric_generator_cases_separate_the_axes(name):
+    """The fixture's heights and widths of a case with different h and w ranges: the two observed ranges differ and
+    reach both ends of the configured ones, so a generator that swapped the axes cannot reproduce the tables."""
+    cfg = gc.make_cfg(name)
+    assert (cfg.min_component_h, cfg.max_component_h) != (cfg.min_component_w, cfg.max_component_w) and cfg.height != cfg.width
+    comp = np.concatenate([c for _, recs, _, _ in gc.load_fixture(name) for c, _, _ in recs])
+    h, w = (int(comp[:, 0].min()), int(comp[:, 0].max())), (int(comp[:, 1].min()), int(comp[:, 1].max()))
+    assert h == (cfg.min_component_h, cfg.max_component_h) and w == (cfg.min_component_w, cfg.max_component_w), (name, h, w)
+    assert h != w
+
+
 def test_constructor_validation_mirrors_reference():
     # dummy_env_rectangular.py:239-251
     with pytest.raises(ValueError): EnvConfig.rect(6, 6, 2, 7, 2, 4, 4, 1)

@@ -4,7 +4,7 @@ reproduced bit for bit (observations, float64 reward, done, info)."""
 import numpy as np
 import pytest
 
-from golden_util import case_names, load_case, pad_component_grid
+from golden_util import ASYMMETRIC, case_names, load_case, pad_component_grid
 from oracle import oracle as orc
 
 
@@ -34,6 +34,53 @@ def test_oracle_reproduces_reference_episode(name):
                 assert info == {}, tag
             else:
                 assert info["wirelength"] == e.info[t, 0] and info["num_intersections"] == e.info[t, 1], tag
+
+
+@pytest.mark.parametrize("name", ASYMMETRIC)
+def test_asymmetric_cases_exercise_both_axes(name):
+    """What makes the H != W fixtures worth having, read off the fixture alone: both kinds of terminal info, a
+    rotated placement of a non-square component, a rejected action.  A rejected action ends the reference's episode, so the
+    accepted action of step t places component t; the grid must grow by exactly its area."""
+    meta, cfg, eps = load_case(name)
+    assert name in case_names() and cfg.height != cfg.width
+    assert (cfg.min_component_w, cfg.max_component_w) != (cfg.min_component_h, cfg.max_component_h)
+    cfg.check_device_limits()
+    routed = worst = rotated = rejected = 0
+    for e in eps:
+        h, w = np.asarray(e.instance.comp_h), np.asarray(e.instance.comp_w)
+        mask, grid = e.obs["action_mask"], e.obs["grid"]
+        for t, (o, x, y) in enumerate(e.actions[:-1]):  # (the last one is the extra step behind the episode's end)
+            ok = 0 <= o < mask.shape[1] and 0 <= x < cfg.height and 0 <= y < cfg.width and mask[t, o, x, y] == 1
+            if ok:
+                assert grid[t + 1].sum() - grid[t].sum() == h[t] * w[t], (name, e.seed, e.ep, t)
+                rotated += o % 2 == 1 and h[t] != w[t]
+            else:
+                assert e.done[t] and (grid[t + 1] == grid[t]).all(), (name, e.seed, e.ep, t)
+                rejected += 1
+            if e.done[t] and not np.isnan(e.info[t, 0]):
+                assert e.info[t, 0] <= cfg.max_wirelength
+                is_worst = e.info[t, 0] == cfg.max_wirelength and e.info[t, 1] == cfg.max_num_intersections
+                worst += is_worst
+                routed += e.info[t, 0] < cfg.max_wirelength
+                assert is_worst == (not ok), (name, e.seed, e.ep, t, e.info[t])
+    assert rotated >= 1 and rejected >= 1, (name, rotated, rejected)
+    if meta["kind"] in ("pin", "spatial"):
+        assert routed >= 1 and worst >= 1, (name, routed, worst)
+
+
+def test_asymmetric_sizes_leave_the_other_range():
+    """Over the H != W cases: components whose h lies outside the w range and components whose w lies outside the h
+    range -- an oracle or generator that drew a side from the other axis' range could not reproduce them."""
+    h_out = w_out = 0
+    for name in ASYMMETRIC:
+        _, cfg, eps = load_case(name)
+        for e in eps:
+            h, w = np.asarray(e.instance.comp_h), np.asarray(e.instance.comp_w)
+            assert cfg.min_component_h <= h.min() and h.max() <= cfg.max_component_h, name
+            assert cfg.min_component_w <= w.min() and w.max() <= cfg.max_component_w, name
+            h_out += int(((h < cfg.min_component_w) | (h > cfg.max_component_w)).sum())
+            w_out += int(((w < cfg.min_component_h) | (w > cfg.max_component_h)).sum())
+    assert h_out >= 1 and w_out >= 1, (h_out, w_out)
 
 
 def test_norm2_matches_numpy_blas_fixture():

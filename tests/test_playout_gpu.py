@@ -26,7 +26,7 @@ def cpu_roots(name, parity):
     """The CPU plan of a case and the oracle's playouts from it, computed once."""
     key = (name, parity)
     if key not in _ROOTS:
-        cfg = pc.CASES[name][0]()
+        cfg = pc.case(name)[0]()
         roots = pc.Roots(name, pc.max_steps(cfg) + parity)
         _ROOTS[key] = (roots, pc.oracle_playouts(roots, [i // pc.K for i in range(roots.P * pc.K)]))
     return _ROOTS[key]
@@ -136,6 +136,31 @@ def test_kinds_and_shapes(name, parity):
     run.close()
 
 
+@pytest.mark.parametrize("parity", [0, 1])
+@pytest.mark.parametrize("name", list(pc.EDGE_CASES))
+def test_edge_shapes(name, parity):
+    """Case 1 at the shapes where k_playout takes another path than at the named configurations (the table of
+    playout_cases.EDGE_CASES): two mask words per row on one and on four wavefronts, more rows and pins than lanes,
+    padding bits behind W, placements 64 or more bits wide and over both words, beam width 4, 1x1 components, a grid the
+    first placement fills.  The mix each case must contain is playout_cases.edge_mix, computed before any device call.
+    rect_4x4_full cannot have a root between fresh and finished (its first placement ends the episode), so there the
+    mix asks for none instead."""
+    roots, expected = cpu_roots(name, parity)
+    cfg, P, K = roots.cfg, roots.P, pc.K
+    mix, missing = pc.edge_mix(name, roots, expected)
+    print(f"EDGE-MIX {name} parity {parity} seed {roots.seed}: {mix}")
+    assert not missing, (missing, mix)
+    run = device_roots(roots)
+    limit = pc.max_steps(cfg)
+    po = run.env.playout(k=K, step_index=pc.STEP0)
+    assert po.actions.shape == (limit, P * K, 3)
+    check_against(po, expected, cfg)                                                     # (b) the CPU oracle
+    want = planner_playouts(run.env, cfg, P * K, child_index(P, K, run.env.device), roots.seed, roots.kw, limit)
+    check_same_as_planner(po, want, cfg)                                                 # (a) the existing device path
+    run.compare_oracle("the roots after the playouts")
+    run.close()
+
+
 def _tensors(e):
     d = {"traj/" + k: v.cpu().numpy() for k, v in e.traj.items()}
     d.update(reward=e.traj_reward.cpu().numpy(), done=e.traj_done.cpu().numpy(), info=e.traj_info.cpu().numpy(),
@@ -189,11 +214,13 @@ def _forced_cases(roots):
     return first, kinds
 
 
-@pytest.mark.parametrize("flat", [False, True], ids=["tuple", "flat"])
-def test_forced_first_actions(flat):
+@pytest.mark.parametrize("name,flat", [("c3_centroid", False), ("c3_centroid", True), ("spatial_7x100", True)],
+                         ids=["tuple", "flat", "spatial_7x100-flat"])
+def test_forced_first_actions(name, flat):
     """Case 3: legal, illegal and out-of-range first actions in both formats; a bad one is a terminal transition with the
-    worst-case reward, as pcbenv_step makes it (the oracle's step_raw)."""
-    roots, _ = cpu_roots("c3_centroid", 0)
+    worst-case reward, as pcbenv_step makes it (the oracle's step_raw).  spatial_7x100: the flat decode by H * W = 700
+    and W = 100, no power of two."""
+    roots, _ = cpu_roots(name, 0)
     cfg, P = roots.cfg, roots.P
     first, kinds = _forced_cases(roots)
     H, W, A = cfg.height, cfg.width, cfg.num_orientations * cfg.height * cfg.width
@@ -271,12 +298,13 @@ def test_root_index_with_repeats_and_errors():
     run.close()
 
 
-@pytest.mark.parametrize("name", ["small_pin", "c3_centroid"])
+@pytest.mark.parametrize("name", ["small_pin", "c3_centroid", "spatial_7x100"])
 def test_truncation(name):
     """Case 5: max_steps = 2, actions_steps = 1: cut playouts report done = 0 and length = 2; action rows beyond
     actions_steps are not written.  Next to the cut playouts there are ones that end at their first transition and, in
     small_pin, ones that end exactly at max_steps (every c3 instance has 16 components and no root of the plan is two
-    transitions from its end, so there the cut ones stand next to length 1 only)."""
+    transitions from its end, so there the cut ones stand next to length 1 only).  spatial_7x100: two mask words per row
+    with padding bits behind column 100."""
     roots, _ = cpu_roots(name, 1)
     cfg, P, K = roots.cfg, roots.P, 2
     root_of = [i // K for i in range(P * K)]
