@@ -593,22 +593,45 @@ class Driver:
         assert np.array_equal(a, want), (tag, "the fused launch took another action than sample_actions draws")
         self.stepped(a, tag)
 
-    def op_rollout(self, n, seed, tag):
-        e, m = self.env, self.model
-        acts = e.rollout_steps(self.t, n).cpu().numpy()
+    def op_rollout(self, n, seed, tag, flat=False, draw_seed=None, first_env_index=None, t0=None, expect=None):
+        """One rollout_steps(n).  flat / draw_seed / first_env_index / t0: the launch through the ABI itself, with the
+        flat action format, another seed than the run seed, another first_env_index than the handle's, another
+        step_index0 than the transitions so far.  expect(k) -> the [B, 3] actions step k must have recorded, asked when
+        the model has taken the steps before k.  Returns the recorded actions as the device wrote them."""
+        import torch
+        e, m, cfg = self.env, self.model, self.cfg
+        if t0 is not None:
+            self.t = int(t0)
+        if flat or draw_seed is not None or first_env_index is not None:
+            from pcbenv import _lib
+            rec = torch.full((n, self.B) if flat else (n, self.B, 3), -7, dtype=torch.int32, device=e.device)
+            _lib.check(e._L.pcbenv_rollout_sampled(
+                e._h, rec.data_ptr(), _lib.ACTION_FLAT if flat else _lib.ACTION_TUPLE, int(n),
+                e.run_seed if draw_seed is None else int(draw_seed),
+                e.first_env_index if first_env_index is None else int(first_env_index), self.t, e._stream()), e._h)
+            rec = rec.cpu().numpy()
+            assert (rec >= 0).all(), (tag, "an action the launch did not record (or a negative one)", np.argwhere(rec < 0)[:5].tolist())
+            HW = cfg.height * cfg.width
+            acts = np.stack([rec // HW, rec % HW // cfg.width, rec % cfg.width], axis=-1).astype(np.int32) if flat else rec
+        else:
+            rec = acts = e.rollout_steps(self.t, n).cpu().numpy()
         traj = self.host_traj()
         rdi = (e.traj_reward.cpu().numpy(), e.traj_done.cpu().numpy(), e.traj_info.cpu().numpy())
         for k in range(n):
             s = (m.slot + k) % m.S
-            expect = m.step(acts[k], slot=s, set_last_done=False)
+            if expect is not None:
+                want = expect(k)
+                assert np.array_equal(acts[k], want), (tag, "step", k, "recorded actions", np.flatnonzero((acts[k] != want).any(axis=1))[:5].tolist())
+            oracle = m.step(acts[k], slot=s, set_last_done=False)
             if k + m.S >= n:  # (an earlier step's slot has been overwritten by a later one)
-                self.check_step(traj, s, expect, (tag, "step", k), rdi)
+                self.check_step(traj, s, oracle, (tag, "step", k), rdi)
                 self.shown[s] = {key: v[s].copy() for key, v in traj.items()}
         self.last_actions = acts[n - 1]
         self.t += n
         e.select_slot(m.slot + n - 1)  # the slot the last transition wrote
         m.select(m.slot + n - 1)
         self.compare(tag, traj)
+        return rec
 
     def op_reset_mask(self, p, seed, tag):
         import torch
