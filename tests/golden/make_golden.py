@@ -25,7 +25,8 @@ with all pin coordinates after whole episodes), `episode_export.npz` (the refere
 episode, before and after placement), `norm2.npz` (np.linalg.norm of length-2 vectors in this container's
 NumPy/OpenBLAS -- SURVEY.md trap T1) and `setorder.npz` (CPython iteration order of
 `set(points) - visited` -- trap T2) and `generator_tables.npz` (the instance tables of eight resets per stream for the
-configurations of tests/generator_cases.py, with the reset and exception class where the reference raised).  The files
+configurations of tests/generator_cases.py, with the reset and exception class where the reference raised) and
+`routing_layouts.npz` (find_reward and beam_search on the hand-built pin layouts of tests/routing_layouts.py).  The files
 are data only; no reference source text is stored.
 """
 import json
@@ -271,6 +272,70 @@ def record_generator_tables():
     return write_npz(os.path.join(HERE, "generator_tables.npz"), data)
 
 
+def record_routing_layouts():
+    """The routing reward on the hand-built pin layouts of tests/routing_layouts.py, from the reference's own find_reward and
+    beam_search driven the way its tests/pin_environment/test_env.py:199-379 drives them: pins with hand-set absolute
+    coordinates in `env.net_pins`, a sentinel current component, then `find_reward()`.  `tests/golden/routing_layouts.npz`:
+    the table itself (net_sizes per layout, cells of all pins), rows = (layout, kind, reward type, beam width, grid side) with
+    values = (reward, reward_wirelength, reward_intersection) as float64 bits, and per (layout, beam width 1..4) the path
+    beam_search returns for every net from its pin_outlier, as pin indices.  Data only; fixed member dates."""
+    from collections import defaultdict
+    sys.path[:0] = [os.path.dirname(HERE), os.path.join(REPO, "rl-environment-for-component-placement_amd")]
+    import routing_layouts as rl
+    import environment.dummy_env_rectangular_pin as mod_pin
+    import environment.dummy_env_rectangular_pin_spatial as mod_spatial
+    mods = {"pin": mod_pin, "spatial": mod_spatial}
+    lays = rl.layouts()
+    names = list(lays)
+    data = {"names": np.array(names), "num_nets": np.array([len(lays[n]) for n in names], np.int16),
+            "net_sizes": np.array([len(net) for n in names for net in lays[n]], np.int16),
+            "cells": np.array([c for n in names for net in lays[n] for c in net], np.int16)}
+
+    def load(env, mod, lay):
+        env.net_pins = defaultdict(list)
+        for n, net in enumerate(lay):
+            for i, (x, y) in enumerate(net):
+                pin = mod.Pin(relative_x=0, relative_y=0, pin_id=i, component_id=0, net_id=n)
+                pin.absolute_x, pin.absolute_y = int(x), int(y)
+                env.net_pins[n].append(pin)
+        env.current_component = mod.Component(-1, -1, -1, [])
+
+    rows, values = [], []
+    for ki, kind in enumerate(rl.KINDS):
+        settings = [(rt, k, rl.H) for rt in ("beam", "both") for k in rl.BEAM_WIDTHS[kind]] + [("centroid", 2, rl.H)]
+        if kind == "pin":
+            settings.append(("centroid", 2, 64))  # the grid the fixed-geometry build of the step kernel is compiled for
+        for rt, k, side in settings:
+            np.random.seed(0)
+            random.seed(0)
+            env = REF[kind](*rl.ctor_args(rt, k, side))
+            for li, name in enumerate(names):
+                load(env, mods[kind], lays[name])
+                reward = env.find_reward()
+                rows.append((li, ki, ("beam", "centroid", "both").index(rt), k, side))
+                values.append((reward, env.reward_wirelength, env.reward_intersection))
+    data["rows"] = np.array(rows, np.int16)
+    data["values"] = np.array(values, np.float64).view(np.uint64)
+    paths = {}
+    for kind in rl.KINDS:
+        np.random.seed(0)
+        random.seed(0)
+        env = REF[kind](*rl.ctor_args("beam", 2))
+        for li, name in enumerate(names):
+            for k in rl.BEAM_WIDTHS[kind]:
+                got = []
+                for net in lays[name]:
+                    pos = [(int(x), int(y)) for x, y in net]
+                    start = env.pin_outlier(pos)
+                    rest = list(pos)
+                    rest.remove(start)
+                    got += [pos.index(p) for p in env.beam_search(start, rest, k)]
+                assert paths.setdefault((li, k), got) == got, (name, k, "the two reference kinds route differently")
+    for k in (1, 2, 3, 4):  # per beam width: the paths of all nets of all layouts, in table order (net_sizes gives the split)
+        data[f"paths_k{k}"] = np.array([i for li in range(len(names)) for i in paths[(li, k)]], np.uint8)
+    return write_npz(os.path.join(HERE, "routing_layouts.npz"), data)
+
+
 def _describe_space(sp):
     """JSON summary of one of the reference's space objects (the stand-in gym classes keep the ctor arguments)."""
     from gym import spaces as gs
@@ -391,6 +456,9 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "generator_tables":  # only the generator's configuration space
         print(f"generator_tables {record_generator_tables() / 1024:.1f} KiB")
         raise SystemExit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "routing_layouts":  # only the routing reward on the hand-built layouts
+        print(f"routing_layouts {record_routing_layouts() / 1024:.1f} KiB")
+        raise SystemExit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "spaces":  # only the declared spaces of every case (existing entries do not change)
         record_spaces()
         raise SystemExit(0)
@@ -411,4 +479,5 @@ if __name__ == "__main__":
     record_episode_export()
     record_model_config()
     record_generator_tables()
+    record_routing_layouts()
     print(f"total {total / 1024:.1f} KiB")

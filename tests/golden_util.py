@@ -18,7 +18,7 @@ MAKE = {"square": EnvConfig.square, "rect": EnvConfig.rect, "pin": EnvConfig.pin
 
 def case_names():
     names = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN_DIR, "*.npz")))
-    return [n for n in names if n not in ("norm2", "setorder", "adapter_views", "episode_export", "generator_tables")]
+    return [n for n in names if n not in ("norm2", "setorder", "adapter_views", "episode_export", "generator_tables", "routing_layouts")]
 
 
 def load_case(name):
