@@ -30,12 +30,14 @@ COMPACT_DTYPES = {"all_components_feature": torch.int16, "placement_mask": torch
 def expand_compact_features(cfg: EnvConfig, compact: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     """Compact feature tensors (pcbenv_compact_features: int16 / int8 / uint8) -> the reference's float64 tensors, bit
     for bit: every element is a small integer except all_components_feature[..., 4], carried as h * w and divided by
-    H * W here in float64 -- the one IEEE division the reference does (`area / grid_area`, S:203-239)."""
+    H * W here in float64 -- the one IEEE division the reference does (`area / grid_area`, S:203-239).  The divisor is a
+    tensor on the features' device: by a Python number torch divides on a GPU by multiplying with the reciprocal, which
+    is one bit off for many h * w unless H * W is a power of two (9 / 448 on a 14 x 32 grid)."""
     out = {}
     for k, t in compact.items():
         f = t.to(torch.float64)
         if k == "all_components_feature":
-            f[..., 4] = f[..., 4] / float(cfg.height * cfg.width)
+            f[..., 4] = f[..., 4] / torch.full((), float(cfg.height * cfg.width), dtype=torch.float64, device=f.device)
         out[k] = f
     return out
 
@@ -113,8 +115,11 @@ class BatchedPlacementEnv:
         compact_features (trajectory layout only): the feature tensors are kept as int16 / int8 / uint8
         (`pcbenv_bind_compact_features`: 8x fewer feature bytes per step) under the same keys of `traj` / `obs`;
         `obs_f64()` / `expand_compact_features` give the reference's float64 tensors, bit for bit.
-        allocator: `f(name, shape, dtype) -> zero-filled device tensor` for the observation tensors (default torch.zeros);
-        lets a caller place them (tools/c5_modes.py studies where the big cell tensors should sit)."""
+        allocator: `f(name, shape, dtype) -> device tensor` for the observation tensors (default torch.zeros); lets a
+        caller place them (tools/c5_modes.py studies where the big cell tensors should sit).  The tensors may hold
+        anything and need only the alignment of their element type: the first unmasked reset writes every byte of the
+        selected slot (tests/test_emission_gpu.py binds sentinel-filled, misplaced views); slots no call has written
+        keep what the allocator left in them."""
         cfg.validate()
         self.cfg, self.num_envs, self.queue_depth = cfg, int(num_envs), int(queue_depth)
         self.run_seed, self.first_env_index = int(run_seed), int(first_env_index)

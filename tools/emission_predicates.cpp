@@ -1,0 +1,23 @@
+// emission_predicates.cpp -- the predicates of csrc/pcb_layout.h that tests/emission_cases.py restates in Python, evaluated
+// by the header itself (the only one included) for shapes read from standard input, one per line:
+//   kind H W O WW threads num_slots num_steps routes cells_aligned16 enabled C mp
+// and printed one line each: fixed_geometry_applies fold_across_lanes member_words.
+// Build and run (tests/test_emission_cases.py does that):
+//   g++ -std=c++17 -fsanitize=address,undefined -Iinclude -Irl-environment-for-component-placement_amd/csrc
+//       -o emission_predicates tools/emission_predicates.cpp && ./emission_predicates < shapes.txt
+#include "pcb_layout.h"
+
+#include <stdio.h>
+
+using namespace pcb_layout;
+
+int main() {
+    int kind, H, W, O, WW, threads, slots, steps, routes, aligned, enabled, C, mp, n = 0;
+    while (scanf("%d %d %d %d %d %d %d %d %d %d %d %d %d", &kind, &H, &W, &O, &WW, &threads, &slots, &steps, &routes, &aligned, &enabled, &C, &mp) == 13) {
+        const StepShape s{kind, H, W, O, WW, threads, slots, steps, routes != 0, aligned != 0, enabled != 0};
+        printf("%d %d %d\n", fixed_geometry_applies(s) ? 1 : 0, fold_across_lanes(WW, threads, H) ? 1 : 0, member_words(kind, C, mp));
+        n++;
+    }
+    fprintf(stderr, "emission_predicates ok: %d shapes\n", n);
+    return feof(stdin) ? 0 : 1;
+}
