@@ -1,7 +1,24 @@
 /*
  * pcbenv.h -- C ABI of libpcbenv.so: batched PCB component-placement
  * environments on MI355X (gfx950).  Plain C, plain pointers and sizes, no torch
- * or C++ types.  Everything is asynchronous on the caller's HIP stream.
+ * or C++ types.  The compute calls are asynchronous on the caller's HIP stream.
+ *
+ * Streams.  Every entry point with a `stream` parameter works on that stream and on no other (tests/stream_cases.py is
+ * this paragraph as a table).  These only enqueue -- kernels, device-to-device copies and, with the on-device generator,
+ * event waits -- and return without waiting for the stream, with no allocation, host copy or synchronisation:
+ * pcbenv_reset, pcbenv_step, pcbenv_sample_actions, pcbenv_step_sampled, pcbenv_rollout_sampled, pcbenv_gather,
+ * pcbenv_playout, pcbenv_sample_logits, pcbenv_evaluate_logits[_backward], pcbenv_sample_axis and
+ * pcbenv_evaluate_axis[_backward].  These move data between the host and the device and return only when `stream` (and,
+ * where the on-device generator is on, its own stream) has done everything enqueued before and by the call:
+ * pcbenv_load_instances, pcbenv_get_instances, pcbenv_get_state, pcbenv_set_state, pcbenv_queue_cursors,
+ * pcbenv_instgen_device_enable and pcbenv_instgen_device_status.  pcbenv_set_option(PCBENV_OPT_TERMINAL_TEAMS) and
+ * pcbenv_bind_buffers[_slots] take no stream and synchronise the whole device, before and after what they change on it;
+ * the other options, pcbenv_bind_compact_features and pcbenv_select_slot change host-side fields only, which the next
+ * call reads.  A handle may be used from different streams as long as the caller orders the calls (an event recorded
+ * behind one call and waited for by the stream of the next) and never makes two calls on one handle at the same time.
+ * Two handles share nothing on the device: they may run concurrently on two streams (pcbenv_gather between two handles
+ * reads the source, whose last launch the caller orders before it).  pcbenv_last_error(env) is per handle;
+ * pcbenv_last_error(NULL) is the message of the latest failure in the process.
  *
  * What each entry point replaces in the reference (PBozmarov/RL-Environment-for-
  * Component-Placement, paths relative to its root):
@@ -297,7 +314,8 @@ int pcbenv_instgen_next_batch(pcbenv_instgen *const *streams, int32_t n, void *r
  * a draw the reference itself fails on / this library does not support (bit 1).  Such a stream has stopped: the records
  * before the failing one are queued and valid, none follows, and once they are consumed its environment must not be
  * reset again (the other environments' streams carry on unaffected).  pcbenv_get_instances copies one queue slot
- * (num_envs packed records) to the host, e.g. to replay an episode on the CPU. */
+ * (num_envs packed records) to the host, e.g. to replay an episode on the CPU.  All three synchronise with `stream`:
+ * pcbenv_instgen_device_enable returns with the whole queue filled, pcbenv_get_instances with the records on the host. */
 int pcbenv_instgen_device_enable(pcbenv *env, const uint32_t *seeds_host, void *stream);
 int pcbenv_instgen_device_status(pcbenv *env, uint32_t *errors_out, void *stream);
 int pcbenv_get_instances(pcbenv *env, int32_t slot, void *host_dst, void *stream);

@@ -127,6 +127,7 @@ static int gen_acquire(pcbenv *env, const uint32_t *seeds_host, hipStream_t s, u
     HIP_TRY(env, hipGetLastError());
     HIP_TRY(env, hipStreamSynchronize(s));
     HIP_TRY(env, hipMemsetAsync(env->gen_produced + B, 0, 4, s));
+    HIP_TRY(env, hipStreamSynchronize(s));  // enable is synchronous w.r.t. `stream`: the next call may come on another one
     return PCBENV_OK;
 }
 extern "C" int pcbenv_instgen_device_enable(pcbenv *env, const uint32_t *seeds_host, void *stream) {

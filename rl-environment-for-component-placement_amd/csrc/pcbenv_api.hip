@@ -114,10 +114,13 @@ extern "C" int pcbenv_set_option(pcbenv *env, int32_t option, int64_t value) {
             return fail(env, PCBENV_EINVAL, "reward helpers need an environment kind with a routing reward");
         value = (value + TERM_SHARDS - 1) & ~(long long)(TERM_SHARDS - 1);
         {   // The lists built so far were laid out for the old capacity: drop them (counters to zero once everything enqueued
-            // has run; no mark matches the next launch's number).  A rare call: it may synchronise.
+            // has run; no mark matches the next launch's number).  A rare call: it synchronises the device, before the
+            // fill and after it -- the fill goes to the null stream, which a non-blocking caller stream is not ordered with,
+            // and the next launch on any stream must find the counters clear.
             DEVICE_GUARD(env);
             HIP_TRY(env, hipDeviceSynchronize());
             HIP_TRY(env, hipMemset(env->dp.term_cnt, 0, TERM_CNT_BYTES));
+            HIP_TRY(env, hipDeviceSynchronize());
             *env->term_seen_host = 0u;
         }
         env->term_wgs = (int)value;
@@ -176,7 +179,14 @@ extern "C" int pcbenv_bind_buffers_slots(pcbenv *env, const pcbenv_buffers *b, i
         env->gather_snap = 0;
         return fail(env, PCBENV_EHIP, "hipMalloc failed");
     }
-    if (d.feat_cache_tag) hipMemset(d.feat_cache_tag, 0xFF, 4 * (size_t)d.B);  // no episode has that number: nothing cached yet
+    // Binding takes no stream: it synchronises the device, so that every launch enqueued so far (on any stream) has written
+    // the old tensors and read the old tags before anything changes, and once more behind the tag fill (which goes to the
+    // null stream), so that the next launch on any stream finds it done.  A rare call.
+    HIP_TRY(env, hipDeviceSynchronize());
+    if (d.feat_cache_tag) {  // no episode has that number: nothing cached yet
+        HIP_TRY(env, hipMemset(d.feat_cache_tag, 0xFF, 4 * (size_t)d.B));
+        HIP_TRY(env, hipDeviceSynchronize());
+    }
     d.num_slots = num_slots; d.slot = 0;
     d.buf = *b;
     if (k != PCBENV_SPATIAL) { d.buf.pin_grid = 0; d.buf.component_grid = 0; }

@@ -738,9 +738,10 @@ class Driver:
         getattr(self, "op_" + name)(arg, seed, (i, name, arg))
 
 
-def run_sequence(setup, seed, counts=None):
+def run_sequence(setup, seed, counts=None, before_op=None):
     """Sequence `seed` of `setup` on the device.  A failure names the setup, the seed and the ops executed so far:
-    `run_sequence(SETUPS[name], seed)` reproduces it."""
+    `run_sequence(SETUPS[name], seed)` reproduces it.  before_op(i, op), if given, is called before every op (the stream
+    tests put a delay on the current stream there); the comparisons are the same either way."""
     if isinstance(setup, str):
         setup = SETUPS[setup]
     ops = schedule(setup, seed)
@@ -750,6 +751,8 @@ def run_sequence(setup, seed, counts=None):
     try:
         for i, op in enumerate(ops):
             done.append(op[:2])
+            if before_op is not None:
+                before_op(i, op)
             drv.run_op(i, op)
     except AssertionError as err:
         raise AssertionError(f"setup={setup.name} seed={seed} failed at op {len(done) - 1} {done[-1]}: {err.args[0] if err.args else ''}"
