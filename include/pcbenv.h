@@ -14,7 +14,8 @@
  * pcbenv_instgen_device_enable and pcbenv_instgen_device_status.  pcbenv_set_option(PCBENV_OPT_TERMINAL_TEAMS) and
  * pcbenv_bind_buffers[_slots] take no stream and synchronise the whole device, before and after what they change on it;
  * the other options, pcbenv_bind_compact_features and pcbenv_select_slot change host-side fields only, which the next
- * call reads.  A handle may be used from different streams as long as the caller orders the calls (an event recorded
+ * call reads.  pcbenv_playout_paths takes its stream as a field of its request and only enqueues on it, exactly as
+ * pcbenv_playout does.  A handle may be used from different streams as long as the caller orders the calls (an event recorded
  * behind one call and waited for by the stream of the next) and never makes two calls on one handle at the same time.
  * Two handles share nothing on the device: they may run concurrently on two streams (pcbenv_gather between two handles
  * reads the source, whose last launch the caller orders before it).  pcbenv_last_error(env) is per handle;
@@ -59,6 +60,9 @@
  *                          caller uses to fork an episode (lookahead, beam search, population resampling)
  *   pcbenv_playout         copy.deepcopy(env) of a reference env object followed by the random policy's simulate() loop
  *                          on the copy, played per fork
+ *                            agent/random/random_policy_square.py:25-58 (and siblings)
+ *   pcbenv_playout_paths   copy.deepcopy(env), env.step(a) for every action of the path, then the random policy's
+ *                          simulate() loop on the copy: the evaluation of a tree node named by its path from the root
  *                            agent/random/random_policy_square.py:25-58 (and siblings)
  *
  * Observations are written into caller-owned device buffers (pcbenv_buffers)
@@ -395,6 +399,66 @@ int pcbenv_playout(const pcbenv *env, const int32_t *root_index_dev, int64_t num
                    double *reward_dev, uint8_t *done_dev, int32_t *length_dev, double *info_dev,
                    int32_t *actions_out_dev, int32_t actions_steps, uint32_t *errors_dev,
                    uint64_t seed, uint64_t first_env_index, uint64_t step_index0, void *stream);
+
+/* Playouts from tree nodes named by a path: pcbenv_playout with a sequence of forced actions per playout, and the legal
+ * mask of the node the sequence leads to.  What a search deeper than one ply (MCTS / UCT, beam search over placements,
+ * CEM over action sequences, re-scoring a stored episode prefix) needs to evaluate a node without materialising it: one
+ * kernel launch on req->stream, no planner handle, no launch per ply, no observation.  The arguments travel in a struct.
+ * The identity.  pcbenv_playout's, with one change: transition t < path_len[i] of playout i applies path_actions[t, i]
+ * instead of a draw; transition t >= path_len[i] draws with the key (seed, first_env_index + i, step_index0 + t) -- what
+ * pcbenv_step_sampled(seed, first_env_index, step_index0 + t) would draw for environment i of a handle of num_playouts
+ * environments after pcbenv_gather and the path's steps had brought root r's episode there -- and every transition is
+ * that handle's, bit for bit.  The draw key depends on t, not on the path.  Hence path_steps == 1 equals pcbenv_playout
+ * with first_actions_dev, and a path equal to the first d actions of the path-less playout with the same keys gives that
+ * playout's outputs bit for bit, for every d.
+ * A bad path action is data: an illegal or out-of-range path action is a terminal transition with the worst-case
+ * reward, as in pcbenv_step.  The playout ends there: the path rows after it are not read for effect and nothing after
+ * it is drawn.
+ * struct_size: sizeof(pcbenv_playout_request) as the caller compiled it.  root_index_dev, num_playouts, reward_dev,
+ * done_dev, length_dev, info_dev, errors_dev, seed, first_env_index, step_index0: as pcbenv_playout.  max_steps counts
+ * all transitions, the path's included.
+ * path_actions_dev: int32 [path_steps, num_playouts, 3] or [path_steps, num_playouts] per action_format: step-major,
+ * the layout of actions_out_dev; may be NULL iff path_steps == 0.  path_len_dev: int32 [num_playouts], or NULL =
+ * path_steps for every playout.  Rows t >= path_len[i] of playout i are never read.
+ * actions_out_dev: rows t < min(length, actions_steps) are written -- a path action is recorded as given (flat: the
+ * value as given) -- and the others are untouched.
+ * leaf_mask_bits_dev (optional): uint64 [num_playouts, 2, H, ceil(W/64)], 8-byte aligned.  Row i receives the legal-mask
+ * bit rows, in the layout pcbenv_mask_bits documents, of the episode after transition min(path_len[i], length[i]) - 1:
+ * the node the path names, or the state in which the episode ended if it ended on the path (an invalid action leaves the
+ * state as it was).  With path_len[i] == 0 it is the root's own.  Every word of the row is written, once.  The bits of
+ * columns >= W and plane 1 of the square kind are copied from the state block as they are and are left unspecified (no
+ * entry point reads them).  Directly usable as mask_bits_dev of pcbenv_evaluate_logits / pcbenv_evaluate_axis.
+ * A path_len[i] outside [0, path_steps] is checked before it addresses anything: bit 1 (value 2) is ORed into
+ * *errors_dev (if not NULL) and the playout reports like a bad root -- length = 0, done = 0, reward = 0.0, NaN info.  A
+ * root_index outside [0, num_envs) still sets bit 0.  A row refused for either reason gets an all-zero leaf mask and no
+ * action row.
+ * Writes nothing the library owns and nothing bound, exactly as pcbenv_playout: a later call on the handle behaves as
+ * without it.  PCBENV_FLAG_AUTO_RESET is ignored, as are the trajectory layout, the selected slot, helper marks in the
+ * root's header and its presampled action.  Not capturable into a hipGraph.
+ * PCBENV_EINVAL (checked before any device call, in this order): null request; struct_size not
+ * sizeof(pcbenv_playout_request); null reward_dev; unknown format; max_steps < 1; path_steps outside [0, max_steps];
+ * path_steps > 0 with null path_actions_dev; actions_steps outside [0, max_steps], or > 0 with null actions_out_dev;
+ * leaf_mask_bits_dev not 8-byte aligned; num_playouts < 0; null root_index_dev with num_playouts not a multiple of
+ * num_envs; null handle.  num_playouts == 0 is a no-op success.  PCBENV_ESTATE: as pcbenv_playout (buffers not bound, no
+ * episode in the handle yet, or req->stream is being captured). */
+typedef struct pcbenv_playout_request {
+    uint32_t struct_size;             /* sizeof(pcbenv_playout_request) as the caller compiled it; any other value: PCBENV_EINVAL */
+    int32_t  action_format;           /* of path_actions_dev and actions_out_dev */
+    const int32_t *root_index_dev;    /* as pcbenv_playout */
+    int64_t  num_playouts;
+    const int32_t *path_actions_dev;  /* int32 [path_steps, num_playouts, 3] or [path_steps, num_playouts]: step-major, the
+                                         layout of actions_out_dev; may be NULL iff path_steps == 0 */
+    const int32_t *path_len_dev;      /* int32 [num_playouts], or NULL = path_steps for every playout */
+    int32_t  path_steps;              /* 0 ... max_steps */
+    int32_t  max_steps;               /* all transitions, the path's included */
+    double  *reward_dev; uint8_t *done_dev; int32_t *length_dev; double *info_dev;   /* as pcbenv_playout */
+    int32_t *actions_out_dev; int32_t actions_steps;                                 /* as pcbenv_playout */
+    uint64_t *leaf_mask_bits_dev;     /* optional: uint64 [num_playouts, 2, H, ceil(W/64)], 8-byte aligned */
+    uint32_t *errors_dev;
+    uint64_t seed, first_env_index, step_index0;
+    void    *stream;
+} pcbenv_playout_request;
+int pcbenv_playout_paths(const pcbenv *env, const pcbenv_playout_request *req);
 
 /* Masked categorical draw from a policy's logits, on the device, one kernel launch on `stream`.
  * logits_dev: C-contiguous [num_envs, A], A = O*H*W (square: H*W), in the flat action order of PCBENV_ACTION_FLAT

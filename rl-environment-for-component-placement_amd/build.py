@@ -3,7 +3,7 @@
 
 hipcc cross-compiles without a GPU.  -ffp-contract=off: one IEEE operation per written operator (the reward path
 must match the reference bit for bit).  The kernels of the four environment kinds are separate translation units
-(csrc/pcb_kind_*.hip) compiled in parallel, as are those of pcbenv_playout (csrc/pcb_playout_*.hip), then linked with the host side -- the C ABI
+(csrc/pcb_kind_*.hip) compiled in parallel, as are those of pcbenv_playout (csrc/pcb_playout_*.hip) and pcbenv_playout_paths (csrc/pcb_playout_paths_*.hip), then linked with the host side -- the C ABI
 (csrc/pcbenv_api.hip), the layout derivation (csrc/pcb_config.hip) and the on-device instance generator with its kernels
 (csrc/pcb_gen.hip), which share csrc/pcb_host.h -- the two kernels every kind uses (csrc/pcb_sample.hip) and the host
 instance generator (csrc/instance_gen.cpp).  csrc/pcb_layout.h is the layout contract both sides compile.
@@ -18,6 +18,7 @@ REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 UNITS = (["pcb_kind_square.hip", "pcb_kind_rect.hip"] + [f"pcb_kind_{k}_{p}.hip" for p in (2, 3, 0, 4, 1) for k in ("spatial", "pin")]  # slowest first
          + [f"pcb_playout_{k}_{p}.hip" for p in (2, 1, 0) for k in ("spatial", "pin")] + ["pcb_playout_rect.hip", "pcb_playout_square.hip"]
+         + [f"pcb_playout_paths_{k}_{p}.hip" for p in (2, 1, 0) for k in ("spatial", "pin")] + ["pcb_playout_paths_rect.hip", "pcb_playout_paths_square.hip"]
          + ["pcb_policy.hip", "pcb_policy_eval.hip", "pcb_policy_axis.hip", "pcb_gen.hip", "pcb_sample.hip", "pcbenv_api.hip", "pcb_config.hip", "instance_gen.cpp"])
 SRC = [os.path.join(CSRC, u) for u in UNITS]
 DEPS = SRC + [os.path.join(REPO, "include", "pcbenv.h")] + sorted(

@@ -36,7 +36,7 @@ struct GatherArgs {
 };
 struct GatherLaunch { DevParams d; GatherArgs g; int threads; hipStream_t stream; };
 
-// pcbenv_playout (pcb_playout_*.hip): d is the root handle's parameter block with d.state = the current state set,
+// pcbenv_playout and pcbenv_playout_paths (pcb_playout_*.hip, pcb_playout_paths_*.hip): d is the root handle's parameter block with d.state = the current state set,
 // buf.reward / buf.info repointed at the playout's rows and everything else a playout must not touch taken out (every
 // other tensor null, flags 0, no terminal list); the rest travels in PlayoutArgs.
 struct PlayoutArgs {
@@ -50,6 +50,11 @@ struct PlayoutArgs {
     unsigned *errors;          // may be null
     int n, per_root, fmt, max_steps, actions_steps;
     u64 seed, first_env, step_index0;
+    // pcbenv_playout_paths only (k_playout<..., PATHS = true>; pcbenv_playout leaves them null / 0)
+    const int *path_actions;   // [path_steps, n, 3] / [path_steps, n], null if path_steps == 0
+    const int *path_len;       // [n] or null: path_steps for every playout
+    u64 *leaf_mask;            // [n, 2, H, WW], may be null
+    int path_steps;
 };
 struct PlayoutLaunch { DevParams d; PlayoutArgs g; int threads; bool routes; hipStream_t stream; };
 
@@ -127,5 +132,6 @@ int pcb_launch_evaluate_axis(const EvalAxisLaunch &a);
 int pcb_launch_evaluate_axis_backward(const EvalAxisBackwardLaunch &a);
 
 #define PCB_DECLARE_KIND(name) int pcb_launch_step_##name(const StepLaunch &a); int pcb_launch_reset_##name(const ResetLaunch &a); \
-    int pcb_launch_gather_##name(const GatherLaunch &a); int pcb_launch_playout_##name(const PlayoutLaunch &a);
+    int pcb_launch_gather_##name(const GatherLaunch &a); int pcb_launch_playout_##name(const PlayoutLaunch &a); \
+    int pcb_launch_playout_paths_##name(const PlayoutLaunch &a);
 PCB_DECLARE_KIND(square) PCB_DECLARE_KIND(rect) PCB_DECLARE_KIND(pin) PCB_DECLARE_KIND(spatial)

@@ -17,12 +17,19 @@
 // is shared is everything with a result in it: window_mask through mask_and_emit(emit = false), sample_action and
 // terminal_reward -- the latter through the parameter block, whose buf.reward / buf.info the host points at the
 // playout's rows (every other tensor null, flags and the terminal list zeroed: pcbenv_playout).
+//
+// PATHS = true is the kernel of pcbenv_playout_paths (instantiated in pcb_playout_paths_*.hip): transition t < path_len[i]
+// applies path_actions[t, i] instead of a draw -- every lane reads the same element, as at the forced t = 0 of PATHS =
+// false, so no wavefront needs another's value -- and the legal-mask bit rows of the node the path ends in (l.vm before
+// transition path_len[i], or after the last transition where the episode ended on the path) go to leaf_mask row i, stored
+// by the whole team, once.  Nothing else differs: with PATHS = false every line added for it is compiled out.
 #pragma once
 #include "pcb_team.h"
 #include "pcb_launch.h"
 
-template <int KIND, int WW, int NW, bool ROUTES>
-__global__ __attribute__((amdgpu_waves_per_eu(4, 8))) __launch_bounds__(64 * NW) void k_playout(DevParams p, PlayoutArgs g) {
+template <int KIND, int WW, int NW, bool ROUTES, bool PATHS>
+// (PATHS on the kinds without pins: the path's few scalars must not cost the eighth wave their PATHS = false twins have)
+__global__ __attribute__((amdgpu_waves_per_eu(PATHS && KIND != PCBENV_PIN && KIND != PCBENV_SPATIAL ? 8 : 4, 8))) __launch_bounds__(64 * NW) void k_playout(DevParams p, PlayoutArgs g) {
     typedef Team<64 * NW> T;
     constexpr int NT = 64 * NW;
     constexpr bool PINS = KIND == PCBENV_PIN || KIND == PCBENV_SPATIAL;
@@ -31,9 +38,14 @@ __global__ __attribute__((amdgpu_waves_per_eu(4, 8))) __launch_bounds__(64 * NW)
     const int i = xcd_contiguous_env((int)blockIdx.x, 0, g.n), lane0 = threadIdx.x;
     const int H = p.H, W = p.W, HW = H * W, plane = H * WW;
     const int r = __builtin_amdgcn_readfirstlane(g.root_index ? g.root_index[i] : i / g.per_root);
-    if ((unsigned)r >= (unsigned)p.B) {  // checked before it addresses anything (team-uniform: nobody meets a barrier below)
+    // the length of playout i's path (wave-uniform; every wavefront of the team reads the same word)
+    const int plen = !PATHS ? 0 : g.path_len ? __builtin_amdgcn_readfirstlane(g.path_len[i]) : g.path_steps;
+    const bool bad_path = PATHS && (unsigned)plen > (unsigned)g.path_steps;
+    u64 *leaf = PATHS && g.leaf_mask ? g.leaf_mask + (size_t)i * 2 * plane : 0;
+    if ((unsigned)r >= (unsigned)p.B || bad_path) {  // checked before either addresses anything (team-uniform: nobody meets a barrier below)
+        if (PATHS && leaf) for (int k = lane0; k < 2 * plane; k += NT) leaf[k] = 0ull;
         if (lane0 == 0) {
-            if (g.errors) atomicOr(g.errors, 1u);
+            if (g.errors) atomicOr(g.errors, ((unsigned)r >= (unsigned)p.B ? 1u : 0u) | (bad_path ? 2u : 0u));
             g.reward[i] = 0.0;
             if (g.done) g.done[i] = 0;
             if (g.length) g.length[i] = 0;
@@ -53,15 +65,18 @@ __global__ __attribute__((amdgpu_waves_per_eu(4, 8))) __launch_bounds__(64 * NW)
         int lane = lane0;
         asm volatile("" : "+v"(lane));
         int o = 0, x = 0, y = 0, given = 0;
-        const bool forced = t == 0 && g.first_actions;
+        // the node the path names: l.vm as the last transition left it, behind the barrier that ended it (or load_state_from's)
+        if (PATHS && leaf && t == plen) for (int k = lane0; k < 2 * plane; k += NT) leaf[k] = l.vm[k];
+        const bool forced = PATHS ? t < plen : (t == 0 && g.first_actions);
+        const int *fa = PATHS ? g.path_actions + per_step * (size_t)t : g.first_actions;
         if (forced) {  // as run_env reads a caller's action: out of range is data (an invalid action), checked before use below
             if (g.fmt == PCBENV_ACTION_FLAT) {
-                const int a = g.first_actions[i];
+                const int a = fa[i];
                 given = a;
                 if (a < 0 || a >= p.O * HW) { o = -1; x = y = 0; }
                 else { o = a / HW; const int rem = a - o * HW; x = rem / W; y = rem - x * W; }
             } else {
-                o = g.first_actions[3 * (size_t)i]; x = g.first_actions[3 * (size_t)i + 1]; y = g.first_actions[3 * (size_t)i + 2];
+                o = fa[3 * (size_t)i]; x = fa[3 * (size_t)i + 1]; y = fa[3 * (size_t)i + 2];
                 if (KIND == PCBENV_SQUARE) o = 0;
             }
         } else {
@@ -125,6 +140,10 @@ __global__ __attribute__((amdgpu_waves_per_eu(4, 8))) __launch_bounds__(64 * NW)
         // `done` is team-uniform: valid, cur and `any` are functions of LDS words every wavefront read behind a barrier
         if (done) break;
         T::lds_sync();
+    }
+    if (PATHS && leaf && length <= plen) {  // the episode ended on the path, or was cut at its end: the state it is left in
+        T::lds_sync();  // team-uniform, as the loop's exit is; mask_and_emit's last words of l.vm are visible behind it
+        for (int k = lane0; k < 2 * plane; k += NT) leaf[k] = l.vm[k];
     }
     // the outputs of the last transition played (Team<>::transition's reward rules)
     if (lane0 == 0) {

@@ -28,8 +28,9 @@ struct KindLaunch {
     int (*reset)(const ResetLaunch &);
     int (*gather)(const GatherLaunch &);
     int (*playout)(const PlayoutLaunch &);
+    int (*playout_paths)(const PlayoutLaunch &);
 };
-#define PCB_KIND_LAUNCH(name) {pcb_launch_step_##name, pcb_launch_reset_##name, pcb_launch_gather_##name, pcb_launch_playout_##name}
+#define PCB_KIND_LAUNCH(name) {pcb_launch_step_##name, pcb_launch_reset_##name, pcb_launch_gather_##name, pcb_launch_playout_##name, pcb_launch_playout_paths_##name}
 static const KindLaunch kind_launch[] = {PCB_KIND_LAUNCH(square), PCB_KIND_LAUNCH(rect), PCB_KIND_LAUNCH(pin), PCB_KIND_LAUNCH(spatial)};
 static_assert(PCBENV_SQUARE == 0 && PCBENV_RECT == 1 && PCBENV_PIN == 2 && PCBENV_SPATIAL == 3, "kind_launch is indexed by kind");
 
@@ -506,6 +507,39 @@ extern "C" int pcbenv_gather(pcbenv *dst, const pcbenv *src, const int32_t *src_
 }
 
 // ---- pcbenv_playout ------------------------------------------------------------------------------------------
+// What pcbenv_playout and pcbenv_playout_paths do once their arguments have passed: the state checks, the parameter block
+// and the launch.  `g` arrives with the caller's pointers and counts; n, per_root and info are filled in here.
+static int playout_enqueue(pcbenv *env, int64_t num_playouts, PlayoutArgs g, void *stream, bool paths, const char *captured) {
+    if (num_playouts > 0x7fffffffll / 8) return fail(env, PCBENV_ELIMIT, "num_playouts too large");
+    if (num_playouts == 0) return PCBENV_OK;
+    if (!env->bound) return fail(env, PCBENV_ESTATE, "pcbenv_bind_buffers has not been called");
+    if (!env->has_episode) return fail(env, PCBENV_ESTATE, "no episode to play: reset the environments first");
+    DEVICE_GUARD(env);
+    hipStream_t s = (hipStream_t)stream;
+    // A captured launch would keep reading the state set that was current at capture time (as pcbenv_sample_logits).
+    if (stream_capturing(s)) return fail(env, PCBENV_ESTATE, captured);
+    PlayoutLaunch a;
+    a.d = env->dp;  // d.state: the current state set, as k_sample reads it
+    DevParams &d = a.d;
+    const bool pins = is_pin_kind(env->cfg.kind);
+    // nothing bound and nothing of the library's can be reached through the block: terminal_reward writes row i of these two
+    memset(&d.buf, 0, sizeof(d.buf));
+    memset(&d.cbuf, 0, sizeof(d.cbuf));
+    d.buf.reward = g.reward; d.buf.info = pins ? g.info : 0;
+    d.flags = 0u; d.num_slots = 1; d.slot = 0; d.stream_stores = 0;
+    d.queue = 0; d.feat_cache = 0; d.feat_cache_tag = 0; d.gen_produced = 0; d.gen_errors = 0; d.cursor_pub = 0;
+    d.seq = 0u; d.term_wgs = 0; d.term_cap = 0; d.term_hpe = 0; d.term_list = 0; d.term_cnt = 0; d.term_arrive = 0; d.term_seen = 0;
+    d.state_out = 0; d.dbg = 0;
+    a.threads = env->threads; a.stream = s;
+    a.routes = pins && env->cfg.reward_type != PCBENV_REWARD_CENTROID;
+    g.n = (int)num_playouts; g.per_root = g.root_index ? 1 : (int)(num_playouts / d.B);
+    if (!pins) g.info = 0;
+    a.g = g;
+    if (paths) kind_launch[env->cfg.kind].playout_paths(a); else kind_launch[env->cfg.kind].playout(a);
+    HIP_TRY(env, hipGetLastError());
+    return PCBENV_OK;
+}
+
 // As pcbenv_sample_logits: the argument checks come before anything touches a device (the null handle last), and nothing
 // the library owns is written -- the kernel gets a parameter block in which nothing but the playout's own reward / info
 // rows can be stored to.
@@ -524,37 +558,40 @@ extern "C" int pcbenv_playout(const pcbenv *cenv, const int32_t *root_index_dev,
     if (env && !root_index_dev && num_playouts % env->dp.B != 0)
         return fail(env, PCBENV_EINVAL, "without root_index, num_playouts must be a multiple of num_envs");
     if (!env) return fail(0, PCBENV_EINVAL, "null handle");
-    if (num_playouts > 0x7fffffffll / 8) return fail(env, PCBENV_ELIMIT, "num_playouts too large");
-    if (num_playouts == 0) return PCBENV_OK;
-    if (!env->bound) return fail(env, PCBENV_ESTATE, "pcbenv_bind_buffers has not been called");
-    if (!env->has_episode) return fail(env, PCBENV_ESTATE, "no episode to play: reset the environments first");
-    DEVICE_GUARD(env);
-    hipStream_t s = (hipStream_t)stream;
-    // A captured launch would keep reading the state set that was current at capture time (as pcbenv_sample_logits).
-    if (stream_capturing(s)) return fail(env, PCBENV_ESTATE, "pcbenv_playout cannot be captured into a graph");
-    PlayoutLaunch a;
-    a.d = env->dp;  // d.state: the current state set, as k_sample reads it
-    DevParams &d = a.d;
-    const bool pins = is_pin_kind(env->cfg.kind);
-    // nothing bound and nothing of the library's can be reached through the block: terminal_reward writes row i of these two
-    memset(&d.buf, 0, sizeof(d.buf));
-    memset(&d.cbuf, 0, sizeof(d.cbuf));
-    d.buf.reward = reward_dev; d.buf.info = pins ? info_dev : 0;
-    d.flags = 0u; d.num_slots = 1; d.slot = 0; d.stream_stores = 0;
-    d.queue = 0; d.feat_cache = 0; d.feat_cache_tag = 0; d.gen_produced = 0; d.gen_errors = 0; d.cursor_pub = 0;
-    d.seq = 0u; d.term_wgs = 0; d.term_cap = 0; d.term_hpe = 0; d.term_list = 0; d.term_cnt = 0; d.term_arrive = 0; d.term_seen = 0;
-    d.state_out = 0; d.dbg = 0;
-    a.threads = env->threads; a.stream = s;
-    a.routes = pins && env->cfg.reward_type != PCBENV_REWARD_CENTROID;
-    PlayoutArgs &g = a.g;
+    PlayoutArgs g = PlayoutArgs();  // the path fields null / 0
     g.root_index = root_index_dev; g.first_actions = first_actions_dev; g.reward = reward_dev; g.done = done_dev;
-    g.length = length_dev; g.info = pins ? info_dev : 0; g.actions_out = actions_out_dev; g.errors = (unsigned *)errors_dev;
-    g.n = (int)num_playouts; g.per_root = root_index_dev ? 1 : (int)(num_playouts / d.B);
+    g.length = length_dev; g.info = info_dev; g.actions_out = actions_out_dev; g.errors = (unsigned *)errors_dev;
     g.fmt = fmt; g.max_steps = max_steps; g.actions_steps = actions_steps;
     g.seed = (u64)seed; g.first_env = (u64)first_env_index; g.step_index0 = (u64)step_index0;
-    kind_launch[env->cfg.kind].playout(a);
-    HIP_TRY(env, hipGetLastError());
-    return PCBENV_OK;
+    return playout_enqueue(env, num_playouts, g, stream, false, "pcbenv_playout cannot be captured into a graph");
+}
+
+// ---- pcbenv_playout_paths ------------------------------------------------------------------------------------
+// pcbenv_playout with a path of forced actions per playout and the legal mask of the node it ends in; the arguments in a
+// struct (the stream among them).  The same rules: every argument check before a device is touched, the null handle last.
+extern "C" int pcbenv_playout_paths(const pcbenv *cenv, const pcbenv_playout_request *q) {
+    pcbenv *env = const_cast<pcbenv *>(cenv);  // the error text only
+    if (!q) return fail(env, PCBENV_EINVAL, "null request");
+    if (q->struct_size != (uint32_t)sizeof(pcbenv_playout_request)) return fail(env, PCBENV_EINVAL, "struct_size is not sizeof(pcbenv_playout_request)");
+    if (!q->reward_dev) return fail(env, PCBENV_EINVAL, "null reward");
+    CHECK_ACTION_FORMAT(env, q->action_format);
+    if (q->max_steps < 1) return fail(env, PCBENV_EINVAL, "max_steps must be at least 1");
+    if (q->path_steps < 0 || q->path_steps > q->max_steps) return fail(env, PCBENV_EINVAL, "path_steps must be in [0, max_steps]");
+    if (q->path_steps > 0 && !q->path_actions_dev) return fail(env, PCBENV_EINVAL, "null path_actions with path_steps > 0");
+    if (q->actions_steps < 0 || q->actions_steps > q->max_steps) return fail(env, PCBENV_EINVAL, "actions_steps must be in [0, max_steps]");
+    if (q->actions_steps > 0 && !q->actions_out_dev) return fail(env, PCBENV_EINVAL, "null actions_out with actions_steps > 0");
+    if (((uintptr_t)q->leaf_mask_bits_dev & 7u) != 0) return fail(env, PCBENV_EINVAL, "leaf_mask_bits must be 8-byte aligned");
+    if (q->num_playouts < 0) return fail(env, PCBENV_EINVAL, "num_playouts must not be negative");
+    if (env && !q->root_index_dev && q->num_playouts % env->dp.B != 0)
+        return fail(env, PCBENV_EINVAL, "without root_index, num_playouts must be a multiple of num_envs");
+    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
+    PlayoutArgs g = PlayoutArgs();
+    g.root_index = q->root_index_dev; g.reward = q->reward_dev; g.done = q->done_dev;
+    g.length = q->length_dev; g.info = q->info_dev; g.actions_out = q->actions_out_dev; g.errors = (unsigned *)q->errors_dev;
+    g.fmt = q->action_format; g.max_steps = q->max_steps; g.actions_steps = q->actions_steps;
+    g.seed = (u64)q->seed; g.first_env = (u64)q->first_env_index; g.step_index0 = (u64)q->step_index0;
+    g.path_actions = q->path_actions_dev; g.path_len = q->path_len_dev; g.leaf_mask = (u64 *)q->leaf_mask_bits_dev; g.path_steps = q->path_steps;
+    return playout_enqueue(env, q->num_playouts, g, q->stream, true, "pcbenv_playout_paths cannot be captured into a graph");
 }
 
 // ---- pcbenv_sample_logits ------------------------------------------------------------------------------------

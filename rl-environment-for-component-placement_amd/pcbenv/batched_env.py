@@ -72,6 +72,7 @@ class Playout:
     length: torch.Tensor            # [n] int32: transitions played
     info: Optional[torch.Tensor]    # [n, 2] float64 (wirelength, num_intersections), NaN where empty; None for square / rect
     actions: Optional[torch.Tensor] # [actions_steps, n, 3] int32, rows t >= length are zero; None if actions_steps == 0
+    leaf_mask: Optional[torch.Tensor] = None  # [n, 2, H, WW] int64 like mask_bits(): the legal mask of the node each path ends in (leaf_mask=True)
 
 
 def default_max_steps(cfg: EnvConfig) -> int:
@@ -631,7 +632,8 @@ class BatchedPlacementEnv:
 
     def playout(self, k: Optional[int] = None, index: Optional[torch.Tensor] = None, step_index: int = 0,
                 first_actions: Optional[torch.Tensor] = None, max_steps: Optional[int] = None,
-                actions_steps: Optional[int] = None, first_env_index: int = 0, check: bool = False) -> Playout:
+                actions_steps: Optional[int] = None, first_env_index: int = 0, check: bool = False,
+                paths: Optional[torch.Tensor] = None, path_len: Optional[torch.Tensor] = None, leaf_mask: bool = False) -> Playout:
         """Play forked episodes to their end on the device without observations (`pcbenv_playout`, one kernel launch, no
         second handle): playout i starts from the episode in progress of environment `index[i]` -- or, with `k`,
         environment i // k (k playouts per environment) -- and takes uniformly drawn legal actions until its first
@@ -641,7 +643,16 @@ class BatchedPlacementEnv:
         handle's, bit for bit.  first_actions: int32 [n, 3] or flat [n]: the action of transition 0 instead of a draw (an
         illegal one ends the playout with the worst-case reward, as `step` would).  actions_steps (default max_steps):
         how many leading actions to record.  Nothing of this environment batch changes.  check=True synchronises and
-        raises IndexError if an index was out of range (those rows report length 0)."""
+        raises IndexError if an index was out of range (those rows report length 0).
+
+        Playouts from tree nodes (`pcbenv_playout_paths`, taken when any of the next three is given): paths, int32
+        [D, n, 3] or flat [D, n], step-major like `actions`: transition t < path_len[i] of playout i applies paths[t, i]
+        instead of a draw, the later ones draw as above (the draw's key depends on t, not on the path, and max_steps counts
+        the path's transitions too).  path_len: int32 [n], default D for every playout; check=True also raises on a value
+        outside [0, D].  A bad path action ends the playout there with the worst-case reward.  leaf_mask=True: the result's
+        `leaf_mask` is the legal mask of the node each path ends in -- or of the state the episode ended in, if it ended
+        on the path -- int64 [n, 2, H, WW] like `mask_bits()`, usable as the mask_bits of the evaluate calls.  `actions`
+        records a path action as given.  first_actions cannot be combined with any of the three (it is a path of one step)."""
         if (k is None) == (index is None):
             raise ValueError("playout: give either k (playouts per environment) or index (the root of every playout)")
         idx = None
@@ -657,6 +668,23 @@ class BatchedPlacementEnv:
         T = default_max_steps(self.cfg) if max_steps is None else int(max_steps)
         A = T if actions_steps is None else int(actions_steps)
         fmt, fa = _lib.ACTION_TUPLE, None
+        use_paths = paths is not None or path_len is not None or leaf_mask
+        if first_actions is not None and use_paths:
+            raise ValueError("playout: first_actions cannot be combined with paths, path_len or leaf_mask (give it as a path of one step)")
+        pa, pl, D = None, None, 0
+        if paths is not None:
+            pa = paths.to(device=self.device, dtype=torch.int32).contiguous()
+            if pa.dim() not in (2, 3) or pa.shape[1] != n or (pa.dim() == 3 and pa.shape[2] != 3):
+                raise ValueError(f"paths must have shape [D, {n}] (flat) or [D, {n}, 3], got {tuple(pa.shape)}")
+            D = pa.shape[0]
+            if pa.dim() == 2:
+                fmt = _lib.ACTION_FLAT
+            if D > T:
+                raise ValueError(f"paths has {D} steps, max_steps is {T}")
+        if path_len is not None:
+            pl = path_len.to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(pl.shape) != (n,):
+                raise ValueError(f"path_len must have shape [{n}], got {tuple(pl.shape)}")
         if first_actions is not None:
             fa = first_actions.to(device=self.device, dtype=torch.int32).contiguous()
             if tuple(fa.shape) not in ((n,), (n, 3)):
@@ -671,9 +699,22 @@ class BatchedPlacementEnv:
         info = torch.empty((n, 2), dtype=torch.float64, device=dev) if pins else None
         actions = torch.zeros((A, n) if fmt == _lib.ACTION_FLAT else (A, n, 3), dtype=torch.int32, device=dev) if A > 0 else None
         err = torch.zeros(1, dtype=torch.int32, device=dev) if check else None
+        H, WW = self.cfg.height, (self.cfg.width + 63) // 64
+        leaf = torch.empty((n, 2, H, WW), dtype=torch.int64, device=dev) if leaf_mask else None
         if n == 0:  # torch gives empty tensors a null pointer
-            return Playout(reward, done, length, info, actions)
+            return Playout(reward, done, length, info, actions, leaf)
         ptr = lambda t: None if t is None else t.data_ptr()
+        if use_paths:
+            req = _lib.PcbenvPlayoutRequest(
+                struct_size=C.sizeof(_lib.PcbenvPlayoutRequest), action_format=fmt, root_index_dev=ptr(idx), num_playouts=n,
+                path_actions_dev=ptr(pa) if D > 0 else None, path_len_dev=ptr(pl), path_steps=D, max_steps=T, reward_dev=reward.data_ptr(),
+                done_dev=done.data_ptr(), length_dev=length.data_ptr(), info_dev=ptr(info), actions_out_dev=ptr(actions), actions_steps=A,
+                leaf_mask_bits_dev=ptr(leaf), errors_dev=ptr(err), seed=self.run_seed, first_env_index=int(first_env_index),
+                step_index0=int(step_index), stream=self._stream().value)
+            _lib.check(self._L.pcbenv_playout_paths(self._h, C.byref(req)), self._h)
+            if check and int(err.item()) != 0:
+                raise IndexError(f"playout: an index is outside [0, {self.num_envs}) or a path_len outside [0, {D}] (those playouts report length 0)")
+            return Playout(reward, done, length, info, actions, leaf)
         _lib.check(self._L.pcbenv_playout(
             self._h, ptr(idx), n, ptr(fa), fmt, T, reward.data_ptr(), done.data_ptr(), length.data_ptr(), ptr(info),
             ptr(actions), A, ptr(err), self.run_seed, int(first_env_index), int(step_index), self._stream()), self._h)

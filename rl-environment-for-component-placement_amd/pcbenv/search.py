@@ -9,6 +9,10 @@ the best child's first action to the root and searches again from the next state
 `best_of_k_playouts` gives the same result without the planner batch: `BatchedPlacementEnv.playout` plays the k forks of
 every root in one kernel launch that writes no observation (pcbenv_playout).  `action_values` scores candidate first
 actions the same way: k playouts behind each candidate, the forced first action of the playout call.
+
+`tree_search` goes deeper than one ply: a batched UCT whose nodes are named by their path from the root and evaluated by
+`BatchedPlacementEnv.playout(paths=...)` (pcbenv_playout_paths) -- one launch per iteration for all roots, no planner
+batch, no node ever materialised.
 """
 from __future__ import annotations
 
@@ -108,3 +112,136 @@ def action_values(root, candidates: torch.Tensor, k: int, step_index: int, max_s
     first = candidates.to(device=root.device, dtype=torch.int32).repeat_interleave(k, dim=1).reshape(P * A * k, 3)
     po = root.playout(k=A * k, step_index=step_index, first_actions=first, max_steps=max_steps, actions_steps=0)
     return aggregate_values(po.reward, po.done, P, A, k)
+
+
+@dataclass
+class TreeSearch:
+    """What `tree_search` returns.  P roots, N = iterations + 1 node slots per root (slot 0 is the root, slots are filled in
+    the order the nodes were created), C = max_children."""
+    action: torch.Tensor         # [P, 3] int32: the most-visited first action (ties: the lowest child slot)
+    child_visits: torch.Tensor   # [P, C] int64: visits of the root's children, 0 where there is none
+    child_actions: torch.Tensor  # [P, C, 3] int32: their actions
+    best_reward: torch.Tensor    # [P] float64: the reward of the best playout seen (the first such playout on ties)
+    best_actions: torch.Tensor   # [T, P, 3] int32: its actions (rows behind its end: don't care)
+    best_length: torch.Tensor    # [P] int64
+    num_nodes: torch.Tensor      # [P] int64: node slots in use
+    parent: torch.Tensor         # [P, N] int64, -1 for the root and for unused slots
+    depth: torch.Tensor          # [P, N] int64
+    node_action: torch.Tensor    # [P, N, 3] int32: the action that leads from the parent to the node
+    visits: torch.Tensor         # [P, N] int64
+    value_sum: torch.Tensor      # [P, N] float64: sum of the final rewards of the playouts through the node
+    value_max: torch.Tensor      # [P, N] float64: the best of them, -inf for unused slots
+    terminal: torch.Tensor       # [P, N] bool: the episode is over at the node
+    children: torch.Tensor       # [P, N, C] int64: node slots of the children in the order they were created, -1 = none
+
+
+def tree_search(root, iterations: int, step_index: int, c_uct: float = 1.0, max_children: int = 4, backend=None,
+                max_steps=None) -> TreeSearch:
+    """Batched UCT over all P = root.num_envs roots in lock-step, the tree in tensors, one playout launch per iteration and
+    no host synchronisation inside the loop.  Iteration m:
+      selection  from the root, descend to the child with the highest q + c_uct * sqrt(ln(visits of the node) / visits of
+                 the child), q = the child's mean playout reward normalised per root by the smallest and largest playout
+                 reward seen so far (0 while they are equal), ties to the lowest child slot; stop at a terminal node or at
+                 a node with fewer than max_children children;
+      launch     backend(paths, path_len, step_index + m * max_steps): P playouts, playout p forced along the path of root
+                 p's selected node (paths int32 [max_steps, P, 3], path_len int32 [P] = the node's depth) and drawing
+                 uniformly behind it -- `root.playout(k=1, paths=..., path_len=..., max_steps=max_steps)` by default;
+      expansion  the action the playout itself drew at row `depth` becomes a new child of the selected node, or revisits the
+                 child that already has that action (no extra sampling launch); the child is terminal if the playout ended
+                 with that transition.  A terminal node is never expanded: its playout replays the path and ends on it;
+      backup     the playout's final reward is added to visits / value_sum / value_max of the leaf and all its ancestors.
+    max_steps: the most transitions of an episode (default: that of root.cfg); it bounds the depth loops.  The playouts of
+    iteration m use step indices step_index + m * max_steps + t, so every draw of a search has its own key and a search is
+    a function of (the roots, run_seed, step_index).  Needs iterations >= 1.  `backend` may be any callable with that
+    signature returning a `Playout` with reward, length and actions (tests: a CPU oracle); everything else is tensor code
+    for any device."""
+    from .batched_env import default_max_steps
+    P, C, M = int(root.num_envs), int(max_children), int(iterations)
+    if M < 1 or C < 1:
+        raise ValueError("tree_search needs iterations >= 1 and max_children >= 1")
+    T = default_max_steps(root.cfg) if max_steps is None else int(max_steps)
+    if backend is None:
+        backend = lambda paths, path_len, s: root.playout(k=1, step_index=s, paths=paths, path_len=path_len, max_steps=T)
+    dev = getattr(root, "device", "cpu")
+    N = M + 1
+    i64 = dict(dtype=torch.int64, device=dev)
+    # one slot, one child column and one path row more than used: where a root has nothing to write, the write goes there
+    parent = torch.full((P, N + 1), -1, **i64)
+    depth = torch.zeros((P, N + 1), **i64)
+    node_action = torch.zeros((P, N + 1, 3), dtype=torch.int32, device=dev)
+    visits = torch.zeros((P, N + 1), **i64)
+    vsum = torch.zeros((P, N + 1), dtype=torch.float64, device=dev)
+    vmax = torch.full((P, N + 1), float("-inf"), dtype=torch.float64, device=dev)
+    terminal = torch.zeros((P, N + 1), dtype=torch.bool, device=dev)
+    children = torch.full((P, N + 1, C + 1), -1, **i64)
+    nchild = torch.zeros((P, N + 1), **i64)
+    count = torch.ones(P, **i64)
+    lo = torch.full((P,), float("inf"), dtype=torch.float64, device=dev)
+    hi = torch.full((P,), float("-inf"), dtype=torch.float64, device=dev)
+    best_reward = torch.full((P,), float("-inf"), dtype=torch.float64, device=dev)
+    best_actions = torch.zeros((T, P, 3), dtype=torch.int32, device=dev)
+    best_length = torch.zeros(P, **i64)
+    rows = torch.arange(P, **i64)
+    trash = torch.full((P,), N, **i64)
+    zero_r = torch.zeros(P, dtype=torch.float64, device=dev)
+    ninf_r = torch.full((P,), float("-inf"), dtype=torch.float64, device=dev)
+    for m in range(M):
+        # selection
+        node = torch.zeros(P, **i64)
+        paths = torch.zeros((T + 1, P, 3), dtype=torch.int32, device=dev)
+        span = torch.where(hi > lo, hi - lo, torch.ones_like(hi))
+        for d in range(min(T, m)):  # (iteration m finds no node deeper than m: a bound the host knows without asking the device)
+            stop = terminal[rows, node] | (nchild[rows, node] < C)
+            ch = children[rows, node, :C]                          # [P, C], all >= 0 where the descent goes on
+            chc = ch.clamp(min=0)
+            n_c = visits[rows[:, None], chc].clamp(min=1).to(torch.float64)
+            q = (vsum[rows[:, None], chc] / n_c - lo[:, None]) / span[:, None]
+            q = torch.where((hi > lo)[:, None], q, torch.zeros_like(q))
+            n_p = visits[rows, node].clamp(min=1).to(torch.float64)
+            ucb = q + c_uct * torch.sqrt(torch.log(n_p)[:, None] / n_c)
+            ucb = torch.where(ch >= 0, ucb, torch.full_like(ucb, float("-inf")))
+            nxt = chc[rows, ucb.argmax(dim=1)]                     # the first maximum: the lowest child slot
+            node = torch.where(stop, node, nxt)
+            paths[torch.where(stop, torch.full_like(node, T), torch.full_like(node, d)), rows] = node_action[rows, node]
+        dsel = depth[rows, node]
+        # launch
+        po = backend(paths[:T], dsel.to(torch.int32), int(step_index) + m * T)
+        r, L = po.reward.to(torch.float64), po.length.to(torch.int64)
+        # expansion: the action drawn at row `depth` (there is one unless the episode ended on the path)
+        drew = (L > dsel) & ~terminal[rows, node]
+        a = po.actions[dsel.clamp(max=T - 1), rows].to(torch.int32)          # [P, 3]
+        ch = children[rows, node, :C]
+        same = (ch >= 0) & (node_action[rows[:, None], ch.clamp(min=0)] == a[:, None, :]).all(dim=2) & drew[:, None]
+        found = same.any(dim=1)
+        old = ch.clamp(min=0)[rows, same.to(torch.int64).argmax(dim=1)]
+        make = drew & ~found & (nchild[rows, node] < C)
+        slot = torch.where(make, count, trash)
+        parent[rows, slot] = torch.where(make, node, torch.full_like(node, -1))
+        depth[rows, slot] = torch.where(make, dsel + 1, torch.zeros_like(dsel))
+        node_action[rows, slot] = torch.where(make[:, None], a, torch.zeros_like(a))
+        terminal[rows, slot] = make & (L <= dsel + 1)
+        children[rows, node, torch.where(make, nchild[rows, node], torch.full_like(node, C))] = slot
+        nchild[rows, node] += make.to(torch.int64)
+        count += make.to(torch.int64)
+        leaf = torch.where(found, old, torch.where(make, slot, node))
+        # backup
+        lo, hi = torch.minimum(lo, r), torch.maximum(hi, r)
+        cur = leaf
+        for _ in range(min(T, m + 1) + 1):  # the leaf is at depth m + 1 at most
+            on = cur >= 0
+            idx = torch.where(on, cur, trash)[:, None]
+            visits.scatter_add_(1, idx, on.to(torch.int64)[:, None])
+            vsum.scatter_add_(1, idx, torch.where(on, r, zero_r)[:, None])
+            vmax.scatter_reduce_(1, idx, torch.where(on, r, ninf_r)[:, None], reduce="amax")
+            cur = torch.where(on, parent[rows, idx[:, 0]], torch.full_like(cur, -1))
+        better = r > best_reward
+        best_reward = torch.where(better, r, best_reward)
+        best_length = torch.where(better, L, best_length)
+        best_actions = torch.where(better[None, :, None], po.actions[:T].to(torch.int32), best_actions)
+    ch = children[:, 0, :C]
+    child_visits = torch.where(ch >= 0, visits[rows[:, None], ch.clamp(min=0)], torch.zeros_like(ch))
+    child_actions = torch.where((ch >= 0)[:, :, None], node_action[rows[:, None], ch.clamp(min=0)], torch.zeros((P, C, 3), dtype=torch.int32, device=dev))
+    action = child_actions[rows, child_visits.argmax(dim=1)]
+    return TreeSearch(action, child_visits, child_actions, best_reward, best_actions, best_length, count,
+                      parent[:, :N], depth[:, :N], node_action[:, :N], visits[:, :N], vsum[:, :N], vmax[:, :N], terminal[:, :N],
+                      children[:, :N, :C])

@@ -1,11 +1,13 @@
 """Receding-horizon Monte-Carlo lookahead with pcbenv.search.best_of_k against the plain uniform-random policy, c3.
-python tools/search_demo.py [--roots 256] [--k 16] [--playouts]
+python tools/search_demo.py [--roots 256] [--k 16] [--playouts | --tree]
 
 Both play the same instances (one episode per root environment).  The search forks every root k times into a planner
 batch (one device-side gather), plays every child to its end with the on-device sampler, and applies the best child's
 first action to the root, then searches again.  --playouts: the same search through pcbenv.search.best_of_k_playouts --
 one pcbenv_playout launch per search step instead of a planner batch and a launch per planner step.  Reports mean final reward of both policies and the search rate in
-planner env-steps/s (wall time of the best_of_k calls)."""
+planner env-steps/s (wall time of the best_of_k calls).  --tree: pcbenv.search.tree_search with k iterations per move -- the
+same number of playouts as best-of-k, spent by UCT on a tree of paths (one pcbenv_playout_paths launch per iteration) -- and
+the most-visited first action is applied."""
 import argparse
 import json
 import os
@@ -17,7 +19,7 @@ import torch  # noqa: E402
 
 from pcbenv import named_config  # noqa: E402
 from pcbenv.batched_env import BatchedPlacementEnv  # noqa: E402
-from pcbenv.search import best_of_k, best_of_k_playouts  # noqa: E402
+from pcbenv.search import best_of_k, best_of_k_playouts, tree_search  # noqa: E402
 
 
 def final_rewards(env, act, T):
@@ -39,6 +41,7 @@ def main():
     ap.add_argument("--k", type=int, default=16)
     ap.add_argument("--config", default="c3")
     ap.add_argument("--playouts", action="store_true", help="search with best_of_k_playouts (no planner batch)")
+    ap.add_argument("--tree", action="store_true", help="search with tree_search, k iterations per move (no planner batch)")
     a = ap.parse_args()
     cfg = named_config(a.config)
     P, k, T = a.roots, a.k, cfg.max_num_components
@@ -49,7 +52,7 @@ def main():
         e.reset()
         return e
     rand_root, search_root = make(P, 11), make(P, 11)
-    planner = None if a.playouts else make(P * k, 12)
+    planner = None if a.playouts or a.tree else make(P * k, 12)
 
     random_final = final_rewards(rand_root, lambda t: rand_root.rollout_step(t)[1:3], T)
     torch.cuda.synchronize()
@@ -59,17 +62,19 @@ def main():
         nonlocal spent, planner_steps
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        if a.playouts:
+        if a.tree:
+            first = tree_search(search_root, k, step_index=1000 + t * T * k).action
+        elif a.playouts:
             res = best_of_k_playouts(search_root, k, step_index=1000 + t * T)
         else:
             res = best_of_k(search_root, planner, k, step_index=1000 + t * T)
         torch.cuda.synchronize()
         spent += time.perf_counter() - t0
         planner_steps += P * k * T
-        _, r, d, _ = search_root.step(res.actions[0])
+        _, r, d, _ = search_root.step(first if a.tree else res.actions[0])
         return r, d
     search_final = final_rewards(search_root, search_step, T)
-    out = {"config": a.config, "roots": P, "k": k, "search": "best_of_k_playouts" if a.playouts else "best_of_k",
+    out = {"config": a.config, "roots": P, "k": k, "search": "tree_search" if a.tree else "best_of_k_playouts" if a.playouts else "best_of_k",
            "random_policy_mean_final_reward": float(random_final.mean()),
            "best_of_k_mean_final_reward": float(search_final.mean()),
            "search_env_steps_per_sec": round(planner_steps / spent), "search_seconds": round(spent, 3)}
