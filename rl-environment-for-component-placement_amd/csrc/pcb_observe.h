@@ -178,11 +178,8 @@ static __device__ inline void build_pin_tables(const DevParams &p, Lds &l, int l
         const PinRec pr = l.pins[q];
         const CompRec cr = l.comps[pr.comp];
         int rx = pr.rel_x, ry = pr.rel_y;
-        if (cr.px >= 0) {  // inverse of S:149-190 place_component
-            const int ax = rx, ay = ry;
-            if (cr.o == 1) { rx = cr.h - 1 - ay; ry = ax; }
-            else if (cr.o == 2) { rx = cr.h - 1 - ax; ry = cr.w - 1 - ay; }
-            else if (cr.o == 3) { rx = ay; ry = cr.w - 1 - ax; }
+        if (cr.px >= 0) {  // placed: undo place_component's rotation (pcb_transition.h)
+            PCB_UNROTATE_REL(cr.o, cr.h, cr.w, rx, ry)
         }
         t.pid[pr.comp * p.mp + l.rank[q]] = (unsigned short)(pr.id & PIN_ID_MASK);
         atomicOr(&t.netmask[(int)pr.comp * p.mp + rx * p.mw + ry], 1u << pr.net);

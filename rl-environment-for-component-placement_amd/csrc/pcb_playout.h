@@ -11,11 +11,12 @@
 // is written.  What a playout writes is its row of the caller's outputs, each element by one lane, once:
 // reward / done / length / info after the last transition and the action of every recorded step.
 //
-// The placement update is restated here instead of calling Team<>::transition: that function stores done and reward rows
-// at every transition (the playout's done row is optional and its reward is the LAST transition's only) and carries the
-// reset and every emission under run-time flags, which this kernel would compile in and hold registers for.  What
-// is shared is everything with a result in it: window_mask through mask_and_emit(emit = false), sample_action and
-// terminal_reward -- the latter through the parameter block, whose buf.reward / buf.info the host points at the
+// Team<>::transition is not called: that function stores done and reward rows at every transition (the playout's done row
+// is optional and its reward is the LAST transition's only) and carries the reset and every emission under run-time flags,
+// which this kernel would compile in and hold registers for.  The loop below has the same steps around the same text: the
+// arithmetic of a transition is pcb_transition.h's, expanded here as in transition; the draw is Team<>::draw_action, which
+// run_env calls too; window_mask through mask_and_emit(emit = false), sample_action and terminal_reward are the step kernel's
+// -- the latter through the parameter block, whose buf.reward / buf.info the host points at the
 // playout's rows (every other tensor null, flags and the terminal list zeroed: pcbenv_playout).
 //
 // PATHS = true is the kernel of pcbenv_playout_paths (instantiated in pcb_playout_paths_*.hip): transition t < path_len[i]
@@ -71,33 +72,22 @@ __global__ __attribute__((amdgpu_waves_per_eu(PATHS && KIND != PCBENV_PIN && KIN
         const int *fa = PATHS ? g.path_actions + per_step * (size_t)t : g.first_actions;
         if (forced) {  // as run_env reads a caller's action: out of range is data (an invalid action), checked before use below
             if (g.fmt == PCBENV_ACTION_FLAT) {
-                const int a = fa[i];
-                given = a;
-                if (a < 0 || a >= p.O * HW) { o = -1; x = y = 0; }
-                else { o = a / HW; const int rem = a - o * HW; x = rem / W; y = rem - x * W; }
+                given = fa[i];
+                unflatten_action(given, p.O, HW, W, &o, &x, &y);
             } else {
                 o = fa[3 * (size_t)i]; x = fa[3 * (size_t)i + 1]; y = fa[3 * (size_t)i + 2];
                 if (KIND == PCBENV_SQUARE) o = 0;
             }
-        } else {
-            if (lane < WAVE) {  // wavefront 0 draws (the result is wave-uniform), the others take it from LDS
-                sample_action(l.vm, p, genv, lane, g.seed, g.step_index0 + (u64)t, &o, &x, &y);
-                if (NT > WAVE && lane == 0) { l.hdr->pad[0] = (unsigned)o; l.hdr->pad[1] = (unsigned)x; l.hdr->flag = (unsigned)y; }
-            }
-            if (NT > WAVE) {
-                T::lds_sync();
-                o = (int)l.hdr->pad[0]; x = (int)l.hdr->pad[1]; y = (int)l.hdr->flag;
-            }
-        }
+        } else T::draw_action(p, l, genv, lane, g.seed, g.step_index0 + (u64)t, &o, &x, &y);
         if (lane == 0 && t < g.actions_steps) {
             int *act = g.actions_out + per_step * (size_t)t;
-            if (g.fmt == PCBENV_ACTION_FLAT) act[i] = forced ? given : o * HW + x * W + y;
+            if (g.fmt == PCBENV_ACTION_FLAT) act[i] = forced ? given : PCB_FLATTEN_ACTION(o, x, y, HW, W);
             else { act[3 * (size_t)i] = o; act[3 * (size_t)i + 1] = x; act[3 * (size_t)i + 2] = y; }
         }
-        // validate_action (S:1699-1723), as Team<>::transition: anything out of range is invalid
+        // validate_action and the update, as Team<>::transition has them: the text of pcb_transition.h, expanded in place
         const int cur = l.hdr->cur, ncomp = l.hdr->ncomp, npins = l.hdr->npins;
-        valid = o >= 0 && o < p.O && x >= 0 && x < H && y >= 0 && y < W && (KIND == PCBENV_SQUARE || cur >= 0);
-        if (valid) valid = (l.vm[(o & 1) * plane + x * WW + (y >> 6)] >> (y & 63)) & 1ull;
+        valid = PCB_ACTION_IN_RANGE(o, x, y, p.O, H, W) && (KIND == PCBENV_SQUARE || cur >= 0);
+        if (valid) valid = PCB_LEGAL_BIT(l.vm, (o & 1) * plane, WW, x, y);
         if (NT > WAVE) T::lds_sync();  // every wavefront has read the cursor and the mask bit before anything below changes them
         done = true;  // an invalid action is a terminal transition with the state unchanged (quirk Q8 iii)
         if (valid) {
@@ -106,14 +96,11 @@ __global__ __attribute__((amdgpu_waves_per_eu(PATHS && KIND != PCBENV_PIN && KIN
             if (KIND == PCBENV_SQUARE) ph = pw = p.component_n;
             else {
                 cr = l.comps[cur];
-                ph = (o & 1) ? cr.w : cr.h;  // S:1742-1747 update_grid
-                pw = (o & 1) ? cr.h : cr.w;
+                ph = PCB_PLACED_H(o, cr.h, cr.w);
+                pw = PCB_PLACED_W(o, cr.h, cr.w);
             }
             for (int rr = x + lane; rr < x + ph && rr < H; rr += NT) {
-                for (int w = 0; w < WW; w++) {
-                    const int lo = max(y, 64 * w) - 64 * w, hi = min(y + pw, 64 * w + 64) - 64 * w;  // bit range in word w
-                    if (hi > lo) l.occ[rr * WW + w] |= ((hi - lo) >= 64 ? ~0ull : ((1ull << (hi - lo)) - 1ull)) << lo;
-                }
+                PCB_OCCUPY_ROW(l.occ, rr * WW, WW, y, pw)
             }
             if (KIND != PCBENV_SQUARE) {
                 if (lane == 0) { l.comps[cur].px = (signed char)x; l.comps[cur].py = (signed char)y; l.comps[cur].o = (unsigned char)o; }
@@ -122,19 +109,15 @@ __global__ __attribute__((amdgpu_waves_per_eu(PATHS && KIND != PCBENV_PIN && KIN
                     for (int q = lane; q < npins; q += NT) {  // S:149-190 place_component
                         PinRec pr = l.pins[q];
                         if (pr.comp != cur) continue;
-                        const int rx = pr.rel_x, ry = pr.rel_y;
-                        if (o == 1) { pr.rel_x = ry; pr.rel_y = ch - rx - 1; }
-                        else if (o == 2) { pr.rel_x = ch - rx - 1; pr.rel_y = cw - ry - 1; }
-                        else if (o == 3) { pr.rel_x = cw - ry - 1; pr.rel_y = rx; }
-                        pr.abs_x = (signed char)(x + pr.rel_x); pr.abs_y = (signed char)(y + pr.rel_y);
+                        PCB_PLACE_PIN(pr, o, ch, cw, x, y)
                         l.pins[q] = pr;
                     }
                 }
-                if (lane == 0) l.hdr->cur = (short)(cur + 1 < ncomp ? cur + 1 : -1);
+                if (lane == 0) l.hdr->cur = (short)next_component(cur, ncomp);
             }
             T::lds_sync();
             const bool any = T::template mask_and_emit<KIND, WW>(p, l, i, lane, false, 0, 0);  // team-uniform (block_any)
-            done = KIND == PCBENV_SQUARE ? !any : (l.hdr->cur < 0 || !any);  // S:1856-1869
+            done = episode_done<KIND>(l.hdr->cur, any);
         }
         length = t + 1;
         // `done` is team-uniform: valid, cur and `any` are functions of LDS words every wavefront read behind a barrier

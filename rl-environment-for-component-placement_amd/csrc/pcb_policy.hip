@@ -28,6 +28,7 @@
 #include "pcb_sampler.h"
 #include "pcb_launch.h"
 #include "pcb_policy_common.h"
+#include "pcb_transition.h"
 
 namespace {
 
@@ -71,7 +72,7 @@ __global__ __launch_bounds__(64 * NW) void k_sample_logits(DevParams p, SampleLo
         // not a distribution: exactly the uniform draw of pcbenv_sample_actions
         int o, x, y;
         sample_action(vm, p, (int)g.first_env + e, lane, g.seed, g.step_index, &o, &x, &y);
-        a = o * HW + x * W + y;
+        a = flatten_action(o, x, y, HW, W);
         logp = -log((double)n); ent = log((double)n);
     } else if (n > 0) {
         double mine = 0.0, tl = 0.0;
@@ -125,7 +126,8 @@ __global__ __launch_bounds__(64 * NW) void k_sample_logits(DevParams p, SampleLo
         }
     }
     if (lane == 0) {
-        const int o = a / HW, x = (a - o * HW) / W, y = a - o * HW - x * W;
+        int o, x, y;
+        split_action(a, HW, W, &o, &x, &y);
         if (g.fmt == PCBENV_ACTION_FLAT) g.actions[e] = a;
         else { g.actions[3 * e] = o; g.actions[3 * e + 1] = x; g.actions[3 * e + 2] = y; }
         if (g.log_prob) g.log_prob[e] = (float)logp;

@@ -23,6 +23,7 @@
 #include "pcbenv.h"
 #include "pcb_launch.h"
 #include "pcb_policy_common.h"
+#include "pcb_transition.h"
 
 namespace {
 
@@ -61,13 +62,13 @@ __device__ inline int stored_action(const u64 *vml, const EvalGeom &q, const int
     if (fmt == PCBENV_ACTION_FLAT) {
         const int a = actions[e];
         if (a < 0 || a >= q.O * HW) { *legal = false; return -1; }
-        o = a / HW; x = (a - o * HW) / q.W; y = a - o * HW - x * q.W;
+        split_action(a, HW, q.W, &o, &x, &y);
     } else {
         o = actions[3 * (size_t)e]; x = actions[3 * (size_t)e + 1]; y = actions[3 * (size_t)e + 2];
-        if (o < 0 || o >= q.O || x < 0 || x >= q.H || y < 0 || y >= q.W) { *legal = false; return -1; }
+        if (o < 0 || o >= q.O || x < 0 || x >= q.H || y < 0 || y >= q.W) { *legal = false; return -1; }  // !PCB_ACTION_IN_RANGE, as it stood
     }
-    *legal = (vml[(o & 1) * q.H * q.WW + x * q.WW + (y >> 6)] >> (y & 63)) & 1ull;
-    return o * HW + x * q.W + y;
+    *legal = PCB_LEGAL_BIT(vml, (o & 1) * q.H * q.WW, q.WW, x, y);
+    return PCB_FLATTEN_ACTION(o, x, y, HW, q.W);
 }
 
 template <typename T, bool VEC, int NW>

@@ -18,6 +18,19 @@ static __device__ inline void presample_next(const DevParams &p, Lds &l, int sam
     }
 }
 
+// A uniformly drawn legal action for every lane of the team: wavefront 0 draws (the result is wave-uniform), the others
+// take it from LDS behind a barrier.
+static __device__ __forceinline__ void draw_action(const DevParams &p, Lds &l, int genv, int lane, u64 seed, u64 step, int *o, int *x, int *y) {
+    if (lane < WAVE) {
+        sample_action(l.vm, p, genv, lane, seed, step, o, x, y);
+        if (NT > WAVE && lane == 0) { l.hdr->pad[0] = (unsigned)*o; l.hdr->pad[1] = (unsigned)*x; l.hdr->flag = (unsigned)*y; }
+    }
+    if (NT > WAVE) {
+        lds_sync();
+        *o = (int)l.hdr->pad[0]; *x = (int)l.hdr->pad[1]; *y = (int)l.hdr->flag;
+    }
+}
+
 // Who runs what of a transition (run_env has the story of the terminal list and its helper teams):
 //   MODE_ALL        the environment's own team does everything (no helpers in this launch, or the environment is not listed);
 //   MODE_DELEGATED  the environment's own team; its episode is certain to end with this transition and REWARD_PARTS helper
@@ -48,9 +61,9 @@ static __device__ __forceinline__ void transition(const DevParams &p, Lds &l, in
     if (mode == MODE_FEATURES) { reset_env<KIND, WW, TRAJ>(p, l, e, row, lane, RESET_FEATURES); return; }
     const bool full = TRAJ && p.num_slots > 1;  // trajectory layout: every tensor of the destination slot is written whole
     const int cur = l.hdr->cur, ncomp = l.hdr->ncomp, npins = l.hdr->npins;
-    // validate_action (S:1699-1723): action_mask[o, x, y] == 1; anything out of range is invalid
-    bool valid = o >= 0 && o < p.O && x >= 0 && x < H && y >= 0 && y < W && (KIND == PCBENV_SQUARE || cur >= 0);
-    if (valid) valid = (l.vm[(o & 1) * plane + x * WW + (y >> 6)] >> (y & 63)) & 1ull;
+    // validate_action and, below, the update: the text of pcb_transition.h, expanded in place (see there)
+    bool valid = PCB_ACTION_IN_RANGE(o, x, y, p.O, H, W) && (KIND == PCBENV_SQUARE || cur >= 0);
+    if (valid) valid = PCB_LEGAL_BIT(l.vm, (o & 1) * plane, WW, x, y);
     if (mode == MODE_REWARD && !valid) return;  // the worst-case reward of an invalid action is the environment's own team's
     const bool obs = mode != MODE_REWARD;  // a reward helper writes no observation byte
     // Delegated and valid: the last component is being placed, the helpers route the reward from their own replay of it.
@@ -69,15 +82,12 @@ static __device__ __forceinline__ void transition(const DevParams &p, Lds &l, in
         if (KIND == PCBENV_SQUARE) ph = pw = p.component_n;
         else {
             cr = l.comps[cur];
-            ph = (o & 1) ? cr.w : cr.h;  // S:1742-1747 update_grid
-            pw = (o & 1) ? cr.h : cr.w;
+            ph = PCB_PLACED_H(o, cr.h, cr.w);
+            pw = PCB_PLACED_W(o, cr.h, cr.w);
         }
         // update_grid: rows x..x+ph-1, columns y..y+pw-1
         for (int r = x + lane; r < x + ph && r < H; r += NT) {
-            for (int w = 0; w < WW; w++) {
-                const int lo = max(y, 64 * w) - 64 * w, hi = min(y + pw, 64 * w + 64) - 64 * w;  // bit range in word w
-                if (hi > lo) l.occ[r * WW + w] |= ((hi - lo) >= 64 ? ~0ull : ((1ull << (hi - lo)) - 1ull)) << lo;
-            }
+            PCB_OCCUPY_ROW(l.occ, r * WW, WW, y, pw)
         }
         if (KIND != PCBENV_SQUARE) {
             if (lane == 0) { l.comps[cur].px = (signed char)x; l.comps[cur].py = (signed char)y; l.comps[cur].o = (unsigned char)o; }
@@ -86,17 +96,13 @@ static __device__ __forceinline__ void transition(const DevParams &p, Lds &l, in
                 for (int q = lane; q < npins; q += NT) {  // S:149-190 place_component
                     PinRec pr = l.pins[q];
                     if (pr.comp != cur) continue;
-                    const int rx = pr.rel_x, ry = pr.rel_y;
-                    if (o == 1) { pr.rel_x = ry; pr.rel_y = ch - rx - 1; }
-                    else if (o == 2) { pr.rel_x = ch - rx - 1; pr.rel_y = cw - ry - 1; }
-                    else if (o == 3) { pr.rel_x = cw - ry - 1; pr.rel_y = rx; }
-                    pr.abs_x = (signed char)(x + pr.rel_x); pr.abs_y = (signed char)(y + pr.rel_y);
+                    PCB_PLACE_PIN(pr, o, ch, cw, x, y)
                     l.pins[q] = pr;
                     if (!full && obs) write_pin_num<KIND>(p, row, pr);
                 }
             }
             if (lane == 0) {
-                const int next = cur + 1 < ncomp ? cur + 1 : -1;
+                const int next = next_component(cur, ncomp);
                 if (!full && obs) {
                     if (p.buf.all_components_feature) {
                         double *cf = p.buf.all_components_feature + ((size_t)row * p.C + cur) * p.F;
@@ -148,7 +154,7 @@ static __device__ __forceinline__ void transition(const DevParams &p, Lds &l, in
             if (KIND == PCBENV_SPATIAL && !skip_emit) emit_pin_grid<WW>(p, l, row, lane, r0, r1);
             STAMP(4);
             if (late) emit_slot_features();
-            done = KIND == PCBENV_SQUARE ? !any : (l.hdr->cur < 0 || !any);  // S:1856-1869
+            done = episode_done<KIND>(l.hdr->cur, any);
         }  // (a reward helper: the last component has just been placed -- that is what being listed is conditional on)
     } else if (!valid && TRAJ && full && !auto_reset && obs) {  // a fresh slot: the unchanged observation has to be written out all the same
         if (KIND == PCBENV_SPATIAL) build_pin_tables(p, l, lane);
@@ -252,23 +258,14 @@ static __device__ __forceinline__ void run_env(const DevParams &p_launch, unsign
                 o = (int)(pa & 0xFFu); x = (int)((pa >> 8) & 0xFFu); y = (int)((pa >> 16) & 0xFFu);  // drawn by the previous launch
                 STAMP(21);
             } else {
-                if (lane < WAVE) {  // wavefront 0 draws (the result is wave-uniform), the others take it from LDS
-                    sample_action(l.vm, p, genv, lane, seed, step_index + (u64)t, &o, &x, &y);
-                    if (NT > WAVE && lane == 0) { l.hdr->pad[0] = (unsigned)o; l.hdr->pad[1] = (unsigned)x; l.hdr->flag = (unsigned)y; }
-                }
-                if (NT > WAVE) {
-                    lds_sync();
-                    o = (int)l.hdr->pad[0]; x = (int)l.hdr->pad[1]; y = (int)l.hdr->flag;
-                }
+                draw_action(p, l, genv, lane, seed, step_index + (u64)t, &o, &x, &y);
             }
             if (lane == 0 && role == ROLE_ENV) {
-                if (fmt == PCBENV_ACTION_FLAT) act[e] = o * HW + x * W + y;
+                if (fmt == PCBENV_ACTION_FLAT) act[e] = PCB_FLATTEN_ACTION(o, x, y, HW, W);
                 else { act[3 * e] = o; act[3 * e + 1] = x; act[3 * e + 2] = y; }
             }
         } else if (fmt == PCBENV_ACTION_FLAT) {  // utils/environment/env_wrappers.py:80-98, :184-199
-            const int a = act[e];
-            if (a < 0 || a >= p.O * HW) { o = -1; x = y = 0; }
-            else { o = a / HW; const int r = a - o * HW; x = r / W; y = r - x * W; }
+            unflatten_action(act[e], p.O, HW, W, &o, &x, &y);
         } else {
             o = act[3 * e]; x = act[3 * e + 1]; y = act[3 * e + 2];
             if (KIND == PCBENV_SQUARE) o = 0;

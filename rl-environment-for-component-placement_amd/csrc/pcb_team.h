@@ -16,6 +16,7 @@
 #include "pcb_env_lds.h"   // Lds, carve, out_row, pin tables, InstRegs
 #include "pcb_routing.h"   // norm2, candidate test, beam search of one net (with pcb_geometry.h, pcb_setmodel.h)
 #include "pcb_sampler.h"   // uniform legal-action draw
+#include "pcb_transition.h"  // action code, validity, extent and row fill, pin rotation, cursor and done: the scalar core
 
 #define NT TN  // inside Team<TN> only (undefined again below)
 template <int TN> struct Team {

@@ -246,7 +246,7 @@ def reset_paths(L, row, first, npins):
 
 def whole_paths(L, row):
     """Every tensor of output row `row` from the state in LDS: k_gather (csrc/pcb_kernels.h:62-70) and the step of the
-    trajectory layout that cannot copy from the cache (csrc/pcb_step.h:140-142, :154-158)."""
+    trajectory layout that cannot copy from the cache (csrc/pcb_step.h:146-148, :160-164)."""
     out = plane_paths(L, row, 0, L.H, False) | feature_paths(L, True)
     if L.kind == KIND_SPATIAL:
         out |= component_grid_paths(L, row, "tables") | pin_grid_paths(L, row, 0, L.H)
@@ -302,20 +302,20 @@ def paths(cfg, layout, placement):
             for e in range(L.B):
                 row = s * L.B + e
                 valid, last = ev["valid"][e], ev["placed_all"][e]
-                if valid and not (L.auto_reset and last and L.kind != KIND_SQUARE):      # csrc/pcb_step.h:66, :122 skip_emit
-                    r0, r1 = ev["range"][e] if L.inc else (0, L.H)                       # :121
+                if valid and not (L.auto_reset and last and L.kind != KIND_SQUARE):      # csrc/pcb_step.h:79, :128 skip_emit
+                    r0, r1 = ev["range"][e] if L.inc else (0, L.H)                       # :127
                     out |= plane_paths(L, row, r0, r1, fixed)
                     if L.kind == KIND_SPATIAL:
-                        out |= pin_grid_paths(L, row, r0, r1)                            # :148
+                        out |= pin_grid_paths(L, row, r0, r1)                            # :154
                         if L.inc:
                             arms.setdefault((e, ev["episode"][e]), set()).add(pin_grid_out_arm(L, row, r0, r1) == "chunks")
-                    if L.S > 1:                                                          # :129 slot_features
+                    if L.S > 1:                                                          # :135 slot_features
                         out |= feature_paths(L, True)
-                        if L.kind == KIND_SPATIAL:                                       # :130 from_cache = feat_cache_valid
+                        if L.kind == KIND_SPATIAL:                                       # :136 from_cache = feat_cache_valid
                             out |= component_grid_paths(L, row, "cache" if L.compact else "tables")
-                elif not valid and L.S > 1 and not L.auto_reset:                         # :153 the unchanged observation, whole
+                elif not valid and L.S > 1 and not L.auto_reset:                         # :159 the unchanged observation, whole
                     out |= whole_paths(L, row)
-                if ev["done"][e] and L.auto_reset:                                       # :169 the reset in the launch
+                if ev["done"][e] and L.auto_reset:                                       # :175 the reset in the launch
                     out |= reset_paths(L, row, False, ev["npins_next"][e])
                 if ev["worst"][e]:
                     out.add("cond:worst-case-terminal")
