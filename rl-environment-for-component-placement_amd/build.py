@@ -3,7 +3,8 @@
 
 hipcc cross-compiles without a GPU.  -ffp-contract=off: one IEEE operation per written operator (the reward path
 must match the reference bit for bit).  The kernels of the four environment kinds are separate translation units
-(csrc/pcb_kind_*.hip) compiled in parallel, as are those of pcbenv_playout (csrc/pcb_playout_*.hip) and pcbenv_playout_paths (csrc/pcb_playout_paths_*.hip), then linked with the host side -- the C ABI
+compiled in parallel -- csrc/pcb_kind.inc, and csrc/pcb_playout.inc for pcbenv_playout and pcbenv_playout_paths, each
+compiled once per row of UNITS below with that row's -D flags -- then linked with the host side -- the C ABI
 (csrc/pcbenv_api.hip), the layout derivation (csrc/pcb_config.hip) and the on-device instance generator with its kernels
 (csrc/pcb_gen.hip), which share csrc/pcb_host.h -- the two kernels every kind uses (csrc/pcb_sample.hip) and the host
 instance generator (csrc/instance_gen.cpp).  csrc/pcb_layout.h is the layout contract both sides compile.
@@ -16,13 +17,27 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
-UNITS = (["pcb_kind_square.hip", "pcb_kind_rect.hip"] + [f"pcb_kind_{k}_{p}.hip" for p in (2, 3, 0, 4, 1) for k in ("spatial", "pin")]  # slowest first
-         + [f"pcb_playout_{k}_{p}.hip" for p in (2, 1, 0) for k in ("spatial", "pin")] + ["pcb_playout_rect.hip", "pcb_playout_square.hip"]
-         + [f"pcb_playout_paths_{k}_{p}.hip" for p in (2, 1, 0) for k in ("spatial", "pin")] + ["pcb_playout_paths_rect.hip", "pcb_playout_paths_square.hip"]
-         + ["pcb_policy.hip", "pcb_policy_eval.hip", "pcb_policy_axis.hip", "pcb_gen.hip", "pcb_sample.hip", "pcbenv_api.hip", "pcb_config.hip", "instance_gen.cpp"])
-SRC = [os.path.join(CSRC, u) for u in UNITS]
-DEPS = SRC + [os.path.join(REPO, "include", "pcbenv.h")] + sorted(
-    os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc")))
+
+
+def unit(stem, source, kind, part=None, paths=False):
+    """One row of UNITS: csrc/<source> compiled for one kind, part (pin kinds) and kernel family into <stem>_<kind>[_<part>].hip.o."""
+    defs = [f"-DPCB_KIND=PCBENV_{kind.upper()}", f"-DPCB_KIND_NAME={kind}"] + ([f"-DPCB_PART={part}"] if part is not None else [])
+    return (f"{stem}_{kind}" + (f"_{part}" if part is not None else "") + ".hip.o", source, ["-x", "hip"] + defs + (["-DPCB_PATHS=1"] if paths else []))
+
+
+# The table of translation units: (object, source, flags of its own), slowest first.  What a part of a pin kind compiles
+# is not said here: pcb_layout::step_build_part / playout_build_part (csrc/pcb_layout.h) decide it inside the source.
+PIN_KINDS, FLAT_KINDS = ("spatial", "pin"), ("rect", "square")
+UNITS = ([unit("pcb_kind", "pcb_kind.inc", k) for k in FLAT_KINDS[::-1]]
+         + [unit("pcb_kind", "pcb_kind.inc", k, p) for p in (2, 3, 0, 4, 1) for k in PIN_KINDS]
+         + [unit("pcb_playout", "pcb_playout.inc", k, p) for p in (2, 1, 0) for k in PIN_KINDS]
+         + [unit("pcb_playout", "pcb_playout.inc", k) for k in FLAT_KINDS]
+         + [unit("pcb_playout_paths", "pcb_playout.inc", k, p, paths=True) for p in (2, 1, 0) for k in PIN_KINDS]
+         + [unit("pcb_playout_paths", "pcb_playout.inc", k, paths=True) for k in FLAT_KINDS]
+         + [(u + ".o", u, []) for u in ("pcb_policy.hip", "pcb_policy_eval.hip", "pcb_policy_axis.hip", "pcb_gen.hip", "pcb_sample.hip",
+                                        "pcbenv_api.hip", "pcb_config.hip", "instance_gen.cpp")])
+DEPS = [os.path.join(REPO, "include", "pcbenv.h")] + sorted(
+    os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc", ".hip", ".cpp")))
 OUT = os.path.join(HERE, "libpcbenv.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17", "-Wno-unused-value", "-pthread"]
 
@@ -42,17 +57,17 @@ def build(force: bool = False, verbose: bool = False, out: str = OUT, extra_flag
     os.makedirs(objdir, exist_ok=True)
     cc, inc = hipcc(), ["-I", os.path.join(REPO, "include"), "-I", CSRC]
 
-    def compile_one(src):
-        obj = os.path.join(objdir, os.path.basename(src) + ".o")
-        cmd = [cc] + FLAGS + list(extra_flags) + inc + ["-c", src, "-o", obj]
+    def compile_one(unit):
+        obj = os.path.join(objdir, unit[0])
+        cmd = [cc] + FLAGS + list(extra_flags) + inc + unit[2] + ["-c", os.path.join(CSRC, unit[1]), "-o", obj]
         import time
         t0 = time.time()
         subprocess.check_call(cmd)
         if verbose:
-            print(f"{time.time() - t0:6.1f} s  " + " ".join(cmd[-4:]), flush=True)
+            print(f"{time.time() - t0:6.1f} s  " + " ".join(cmd[len(FLAGS) + len(extra_flags) + len(inc) + 1:]), flush=True)
         return obj
-    with ThreadPoolExecutor(max_workers=jobs or min(len(SRC), os.cpu_count() or 1, 8)) as ex:
-        objs = list(ex.map(compile_one, SRC))
+    with ThreadPoolExecutor(max_workers=jobs or min(len(UNITS), os.cpu_count() or 1, 8)) as ex:
+        objs = list(ex.map(compile_one, UNITS))
     cmd = [cc, "--offload-arch=gfx950", "-shared", "-fPIC", "-pthread", "-o", out] + objs
     if verbose:
         print(" ".join(cmd), flush=True)

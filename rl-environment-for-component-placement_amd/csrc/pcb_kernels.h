@@ -92,21 +92,15 @@ __global__ __launch_bounds__(64 * NW) void k_gather(DevParams p, GatherArgs g) {
 // Four wavefronts per SIMD (16 one-wavefront workgroups per CU) is all a launch of up to ~4 workgroups per SIMD needs and
 // what LDS allows anyway; holding the lean build to 72 VGPRs for 7 wavefronts (spills inside the routing reward and one
 // at entry) measured 2-5 % slower at every batch size, so both builds may use up to 128.
-// BUILD: what is a compile-time fact of the launch.  STEP_BUILD_INPLACE / _INPLACE_STREAM: the in-place layout, one
+// BUILD (pcb_layout.h STEP_BUILD_*, chosen by pcb_layout::select_step_build): what is a compile-time fact of the launch.  STEP_BUILD_INPLACE / _INPLACE_STREAM: the in-place layout, one
 // transition, write-through / streaming stores (the lean build: no step loop, no whole-tensor feature emission);
 // STEP_BUILD_SLOT: the trajectory layout, one transition per launch (what a PPO collect runs: whole-tensor emission, no
 // loop -- 80 VGPRs and 140 spilled scalars against the rollout build's 125 and 800, c4 68 instead of 80 us per step);
 // STEP_BUILD_ROLLOUT: the trajectory layout and num_steps transitions per launch (the persistent rollout).
-#define STEP_BUILD_INPLACE 0
-#define STEP_BUILD_INPLACE_STREAM 1
-#define STEP_BUILD_SLOT 2
-#define STEP_BUILD_ROLLOUT 3
 // GEO: the grid shape as a compile-time fact of the launch.  STEP_GEO_RUNTIME: H, W, O come with the parameter block;
 // STEP_GEO_64: the 64 x 64 grid of a pin kind (pcb_layout::fixed_geometry), for launches pcb_layout::fixed_geometry_applies
-// admits -- the in-place builds on one wavefront without routes only (pcb_kind_*_4.hip).  The routed, slot and rollout
+// admits -- the in-place builds on one wavefront without routes only (part 4 of pcb_layout::step_build_part).  The routed, slot and rollout
 // builds, k_reset and k_gather keep the run-time geometry: none of them is on the path of a step of the lock-step loop.
-#define STEP_GEO_RUNTIME 0
-#define STEP_GEO_64 1
 template <int KIND, int WW, int NW, bool ROUTES, int BUILD, int GEO = STEP_GEO_RUNTIME>
 __global__ __attribute__((amdgpu_waves_per_eu(4, 8))) __launch_bounds__(64 * NW) void k_step(DevParams p, int *__restrict__ actions, int fmt, int sampled,
                                                u64 seed, u64 first_env, u64 step_index, int num_steps_) {

@@ -1,6 +1,7 @@
-// pcb_launch.h -- what the host side (pcbenv_api.hip) and the kernel translation units (pcb_kind_*.hip, pcb_sample.hip,
-// pcb_policy*.hip) share: one launch entry per kernel family and environment kind, so that the host side compiles no
-// device code and the kernel instantiations of the four kinds compile in parallel.
+// pcb_launch.h -- what the host side (pcbenv_api.hip) and the kernel translation units (pcb_kind.inc and pcb_playout.inc,
+// once per unit of build.py's table; pcb_sample.hip, pcb_policy*.hip) share: one launch entry per kernel family and
+// environment kind, so that the host side compiles no device code and the kernel instantiations of the four kinds compile
+// in parallel.  Which instantiation an entry launches is pcb_layout::select_step_build / select_playout_build.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,11 +14,11 @@ struct StepLaunch {
     u64 seed, first_env, step_index;
     int num_steps;
     int threads;        // threads per environment of the plain kernels (64 / 256)
-    bool routes, traj;  // beam / both routes compiled in; trajectory layout or persistent rollout
+    bool routes;        // pcb_layout::routes_compiled_in
     bool cells_aligned16, fixed_geometry;  // of the binding / PCBENV_OPT_FIXED_GEOMETRY: pcb_layout::StepShape, step_shape() below
     hipStream_t stream;
 };
-// what pcb_layout::fixed_geometry_applies is asked about a launch
+// what pcb_layout::select_step_build is asked about a launch (besides d.stream_stores)
 static inline pcb_layout::StepShape step_shape(const StepLaunch &a) {
     const DevParams &d = a.d;
     return pcb_layout::StepShape{d.kind, d.H, d.W, d.O, d.WW, a.threads, d.num_slots, a.num_steps, a.routes, a.cells_aligned16, a.fixed_geometry};
@@ -36,7 +37,7 @@ struct GatherArgs {
 };
 struct GatherLaunch { DevParams d; GatherArgs g; int threads; hipStream_t stream; };
 
-// pcbenv_playout and pcbenv_playout_paths (pcb_playout_*.hip, pcb_playout_paths_*.hip): d is the root handle's parameter block with d.state = the current state set,
+// pcbenv_playout and pcbenv_playout_paths (pcb_playout.inc; paths says which): d is the root handle's parameter block with d.state = the current state set,
 // buf.reward / buf.info repointed at the playout's rows and everything else a playout must not touch taken out (every
 // other tensor null, flags 0, no terminal list); the rest travels in PlayoutArgs.
 struct PlayoutArgs {
@@ -56,7 +57,7 @@ struct PlayoutArgs {
     u64 *leaf_mask;            // [n, 2, H, WW], may be null
     int path_steps;
 };
-struct PlayoutLaunch { DevParams d; PlayoutArgs g; int threads; bool routes; hipStream_t stream; };
+struct PlayoutLaunch { DevParams d; PlayoutArgs g; int threads; bool routes, paths; hipStream_t stream; };
 
 // pcbenv_sample_actions and pcbenv_queue_cursors (pcb_sample.hip): d.state = the current state set; out = two words, min and max
 struct SampleLaunch { DevParams d; int *actions; int fmt; u64 seed, first_env, step_index; hipStream_t stream; };
@@ -132,6 +133,5 @@ int pcb_launch_evaluate_axis(const EvalAxisLaunch &a);
 int pcb_launch_evaluate_axis_backward(const EvalAxisBackwardLaunch &a);
 
 #define PCB_DECLARE_KIND(name) int pcb_launch_step_##name(const StepLaunch &a); int pcb_launch_reset_##name(const ResetLaunch &a); \
-    int pcb_launch_gather_##name(const GatherLaunch &a); int pcb_launch_playout_##name(const PlayoutLaunch &a); \
-    int pcb_launch_playout_paths_##name(const PlayoutLaunch &a);
+    int pcb_launch_gather_##name(const GatherLaunch &a); int pcb_launch_playout_##name(const PlayoutLaunch &a);
 PCB_DECLARE_KIND(square) PCB_DECLARE_KIND(rect) PCB_DECLARE_KIND(pin) PCB_DECLARE_KIND(spatial)

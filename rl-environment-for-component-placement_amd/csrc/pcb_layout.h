@@ -61,6 +61,9 @@ PCB_HD constexpr int imax(int a, int b) { return a > b ? a : b; }
 PCB_HD constexpr bool is_pin_kind(int k) { return k == PCBENV_PIN || k == PCBENV_SPATIAL; }
 // threads per environment (64 / 256) -> wavefronts of a team: Team<64 * NW>
 PCB_HD constexpr int wavefronts(int threads) { return threads / WAVE; }
+// Whether the kernels of a handle have the beam / both routes of the terminal reward compiled in (ROUTES of k_step and
+// k_playout) and its LDS holds the beam search's scratch.
+PCB_HD constexpr bool routes_compiled_in(int kind, int reward_type) { return is_pin_kind(kind) && reward_type != PCBENV_REWARD_CENTROID; }
 
 // Whether window_mask (pcb_team_io.h) folds its rows across the lanes of a one-wavefront team, one row per lane, and
 // never touches hf -- `threads` is the team size, NT in the kernels -- or stages the folded rows in LDS at hf.
@@ -110,7 +113,7 @@ struct Layout {
     int ldsBytes;
 };
 PCB_HD constexpr int beam_bytes(const Geometry &g) {
-    return is_pin_kind(g.kind) && g.reward_type != PCBENV_REWARD_CENTROID ? BEAM_LDS_BYTES(g.N, g.beam_width) : 0;
+    return routes_compiled_in(g.kind, g.reward_type) ? BEAM_LDS_BYTES(g.N, g.beam_width) : 0;
 }
 PCB_HD constexpr int seg_bytes(const Geometry &g) {
     return is_pin_kind(g.kind) ? SEG_LDS_BYTES(g.P, g.N, wavefronts(g.threads), beam_bytes(g)) : 0;
@@ -153,7 +156,7 @@ struct StepShape {
     int kind, H, W, O, WW, threads, num_slots, num_steps;
     bool routes, cells_aligned16, enabled;
 };
-// The one predicate that says when the fixed build applies (the launch switch of pcb_kind.inc uses nothing else): a
+// The one predicate that says when the fixed build applies (select_step_build below uses nothing else): a
 // pin kind without routes on the 64 x 64 grid, one wavefront per environment, in-place layout, one transition per launch.
 PCB_HD constexpr bool fixed_geometry_applies(const StepShape &s) {
     return s.enabled && is_pin_kind(s.kind) && !s.routes && s.H == FIXED_GEO_SIDE && s.W == FIXED_GEO_SIDE &&
@@ -161,5 +164,72 @@ PCB_HD constexpr bool fixed_geometry_applies(const StepShape &s) {
            s.cells_aligned16;
 }
 PCB_HD inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }  // (a null pointer -- tensor not bound -- is)
+
+// ---- which instantiation of k_step / k_playout a launch runs, and which translation unit compiles it -----------------
+// BUILD of k_step (pcb_kernels.h has what each compiles in): the in-place layout with write-through / streaming stores,
+// one transition into a trajectory slot, the persistent rollout; GEO: the grid shape at run time / the 64 x 64 constants.
+#define STEP_BUILD_INPLACE 0
+#define STEP_BUILD_INPLACE_STREAM 1
+#define STEP_BUILD_SLOT 2
+#define STEP_BUILD_ROLLOUT 3
+#define STEP_GEO_RUNTIME 0
+#define STEP_GEO_64 1
+#define BUILD_PART_NONE (-1)  // no unit compiles that combination: it does not exist
+// The template arguments of k_step<KIND, ww, nw, routes, build, geo> and of k_playout<KIND, ww, nw, routes, paths>.
+struct StepBuild { int ww, nw; bool routes; int build, geo; };
+struct PlayoutBuild { int ww, nw; bool routes, paths; };
+// The candidates, numbered: pcb_kind.inc / pcb_playout.inc walk them and compile those their unit owns.
+#define STEP_BUILDS 64
+#define PLAYOUT_BUILDS 16
+PCB_HD constexpr StepBuild step_build_at(int i) { return StepBuild{1 + (i & 1), (i >> 1 & 1) ? 4 : 1, (i >> 2 & 1) != 0, i >> 3 & 3, i >> 5 & 1}; }
+PCB_HD constexpr PlayoutBuild playout_build_at(int i) { return PlayoutBuild{1 + (i & 1), (i >> 1 & 1) ? 4 : 1, (i >> 2 & 1) != 0, (i >> 3 & 1) != 0}; }
+PCB_HD constexpr int build_index(const StepBuild &b) { return (b.ww - 1) | (b.nw == 4) << 1 | (int)b.routes << 2 | b.build << 3 | b.geo << 5; }
+PCB_HD constexpr int build_index(const PlayoutBuild &b) { return (b.ww - 1) | (b.nw == 4) << 1 | (int)b.routes << 2 | (int)b.paths << 3; }
+
+// The build of a step launch; stream_stores is the launch's store policy (DevParams::stream_stores).  A launch is of the
+// trajectory layout if it writes one of several slots or makes several transitions.
+PCB_HD constexpr StepBuild select_step_build(const StepShape &s, bool stream_stores) {
+    const bool traj = s.num_slots > 1 || s.num_steps > 1;
+    return StepBuild{s.WW, wavefronts(s.threads), s.routes,
+                     traj ? (s.num_steps == 1 ? STEP_BUILD_SLOT : STEP_BUILD_ROLLOUT) : stream_stores ? STEP_BUILD_INPLACE_STREAM : STEP_BUILD_INPLACE,
+                     fixed_geometry_applies(s) ? STEP_GEO_64 : STEP_GEO_RUNTIME};
+}
+PCB_HD constexpr PlayoutBuild select_playout_build(int WW, int threads, bool routes, bool paths) {
+    return PlayoutBuild{WW, wavefronts(threads), routes, paths};
+}
+// The unit of build.py's table that compiles a build.  k_step of a pin kind: 4 = the 64 x 64 grid compiled in, 2 / 3 =
+// with routes on one / four wavefronts, 1 = without routes into a trajectory slot, 0 = everything else, next to k_reset,
+// k_gather and the entry points (pcb_kind.inc says why the slot build is on its own); k_playout of a pin kind, PATHS or
+// not: 0 = without routes, 1 / 2 = with routes on one / four wavefronts.  Square and rect have no routes and one unit.
+PCB_HD constexpr int step_build_part(int kind, const StepBuild &b) {
+    if (b.geo == STEP_GEO_64)
+        return is_pin_kind(kind) && !b.routes && b.ww == 1 && b.nw == 1 && b.build <= STEP_BUILD_INPLACE_STREAM ? 4 : BUILD_PART_NONE;
+    if (b.routes) return is_pin_kind(kind) ? (b.nw == 1 ? 2 : 3) : BUILD_PART_NONE;
+    return is_pin_kind(kind) && b.build == STEP_BUILD_SLOT ? 1 : 0;
+}
+PCB_HD constexpr int playout_build_part(int kind, const PlayoutBuild &b) {
+    if (b.routes) return is_pin_kind(kind) ? (b.nw == 1 ? 1 : 2) : BUILD_PART_NONE;
+    return 0;
+}
+// Every launch of a handle that pcbenv_create admits has a unit, and c3 / c4 in place on one wavefront run the fixed build.
+PCB_HD constexpr bool every_launch_has_a_unit() {
+    for (int i = 0; i < 4 * 2 * 2 * 2 * 2 * 2 * 2 * 2 * 2; i++) {
+        const int kind = i & 3, WW = 1 + (i >> 2 & 1), side = (i >> 3 & 1) ? FIXED_GEO_SIDE : 40, threads = (i >> 4 & 1) ? MAX_NT : WAVE;
+        const bool routes = routes_compiled_in(kind, (i >> 5 & 1) ? PCBENV_REWARD_BOTH : PCBENV_REWARD_CENTROID);
+        const StepShape s{kind, side, side * WW, is_pin_kind(kind) ? FIXED_GEO_ORIENTATIONS : 2, WW, threads, 1 + (i >> 6 & 1), 1 + 2 * (i >> 7 & 1), routes, (i >> 8 & 1) != 0, true};
+        for (int policy = 0; policy < 2; policy++) {
+            const StepBuild b = select_step_build(s, policy != 0);
+            if (step_build_part(kind, b) == BUILD_PART_NONE || build_index(step_build_at(build_index(b))) != build_index(b)) return false;
+        }
+        for (int paths = 0; paths < 2; paths++)
+            if (playout_build_part(kind, select_playout_build(WW, threads, routes, paths != 0)) == BUILD_PART_NONE) return false;
+    }
+    return true;
+}
+static_assert(every_launch_has_a_unit(), "select_step_build / select_playout_build give a build no unit compiles");
+static_assert(select_step_build(StepShape{PCBENV_PIN, 64, 64, 4, 1, WAVE, 1, 1, false, true, true}, false).geo == STEP_GEO_64 &&
+              select_step_build(StepShape{PCBENV_SPATIAL, 64, 64, 4, 1, WAVE, 1, 1, false, true, true}, true).geo == STEP_GEO_64 &&
+              step_build_part(PCBENV_SPATIAL, select_step_build(StepShape{PCBENV_SPATIAL, 64, 64, 4, 1, WAVE, 1, 1, false, true, true}, true)) == 4,
+              "c3 / c4 on one wavefront in place run the geometry-fixed build");
 
 }  // namespace pcb_layout

@@ -1,6 +1,6 @@
 // pcbenv_api.hip -- host side of libpcbenv.so's C ABI (include/pcbenv.h): create / destroy / options / bind / load,
 // reset / step / rollout / sample, checkpoint, gather, playout and the logits entry points.  No kernel is defined here: the
-// environment kernels are instantiated per kind in pcb_kind_*.hip, k_sample and k_cursor_range in pcb_sample.hip and the
+// environment kernels are instantiated per kind in pcb_kind.inc / pcb_playout.inc, k_sample and k_cursor_range in pcb_sample.hip and the
 // policy kernels in pcb_policy*.hip (all reached through pcb_launch.h); pcb_config.hip derives the layout from a
 // configuration and pcb_gen.hip owns the on-device instance generator (pcb_host.h declares what the three share).
 #include <stdlib.h>
@@ -22,15 +22,14 @@ extern "C" int pcbenv_abi_version(void) { return PCBENV_ABI_VERSION; }
 
 extern "C" const char *pcbenv_last_error(const pcbenv *env) { return env ? env->err : g_err; }
 
-// The launch functions of an environment kind (pcb_kind_*.hip), indexed by pcbenv_config::kind.
+// The launch functions of an environment kind (pcb_kind.inc, pcb_playout.inc), indexed by pcbenv_config::kind.
 struct KindLaunch {
     int (*step)(const StepLaunch &);
     int (*reset)(const ResetLaunch &);
     int (*gather)(const GatherLaunch &);
     int (*playout)(const PlayoutLaunch &);
-    int (*playout_paths)(const PlayoutLaunch &);
 };
-#define PCB_KIND_LAUNCH(name) {pcb_launch_step_##name, pcb_launch_reset_##name, pcb_launch_gather_##name, pcb_launch_playout_##name, pcb_launch_playout_paths_##name}
+#define PCB_KIND_LAUNCH(name) {pcb_launch_step_##name, pcb_launch_reset_##name, pcb_launch_gather_##name, pcb_launch_playout_##name}
 static const KindLaunch kind_launch[] = {PCB_KIND_LAUNCH(square), PCB_KIND_LAUNCH(rect), PCB_KIND_LAUNCH(pin), PCB_KIND_LAUNCH(spatial)};
 static_assert(PCBENV_SQUARE == 0 && PCBENV_RECT == 1 && PCBENV_PIN == 2 && PCBENV_SPATIAL == 3, "kind_launch is indexed by kind");
 
@@ -257,14 +256,12 @@ static int dispatch_step(pcbenv *env, int *actions, int fmt, int sampled, u64 se
     DevParams &d = a.d;
     a.actions = actions; a.fmt = fmt; a.sampled = sampled; a.seed = seed; a.first_env = first_env; a.step_index = step_index;
     a.num_steps = num_steps; a.threads = env->threads; a.stream = s;
-    // in-place build (one transition, store policy compiled in) or the trajectory layout's: one transition into a slot / the rollout loop
-    a.traj = d.num_slots > 1 || num_steps > 1;
     // The trajectory layout cycles through num_slots slots: the store policy is chosen on the bytes of all of them (a slot is
     // next written num_slots steps later; one launch per step into a [17, B, ...] trajectory measured + 14 % at c3, + 3 % at
     // c4 with streaming stores).  In place, the steps overwrite the same lines and the per-transition choice of
     // pcbenv_create stands.
-    if (a.traj && d.num_slots > 1) d.stream_stores = stream_stores(env, d.num_slots);
-    a.routes = is_pin_kind(env->cfg.kind) && env->cfg.reward_type != PCBENV_REWARD_CENTROID;
+    if (d.num_slots > 1) d.stream_stores = stream_stores(env, d.num_slots);
+    a.routes = pcb_layout::routes_compiled_in(env->cfg.kind, env->cfg.reward_type);
     a.cells_aligned16 = env->cells_aligned16; a.fixed_geometry = env->fixed_geometry;
     if (++env->seq == 0u) env->seq = 1u;  // 0 is "not listed" in the marks
     d.seq = env->seq;
@@ -531,11 +528,11 @@ static int playout_enqueue(pcbenv *env, int64_t num_playouts, PlayoutArgs g, voi
     d.seq = 0u; d.term_wgs = 0; d.term_cap = 0; d.term_hpe = 0; d.term_list = 0; d.term_cnt = 0; d.term_arrive = 0; d.term_seen = 0;
     d.state_out = 0; d.dbg = 0;
     a.threads = env->threads; a.stream = s;
-    a.routes = pins && env->cfg.reward_type != PCBENV_REWARD_CENTROID;
+    a.routes = pcb_layout::routes_compiled_in(env->cfg.kind, env->cfg.reward_type); a.paths = paths;
     g.n = (int)num_playouts; g.per_root = g.root_index ? 1 : (int)(num_playouts / d.B);
     if (!pins) g.info = 0;
     a.g = g;
-    if (paths) kind_launch[env->cfg.kind].playout_paths(a); else kind_launch[env->cfg.kind].playout(a);
+    kind_launch[env->cfg.kind].playout(a);
     HIP_TRY(env, hipGetLastError());
     return PCBENV_OK;
 }

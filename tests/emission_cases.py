@@ -110,34 +110,34 @@ class Layout:
         t = kw.get("threads_per_env", 0)                                                # csrc/pcb_config.hip:111-112
         self.threads = t if t in (64, 256) else (256 if self.H * self.W * (self.K + 5 if k == KIND_SPATIAL else 5) > 64 * 1024 else 64)
         self.NW = self.threads // 64
-        self.routes = pins and cfg.reward_type != "centroid"                            # csrc/pcbenv_api.hip:256
+        self.routes = pins and cfg.reward_type != "centroid"                            # pcb_layout::routes_compiled_in
         self.S = kw.get("num_slots", 1)
         self.inc, self.compact = bool(kw.get("incremental_obs")), bool(kw.get("compact_features"))
         self.auto_reset = bool(kw.get("auto_reset"))
         self.cg_total = self.C * self.mp * self.K
-        # csrc/pcb_config.hip:93, csrc/pcb_host.h:85, csrc/pcbenv_api.hip:255: the bytes of every slot against the threshold
+        # csrc/pcb_config.hip:93, csrc/pcb_host.h:85, dispatch_step (csrc/pcbenv_api.hip): the bytes of every slot against the threshold
         cells = self.H * self.W
         per_env = cells * self.O if self.inc else cells * (1 + self.O + (self.K if k == KIND_SPATIAL else 0))
         self.stream = per_env * B * self.S > (STREAM_THRESHOLD_DEFAULT if stream_threshold is None else stream_threshold)
-        self.cells_aligned16 = all(self.offsets.get(n, 0) % 16 == 0 for n in ("grid", "action_mask", "pin_grid"))  # csrc/pcbenv_api.hip:186
+        self.cells_aligned16 = all(self.offsets.get(n, 0) % 16 == 0 for n in ("grid", "action_mask", "pin_grid"))  # pcbenv_bind_buffers_slots
 
     def off(self, name):
         return self.offsets.get(name, 0)
 
 
 def fixed_geometry_applies(L, enabled=True, num_steps=1):
-    """csrc/pcb_layout.h:158 fixed_geometry_applies."""
+    """pcb_layout::fixed_geometry_applies (csrc/pcb_layout.h)."""
     return (enabled and L.kind in (KIND_PIN, KIND_SPATIAL) and not L.routes and L.H == 64 and L.W == 64 and L.O == 4 and L.WW == 1
             and L.threads // 64 == 1 and L.S == 1 and num_steps == 1 and L.cells_aligned16)
 
 
 def fold_across_lanes(WW, threads, H):
-    """csrc/pcb_layout.h:68 fold_across_lanes."""
+    """pcb_layout::fold_across_lanes (csrc/pcb_layout.h)."""
     return WW == 1 and threads == 64 and H <= 64
 
 
 def member_words(kind, C, mp):
-    """csrc/pcb_layout.h:79 member_words."""
+    """pcb_layout::member_words (csrc/pcb_layout.h)."""
     return (C * mp + 63) // 64 if kind == KIND_PIN else 0
 
 
@@ -253,15 +253,30 @@ def whole_paths(L, row):
     return out
 
 
-def step_build(L):
-    """The k_step instantiation of a one-transition launch: csrc/pcb_kind.inc:36-41, :70-119 -> (BUILD, fixed)."""
-    if L.S > 1:
-        return "slot", False
-    return ("inplace_stream" if L.stream else "inplace"), fixed_geometry_applies(L)
+STEP_BUILDS = ("inplace", "inplace_stream", "slot", "rollout")  # STEP_BUILD_* of csrc/pcb_layout.h, by value
+
+
+def step_build(L, num_steps=1, enabled=True):
+    """The k_step instantiation of a launch of num_steps transitions: pcb_layout::select_step_build (csrc/pcb_layout.h)
+    -> (WW, NW, routes, BUILD, fixed)."""
+    traj = L.S > 1 or num_steps > 1
+    build = ("slot" if num_steps == 1 else "rollout") if traj else ("inplace_stream" if L.stream else "inplace")
+    return L.WW, L.NW, L.routes, build, fixed_geometry_applies(L, enabled, num_steps)
+
+
+def step_build_part(kind, build):
+    """The translation unit that compiles a build: pcb_layout::step_build_part (csrc/pcb_layout.h); None = no unit does."""
+    WW, NW, routes, name, fixed = build
+    pins = kind in (KIND_PIN, KIND_SPATIAL)
+    if fixed:
+        return 4 if pins and not routes and WW == 1 and NW == 1 and name in ("inplace", "inplace_stream") else None
+    if routes:
+        return (2 if NW == 1 else 3) if pins else None
+    return 1 if pins and name == "slot" else 0
 
 
 def build_paths(L, name=""):
-    build, fixed = step_build(L)
+    build, fixed = step_build(L)[3:]
     kind = KIND_NAME[L.kind]
     out = {f"build:BUILD={build}", f"build:kind={kind}", f"build:WW={L.WW}", f"build:NW={L.NW}"}
     if L.kind in (KIND_PIN, KIND_SPATIAL):
@@ -277,7 +292,7 @@ def build_paths(L, name=""):
 
 def instantiation(L):
     """The kernel a step launch of this layout runs, by name."""
-    build, fixed = step_build(L)
+    build, fixed = step_build(L)[3:]
     return f"k_step<{KIND_NAME[L.kind]}, WW={L.WW}, NW={L.NW}, routes={int(L.routes)}, {build}{', geo64' if fixed else ''}>"
 
 
@@ -286,7 +301,7 @@ def paths(cfg, layout, placement):
     L = layout
     assert L.cfg == cfg
     out = build_paths(L)
-    fixed = step_build(L)[1]
+    fixed = step_build(L)[4]
     arms = {}  # (environment, episode) -> the pin_grid output arms of its incremental steps
     for ev in placement:
         s = ev["slot"]

@@ -1,7 +1,8 @@
 // emission_predicates.cpp -- the predicates of csrc/pcb_layout.h that tests/emission_cases.py restates in Python, evaluated
 // by the header itself (the only one included) for shapes read from standard input, one per line:
-//   kind H W O WW threads num_slots num_steps routes cells_aligned16 enabled C mp
-// and printed one line each: fixed_geometry_applies fold_across_lanes member_words.
+//   kind H W O WW threads num_slots num_steps routes cells_aligned16 enabled C mp stream_stores
+// and printed one line each: fixed_geometry_applies fold_across_lanes member_words, then the five fields of
+// select_step_build (ww nw routes build geo) and step_build_part of that build (-1 = no unit compiles it).
 // Build and run (tests/test_emission_cases.py does that):
 //   g++ -std=c++17 -fsanitize=address,undefined -Iinclude -Irl-environment-for-component-placement_amd/csrc
 //       -o emission_predicates tools/emission_predicates.cpp && ./emission_predicates < shapes.txt
@@ -12,10 +13,12 @@
 using namespace pcb_layout;
 
 int main() {
-    int kind, H, W, O, WW, threads, slots, steps, routes, aligned, enabled, C, mp, n = 0;
-    while (scanf("%d %d %d %d %d %d %d %d %d %d %d %d %d", &kind, &H, &W, &O, &WW, &threads, &slots, &steps, &routes, &aligned, &enabled, &C, &mp) == 13) {
+    int kind, H, W, O, WW, threads, slots, steps, routes, aligned, enabled, C, mp, stream, n = 0;
+    while (scanf("%d %d %d %d %d %d %d %d %d %d %d %d %d %d", &kind, &H, &W, &O, &WW, &threads, &slots, &steps, &routes, &aligned, &enabled, &C, &mp, &stream) == 14) {
         const StepShape s{kind, H, W, O, WW, threads, slots, steps, routes != 0, aligned != 0, enabled != 0};
-        printf("%d %d %d\n", fixed_geometry_applies(s) ? 1 : 0, fold_across_lanes(WW, threads, H) ? 1 : 0, member_words(kind, C, mp));
+        const StepBuild b = select_step_build(s, stream != 0);
+        printf("%d %d %d %d %d %d %d %d %d\n", fixed_geometry_applies(s) ? 1 : 0, fold_across_lanes(WW, threads, H) ? 1 : 0, member_words(kind, C, mp),
+               b.ww, b.nw, b.routes ? 1 : 0, b.build, b.geo, step_build_part(kind, b));
         n++;
     }
     fprintf(stderr, "emission_predicates ok: %d shapes\n", n);

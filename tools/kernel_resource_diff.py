@@ -4,9 +4,12 @@ python tools/kernel_resource_diff.py OLD_OBJDIR NEW_OBJDIR
 The object directories are what build.py leaves under build/<library name>/.  Per translation unit, the gfx950 code object
 is unbundled from the .hip_fatbin section of the unit's object file; a kernel's registers, spills, scratch and static LDS
 are its entry in the code object's metadata note -- the figures `-Rpass-analysis=kernel-resource-usage` prints, read per
-unit instead of from the interleaved output of a parallel build -- and its code size is the size of its symbol.  Prints
+unit instead of from the interleaved output of a parallel build -- its code size is the size of its symbol and its code
+digest a hash of that symbol's bytes in .text (the instructions themselves: two builds with equal digests run the same
+code, whatever else in the files differs).  Prints
 one line per (unit, kernel) that exists only in OLD or differs, the kernels only NEW has in full, and a summary; exit
 status 1 if anything of OLD's is missing or different."""
+import hashlib
 import os
 import re
 import subprocess
@@ -43,10 +46,17 @@ def kernels(objdir):
                     cur[m.group(1)] = m.group(2)
                 elif m.group(1) == ".name":
                     out[(unit, m.group(2))] = cur
+            text = re.search(r"\] \.text\s+PROGBITS\s+([0-9a-f]+) ([0-9a-f]+) ([0-9a-f]+)",
+                             subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "-SW", co], text=True))
+            addr, off = int(text.group(1), 16), int(text.group(2), 16)
+            image = open(co, "rb").read()
             for line in subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "-sW", co], text=True).splitlines():
                 p = line.split()
                 if len(p) >= 8 and p[3] == "FUNC" and p[6] != "UND" and (unit, p[7]) in out:
                     out[(unit, p[7])]["code_bytes"] = p[2]
+                    start = off + int(p[1], 16) - addr
+                    assert addr <= int(p[1], 16) and start + int(p[2]) <= off + int(text.group(3), 16), (unit, p[7])
+                    out[(unit, p[7])]["code_digest"] = hashlib.sha256(image[start:start + int(p[2])]).hexdigest()[:16]
     return out
 
 
@@ -59,7 +69,7 @@ def demangle(name):
 
 def main():
     old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
-    cols = FIELDS + ("code_bytes",)
+    cols = FIELDS + ("code_bytes", "code_digest")
     moved = 0
     for key in sorted(old):
         if key not in new:
