@@ -39,6 +39,44 @@ __device__ inline void store_agent(unsigned *p, unsigned v) { __hip_atomic_store
 #define STAMP_ROWS_BY_ENV(launch, e) const DevParams &p = (launch)
 #endif
 
+// ---- cold fields of the parameter block ----
+// PCB_COLD(p, field): a field of DevParams that only a terminal transition, the reset behind it or the terminal-list
+// bookkeeping reads (reward weights and norms, the instance queue, the generator's counters, the list's arrays).  Held
+// as a value from kernel entry, such a field occupies scalar registers through the whole plain transition, where the
+// compiler parks it in a vector lane on the way in (profiles/step_head.txt).  The geometry-fixed builds of k_step --
+// part 4 of pcb_layout::step_build_part, the only kernels of their units, with the block as first kernel argument at
+// offset 0 -- load it from the kernel-argument segment where it is used instead: the pointer goes through an empty
+// volatile asm, so the load can be neither merged with the entry loads nor hoisted out of the branch it stands in.
+// Every other unit reads the field of the block as before (same device code).
+#if defined(PCB_PART) && PCB_PART == 4
+#define PCB_GEO64_UNIT 1  // this unit compiles the geometry-fixed builds of k_step and nothing else
+template <class T> __device__ __forceinline__ T kernarg_field_at_use(unsigned offset) {
+    typedef const __attribute__((address_space(4))) unsigned char *kernarg_ptr;
+    kernarg_ptr k = (kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return *(const __attribute__((address_space(4))) T *)(k + offset);
+}
+// The kernel-argument segment of a launch is fresh memory: the first scalar load of each of its 64-byte lines misses
+// the scalar cache, and the compiler reloads fields where they are used, one line and one wait at a time, along the
+// head of a transition.  kernarg_warm() touches every line of the segment at kernel entry, all loads in flight
+// together behind one wait, so that the loads further down hit.  BYTES: the size of the segment.
+template <int BYTES> __device__ __forceinline__ void kernarg_warm() {
+    static_assert(BYTES > 0x200 + 4 && BYTES <= 0x240, "one load per 64-byte line of the segment, and its last word");
+    typedef const __attribute__((address_space(4))) unsigned char *kernarg_ptr;
+    kernarg_ptr k = (kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+    unsigned t0, t1, t2, t3, t4, t5, t6, t7, t8, t9;
+    asm volatile("s_load_dword %0, %10, 0x0\n\ts_load_dword %1, %10, 0x40\n\ts_load_dword %2, %10, 0x80\n\ts_load_dword %3, %10, 0xc0\n\t"
+                 "s_load_dword %4, %10, 0x100\n\ts_load_dword %5, %10, 0x140\n\ts_load_dword %6, %10, 0x180\n\ts_load_dword %7, %10, 0x1c0\n\t"
+                 "s_load_dword %8, %10, 0x200\n\ts_load_dword %9, %10, %11\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(t0), "=&s"(t1), "=&s"(t2), "=&s"(t3), "=&s"(t4), "=&s"(t5), "=&s"(t6), "=&s"(t7), "=&s"(t8), "=&s"(t9)
+                 : "s"(k), "n"((BYTES - 4) & ~3));
+}
+#define PCB_COLD(p, field) kernarg_field_at_use<std::remove_cv_t<std::remove_reference_t<decltype((p).field)>>>((unsigned)offsetof(DevParams, field))
+#else
+#define PCB_GEO64_UNIT 0
+#define PCB_COLD(p, field) ((p).field)
+#endif
+
 
 // ---- bit rows ----
 template <int WW> struct Row;

@@ -106,6 +106,10 @@ __global__ __attribute__((amdgpu_waves_per_eu(4, 8))) __launch_bounds__(64 * NW)
                                                u64 seed, u64 first_env, u64 step_index, int num_steps_) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr bool TRAJ = BUILD == STEP_BUILD_SLOT || BUILD == STEP_BUILD_ROLLOUT;
+#if PCB_GEO64_UNIT
+    // (the segment: the block, a multiple of 8 bytes, then actions .. num_steps_ without padding between them)
+    kernarg_warm<sizeof(DevParams) + sizeof(int *) + 2 * sizeof(int) + 3 * sizeof(u64) + sizeof(int)>();
+#endif
     if (!TRAJ) p.stream_stores = BUILD == STEP_BUILD_INPLACE_STREAM;  // the launch's choice as a compile-time constant: only one store policy is compiled in
     if (GEO == STEP_GEO_64) {  // likewise the geometry, before anything reads it: what the host put there are these very values
         static_assert(GEO == STEP_GEO_RUNTIME || (pcb_layout::is_pin_kind(KIND) && WW == 1 && NW == 1 && !ROUTES && !TRAJ), "pcb_layout::fixed_geometry_applies");

@@ -61,7 +61,12 @@ static __device__ inline bool mask_and_emit(const DevParams &p, Lds &l, int row,
     const int H = p.H, W = p.W, HW = H * W, plane = H * WW;
     const int cur = l.hdr->cur;
     unsigned char *m = (emit && p.buf.action_mask) ? p.buf.action_mask + (size_t)row * p.O * HW : 0;
-    if (emit && p.buf.grid) emit_plane<WW>(p.buf.grid + (size_t)row * HW, l.occ, gr0, gr1, W, lane, p.stream_stores);
+    if (emit && p.buf.grid) {
+        // Without PCBENV_FLAG_INCREMENTAL_OBS every caller's row range is the whole plane: the geometry-fixed build, where
+        // H * W is a constant, says so to emit_plane_, which then writes its trips out.  (Any other unit: the else is all there is.)
+        if (PCB_GEO64_UNIT && __builtin_constant_p(HW) && !(p.flags & PCBENV_FLAG_INCREMENTAL_OBS)) emit_plane<WW>(p.buf.grid + (size_t)row * HW, l.occ, 0, H, W, lane, p.stream_stores);
+        else emit_plane<WW>(p.buf.grid + (size_t)row * HW, l.occ, gr0, gr1, W, lane, p.stream_stores);
+    }
     bool any = false;
     if (KIND == PCBENV_SQUARE) {
         any = window_mask<WW>(l.occ, l.hf, l.vm, H, W, p.component_n, p.component_n, lane, &l.hdr->flag);
@@ -465,10 +470,13 @@ template <int KIND> static __device__ inline void emit_features_full(const DevPa
 template <int KIND, bool ROUTES>
 static __device__ __forceinline__ void terminal_reward(const DevParams &p, Lds &l, int row, int lane, int part, int nparts, unsigned pos) {
     const bool placed_all = l.hdr->cur < 0;
+    // (cold fields, pcb_device.h PCB_COLD: read here, where an episode ends, not carried from kernel entry)
+    const double w_wl = PCB_COLD(p, w_wl), w_int = PCB_COLD(p, w_int), wl_norm = PCB_COLD(p, wl_norm), int_norm = PCB_COLD(p, int_norm);
     double reward, wl, ni;
     if (!placed_all) {  // S:853-863 worst case: the upper bounds, normalised (spatial: twice, quirk Q3)
-        reward = -p.w_wl * (p.max_wl / p.wl_norm) - p.w_int * (p.max_int / p.int_norm);
-        wl = p.max_wl; ni = p.max_int;
+        const double max_wl = PCB_COLD(p, max_wl), max_int = PCB_COLD(p, max_int);
+        reward = -w_wl * (max_wl / wl_norm) - w_int * (max_int / int_norm);
+        wl = max_wl; ni = max_int;
     } else {
         double wsum[2] = {0.0, 0.0}; int cnt[2] = {0, 0};
         if (!ROUTES) route_centroid(p, l.hdr, l.pins, l.seg, lane, part, nparts, &wsum[0], &cnt[0]);
@@ -477,17 +485,18 @@ static __device__ __forceinline__ void terminal_reward(const DevParams &p, Lds &
             if (lane != 0) return;  // one lane carries the shares; nobody else writes anything below
             static_assert(REWARD_PARTS < 256 && PCBENV_MAX_PINS * (PCBENV_MAX_PINS - 1) / 2 < (1 << 28), "`mine`: 8 bits of arrivals, 28 bits per count of segment pairs");
             const u64 mine = 1ull | ((u64)(unsigned)cnt[0] << 8) | ((u64)(unsigned)cnt[1] << 36);
-            const u64 before = atomicAdd((unsigned long long *)(p.term_arrive + pos), (unsigned long long)mine);
+            u64 *arrive = PCB_COLD(p, term_arrive) + pos;
+            const u64 before = atomicAdd((unsigned long long *)arrive, (unsigned long long)mine);
             if ((int)(before & 0xFFull) != nparts - 1) return;  // not the last: the totals are somebody else's to write
             const u64 total = before + mine;
             cnt[0] = (int)((total >> 8) & 0xFFFFFFFull); cnt[1] = (int)(total >> 36);
-            __hip_atomic_store(p.term_arrive + pos, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(arrive, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         // S:609-627 lowest_num_intersections: ties keep the beam route (quirk Q9)
         const int pick = (ROUTES && p.reward_type == PCBENV_REWARD_BOTH && cnt[1] < cnt[0]) ? 1 : 0;
-        wl = wsum[pick] / p.wl_norm;
-        ni = (double)cnt[pick] / p.int_norm;
-        reward = -1 * (p.w_wl * wl + p.w_int * ni);
+        wl = wsum[pick] / wl_norm;
+        ni = (double)cnt[pick] / int_norm;
+        reward = -1 * (w_wl * wl + w_int * ni);
     }
     if (lane == 0) {
         p.buf.reward[row] = reward;

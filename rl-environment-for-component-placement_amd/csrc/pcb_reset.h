@@ -3,8 +3,9 @@
 // reset (R:310-351, P:1544-1597, S:1487-1549, Q:74-113): header is in LDS; builds the new episode's state in
 // LDS from the next queued instance and rewrites every observation tensor of environment e.
 static __device__ inline void fetch_instance(const DevParams &p, unsigned qcursor, int e, int lane, InstRegs &ir) {
-    const unsigned slot = qcursor % (unsigned)p.Q;
-    const unsigned char *rec = p.queue + ((size_t)slot * p.B + e) * p.instStride;
+    // (cold fields, pcb_device.h PCB_COLD: the queue is read at a reset only)
+    const unsigned slot = qcursor % (unsigned)PCB_COLD(p, Q);
+    const unsigned char *rec = PCB_COLD(p, queue) + ((size_t)slot * p.B + e) * PCB_COLD(p, instStride);
     const int *ih = (const int *)rec;
     const u64 *crec = (const u64 *)(rec + 16), *prec = crec + p.C;  // 8-byte records, one load each
     ir.nc = load_agent(ih); ir.nn = load_agent(ih + 1); ir.np = load_agent(ih + 2);
@@ -34,7 +35,8 @@ template <int KIND, int WW, bool TRAJ> static __device__ inline void reset_env(c
     InstRegs ir;
     if (KIND != PCBENV_SQUARE) {
         fetch_instance(p, l.hdr->qcursor, e, lane, ir);
-        if (owner && p.gen_produced && lane == 0 && load_agent(p.gen_produced + e) <= l.hdr->qcursor) atomicOr(p.gen_errors, 1u);
+        const unsigned *produced = PCB_COLD(p, gen_produced);
+        if (owner && produced && lane == 0 && load_agent(produced + e) <= l.hdr->qcursor) atomicOr(PCB_COLD(p, gen_errors), 1u);
     }
     bool rows_cleared = false;
     // (The last clause is always true: pcb_layout::member_words gives the pin kind a bit per row.  It stays, like the
@@ -101,7 +103,7 @@ template <int KIND, int WW, bool TRAJ> static __device__ inline void reset_env(c
         lds_sync();
         // The advanced cursor tells the generator that the record's slot may be overwritten: published only now that every
         // wavefront of the team has its part of the record (the loads were waited for before the LDS writes above).
-        if (owner && lane == 0) store_agent(p.cursor_pub + e, l.hdr->qcursor);
+        if (owner && lane == 0) store_agent(PCB_COLD(p, cursor_pub) + e, l.hdr->qcursor);
         if (KIND == PCBENV_PIN && lane < WAVE) {
             // quirk Q1: rows [component, pin_id] collide; the last writer in self.pins order wins.  Wavefront 0 keeps
             // the (component, pin_id) keys of its lanes' slots in registers and walks the pins with v_readlane:
@@ -184,6 +186,7 @@ template <int KIND, int WW, bool TRAJ> static __device__ inline void reset_env(c
             // all_components_feature (R:60-79, S:203-239): [h, w, -1, -1, area/(H*W), (spatial: pin ids, -1 pad)]; absent rows 0
             if (p.buf.all_components_feature) {
                 double *cf = p.buf.all_components_feature + (size_t)row * p.C * p.F;
+                const double area = PCB_COLD(p, area);
                 // one (component, field) element per lane and trip, the pair advanced without a division per element
                 int c = lane / p.F, k = lane - c * p.F;
                 const int dc = NT / p.F, dk = NT - dc * p.F;
@@ -192,7 +195,7 @@ template <int KIND, int WW, bool TRAJ> static __device__ inline void reset_env(c
                     if (c < nc) {
                         const CompRec cr = l.comps[c];
                         if (k == 0) v = cr.h; else if (k == 1) v = cr.w; else if (k == 2 || k == 3) v = -1.0;
-                        else if (k == 4) v = (double)(cr.h * cr.w) / p.area;
+                        else if (k == 4) v = (double)(cr.h * cr.w) / area;
                         else {
                             const unsigned id = KIND == PCBENV_SPATIAL ? t.pid[c * p.mp + k - 5] : 0xFFFFu;
                             v = id == 0xFFFFu ? -1.0 : (double)id;

@@ -291,10 +291,11 @@ static __device__ __forceinline__ void run_env(const DevParams &p_launch, unsign
             // together (episodes in lock-step) 4 096 returning atomic adds on one word took 37 us.
             const unsigned ring = (p.seq + 1u) & 3u, cps = (unsigned)p.term_cap / TERM_SHARDS;
             const unsigned shard = ((unsigned)e * 0x9E3779B1u) >> (32 - TERM_SHARD_BITS);
-            const unsigned idx = atomicAdd(p.term_cnt + (ring * TERM_SHARDS + shard) * TERM_CNT_STRIDE, 1u);
+            // (cold fields, pcb_device.h PCB_COLD: one launch per episode gets here)
+            const unsigned idx = atomicAdd(PCB_COLD(p, term_cnt) + (ring * TERM_SHARDS + shard) * TERM_CNT_STRIDE, 1u);
             if (idx < cps) {
                 const unsigned mpos = idx * TERM_SHARDS + shard;  // entries in the order their helpers are launched: the first of every shard first
-                p.term_list[ring * (unsigned)p.term_cap + mpos] = e;
+                PCB_COLD(p, term_list)[ring * (unsigned)p.term_cap + mpos] = e;
                 mark = ((u64)(p.seq + 1u) << 32) | mpos;
             }
         }

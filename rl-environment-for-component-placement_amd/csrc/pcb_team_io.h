@@ -33,6 +33,17 @@ template <int WW, bool STREAM> static __device__ inline void emit_plane_(unsigne
     if ((W & 15) == 0 && (((uintptr_t)dst) & 15) == 0) {
         const ObsDst d = obs_dst(dst, (long long)r1 * W);
         const int sh = (W & (W - 1)) == 0 ? __ffs(W) - 1 : -1;
+        // The geometry-fixed build, rows [0, H): the trips written out, as in emit_plane2_ below (which has the story).
+        // Any other unit (PCB_GEO64_UNIT, pcb_device.h), or a row range known only at run time: the loop is all there is.
+        if (PCB_GEO64_UNIT && __builtin_constant_p(r0) && __builtin_constant_p(r1 * W) && r0 == 0 && (r1 * W / 16) % NT == 0 && r1 * W / 16 / NT <= 8) {
+            PCB_UNROLL
+            for (int k = 0; k < r1 * W / 16 / NT; k++) {
+                const int cell = (lane + k * NT) * 16, r = sh >= 0 ? cell >> sh : cell / W, col = cell - r * W;
+                unsigned b = (unsigned)(bits[r * WW + (col >> 6)] >> (col & 63)) & 0xFFFFu;
+                STORE16<STREAM>(d, (unsigned)cell, expand16(b));
+            }
+            return;
+        }
         for (int c = r0 * W / 16 + lane; c < r1 * W / 16; c += NT) {
             int cell = c * 16, r = sh >= 0 ? cell >> sh : cell / W, col = cell - r * W;
             unsigned b = (unsigned)(bits[r * WW + (col >> 6)] >> (col & 63)) & 0xFFFFu;
