@@ -15,8 +15,9 @@
  * pcbenv_bind_buffers[_slots] take no stream and synchronise the whole device, before and after what they change on it;
  * the other options, pcbenv_bind_compact_features and pcbenv_select_slot change host-side fields only, which the next
  * call reads.  pcbenv_playout_paths takes its stream as a field of its request and only enqueues on it, exactly as
- * pcbenv_playout does.  A handle may be used from different streams as long as the caller orders the calls (an event recorded
- * behind one call and waited for by the stream of the next) and never makes two calls on one handle at the same time.
+ * pcbenv_playout does.  pcbenv_tree_advance likewise: it only enqueues one kernel on its request's stream.  A handle may
+ * be used from different streams as long as the caller orders the calls (an event recorded behind one call and waited
+ * for by the stream of the next) and never makes two calls on one handle at the same time.
  * Two handles share nothing on the device: they may run concurrently on two streams (pcbenv_gather between two handles
  * reads the source, whose last launch the caller orders before it).  pcbenv_last_error(env) is per handle;
  * pcbenv_last_error(NULL) is the message of the latest failure in the process.
@@ -64,6 +65,8 @@
  *   pcbenv_playout_paths   copy.deepcopy(env), env.step(a) for every action of the path, then the random policy's
  *                          simulate() loop on the copy: the evaluation of a tree node named by its path from the root
  *                            agent/random/random_policy_square.py:25-58 (and siblings)
+ *   pcbenv_tree_advance    no counterpart: the reference has no search.  The bookkeeping of a batched UCT around
+ *                          pcbenv_playout_paths (selection, expansion, backup), one launch for all roots
  *
  * Observations are written into caller-owned device buffers (pcbenv_buffers)
  * and updated in place by the next call; the library owns only the handle, the
@@ -459,6 +462,76 @@ typedef struct pcbenv_playout_request {
     void    *stream;
 } pcbenv_playout_request;
 int pcbenv_playout_paths(const pcbenv *env, const pcbenv_playout_request *req);
+
+/* The tree around pcbenv_playout_paths: UCT selection, expansion and backup of P search trees, one per root, in one
+ * kernel launch on req->stream.  An iteration of a batched search is then two launches with nothing between them:
+ * pcbenv_tree_advance(ABSORB | SELECT) writes selected / path_len / paths, pcbenv_playout_paths plays the P nodes they
+ * name, and the next pcbenv_tree_advance absorbs its reward / length / actions.  The caller owns every tensor; the
+ * handle supplies the device and pcbenv_last_error only: nothing the library owns is read or written and no bound
+ * buffers are needed.  Enqueue only, no allocation, no synchronisation.  Not meant to be captured into a hipGraph.
+ * The tree of root p has N = capacity node slots, slot 0 the root, filled in the order the nodes are made; a node has
+ * up to C = max_children children, children[p, n, 0 .. num_children[p, n]) in the order they were made, -1 behind them.
+ * phases is a set of the three below; one launch runs them in the order INIT, ABSORB, SELECT.
+ * PCBENV_TREE_INIT.  num_nodes = 1, reward_lo = +inf, reward_hi = -inf, best_reward = -inf, best_length = 0; every
+ * slot (the root and the unused ones alike): parent = -1, depth = 0, visits = 0, num_children = 0, node_action = 0,
+ * value_sum = 0, value_max = -inf, terminal = 0, children = -1.  best_actions is not written.
+ * PCBENV_TREE_SELECT.  Start at node 0.  Stop at a node that is terminal or has fewer than C children; otherwise go to
+ * the child with the highest q + c_uct * sqrt(ln[visits(node)] / visits(child)), with
+ * q = (value_sum(child) / visits(child) - reward_lo) / (reward_hi - reward_lo) if reward_hi > reward_lo, else 0; all of
+ * it float64, one IEEE operation per operator, visits taken as at least 1; ties go to the lowest child slot.  ln[n] is
+ * ln_dev[min(n, N)]: the caller's table (the kernel never computes a logarithm, so a search is a function of the
+ * table); a tree with N = iterations + 1 slots never reads past n = iterations.  Level d of the descent writes
+ * paths[d, p, :] = node_action(child); then path_len[p] = depth(selected) = the levels taken and selected[p].  Rows
+ * >= path_len[p] of paths are untouched.  At most max_steps levels.
+ * PCBENV_TREE_ABSORB.  reward[p], length[p], actions[:, p, :] are what the playout from selected[p] returned (rewards
+ * are finite).  With node = selected[p]: drew = length > depth(node) && !terminal(node), a = actions[min(depth,
+ * T - 1), p].  If drew and a child of node has action a, the leaf is the first such child.  Else, if drew, node has fewer
+ * than C children and num_nodes < N, the leaf is a new child in slot num_nodes (parent = node, depth + 1, node_action =
+ * a, terminal = length <= depth + 1), appended to node's children.  Else the leaf is node; where only num_nodes == N
+ * kept a child from being made, bit 0 (value 1) is ORed into *errors_dev.  Then reward_lo = min(reward_lo, r), reward_hi =
+ * max(reward_hi, r); visits += 1, value_sum += r, value_max = max(value_max, r) on the leaf and every ancestor; and if
+ * r > best_reward: best_reward = r, best_length = length, best_actions[t, p, :] = actions[t, p, :] for t < length.
+ * Rows >= length of best_actions are untouched.
+ * A slot number the kernel reads back -- selected[p], num_nodes[p], a child, a parent -- is compared with N before it
+ * addresses anything; one out of range ends that root's phase where it stands and ORs bit 1 (value 2) into *errors_dev.
+ * Layouts (int32 unless said): num_nodes [P]; parent, depth, visits, num_children [P, N]; node_action [P, N, 3];
+ * children [P, N, C]; value_sum, value_max float64 [P, N]; terminal uint8 [P, N]; reward_lo, reward_hi, best_reward
+ * float64 [P]; best_length [P]; best_actions [T, P, 3]; selected, path_len [P]; paths [T, P, 3]; reward float64 [P];
+ * length [P]; actions [T, P, 3] -- the step-major tuple format of pcbenv_playout_paths' path_actions_dev and
+ * actions_out_dev, T = max_steps.  errors_dev may be NULL.
+ * PCBENV_EINVAL (checked before any device call, in this order): null request; struct_size not
+ * sizeof(pcbenv_tree_request); phases 0 or with unknown bits, then INIT together with ABSORB; num_roots < 0; capacity < 1;
+ * max_children outside [1, PCBENV_MAX_TREE_CHILDREN]; max_steps < 1; a null tensor among num_nodes ... reward_hi (every
+ * phase), best_reward, best_length (INIT, ABSORB), best_actions (ABSORB); null selected (ABSORB, SELECT); null path_len or
+ * paths (SELECT); null ln_dev (SELECT); null reward, length or actions (ABSORB); ln_dev or a float64 tensor not 8-byte
+ * aligned; null handle.  num_roots == 0 is a no-op success. */
+#define PCBENV_TREE_INIT 1
+#define PCBENV_TREE_ABSORB 2
+#define PCBENV_TREE_SELECT 4
+#define PCBENV_MAX_TREE_CHILDREN 64
+typedef struct pcbenv_tree_request {
+    uint32_t struct_size; int32_t phases;            /* INIT, ABSORB, SELECT in that order; INIT|ABSORB is EINVAL */
+    int32_t num_roots /*P*/, capacity /*N node slots per root*/, max_children /*C*/, max_steps /*T*/;
+    double c_uct;
+    const double *ln_dev;                            /* float64 [N + 1]: ln_dev[n] = the caller's ln n, n >= 1 */
+    /* the tree, caller-owned device memory, root-major */
+    int32_t *num_nodes;                              /* [P] */
+    int32_t *parent, *depth, *visits, *num_children; /* [P, N] */
+    int32_t *node_action;                            /* [P, N, 3] */
+    int32_t *children;                               /* [P, N, C] */
+    double *value_sum, *value_max;                   /* [P, N] */
+    uint8_t *terminal;                               /* [P, N] */
+    double *reward_lo, *reward_hi, *best_reward;     /* [P] */
+    int32_t *best_length;                            /* [P] */
+    int32_t *best_actions;                           /* [T, P, 3] */
+    /* exchange with pcbenv_playout_paths (tuple format, step-major) */
+    int32_t *selected, *path_len;                    /* [P]   written by SELECT */
+    int32_t *paths;                                  /* [T, P, 3]: rows t < path_len[p] written, the others untouched */
+    const double *reward; const int32_t *length; const int32_t *actions;  /* [P], [P], [T, P, 3]: read by ABSORB */
+    uint32_t *errors_dev;                            /* optional */
+    void *stream;
+} pcbenv_tree_request;
+int pcbenv_tree_advance(const pcbenv *env, const pcbenv_tree_request *req);
 
 /* Masked categorical draw from a policy's logits, on the device, one kernel launch on `stream`.
  * logits_dev: C-contiguous [num_envs, A], A = O*H*W (square: H*W), in the flat action order of PCBENV_ACTION_FLAT

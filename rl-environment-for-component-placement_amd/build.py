@@ -6,8 +6,9 @@ must match the reference bit for bit).  The kernels of the four environment kind
 compiled in parallel -- csrc/pcb_kind.inc, and csrc/pcb_playout.inc for pcbenv_playout and pcbenv_playout_paths, each
 compiled once per row of UNITS below with that row's -D flags -- then linked with the host side -- the C ABI
 (csrc/pcbenv_api.hip), the layout derivation (csrc/pcb_config.hip) and the on-device instance generator with its kernels
-(csrc/pcb_gen.hip), which share csrc/pcb_host.h -- the two kernels every kind uses (csrc/pcb_sample.hip) and the host
-instance generator (csrc/instance_gen.cpp).  csrc/pcb_layout.h is the layout contract both sides compile.
+(csrc/pcb_gen.hip), which share csrc/pcb_host.h -- the two kernels every kind uses (csrc/pcb_sample.hip), the policy kernels
+(csrc/pcb_policy*.hip), the tree step with its entry point (csrc/pcb_tree.hip) and the host instance generator
+(csrc/instance_gen.cpp).  csrc/pcb_layout.h is the layout contract both sides compile.
 """
 import os
 import subprocess
@@ -34,7 +35,7 @@ UNITS = ([unit("pcb_kind", "pcb_kind.inc", k) for k in FLAT_KINDS[::-1]]
          + [unit("pcb_playout", "pcb_playout.inc", k) for k in FLAT_KINDS]
          + [unit("pcb_playout_paths", "pcb_playout.inc", k, p, paths=True) for p in (2, 1, 0) for k in PIN_KINDS]
          + [unit("pcb_playout_paths", "pcb_playout.inc", k, paths=True) for k in FLAT_KINDS]
-         + [(u + ".o", u, []) for u in ("pcb_policy.hip", "pcb_policy_eval.hip", "pcb_policy_axis.hip", "pcb_gen.hip", "pcb_sample.hip",
+         + [(u + ".o", u, []) for u in ("pcb_policy.hip", "pcb_policy_eval.hip", "pcb_policy_axis.hip", "pcb_tree.hip", "pcb_gen.hip", "pcb_sample.hip",
                                         "pcbenv_api.hip", "pcb_config.hip", "instance_gen.cpp")])
 DEPS = [os.path.join(REPO, "include", "pcbenv.h")] + sorted(
     os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc", ".hip", ".cpp")))

@@ -20,6 +20,9 @@ EVAL_ERR_NONFINITE, EVAL_ERR_ALL_NEG_INF, EVAL_ERR_ACTION = 1, 2, 4  # bits of p
 EVAL_ROW_OK, EVAL_ROW_ZERO, EVAL_ROW_NO_ONE_HOT = 0, 1, 2  # row status, stats[:, 3]
 AXIS_ORIENTATION, AXIS_X, AXIS_Y = 0, 1, 2
 AXIS_ERR_NONFINITE, AXIS_ERR_ALL_NEG_INF, AXIS_ERR_VALUE, AXIS_ERR_GIVEN = 1, 2, 4, 8  # bits of the axis entry points' *errors_dev
+TREE_INIT, TREE_ABSORB, TREE_SELECT = 1, 2, 4  # phases of pcbenv_tree_advance
+MAX_TREE_CHILDREN = 64
+TREE_ERR_FULL, TREE_ERR_TREE = 1, 2  # bits of pcbenv_tree_advance's *errors_dev
 
 EXPORTS = ("pcbenv_abi_version", "pcbenv_create", "pcbenv_destroy", "pcbenv_last_error",
            "pcbenv_instance_stride", "pcbenv_max_total_pins", "pcbenv_set_option", "pcbenv_bind_buffers", "pcbenv_bind_buffers_slots", "pcbenv_bind_compact_features", "pcbenv_select_slot",
@@ -28,7 +31,7 @@ EXPORTS = ("pcbenv_abi_version", "pcbenv_create", "pcbenv_destroy", "pcbenv_last
            "pcbenv_instgen_device_enable", "pcbenv_instgen_device_status", "pcbenv_get_instances",
            "pcbenv_instgen_create", "pcbenv_instgen_destroy", "pcbenv_instgen_next", "pcbenv_instgen_next_batch",
            "pcbenv_gather", "pcbenv_sample_logits", "pcbenv_evaluate_logits", "pcbenv_evaluate_logits_backward",
-           "pcbenv_sample_axis", "pcbenv_evaluate_axis", "pcbenv_evaluate_axis_backward", "pcbenv_playout", "pcbenv_playout_paths")
+           "pcbenv_sample_axis", "pcbenv_evaluate_axis", "pcbenv_evaluate_axis_backward", "pcbenv_playout", "pcbenv_playout_paths", "pcbenv_tree_advance")
 
 
 class PcbenvConfig(C.Structure):
@@ -64,6 +67,17 @@ class PcbenvPlayoutRequest(C.Structure):
                 ("reward_dev", C.c_void_p), ("done_dev", C.c_void_p), ("length_dev", C.c_void_p), ("info_dev", C.c_void_p),
                 ("actions_out_dev", C.c_void_p), ("actions_steps", C.c_int32), ("leaf_mask_bits_dev", C.c_void_p), ("errors_dev", C.c_void_p),
                 ("seed", C.c_uint64), ("first_env_index", C.c_uint64), ("step_index0", C.c_uint64), ("stream", C.c_void_p)]
+
+
+TREE_TENSORS = ("num_nodes", "parent", "depth", "visits", "num_children", "node_action", "children", "value_sum", "value_max", "terminal",
+                "reward_lo", "reward_hi", "best_reward", "best_length", "best_actions")
+
+
+class PcbenvTreeRequest(C.Structure):
+    """pcbenv_tree_request (include/pcbenv.h), the arguments of pcbenv_tree_advance."""
+    _fields_ = ([("struct_size", C.c_uint32), ("phases", C.c_int32), ("num_roots", C.c_int32), ("capacity", C.c_int32),
+                 ("max_children", C.c_int32), ("max_steps", C.c_int32), ("c_uct", C.c_double), ("ln_dev", C.c_void_p)]
+                + [(n, C.c_void_p) for n in TREE_TENSORS + ("selected", "path_len", "paths", "reward", "length", "actions", "errors_dev", "stream")])
 
 
 _lib = None
@@ -127,6 +141,7 @@ def load():
     L.pcbenv_playout.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     L.pcbenv_playout_paths.argtypes = [C.c_void_p, C.POINTER(PcbenvPlayoutRequest)]
+    L.pcbenv_tree_advance.argtypes = [C.c_void_p, C.POINTER(PcbenvTreeRequest)]
     L.pcbenv_mask_bits.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.pcbenv_mask_bits.restype = C.c_void_p
     if L.pcbenv_abi_version() != ABI_VERSION:

@@ -722,6 +722,56 @@ class BatchedPlacementEnv:
             raise IndexError(f"playout: an index is outside [0, {self.num_envs}) (those playouts report length 0)")
         return Playout(reward, done, length, info, actions)
 
+    def tree_request(self, tree: Dict[str, torch.Tensor], c_uct: float = 1.0) -> "_lib.PcbenvTreeRequest":
+        """The request of `tree_advance` for the tensors in `tree` (see `pcbenv.search.new_tree` for a set of the right
+        shapes): the keys are the members of pcbenv_tree_request -- `ln_dev`, the tree tensors `num_nodes` ... `best_actions`,
+        `selected`, `path_len`, `paths` and optionally `errors_dev` -- on this device, contiguous, of the dtypes and shapes
+        include/pcbenv.h gives; P, N, C and T are read off `children` [P, N, C] and `paths` [T, P, 3].  The request holds
+        addresses only: the caller keeps the tensors alive."""
+        i32, f64 = torch.int32, torch.float64
+        ch, paths = tree["children"], tree["paths"]
+        if ch.dim() != 3 or paths.dim() != 3 or paths.shape[1:] != (ch.shape[0], 3):
+            raise ValueError(f"children must be [P, N, C] and paths [T, P, 3], got {tuple(ch.shape)} and {tuple(paths.shape)}")
+        (P, N, Cc), T = ch.shape, paths.shape[0]
+        want = {"ln_dev": (f64, (N + 1,)), "num_nodes": (i32, (P,)), "parent": (i32, (P, N)), "depth": (i32, (P, N)), "visits": (i32, (P, N)),
+                "num_children": (i32, (P, N)), "node_action": (i32, (P, N, 3)), "children": (i32, (P, N, Cc)), "value_sum": (f64, (P, N)),
+                "value_max": (f64, (P, N)), "terminal": (torch.uint8, (P, N)), "reward_lo": (f64, (P,)), "reward_hi": (f64, (P,)),
+                "best_reward": (f64, (P,)), "best_length": (i32, (P,)), "best_actions": (i32, (T, P, 3)), "selected": (i32, (P,)),
+                "path_len": (i32, (P,)), "paths": (i32, (T, P, 3))}
+        if tree.get("errors_dev") is not None:
+            want["errors_dev"] = (i32, (1,))
+        req = _lib.PcbenvTreeRequest(struct_size=C.sizeof(_lib.PcbenvTreeRequest), num_roots=P, capacity=N, max_children=Cc, max_steps=T,
+                                     c_uct=float(c_uct))
+        for name, (dtype, shape) in want.items():
+            self._tree_tensor(name, tree[name], dtype, shape)
+            setattr(req, name, tree[name].data_ptr() or None)
+        return req
+
+    def _tree_tensor(self, name, t, dtype, shape):
+        here = t.device.type == self.device.type and self.device.index in (None, t.device.index)
+        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or not here:
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {list(shape)} on {self.device}, "
+                             f"got {t.dtype} {list(t.shape)} on {t.device}")
+
+    def tree_advance(self, req: "_lib.PcbenvTreeRequest", phases: int, reward: Optional[torch.Tensor] = None,
+                     length: Optional[torch.Tensor] = None, actions: Optional[torch.Tensor] = None) -> None:
+        """One step of P search trees on the device (`pcbenv_tree_advance`, one kernel launch on the current stream, nothing
+        else): `phases` is a set of `_lib.TREE_INIT`, `TREE_ABSORB`, `TREE_SELECT`, run in that order.  SELECT descends every
+        tree by UCT and writes `selected`, `path_len` and `paths` -- the `paths=` / `path_len=` of the next `playout` call;
+        ABSORB takes that playout's `reward` [P] float64, `length` [P] int32 and `actions` [T, P, 3] int32, expands and
+        backs up.  `req`: `tree_request(tree, c_uct)`, reusable for every call on the same tensors."""
+        P, T = req.num_roots, req.max_steps
+        if P == 0:  # torch gives empty tensors a null pointer
+            return
+        req.phases = int(phases)
+        for name, t, dtype, shape in (("reward", reward, torch.float64, (P,)), ("length", length, torch.int32, (P,)),
+                                      ("actions", actions, torch.int32, (T, P, 3))):
+            if t is not None:
+                self._tree_tensor(name, t, dtype, shape)
+            setattr(req, name, None if t is None else (t.data_ptr() or None))
+        req.stream = self._stream().value
+        _lib.check(self._L.pcbenv_tree_advance(self._h, C.byref(req)), self._h)
+
     def queue_cursors(self):
         """(min, max) over the environments of the number of resets performed so far (synchronises)."""
         lo, hi = C.c_uint32(), C.c_uint32()

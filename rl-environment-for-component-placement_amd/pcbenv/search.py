@@ -12,7 +12,8 @@ actions the same way: k playouts behind each candidate, the forced first action 
 
 `tree_search` goes deeper than one ply: a batched UCT whose nodes are named by their path from the root and evaluated by
 `BatchedPlacementEnv.playout(paths=...)` (pcbenv_playout_paths) -- one launch per iteration for all roots, no planner
-batch, no node ever materialised.
+batch, no node ever materialised.  `tree_search_device` is the same search with the tree kept by the device
+(pcbenv_tree_advance): two launches per iteration and no tensor operation between them.
 """
 from __future__ import annotations
 
@@ -245,3 +246,82 @@ def tree_search(root, iterations: int, step_index: int, c_uct: float = 1.0, max_
     return TreeSearch(action, child_visits, child_actions, best_reward, best_actions, best_length, count,
                       parent[:, :N], depth[:, :N], node_action[:, :N], visits[:, :N], vsum[:, :N], vmax[:, :N], terminal[:, :N],
                       children[:, :N, :C])
+
+
+@dataclass
+class DeviceTreeSearch(TreeSearch):
+    """What `tree_search_device` returns: `TreeSearch`, and the error word of the launches."""
+    errors: torch.Tensor         # 0-dim int32: bit 0 = the tree was full when a node was due (capacity < iterations + 1)
+
+
+def ln_table(N: int) -> torch.Tensor:
+    """ln n for n = 0 .. N as `tree_search` computes it (torch's float64 log on the CPU), entry 0 set to 0: float64 [N + 1]."""
+    ln = torch.log(torch.arange(N + 1, dtype=torch.float64))
+    ln[0] = 0.0
+    return ln
+
+
+_LN_ON_DEVICE = {}
+
+
+def ln_table_on(N: int, device) -> torch.Tensor:
+    """`ln_table(N)` on `device`, uploaded once per (N, device) and kept: a search enqueues no host copy of its own."""
+    key = (int(N), str(device))
+    if key not in _LN_ON_DEVICE:
+        _LN_ON_DEVICE[key] = ln_table(N).to(device)
+    return _LN_ON_DEVICE[key]
+
+
+def new_tree(P: int, N: int, C: int, T: int, device) -> dict:
+    """The tensors of P trees of N node slots, C children per node and T steps, as `BatchedPlacementEnv.tree_request`
+    takes them.  Uninitialised but for `paths`, `best_actions` and `errors_dev`: PCBENV_TREE_INIT fills the rest."""
+    i32, f64 = dict(dtype=torch.int32, device=device), dict(dtype=torch.float64, device=device)
+    tree = {n: torch.empty((P, N), **i32) for n in ("parent", "depth", "visits", "num_children")}
+    tree.update({n: torch.empty((P, N), **f64) for n in ("value_sum", "value_max")})
+    tree.update({n: torch.empty(P, **f64) for n in ("reward_lo", "reward_hi", "best_reward")})
+    tree.update({n: torch.empty(P, **i32) for n in ("num_nodes", "best_length", "selected", "path_len")})
+    tree.update(node_action=torch.empty((P, N, 3), **i32), children=torch.empty((P, N, C), **i32),
+                terminal=torch.empty((P, N), dtype=torch.uint8, device=device), best_actions=torch.zeros((T, P, 3), **i32),
+                paths=torch.zeros((T, P, 3), **i32), errors_dev=torch.zeros(1, **i32), ln_dev=ln_table_on(N, device))
+    return tree
+
+
+def tree_result(tree: dict) -> DeviceTreeSearch:
+    """The tensors of a device tree in the form `tree_search` reports (int32 widened to int64, the root's children summed up)."""
+    w = lambda n: tree[n].to(torch.int64)
+    children, visits, node_action = w("children"), w("visits"), tree["node_action"]
+    P, _, C = children.shape
+    rows = torch.arange(P, dtype=torch.int64, device=children.device)
+    ch = children[:, 0, :]
+    child_visits = torch.where(ch >= 0, visits[rows[:, None], ch.clamp(min=0)], torch.zeros_like(ch))
+    child_actions = torch.where((ch >= 0)[:, :, None], node_action[rows[:, None], ch.clamp(min=0)], torch.zeros_like(node_action[:, :1]).expand(P, C, 3))
+    action = child_actions[rows, child_visits.argmax(dim=1)]
+    return DeviceTreeSearch(action, child_visits, child_actions, tree["best_reward"], tree["best_actions"], w("best_length"), w("num_nodes"),
+                            w("parent"), w("depth"), node_action, visits, tree["value_sum"], tree["value_max"], tree["terminal"].bool(),
+                            children, tree["errors_dev"][0])
+
+
+def tree_search_device(root, iterations: int, step_index: int, c_uct: float = 1.0, max_children: int = 4, max_steps=None,
+                       capacity=None) -> DeviceTreeSearch:
+    """`tree_search` with the tree kept by the device: an iteration is two kernel launches, `root.tree_advance`
+    (pcbenv_tree_advance: backup of the last playout, expansion, the next selection) and `root.playout(paths=...)`, with
+    no tensor operation between them.  The same search as `tree_search(root, iterations, step_index, c_uct, max_children,
+    max_steps=max_steps)` -- the same playouts, the same tree, field by field -- as long as no two UCT scores of one
+    selection differ only by the rounding of a logarithm (the table of ln n is torch's float64 log on the CPU).
+    capacity: node slots per root, default iterations + 1 (what the search can use at most).  A smaller tree stops growing
+    when it is full -- later playouts are backed up into existing nodes -- and reports bit 0 in `errors`; ln n is then
+    taken at n = capacity for larger n.  max_children is 64 at most."""
+    from . import _lib
+    from .batched_env import default_max_steps
+    P, C, M = int(root.num_envs), int(max_children), int(iterations)
+    if M < 1 or C < 1:
+        raise ValueError("tree_search_device needs iterations >= 1 and max_children >= 1")
+    T = default_max_steps(root.cfg) if max_steps is None else int(max_steps)
+    N = M + 1 if capacity is None else int(capacity)
+    tree = new_tree(P, N, C, T, root.device)
+    req = root.tree_request(tree, c_uct)
+    root.tree_advance(req, _lib.TREE_INIT | _lib.TREE_SELECT)
+    for m in range(M):
+        po = root.playout(k=1, step_index=int(step_index) + m * T, paths=tree["paths"], path_len=tree["path_len"], max_steps=T)
+        root.tree_advance(req, _lib.TREE_ABSORB | (_lib.TREE_SELECT if m + 1 < M else 0), po.reward, po.length, po.actions)
+    return tree_result(tree)

@@ -1,5 +1,5 @@
 """Receding-horizon Monte-Carlo lookahead with pcbenv.search.best_of_k against the plain uniform-random policy, c3.
-python tools/search_demo.py [--roots 256] [--k 16] [--playouts | --tree]
+python tools/search_demo.py [--roots 256] [--k 16] [--playouts | --tree [--device-tree]]
 
 Both play the same instances (one episode per root environment).  The search forks every root k times into a planner
 batch (one device-side gather), plays every child to its end with the on-device sampler, and applies the best child's
@@ -7,7 +7,8 @@ first action to the root, then searches again.  --playouts: the same search thro
 one pcbenv_playout launch per search step instead of a planner batch and a launch per planner step.  Reports mean final reward of both policies and the search rate in
 planner env-steps/s (wall time of the best_of_k calls).  --tree: pcbenv.search.tree_search with k iterations per move -- the
 same number of playouts as best-of-k, spent by UCT on a tree of paths (one pcbenv_playout_paths launch per iteration) -- and
-the most-visited first action is applied."""
+the most-visited first action is applied.  --tree --device-tree: the same search through pcbenv.search.tree_search_device, the
+tree kept by the device (pcbenv_tree_advance): two launches per iteration."""
 import argparse
 import json
 import os
@@ -19,7 +20,7 @@ import torch  # noqa: E402
 
 from pcbenv import named_config  # noqa: E402
 from pcbenv.batched_env import BatchedPlacementEnv  # noqa: E402
-from pcbenv.search import best_of_k, best_of_k_playouts, tree_search  # noqa: E402
+from pcbenv.search import best_of_k, best_of_k_playouts, tree_search, tree_search_device  # noqa: E402
 
 
 def final_rewards(env, act, T):
@@ -42,7 +43,10 @@ def main():
     ap.add_argument("--config", default="c3")
     ap.add_argument("--playouts", action="store_true", help="search with best_of_k_playouts (no planner batch)")
     ap.add_argument("--tree", action="store_true", help="search with tree_search, k iterations per move (no planner batch)")
+    ap.add_argument("--device-tree", action="store_true", help="with --tree: tree_search_device (the tree on the device)")
     a = ap.parse_args()
+    if a.device_tree and not a.tree:
+        ap.error("--device-tree goes with --tree")
     cfg = named_config(a.config)
     P, k, T = a.roots, a.k, cfg.max_num_components
 
@@ -63,7 +67,7 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if a.tree:
-            first = tree_search(search_root, k, step_index=1000 + t * T * k).action
+            first = (tree_search_device if a.device_tree else tree_search)(search_root, k, step_index=1000 + t * T * k).action
         elif a.playouts:
             res = best_of_k_playouts(search_root, k, step_index=1000 + t * T)
         else:
@@ -74,7 +78,7 @@ def main():
         _, r, d, _ = search_root.step(first if a.tree else res.actions[0])
         return r, d
     search_final = final_rewards(search_root, search_step, T)
-    out = {"config": a.config, "roots": P, "k": k, "search": "tree_search" if a.tree else "best_of_k_playouts" if a.playouts else "best_of_k",
+    out = {"config": a.config, "roots": P, "k": k, "search": "tree_search_device" if a.device_tree else "tree_search" if a.tree else "best_of_k_playouts" if a.playouts else "best_of_k",
            "random_policy_mean_final_reward": float(random_final.mean()),
            "best_of_k_mean_final_reward": float(search_final.mean()),
            "search_env_steps_per_sec": round(planner_steps / spent), "search_seconds": round(spent, 3)}
