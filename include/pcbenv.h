@@ -15,7 +15,9 @@
  * pcbenv_bind_buffers[_slots] take no stream and synchronise the whole device, before and after what they change on it;
  * the other options, pcbenv_bind_compact_features and pcbenv_select_slot change host-side fields only, which the next
  * call reads.  pcbenv_playout_paths takes its stream as a field of its request and only enqueues on it, exactly as
- * pcbenv_playout does.  pcbenv_tree_advance likewise: it only enqueues one kernel on its request's stream.  A handle may
+ * pcbenv_playout does.  pcbenv_tree_advance likewise: it only enqueues one kernel on its request's stream.
+ * pcbenv_gather_paths takes its stream as a field of its request too and only enqueues on it, exactly as pcbenv_gather
+ * does.  A handle may
  * be used from different streams as long as the caller orders the calls (an event recorded behind one call and waited
  * for by the stream of the next) and never makes two calls on one handle at the same time.
  * Two handles share nothing on the device: they may run concurrently on two streams (pcbenv_gather between two handles
@@ -67,6 +69,8 @@
  *                            agent/random/random_policy_square.py:25-58 (and siblings)
  *   pcbenv_tree_advance    no counterpart: the reference has no search.  The bookkeeping of a batched UCT around
  *                          pcbenv_playout_paths (selection, expansion, backup), one launch for all roots
+ *   pcbenv_gather_paths    copy.deepcopy(env) followed by env.step(a) for every action of a path: a tree node named by
+ *                          its path from a root, with its observations (what a network needs to score the node)
  *
  * Observations are written into caller-owned device buffers (pcbenv_buffers)
  * and updated in place by the next call; the library owns only the handle, the
@@ -462,6 +466,51 @@ typedef struct pcbenv_playout_request {
     void    *stream;
 } pcbenv_playout_request;
 int pcbenv_playout_paths(const pcbenv *env, const pcbenv_playout_request *req);
+
+/* Materialise tree nodes named by a path: pcbenv_gather followed by a per-row path of forced actions, in ONE kernel
+ * launch on req->stream (within one handle, preceded by the 25-byte-per-environment snapshot copy pcbenv_gather makes).
+ * What a network needs to score a node -- priors at a tree's nodes, a learned rollout policy behind a path: the node's
+ * grid, action_mask, pin_grid and feature tensors in a handle.  The observations are written once, however long the path.
+ * The identity.  After the call, environment i of dst is what pcbenv_gather(dst, src, src_index) would have made it,
+ * followed by transitions t = 0, 1, ..., path_len[i] - 1 of environment i ALONE, each the transition pcbenv_step would
+ * make with action path_actions[t, i] on a handle without PCBENV_FLAG_AUTO_RESET, stopping behind the first one that
+ * reports `done`.  Every bound tensor of row i in the destination's selected slot (pcbenv_buffers, the compact feature
+ * tensors, the mask marginals) is written whole and shows the state after the last transition applied; reward / done /
+ * info are those of the last transition applied, or -- with no transition applied -- the source row's, as pcbenv_gather
+ * copies them; length_dev[i] is the number of transitions applied; and the state block is the one those calls would
+ * have left, so every later call on dst behaves as after them.
+ * path_steps == 0: the call is pcbenv_gather, bit for bit, state block included.
+ * A bad path action is data: an illegal or out-of-range action is a terminal transition with the worst-case reward and
+ * the state unchanged, as in pcbenv_step.  It is the last transition applied: path rows behind it, and rows
+ * t >= path_len[i], are never read for effect.  A root whose episode is already over still gets its path applied (there
+ * is no done latch, as in pcbenv_step): only a `done` among the row's own transitions stops it.
+ * The call never resets and never consumes an instance: PCBENV_FLAG_AUTO_RESET of dst is ignored for these transitions
+ * (a later pcbenv_step of dst resets as usual).  Everything pcbenv_gather says stays the destination's own stays so: the
+ * queue cursor, the episode count, the generator state, the bind generation of its feature rows; no terminal-list mark
+ * and no presampled action is left; the spatial feature cache is refilled under the destination's episode tag.
+ * Rows with src_index[i] == -1 keep their episode: none of their tensors is touched, their path is not read and
+ * length_dev[i] = 0.  Any other out-of-range src_index does the same and ORs bit 0 into *errors_dev (if not NULL).  A
+ * path_len[i] outside [0, path_steps] is checked before it addresses or bounds anything: the row keeps its episode in
+ * the same way and bit 1 (value 2) is ORed in.
+ * Enqueue-only on req->stream: no allocation, no host synchronisation.  Not capturable into a hipGraph (PCBENV_ESTATE,
+ * as pcbenv_gather); a handle that works in place after a capture gets the result copied back into its set, as
+ * pcbenv_gather does.  Afterwards the handle has an episode.
+ * PCBENV_EINVAL (checked before any device call, in this order): null request; struct_size not
+ * sizeof(pcbenv_gather_paths_request); unknown format; path_steps < 0; path_steps > 0 with null path_actions_dev; null
+ * src_index_dev; null handle; the definition / device mismatches pcbenv_gather refuses.  PCBENV_ESTATE: as pcbenv_gather. */
+typedef struct pcbenv_gather_paths_request {
+    uint32_t struct_size;             /* sizeof as the caller compiled it; any other value: PCBENV_EINVAL */
+    int32_t  action_format;           /* of path_actions_dev */
+    const pcbenv *src;                /* NULL or dst: the same handle; as pcbenv_gather */
+    const int32_t *src_index_dev;     /* int32 [dst num_envs]; -1 keeps the row's episode; as pcbenv_gather */
+    const int32_t *path_actions_dev;  /* int32 [path_steps, B, 3] or [path_steps, B], step-major; NULL iff path_steps == 0 */
+    const int32_t *path_len_dev;      /* int32 [B], or NULL = path_steps for every row */
+    int32_t  path_steps;              /* >= 0 */
+    int32_t *length_dev;              /* optional int32 [B]: transitions applied to row i */
+    uint32_t *errors_dev;             /* optional */
+    void    *stream;
+} pcbenv_gather_paths_request;
+int pcbenv_gather_paths(pcbenv *dst, const pcbenv_gather_paths_request *req);
 
 /* The tree around pcbenv_playout_paths: UCT selection, expansion and backup of P search trees, one per root, in one
  * kernel launch on req->stream.  An iteration of a batched search is then two launches with nothing between them:

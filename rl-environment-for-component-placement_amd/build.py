@@ -3,8 +3,8 @@
 
 hipcc cross-compiles without a GPU.  -ffp-contract=off: one IEEE operation per written operator (the reward path
 must match the reference bit for bit).  The kernels of the four environment kinds are separate translation units
-compiled in parallel -- csrc/pcb_kind.inc, and csrc/pcb_playout.inc for pcbenv_playout and pcbenv_playout_paths, each
-compiled once per row of UNITS below with that row's -D flags -- then linked with the host side -- the C ABI
+compiled in parallel -- csrc/pcb_kind.inc, csrc/pcb_playout.inc for pcbenv_playout and pcbenv_playout_paths, and
+csrc/pcb_gather_paths.inc for pcbenv_gather_paths, each compiled once per row of UNITS below with that row's -D flags -- then linked with the host side -- the C ABI
 (csrc/pcbenv_api.hip), the layout derivation (csrc/pcb_config.hip) and the on-device instance generator with its kernels
 (csrc/pcb_gen.hip), which share csrc/pcb_host.h -- the two kernels every kind uses (csrc/pcb_sample.hip), the policy kernels
 (csrc/pcb_policy*.hip), the tree step with its entry point (csrc/pcb_tree.hip) and the host instance generator
@@ -35,6 +35,8 @@ UNITS = ([unit("pcb_kind", "pcb_kind.inc", k) for k in FLAT_KINDS[::-1]]
          + [unit("pcb_playout", "pcb_playout.inc", k) for k in FLAT_KINDS]
          + [unit("pcb_playout_paths", "pcb_playout.inc", k, p, paths=True) for p in (2, 1, 0) for k in PIN_KINDS]
          + [unit("pcb_playout_paths", "pcb_playout.inc", k, paths=True) for k in FLAT_KINDS]
+         + [unit("pcb_gather_paths", "pcb_gather_paths.inc", k, p) for p in (2, 1, 0) for k in PIN_KINDS]
+         + [unit("pcb_gather_paths", "pcb_gather_paths.inc", k) for k in FLAT_KINDS]
          + [(u + ".o", u, []) for u in ("pcb_policy.hip", "pcb_policy_eval.hip", "pcb_policy_axis.hip", "pcb_tree.hip", "pcb_gen.hip", "pcb_sample.hip",
                                         "pcbenv_api.hip", "pcb_config.hip", "instance_gen.cpp")])
 DEPS = [os.path.join(REPO, "include", "pcbenv.h")] + sorted(

@@ -1,5 +1,5 @@
-// pcb_launch.h -- what the host side (pcbenv_api.hip) and the kernel translation units (pcb_kind.inc and pcb_playout.inc,
-// once per unit of build.py's table; pcb_sample.hip, pcb_policy*.hip) share: one launch entry per kernel family and
+// pcb_launch.h -- what the host side (pcbenv_api.hip) and the kernel translation units (pcb_kind.inc, pcb_playout.inc and
+// pcb_gather_paths.inc, once per unit of build.py's table; pcb_sample.hip, pcb_policy*.hip) share: one launch entry per kernel family and
 // environment kind, so that the host side compiles no device code and the kernel instantiations of the four kinds compile
 // in parallel.  Which instantiation an entry launches is pcb_layout::select_step_build / select_playout_build.
 #pragma once
@@ -36,6 +36,14 @@ struct GatherArgs {
     int src_B;
 };
 struct GatherLaunch { DevParams d; GatherArgs g; int threads; hipStream_t stream; };
+// pcbenv_gather_paths (pcb_gather_paths.inc): d and g as for pcbenv_gather; the paths travel in GatherPathArgs.
+struct GatherPathArgs {
+    const int *path_actions;  // [path_steps, B, 3] / [path_steps, B] of the destination's B, null if path_steps == 0
+    const int *path_len;      // [B] or null: path_steps for every row
+    int *length;              // [B], may be null
+    int fmt, path_steps;
+};
+struct GatherPathsLaunch { DevParams d; GatherArgs g; GatherPathArgs q; int threads; bool routes; hipStream_t stream; };
 
 // pcbenv_playout and pcbenv_playout_paths (pcb_playout.inc; paths says which): d is the root handle's parameter block with d.state = the current state set,
 // buf.reward / buf.info repointed at the playout's rows and everything else a playout must not touch taken out (every
@@ -133,5 +141,6 @@ int pcb_launch_evaluate_axis(const EvalAxisLaunch &a);
 int pcb_launch_evaluate_axis_backward(const EvalAxisBackwardLaunch &a);
 
 #define PCB_DECLARE_KIND(name) int pcb_launch_step_##name(const StepLaunch &a); int pcb_launch_reset_##name(const ResetLaunch &a); \
-    int pcb_launch_gather_##name(const GatherLaunch &a); int pcb_launch_playout_##name(const PlayoutLaunch &a);
+    int pcb_launch_gather_##name(const GatherLaunch &a); int pcb_launch_playout_##name(const PlayoutLaunch &a); \
+    int pcb_launch_gather_paths_##name(const GatherPathsLaunch &a);
 PCB_DECLARE_KIND(square) PCB_DECLARE_KIND(rect) PCB_DECLARE_KIND(pin) PCB_DECLARE_KIND(spatial)

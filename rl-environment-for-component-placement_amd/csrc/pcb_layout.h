@@ -178,13 +178,17 @@ PCB_HD inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 // The template arguments of k_step<KIND, ww, nw, routes, build, geo> and of k_playout<KIND, ww, nw, routes, paths>.
 struct StepBuild { int ww, nw; bool routes; int build, geo; };
 struct PlayoutBuild { int ww, nw; bool routes, paths; };
+struct GatherPathsBuild { int ww, nw; bool routes; };  // k_gather_paths<KIND, ww, nw, routes> (pcb_gather_paths.h)
 // The candidates, numbered: pcb_kind.inc / pcb_playout.inc walk them and compile those their unit owns.
 #define STEP_BUILDS 64
 #define PLAYOUT_BUILDS 16
+#define GATHER_PATHS_BUILDS 8
 PCB_HD constexpr StepBuild step_build_at(int i) { return StepBuild{1 + (i & 1), (i >> 1 & 1) ? 4 : 1, (i >> 2 & 1) != 0, i >> 3 & 3, i >> 5 & 1}; }
 PCB_HD constexpr PlayoutBuild playout_build_at(int i) { return PlayoutBuild{1 + (i & 1), (i >> 1 & 1) ? 4 : 1, (i >> 2 & 1) != 0, (i >> 3 & 1) != 0}; }
+PCB_HD constexpr GatherPathsBuild gather_paths_build_at(int i) { return GatherPathsBuild{1 + (i & 1), (i >> 1 & 1) ? 4 : 1, (i >> 2 & 1) != 0}; }
 PCB_HD constexpr int build_index(const StepBuild &b) { return (b.ww - 1) | (b.nw == 4) << 1 | (int)b.routes << 2 | b.build << 3 | b.geo << 5; }
 PCB_HD constexpr int build_index(const PlayoutBuild &b) { return (b.ww - 1) | (b.nw == 4) << 1 | (int)b.routes << 2 | (int)b.paths << 3; }
+PCB_HD constexpr int build_index(const GatherPathsBuild &b) { return (b.ww - 1) | (b.nw == 4) << 1 | (int)b.routes << 2; }
 
 // The build of a step launch; stream_stores is the launch's store policy (DevParams::stream_stores).  A launch is of the
 // trajectory layout if it writes one of several slots or makes several transitions.
@@ -197,10 +201,15 @@ PCB_HD constexpr StepBuild select_step_build(const StepShape &s, bool stream_sto
 PCB_HD constexpr PlayoutBuild select_playout_build(int WW, int threads, bool routes, bool paths) {
     return PlayoutBuild{WW, wavefronts(threads), routes, paths};
 }
+// (threads: the DESTINATION's team size, as for k_gather)
+PCB_HD constexpr GatherPathsBuild select_gather_paths_build(int WW, int threads, bool routes) {
+    return GatherPathsBuild{WW, wavefronts(threads), routes};
+}
 // The unit of build.py's table that compiles a build.  k_step of a pin kind: 4 = the 64 x 64 grid compiled in, 2 / 3 =
 // with routes on one / four wavefronts, 1 = without routes into a trajectory slot, 0 = everything else, next to k_reset,
 // k_gather and the entry points (pcb_kind.inc says why the slot build is on its own); k_playout of a pin kind, PATHS or
-// not: 0 = without routes, 1 / 2 = with routes on one / four wavefronts.  Square and rect have no routes and one unit.
+// not, and k_gather_paths in units of its own: 0 = without routes, 1 / 2 = with routes on one / four wavefronts.  Square
+// and rect have no routes and one unit.
 PCB_HD constexpr int step_build_part(int kind, const StepBuild &b) {
     if (b.geo == STEP_GEO_64)
         return is_pin_kind(kind) && !b.routes && b.ww == 1 && b.nw == 1 && b.build <= STEP_BUILD_INPLACE_STREAM ? 4 : BUILD_PART_NONE;
@@ -210,6 +219,9 @@ PCB_HD constexpr int step_build_part(int kind, const StepBuild &b) {
 PCB_HD constexpr int playout_build_part(int kind, const PlayoutBuild &b) {
     if (b.routes) return is_pin_kind(kind) ? (b.nw == 1 ? 1 : 2) : BUILD_PART_NONE;
     return 0;
+}
+PCB_HD constexpr int gather_paths_build_part(int kind, const GatherPathsBuild &b) {
+    return playout_build_part(kind, PlayoutBuild{b.ww, b.nw, b.routes, true});
 }
 // Every launch of a handle that pcbenv_create admits has a unit, and c3 / c4 in place on one wavefront run the fixed build.
 PCB_HD constexpr bool every_launch_has_a_unit() {
@@ -223,10 +235,12 @@ PCB_HD constexpr bool every_launch_has_a_unit() {
         }
         for (int paths = 0; paths < 2; paths++)
             if (playout_build_part(kind, select_playout_build(WW, threads, routes, paths != 0)) == BUILD_PART_NONE) return false;
+        const GatherPathsBuild gb = select_gather_paths_build(WW, threads, routes);
+        if (gather_paths_build_part(kind, gb) == BUILD_PART_NONE || build_index(gather_paths_build_at(build_index(gb))) != build_index(gb)) return false;
     }
     return true;
 }
-static_assert(every_launch_has_a_unit(), "select_step_build / select_playout_build give a build no unit compiles");
+static_assert(every_launch_has_a_unit(), "select_step_build / select_playout_build / select_gather_paths_build give a build no unit compiles");
 static_assert(select_step_build(StepShape{PCBENV_PIN, 64, 64, 4, 1, WAVE, 1, 1, false, true, true}, false).geo == STEP_GEO_64 &&
               select_step_build(StepShape{PCBENV_SPATIAL, 64, 64, 4, 1, WAVE, 1, 1, false, true, true}, true).geo == STEP_GEO_64 &&
               step_build_part(PCBENV_SPATIAL, select_step_build(StepShape{PCBENV_SPATIAL, 64, 64, 4, 1, WAVE, 1, 1, false, true, true}, true)) == 4,

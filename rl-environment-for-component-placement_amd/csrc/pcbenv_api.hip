@@ -1,6 +1,6 @@
 // pcbenv_api.hip -- host side of libpcbenv.so's C ABI (include/pcbenv.h): create / destroy / options / bind / load,
 // reset / step / rollout / sample, checkpoint, gather, playout and the logits entry points.  No kernel is defined here: the
-// environment kernels are instantiated per kind in pcb_kind.inc / pcb_playout.inc, k_sample and k_cursor_range in pcb_sample.hip and the
+// environment kernels are instantiated per kind in pcb_kind.inc / pcb_playout.inc / pcb_gather_paths.inc, k_sample and k_cursor_range in pcb_sample.hip and the
 // policy kernels in pcb_policy*.hip (all reached through pcb_launch.h); pcb_config.hip derives the layout from a
 // configuration and pcb_gen.hip owns the on-device instance generator (pcb_host.h declares what the three share).
 #include <stdlib.h>
@@ -22,14 +22,15 @@ extern "C" int pcbenv_abi_version(void) { return PCBENV_ABI_VERSION; }
 
 extern "C" const char *pcbenv_last_error(const pcbenv *env) { return env ? env->err : g_err; }
 
-// The launch functions of an environment kind (pcb_kind.inc, pcb_playout.inc), indexed by pcbenv_config::kind.
+// The launch functions of an environment kind (pcb_kind.inc, pcb_playout.inc, pcb_gather_paths.inc), indexed by pcbenv_config::kind.
 struct KindLaunch {
     int (*step)(const StepLaunch &);
     int (*reset)(const ResetLaunch &);
     int (*gather)(const GatherLaunch &);
     int (*playout)(const PlayoutLaunch &);
+    int (*gather_paths)(const GatherPathsLaunch &);
 };
-#define PCB_KIND_LAUNCH(name) {pcb_launch_step_##name, pcb_launch_reset_##name, pcb_launch_gather_##name, pcb_launch_playout_##name}
+#define PCB_KIND_LAUNCH(name) {pcb_launch_step_##name, pcb_launch_reset_##name, pcb_launch_gather_##name, pcb_launch_playout_##name, pcb_launch_gather_paths_##name}
 static const KindLaunch kind_launch[] = {PCB_KIND_LAUNCH(square), PCB_KIND_LAUNCH(rect), PCB_KIND_LAUNCH(pin), PCB_KIND_LAUNCH(spatial)};
 static_assert(PCBENV_SQUARE == 0 && PCBENV_RECT == 1 && PCBENV_PIN == 2 && PCBENV_SPATIAL == 3, "kind_launch is indexed by kind");
 
@@ -454,10 +455,12 @@ extern "C" int pcbenv_set_state(pcbenv *env, const void *host_src, void *stream)
 // The environment definition is every pcbenv_config field from kind through weight_num_intersections.
 static_assert(offsetof(pcbenv_config, weight_num_intersections) + sizeof(double) == offsetof(pcbenv_config, num_envs),
               "the definition fields end where the batch fields begin");
-extern "C" int pcbenv_gather(pcbenv *dst, const pcbenv *src, const int32_t *src_index_dev, uint32_t *errors_dev, void *stream) {
-    if (!dst) return fail(0, PCBENV_EINVAL, "null handle");
+// What pcbenv_gather and pcbenv_gather_paths do once their own arguments have passed (dst and src_index_dev are not
+// null): the checks of the two handles, the parameter block, the same-handle snapshot, the launch -- k_gather, or with
+// `paths` k_gather_paths -- then the set swap or, for a handle that works in place, the copy back.
+static int gather_enqueue(pcbenv *dst, const pcbenv *src, const int32_t *src_index_dev, uint32_t *errors_dev, void *stream,
+                          const GatherPathArgs *paths, const char *captured) {
     if (!src) src = dst;
-    if (!src_index_dev) return fail(dst, PCBENV_EINVAL, "null src_index");
     if (src != dst) {
         if (src->device != dst->device) return fail(dst, PCBENV_EINVAL, "the two handles are on different devices");
         if (memcmp(&src->cfg, &dst->cfg, offsetof(pcbenv_config, num_envs)) != 0)
@@ -467,11 +470,12 @@ extern "C" int pcbenv_gather(pcbenv *dst, const pcbenv *src, const int32_t *src_
     DEVICE_GUARD(dst);
     hipStream_t s = (hipStream_t)stream;
     // A captured launch would be replayed with the state sets of the capture: the second replay would read a stale set.
-    if (stream_capturing(s)) return fail(dst, PCBENV_ESTATE, "pcbenv_gather cannot be captured into a graph");
-    GatherLaunch a;
+    if (stream_capturing(s)) return fail(dst, PCBENV_ESTATE, captured);
+    GatherPathsLaunch a;
     a.d = dst->dp;
     DevParams &d = a.d;
     a.threads = dst->threads; a.stream = s;
+    a.routes = pcb_layout::routes_compiled_in(dst->cfg.kind, dst->cfg.reward_type);
     // the store policy a trajectory-layout step launch would use (dispatch_step)
     if (d.num_slots > 1) d.stream_stores = stream_stores(dst, d.num_slots);
     d.state = dst->state_buf[dst->state_cur];
@@ -491,7 +495,12 @@ extern "C" int pcbenv_gather(pcbenv *dst, const pcbenv *src, const int32_t *src_
     } else {
         g.reward = sp.buf.reward + r0; g.info = sp.buf.info ? sp.buf.info + 2 * r0 : 0; g.done = sp.buf.done + r0;
     }
-    kind_launch[dst->cfg.kind].gather(a);
+    if (paths) {
+        a.q = *paths;
+        kind_launch[dst->cfg.kind].gather_paths(a);
+    } else {
+        kind_launch[dst->cfg.kind].gather(GatherLaunch{a.d, a.g, a.threads, a.stream});
+    }
     HIP_TRY(dst, hipGetLastError());
     dst->has_episode = true;
     if (dst->in_place) {  // a captured graph works on the current set (dispatch_step): the gathered blocks go back into it
@@ -501,6 +510,29 @@ extern "C" int pcbenv_gather(pcbenv *dst, const pcbenv *src, const int32_t *src_
     dst->state_cur ^= 1;
     dst->dp.state = dst->dp.state_out = dst->state_buf[dst->state_cur];
     return PCBENV_OK;
+}
+
+extern "C" int pcbenv_gather(pcbenv *dst, const pcbenv *src, const int32_t *src_index_dev, uint32_t *errors_dev, void *stream) {
+    if (!dst) return fail(0, PCBENV_EINVAL, "null handle");
+    if (!src_index_dev) return fail(dst, PCBENV_EINVAL, "null src_index");
+    return gather_enqueue(dst, src, src_index_dev, errors_dev, stream, 0, "pcbenv_gather cannot be captured into a graph");
+}
+
+// ---- pcbenv_gather_paths -------------------------------------------------------------------------------------
+// pcbenv_gather with a path of forced actions per row, applied in the same launch (k_gather_paths); the arguments in a
+// struct (the stream among them).  Every argument check comes before a device is touched, the null handle behind them.
+extern "C" int pcbenv_gather_paths(pcbenv *dst, const pcbenv_gather_paths_request *q) {
+    if (!q) return fail(dst, PCBENV_EINVAL, "null request");
+    if (q->struct_size != (uint32_t)sizeof(pcbenv_gather_paths_request)) return fail(dst, PCBENV_EINVAL, "struct_size is not sizeof(pcbenv_gather_paths_request)");
+    CHECK_ACTION_FORMAT(dst, q->action_format);
+    if (q->path_steps < 0) return fail(dst, PCBENV_EINVAL, "path_steps must not be negative");
+    if (q->path_steps > 0 && !q->path_actions_dev) return fail(dst, PCBENV_EINVAL, "null path_actions with path_steps > 0");
+    if (!q->src_index_dev) return fail(dst, PCBENV_EINVAL, "null src_index");
+    if (!dst) return fail(0, PCBENV_EINVAL, "null handle");
+    GatherPathArgs g;
+    g.path_actions = q->path_actions_dev; g.path_len = q->path_len_dev; g.length = q->length_dev;
+    g.fmt = q->action_format; g.path_steps = q->path_steps;
+    return gather_enqueue(dst, q->src, q->src_index_dev, q->errors_dev, q->stream, &g, "pcbenv_gather_paths cannot be captured into a graph");
 }
 
 // ---- pcbenv_playout ------------------------------------------------------------------------------------------

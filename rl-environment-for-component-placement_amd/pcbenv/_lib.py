@@ -31,7 +31,8 @@ EXPORTS = ("pcbenv_abi_version", "pcbenv_create", "pcbenv_destroy", "pcbenv_last
            "pcbenv_instgen_device_enable", "pcbenv_instgen_device_status", "pcbenv_get_instances",
            "pcbenv_instgen_create", "pcbenv_instgen_destroy", "pcbenv_instgen_next", "pcbenv_instgen_next_batch",
            "pcbenv_gather", "pcbenv_sample_logits", "pcbenv_evaluate_logits", "pcbenv_evaluate_logits_backward",
-           "pcbenv_sample_axis", "pcbenv_evaluate_axis", "pcbenv_evaluate_axis_backward", "pcbenv_playout", "pcbenv_playout_paths", "pcbenv_tree_advance")
+           "pcbenv_sample_axis", "pcbenv_evaluate_axis", "pcbenv_evaluate_axis_backward", "pcbenv_playout", "pcbenv_playout_paths", "pcbenv_tree_advance",
+           "pcbenv_gather_paths")
 
 
 class PcbenvConfig(C.Structure):
@@ -67,6 +68,13 @@ class PcbenvPlayoutRequest(C.Structure):
                 ("reward_dev", C.c_void_p), ("done_dev", C.c_void_p), ("length_dev", C.c_void_p), ("info_dev", C.c_void_p),
                 ("actions_out_dev", C.c_void_p), ("actions_steps", C.c_int32), ("leaf_mask_bits_dev", C.c_void_p), ("errors_dev", C.c_void_p),
                 ("seed", C.c_uint64), ("first_env_index", C.c_uint64), ("step_index0", C.c_uint64), ("stream", C.c_void_p)]
+
+
+class PcbenvGatherPathsRequest(C.Structure):
+    """pcbenv_gather_paths_request (include/pcbenv.h), the arguments of pcbenv_gather_paths."""
+    _fields_ = [("struct_size", C.c_uint32), ("action_format", C.c_int32), ("src", C.c_void_p), ("src_index_dev", C.c_void_p),
+                ("path_actions_dev", C.c_void_p), ("path_len_dev", C.c_void_p), ("path_steps", C.c_int32), ("length_dev", C.c_void_p),
+                ("errors_dev", C.c_void_p), ("stream", C.c_void_p)]
 
 
 TREE_TENSORS = ("num_nodes", "parent", "depth", "visits", "num_children", "node_action", "children", "value_sum", "value_max", "terminal",
@@ -142,6 +150,7 @@ def load():
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     L.pcbenv_playout_paths.argtypes = [C.c_void_p, C.POINTER(PcbenvPlayoutRequest)]
     L.pcbenv_tree_advance.argtypes = [C.c_void_p, C.POINTER(PcbenvTreeRequest)]
+    L.pcbenv_gather_paths.argtypes = [C.c_void_p, C.POINTER(PcbenvGatherPathsRequest)]
     L.pcbenv_mask_bits.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.pcbenv_mask_bits.restype = C.c_void_p
     if L.pcbenv_abi_version() != ABI_VERSION:

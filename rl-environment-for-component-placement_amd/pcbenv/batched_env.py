@@ -602,7 +602,8 @@ class BatchedPlacementEnv:
             int(step_index0), self._stream()), self._h)
         return out
 
-    def gather_(self, index: torch.Tensor, source: Optional["BatchedPlacementEnv"] = None, check: bool = False) -> Dict[str, torch.Tensor]:
+    def gather_(self, index: torch.Tensor, source: Optional["BatchedPlacementEnv"] = None, check: bool = False,
+                paths: Optional[torch.Tensor] = None, path_len: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """Fork / reorder episodes on the device (`pcbenv_gather`, one kernel launch, no host round trip): environment i
         continues the episode in progress of environment `index[i]` of `source` (default: this environment batch; any
         permutation or repetition), `-1` keeps i's own episode.  `source` needs an equal definition (the same EnvConfig;
@@ -610,11 +611,23 @@ class BatchedPlacementEnv:
         (selected slot) then equals what `index[i]` showed, and later steps of i go as those of `index[i]` would have.  The
         instance stream stays i's own: its next reset takes its own next instance (the one difference from
         `copy.deepcopy` of a reference env).  check=True raises IndexError if an index was out of range (such rows keep
-        their episode); it synchronises the host, so it is off by default."""
+        their episode); it synchronises the host, so it is off by default.
+
+        Tree nodes named by a path (`pcbenv_gather_paths`, still one kernel launch; taken when `paths` or `path_len` is
+        given): paths, int32 [D, B, 3] or flat [D, B], step-major like `playout(paths=...)`: after the fork, environment i
+        alone makes transitions t < path_len[i] with action paths[t, i], as `step` would on a batch with auto_reset=False,
+        and stops behind the first one that reports done.  The observations show the state after the last transition
+        applied; reward / done / info are that transition's (with none applied: the forked row's).  A bad path action
+        ends the row's path there with the worst-case reward, as `step` would.  It never resets.  path_len: int32 [B],
+        default D for every row; a value outside [0, D] keeps the row's episode like a bad index (check=True raises on it
+        too).  The number of transitions applied to every row is left in `self.gather_length`, int32 [B] on the device
+        (0 for rows that kept their episode); without `paths` / `path_len` that attribute is left as it was."""
         src = self if source is None else source
         idx = index.to(device=self.device, dtype=torch.int32).contiguous()
         if tuple(idx.shape) != (self.num_envs,):
             raise ValueError(f"index must have shape [{self.num_envs}], got {tuple(idx.shape)}")
+        if paths is not None or path_len is not None:
+            return self._gather_paths(src, idx, check, paths, path_len)
         err = torch.zeros(1, dtype=torch.int32, device=self.device) if check else None
         # reset_done() reads _last_done: the kernel carries `done` of the selected slots over; where _last_done lives in
         # another slot (either side), the forked rows' flags are taken from the source's _last_done here, before the launch
@@ -628,6 +641,46 @@ class BatchedPlacementEnv:
             self._last_done = torch.where(taken, forked, self._last_done)
         if check and int(err.item()) != 0:
             raise IndexError(f"gather_: an index is outside [-1, {src.num_envs}) (those environments kept their episode)")
+        return self.obs
+
+    def _gather_paths(self, src, idx, check, paths, path_len):
+        """`gather_` with paths: the shapes and the format detection are those of `playout(paths=...)`."""
+        B, fmt, pa, pl, D = self.num_envs, _lib.ACTION_TUPLE, None, None, 0
+        if paths is not None:
+            pa = paths.to(device=self.device, dtype=torch.int32).contiguous()
+            if pa.dim() not in (2, 3) or pa.shape[1] != B or (pa.dim() == 3 and pa.shape[2] != 3):
+                raise ValueError(f"paths must have shape [D, {B}] (flat) or [D, {B}, 3], got {tuple(pa.shape)}")
+            D = pa.shape[0]
+            if pa.dim() == 2:
+                fmt = _lib.ACTION_FLAT
+        if path_len is not None:
+            pl = path_len.to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(pl.shape) != (B,):
+                raise ValueError(f"path_len must have shape [{B}], got {tuple(pl.shape)}")
+        err = torch.zeros(1, dtype=torch.int32, device=self.device) if check else None
+        length = torch.empty(B, dtype=torch.int32, device=self.device)
+        # as in gather_: where _last_done lives in another slot (either side), the rows without a transition take the
+        # source's flag from here; the rows with one take the `done` the kernel wrote
+        in_slot = (self._last_done.data_ptr() == self.done.data_ptr() and src._last_done.data_ptr() == src.done.data_ptr())
+        if not in_slot:
+            taken = (idx >= 0) & (idx < src.num_envs)
+            if pl is not None:
+                taken &= (pl >= 0) & (pl <= D)
+            forked = src._last_done[idx.long().clamp(0, src.num_envs - 1)]
+        ptr = lambda t: None if t is None else t.data_ptr()
+        req = _lib.PcbenvGatherPathsRequest(
+            struct_size=C.sizeof(_lib.PcbenvGatherPathsRequest), action_format=fmt, src=None if src is self else src._h,
+            src_index_dev=idx.data_ptr(), path_actions_dev=ptr(pa) if D > 0 else None, path_len_dev=ptr(pl), path_steps=D,
+            length_dev=length.data_ptr(), errors_dev=ptr(err), stream=self._stream().value)
+        _lib.check(self._L.pcbenv_gather_paths(self._h, C.byref(req)), self._h)
+        self.gather_length = length
+        if not in_slot:
+            self._last_done = torch.where(length > 0, self.done, torch.where(taken, forked, self._last_done))
+        if check:
+            bits = int(err.item())
+            if bits:
+                raise IndexError(f"gather_: an index is outside [-1, {src.num_envs}) or a path_len outside [0, {D}] "
+                                 f"(error bits {bits}; those environments kept their episode)")
         return self.obs
 
     def playout(self, k: Optional[int] = None, index: Optional[torch.Tensor] = None, step_index: int = 0,

@@ -14,6 +14,10 @@ actions the same way: k playouts behind each candidate, the forced first action 
 `BatchedPlacementEnv.playout(paths=...)` (pcbenv_playout_paths) -- one launch per iteration for all roots, no planner
 batch, no node ever materialised.  `tree_search_device` is the same search with the tree kept by the device
 (pcbenv_tree_advance): two launches per iteration and no tensor operation between them.
+
+`policy_backend` replaces the uniform rollout of either search by a policy's: the node a path names is materialised
+in a planner batch by `gather_(paths=...)` (pcbenv_gather_paths, one launch), and the rollout behind it draws from the
+logits a network gives for the planner's observations.
 """
 from __future__ import annotations
 
@@ -248,6 +252,62 @@ def tree_search(root, iterations: int, step_index: int, c_uct: float = 1.0, max_
                       children[:, :N, :C])
 
 
+def policy_backend(root, planner, logits_fn, greedy=False):
+    """A `backend` for `tree_search` / `tree_search_device` that plays the rollout behind the path with a POLICY instead
+    of the uniform draw: `(paths, path_len, step_index0) -> Playout`.  planner: P = root.num_envs environments of the
+    root's definition with auto_reset=False, the root's run_seed and first_env_index 0.  logits_fn(obs) -> logits as
+    `planner.sample_logits` takes them (a network on the planner's observation dict).
+
+    One call: `planner.gather_(arange(P), source=root, paths=paths, path_len=path_len)` materialises the P nodes the paths
+    name (pcbenv_gather_paths, one launch); then for every absolute transition index t = 0 .. max_steps - 1 (max_steps =
+    paths.shape[0]) one `logits_fn`, one `planner.sample_logits(..., step_index=step_index0 + t)` and one `planner.step`
+    -- a fixed number of launches and no host synchronisation, as in `best_of_k`.  Row i takes part from t = path_len[i]
+    on: before that it is handed an action that is no action, (-1, -1, -1), which leaves its state and observations as
+    they are (an invalid action is a terminal transition with the state unchanged, and there is no done latch); its
+    reward / done of those launches are not looked at.  The draw of transition t has the key (run_seed, i, step_index0 +
+    t), that of `root.playout(paths=...)`: constant logits give that call's playouts bit for bit.
+
+    Returns Playout(reward, done, length, info, actions): reward / length / info of each row's first `done` (rows that
+    ended on the path report what `gather_` reported; a row cut at max_steps reports its last transition and done = 0);
+    actions[t] is the path as given for t < path_len, the action drawn for path_len <= t < length, zero behind."""
+    from .batched_env import Playout
+    from .config import KIND_PIN, KIND_SPATIAL
+    P = int(planner.num_envs)
+    if P != int(root.num_envs):
+        raise ValueError(f"the planner needs {int(root.num_envs)} environments, it has {P}")
+    if planner.auto_reset:
+        raise ValueError("the planner must be created with auto_reset=False (a row's episode ends at its first done)")
+    if planner.run_seed != root.run_seed or planner.first_env_index != 0:
+        raise ValueError("the planner must have the root's run_seed and first_env_index 0 (the keys of the draws)")
+
+    def backend(paths, path_len, step_index0):
+        dev, T = planner.device, int(paths.shape[0])
+        planner.gather_(torch.arange(P, dtype=torch.int32, device=dev), source=root, paths=paths, path_len=path_len)
+        plen = path_len.to(device=dev, dtype=torch.int64)
+        pins = getattr(getattr(planner, "cfg", None), "kind", None) in (KIND_PIN, KIND_SPATIAL)  # the kinds with an info row
+        length = planner.gather_length.to(torch.int64)
+        finished = (length > 0) & planner.done.bool()  # the episode ended on the path
+        reward, done = planner.reward.clone(), finished.clone()
+        info = planner.info_raw.clone() if pins else None
+        actions = paths.to(device=dev, dtype=torch.int32).clone()
+        no_action = torch.full((P, 3), -1, dtype=torch.int32, device=dev)
+        for t in range(T):
+            drawn, _, _ = planner.sample_logits(logits_fn(planner.obs), step_index=int(step_index0) + t, greedy=greedy)
+            held = plen > t
+            _, r, d, _ = planner.step(torch.where(held[:, None], no_action, drawn))
+            live = ~held & ~finished
+            actions[t] = torch.where(held[:, None], actions[t], torch.where(live[:, None], drawn, torch.zeros_like(drawn)))
+            reward = torch.where(live, r, reward)
+            if pins:
+                info = torch.where(live[:, None], planner.info_raw, info)
+            length = torch.where(live, torch.full_like(length, t + 1), length)
+            first = live & d.bool()
+            done |= first
+            finished |= first
+        return Playout(reward, done.to(torch.uint8), length.to(torch.int32), info, actions)
+    return backend
+
+
 @dataclass
 class DeviceTreeSearch(TreeSearch):
     """What `tree_search_device` returns: `TreeSearch`, and the error word of the launches."""
@@ -302,7 +362,7 @@ def tree_result(tree: dict) -> DeviceTreeSearch:
 
 
 def tree_search_device(root, iterations: int, step_index: int, c_uct: float = 1.0, max_children: int = 4, max_steps=None,
-                       capacity=None) -> DeviceTreeSearch:
+                       capacity=None, backend=None) -> DeviceTreeSearch:
     """`tree_search` with the tree kept by the device: an iteration is two kernel launches, `root.tree_advance`
     (pcbenv_tree_advance: backup of the last playout, expansion, the next selection) and `root.playout(paths=...)`, with
     no tensor operation between them.  The same search as `tree_search(root, iterations, step_index, c_uct, max_children,
@@ -310,7 +370,8 @@ def tree_search_device(root, iterations: int, step_index: int, c_uct: float = 1.
     selection differ only by the rounding of a logarithm (the table of ln n is torch's float64 log on the CPU).
     capacity: node slots per root, default iterations + 1 (what the search can use at most).  A smaller tree stops growing
     when it is full -- later playouts are backed up into existing nodes -- and reports bit 0 in `errors`; ln n is then
-    taken at n = capacity for larger n.  max_children is 64 at most."""
+    taken at n = capacity for larger n.  max_children is 64 at most.  backend: as in `tree_search` (for instance
+    `policy_backend`), called in place of `root.playout`; its reward / length / actions must be on the root's device."""
     from . import _lib
     from .batched_env import default_max_steps
     P, C, M = int(root.num_envs), int(max_children), int(iterations)
@@ -321,7 +382,9 @@ def tree_search_device(root, iterations: int, step_index: int, c_uct: float = 1.
     tree = new_tree(P, N, C, T, root.device)
     req = root.tree_request(tree, c_uct)
     root.tree_advance(req, _lib.TREE_INIT | _lib.TREE_SELECT)
+    if backend is None:
+        backend = lambda paths, path_len, s: root.playout(k=1, step_index=s, paths=paths, path_len=path_len, max_steps=T)
     for m in range(M):
-        po = root.playout(k=1, step_index=int(step_index) + m * T, paths=tree["paths"], path_len=tree["path_len"], max_steps=T)
+        po = backend(tree["paths"], tree["path_len"], int(step_index) + m * T)
         root.tree_advance(req, _lib.TREE_ABSORB | (_lib.TREE_SELECT if m + 1 < M else 0), po.reward, po.length, po.actions)
     return tree_result(tree)

@@ -1,5 +1,5 @@
 """Receding-horizon Monte-Carlo lookahead with pcbenv.search.best_of_k against the plain uniform-random policy, c3.
-python tools/search_demo.py [--roots 256] [--k 16] [--playouts | --tree [--device-tree]]
+python tools/search_demo.py [--roots 256] [--k 16] [--playouts | --tree [--device-tree] [--policy]]
 
 Both play the same instances (one episode per root environment).  The search forks every root k times into a planner
 batch (one device-side gather), plays every child to its end with the on-device sampler, and applies the best child's
@@ -8,7 +8,10 @@ one pcbenv_playout launch per search step instead of a planner batch and a launc
 planner env-steps/s (wall time of the best_of_k calls).  --tree: pcbenv.search.tree_search with k iterations per move -- the
 same number of playouts as best-of-k, spent by UCT on a tree of paths (one pcbenv_playout_paths launch per iteration) -- and
 the most-visited first action is applied.  --tree --device-tree: the same search through pcbenv.search.tree_search_device, the
-tree kept by the device (pcbenv_tree_advance): two launches per iteration."""
+tree kept by the device (pcbenv_tree_advance): two launches per iteration.  --tree --policy (a spatial configuration:
+--config c4): the rollout behind every path is played by a policy instead of the uniform draw -- pcbenv.search.policy_backend
+materialises the nodes in a planner batch (pcbenv_gather_paths) and draws from the logits of pcbenv/policy.py's model with
+its initial weights (seeded, untrained: the demo shows the plumbing, not a trained policy's strength)."""
 import argparse
 import json
 import os
@@ -20,7 +23,8 @@ import torch  # noqa: E402
 
 from pcbenv import named_config  # noqa: E402
 from pcbenv.batched_env import BatchedPlacementEnv  # noqa: E402
-from pcbenv.search import best_of_k, best_of_k_playouts, tree_search, tree_search_device  # noqa: E402
+from pcbenv.config import KIND_SPATIAL  # noqa: E402
+from pcbenv.search import best_of_k, best_of_k_playouts, policy_backend, tree_search, tree_search_device  # noqa: E402
 
 
 def final_rewards(env, act, T):
@@ -44,10 +48,15 @@ def main():
     ap.add_argument("--playouts", action="store_true", help="search with best_of_k_playouts (no planner batch)")
     ap.add_argument("--tree", action="store_true", help="search with tree_search, k iterations per move (no planner batch)")
     ap.add_argument("--device-tree", action="store_true", help="with --tree: tree_search_device (the tree on the device)")
+    ap.add_argument("--policy", action="store_true", help="with --tree: rollouts by pcbenv/policy.py's model (initial weights) through policy_backend")
     a = ap.parse_args()
     if a.device_tree and not a.tree:
         ap.error("--device-tree goes with --tree")
+    if a.policy and not a.tree:
+        ap.error("--policy goes with --tree")
     cfg = named_config(a.config)
+    if a.policy and cfg.kind != KIND_SPATIAL:
+        ap.error("--policy needs a spatial configuration, the one pcbenv/policy.py's model reads (--config c4)")
     P, k, T = a.roots, a.k, cfg.max_num_components
 
     def make(n, seed):
@@ -56,7 +65,17 @@ def main():
         e.reset()
         return e
     rand_root, search_root = make(P, 11), make(P, 11)
-    planner = None if a.playouts or a.tree else make(P * k, 12)
+    planner = make(P, 11) if a.policy else None if a.playouts or a.tree else make(P * k, 12)  # (policy_backend: the root's run seed)
+    backend = None
+    if a.policy:
+        from pcbenv.policy import SpatialPolicy
+        torch.manual_seed(0)
+        model = SpatialPolicy(cfg).to(search_root.device).eval()
+
+        def logits_fn(obs):
+            with torch.no_grad():
+                return model(obs, mask=False)[0].contiguous()
+        backend = policy_backend(search_root, planner, logits_fn)
 
     random_final = final_rewards(rand_root, lambda t: rand_root.rollout_step(t)[1:3], T)
     torch.cuda.synchronize()
@@ -67,7 +86,7 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if a.tree:
-            first = (tree_search_device if a.device_tree else tree_search)(search_root, k, step_index=1000 + t * T * k).action
+            first = (tree_search_device if a.device_tree else tree_search)(search_root, k, step_index=1000 + t * T * k, backend=backend).action
         elif a.playouts:
             res = best_of_k_playouts(search_root, k, step_index=1000 + t * T)
         else:
@@ -78,7 +97,7 @@ def main():
         _, r, d, _ = search_root.step(first if a.tree else res.actions[0])
         return r, d
     search_final = final_rewards(search_root, search_step, T)
-    out = {"config": a.config, "roots": P, "k": k, "search": "tree_search_device" if a.device_tree else "tree_search" if a.tree else "best_of_k_playouts" if a.playouts else "best_of_k",
+    out = {"config": a.config, "roots": P, "k": k, "search": ("tree_search_device" if a.device_tree else "tree_search") + ("+policy_backend" if a.policy else "") if a.tree else "best_of_k_playouts" if a.playouts else "best_of_k",
            "random_policy_mean_final_reward": float(random_final.mean()),
            "best_of_k_mean_final_reward": float(search_final.mean()),
            "search_env_steps_per_sec": round(planner_steps / spent), "search_seconds": round(spent, 3)}
