@@ -4,7 +4,9 @@
 hipcc cross-compiles without a GPU.  -ffp-contract=off: one IEEE operation per written operator (the reward path
 must match the reference bit for bit).  The kernels of the four environment kinds are separate translation units
 compiled in parallel -- csrc/pcb_kind.inc, csrc/pcb_playout.inc for pcbenv_playout and pcbenv_playout_paths, and
-csrc/pcb_gather_paths.inc for pcbenv_gather_paths, each compiled once per row of UNITS below with that row's -D flags -- then linked with the host side -- the C ABI
+csrc/pcb_gather_paths.inc for pcbenv_gather_paths, each compiled once per row of UNITS below with that row's -D flags: the
+kind (a template argument in the sources), the part and, for the second family of k_playout, PCB_PATHS -- then linked with
+the host side -- the C ABI
 (csrc/pcbenv_api.hip), the layout derivation (csrc/pcb_config.hip) and the on-device instance generator with its kernels
 (csrc/pcb_gen.hip), which share csrc/pcb_host.h -- the two kernels every kind uses (csrc/pcb_sample.hip), the policy kernels
 (csrc/pcb_policy*.hip), the tree step with its entry point (csrc/pcb_tree.hip) and the host instance generator
@@ -22,12 +24,13 @@ CSRC = os.path.join(HERE, "csrc")
 
 def unit(stem, source, kind, part=None, paths=False):
     """One row of UNITS: csrc/<source> compiled for one kind, part (pin kinds) and kernel family into <stem>_<kind>[_<part>].hip.o."""
-    defs = [f"-DPCB_KIND=PCBENV_{kind.upper()}", f"-DPCB_KIND_NAME={kind}"] + ([f"-DPCB_PART={part}"] if part is not None else [])
+    defs = [f"-DPCB_KIND=PCBENV_{kind.upper()}"] + ([f"-DPCB_PART={part}"] if part is not None else [])
     return (f"{stem}_{kind}" + (f"_{part}" if part is not None else "") + ".hip.o", source, ["-x", "hip"] + defs + (["-DPCB_PATHS=1"] if paths else []))
 
 
 # The table of translation units: (object, source, flags of its own), slowest first.  What a part of a pin kind compiles
-# is not said here: pcb_layout::step_build_part / playout_build_part (csrc/pcb_layout.h) decide it inside the source.
+# is not said here: pcb_layout::step_build_part / playout_build_part / gather_paths_build_part (csrc/pcb_layout.h) decide
+# it inside the source, and the host side calls exactly the parts some build maps to (csrc/pcb_launch.h launch_family).
 PIN_KINDS, FLAT_KINDS = ("spatial", "pin"), ("rect", "square")
 UNITS = ([unit("pcb_kind", "pcb_kind.inc", k) for k in FLAT_KINDS[::-1]]
          + [unit("pcb_kind", "pcb_kind.inc", k, p) for p in (2, 3, 0, 4, 1) for k in PIN_KINDS]

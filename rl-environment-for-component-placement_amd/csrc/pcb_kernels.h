@@ -1,7 +1,7 @@
 // pcb_kernels.h -- the __global__ kernel templates of the environment kinds: k_reset, k_gather, k_step
 // Part of libpcbenv.so (CDNA4 / gfx950 only).
 #pragma once
-#include "pcb_team.h"
+#include "pcb_walk.h"
 #include "pcb_launch.h"
 
 template <int KIND, int WW, int NW>
@@ -31,13 +31,8 @@ __global__ __launch_bounds__(64 * NW) void k_reset(DevParams p, const unsigned c
 // launch writes), and every bound tensor of the destination's selected slot written whole from LDS -- the emission of a
 // trajectory slot, where nothing may be assumed about what the destination holds.  Rows with j == -1 or j out of
 // range keep their episode: their block is copied as it is, and none of their tensors is touched.
-// What the header must not take over from the source:
-//   qcursor, episode  the destination's instance stream: its next reset takes its own next record.  feat_cache_valid
-//                     compares the cache tag with `episode`, so the spatial cache is refilled below under that tag;
-//   term_seq / pos    a copied terminal-list mark would claim the source's list entry in the next step launch
-//                     (MODE_DELEGATED waiting for helpers that work on another environment): not listed;
-//   pre_action        drawn from the source's mask for the source's global index: cleared;
-//   feat_gen          the destination's bind generation: its pin-feature rows are written whole here.
+// The header patch and the emission are pcb_walk.h's text, which k_gather_paths expands too; it says what the header must
+// not take over from the source, and why.
 template <int KIND, int WW, int NW>
 __global__ __launch_bounds__(64 * NW) void k_gather(DevParams p, GatherArgs g) {
     typedef Team<64 * NW> T;
@@ -50,24 +45,10 @@ __global__ __launch_bounds__(64 * NW) void k_gather(DevParams p, GatherArgs g) {
     T::load_state_from(smem, take ? g.src_state + (size_t)j * p.stateStride : own, p, lane);
     Lds l = carve(smem, p);
     if (take) {
-        if (lane == 0) {
-            const EnvHdr *oh = (const EnvHdr *)own;
-            l.hdr->qcursor = oh->qcursor; l.hdr->episode = oh->episode;
-            l.hdr->term_seq = 0u; l.hdr->term_pos = 0u;
-            l.hdr->pre_action = 0u;
-            if (KIND == PCBENV_PIN || KIND == PCBENV_SPATIAL) l.hdr->feat_gen = p.bind_gen;
-        }
+        PCB_GATHER_PATCH_HEADER(own, lane)
         T::lds_sync();
         const int row = out_row(p, p.slot, e);
-        if (KIND == PCBENV_SPATIAL) T::build_pin_tables(p, l, lane);
-        T::template emit_features_full<KIND>(p, l, row, lane);
-        if (KIND == PCBENV_SPATIAL) {
-            T::emit_component_grid(p, l, row, lane);  // from the pin tables (unrotated coordinates)
-            T::feat_cache_fill(p, l, e, lane);        // trajectory layout: what this episode's steps copy, tagged with `episode`
-            T::lds_sync();                            // the tables share their zone with the class map of emit_pin_grid
-        }
-        T::template mask_and_emit<KIND, WW>(p, l, row, lane, true, 0, p.H);
-        if (KIND == PCBENV_SPATIAL) T::template emit_pin_grid<WW>(p, l, row, lane, 0, p.H);
+        PCB_GATHER_EMIT_SLOT(e, row, lane)
         if (lane == 0) {
             p.buf.reward[row] = g.reward[j];
             p.buf.done[row] = g.done[j];

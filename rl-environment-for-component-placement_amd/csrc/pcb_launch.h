@@ -1,7 +1,8 @@
 // pcb_launch.h -- what the host side (pcbenv_api.hip) and the kernel translation units (pcb_kind.inc, pcb_playout.inc and
-// pcb_gather_paths.inc, once per unit of build.py's table; pcb_sample.hip, pcb_policy*.hip) share: one launch entry per kernel family and
-// environment kind, so that the host side compiles no device code and the kernel instantiations of the four kinds compile
-// in parallel.  Which instantiation an entry launches is pcb_layout::select_step_build / select_playout_build.
+// pcb_gather_paths.inc, once per unit of build.py's table; pcb_sample.hip, pcb_policy*.hip) share: the launch structs and
+// one launch entry per kernel family, so that the host side compiles no device code and the kernel instantiations of the
+// four kinds compile in parallel.  The families compiled per kind and part are described at the end; which instantiation
+// their entries launch is pcb_layout::select_step_build / select_playout_build / select_gather_paths_build.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -140,7 +141,60 @@ int pcb_launch_sample_axis(const SampleAxisLaunch &a);
 int pcb_launch_evaluate_axis(const EvalAxisLaunch &a);
 int pcb_launch_evaluate_axis_backward(const EvalAxisBackwardLaunch &a);
 
-#define PCB_DECLARE_KIND(name) int pcb_launch_step_##name(const StepLaunch &a); int pcb_launch_reset_##name(const ResetLaunch &a); \
-    int pcb_launch_gather_##name(const GatherLaunch &a); int pcb_launch_playout_##name(const PlayoutLaunch &a); \
-    int pcb_launch_gather_paths_##name(const GatherPathsLaunch &a);
-PCB_DECLARE_KIND(square) PCB_DECLARE_KIND(rect) PCB_DECLARE_KIND(pin) PCB_DECLARE_KIND(spatial)
+// ---- the kernel families compiled per environment kind and part (build.py's unit table) -----------------------------------
+// A family names its launch and build structs, numbers its candidate builds and forwards to pcb_layout.h, which alone
+// says which build a launch runs (select) and which part compiles it (part).  launch<KIND, I> enqueues candidate I: the
+// unit that sees the kernel template defines it (pcb_kind.inc, pcb_playout.inc, pcb_gather_paths.inc).
+struct StepFamily {
+    typedef StepLaunch Launch;
+    typedef pcb_layout::StepBuild Build;
+    static constexpr int builds = STEP_BUILDS, parts = STEP_PARTS;
+    static constexpr Build build_at(int i) { return pcb_layout::step_build_at(i); }
+    static constexpr int part(int kind, const Build &b) { return pcb_layout::step_build_part(kind, b); }
+    static Build select(const Launch &a) { return pcb_layout::select_step_build(step_shape(a), a.d.stream_stores != 0); }
+    template <int KIND, int I> static void launch(const Launch &a);
+};
+struct PlayoutFamily {  // (k_playout's PATHS = true builds have units of their own: playout_build_unit counts them as further parts)
+    typedef PlayoutLaunch Launch;
+    typedef pcb_layout::PlayoutBuild Build;
+    static constexpr int builds = PLAYOUT_BUILDS, parts = 2 * PLAYOUT_PARTS;
+    static constexpr Build build_at(int i) { return pcb_layout::playout_build_at(i); }
+    static constexpr int part(int kind, const Build &b) { return pcb_layout::playout_build_unit(kind, b); }
+    static Build select(const Launch &a) { return pcb_layout::select_playout_build(a.d.WW, a.threads, a.routes, a.paths); }
+    template <int KIND, int I> static void launch(const Launch &a);
+};
+struct GatherPathsFamily {
+    typedef GatherPathsLaunch Launch;
+    typedef pcb_layout::GatherPathsBuild Build;
+    static constexpr int builds = GATHER_PATHS_BUILDS, parts = PLAYOUT_PARTS;
+    static constexpr Build build_at(int i) { return pcb_layout::gather_paths_build_at(i); }
+    static constexpr int part(int kind, const Build &b) { return pcb_layout::gather_paths_build_part(kind, b); }
+    static Build select(const Launch &a) { return pcb_layout::select_gather_paths_build(a.d.WW, a.threads, a.routes); }
+    template <int KIND, int I> static void launch(const Launch &a);
+};
+// Whether build.py's table has a unit for part `part` of family F and kind `kind`: some candidate is that part's.
+template <class F> constexpr bool part_exists(int kind, int part) {
+    for (int i = 0; i < F::builds; i++)
+        if (F::part(kind, F::build_at(i)) == part) return true;
+    return false;
+}
+// Build b of family F, which F::part gives part PART, launched from the unit that compiles it: pcb_dispatch.h defines
+// this, and each unit instantiates it for its own F, KIND and PART.  0, or -1 if b is not among the unit's candidates.
+template <class F, int KIND, int PART> int launch_in_unit(const typename F::Launch &a, const typename F::Build &b);
+// The entry of family F for kind KIND: selects the build and makes one call into the part that compiles it, among the
+// parts build.py's table has.  -1: no unit compiles b (pcb_layout::every_launch_has_a_unit asserts there is no such launch).
+template <class F, int KIND, int PART = 0> int launch_part(const typename F::Launch &a, const typename F::Build &b, int part) {
+    if constexpr (PART < F::parts) {
+        if constexpr (part_exists<F>(KIND, PART))
+            if (part == PART) return launch_in_unit<F, KIND, PART>(a, b);
+        return launch_part<F, KIND, PART + 1>(a, b, part);
+    }
+    return -1;
+}
+template <class F, int KIND> int launch_family(const typename F::Launch &a) {
+    const typename F::Build b = F::select(a);
+    return launch_part<F, KIND>(a, b, F::part(KIND, b));
+}
+// k_reset and k_gather have one build per team shape and live in part 0 of pcb_kind.inc.
+template <int KIND> int pcb_launch_reset(const ResetLaunch &a);
+template <int KIND> int pcb_launch_gather(const GatherLaunch &a);

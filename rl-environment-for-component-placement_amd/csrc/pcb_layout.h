@@ -175,20 +175,33 @@ PCB_HD inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 #define STEP_GEO_RUNTIME 0
 #define STEP_GEO_64 1
 #define BUILD_PART_NONE (-1)  // no unit compiles that combination: it does not exist
-// The template arguments of k_step<KIND, ww, nw, routes, build, geo> and of k_playout<KIND, ww, nw, routes, paths>.
+// The template arguments every family has -- words per bit row (1 / 2), wavefronts per team (1 / 4), routes -- are the low
+// TEAM_BUILD_BITS bits of its numbering; those of k_step<KIND, ww, nw, routes, build, geo> and of k_playout<KIND, ww, nw,
+// routes, paths> follow them; k_gather_paths<KIND, ww, nw, routes> (pcb_gather_paths.h) has no others.
+struct TeamBuild { int ww, nw; bool routes; };
 struct StepBuild { int ww, nw; bool routes; int build, geo; };
 struct PlayoutBuild { int ww, nw; bool routes, paths; };
-struct GatherPathsBuild { int ww, nw; bool routes; };  // k_gather_paths<KIND, ww, nw, routes> (pcb_gather_paths.h)
-// The candidates, numbered: pcb_kind.inc / pcb_playout.inc walk them and compile those their unit owns.
-#define STEP_BUILDS 64
-#define PLAYOUT_BUILDS 16
-#define GATHER_PATHS_BUILDS 8
-PCB_HD constexpr StepBuild step_build_at(int i) { return StepBuild{1 + (i & 1), (i >> 1 & 1) ? 4 : 1, (i >> 2 & 1) != 0, i >> 3 & 3, i >> 5 & 1}; }
-PCB_HD constexpr PlayoutBuild playout_build_at(int i) { return PlayoutBuild{1 + (i & 1), (i >> 1 & 1) ? 4 : 1, (i >> 2 & 1) != 0, (i >> 3 & 1) != 0}; }
-PCB_HD constexpr GatherPathsBuild gather_paths_build_at(int i) { return GatherPathsBuild{1 + (i & 1), (i >> 1 & 1) ? 4 : 1, (i >> 2 & 1) != 0}; }
-PCB_HD constexpr int build_index(const StepBuild &b) { return (b.ww - 1) | (b.nw == 4) << 1 | (int)b.routes << 2 | b.build << 3 | b.geo << 5; }
-PCB_HD constexpr int build_index(const PlayoutBuild &b) { return (b.ww - 1) | (b.nw == 4) << 1 | (int)b.routes << 2 | (int)b.paths << 3; }
-PCB_HD constexpr int build_index(const GatherPathsBuild &b) { return (b.ww - 1) | (b.nw == 4) << 1 | (int)b.routes << 2; }
+typedef TeamBuild GatherPathsBuild;
+// The candidates of a family, numbered: pcb_dispatch.h walks them and a unit compiles those that are its part.
+#define TEAM_BUILD_BITS 3
+#define STEP_BUILDS (8 << TEAM_BUILD_BITS)
+#define PLAYOUT_BUILDS (2 << TEAM_BUILD_BITS)
+#define GATHER_PATHS_BUILDS (1 << TEAM_BUILD_BITS)
+PCB_HD constexpr TeamBuild team_build_at(int i) { return TeamBuild{1 + (i & 1), (i >> 1 & 1) ? 4 : 1, (i >> 2 & 1) != 0}; }
+PCB_HD constexpr int build_index(const TeamBuild &b) { return (b.ww - 1) | (b.nw == 4) << 1 | (int)b.routes << 2; }
+PCB_HD constexpr StepBuild step_build_at(int i) {
+    const TeamBuild t = team_build_at(i);
+    return StepBuild{t.ww, t.nw, t.routes, i >> TEAM_BUILD_BITS & 3, i >> (TEAM_BUILD_BITS + 2) & 1};
+}
+PCB_HD constexpr PlayoutBuild playout_build_at(int i) {
+    const TeamBuild t = team_build_at(i);
+    return PlayoutBuild{t.ww, t.nw, t.routes, (i >> TEAM_BUILD_BITS & 1) != 0};
+}
+PCB_HD constexpr GatherPathsBuild gather_paths_build_at(int i) { return team_build_at(i); }
+PCB_HD constexpr int build_index(const StepBuild &b) {
+    return build_index(TeamBuild{b.ww, b.nw, b.routes}) | b.build << TEAM_BUILD_BITS | b.geo << (TEAM_BUILD_BITS + 2);
+}
+PCB_HD constexpr int build_index(const PlayoutBuild &b) { return build_index(TeamBuild{b.ww, b.nw, b.routes}) | (int)b.paths << TEAM_BUILD_BITS; }
 
 // The build of a step launch; stream_stores is the launch's store policy (DevParams::stream_stores).  A launch is of the
 // trajectory layout if it writes one of several slots or makes several transitions.
@@ -209,7 +222,9 @@ PCB_HD constexpr GatherPathsBuild select_gather_paths_build(int WW, int threads,
 // with routes on one / four wavefronts, 1 = without routes into a trajectory slot, 0 = everything else, next to k_reset,
 // k_gather and the entry points (pcb_kind.inc says why the slot build is on its own); k_playout of a pin kind, PATHS or
 // not, and k_gather_paths in units of its own: 0 = without routes, 1 / 2 = with routes on one / four wavefronts.  Square
-// and rect have no routes and one unit.
+// and rect have no routes and one unit.  STEP_PARTS / PLAYOUT_PARTS: one more than the highest part.
+#define STEP_PARTS 5
+#define PLAYOUT_PARTS 3
 PCB_HD constexpr int step_build_part(int kind, const StepBuild &b) {
     if (b.geo == STEP_GEO_64)
         return is_pin_kind(kind) && !b.routes && b.ww == 1 && b.nw == 1 && b.build <= STEP_BUILD_INPLACE_STREAM ? 4 : BUILD_PART_NONE;
@@ -222,6 +237,11 @@ PCB_HD constexpr int playout_build_part(int kind, const PlayoutBuild &b) {
 }
 PCB_HD constexpr int gather_paths_build_part(int kind, const GatherPathsBuild &b) {
     return playout_build_part(kind, PlayoutBuild{b.ww, b.nw, b.routes, true});
+}
+// k_playout's unit, numbered as one family's parts: the PATHS = true builds behind the PLAYOUT_PARTS of the others.
+PCB_HD constexpr int playout_build_unit(int kind, const PlayoutBuild &b) {
+    const int part = playout_build_part(kind, b);
+    return part == BUILD_PART_NONE ? BUILD_PART_NONE : part + (b.paths ? PLAYOUT_PARTS : 0);
 }
 // Every launch of a handle that pcbenv_create admits has a unit, and c3 / c4 in place on one wavefront run the fixed build.
 PCB_HD constexpr bool every_launch_has_a_unit() {

@@ -13,9 +13,10 @@
 //
 // Team<>::transition is not called: that function stores done and reward rows at every transition (the playout's done row
 // is optional and its reward is the LAST transition's only) and carries the reset and every emission under run-time flags,
-// which this kernel would compile in and hold registers for.  The loop below has the same steps around the same text: the
-// arithmetic of a transition is pcb_transition.h's, expanded here as in transition; the draw is Team<>::draw_action, which
-// run_env calls too; window_mask through mask_and_emit(emit = false), sample_action and terminal_reward are the step kernel's
+// which this kernel would compile in and hold registers for.  The loop below has the same steps: the draw is
+// Team<>::draw_action, which run_env calls too; the read of a forced action and the transition itself -- validate, update,
+// barriers, window_mask through mask_and_emit(emit = false), done -- are pcb_walk.h's PCB_READ_FORCED_ACTION and
+// PCB_TRANSITION_NO_OBS, the one statement k_gather_paths expands too; sample_action and terminal_reward are the step kernel's
 // -- the latter through the parameter block, whose buf.reward / buf.info the host points at the
 // playout's rows (every other tensor null, flags and the terminal list zeroed: pcbenv_playout).
 //
@@ -25,7 +26,7 @@
 // transition path_len[i], or after the last transition where the episode ended on the path) go to leaf_mask row i, stored
 // by the whole team, once.  Nothing else differs: with PATHS = false every line added for it is compiled out.
 #pragma once
-#include "pcb_team.h"
+#include "pcb_walk.h"
 #include "pcb_launch.h"
 
 template <int KIND, int WW, int NW, bool ROUTES, bool PATHS>
@@ -70,58 +71,17 @@ __global__ __attribute__((amdgpu_waves_per_eu(PATHS && KIND != PCBENV_PIN && KIN
         if (PATHS && leaf && t == plen) for (int k = lane0; k < 2 * plane; k += NT) leaf[k] = l.vm[k];
         const bool forced = PATHS ? t < plen : (t == 0 && g.first_actions);
         const int *fa = PATHS ? g.path_actions + per_step * (size_t)t : g.first_actions;
-        if (forced) {  // as run_env reads a caller's action: out of range is data (an invalid action), checked before use below
-            if (g.fmt == PCBENV_ACTION_FLAT) {
-                given = fa[i];
-                unflatten_action(given, p.O, HW, W, &o, &x, &y);
-            } else {
-                o = fa[3 * (size_t)i]; x = fa[3 * (size_t)i + 1]; y = fa[3 * (size_t)i + 2];
-                if (KIND == PCBENV_SQUARE) o = 0;
-            }
+        if (forced) {
+            PCB_READ_FORCED_ACTION(fa, g.fmt, i, given, o, x, y)
         } else T::draw_action(p, l, genv, lane, g.seed, g.step_index0 + (u64)t, &o, &x, &y);
         if (lane == 0 && t < g.actions_steps) {
             int *act = g.actions_out + per_step * (size_t)t;
             if (g.fmt == PCBENV_ACTION_FLAT) act[i] = forced ? given : PCB_FLATTEN_ACTION(o, x, y, HW, W);
             else { act[3 * (size_t)i] = o; act[3 * (size_t)i + 1] = x; act[3 * (size_t)i + 2] = y; }
         }
-        // validate_action and the update, as Team<>::transition has them: the text of pcb_transition.h, expanded in place
-        const int cur = l.hdr->cur, ncomp = l.hdr->ncomp, npins = l.hdr->npins;
-        valid = PCB_ACTION_IN_RANGE(o, x, y, p.O, H, W) && (KIND == PCBENV_SQUARE || cur >= 0);
-        if (valid) valid = PCB_LEGAL_BIT(l.vm, (o & 1) * plane, WW, x, y);
-        if (NT > WAVE) T::lds_sync();  // every wavefront has read the cursor and the mask bit before anything below changes them
-        done = true;  // an invalid action is a terminal transition with the state unchanged (quirk Q8 iii)
-        if (valid) {
-            int ph, pw;
-            CompRec cr = CompRec();
-            if (KIND == PCBENV_SQUARE) ph = pw = p.component_n;
-            else {
-                cr = l.comps[cur];
-                ph = PCB_PLACED_H(o, cr.h, cr.w);
-                pw = PCB_PLACED_W(o, cr.h, cr.w);
-            }
-            for (int rr = x + lane; rr < x + ph && rr < H; rr += NT) {
-                PCB_OCCUPY_ROW(l.occ, rr * WW, WW, y, pw)
-            }
-            if (KIND != PCBENV_SQUARE) {
-                if (lane == 0) { l.comps[cur].px = (signed char)x; l.comps[cur].py = (signed char)y; l.comps[cur].o = (unsigned char)o; }
-                if (PINS) {
-                    const int ch = cr.h, cw = cr.w;
-                    for (int q = lane; q < npins; q += NT) {  // S:149-190 place_component
-                        PinRec pr = l.pins[q];
-                        if (pr.comp != cur) continue;
-                        PCB_PLACE_PIN(pr, o, ch, cw, x, y)
-                        l.pins[q] = pr;
-                    }
-                }
-                if (lane == 0) l.hdr->cur = (short)next_component(cur, ncomp);
-            }
-            T::lds_sync();
-            const bool any = T::template mask_and_emit<KIND, WW>(p, l, i, lane, false, 0, 0);  // team-uniform (block_any)
-            done = episode_done<KIND>(l.hdr->cur, any);
-        }
+        PCB_TRANSITION_NO_OBS(i, lane, o, x, y, valid, done)
         length = t + 1;
-        // `done` is team-uniform: valid, cur and `any` are functions of LDS words every wavefront read behind a barrier
-        if (done) break;
+        if (done) break;  // team-uniform
         T::lds_sync();
     }
     if (PATHS && leaf && length <= plen) {  // the episode ended on the path, or was cut at its end: the state it is left in

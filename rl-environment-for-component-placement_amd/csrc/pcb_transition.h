@@ -3,7 +3,8 @@
 // This is the arithmetic that must match the reference bit for bit.  Plain C++17 behind PCB_HD (it includes only
 // pcb_records.h): the step, playout and policy kernels and tools/transition_check.cpp, which replays the recorded reference
 // transitions of tests/golden on the CPU, compile the same text.  Nothing here knows a team size: the loops over rows and
-// pins that stride by it, and the barriers, stay with the callers (Team<>::transition, k_playout).
+// pins that stride by it, and the barriers, stay with the two callers: Team<>::transition (pcb_step.h) and, without
+// observations, PCB_TRANSITION_NO_OBS (pcb_walk.h), which k_playout and k_gather_paths expand.
 //
 // Each piece is a macro with a function of the same name in lower case around it.  The step and playout kernels expand
 // the macros where the text used to stand: an inlined function body reaches the optimiser in another shape than the same expression

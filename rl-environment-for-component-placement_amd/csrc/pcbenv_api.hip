@@ -1,6 +1,6 @@
 // pcbenv_api.hip -- host side of libpcbenv.so's C ABI (include/pcbenv.h): create / destroy / options / bind / load,
 // reset / step / rollout / sample, checkpoint, gather, playout and the logits entry points.  No kernel is defined here: the
-// environment kernels are instantiated per kind in pcb_kind.inc / pcb_playout.inc / pcb_gather_paths.inc, k_sample and k_cursor_range in pcb_sample.hip and the
+// environment kernels are instantiated per kind and part in pcb_kind.inc / pcb_playout.inc / pcb_gather_paths.inc, k_sample and k_cursor_range in pcb_sample.hip and the
 // policy kernels in pcb_policy*.hip (all reached through pcb_launch.h); pcb_config.hip derives the layout from a
 // configuration and pcb_gen.hip owns the on-device instance generator (pcb_host.h declares what the three share).
 #include <stdlib.h>
@@ -22,7 +22,7 @@ extern "C" int pcbenv_abi_version(void) { return PCBENV_ABI_VERSION; }
 
 extern "C" const char *pcbenv_last_error(const pcbenv *env) { return env ? env->err : g_err; }
 
-// The launch functions of an environment kind (pcb_kind.inc, pcb_playout.inc, pcb_gather_paths.inc), indexed by pcbenv_config::kind.
+// The launch functions of an environment kind (pcb_launch.h: the entries of the three families, k_reset and k_gather), indexed by pcbenv_config::kind.
 struct KindLaunch {
     int (*step)(const StepLaunch &);
     int (*reset)(const ResetLaunch &);
@@ -30,9 +30,14 @@ struct KindLaunch {
     int (*playout)(const PlayoutLaunch &);
     int (*gather_paths)(const GatherPathsLaunch &);
 };
-#define PCB_KIND_LAUNCH(name) {pcb_launch_step_##name, pcb_launch_reset_##name, pcb_launch_gather_##name, pcb_launch_playout_##name, pcb_launch_gather_paths_##name}
-static const KindLaunch kind_launch[] = {PCB_KIND_LAUNCH(square), PCB_KIND_LAUNCH(rect), PCB_KIND_LAUNCH(pin), PCB_KIND_LAUNCH(spatial)};
+template <int KIND> static constexpr KindLaunch kind_entries() {
+    return KindLaunch{launch_family<StepFamily, KIND>, pcb_launch_reset<KIND>, pcb_launch_gather<KIND>, launch_family<PlayoutFamily, KIND>, launch_family<GatherPathsFamily, KIND>};
+}
+static const KindLaunch kind_launch[] = {kind_entries<PCBENV_SQUARE>(), kind_entries<PCBENV_RECT>(), kind_entries<PCBENV_PIN>(), kind_entries<PCBENV_SPATIAL>()};
 static_assert(PCBENV_SQUARE == 0 && PCBENV_RECT == 1 && PCBENV_PIN == 2 && PCBENV_SPATIAL == 3, "kind_launch is indexed by kind");
+// A launch function's -1: the build pcb_layout selected is in no unit (pcb_layout::every_launch_has_a_unit asserts that
+// there is no such launch): nothing was enqueued.
+static int launched(pcbenv *env, int rc) { return rc == 0 ? PCBENV_OK : fail(env, PCBENV_EHIP, "no translation unit of the library compiles the kernel build of this launch"); }
 
 // validate, derive, allocate, zero
 extern "C" int pcbenv_create(const pcbenv_config *cfg, int device, pcbenv **out) {
@@ -319,9 +324,10 @@ static int consuming_launch(pcbenv *env, void *stream, Checks checks, Launch lau
     for (int t = 0; t < plan.launches; t++) {
         rc = gen_before_launch(env, plan.consumes, s);
         if (rc) return rc;
-        launch(t, s);
+        const int launch_rc = launch(t, s);
         if (t == plan.launches - 1) HIP_TRY(env, hipGetLastError());
         gen_after_launch(env, plan.consumes, s);
+        if (launched(env, launch_rc)) return PCBENV_EHIP;
     }
     return PCBENV_OK;
 }
@@ -337,7 +343,7 @@ static int step_checks(pcbenv *env, const void *actions_dev, int fmt, LaunchPlan
 extern "C" int pcbenv_reset(pcbenv *env, const uint8_t *mask_dev, void *stream) {
     const int rc = consuming_launch(
         env, stream, [&](LaunchPlan &plan) { plan.consumes = 1; return check_queue(env); },
-        [&](int, hipStream_t s) { launch_reset(env, mask_dev, s); });
+        [&](int, hipStream_t s) { return launch_reset(env, mask_dev, s); });
     if (rc == PCBENV_OK) env->has_episode = true;
     return rc;
 }
@@ -360,14 +366,14 @@ extern "C" int pcbenv_get_instances(pcbenv *env, int32_t slot, void *host_dst, v
 extern "C" int pcbenv_step(pcbenv *env, const int32_t *actions_dev, int32_t fmt, void *stream) {
     return consuming_launch(
         env, stream, [&](LaunchPlan &plan) { return step_checks(env, actions_dev, fmt, plan); },
-        [&](int, hipStream_t s) { dispatch_step(env, (int *)actions_dev, fmt, 0, 0, 0, 0, 1, s); });
+        [&](int, hipStream_t s) { return dispatch_step(env, (int *)actions_dev, fmt, 0, 0, 0, 0, 1, s); });
 }
 
 extern "C" int pcbenv_step_sampled(pcbenv *env, int32_t *actions_out_dev, int32_t fmt, uint64_t seed,
                                    uint64_t first_env_index, uint64_t step_index, void *stream) {
     return consuming_launch(
         env, stream, [&](LaunchPlan &plan) { return step_checks(env, actions_out_dev, fmt, plan); },
-        [&](int, hipStream_t s) { dispatch_step(env, actions_out_dev, fmt, 1, seed, first_env_index, step_index, 1, s); });
+        [&](int, hipStream_t s) { return dispatch_step(env, actions_out_dev, fmt, 1, seed, first_env_index, step_index, 1, s); });
 }
 
 // num_steps transitions: one launch of the persistent rollout kernel, every step of which may end an episode, or, with the
@@ -386,9 +392,9 @@ extern "C" int pcbenv_rollout_sampled(pcbenv *env, int32_t *actions_out_dev, int
             return PCBENV_OK;
         },
         [&](int t, hipStream_t s) {
-            if (!per_step) { dispatch_step(env, actions_out_dev, fmt, 1, seed, first_env_index, step_index0, num_steps, s); return; }
+            if (!per_step) return dispatch_step(env, actions_out_dev, fmt, 1, seed, first_env_index, step_index0, num_steps, s);
             const size_t actions_per_step = (size_t)env->dp.B * (fmt == PCBENV_ACTION_TUPLE ? 3 : 1);
-            dispatch_step(env, actions_out_dev + actions_per_step * (size_t)t, fmt, 1, seed, first_env_index, step_index0 + (uint64_t)t, 1, s);
+            return dispatch_step(env, actions_out_dev + actions_per_step * (size_t)t, fmt, 1, seed, first_env_index, step_index0 + (uint64_t)t, 1, s);
         });
 }
 
@@ -495,12 +501,9 @@ static int gather_enqueue(pcbenv *dst, const pcbenv *src, const int32_t *src_ind
     } else {
         g.reward = sp.buf.reward + r0; g.info = sp.buf.info ? sp.buf.info + 2 * r0 : 0; g.done = sp.buf.done + r0;
     }
-    if (paths) {
-        a.q = *paths;
-        kind_launch[dst->cfg.kind].gather_paths(a);
-    } else {
-        kind_launch[dst->cfg.kind].gather(GatherLaunch{a.d, a.g, a.threads, a.stream});
-    }
+    if (paths) a.q = *paths;
+    if (launched(dst, paths ? kind_launch[dst->cfg.kind].gather_paths(a) : kind_launch[dst->cfg.kind].gather(GatherLaunch{a.d, a.g, a.threads, a.stream})))
+        return PCBENV_EHIP;
     HIP_TRY(dst, hipGetLastError());
     dst->has_episode = true;
     if (dst->in_place) {  // a captured graph works on the current set (dispatch_step): the gathered blocks go back into it
@@ -564,29 +567,41 @@ static int playout_enqueue(pcbenv *env, int64_t num_playouts, PlayoutArgs g, voi
     g.n = (int)num_playouts; g.per_root = g.root_index ? 1 : (int)(num_playouts / d.B);
     if (!pins) g.info = 0;
     a.g = g;
-    kind_launch[env->cfg.kind].playout(a);
+    if (launched(env, kind_launch[env->cfg.kind].playout(a))) return PCBENV_EHIP;
     HIP_TRY(env, hipGetLastError());
     return PCBENV_OK;
 }
 
-// As pcbenv_sample_logits: the argument checks come before anything touches a device (the null handle last), and nothing
-// the library owns is written -- the kernel gets a parameter block in which nothing but the playout's own reward / info
-// rows can be stored to.
+// The argument checks of pcbenv_playout and, with `paths` (its request; null otherwise), of pcbenv_playout_paths, whose own
+// stand where its contract has them.  As pcbenv_sample_logits: they come before anything touches a device, the null
+// handle last.
+static int playout_checks(pcbenv *env, const double *reward_dev, int32_t fmt, int32_t max_steps, int32_t actions_steps, const int32_t *actions_out_dev,
+                          const int32_t *root_index_dev, int64_t num_playouts, const pcbenv_playout_request *paths) {
+    if (!reward_dev) return fail(env, PCBENV_EINVAL, "null reward");
+    CHECK_ACTION_FORMAT(env, fmt);
+    if (max_steps < 1) return fail(env, PCBENV_EINVAL, "max_steps must be at least 1");
+    if (paths && (paths->path_steps < 0 || paths->path_steps > max_steps)) return fail(env, PCBENV_EINVAL, "path_steps must be in [0, max_steps]");
+    if (paths && paths->path_steps > 0 && !paths->path_actions_dev) return fail(env, PCBENV_EINVAL, "null path_actions with path_steps > 0");
+    if (actions_steps < 0 || actions_steps > max_steps) return fail(env, PCBENV_EINVAL, "actions_steps must be in [0, max_steps]");
+    if (actions_steps > 0 && !actions_out_dev) return fail(env, PCBENV_EINVAL, "null actions_out with actions_steps > 0");
+    if (paths && ((uintptr_t)paths->leaf_mask_bits_dev & 7u) != 0) return fail(env, PCBENV_EINVAL, "leaf_mask_bits must be 8-byte aligned");
+    if (num_playouts < 0) return fail(env, PCBENV_EINVAL, "num_playouts must not be negative");
+    if (env && !root_index_dev && num_playouts % env->dp.B != 0)
+        return fail(env, PCBENV_EINVAL, "without root_index, num_playouts must be a multiple of num_envs");
+    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
+    return PCBENV_OK;
+}
+
+// Nothing the library owns is written -- the kernel gets a parameter block in which nothing but the playout's own reward /
+// info rows can be stored to.
 extern "C" int pcbenv_playout(const pcbenv *cenv, const int32_t *root_index_dev, int64_t num_playouts,
                               const int32_t *first_actions_dev, int32_t fmt, int32_t max_steps, double *reward_dev,
                               uint8_t *done_dev, int32_t *length_dev, double *info_dev, int32_t *actions_out_dev,
                               int32_t actions_steps, uint32_t *errors_dev, uint64_t seed, uint64_t first_env_index,
                               uint64_t step_index0, void *stream) {
     pcbenv *env = const_cast<pcbenv *>(cenv);  // the error text only
-    if (!reward_dev) return fail(env, PCBENV_EINVAL, "null reward");
-    CHECK_ACTION_FORMAT(env, fmt);
-    if (max_steps < 1) return fail(env, PCBENV_EINVAL, "max_steps must be at least 1");
-    if (actions_steps < 0 || actions_steps > max_steps) return fail(env, PCBENV_EINVAL, "actions_steps must be in [0, max_steps]");
-    if (actions_steps > 0 && !actions_out_dev) return fail(env, PCBENV_EINVAL, "null actions_out with actions_steps > 0");
-    if (num_playouts < 0) return fail(env, PCBENV_EINVAL, "num_playouts must not be negative");
-    if (env && !root_index_dev && num_playouts % env->dp.B != 0)
-        return fail(env, PCBENV_EINVAL, "without root_index, num_playouts must be a multiple of num_envs");
-    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
+    const int rc = playout_checks(env, reward_dev, fmt, max_steps, actions_steps, actions_out_dev, root_index_dev, num_playouts, 0);
+    if (rc) return rc;
     PlayoutArgs g = PlayoutArgs();  // the path fields null / 0
     g.root_index = root_index_dev; g.first_actions = first_actions_dev; g.reward = reward_dev; g.done = done_dev;
     g.length = length_dev; g.info = info_dev; g.actions_out = actions_out_dev; g.errors = (unsigned *)errors_dev;
@@ -602,18 +617,8 @@ extern "C" int pcbenv_playout_paths(const pcbenv *cenv, const pcbenv_playout_req
     pcbenv *env = const_cast<pcbenv *>(cenv);  // the error text only
     if (!q) return fail(env, PCBENV_EINVAL, "null request");
     if (q->struct_size != (uint32_t)sizeof(pcbenv_playout_request)) return fail(env, PCBENV_EINVAL, "struct_size is not sizeof(pcbenv_playout_request)");
-    if (!q->reward_dev) return fail(env, PCBENV_EINVAL, "null reward");
-    CHECK_ACTION_FORMAT(env, q->action_format);
-    if (q->max_steps < 1) return fail(env, PCBENV_EINVAL, "max_steps must be at least 1");
-    if (q->path_steps < 0 || q->path_steps > q->max_steps) return fail(env, PCBENV_EINVAL, "path_steps must be in [0, max_steps]");
-    if (q->path_steps > 0 && !q->path_actions_dev) return fail(env, PCBENV_EINVAL, "null path_actions with path_steps > 0");
-    if (q->actions_steps < 0 || q->actions_steps > q->max_steps) return fail(env, PCBENV_EINVAL, "actions_steps must be in [0, max_steps]");
-    if (q->actions_steps > 0 && !q->actions_out_dev) return fail(env, PCBENV_EINVAL, "null actions_out with actions_steps > 0");
-    if (((uintptr_t)q->leaf_mask_bits_dev & 7u) != 0) return fail(env, PCBENV_EINVAL, "leaf_mask_bits must be 8-byte aligned");
-    if (q->num_playouts < 0) return fail(env, PCBENV_EINVAL, "num_playouts must not be negative");
-    if (env && !q->root_index_dev && q->num_playouts % env->dp.B != 0)
-        return fail(env, PCBENV_EINVAL, "without root_index, num_playouts must be a multiple of num_envs");
-    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
+    const int rc = playout_checks(env, q->reward_dev, q->action_format, q->max_steps, q->actions_steps, q->actions_out_dev, q->root_index_dev, q->num_playouts, q);
+    if (rc) return rc;
     PlayoutArgs g = PlayoutArgs();
     g.root_index = q->root_index_dev; g.reward = q->reward_dev; g.done = q->done_dev;
     g.length = q->length_dev; g.info = q->info_dev; g.actions_out = q->actions_out_dev; g.errors = (unsigned *)q->errors_dev;

@@ -626,41 +626,12 @@ class BatchedPlacementEnv:
         idx = index.to(device=self.device, dtype=torch.int32).contiguous()
         if tuple(idx.shape) != (self.num_envs,):
             raise ValueError(f"index must have shape [{self.num_envs}], got {tuple(idx.shape)}")
-        if paths is not None or path_len is not None:
-            return self._gather_paths(src, idx, check, paths, path_len)
+        use_paths = paths is not None or path_len is not None
+        pa, pl, D, fmt = self._path_args(paths, path_len, self.num_envs)
         err = torch.zeros(1, dtype=torch.int32, device=self.device) if check else None
         # reset_done() reads _last_done: the kernel carries `done` of the selected slots over; where _last_done lives in
-        # another slot (either side), the forked rows' flags are taken from the source's _last_done here, before the launch
-        in_slot = (self._last_done.data_ptr() == self.done.data_ptr() and src._last_done.data_ptr() == src.done.data_ptr())
-        if not in_slot:
-            taken = (idx >= 0) & (idx < src.num_envs)
-            forked = src._last_done[idx.long().clamp(0, src.num_envs - 1)]
-        _lib.check(self._L.pcbenv_gather(self._h, None if src is self else src._h, idx.data_ptr(),
-                                         None if err is None else err.data_ptr(), self._stream()), self._h)
-        if not in_slot:
-            self._last_done = torch.where(taken, forked, self._last_done)
-        if check and int(err.item()) != 0:
-            raise IndexError(f"gather_: an index is outside [-1, {src.num_envs}) (those environments kept their episode)")
-        return self.obs
-
-    def _gather_paths(self, src, idx, check, paths, path_len):
-        """`gather_` with paths: the shapes and the format detection are those of `playout(paths=...)`."""
-        B, fmt, pa, pl, D = self.num_envs, _lib.ACTION_TUPLE, None, None, 0
-        if paths is not None:
-            pa = paths.to(device=self.device, dtype=torch.int32).contiguous()
-            if pa.dim() not in (2, 3) or pa.shape[1] != B or (pa.dim() == 3 and pa.shape[2] != 3):
-                raise ValueError(f"paths must have shape [D, {B}] (flat) or [D, {B}, 3], got {tuple(pa.shape)}")
-            D = pa.shape[0]
-            if pa.dim() == 2:
-                fmt = _lib.ACTION_FLAT
-        if path_len is not None:
-            pl = path_len.to(device=self.device, dtype=torch.int32).contiguous()
-            if tuple(pl.shape) != (B,):
-                raise ValueError(f"path_len must have shape [{B}], got {tuple(pl.shape)}")
-        err = torch.zeros(1, dtype=torch.int32, device=self.device) if check else None
-        length = torch.empty(B, dtype=torch.int32, device=self.device)
-        # as in gather_: where _last_done lives in another slot (either side), the rows without a transition take the
-        # source's flag from here; the rows with one take the `done` the kernel wrote
+        # another slot (either side), the forked rows' flags are taken from the source's _last_done here, before the
+        # launch -- for the rows without a transition; those with one take the `done` the kernel wrote
         in_slot = (self._last_done.data_ptr() == self.done.data_ptr() and src._last_done.data_ptr() == src.done.data_ptr())
         if not in_slot:
             taken = (idx >= 0) & (idx < src.num_envs)
@@ -668,20 +639,43 @@ class BatchedPlacementEnv:
                 taken &= (pl >= 0) & (pl <= D)
             forked = src._last_done[idx.long().clamp(0, src.num_envs - 1)]
         ptr = lambda t: None if t is None else t.data_ptr()
-        req = _lib.PcbenvGatherPathsRequest(
-            struct_size=C.sizeof(_lib.PcbenvGatherPathsRequest), action_format=fmt, src=None if src is self else src._h,
-            src_index_dev=idx.data_ptr(), path_actions_dev=ptr(pa) if D > 0 else None, path_len_dev=ptr(pl), path_steps=D,
-            length_dev=length.data_ptr(), errors_dev=ptr(err), stream=self._stream().value)
-        _lib.check(self._L.pcbenv_gather_paths(self._h, C.byref(req)), self._h)
-        self.gather_length = length
+        if use_paths:
+            length = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
+            req = _lib.PcbenvGatherPathsRequest(
+                struct_size=C.sizeof(_lib.PcbenvGatherPathsRequest), action_format=fmt, src=None if src is self else src._h,
+                src_index_dev=idx.data_ptr(), path_actions_dev=ptr(pa) if D > 0 else None, path_len_dev=ptr(pl), path_steps=D,
+                length_dev=length.data_ptr(), errors_dev=ptr(err), stream=self._stream().value)
+            _lib.check(self._L.pcbenv_gather_paths(self._h, C.byref(req)), self._h)
+            self.gather_length = length
+        else:
+            _lib.check(self._L.pcbenv_gather(self._h, None if src is self else src._h, idx.data_ptr(), ptr(err), self._stream()), self._h)
         if not in_slot:
-            self._last_done = torch.where(length > 0, self.done, torch.where(taken, forked, self._last_done))
-        if check:
-            bits = int(err.item())
-            if bits:
-                raise IndexError(f"gather_: an index is outside [-1, {src.num_envs}) or a path_len outside [0, {D}] "
-                                 f"(error bits {bits}; those environments kept their episode)")
+            kept = torch.where(taken, forked, self._last_done)
+            self._last_done = torch.where(length > 0, self.done, kept) if use_paths else kept
+        bits = int(err.item()) if check else 0
+        if bits and use_paths:
+            raise IndexError(f"gather_: an index is outside [-1, {src.num_envs}) or a path_len outside [0, {D}] "
+                             f"(error bits {bits}; those environments kept their episode)")
+        if bits:
+            raise IndexError(f"gather_: an index is outside [-1, {src.num_envs}) (those environments kept their episode)")
         return self.obs
+
+    def _path_args(self, paths, path_len, n):
+        """The `paths` / `path_len` of `gather_` and `playout` for n rows -> (paths, path_len, D, action format), the
+        tensors int32, contiguous, on this device or None; without `paths`, D = 0 and the format is the tuple one."""
+        pa, pl, D, fmt = None, None, 0, _lib.ACTION_TUPLE
+        if paths is not None:
+            pa = paths.to(device=self.device, dtype=torch.int32).contiguous()
+            if pa.dim() not in (2, 3) or pa.shape[1] != n or (pa.dim() == 3 and pa.shape[2] != 3):
+                raise ValueError(f"paths must have shape [D, {n}] (flat) or [D, {n}, 3], got {tuple(pa.shape)}")
+            D = pa.shape[0]
+            if pa.dim() == 2:
+                fmt = _lib.ACTION_FLAT
+        if path_len is not None:
+            pl = path_len.to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(pl.shape) != (n,):
+                raise ValueError(f"path_len must have shape [{n}], got {tuple(pl.shape)}")
+        return pa, pl, D, fmt
 
     def playout(self, k: Optional[int] = None, index: Optional[torch.Tensor] = None, step_index: int = 0,
                 first_actions: Optional[torch.Tensor] = None, max_steps: Optional[int] = None,
@@ -720,24 +714,13 @@ class BatchedPlacementEnv:
             n = self.num_envs * int(k)
         T = default_max_steps(self.cfg) if max_steps is None else int(max_steps)
         A = T if actions_steps is None else int(actions_steps)
-        fmt, fa = _lib.ACTION_TUPLE, None
         use_paths = paths is not None or path_len is not None or leaf_mask
         if first_actions is not None and use_paths:
             raise ValueError("playout: first_actions cannot be combined with paths, path_len or leaf_mask (give it as a path of one step)")
-        pa, pl, D = None, None, 0
-        if paths is not None:
-            pa = paths.to(device=self.device, dtype=torch.int32).contiguous()
-            if pa.dim() not in (2, 3) or pa.shape[1] != n or (pa.dim() == 3 and pa.shape[2] != 3):
-                raise ValueError(f"paths must have shape [D, {n}] (flat) or [D, {n}, 3], got {tuple(pa.shape)}")
-            D = pa.shape[0]
-            if pa.dim() == 2:
-                fmt = _lib.ACTION_FLAT
-            if D > T:
-                raise ValueError(f"paths has {D} steps, max_steps is {T}")
-        if path_len is not None:
-            pl = path_len.to(device=self.device, dtype=torch.int32).contiguous()
-            if tuple(pl.shape) != (n,):
-                raise ValueError(f"path_len must have shape [{n}], got {tuple(pl.shape)}")
+        fa = None
+        pa, pl, D, fmt = self._path_args(paths, path_len, n)
+        if D > T:
+            raise ValueError(f"paths has {D} steps, max_steps is {T}")
         if first_actions is not None:
             fa = first_actions.to(device=self.device, dtype=torch.int32).contiguous()
             if tuple(fa.shape) not in ((n,), (n, 3)):
