@@ -1,5 +1,6 @@
 // pcbenv_api.hip -- host side of libpcbenv.so's C ABI (include/pcbenv.h): create / destroy / options / bind / load,
-// reset / step / rollout / sample, checkpoint, gather, playout and the logits entry points.  No kernel is defined here: the
+// reset / step / rollout / sample, checkpoint, gather, playout and the six policy entry points (the logits and the axis
+// calls: their shared checks and prologue are stated once, in front of them).  No kernel is defined here: the
 // environment kernels are instantiated per kind and part in pcb_kind.inc / pcb_playout.inc / pcb_gather_paths.inc, k_sample and k_cursor_range in pcb_sample.hip and the
 // policy kernels in pcb_policy*.hip (all reached through pcb_launch.h); pcb_config.hip derives the layout from a
 // configuration and pcb_gen.hip owns the on-device instance generator (pcb_host.h declares what the three share).
@@ -628,61 +629,91 @@ extern "C" int pcbenv_playout_paths(const pcbenv *cenv, const pcbenv_playout_req
     return playout_enqueue(env, q->num_playouts, g, q->stream, true, "pcbenv_playout_paths cannot be captured into a graph");
 }
 
-// ---- pcbenv_sample_logits ------------------------------------------------------------------------------------
-// The argument checks come before anything touches a device (a null handle included), so that every one of them can be
-// exercised without a GPU.  Nothing the library owns is written: no state block, presampled action, terminal list or
-// queue, and no generator interaction (nothing is consumed).
+// ---- the policy entry points -----------------------------------------------------------------------------------
+// pcbenv_sample_logits, pcbenv_evaluate_logits[_backward], pcbenv_sample_axis and pcbenv_evaluate_axis[_backward].  Their
+// argument checks come before anything touches a device (a null handle included, and last), so that every one of them can
+// be exercised without a GPU; the first to fire decides the message, in the order include/pcbenv.h gives.  Each check that
+// more than one of them makes is stated once, here.
 static int logits_elem_bytes(int32_t logits_dtype) { return logits_dtype == PCBENV_LOGITS_F32 ? 4 : 2; }
-// the checks pcbenv_sample_logits and pcbenv_evaluate_logits[_backward] share
-static int logits_checks(pcbenv *env, const void *logits_dev, int32_t logits_dtype, const int32_t *actions_dev, int32_t fmt) {
+static int head_checks(pcbenv *env, const void *logits_dev, const int32_t *actions_dev, int32_t logits_dtype) {
     if (!logits_dev) return fail(env, PCBENV_EINVAL, "null logits");
     if (!actions_dev) return fail(env, PCBENV_EINVAL, "null actions");
     if (logits_dtype != PCBENV_LOGITS_F32 && logits_dtype != PCBENV_LOGITS_BF16) return fail(env, PCBENV_EINVAL, "unknown logits dtype");
-    CHECK_ACTION_FORMAT(env, fmt);
+    return PCBENV_OK;
+}
+static int logits_aligned(pcbenv *env, const void *logits_dev, int32_t logits_dtype) {
     if ((uintptr_t)logits_dev % logits_elem_bytes(logits_dtype) != 0)
         return fail(env, PCBENV_EINVAL, "logits pointer not aligned to its element size");
     return PCBENV_OK;
 }
-extern "C" int pcbenv_sample_logits(pcbenv *env, const void *logits_dev, int32_t logits_dtype, int32_t mode,
-                                    int32_t *actions_dev, int32_t fmt, float *log_prob_dev, float *entropy_dev,
-                                    uint32_t *errors_dev, uint64_t seed, uint64_t first_env_index, uint64_t step_index,
-                                    void *stream) {
-    const int rc = logits_checks(env, logits_dev, logits_dtype, actions_dev, fmt);
-    if (rc != PCBENV_OK) return rc;
-    if (mode != PCBENV_DRAW_SAMPLE && mode != PCBENV_DRAW_GREEDY) return fail(env, PCBENV_EINVAL, "unknown draw mode");
-    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
-    if (!env->bound) return fail(env, PCBENV_ESTATE, "pcbenv_bind_buffers has not been called");
-    DEVICE_GUARD(env);
-    hipStream_t s = (hipStream_t)stream;
-    // A captured launch would keep reading the state set that was current at capture time (as pcbenv_gather).
-    if (stream_capturing(s)) return fail(env, PCBENV_ESTATE, "pcbenv_sample_logits cannot be captured into a graph");
-    SampleLogitsLaunch a;
-    a.d = env->dp;  // d.state: the current state set, as k_sample reads it
-    a.dtype = logits_dtype; a.stream = s;
-    SampleLogitsArgs &g = a.g;
-    g.logits = logits_dev; g.actions = actions_dev; g.log_prob = log_prob_dev; g.entropy = entropy_dev;
-    g.errors = (unsigned *)errors_dev; g.seed = (u64)seed; g.first_env = (u64)first_env_index; g.step_index = (u64)step_index;
-    g.fmt = fmt; g.greedy = mode == PCBENV_DRAW_GREEDY;
-    pcb_launch_sample_logits(a);
-    HIP_TRY(env, hipGetLastError());
-    return PCBENV_OK;
-}
-
-// ---- pcbenv_evaluate_logits / pcbenv_evaluate_logits_backward ------------------------------------------------------
-// As pcbenv_sample_logits: the argument checks come before anything touches a device.  The handle gives the geometry
-// and the device; nothing the library owns is read or written, so no buffers need to be bound.
-static int evaluate_checks(pcbenv *env, const void *logits_dev, int32_t logits_dtype, const uint64_t *mask_bits_dev,
-                           const int32_t *actions_dev, int32_t fmt, int64_t num_rows) {
-    const int rc = logits_checks(env, logits_dev, logits_dtype, actions_dev, fmt);
-    if (rc != PCBENV_OK) return rc;
+static int rows_checks(pcbenv *env, const uint64_t *mask_bits_dev, int64_t num_rows) {
     if (!mask_bits_dev) return fail(env, PCBENV_EINVAL, "null mask bits");
     if ((uintptr_t)mask_bits_dev % 8 != 0) return fail(env, PCBENV_EINVAL, "mask bits pointer not aligned to 8 bytes");
     if (num_rows < 0 || num_rows > INT32_MAX) return fail(env, PCBENV_EINVAL, "num_rows out of range");
     return PCBENV_OK;
 }
+static int grad_logits_checks(pcbenv *env, const void *grad_logits_dev, int32_t logits_dtype) {
+    if (!grad_logits_dev) return fail(env, PCBENV_EINVAL, "null grad logits");
+    if ((uintptr_t)grad_logits_dev % logits_elem_bytes(logits_dtype) != 0)
+        return fail(env, PCBENV_EINVAL, "grad logits pointer not aligned to its element size");
+    return PCBENV_OK;
+}
+// the checks pcbenv_sample_logits and pcbenv_evaluate_logits[_backward] share, and those of the three axis calls (the
+// evaluate ones pass PCBENV_DRAW_SAMPLE)
+static int logits_checks(pcbenv *env, const void *logits_dev, int32_t logits_dtype, const int32_t *actions_dev, int32_t fmt) {
+    if (const int rc = head_checks(env, logits_dev, actions_dev, logits_dtype)) return rc;
+    CHECK_ACTION_FORMAT(env, fmt);
+    return logits_aligned(env, logits_dev, logits_dtype);
+}
+static int axis_checks(pcbenv *env, int32_t axis, uint32_t given, const void *logits_dev, int32_t logits_dtype, int32_t mode,
+                       const int32_t *actions_dev) {
+    if (const int rc = head_checks(env, logits_dev, actions_dev, logits_dtype)) return rc;
+    if (mode != PCBENV_DRAW_SAMPLE && mode != PCBENV_DRAW_GREEDY) return fail(env, PCBENV_EINVAL, "unknown draw mode");
+    if (axis != PCBENV_AXIS_ORIENTATION && axis != PCBENV_AXIS_X && axis != PCBENV_AXIS_Y) return fail(env, PCBENV_EINVAL, "unknown axis");
+    if (given & ~7u) return fail(env, PCBENV_EINVAL, "given has a bit above 4");
+    if (given & (1u << axis)) return fail(env, PCBENV_EINVAL, "given contains the axis itself");
+    return logits_aligned(env, logits_dev, logits_dtype);
+}
 static EvalGeom eval_geom(const pcbenv *env, int64_t num_rows) {
     const DevParams &d = env->dp;
     return EvalGeom{d.O, d.H, d.W, d.WW, (int)num_rows};
+}
+
+// What the six do once their own arguments have passed.  `sampler`: the name of a function that reads the handle's current
+// state set (null for the evaluate calls, which take geometry and device from the handle and nothing else): it needs
+// bound buffers, and it cannot be captured -- a captured launch would keep reading the set that was current at capture
+// time (as pcbenv_gather).  `no_rows`: the evaluate calls' num_rows == 0, a no-op behind the null handle.  `launch(s)`
+// fills the launch struct and returns its launch function's value.  Nothing the library owns is written: no state block,
+// presampled action, terminal list or queue, and no generator interaction (nothing is consumed).
+template <class Launch>
+static int policy_launch(pcbenv *env, const char *sampler, bool no_rows, void *stream, Launch launch) {
+    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
+    if (sampler && !env->bound) return fail(env, PCBENV_ESTATE, "pcbenv_bind_buffers has not been called");
+    if (no_rows) return PCBENV_OK;
+    DEVICE_GUARD(env);
+    hipStream_t s = (hipStream_t)stream;
+    if (sampler && stream_capturing(s)) return fail(env, PCBENV_ESTATE, "%s cannot be captured into a graph", sampler);
+    if (launched(env, launch(s))) return PCBENV_EHIP;
+    HIP_TRY(env, hipGetLastError());
+    return PCBENV_OK;
+}
+
+extern "C" int pcbenv_sample_logits(pcbenv *env, const void *logits_dev, int32_t logits_dtype, int32_t mode,
+                                    int32_t *actions_dev, int32_t fmt, float *log_prob_dev, float *entropy_dev,
+                                    uint32_t *errors_dev, uint64_t seed, uint64_t first_env_index, uint64_t step_index,
+                                    void *stream) {
+    if (const int rc = logits_checks(env, logits_dev, logits_dtype, actions_dev, fmt)) return rc;
+    if (mode != PCBENV_DRAW_SAMPLE && mode != PCBENV_DRAW_GREEDY) return fail(env, PCBENV_EINVAL, "unknown draw mode");
+    return policy_launch(env, "pcbenv_sample_logits", false, stream, [&](hipStream_t s) {
+        SampleLogitsLaunch a;
+        a.d = env->dp;  // d.state: the current state set, as k_sample reads it
+        a.dtype = logits_dtype; a.stream = s;
+        SampleLogitsArgs &g = a.g;
+        g.logits = logits_dev; g.actions = actions_dev; g.log_prob = log_prob_dev; g.entropy = entropy_dev;
+        g.errors = (unsigned *)errors_dev; g.seed = (u64)seed; g.first_env = (u64)first_env_index; g.step_index = (u64)step_index;
+        g.fmt = fmt; g.greedy = mode == PCBENV_DRAW_GREEDY;
+        return pcb_launch_sample_logits(a);
+    });
 }
 
 extern "C" int pcbenv_evaluate_logits(const pcbenv *cenv, const void *logits_dev, int32_t logits_dtype,
@@ -690,20 +721,17 @@ extern "C" int pcbenv_evaluate_logits(const pcbenv *cenv, const void *logits_dev
                                       int64_t num_rows, float *log_prob_dev, float *entropy_dev, float *stats_dev,
                                       uint32_t *errors_dev, void *stream) {
     pcbenv *env = const_cast<pcbenv *>(cenv);  // the error text only
-    const int rc = evaluate_checks(env, logits_dev, logits_dtype, mask_bits_dev, actions_dev, fmt, num_rows);
-    if (rc != PCBENV_OK) return rc;
+    if (const int rc = logits_checks(env, logits_dev, logits_dtype, actions_dev, fmt)) return rc;
+    if (const int rc = rows_checks(env, mask_bits_dev, num_rows)) return rc;
     if ((uintptr_t)stats_dev % 16 != 0) return fail(env, PCBENV_EINVAL, "stats pointer not aligned to 16 bytes");
-    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
-    if (num_rows == 0) return PCBENV_OK;
-    DEVICE_GUARD(env);
-    EvalLogitsLaunch a;
-    a.q = eval_geom(env, num_rows); a.dtype = logits_dtype; a.stream = (hipStream_t)stream;
-    EvalLogitsArgs &g = a.g;
-    g.logits = logits_dev; g.mask_bits = (const u64 *)mask_bits_dev; g.actions = actions_dev; g.log_prob = log_prob_dev;
-    g.entropy = entropy_dev; g.stats = stats_dev; g.errors = (unsigned *)errors_dev; g.fmt = fmt;
-    pcb_launch_evaluate_logits(a);
-    HIP_TRY(env, hipGetLastError());
-    return PCBENV_OK;
+    return policy_launch(env, 0, num_rows == 0, stream, [&](hipStream_t s) {
+        EvalLogitsLaunch a;
+        a.q = eval_geom(env, num_rows); a.dtype = logits_dtype; a.stream = s;
+        EvalLogitsArgs &g = a.g;
+        g.logits = logits_dev; g.mask_bits = (const u64 *)mask_bits_dev; g.actions = actions_dev; g.log_prob = log_prob_dev;
+        g.entropy = entropy_dev; g.stats = stats_dev; g.errors = (unsigned *)errors_dev; g.fmt = fmt;
+        return pcb_launch_evaluate_logits(a);
+    });
 }
 
 extern "C" int pcbenv_evaluate_logits_backward(const pcbenv *cenv, const void *logits_dev, int32_t logits_dtype,
@@ -711,74 +739,37 @@ extern "C" int pcbenv_evaluate_logits_backward(const pcbenv *cenv, const void *l
                                                int64_t num_rows, const float *stats_dev, const float *grad_log_prob_dev,
                                                const float *grad_entropy_dev, void *grad_logits_dev, void *stream) {
     pcbenv *env = const_cast<pcbenv *>(cenv);  // the error text only
-    const int rc = evaluate_checks(env, logits_dev, logits_dtype, mask_bits_dev, actions_dev, fmt, num_rows);
-    if (rc != PCBENV_OK) return rc;
+    if (const int rc = logits_checks(env, logits_dev, logits_dtype, actions_dev, fmt)) return rc;
+    if (const int rc = rows_checks(env, mask_bits_dev, num_rows)) return rc;
     if (!stats_dev) return fail(env, PCBENV_EINVAL, "null stats");
     if ((uintptr_t)stats_dev % 16 != 0) return fail(env, PCBENV_EINVAL, "stats pointer not aligned to 16 bytes");
-    if (!grad_logits_dev) return fail(env, PCBENV_EINVAL, "null grad logits");
-    if ((uintptr_t)grad_logits_dev % logits_elem_bytes(logits_dtype) != 0)
-        return fail(env, PCBENV_EINVAL, "grad logits pointer not aligned to its element size");
-    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
-    if (num_rows == 0) return PCBENV_OK;
-    DEVICE_GUARD(env);
-    EvalLogitsBackwardLaunch a;
-    a.q = eval_geom(env, num_rows); a.dtype = logits_dtype; a.stream = (hipStream_t)stream;
-    EvalLogitsBackwardArgs &g = a.g;
-    g.logits = logits_dev; g.mask_bits = (const u64 *)mask_bits_dev; g.actions = actions_dev; g.stats = stats_dev;
-    g.grad_log_prob = grad_log_prob_dev; g.grad_entropy = grad_entropy_dev; g.grad_logits = grad_logits_dev; g.fmt = fmt;
-    pcb_launch_evaluate_logits_backward(a);
-    HIP_TRY(env, hipGetLastError());
-    return PCBENV_OK;
+    if (const int rc = grad_logits_checks(env, grad_logits_dev, logits_dtype)) return rc;
+    return policy_launch(env, 0, num_rows == 0, stream, [&](hipStream_t s) {
+        EvalLogitsBackwardLaunch a;
+        a.q = eval_geom(env, num_rows); a.dtype = logits_dtype; a.stream = s;
+        EvalLogitsBackwardArgs &g = a.g;
+        g.logits = logits_dev; g.mask_bits = (const u64 *)mask_bits_dev; g.actions = actions_dev; g.stats = stats_dev;
+        g.grad_log_prob = grad_log_prob_dev; g.grad_entropy = grad_entropy_dev; g.grad_logits = grad_logits_dev; g.fmt = fmt;
+        return pcb_launch_evaluate_logits_backward(a);
+    });
 }
 
-// ---- pcbenv_sample_axis / pcbenv_evaluate_axis / pcbenv_evaluate_axis_backward --------------------------------------
-// One stage of a factorised policy.  As the logits entry points: the argument checks come before anything touches a
-// device, in the order of logits_checks; nothing the library owns is written.
-static int axis_checks(pcbenv *env, int32_t axis, uint32_t given, const void *logits_dev, int32_t logits_dtype, int32_t mode,
-                       const int32_t *actions_dev) {
-    if (!logits_dev) return fail(env, PCBENV_EINVAL, "null logits");
-    if (!actions_dev) return fail(env, PCBENV_EINVAL, "null actions");
-    if (logits_dtype != PCBENV_LOGITS_F32 && logits_dtype != PCBENV_LOGITS_BF16) return fail(env, PCBENV_EINVAL, "unknown logits dtype");
-    if (mode != PCBENV_DRAW_SAMPLE && mode != PCBENV_DRAW_GREEDY) return fail(env, PCBENV_EINVAL, "unknown draw mode");
-    if (axis != PCBENV_AXIS_ORIENTATION && axis != PCBENV_AXIS_X && axis != PCBENV_AXIS_Y) return fail(env, PCBENV_EINVAL, "unknown axis");
-    if (given & ~7u) return fail(env, PCBENV_EINVAL, "given has a bit above 4");
-    if (given & (1u << axis)) return fail(env, PCBENV_EINVAL, "given contains the axis itself");
-    if ((uintptr_t)logits_dev % logits_elem_bytes(logits_dtype) != 0)
-        return fail(env, PCBENV_EINVAL, "logits pointer not aligned to its element size");
-    return PCBENV_OK;
-}
-static int evaluate_axis_checks(pcbenv *env, int32_t axis, uint32_t given, const void *logits_dev, int32_t logits_dtype,
-                                const uint64_t *mask_bits_dev, const int32_t *actions_dev, int64_t num_rows) {
-    const int rc = axis_checks(env, axis, given, logits_dev, logits_dtype, PCBENV_DRAW_SAMPLE, actions_dev);
-    if (rc != PCBENV_OK) return rc;
-    if (!mask_bits_dev) return fail(env, PCBENV_EINVAL, "null mask bits");
-    if ((uintptr_t)mask_bits_dev % 8 != 0) return fail(env, PCBENV_EINVAL, "mask bits pointer not aligned to 8 bytes");
-    if (num_rows < 0 || num_rows > INT32_MAX) return fail(env, PCBENV_EINVAL, "num_rows out of range");
-    return PCBENV_OK;
-}
-
+// One stage of a factorised policy.
 extern "C" int pcbenv_sample_axis(pcbenv *env, int32_t axis, uint32_t given, const void *logits_dev, int32_t logits_dtype,
                                   int32_t mode, int32_t *actions_dev, float *log_prob_dev, float *entropy_dev,
                                   uint32_t *errors_dev, uint64_t seed, uint64_t first_env_index, uint64_t step_index,
                                   void *stream) {
-    const int rc = axis_checks(env, axis, given, logits_dev, logits_dtype, mode, actions_dev);
-    if (rc != PCBENV_OK) return rc;
-    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
-    if (!env->bound) return fail(env, PCBENV_ESTATE, "pcbenv_bind_buffers has not been called");
-    DEVICE_GUARD(env);
-    hipStream_t s = (hipStream_t)stream;
-    // A captured launch would keep reading the state set that was current at capture time (as pcbenv_sample_logits).
-    if (stream_capturing(s)) return fail(env, PCBENV_ESTATE, "pcbenv_sample_axis cannot be captured into a graph");
-    SampleAxisLaunch a;
-    a.d = env->dp;  // d.state: the current state set, as k_sample_logits reads it
-    a.s = AxisStage{axis, given}; a.dtype = logits_dtype; a.stream = s;
-    SampleAxisArgs &g = a.g;
-    g.logits = logits_dev; g.actions = actions_dev; g.log_prob = log_prob_dev; g.entropy = entropy_dev;
-    g.errors = (unsigned *)errors_dev; g.seed = (u64)seed; g.first_env = (u64)first_env_index; g.step_index = (u64)step_index;
-    g.greedy = mode == PCBENV_DRAW_GREEDY;
-    pcb_launch_sample_axis(a);
-    HIP_TRY(env, hipGetLastError());
-    return PCBENV_OK;
+    if (const int rc = axis_checks(env, axis, given, logits_dev, logits_dtype, mode, actions_dev)) return rc;
+    return policy_launch(env, "pcbenv_sample_axis", false, stream, [&](hipStream_t s) {
+        SampleAxisLaunch a;
+        a.d = env->dp;  // d.state: the current state set, as k_sample_logits reads it
+        a.s = AxisStage{axis, given}; a.dtype = logits_dtype; a.stream = s;
+        SampleAxisArgs &g = a.g;
+        g.logits = logits_dev; g.actions = actions_dev; g.log_prob = log_prob_dev; g.entropy = entropy_dev;
+        g.errors = (unsigned *)errors_dev; g.seed = (u64)seed; g.first_env = (u64)first_env_index; g.step_index = (u64)step_index;
+        g.greedy = mode == PCBENV_DRAW_GREEDY;
+        return pcb_launch_sample_axis(a);
+    });
 }
 
 extern "C" int pcbenv_evaluate_axis(const pcbenv *cenv, int32_t axis, uint32_t given, const void *logits_dev,
@@ -786,19 +777,16 @@ extern "C" int pcbenv_evaluate_axis(const pcbenv *cenv, int32_t axis, uint32_t g
                                     int64_t num_rows, float *log_prob_dev, float *entropy_dev, uint32_t *errors_dev,
                                     void *stream) {
     pcbenv *env = const_cast<pcbenv *>(cenv);  // the error text only
-    const int rc = evaluate_axis_checks(env, axis, given, logits_dev, logits_dtype, mask_bits_dev, actions_dev, num_rows);
-    if (rc != PCBENV_OK) return rc;
-    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
-    if (num_rows == 0) return PCBENV_OK;
-    DEVICE_GUARD(env);
-    EvalAxisLaunch a;
-    a.q = eval_geom(env, num_rows); a.s = AxisStage{axis, given}; a.dtype = logits_dtype; a.stream = (hipStream_t)stream;
-    EvalAxisArgs &g = a.g;
-    g.logits = logits_dev; g.mask_bits = (const u64 *)mask_bits_dev; g.actions = actions_dev; g.log_prob = log_prob_dev;
-    g.entropy = entropy_dev; g.errors = (unsigned *)errors_dev;
-    pcb_launch_evaluate_axis(a);
-    HIP_TRY(env, hipGetLastError());
-    return PCBENV_OK;
+    if (const int rc = axis_checks(env, axis, given, logits_dev, logits_dtype, PCBENV_DRAW_SAMPLE, actions_dev)) return rc;
+    if (const int rc = rows_checks(env, mask_bits_dev, num_rows)) return rc;
+    return policy_launch(env, 0, num_rows == 0, stream, [&](hipStream_t s) {
+        EvalAxisLaunch a;
+        a.q = eval_geom(env, num_rows); a.s = AxisStage{axis, given}; a.dtype = logits_dtype; a.stream = s;
+        EvalAxisArgs &g = a.g;
+        g.logits = logits_dev; g.mask_bits = (const u64 *)mask_bits_dev; g.actions = actions_dev; g.log_prob = log_prob_dev;
+        g.entropy = entropy_dev; g.errors = (unsigned *)errors_dev;
+        return pcb_launch_evaluate_axis(a);
+    });
 }
 
 extern "C" int pcbenv_evaluate_axis_backward(const pcbenv *cenv, int32_t axis, uint32_t given, const void *logits_dev,
@@ -806,22 +794,17 @@ extern "C" int pcbenv_evaluate_axis_backward(const pcbenv *cenv, int32_t axis, u
                                              int64_t num_rows, const float *grad_log_prob_dev, const float *grad_entropy_dev,
                                              void *grad_logits_dev, void *stream) {
     pcbenv *env = const_cast<pcbenv *>(cenv);  // the error text only
-    const int rc = evaluate_axis_checks(env, axis, given, logits_dev, logits_dtype, mask_bits_dev, actions_dev, num_rows);
-    if (rc != PCBENV_OK) return rc;
-    if (!grad_logits_dev) return fail(env, PCBENV_EINVAL, "null grad logits");
-    if ((uintptr_t)grad_logits_dev % logits_elem_bytes(logits_dtype) != 0)
-        return fail(env, PCBENV_EINVAL, "grad logits pointer not aligned to its element size");
-    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
-    if (num_rows == 0) return PCBENV_OK;
-    DEVICE_GUARD(env);
-    EvalAxisBackwardLaunch a;
-    a.q = eval_geom(env, num_rows); a.s = AxisStage{axis, given}; a.dtype = logits_dtype; a.stream = (hipStream_t)stream;
-    EvalAxisBackwardArgs &g = a.g;
-    g.logits = logits_dev; g.mask_bits = (const u64 *)mask_bits_dev; g.actions = actions_dev;
-    g.grad_log_prob = grad_log_prob_dev; g.grad_entropy = grad_entropy_dev; g.grad_logits = grad_logits_dev;
-    pcb_launch_evaluate_axis_backward(a);
-    HIP_TRY(env, hipGetLastError());
-    return PCBENV_OK;
+    if (const int rc = axis_checks(env, axis, given, logits_dev, logits_dtype, PCBENV_DRAW_SAMPLE, actions_dev)) return rc;
+    if (const int rc = rows_checks(env, mask_bits_dev, num_rows)) return rc;
+    if (const int rc = grad_logits_checks(env, grad_logits_dev, logits_dtype)) return rc;
+    return policy_launch(env, 0, num_rows == 0, stream, [&](hipStream_t s) {
+        EvalAxisBackwardLaunch a;
+        a.q = eval_geom(env, num_rows); a.s = AxisStage{axis, given}; a.dtype = logits_dtype; a.stream = s;
+        EvalAxisBackwardArgs &g = a.g;
+        g.logits = logits_dev; g.mask_bits = (const u64 *)mask_bits_dev; g.actions = actions_dev;
+        g.grad_log_prob = grad_log_prob_dev; g.grad_entropy = grad_entropy_dev; g.grad_logits = grad_logits_dev;
+        return pcb_launch_evaluate_axis_backward(a);
+    });
 }
 
 extern "C" int pcbenv_queue_cursors(pcbenv *env, uint32_t *min_out, uint32_t *max_out, void *stream) {

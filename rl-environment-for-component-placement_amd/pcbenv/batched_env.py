@@ -93,11 +93,34 @@ def _as_tensor(ptr: int, nbytes: int, device) -> torch.Tensor:
     return torch.as_tensor(_ExternalBlock(ptr, nbytes), device=device)
 
 
+LOGITS_DTYPES = (torch.float32, torch.bfloat16)
+
+
 def _logits_dtype(logits) -> int:
     """The library's code (`_lib.LOGITS_*`) for a float32 or bfloat16 tensor of logits; ValueError otherwise."""
-    if not isinstance(logits, torch.Tensor) or logits.dtype not in (torch.float32, torch.bfloat16):
+    if not isinstance(logits, torch.Tensor) or logits.dtype not in LOGITS_DTYPES:
         raise ValueError("logits must be a float32 or bfloat16 tensor")
     return _lib.LOGITS_F32 if logits.dtype == torch.float32 else _lib.LOGITS_BF16
+
+
+def check_tensor(device, name, t, dtype, shape) -> None:
+    """The one test of a caller's tensor before its address goes to a launch: `t` is a tensor of `dtype` (one torch dtype
+    or a tuple of them) and exactly `shape`, C-contiguous -- no copy is made -- and on `device`, index included
+    (`t.device == device`); ValueError naming the argument otherwise.  An entry of `shape` that is not a number ("N")
+    stands for a size that could not be read off the tensors: it matches nothing."""
+    dtypes = dtype if isinstance(dtype, tuple) else (dtype,)
+    if (isinstance(t, torch.Tensor) and t.dtype in dtypes and tuple(t.shape) == tuple(shape) and t.is_contiguous()
+            and t.device == device):
+        return
+    got = type(t).__name__ if not isinstance(t, torch.Tensor) else (
+        f"{t.dtype} [{', '.join(map(str, t.shape))}] on {t.device}" + ("" if t.is_contiguous() else ", not contiguous"))
+    raise ValueError(f"{name}: must have shape [{', '.join(map(str, shape))}] and dtype {' or '.join(map(str, dtypes))}, "
+                     f"must be C-contiguous (no copy is made) and must be on {device}; got {got}")
+
+
+def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    """The address of an optional tensor argument: None (a null pointer) for None."""
+    return None if t is None else t.data_ptr()
 
 
 class BatchedPlacementEnv:
@@ -124,9 +147,11 @@ class BatchedPlacementEnv:
         cfg.validate()
         self.cfg, self.num_envs, self.queue_depth = cfg, int(num_envs), int(queue_depth)
         self.run_seed, self.first_env_index = int(run_seed), int(first_env_index)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
+        dev = torch.device(device)
+        if dev.type != "cuda":
             raise RuntimeError("BatchedPlacementEnv needs a GPU device (there is no CPU fallback)")
+        # the device the handle lives on, index included: one named without an index is the current device, now and for good
+        self.device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
         self._L = _lib.load()
         # per-environment spaces (the reference constructors' declarations); every tensor adds a leading batch dim
         from .spaces import action_space_for, observation_space_for
@@ -138,8 +163,7 @@ class BatchedPlacementEnv:
                                       | (_lib.FLAG_AUTO_RESET if auto_reset else 0))
         self._ccfg.threads_per_env = int(threads_per_env)  # 0 = auto; 64 / 256 threads (1 / 4 waves) per environment
         h = C.c_void_p()
-        dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        _lib.check(self._L.pcbenv_create(C.byref(self._ccfg), dev_index, C.byref(h)))
+        _lib.check(self._L.pcbenv_create(C.byref(self._ccfg), self.device.index, C.byref(h)))
         self._h = h
         for name, value in (options or {}).items():
             self.set_option(name, value)
@@ -176,13 +200,13 @@ class BatchedPlacementEnv:
                 t = self.traj_marginals.get("rows")
             if self.compact_features and name in FEATURE_KEYS:
                 t = None  # not produced in float64: the compact twin is bound below
-            setattr(bufs, name, t.data_ptr() if t is not None else None)
+            setattr(bufs, name, _ptr(t))
         _lib.check(self._L.pcbenv_bind_buffers_slots(self._h, C.byref(bufs), S), self._h)
         if self.compact_features:
             cb = _lib.PcbenvCompactFeatures()
             for name in _lib.COMPACT_FIELDS:
                 t = self.traj.get(name)
-                setattr(cb, name, t.data_ptr() if t is not None else None)
+                setattr(cb, name, _ptr(t))
             _lib.check(self._L.pcbenv_bind_compact_features(self._h, C.byref(cb)), self._h)
         self.slot = -1
         self.select_slot(0)
@@ -212,6 +236,14 @@ class BatchedPlacementEnv:
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _log_prob_entropy(self, n: int):
+        """The (log_prob, entropy) a policy call returns: float32 [n], for the kernel to fill."""
+        return torch.empty(n, dtype=torch.float32, device=self.device), torch.empty(n, dtype=torch.float32, device=self.device)
+
+    def _error_word(self, check: bool) -> Optional[torch.Tensor]:
+        """The zeroed int32 [1] a kernel ORs its error bits into, for a call with check=True; None otherwise."""
+        return torch.zeros(1, dtype=torch.int32, device=self.device) if check else None
 
     def select_slot(self, slot: int):
         """The slot of the `[num_slots, B, ...]` tensors the next reset / step writes; `obs`, `reward`, `done`,
@@ -370,7 +402,8 @@ class BatchedPlacementEnv:
         return {"wirelength": self.info_raw[:, 0], "num_intersections": self.info_raw[:, 1]}
 
     def sample_actions(self, step_index: int, flat: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Uniform draw over the legal actions of every environment, on device (random-policy counterpart)."""
+        """Uniform draw over the legal actions of every environment, on device (random-policy counterpart).
+        out: int32 [B, 3] or [B] (flat), C-contiguous, on `self.device`; not checked."""
         if out is None:
             out = torch.empty((self.num_envs,) if flat else (self.num_envs, 3), dtype=torch.int32, device=self.device)
         _lib.check(self._L.pcbenv_sample_actions(
@@ -389,25 +422,17 @@ class BatchedPlacementEnv:
         `sample_actions(step_index)` draws.  Returns (actions int32 [B, 3] or [B] (flat), log_prob float32 [B],
         entropy float32 [B]).  check=True synchronises and raises if a legal logit was NaN / +inf or every legal logit
         -inf (those environments then took the uniform draw)."""
-        B, A = self.num_envs, self.cfg.num_orientations * self.cfg.height * self.cfg.width
+        cfg, B = self.cfg, self.num_envs
         dtype = _logits_dtype(logits)
-        if logits.device != self.device and not (logits.device.type == "cuda" and self.device.index is None
-                                                 and logits.device.index == torch.cuda.current_device()):
-            raise ValueError(f"logits must be on {self.device}, got {logits.device}")
-        shapes = ((B, A), (B, self.cfg.num_orientations, self.cfg.height, self.cfg.width))
-        if tuple(logits.shape) not in shapes:
-            raise ValueError(f"logits must have shape {list(shapes[0])} or {list(shapes[1])}, got {list(logits.shape)}")
-        if not logits.is_contiguous():
-            raise ValueError("logits must be C-contiguous (no copy is made)")
+        grid = (B, cfg.num_orientations, cfg.height, cfg.width)
+        check_tensor(self.device, "logits", logits, LOGITS_DTYPES, grid if logits.dim() == 4 else (B, grid[1] * grid[2] * grid[3]))
         if out is None:
             out = torch.empty((B,) if flat else (B, 3), dtype=torch.int32, device=self.device)
-        log_prob = torch.empty(B, dtype=torch.float32, device=self.device)
-        entropy = torch.empty(B, dtype=torch.float32, device=self.device)
-        err = torch.zeros(1, dtype=torch.int32, device=self.device) if check else None
+        check_tensor(self.device, "out", out, torch.int32, (B,) if flat else (B, 3))
+        (log_prob, entropy), err = self._log_prob_entropy(B), self._error_word(check)
         _lib.check(self._L.pcbenv_sample_logits(
             self._h, logits.data_ptr(), dtype, _lib.DRAW_GREEDY if greedy else _lib.DRAW_SAMPLE, out.data_ptr(),
-            _lib.ACTION_FLAT if flat else _lib.ACTION_TUPLE,
-            log_prob.data_ptr(), entropy.data_ptr(), None if err is None else err.data_ptr(), self.run_seed,
+            _lib.ACTION_FLAT if flat else _lib.ACTION_TUPLE, log_prob.data_ptr(), entropy.data_ptr(), _ptr(err), self.run_seed,
             self.first_env_index, int(step_index), self._stream()), self._h)
         if check:
             bits = int(err.item())
@@ -416,24 +441,28 @@ class BatchedPlacementEnv:
                                          "legal logit was -inf); those environments took the uniform draw")
         return out, log_prob, entropy
 
-    def _check_eval_args(self, logits, mask_bits, actions):
-        """Shapes, dtypes and devices of an evaluate_logits call -> (num_rows, flat, logits dtype code)."""
-        cfg = self.cfg
-        A, H, WW = cfg.num_orientations * cfg.height * cfg.width, cfg.height, (cfg.width + 63) // 64
+    def _check_rows(self, n, logits, actions, mask_bits=None, flat_ok=False, rows=None):
+        """The tensors every policy call but sample_logits takes -- logits [N, n] float32 or bfloat16, actions int32 [N, 3]
+        (with flat_ok also [N]) and, where the call reads stored legal sets, mask_bits int64 [N, 2, H, WW] -> (N, the
+        logits' dtype code).  N is `rows` or, without it, what logits has."""
         dtype = _logits_dtype(logits)
-        if logits.dim() != 2 or logits.shape[1] != A:
-            raise ValueError(f"logits must have shape [N, {A}], got {list(logits.shape)}")
-        N = logits.shape[0]
-        if mask_bits.dtype != torch.int64 or tuple(mask_bits.shape) != (N, 2, H, WW):
-            raise ValueError(f"mask_bits must be int64 [{N}, 2, {H}, {WW}], got {mask_bits.dtype} {list(mask_bits.shape)}")
-        if actions.dtype != torch.int32 or tuple(actions.shape) not in ((N,), (N, 3)):
-            raise ValueError(f"actions must be int32 [{N}] (flat) or [{N}, 3], got {actions.dtype} {list(actions.shape)}")
-        for name, t in (("logits", logits), ("mask_bits", mask_bits), ("actions", actions)):
-            if t.device.type != self.device.type or (self.device.index is not None and t.device.index != self.device.index):
-                raise ValueError(f"{name} must be on {self.device}, got {t.device}")
-            if not t.is_contiguous():
-                raise ValueError(f"{name} must be C-contiguous (no copy is made)")
-        return N, actions.dim() == 1, dtype
+        N = rows if rows is not None else logits.shape[0] if logits.dim() == 2 else "N"
+        check_tensor(self.device, "logits", logits, LOGITS_DTYPES, (N, n))
+        check_tensor(self.device, "actions", actions, torch.int32, (N,) if flat_ok and actions.dim() == 1 else (N, 3))
+        if mask_bits is not None:
+            check_tensor(self.device, "mask_bits", mask_bits, torch.int64, (N, 2, self.cfg.height, (self.cfg.width + 63) // 64))
+        return N, dtype
+
+    def _check_gradient_args(self, logits, out, optional):
+        """The backward calls' own tensors: `out` like logits (a fresh one for None; returned) and the float32 ones that
+        may be None, (name, tensor, shape) each."""
+        for name, t, shape in optional:
+            if t is not None:
+                check_tensor(self.device, name, t, torch.float32, shape)
+        if out is None:
+            return torch.empty_like(logits)
+        check_tensor(self.device, "out must match logits", out, logits.dtype, logits.shape)
+        return out
 
     def evaluate_logits_forward(self, logits, mask_bits, actions, stats: Optional[torch.Tensor] = None,
                                 errors: Optional[torch.Tensor] = None):
@@ -441,15 +470,16 @@ class BatchedPlacementEnv:
         masked categorical of `logits` [N, A] with the legal sets `mask_bits` [N, 2, H, WW] (what `mask_bits()` returned
         when the rows were stored).  stats: float32 [N, 4] the backward call needs, or None.  errors: int32 [1] the error
         bits are ORed into, or None."""
-        N, flat, dtype = self._check_eval_args(logits, mask_bits, actions)
-        log_prob = torch.empty(N, dtype=torch.float32, device=logits.device)
-        entropy = torch.empty(N, dtype=torch.float32, device=logits.device)
+        N, dtype = self._check_rows(self.cfg.num_orientations * self.cfg.height * self.cfg.width, logits, actions, mask_bits, flat_ok=True)
+        flat = actions.dim() == 1
+        if stats is not None:
+            check_tensor(self.device, "stats", stats, torch.float32, (N, 4))
+        log_prob, entropy = self._log_prob_entropy(N)
         if N == 0:  # torch gives empty tensors a null pointer
             return log_prob, entropy
         _lib.check(self._L.pcbenv_evaluate_logits(
             self._h, logits.data_ptr(), dtype, mask_bits.data_ptr(), actions.data_ptr(), _lib.ACTION_FLAT if flat else _lib.ACTION_TUPLE, N,
-            log_prob.data_ptr(), entropy.data_ptr(), None if stats is None else stats.data_ptr(),
-            None if errors is None else errors.data_ptr(), self._stream()), self._h)
+            log_prob.data_ptr(), entropy.data_ptr(), _ptr(stats), _ptr(errors), self._stream()), self._h)
         return log_prob, entropy
 
     def evaluate_logits_backward(self, logits, mask_bits, actions, stats, grad_log_prob, grad_entropy,
@@ -457,20 +487,14 @@ class BatchedPlacementEnv:
         """`pcbenv_evaluate_logits_backward`, one kernel launch: the gradient with respect to `logits`, every element
         written (into `out`, or a fresh `torch.empty_like(logits)`).  grad_log_prob / grad_entropy: float32 [N] or None
         (zero)."""
-        N, flat, dtype = self._check_eval_args(logits, mask_bits, actions)
-        if out is None:
-            out = torch.empty_like(logits)
-        for name, t, shape in (("stats", stats, (N, 4)), ("grad_log_prob", grad_log_prob, (N,)), ("grad_entropy", grad_entropy, (N,))):
-            if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != logits.device):
-                raise ValueError(f"{name} must be a C-contiguous float32 tensor {list(shape)} on {logits.device}")
-        if out.dtype != logits.dtype or out.shape != logits.shape or not out.is_contiguous() or out.device != logits.device:
-            raise ValueError("out must match logits in dtype, shape and device and be C-contiguous")
+        N, dtype = self._check_rows(self.cfg.num_orientations * self.cfg.height * self.cfg.width, logits, actions, mask_bits, flat_ok=True)
+        flat = actions.dim() == 1
+        out = self._check_gradient_args(logits, out, (("stats", stats, (N, 4)), ("grad_log_prob", grad_log_prob, (N,)), ("grad_entropy", grad_entropy, (N,))))
         if N == 0:
             return out
         _lib.check(self._L.pcbenv_evaluate_logits_backward(
             self._h, logits.data_ptr(), dtype, mask_bits.data_ptr(), actions.data_ptr(), _lib.ACTION_FLAT if flat else _lib.ACTION_TUPLE, N,
-            None if stats is None else stats.data_ptr(), None if grad_log_prob is None else grad_log_prob.data_ptr(),
-            None if grad_entropy is None else grad_entropy.data_ptr(), out.data_ptr(), self._stream()), self._h)
+            _ptr(stats), _ptr(grad_log_prob), _ptr(grad_entropy), out.data_ptr(), self._stream()), self._h)
         return out
 
     @torch.no_grad()
@@ -492,29 +516,6 @@ class BatchedPlacementEnv:
             raise ValueError(f"given must name axes 0..2 other than the stage's own ({axis}), got {given}")
         return axis, bits, (self.cfg.num_orientations, self.cfg.height, self.cfg.width)[axis]
 
-    def _check_axis_tensors(self, n, logits, actions, mask_bits=None):
-        """Shapes, dtypes, devices and contiguity of an axis call -> (rows, logits dtype code)."""
-        dtype = _logits_dtype(logits)
-        if logits.dim() != 2 or logits.shape[1] != n:
-            raise ValueError(f"logits must have shape [N, {n}], got {list(logits.shape)}")
-        N = logits.shape[0]
-        if actions.dtype != torch.int32 or tuple(actions.shape) != (N, 3):
-            raise ValueError(f"actions must be int32 [{N}, 3], got {actions.dtype} {list(actions.shape)}")
-        tensors = [("logits", logits), ("actions", actions)]
-        if mask_bits is not None:
-            H, WW = self.cfg.height, (self.cfg.width + 63) // 64
-            if mask_bits.dtype != torch.int64 or tuple(mask_bits.shape) != (N, 2, H, WW):
-                raise ValueError(f"mask_bits must be int64 [{N}, 2, {H}, {WW}], got {mask_bits.dtype} {list(mask_bits.shape)}")
-            tensors.append(("mask_bits", mask_bits))
-        for name, t in tensors:
-            # as sample_logits: the handle's device, or -- where it was named without an index -- the current one
-            if t.device != self.device and not (t.device.type == "cuda" and self.device.type == "cuda" and self.device.index is None
-                                                and t.device.index == torch.cuda.current_device()):
-                raise ValueError(f"{name} must be on {self.device}, got {t.device}")
-            if not t.is_contiguous():
-                raise ValueError(f"{name} must be C-contiguous (no copy is made)")
-        return N, dtype
-
     def sample_axis(self, axis, logits: torch.Tensor, step_index: int, actions: torch.Tensor, given=(),
                     greedy: bool = False, check: bool = False):
         """One stage of a factorised policy on the device (`pcbenv_sample_axis`, one kernel launch): the masked
@@ -526,15 +527,11 @@ class BatchedPlacementEnv:
         utils/agent/factorized_action_distributions.py:107-818).  Returns (log_prob, entropy) float32 [B].  check=True
         synchronises and raises if a logit of a legal set was NaN / +inf, every one -inf, or a given value out of range."""
         axis, bits, n = self._axis_stage(axis, given)
-        N, dtype = self._check_axis_tensors(n, logits, actions)
-        if N != self.num_envs:
-            raise ValueError(f"logits must have shape [{self.num_envs}, {n}], got {list(logits.shape)}")
-        log_prob = torch.empty(N, dtype=torch.float32, device=self.device)
-        entropy = torch.empty(N, dtype=torch.float32, device=self.device)
-        err = torch.zeros(1, dtype=torch.int32, device=self.device) if check else None
+        N, dtype = self._check_rows(n, logits, actions, rows=self.num_envs)  # the sampler's rows are the handle's environments
+        (log_prob, entropy), err = self._log_prob_entropy(N), self._error_word(check)
         _lib.check(self._L.pcbenv_sample_axis(
             self._h, axis, bits, logits.data_ptr(), dtype, _lib.DRAW_GREEDY if greedy else _lib.DRAW_SAMPLE,
-            actions.data_ptr(), log_prob.data_ptr(), entropy.data_ptr(), None if err is None else err.data_ptr(),
+            actions.data_ptr(), log_prob.data_ptr(), entropy.data_ptr(), _ptr(err),
             self.run_seed, self.first_env_index, int(step_index), self._stream()), self._h)
         if check:
             e = int(err.item())
@@ -549,14 +546,13 @@ class BatchedPlacementEnv:
         derived from `mask_bits` int64 [N, 2, H, WW] and the given columns of `actions`.  errors: int32 [1] the error bits
         are ORed into, or None."""
         axis, bits, n = self._axis_stage(axis, given)
-        N, dtype = self._check_axis_tensors(n, logits, actions, mask_bits)
-        log_prob = torch.empty(N, dtype=torch.float32, device=logits.device)
-        entropy = torch.empty(N, dtype=torch.float32, device=logits.device)
+        N, dtype = self._check_rows(n, logits, actions, mask_bits)
+        log_prob, entropy = self._log_prob_entropy(N)
         if N == 0:  # torch gives empty tensors a null pointer
             return log_prob, entropy
         _lib.check(self._L.pcbenv_evaluate_axis(
             self._h, axis, bits, logits.data_ptr(), dtype, mask_bits.data_ptr(), actions.data_ptr(), N, log_prob.data_ptr(),
-            entropy.data_ptr(), None if errors is None else errors.data_ptr(), self._stream()), self._h)
+            entropy.data_ptr(), _ptr(errors), self._stream()), self._h)
         return log_prob, entropy
 
     def evaluate_axis_backward(self, axis, given, logits, mask_bits, actions, grad_log_prob, grad_entropy,
@@ -564,25 +560,19 @@ class BatchedPlacementEnv:
         """`pcbenv_evaluate_axis_backward`, one kernel launch: the gradient with respect to `logits`, every element written
         (into `out`, or a fresh `torch.empty_like(logits)`).  grad_log_prob / grad_entropy: float32 [N] or None (zero)."""
         axis, bits, n = self._axis_stage(axis, given)
-        N, dtype = self._check_axis_tensors(n, logits, actions, mask_bits)
-        if out is None:
-            out = torch.empty_like(logits)
-        for name, t in (("grad_log_prob", grad_log_prob), ("grad_entropy", grad_entropy)):
-            if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (N,) or not t.is_contiguous() or t.device != logits.device):
-                raise ValueError(f"{name} must be a C-contiguous float32 tensor [{N}] on {logits.device}")
-        if out.dtype != logits.dtype or out.shape != logits.shape or not out.is_contiguous() or out.device != logits.device:
-            raise ValueError("out must match logits in dtype, shape and device and be C-contiguous")
+        N, dtype = self._check_rows(n, logits, actions, mask_bits)
+        out = self._check_gradient_args(logits, out, (("grad_log_prob", grad_log_prob, (N,)), ("grad_entropy", grad_entropy, (N,))))
         if N == 0:
             return out
         _lib.check(self._L.pcbenv_evaluate_axis_backward(
             self._h, axis, bits, logits.data_ptr(), dtype, mask_bits.data_ptr(), actions.data_ptr(), N,
-            None if grad_log_prob is None else grad_log_prob.data_ptr(),
-            None if grad_entropy is None else grad_entropy.data_ptr(), out.data_ptr(), self._stream()), self._h)
+            _ptr(grad_log_prob), _ptr(grad_entropy), out.data_ptr(), self._stream()), self._h)
         return out
 
     def rollout_step(self, step_index: int, flat: bool = False, out: Optional[torch.Tensor] = None):
         """`sample_actions` + `step` in one kernel launch (the body of the reference's random-policy
-        `simulate()` loop, agent/random/random_policy_square.py:38-56); `out` receives the actions taken."""
+        `simulate()` loop, agent/random/random_policy_square.py:38-56); `out` receives the actions taken: int32 [B, 3] or
+        [B] (flat), C-contiguous, on `self.device`; not checked."""
         if out is None:
             out = torch.empty((self.num_envs,) if flat else (self.num_envs, 3), dtype=torch.int32, device=self.device)
         _lib.check(self._L.pcbenv_step_sampled(
@@ -594,7 +584,8 @@ class BatchedPlacementEnv:
     def rollout_steps(self, step_index0: int, num_steps: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """`num_steps` sample+step transitions in one persistent kernel launch (use with auto_reset=True): step t
         writes slot `(self.slot + t) % num_slots`; returns the actions taken, int32 [num_steps, B, 3].  The selected
-        slot is left where it was -- `select_slot(self.slot + num_steps)` continues behind the rollout."""
+        slot is left where it was -- `select_slot(self.slot + num_steps)` continues behind the rollout.
+        out: int32 [num_steps, B, 3], C-contiguous, on `self.device`; not checked."""
         if out is None:
             out = torch.empty((num_steps, self.num_envs, 3), dtype=torch.int32, device=self.device)
         _lib.check(self._L.pcbenv_rollout_sampled(
@@ -628,7 +619,7 @@ class BatchedPlacementEnv:
             raise ValueError(f"index must have shape [{self.num_envs}], got {tuple(idx.shape)}")
         use_paths = paths is not None or path_len is not None
         pa, pl, D, fmt = self._path_args(paths, path_len, self.num_envs)
-        err = torch.zeros(1, dtype=torch.int32, device=self.device) if check else None
+        err = self._error_word(check)
         # reset_done() reads _last_done: the kernel carries `done` of the selected slots over; where _last_done lives in
         # another slot (either side), the forked rows' flags are taken from the source's _last_done here, before the
         # launch -- for the rows without a transition; those with one take the `done` the kernel wrote
@@ -638,17 +629,16 @@ class BatchedPlacementEnv:
             if pl is not None:
                 taken &= (pl >= 0) & (pl <= D)
             forked = src._last_done[idx.long().clamp(0, src.num_envs - 1)]
-        ptr = lambda t: None if t is None else t.data_ptr()
         if use_paths:
             length = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
             req = _lib.PcbenvGatherPathsRequest(
                 struct_size=C.sizeof(_lib.PcbenvGatherPathsRequest), action_format=fmt, src=None if src is self else src._h,
-                src_index_dev=idx.data_ptr(), path_actions_dev=ptr(pa) if D > 0 else None, path_len_dev=ptr(pl), path_steps=D,
-                length_dev=length.data_ptr(), errors_dev=ptr(err), stream=self._stream().value)
+                src_index_dev=idx.data_ptr(), path_actions_dev=_ptr(pa) if D > 0 else None, path_len_dev=_ptr(pl), path_steps=D,
+                length_dev=length.data_ptr(), errors_dev=_ptr(err), stream=self._stream().value)
             _lib.check(self._L.pcbenv_gather_paths(self._h, C.byref(req)), self._h)
             self.gather_length = length
         else:
-            _lib.check(self._L.pcbenv_gather(self._h, None if src is self else src._h, idx.data_ptr(), ptr(err), self._stream()), self._h)
+            _lib.check(self._L.pcbenv_gather(self._h, None if src is self else src._h, idx.data_ptr(), _ptr(err), self._stream()), self._h)
         if not in_slot:
             kept = torch.where(taken, forked, self._last_done)
             self._last_done = torch.where(length > 0, self.done, kept) if use_paths else kept
@@ -734,26 +724,25 @@ class BatchedPlacementEnv:
         length = torch.empty(n, dtype=torch.int32, device=dev)
         info = torch.empty((n, 2), dtype=torch.float64, device=dev) if pins else None
         actions = torch.zeros((A, n) if fmt == _lib.ACTION_FLAT else (A, n, 3), dtype=torch.int32, device=dev) if A > 0 else None
-        err = torch.zeros(1, dtype=torch.int32, device=dev) if check else None
+        err = self._error_word(check)
         H, WW = self.cfg.height, (self.cfg.width + 63) // 64
         leaf = torch.empty((n, 2, H, WW), dtype=torch.int64, device=dev) if leaf_mask else None
         if n == 0:  # torch gives empty tensors a null pointer
             return Playout(reward, done, length, info, actions, leaf)
-        ptr = lambda t: None if t is None else t.data_ptr()
         if use_paths:
             req = _lib.PcbenvPlayoutRequest(
-                struct_size=C.sizeof(_lib.PcbenvPlayoutRequest), action_format=fmt, root_index_dev=ptr(idx), num_playouts=n,
-                path_actions_dev=ptr(pa) if D > 0 else None, path_len_dev=ptr(pl), path_steps=D, max_steps=T, reward_dev=reward.data_ptr(),
-                done_dev=done.data_ptr(), length_dev=length.data_ptr(), info_dev=ptr(info), actions_out_dev=ptr(actions), actions_steps=A,
-                leaf_mask_bits_dev=ptr(leaf), errors_dev=ptr(err), seed=self.run_seed, first_env_index=int(first_env_index),
+                struct_size=C.sizeof(_lib.PcbenvPlayoutRequest), action_format=fmt, root_index_dev=_ptr(idx), num_playouts=n,
+                path_actions_dev=_ptr(pa) if D > 0 else None, path_len_dev=_ptr(pl), path_steps=D, max_steps=T, reward_dev=reward.data_ptr(),
+                done_dev=done.data_ptr(), length_dev=length.data_ptr(), info_dev=_ptr(info), actions_out_dev=_ptr(actions), actions_steps=A,
+                leaf_mask_bits_dev=_ptr(leaf), errors_dev=_ptr(err), seed=self.run_seed, first_env_index=int(first_env_index),
                 step_index0=int(step_index), stream=self._stream().value)
             _lib.check(self._L.pcbenv_playout_paths(self._h, C.byref(req)), self._h)
             if check and int(err.item()) != 0:
                 raise IndexError(f"playout: an index is outside [0, {self.num_envs}) or a path_len outside [0, {D}] (those playouts report length 0)")
             return Playout(reward, done, length, info, actions, leaf)
         _lib.check(self._L.pcbenv_playout(
-            self._h, ptr(idx), n, ptr(fa), fmt, T, reward.data_ptr(), done.data_ptr(), length.data_ptr(), ptr(info),
-            ptr(actions), A, ptr(err), self.run_seed, int(first_env_index), int(step_index), self._stream()), self._h)
+            self._h, _ptr(idx), n, _ptr(fa), fmt, T, reward.data_ptr(), done.data_ptr(), length.data_ptr(), _ptr(info),
+            _ptr(actions), A, _ptr(err), self.run_seed, int(first_env_index), int(step_index), self._stream()), self._h)
         if check and int(err.item()) != 0:
             raise IndexError(f"playout: an index is outside [0, {self.num_envs}) (those playouts report length 0)")
         return Playout(reward, done, length, info, actions)
@@ -779,15 +768,9 @@ class BatchedPlacementEnv:
         req = _lib.PcbenvTreeRequest(struct_size=C.sizeof(_lib.PcbenvTreeRequest), num_roots=P, capacity=N, max_children=Cc, max_steps=T,
                                      c_uct=float(c_uct))
         for name, (dtype, shape) in want.items():
-            self._tree_tensor(name, tree[name], dtype, shape)
-            setattr(req, name, tree[name].data_ptr() or None)
+            check_tensor(self.device, name, tree[name], dtype, shape)
+            setattr(req, name, _ptr(tree[name]))
         return req
-
-    def _tree_tensor(self, name, t, dtype, shape):
-        here = t.device.type == self.device.type and self.device.index in (None, t.device.index)
-        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or not here:
-            raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {list(shape)} on {self.device}, "
-                             f"got {t.dtype} {list(t.shape)} on {t.device}")
 
     def tree_advance(self, req: "_lib.PcbenvTreeRequest", phases: int, reward: Optional[torch.Tensor] = None,
                      length: Optional[torch.Tensor] = None, actions: Optional[torch.Tensor] = None) -> None:
@@ -803,8 +786,8 @@ class BatchedPlacementEnv:
         for name, t, dtype, shape in (("reward", reward, torch.float64, (P,)), ("length", length, torch.int32, (P,)),
                                       ("actions", actions, torch.int32, (T, P, 3))):
             if t is not None:
-                self._tree_tensor(name, t, dtype, shape)
-            setattr(req, name, None if t is None else (t.data_ptr() or None))
+                check_tensor(self.device, name, t, dtype, shape)
+            setattr(req, name, _ptr(t))
         req.stream = self._stream().value
         _lib.check(self._L.pcbenv_tree_advance(self._h, C.byref(req)), self._h)
 
@@ -857,16 +840,15 @@ class BatchedPlacementEnv:
         """Bit-packed legal-action mask, int64 [B, 2, H, ceil(W/64)] (a copy; bit y of word [b, o, x, y // 64]).
         out: a C-contiguous int64 tensor of that shape on `self.device` to write into instead (for example one step's
         row of a [T, B, 2, H, WW] trajectory tensor); it is returned."""
+        H, WW = self.cfg.height, (self.cfg.width + 63) // 64
+        if out is not None:  # before the library is asked for the block
+            check_tensor(self.device, "out", out, torch.int64, (self.num_envs, 2, H, WW))
         stride = C.c_int64()
         ptr = self._L.pcbenv_mask_bits(self._h, C.byref(stride))
-        H, WW = self.cfg.height, (self.cfg.width + 63) // 64
-        nbytes = stride.value * self.num_envs
-        raw = _as_tensor(ptr, nbytes, self.device)  # library-owned block, wrapped without taking ownership
+        raw = _as_tensor(ptr, stride.value * self.num_envs, self.device)  # library-owned block, wrapped without taking ownership
         rows = raw.view(self.num_envs, stride.value)[:, :2 * H * WW * 8]
         if out is None:
             return rows.contiguous().view(torch.int64).view(self.num_envs, 2, H, WW)
-        if out.dtype != torch.int64 or tuple(out.shape) != (self.num_envs, 2, H, WW) or not out.is_contiguous() or out.device.type != self.device.type:
-            raise ValueError(f"mask_bits: out must be a C-contiguous int64 tensor [{self.num_envs}, 2, {H}, {WW}] on {self.device}")
         out.view(torch.uint8).view(self.num_envs, 2 * H * WW * 8).copy_(rows)
         return out
 

@@ -2,21 +2,11 @@
 parameter validation (no device needed) behaves like the reference constructors.
 No compute call is made: this runs in the CPU-only container."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
+from abi_header import declared_functions as _declared_functions
 from pcbenv import EnvConfig, named_config, _lib
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _declared_functions():
-    text = open(os.path.join(REPO, "include", "pcbenv.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(pcbenv_[a-z_]+)\s*\(", text)))
-
 
 def test_header_symbols_are_exported():
     L = _lib.load()

@@ -4,7 +4,6 @@ Also the float64 restatement of the contract (tests/evaluate_contract.py) agains
 reference's chain (masked_logits + Categorical), and masked_categorical.evaluate_torch against the restatement.  No
 compute call is made."""
 import ctypes as C
-import os
 import re
 from types import SimpleNamespace
 
@@ -13,16 +12,12 @@ import pytest
 import torch
 
 import evaluate_contract as ec
+from abi_header import text as _header
 from pcbenv import _lib
 from pcbenv.masked_categorical import evaluate, evaluate_torch, unpack_mask_bits
 from pcbenv.rollout import masked_logits
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [(1, 8, 8), (2, 6, 6), (4, 10, 10), (4, 16, 64), (4, 5, 128), (4, 7, 100), (2, 33, 65), (1, 3, 128), (4, 100, 9)]
-
-
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "pcbenv.h")).read(), flags=re.S)
 
 
 def test_header_declares_both_signatures():

@@ -169,8 +169,8 @@ def test_wrapper_argument_errors():
         with pytest.raises(ValueError):
             env._axis_stage(axis, given)
     ok = dict(logits=torch.zeros((B, H)), actions=torch.zeros((B, 3), dtype=torch.int32), bits=torch.zeros((B, 2, H, 2), dtype=torch.int64))
-    assert env._check_axis_tensors(H, ok["logits"], ok["actions"], ok["bits"]) == (B, 0)
-    assert env._check_axis_tensors(H, ok["logits"].bfloat16(), ok["actions"])[1] == 1
+    assert env._check_rows(H, ok["logits"], ok["actions"], ok["bits"]) == (B, 0)
+    assert env._check_rows(H, ok["logits"].bfloat16(), ok["actions"])[1] == 1
     bad = [
         dict(logits=torch.zeros((B, H), dtype=torch.float64)), dict(logits=torch.zeros((B, H), dtype=torch.float16)),
         dict(logits=torch.zeros((B, H + 1))), dict(logits=torch.zeros(B * H)), dict(logits=torch.zeros((B, 2 * H))[:, ::2]),
@@ -182,7 +182,7 @@ def test_wrapper_argument_errors():
     for change in bad:
         args = dict(ok, **change)
         with pytest.raises(ValueError):
-            env._check_axis_tensors(H, args["logits"], args["actions"], args["bits"])
+            env._check_rows(H, args["logits"], args["actions"], args["bits"])
         with pytest.raises(ValueError):
             env.evaluate_axis_forward(1, (0,), args["logits"], args["bits"], args["actions"])
         with pytest.raises(ValueError):
@@ -201,4 +201,4 @@ def test_wrapper_argument_errors():
     with pytest.raises(ValueError, match="out must match"):
         env.evaluate_axis_backward(1, (0,), ok["logits"], ok["bits"], ok["actions"], None, None, out=torch.zeros((B, H), dtype=torch.bfloat16))
     with pytest.raises(ValueError, match="must be on"):  # a handle on a GPU refuses host tensors before any device call
-        _Shell(cfg, B, "cuda:0")._check_axis_tensors(H, ok["logits"], ok["actions"])
+        _Shell(cfg, B, "cuda:0")._check_rows(H, ok["logits"], ok["actions"])

@@ -2,19 +2,17 @@
 argument checks that need no device refuse what they must.  Also the index arithmetic of search.best_of_k on CPU
 tensors.  No compute call is made."""
 import ctypes as C
-import os
 import re
 
 import torch
 
+import abi_header
 from pcbenv import _lib
 from pcbenv.search import child_index, pick_best
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 
 def test_gather_is_declared_exported_and_bound():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "pcbenv.h")).read(), flags=re.S)
+    text = abi_header.text()
     assert re.search(r"\bint\s+pcbenv_gather\s*\(\s*pcbenv\s*\*\s*dst\s*,\s*const\s+pcbenv\s*\*\s*src\s*,\s*const\s+int32_t\s*\*"
                      r"\s*src_index_dev\s*,\s*uint32_t\s*\*\s*errors_dev\s*,\s*void\s*\*\s*stream\s*\)", text)
     assert "pcbenv_gather" in _lib.EXPORTS

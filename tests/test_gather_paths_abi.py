@@ -4,33 +4,22 @@ refuses what it must before anything touches a device -- in the order the header
 request's own fields.  (The last check of that order, two handles of different definitions or devices, needs two handles
 and so a device: tests/test_gather_paths_gpu.py makes it.)  No compute call is made."""
 import ctypes as C
-import os
 import re
 
 import pytest
 
+from abi_header import raw as _raw, structs as _structs, text as _text
 from pcbenv import _lib
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIELDS = [("uint32_t", "struct_size"), ("int32_t", "action_format"), ("const pcbenv *", "src"), ("const int32_t *", "src_index_dev"),
           ("const int32_t *", "path_actions_dev"), ("const int32_t *", "path_len_dev"), ("int32_t", "path_steps"),
           ("int32_t *", "length_dev"), ("uint32_t *", "errors_dev"), ("void *", "stream")]
 
 
-def _raw():
-    return open(os.path.join(REPO, "include", "pcbenv.h")).read()
-
-
-def _text():
-    return re.sub(r"/\*.*?\*/", "", _raw(), flags=re.S)
-
-
 def test_header_declares_the_function_the_struct_and_the_contract():
     raw, text = _raw(), _text()
     assert re.search(r"\bint\s+pcbenv_gather_paths\s*\(\s*pcbenv\s*\*\s*dst\s*,\s*const\s+pcbenv_gather_paths_request\s*\*\s*req\s*\)\s*;", text)
-    m = re.search(r"typedef\s+struct\s+pcbenv_gather_paths_request\s*\{(.*?)\}\s*pcbenv_gather_paths_request\s*;", text, flags=re.S)
-    assert m, "the request struct is not declared"
-    fields = [(re.sub(r"\s+", " ", t).strip(), n) for t, n in re.findall(r"([\w\s]+?\*?)\s*(\w+)\s*;", m.group(1))]
+    assert "pcbenv_gather_paths_request" in _structs(), "the request struct is not declared"
+    fields = _structs()["pcbenv_gather_paths_request"]
     norm = lambda t: re.sub(r"\s*\*\s*", " *", t).strip()
     assert [(norm(t), n) for t, n in fields] == [(norm(t), n) for t, n in FIELDS], fields
     assert re.search(r"#define\s+PCBENV_ABI_VERSION\s+3\b", text)  # an addition: the version stays

@@ -2,22 +2,17 @@
 pcbenv/_lib.py binds it, and every argument check refuses what it must before anything touches a device -- in the order
 the header gives, the null handle last.  No compute call is made."""
 import ctypes as C
-import os
 import re
 
 import pytest
 
+from abi_header import raw as _raw, text as _text
 from pcbenv import _lib
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PARAMS = ["const pcbenv *env", "const int32_t *root_index_dev", "int64_t num_playouts", "const int32_t *first_actions_dev",
           "int32_t action_format", "int32_t max_steps", "double *reward_dev", "uint8_t *done_dev", "int32_t *length_dev",
           "double *info_dev", "int32_t *actions_out_dev", "int32_t actions_steps", "uint32_t *errors_dev", "uint64_t seed",
           "uint64_t first_env_index", "uint64_t step_index0", "void *stream"]
-
-
-def _raw():
-    return open(os.path.join(REPO, "include", "pcbenv.h")).read()
 
 
 def _sig(ret, name, params):
@@ -33,7 +28,7 @@ def _sig(ret, name, params):
 
 def test_header_declares_the_signature_and_the_contract():
     raw = _raw()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
+    text = _text()
     assert re.search(_sig("int", "pcbenv_playout", PARAMS), text)
     assert re.search(r"#define\s+PCBENV_ABI_VERSION\s+3\b", text)  # an addition: the version stays
     # the "what each entry point replaces" block names the reference's lines

@@ -2,14 +2,13 @@
 libpcbenv.so exports it, pcbenv/_lib.py binds it, and every argument check refuses what it must before anything touches a
 device -- in the order the header gives, the null handle last.  No compute call is made."""
 import ctypes as C
-import os
 import re
 
 import pytest
 
+from abi_header import raw as _raw, structs as _structs, text as _text
 from pcbenv import _lib
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIELDS = [("uint32_t", "struct_size"), ("int32_t", "action_format"), ("const int32_t *", "root_index_dev"), ("int64_t", "num_playouts"),
           ("const int32_t *", "path_actions_dev"), ("const int32_t *", "path_len_dev"), ("int32_t", "path_steps"), ("int32_t", "max_steps"),
           ("double *", "reward_dev"), ("uint8_t *", "done_dev"), ("int32_t *", "length_dev"), ("double *", "info_dev"),
@@ -18,28 +17,11 @@ FIELDS = [("uint32_t", "struct_size"), ("int32_t", "action_format"), ("const int
 CTYPES = {"uint32_t": C.c_uint32, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64}
 
 
-def _raw():
-    return open(os.path.join(REPO, "include", "pcbenv.h")).read()
-
-
-def _header_fields(text):
-    """(type, name) of every member of pcbenv_playout_request, in order; `uint64_t a, b, c;` declares three."""
-    body = re.search(r"typedef\s+struct\s+pcbenv_playout_request\s*\{(.*?)\}\s*pcbenv_playout_request\s*;", text, flags=re.S).group(1)
-    out = []
-    for decl in filter(None, (d.strip() for d in body.split(";"))):
-        m = re.fullmatch(r"((?:const\s+)?\w+)\s*(.*)", decl, flags=re.S)
-        base = " ".join(m.group(1).split())
-        for item in m.group(2).split(","):
-            item = item.strip()
-            out.append((base + " *", item[1:].strip()) if item.startswith("*") else (base, item))
-    return out
-
-
 def test_header_declares_the_function_the_struct_and_the_contract():
     raw = _raw()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
+    text = _text()
     assert re.search(r"\bint\s+pcbenv_playout_paths\s*\(\s*const\s+pcbenv\s*\*\s*env\s*,\s*const\s+pcbenv_playout_request\s*\*\s*req\s*\)\s*;", text)
-    assert _header_fields(text) == FIELDS
+    assert _structs()["pcbenv_playout_request"] == FIELDS
     assert re.search(r"#define\s+PCBENV_ABI_VERSION\s+3\b", text)  # an addition: the version stays
     assert raw.index("int pcbenv_playout(") < raw.index("int pcbenv_playout_paths(")  # the old declaration comes first
     top = raw.split("#ifndef PCBENV_H")[0]

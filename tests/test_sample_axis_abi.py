@@ -2,18 +2,12 @@
 with the axis enum, libpcbenv.so exports them, pcbenv/_lib.py binds them, and every argument check refuses what it must
 before anything touches a device.  No compute call is made."""
 import ctypes as C
-import os
 import re
 
 import pytest
 
+from abi_header import raw as _raw, text as _header
 from pcbenv import _lib
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "pcbenv.h")).read(), flags=re.S)
 
 
 def _sig(ret, name, params):
@@ -47,7 +41,7 @@ def test_header_declares_signatures_and_enum():
     assert re.search(r"#define\s+PCBENV_ABI_VERSION\s+3\b", text)
     # the "what each entry point replaces" block names the reference's lines
     assert re.search(r"pcbenv_sample_axis.*?factorized_action_distributions\.py:107-818",
-                     open(os.path.join(REPO, "include", "pcbenv.h")).read().split("#ifndef PCBENV_H")[0], flags=re.S)
+                     _raw().split("#ifndef PCBENV_H")[0], flags=re.S)
 
 
 def test_exported_and_bound():

@@ -369,3 +369,32 @@ def test_refused_without_bound_buffers_and_under_capture():
     assert rc == _lib.PCBENV_ESTATE and "captured" in msg
     env.step(env.sample_actions(0))  # the handle works on
     env.close()
+
+
+def test_a_handle_named_without_an_index_lives_on_the_current_device():
+    """`device="cuda"` is resolved once, at creation: `env.device` carries the index, and tensors made with `env.device`
+    or with "cuda" are accepted and give what a handle made with the explicit index gives, bit for bit."""
+    cfg, B = CONFIGS["rect_6x6"](), 2
+    O, H, W = sizes(cfg)
+    here = torch.device("cuda", torch.cuda.current_device())
+    rng = np.random.RandomState(3)
+    flat, row = rng.randn(B, O * H * W).astype(np.float32), rng.randn(B, O).astype(np.float32)
+
+    def run(env, device):
+        on = lambda a: torch.from_numpy(a).to(device)
+        bits = env.mask_bits(out=torch.empty((B, 2, H, (W + 63) // 64), dtype=torch.int64, device=device))
+        actions, lp, ent = env.sample_logits(on(flat), 0)
+        staged = torch.zeros((B, 3), dtype=torch.int32, device=device)
+        out = [bits, actions, lp, ent, *env.sample_axis(0, on(row), 0, staged), staged]
+        out += env.evaluate_logits(on(flat), bits, actions)
+        out += env.evaluate_axis_forward(0, (), on(row), bits, staged)
+        return [t.cpu() for t in out]
+    want = None
+    for name in ("cuda", str(here)):
+        env = make_env(cfg, B, device=name)
+        assert env.device == here
+        for device in (env.device, "cuda"):
+            got = run(env, device)
+            want = want or got
+            assert len(got) == len(want) == 11 and all(torch.equal(a, b) for a, b in zip(got, want)), (name, device)
+        env.close()

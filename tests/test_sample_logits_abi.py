@@ -2,20 +2,14 @@
 pcbenv/_lib.py binds it, and every argument check refuses what it must before anything touches a device.  Also the
 float64 restatement of the contract (tests/sampling_contract.py) against the uniform pick.  No compute call is made."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
 import sampling_contract as sc
+from abi_header import text as _header
 from pcbenv import _lib
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "pcbenv.h")).read(), flags=re.S)
 
 
 def test_header_declares_signature_and_enums():

@@ -9,24 +9,18 @@ import subprocess
 
 import pytest
 
+from abi_header import REPO, raw as _raw, structs as _structs, text as _text
 from pcbenv import _lib
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 POINTERS = ("ln_dev",) + _lib.TREE_TENSORS + ("selected", "path_len", "paths", "reward", "length", "actions", "errors_dev", "stream")
 MEMBERS = ("struct_size", "phases", "num_roots", "capacity", "max_children", "max_steps", "c_uct") + POINTERS
 
 
-def _raw():
-    return open(os.path.join(REPO, "include", "pcbenv.h")).read()
-
-
 def test_header_declares_the_function_the_struct_and_the_contract():
     raw = _raw()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
+    text = _text()
     assert re.search(r"\bint\s+pcbenv_tree_advance\s*\(\s*const\s+pcbenv\s*\*\s*env\s*,\s*const\s+pcbenv_tree_request\s*\*\s*req\s*\)\s*;", text)
-    body = re.search(r"typedef\s+struct\s+pcbenv_tree_request\s*\{(.*?)\}\s*pcbenv_tree_request\s*;", text, flags=re.S).group(1)
-    names = [item.strip().lstrip("*").strip() for decl in body.split(";") if decl.strip()
-             for item in re.sub(r"^\s*(?:const\s+)?\w+\s", "", decl.strip(), count=1).split(",")]
+    names = [n for _, n in _structs()["pcbenv_tree_request"]]
     assert tuple(names) == MEMBERS
     for name, value in (("PCBENV_TREE_INIT", 1), ("PCBENV_TREE_ABSORB", 2), ("PCBENV_TREE_SELECT", 4), ("PCBENV_MAX_TREE_CHILDREN", 64)):
         assert re.search(rf"#define\s+{name}\s+{value}\b", text), name
