@@ -7,7 +7,10 @@
    EVERY call every tensor of the request equals the state of csrc/pcb_tree.h replayed on the CPU.
 3. Every tensor is a view into a sentinel-filled buffer: the guards, the rows nothing was due in and the inputs keep their
    bytes, and a phase that was not asked for writes nothing.
-4. A search on a side stream behind a delay returns before the stream reaches it and gives the default stream's tree."""
+4. A search on a side stream behind a delay returns before the stream reaches it and gives the default stream's tree.
+5. 2. and 3. at every group width G (k_tree_advance<4> ... <64>) with C == G and with C == G / 2 + 1, over three blocks whose last
+   one, and from G = 16 on its last wavefront, is partly filled (tree_cases.WIDTHS); and once with no error word in the request.
+6. Trees the caller has damaged between two calls (tree_cases.damaged): the kernel does what the model does, in every tensor."""
 import time
 from types import SimpleNamespace
 
@@ -96,6 +99,8 @@ REPLAYS = {  # P, T, C, iterations, capacity, split, cells of the game (x 2 orie
     "capacity4": (7, 5, 3, 40, 4, False, 3),
     "one_phase_per_call": (7, 5, 3, 16, None, True, 3),
 }
+# every k_tree_advance<G> with C == G and with C == G / 2 + 1, three blocks each, the last one and its last wavefront partly filled
+REPLAYS.update({name: (P, tc.WIDTH_T, C, iterations, None, False, cells) for name, (P, C, iterations, cells, _, _) in tc.WIDTHS.items()})
 
 
 @pytest.fixture(scope="module")
@@ -105,19 +110,20 @@ def handle():
     env.close()
 
 
-@pytest.mark.parametrize("what", list(REPLAYS))
-def test_the_kernel_alone_equals_the_model_after_every_call(handle, what):
-    P, T, C, iterations, capacity, split, cells = REPLAYS[what]
-    case = tc.synthetic(P, T, C, iterations, capacity=capacity, split=split, cells=cells)
-    if what == "C64_P1":
-        assert any(s["path_len"].max() > 0 for s in case.states), "no descent over 64 children"
-    if what == "capacity4":
-        assert case.states[-1]["errors"] & 1
+def assert_equals_the_model_after_every_call(handle, case, errors_dev=True):
+    """case.seq call by call through tree_advance into guarded tensors; case.states: the model's state after each call.
+    errors_dev=False: the request names no error word (the guarded one must keep its zero)."""
+    P, C, T = case.P, case.C, case.T
     g = Guarded(P, case.N, C, T, handle.device)
-    req = handle.tree_request(g.t, case.c_uct)
+    req = handle.tree_request(g.t if errors_dev else {n: t for n, t in g.t.items() if n != "errors_dev"}, case.c_uct)
+    assert (req.errors_dev is not None) == errors_dev
     before = g.snapshot()
     for i, (call, want) in enumerate(zip(case.seq, case.states)):
         playout = {}
+        for name, at, value in call.get("pokes", ()):  # the damage a caller does between two calls
+            g.t[name].view(-1)[at] = value
+        if call.get("pokes") and not call["phases"] & tc.ABSORB:
+            before = g.snapshot()
         if call["phases"] & tc.ABSORB:
             for name, a in zip(("reward", "length", "actions"), call["playout"]):
                 g.t[name].copy_(torch.from_numpy(np.ascontiguousarray(a)))
@@ -138,7 +144,7 @@ def test_the_kernel_alone_equals_the_model_after_every_call(handle, what):
                 assert tc.same_bits(got, model), (i, f)
             else:
                 assert np.array_equal(got.astype(np.int64), model), (i, f)
-        assert int(g.inside(after, "errors_dev")[0]) == want["errors"], i
+        assert int(g.inside(after, "errors_dev")[0]) == (want["errors"] if errors_dev else 0), i
         untouched = ()
         if call["phases"] == tc.SELECT:
             untouched = tc.TREE_FIELDS
@@ -149,6 +155,45 @@ def test_the_kernel_alone_equals_the_model_after_every_call(handle, what):
         for f in untouched:  # a phase that was not asked for wrote nothing
             assert np.array_equal(after[f], before[f]), (i, f)
         before = after
+
+
+@pytest.mark.parametrize("what", list(REPLAYS))
+def test_the_kernel_alone_equals_the_model_after_every_call(handle, what):
+    P, T, C, iterations, capacity, split, cells = REPLAYS[what]
+    if what in tc.WIDTHS:  # with the checks, made on the CPU, that the row reaches what it is there for
+        case = tc.width_case(what)
+    else:
+        case = tc.synthetic(P, T, C, iterations, capacity=capacity, split=split, cells=cells)
+    if what == "C64_P1":
+        assert any(s["path_len"].max() > 0 for s in case.states), "no descent over 64 children"
+    if what == "capacity4":
+        assert case.states[-1]["errors"] & 1
+    assert_equals_the_model_after_every_call(handle, case)
+
+
+def test_without_an_error_word(handle):
+    """errors_dev is optional: the search of a tree of four slots, which is full (ERR_FULL) in most of its calls, with no
+    error word in the request grows the model's tree all the same."""
+    P, T, C, iterations, capacity, split, cells = REPLAYS["capacity4"]
+    case = tc.synthetic(P, T, C, iterations, capacity=capacity, split=split, cells=cells)
+    assert sum(bool(s["errors"] & tc.ERR_FULL) for s in case.states) > 10
+    assert_equals_the_model_after_every_call(handle, case, errors_dev=False)
+
+
+@pytest.mark.parametrize("G, name", tc.DAMAGE_CASES)
+def test_a_damaged_tree_is_handled_as_the_model_handles_it(handle, G, name):
+    """Trees the caller has damaged (tests/tree_cases.py:damaged; tests/test_tree_model.py asserts on the model's dump that
+    each scenario reaches the path it is named after): the kernel's lane-parallel checks give what the serial ones give,
+    in every tensor after every call.  Only roots 0 < p < P - 1 are damaged and only by values within two slots of the valid
+    range: were a check missing, the stray access would fall into a neighbouring root's rows, which are compared."""
+    sc = tc.damaged(G, name)
+    assert 0 < sc.p < sc.P - 1
+    N, C, T = sc.N, sc.C, sc.T
+    allowed = dict(selected=(-1, 0, sc.child[0], N), num_nodes=(0, N + 1), children=(0, N), parent=(sc.child[0], N), depth=(-1, T, T + 3),
+                   num_children=(-1, C, C + 5))
+    for f, at, value in sc.seq[sc.k]["pokes"]:
+        assert value in allowed[f], (f, value)
+    assert_equals_the_model_after_every_call(handle, sc)
 
 
 def test_no_roots_is_a_no_op(handle):

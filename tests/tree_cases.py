@@ -12,7 +12,11 @@ means, and with equal visits equal scores, occur; root p % 7 == 5 is refused by 
 of root p % 7 == 6 is over after its first transition (length 1, the root's children are terminal).
 
 `score_gaps` walks the selections of a replay again in Python floats -- the operations of csrc/pcb_tree.h:uct_score one by
-one, each a single IEEE operation -- and returns the distances between the best and the second-best score."""
+one, each a single IEEE operation -- and returns the distances between the best and the second-best score.
+
+`WIDTHS` / `width_case` are synthetic searches at every group width of the kernel over three blocks; `damaged` continues a
+healthy search with one call before which the caller has written out-of-range values into the tree (`pokes`), the cases of
+csrc/pcb_tree.h's promise that such a tree stops the walk and reports ERR_TREE."""
 import functools
 import math
 import os
@@ -30,6 +34,7 @@ from pcbenv.search import ln_table, tree_search
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INIT, ABSORB, SELECT = 1, 2, 4
+ERR_FULL, ERR_TREE = 1, 2  # the bits of the error word
 FILL = -7  # what the model's int32 tensors hold before the first call
 TREE_FIELDS = ("num_nodes", "parent", "depth", "visits", "num_children", "node_action", "children", "value_sum", "value_max", "terminal",
                "reward_lo", "reward_hi", "best_reward", "best_length", "best_actions")
@@ -37,6 +42,8 @@ STATE_FIELDS = ("selected", "path_len", "paths") + TREE_FIELDS
 FLOATS = ("value_sum", "value_max", "reward_lo", "reward_hi", "best_reward")
 ITERATIONS, STEP_INDEX, C_UCT, MAX_CHILDREN = 24, 5000, 0.7, 3          # of the searches on real roots (tests/test_tree_search_gpu.py's)
 ORACLE_CASES = (("small_pin", ITERATIONS), ("c3_centroid", ITERATIONS), ("spatial_7x100_t256", 12))
+POKED_CALL = 8  # next to the phases of a call in the model's input: pokes follow
+POKED = ("selected", "num_nodes", "parent", "depth", "num_children", "children")  # the tensors a call's pokes may name, by number
 GAP_BOUND = 1e-12  # a last-bit difference between two implementations of log moves a score by some 1e-16
 
 
@@ -100,10 +107,13 @@ def _words(a, floats=False):
 
 def replay(P, N, C, T, c_uct, seq):
     """-> [state after call i]: dicts of STATE_FIELDS (int64; FLOATS as float64) and `errors`.  Raises if the program
-    reports a selection that differs from the recorded one, or anything on stderr."""
+    reports a selection that differs from the recorded one, or anything on stderr.  A call may carry `pokes`, a list of
+    (tensor of POKED, flat index, value) stored into the state before its phases run."""
     parts = [np.array([P, N, C, T, len(seq), struct.unpack("<q", struct.pack("<d", float(c_uct)))[0]], np.int64), _words(ln_table(N).numpy(), True)]
     for c in seq:
-        parts.append(np.array([c["phases"], int(c["expect"] is not None)], np.int64))
+        pokes = c.get("pokes", ())
+        parts.append(np.array([c["phases"] | (POKED_CALL if pokes else 0), int(c["expect"] is not None)] +
+                              ([len(pokes)] + [w for name, at, value in pokes for w in (POKED.index(name), at, value)] if pokes else []), np.int64))
         if c["phases"] & ABSORB:
             r, L, a = c["playout"]
             parts += [_words(r, True), _words(L), _words(a)]
@@ -177,6 +187,28 @@ def min_gap(states, seq, C, c_uct, N):
     return min(gaps) if gaps else math.inf
 
 
+def exact_ties(state, C, c_uct, N):
+    """Levels of the descents of `state` at which the best score occurs twice."""
+    n = 0
+    ln = ln_table(N).numpy()
+    for p in range(state["num_nodes"].shape[0]):
+        lo, hi, node = float(state["reward_lo"][p]), float(state["reward_hi"][p]), 0
+        while not state["terminal"][p, node] and state["num_children"][p, node] == C:
+            sc = []
+            for c in range(C):
+                ch = int(state["children"][p, node, c])
+                n_c = float(max(int(state["visits"][p, ch]), 1))
+                q = (float(state["value_sum"][p, ch]) / n_c - lo) / (hi - lo) if hi > lo else 0.0
+                sc.append(q + c_uct * math.sqrt(float(ln[min(max(int(state["visits"][p, node]), 1), N)]) / n_c))
+            n += sc.count(max(sc)) > 1
+            node = int(state["children"][p, node, sc.index(max(sc))])
+    return n
+
+
+def ties(case):
+    return sum(exact_ties(s, case.C, case.c_uct, case.N) for s, c in zip(case.states, case.seq) if c["phases"] & SELECT)
+
+
 # ---- the synthetic game ---------------------------------------------------------------------------------------------
 def _mix(*xs):
     h = 0x9E3779B97F4A7C15
@@ -224,6 +256,133 @@ def synthetic(P, T, C, iterations, c_uct=0.9, seed=11, capacity=None, split=Fals
         for c in seq:
             c["expect"] = None
     return SimpleNamespace(P=P, N=N, C=C, T=T, c_uct=c_uct, ts=ts, seq=seq, states=replay(P, N, C, T, c_uct, seq))
+
+
+# ---- every group width, more than one block ------------------------------------------------------------------------
+def group_lanes(C):
+    """csrc/pcb_tree.hip:group_lanes -- the lanes per root of the k_tree_advance<G> the host picks for max_children = C."""
+    g = 4
+    while g < C:
+        g <<= 1
+    return g
+
+
+BLOCK = 256  # threads of a k_tree_advance workgroup: 256 / G roots
+# P, C, iterations, cells of synthetic(P, 5, C, iterations, cells=cells); then the G and the blocks the row is there for.
+# C == G (every lane owns a child) and C == G / 2 + 1 (the most idle lanes of a width) at each width but 64, whose C == G
+# case is the single root of test_tree_advance_gpu.REPLAYS["C64_P1"]; three blocks, the last partly filled, and from
+# G = 16 on an odd P: the last wavefront in use is partly filled too.
+WIDTHS = {
+    "G4_C4_P130": (130, 4, 40, 3, 4, 3),
+    "G8_C8_P70": (70, 8, 48, 6, 8, 3),
+    "G16_C9_P35": (35, 9, 56, 8, 16, 3),
+    "G16_C16_P35": (35, 16, 72, 12, 16, 3),
+    "G32_C17_P19": (19, 17, 80, 14, 32, 3),
+    "G32_C32_P19": (19, 32, 120, 24, 32, 3),
+    "G64_C33_P9": (9, 33, 130, 26, 64, 3),
+    "G64_C63_P9": (9, 63, 110, 100, 64, 3),  # 200 actions: a root has its 63 children after some 76 playouts
+}
+WIDTH_T = 5
+
+
+def width_case(name):
+    """synthetic() of a row of WIDTHS, after the checks that the row still exercises what it is there for: the width, the
+    blocks, the partly filled tail, a descent through a full node in the first and in the last block, exact ties, no error."""
+    P, C, iterations, cells, G, blocks = WIDTHS[name]
+    per_block, per_wave = BLOCK // G, 64 // G
+    assert group_lanes(C) == G and (C == G or C == G // 2 + 1 or (G, C) == (64, 63)), name
+    assert -(-P // per_block) == blocks and P % per_block != 0, name
+    assert G < 16 or P % 2 == 1 and (per_wave == 1 or P % per_wave != 0), name
+    case = synthetic(P, WIDTH_T, C, iterations, cells=cells)
+    first, last = slice(0, per_block), slice((blocks - 1) * per_block, P)
+    assert any((s["path_len"][first] > 0).any() for s in case.states) and any((s["path_len"][last] > 0).any() for s in case.states), name
+    assert case.states[-1]["errors"] == 0, name
+    assert ties(case) > 0, name
+    return case
+
+
+# ---- trees the caller has damaged -----------------------------------------------------------------------------------
+# G: P, T, C, iterations, cells of the healthy game, and the roots a scenario may damage: 0 < p < P - 1 (a check that
+# failed to hold would then show in a neighbouring root's rows of the same tensor, which every comparison covers), not
+# a refused root (p % 7 == 5) nor one whose children are all terminal (p % 7 == 6), and at G < 64 not at the bottom of
+# its wavefront: the groups sit at lanes 16 ... 48.
+DAMAGE_GAMES = {4: (9, 5, 3, 40, 3, (4, 7)), 16: (7, 5, 9, 56, 8, (1, 2, 3)), 64: (3, 5, 33, 130, 26, (1,))}
+NO_ACTION = (0, 1, 0)  # the second coordinate of every action of the game is 0: no node has this one
+DAMAGE = ("selected_N", "selected_minus_1", "num_nodes_0", "num_nodes_N_plus_1",
+          "last_child_bad_match_below", "first_child_bad", "middle_child_bad_no_match",
+          "last_child_bad_match_below_absorb_alone", "first_child_bad_absorb_alone", "middle_child_bad_no_match_absorb_alone",
+          "parent_N", "parent_self", "root_its_own_child",
+          "depth_minus_1", "depth_T", "depth_T_plus_3", "num_children_minus_1", "num_children_C_plus_5")
+DAMAGE_CASES = ([(4, n) for n in DAMAGE] + [(16, n) for n in DAMAGE[4:] if not n.endswith("absorb_alone")] +
+                [(64, n) for n in ("last_child_bad_match_below", "first_child_bad", "middle_child_bad_no_match")])
+
+
+def flat(shape, *index):
+    return int(np.ravel_multi_index(index, shape))
+
+
+@functools.lru_cache(maxsize=None)
+def damaged(G, name):
+    """-> SimpleNamespace(P, N, C, T, c_uct, seq, states, base, k, p, node, ...): a healthy prefix seq[:k] of the game of
+    width G, after which root p is full; call k with the pokes and, where the scenario needs a particular playout, a
+    hand-written one for root p; then two more ABSORB|SELECT calls with the playouts the healthy search got.  `base` is
+    the healthy search: its states are those of the roots nothing was done to.  node: the node call k's ABSORB is about."""
+    P, T, C, iterations, cells, roots = DAMAGE_GAMES[G]
+    base = synthetic(P, T, C, iterations, cells=cells)
+    N, shp = base.N, shapes(P, base.N, C, T)
+    p = roots[DAMAGE.index(name) % len(roots)]
+    makes_child = name.startswith("depth_")  # the node selected by the healthy search must be able to take a child
+    for k in range(1, len(base.seq) - 3):
+        st = base.states[k - 1]
+        node = int(st["selected"][p])
+        if st["num_children"][p, 0] == C and st["num_nodes"][p] < N and all(base.seq[i]["phases"] == ABSORB | SELECT for i in range(k, k + 3)) and \
+                (not makes_child or (node != 0 and not st["terminal"][p, node] and st["num_children"][p, node] < C)):
+            break
+    else:
+        raise AssertionError(f"no call of the healthy search after which root {p} suits {name}")
+    assert st["errors"] == 0
+    child = [int(c) for c in st["children"][p, 0]]
+    pokes, hand = [], None  # hand: reward, length, the action of row `row` of root p's playout
+    poke = lambda f, value, *index: pokes.append((f, flat(shp[f], *index), int(value)))
+    if name in ("selected_N", "selected_minus_1"):
+        poke("selected", N if name == "selected_N" else -1, p)
+    elif name in ("num_nodes_0", "num_nodes_N_plus_1"):
+        poke("num_nodes", 0 if name == "num_nodes_0" else N + 1, p)
+    elif "_child_bad" in name:
+        c, drawn = {"l": (C - 1, child[0]), "f": (0, child[1]), "m": (C // 2, None)}[name[0]]
+        node = 0
+        poke("selected", 0, p)
+        poke("children", N, p, 0, c)
+        hand = (0.5, 1, 0, NO_ACTION if drawn is None else tuple(int(a) for a in st["node_action"][p, drawn]))
+    elif name in ("parent_N", "parent_self"):
+        node = child[0]  # a playout of length 1 from a node of depth 1 draws nothing: it ends in the node
+        poke("selected", node, p)
+        poke("parent", N if name == "parent_N" else node, p, node)
+        hand = (0.5, 1, 0, NO_ACTION)
+    elif name == "root_its_own_child":
+        for c in range(C):
+            poke("children", 0, p, 0, c)
+        poke("num_children", C, p, 0)
+    elif name.startswith("depth_"):
+        poke("depth", {"depth_minus_1": -1, "depth_T": T, "depth_T_plus_3": T + 3}[name], p, node)
+        hand = (0.5, T + 4, T - 1 if name != "depth_minus_1" else 0, NO_ACTION)  # longer than any depth: an action was drawn
+    else:
+        node = 0
+        poke("selected", 0, p)
+        poke("num_children", -1 if name == "num_children_minus_1" else C + 5, p, 0)
+        hand = (0.5, 1, 0, NO_ACTION)
+    playout = base.seq[k]["playout"]
+    if hand is not None:
+        reward, length, actions = (np.array(a, copy=True) for a in playout)
+        reward[p], length[p] = hand[0], hand[1]
+        actions[:, p] = (1, 0, 0)  # rows the scenario must not read: an action of the game, and not the drawn one
+        actions[hand[2], p] = hand[3]
+        playout = (reward, length, actions)
+    alone = name.endswith("absorb_alone")
+    seq = base.seq[:k] + [dict(phases=ABSORB if alone else ABSORB | SELECT, playout=playout, expect=None, pokes=pokes)] + \
+        [dict(phases=ABSORB | SELECT, playout=base.seq[i]["playout"], expect=None) for i in (k + 1, k + 2)]
+    return SimpleNamespace(P=P, N=N, C=C, T=T, c_uct=base.c_uct, seq=seq, states=replay(P, N, C, T, base.c_uct, seq), base=base, k=k, p=p,
+                           node=node, child=child, hand=hand, name=name)
 
 
 # ---- searches on real roots (the CPU oracle plays the playouts) ---------------------------------------------------

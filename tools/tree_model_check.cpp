@@ -5,8 +5,12 @@
 //   g++ -std=c++17 -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -I rl-environment-for-component-placement_amd/csrc
 //
 // stdin and stdout are streams of little-endian int64 words (a float64 travels as its bits).
-//   in:   P N C T calls c_uct | ln[N + 1] | per call: phases check
+//   in:   P N C T calls c_uct | ln[N + 1] | per call: phases check [POKED: pokes | pokes x (tensor, flat index, value)]
 //           [ABSORB: reward[P] length[P] actions[T P 3]]  [SELECT and check: path_len[P] paths[T P 3] as recorded]
+//         phases: the PHASE_ bits of csrc/pcb_tree.h, and POKED = 8 if the call brings pokes (a call without them reads as
+//         it did before there were any).  A poke stores `value` into one element of the state before the phases of its
+//         call run -- the damage a caller can do to a tree.  tensor: 0 selected, 1 num_nodes, 2 parent, 3 depth, 4 num_children, 5 children
+//         (tests/tree_cases.py:POKED).  From the first poke on path_len == depth(selected) is no longer checked.
 //   out:  per call: errors | selected[P] path_len[P] paths[T P 3] | num_nodes[P] parent depth visits num_children [P N]
 //           node_action[P N 3] children[P N C] value_sum value_max terminal [P N] reward_lo reward_hi best_reward
 //           best_length [P] best_actions[T P 3]
@@ -55,10 +59,21 @@ int main() {
     std::vector<uint8_t> terminal(PN, 0xf9);
     std::vector<double> reward(P);
     std::vector<int> length(P), actions(TP3), want_len(P), want_paths(TP3);
+    std::vector<int> *const poked[] = {&selected, &num_nodes, &parent, &depth, &num_children, &children};
+    enum { POKED = 8 };
     unsigned errors = 0u;
+    bool damaged = false;
     for (int call = 0; call < calls; call++) {
-        const int phases = (int)read_word(&ok), check = (int)read_word(&ok);
-        if (!ok || phases <= 0 || phases > 7 || ((phases & PHASE_INIT) && (phases & PHASE_ABSORB))) { fprintf(stderr, "call %d: bad phases\n", call); return 2; }
+        const int word = (int)read_word(&ok), check = (int)read_word(&ok);
+        const int phases = word & ~POKED;
+        const int64_t pokes = (word & POKED) ? read_word(&ok) : 0;
+        for (int64_t i = 0; ok && i < pokes; i++) {
+            const int64_t tensor = read_word(&ok), at = read_word(&ok), value = read_word(&ok);
+            if (!ok || tensor < 0 || tensor >= 6 || at < 0 || (uint64_t)at >= poked[tensor]->size() || value != (int)value) { fprintf(stderr, "call %d: bad poke\n", call); return 2; }
+            (*poked[tensor])[(size_t)at] = (int)value;
+            damaged = true;
+        }
+        if (!ok || pokes < 0 || phases <= 0 || phases > 7 || ((phases & PHASE_INIT) && (phases & PHASE_ABSORB))) { fprintf(stderr, "call %d: bad phases\n", call); return 2; }
         if (phases & PHASE_ABSORB) {
             for (double &x : reward) x = as_double(read_word(&ok));
             ok = ok && read_ints(length) && read_ints(actions);
@@ -73,7 +88,7 @@ int main() {
             if (phases & PHASE_ABSORB) errors |= tree_absorb(r, selected[p], reward[p], length[p], actions.data());
             if (phases & PHASE_SELECT) {
                 errors |= tree_select(r, c_uct, ln.data(), paths.data(), &path_len[p], &selected[p]);
-                if (path_len[p] != r.depth[selected[p]]) { fprintf(stderr, "call %d root %d: path_len %d, depth of the selected node %d\n", call, p, path_len[p], r.depth[selected[p]]); return 1; }
+                if (!damaged && path_len[p] != r.depth[selected[p]]) { fprintf(stderr, "call %d root %d: path_len %d, depth of the selected node %d\n", call, p, path_len[p], r.depth[selected[p]]); return 1; }
                 if (!check) continue;
                 if (path_len[p] != want_len[p]) { fprintf(stderr, "call %d root %d: path_len %d, recorded %d\n", call, p, path_len[p], want_len[p]); return 1; }
                 for (int d = 0; d < path_len[p]; d++)
