@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _search_lib
 from .config import EnvConfig, KIND_PIN, KIND_RECT, KIND_SPATIAL, KIND_SQUARE
 from .instances import Instance, InstanceStream, env_seed, pack_instances
 
@@ -152,7 +152,7 @@ class BatchedPlacementEnv:
             raise RuntimeError("BatchedPlacementEnv needs a GPU device (there is no CPU fallback)")
         # the device the handle lives on, index included: one named without an index is the current device, now and for good
         self.device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
-        self._L = _lib.load()
+        self._L = _search_lib.bind(_lib.load())
         # per-environment spaces (the reference constructors' declarations); every tensor adds a leading batch dim
         from .spaces import action_space_for, observation_space_for
         self.action_space = self.single_action_space = action_space_for(cfg)
@@ -790,6 +790,56 @@ class BatchedPlacementEnv:
             setattr(req, name, _ptr(t))
         req.stream = self._stream().value
         _lib.check(self._L.pcbenv_tree_advance(self._h, C.byref(req)), self._h)
+
+    def puct_request(self, tree: Dict[str, torch.Tensor], c_puct: float = 1.0, max_children: int = 16) -> "_search_lib.PcbenvPuctRequest":
+        """The request of `puct_advance` for the tensors in `tree` (see `pcbenv.search.new_puct_tree` for a set of the right
+        shapes): the keys are the members of pcbenv_puct_request (include/pcbenv_search.h) -- the tree tensors `num_nodes`
+        ... `reward_hi`, `selected`, `path_len`, `paths` and optionally `errors_dev` -- on this device, contiguous, of the
+        dtypes and shapes the header gives; P, N and T are read off `parent` [P, N] and `paths` [T, P, 3], C = max_children
+        is an argument (the tree has no tensor with that extent).  The request holds addresses only: the caller keeps the
+        tensors alive."""
+        i32, f64 = torch.int32, torch.float64
+        par, paths = tree["parent"], tree["paths"]
+        if par.dim() != 2 or paths.dim() != 3 or paths.shape[1:] != (par.shape[0], 3):
+            raise ValueError(f"parent must be [P, N] and paths [T, P, 3], got {tuple(par.shape)} and {tuple(paths.shape)}")
+        (P, N), T = par.shape, paths.shape[0]
+        want = {"num_nodes": (i32, (P,)), "node_action": (i32, (P, N, 3)), "terminal": (torch.uint8, (P, N)), "reward_lo": (f64, (P,)),
+                "reward_hi": (f64, (P,)), "selected": (i32, (P,)), "path_len": (i32, (P,)), "paths": (i32, (T, P, 3))}
+        want.update({n: (i32, (P, N)) for n in ("parent", "depth", "visits", "num_children", "first_child")})
+        want.update({n: (f64, (P, N)) for n in ("prior", "value_sum", "value_max")})
+        if tree.get("errors_dev") is not None:
+            want["errors_dev"] = (i32, (1,))
+        req = _search_lib.PcbenvPuctRequest(struct_size=C.sizeof(_search_lib.PcbenvPuctRequest), num_roots=P, capacity=N,
+                                            max_children=int(max_children), max_steps=T, c_puct=float(c_puct))
+        for name, (dtype, shape) in want.items():
+            check_tensor(self.device, name, tree[name], dtype, shape)
+            setattr(req, name, _ptr(tree[name]))
+        return req
+
+    def puct_advance(self, req: "_search_lib.PcbenvPuctRequest", phases: int, value: Optional[torch.Tensor] = None,
+                     leaf_terminal: Optional[torch.Tensor] = None, cand_count: Optional[torch.Tensor] = None,
+                     cand_actions: Optional[torch.Tensor] = None, cand_prior: Optional[torch.Tensor] = None) -> None:
+        """One step of P PUCT search trees on the device (`pcbenv_puct_advance`, one kernel launch on the current stream,
+        nothing else): `phases` is a set of `_lib.TREE_INIT`, `TREE_ABSORB`, `TREE_SELECT`, run in that order.  SELECT descends
+        every tree by q + c_puct * prior * sqrt(n) / (1 + n_c) and writes `selected`, `path_len` and `paths` -- the `paths=` /
+        `path_len=` of the next `gather_` or `playout` call; ABSORB takes the evaluation of the selected nodes -- `value` [P]
+        float64, `leaf_terminal` [P] uint8, `cand_count` [P] int32, `cand_actions` [P, K, 3] int32, `cand_prior` [P, K]
+        float32; K is read off `cand_prior` -- expands and backs up.  `req`: `puct_request(tree, c_puct, max_children)`,
+        reusable for every call on the same tensors."""
+        P = req.num_roots
+        if P == 0:  # torch gives empty tensors a null pointer
+            return
+        req.phases = int(phases)
+        K = int(cand_prior.shape[1]) if isinstance(cand_prior, torch.Tensor) and cand_prior.dim() == 2 else "K"
+        req.num_candidates = K if isinstance(K, int) else 0
+        for name, t, dtype, shape in (("value", value, torch.float64, (P,)), ("leaf_terminal", leaf_terminal, torch.uint8, (P,)),
+                                      ("cand_count", cand_count, torch.int32, (P,)), ("cand_actions", cand_actions, torch.int32, (P, K, 3)),
+                                      ("cand_prior", cand_prior, torch.float32, (P, K))):
+            if t is not None:
+                check_tensor(self.device, name, t, dtype, shape)
+            setattr(req, name, _ptr(t))
+        req.stream = self._stream().value
+        _lib.check(self._L.pcbenv_puct_advance(self._h, C.byref(req)), self._h)
 
     def queue_cursors(self):
         """(min, max) over the environments of the number of resets performed so far (synchronises)."""

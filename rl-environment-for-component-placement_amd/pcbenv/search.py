@@ -15,6 +15,11 @@ actions the same way: k playouts behind each candidate, the forced first action 
 batch, no node ever materialised.  `tree_search_device` is the same search with the tree kept by the device
 (pcbenv_tree_advance): two launches per iteration and no tensor operation between them.
 
+`puct_search` is the AlphaZero search -- a node is expanded with a policy's best legal actions and their priors, selected
+by q + c * prior * sqrt(n) / (1 + n_c) and scored by a value -- and `puct_search_device` the same search with the tree
+kept by the device (pcbenv_puct_advance, include/pcbenv_search.h): one launch per iteration next to the evaluation.
+`network_evaluator` is the evaluation by a network on `gather_(paths=...)`'s observations; `top_priors` its candidates.
+
 `policy_backend` replaces the uniform rollout of either search by a policy's: the node a path names is materialised
 in a planner batch by `gather_(paths=...)` (pcbenv_gather_paths, one launch), and the rollout behind it draws from the
 logits a network gives for the planner's observations.
@@ -388,3 +393,275 @@ def tree_search_device(root, iterations: int, step_index: int, c_uct: float = 1.
         po = backend(tree["paths"], tree["path_len"], int(step_index) + m * T)
         root.tree_advance(req, _lib.TREE_ABSORB | (_lib.TREE_SELECT if m + 1 < M else 0), po.reward, po.length, po.actions)
     return tree_result(tree)
+
+
+# ---- PUCT: priors in selection and expansion, a value at the leaf --------------------------------------------------
+@dataclass
+class Evaluation:
+    """What an evaluator says of the P nodes the paths name (`evaluate(paths, path_len, step_index0) -> Evaluation`)."""
+    value: torch.Tensor         # [P] float64, finite: the value backed up from the node
+    terminal: torch.Tensor      # [P] uint8 / bool: the episode is over at the node
+    cand_count: torch.Tensor    # [P] int32: candidates given (a count outside [0, K] is clamped)
+    cand_actions: torch.Tensor  # [P, K, 3] int32: candidate actions in the tuple format `step` takes
+    cand_prior: torch.Tensor    # [P, K] float32: their prior probabilities, used as given
+
+
+PUCT_TREE_TENSORS = ("num_nodes", "parent", "depth", "visits", "num_children", "first_child", "node_action", "prior", "value_sum", "value_max",
+                     "terminal", "reward_lo", "reward_hi")
+
+
+@dataclass
+class PuctSearch:
+    """What `puct_search` and `puct_search_device` return.  P roots, N = capacity node slots per root (slot 0 is the root; the k
+    children of a node are the slots first_child .. first_child + k - 1), C = max_children."""
+    action: torch.Tensor         # [P, 3] int32: the most-visited root child's action (ties: the lowest slot; zero without children)
+    child_visits: torch.Tensor   # [P, C] int64: visits of the root's children, 0 where there is none
+    child_actions: torch.Tensor  # [P, C, 3] int32: their actions
+    child_priors: torch.Tensor   # [P, C] float64: their priors
+    root_value: torch.Tensor     # [P] float64: value_sum / visits of slot 0
+    num_nodes: torch.Tensor      # [P] int64: node slots in use
+    parent: torch.Tensor         # [P, N] int64, -1 for the root and for unused slots
+    depth: torch.Tensor          # [P, N] int64
+    visits: torch.Tensor         # [P, N] int64
+    num_children: torch.Tensor   # [P, N] int64
+    first_child: torch.Tensor    # [P, N] int64, -1 for a node not expanded
+    node_action: torch.Tensor    # [P, N, 3] int32: the action that leads from the parent to the node
+    prior: torch.Tensor          # [P, N] float64: the prior the node was given when its parent was expanded
+    value_sum: torch.Tensor      # [P, N] float64: sum of the values backed up through the node
+    value_max: torch.Tensor      # [P, N] float64: the largest of them, -inf for unused slots
+    terminal: torch.Tensor       # [P, N] bool: the episode is over at the node
+    reward_lo: torch.Tensor      # [P] float64: the smallest value seen (+inf before the first)
+    reward_hi: torch.Tensor      # [P] float64: the largest
+    errors: torch.Tensor         # 0-dim int32: bit 0 = the children of a node did not fit into the free slots
+
+
+def new_puct_tree(P: int, N: int, T: int, device) -> dict:
+    """The tensors of P PUCT trees of N node slots and T steps, as `BatchedPlacementEnv.puct_request` takes them.
+    Uninitialised but for `paths` and `errors_dev`: PCBENV_TREE_INIT fills the rest."""
+    i32, f64 = dict(dtype=torch.int32, device=device), dict(dtype=torch.float64, device=device)
+    tree = {n: torch.empty((P, N), **i32) for n in ("parent", "depth", "visits", "num_children", "first_child")}
+    tree.update({n: torch.empty((P, N), **f64) for n in ("prior", "value_sum", "value_max")})
+    tree.update({n: torch.empty(P, **f64) for n in ("reward_lo", "reward_hi")})
+    tree.update({n: torch.empty(P, **i32) for n in ("num_nodes", "selected", "path_len")})
+    tree.update(node_action=torch.empty((P, N, 3), **i32), terminal=torch.empty((P, N), dtype=torch.uint8, device=device),
+                paths=torch.zeros((T, P, 3), **i32), errors_dev=torch.zeros(1, **i32))
+    return tree
+
+
+def puct_result(tree: dict, max_children: int) -> PuctSearch:
+    """The tensors of a PUCT tree in the form the searches report (int32 widened to int64, the root's children summed up)."""
+    w = lambda n: tree[n].to(torch.int64)
+    visits, node_action, prior = w("visits"), tree["node_action"], tree["prior"]
+    P, N = visits.shape
+    C = int(max_children)
+    dev = visits.device
+    rows = torch.arange(P, dtype=torch.int64, device=dev)
+    lane = torch.arange(C, dtype=torch.int64, device=dev)
+    have = lane[None, :] < w("num_children")[:, :1]
+    ch = torch.where(have, w("first_child")[:, :1] + lane[None, :], torch.zeros((), dtype=torch.int64, device=dev)).clamp(0, N - 1)
+    child_visits = torch.where(have, visits[rows[:, None], ch], torch.zeros_like(ch))
+    child_actions = torch.where(have[:, :, None], node_action[rows[:, None], ch], torch.zeros_like(node_action[:, :1]).expand(P, C, 3))
+    child_priors = torch.where(have, prior[rows[:, None], ch], torch.zeros_like(prior[:, :1]).expand(P, C))
+    action = child_actions[rows, child_visits.argmax(dim=1)]
+    return PuctSearch(action, child_visits, child_actions, child_priors, tree["value_sum"][:, 0] / visits[:, 0].to(torch.float64),
+                      w("num_nodes"), w("parent"), w("depth"), visits, w("num_children"), w("first_child"), node_action, prior,
+                      tree["value_sum"], tree["value_max"], tree["terminal"].bool(), tree["reward_lo"], tree["reward_hi"],
+                      tree["errors_dev"][0])
+
+
+def _puct_arguments(root, iterations, max_children, max_steps, capacity):
+    from .batched_env import default_max_steps
+    P, C, M = int(root.num_envs), int(max_children), int(iterations)
+    if M < 1 or C < 1 or C > 64:
+        raise ValueError("a PUCT search needs iterations >= 1 and max_children in [1, 64]")
+    T = default_max_steps(root.cfg) if max_steps is None else int(max_steps)
+    N = 1 + M * C if capacity is None else int(capacity)
+    if T < 1 or N < 1:
+        raise ValueError("a PUCT search needs max_steps >= 1 and capacity >= 1")
+    return P, C, M, T, N
+
+
+def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float = 1.0, max_children: int = 16, max_steps=None,
+                capacity=None) -> PuctSearch:
+    """Batched PUCT (the AlphaZero search) over all P = root.num_envs roots in lock-step, the tree in tensors, one
+    `evaluate` per iteration and no host synchronisation inside the loop: the specification of pcbenv_puct_advance
+    (include/pcbenv_search.h), in tensor code for any device.  Iteration m:
+      selection  from the root, descend to the child with the highest q + c_puct * prior * sqrt(max(visits of the node, 1)) /
+                 (1 + visits of the child), q = the child's mean value normalised per root by the smallest and largest value
+                 seen so far, 0 for a child without a visit or while the two are equal; ties to the lowest child; stop at a
+                 terminal node or at one that has no children, after max_steps levels at the latest;
+      evaluate   evaluate(paths, path_len, step_index + m * max_steps) -> Evaluation of the P selected nodes (paths int32
+                 [max_steps, P, 3], path_len int32 [P] = the levels descended);
+      expansion  a node the evaluation calls terminal is marked so, for good.  Any other node that has no children and is not
+                 terminal gets k = clamp(cand_count, 0, min(K, max_children)) children at once, in consecutive slots, with the
+                 candidates' actions and priors as given -- or none at all, and bit 0 of `errors`, if fewer than k slots are
+                 free.  With k = 0 the node stays a leaf and is evaluated again when it is selected again;
+      backup     the value is added to visits / value_sum / value_max of the node and all its ancestors.
+    capacity: node slots per root, default 1 + iterations * max_children (what the search can use at most).  max_steps: the
+    most transitions of an episode (default: that of root.cfg).  Needs iterations >= 1."""
+    P, C, M, T, N = _puct_arguments(root, iterations, max_children, max_steps, capacity)
+    dev = getattr(root, "device", "cpu")
+    i64, f64 = dict(dtype=torch.int64, device=dev), dict(dtype=torch.float64, device=dev)
+    # one slot and one path row more than used: where a root has nothing to write, the write goes there
+    parent, first_child = torch.full((P, N + 1), -1, **i64), torch.full((P, N + 1), -1, **i64)
+    depth, visits, nchild = torch.zeros((P, N + 1), **i64), torch.zeros((P, N + 1), **i64), torch.zeros((P, N + 1), **i64)
+    node_action = torch.zeros((P, N + 1, 3), dtype=torch.int32, device=dev)
+    prior, vsum = torch.zeros((P, N + 1), **f64), torch.zeros((P, N + 1), **f64)
+    vmax = torch.full((P, N + 1), float("-inf"), **f64)
+    terminal = torch.zeros((P, N + 1), dtype=torch.bool, device=dev)
+    count = torch.ones(P, **i64)
+    lo, hi = torch.full((P,), float("inf"), **f64), torch.full((P,), float("-inf"), **f64)
+    errors = torch.zeros(1, dtype=torch.int32, device=dev)
+    rows, lane = torch.arange(P, **i64), torch.arange(C, **i64)
+    trash = torch.full((P,), N, **i64)
+    zero_r, ninf_r = torch.zeros(P, **f64), torch.full((P,), float("-inf"), **f64)
+    for m in range(M):
+        # selection (iteration m finds no node deeper than m: a bound the host knows without asking the device)
+        node = torch.zeros(P, **i64)
+        plen = torch.zeros(P, **i64)
+        stopped = torch.zeros(P, dtype=torch.bool, device=dev)
+        paths = torch.zeros((T + 1, P, 3), dtype=torch.int32, device=dev)
+        wide = hi > lo
+        span = torch.where(wide, hi - lo, torch.ones_like(hi))
+        for d in range(min(T, m)):
+            k = nchild[rows, node]
+            stopped = stopped | terminal[rows, node] | (k == 0)
+            fc = first_child[rows, node]
+            mine = (lane[None, :] < k[:, None]) & ~stopped[:, None]
+            ch = torch.where(mine, fc[:, None] + lane[None, :], trash[:, None])
+            n_c = visits[rows[:, None], ch]
+            n_cf = n_c.to(torch.float64)
+            q = (vsum[rows[:, None], ch] / n_cf.clamp(min=1.0) - lo[:, None]) / span[:, None]
+            q = torch.where((n_c > 0) & wide[:, None], q, torch.zeros_like(q))
+            n_p = visits[rows, node].clamp(min=1).to(torch.float64)
+            u = c_puct * prior[rows[:, None], ch] * torch.sqrt(n_p)[:, None] / (1.0 + n_cf)
+            score = torch.where(mine, q + u, torch.full_like(q, float("-inf")))
+            nxt = fc + score.argmax(dim=1)                         # the first maximum: the lowest child
+            node = torch.where(stopped, node, nxt)
+            paths[torch.where(stopped, torch.full_like(node, T), torch.full_like(node, d)), rows] = node_action[rows, node]
+            plen = plen + (~stopped).to(torch.int64)
+        # evaluation
+        ev = evaluate(paths[:T], plen.to(torch.int32), int(step_index) + m * T)
+        value = ev.value.to(device=dev, dtype=torch.float64)
+        over = ev.terminal.to(device=dev).bool()
+        K = int(ev.cand_prior.shape[1])
+        Kc = min(K, C)
+        # expansion: all the children at once, or none
+        terminal[rows, node] = terminal[rows, node] | over
+        k = ev.cand_count.to(device=dev, dtype=torch.int64).clamp(0, Kc)
+        due = ~over & (nchild[rows, node] == 0) & ~terminal[rows, node] & (k > 0)
+        fits = count + k <= N
+        make = due & fits
+        errors = errors | ((due & ~fits).any().to(torch.int32) * 1)
+        on = make[:, None] & (lane[None, :Kc] < k[:, None])
+        slot = torch.where(on, count[:, None] + lane[None, :Kc], trash[:, None])
+        parent[rows[:, None], slot] = torch.where(on, node[:, None], torch.full_like(slot, -1))
+        depth[rows[:, None], slot] = torch.where(on, depth[rows, node][:, None] + 1, torch.zeros_like(slot))
+        acts = ev.cand_actions.to(device=dev, dtype=torch.int32)[:, :Kc]
+        node_action[rows[:, None], slot] = torch.where(on[:, :, None], acts, torch.zeros_like(acts))
+        pri = ev.cand_prior.to(device=dev, dtype=torch.float32)[:, :Kc].to(torch.float64)
+        prior[rows[:, None], slot] = torch.where(on, pri, torch.zeros_like(pri))
+        at = torch.where(make, node, trash)
+        first_child[rows, at] = torch.where(make, count, torch.full_like(count, -1))
+        nchild[rows, at] = torch.where(make, k, torch.zeros_like(k))
+        count = count + torch.where(make, k, torch.zeros_like(k))
+        # backup
+        lo, hi = torch.minimum(lo, value), torch.maximum(hi, value)
+        cur = node
+        for _ in range(min(T, m) + 1):  # the node is at depth m at most
+            on = cur >= 0
+            idx = torch.where(on, cur, trash)[:, None]
+            visits.scatter_add_(1, idx, on.to(torch.int64)[:, None])
+            vsum.scatter_add_(1, idx, torch.where(on, value, zero_r)[:, None])
+            vmax.scatter_reduce_(1, idx, torch.where(on, value, ninf_r)[:, None], reduce="amax")
+            cur = torch.where(on, parent[rows, idx[:, 0]], torch.full_like(cur, -1))
+    tree = dict(num_nodes=count, parent=parent[:, :N], depth=depth[:, :N], visits=visits[:, :N], num_children=nchild[:, :N],
+                first_child=first_child[:, :N], node_action=node_action[:, :N], prior=prior[:, :N], value_sum=vsum[:, :N],
+                value_max=vmax[:, :N], terminal=terminal[:, :N], reward_lo=lo, reward_hi=hi, errors_dev=errors)
+    return puct_result(tree, C)
+
+
+def puct_search_device(root, iterations: int, step_index: int, evaluate, c_puct: float = 1.0, max_children: int = 16, max_steps=None,
+                       capacity=None) -> PuctSearch:
+    """`puct_search` with the tree kept by the device: an iteration is `evaluate` and one kernel launch,
+    `root.puct_advance` (pcbenv_puct_advance: expansion, backup, the next selection), with no tensor operation between
+    them: INIT | SELECT first, then per iteration `evaluate(tree paths, path_len, step_index + m * max_steps)` followed by
+    ABSORB | SELECT, the last iteration by ABSORB alone.  The same search as `puct_search` with the same arguments -- the
+    same evaluations, the same tree, field by field, floats by their bits: the score has no logarithm, every operation of
+    it is a single IEEE one on either side.  The evaluation's tensors must be on the root's device, contiguous, of the
+    dtypes `Evaluation` names (`terminal` may be bool)."""
+    from . import _lib
+    P, C, M, T, N = _puct_arguments(root, iterations, max_children, max_steps, capacity)
+    tree = new_puct_tree(P, N, T, root.device)
+    req = root.puct_request(tree, c_puct, C)
+    root.puct_advance(req, _lib.TREE_INIT | _lib.TREE_SELECT)
+    for m in range(M):
+        ev = evaluate(tree["paths"], tree["path_len"], int(step_index) + m * T)
+        over = ev.terminal.view(torch.uint8) if ev.terminal.dtype == torch.bool else ev.terminal
+        root.puct_advance(req, _lib.TREE_ABSORB | (_lib.TREE_SELECT if m + 1 < M else 0), ev.value, over, ev.cand_count, ev.cand_actions,
+                          ev.cand_prior)
+    return puct_result(tree, C)
+
+
+def top_priors(logits: torch.Tensor, action_mask: torch.Tensor, K: int):
+    """The K most probable legal actions of a masked policy: (cand_count int32 [P], cand_actions int32 [P, K, 3],
+    cand_prior float32 [P, K]).  logits [P, A] in flat action order (a = o*H*W + x*W + y), action_mask [P, O, H, W] (or
+    [P, H, W]: one orientation), non-zero = legal.  The probabilities are the float32 softmax over the legal logits,
+    exp(l - max) / sum; a stable descending sort puts equal probabilities in flat-index order, the first K are kept
+    (cand_count = min(K, legal count); the entries behind it are zero) and come back in the tuple format `step` takes.
+    A torch chain for any device, no host synchronisation."""
+    P = logits.shape[0]
+    legal = action_mask.reshape(P, -1) != 0
+    A = legal.shape[1]
+    H, W = int(action_mask.shape[-2]), int(action_mask.shape[-1])
+    l32 = logits.reshape(P, A).to(torch.float32)
+    ninf = torch.full_like(l32, float("-inf"))
+    top = torch.where(legal, l32, ninf).max(dim=1, keepdim=True).values
+    e = torch.where(legal, torch.exp(l32 - torch.where(legal.any(dim=1, keepdim=True), top, torch.zeros_like(top))), torch.zeros_like(l32))
+    p = e / e.sum(dim=1, keepdim=True).clamp(min=torch.finfo(torch.float32).tiny)
+    K = int(K)
+    order = torch.sort(torch.where(legal, p, torch.full_like(p, -1.0)), dim=1, descending=True, stable=True).indices[:, :K]
+    if order.shape[1] < K:  # fewer actions than candidates asked for
+        order = torch.cat([order, torch.zeros((P, K - order.shape[1]), dtype=order.dtype, device=order.device)], dim=1)
+    count = legal.sum(dim=1).clamp(max=K)
+    kept = torch.arange(K, device=logits.device)[None, :] < count[:, None]
+    flat = torch.where(kept, order, torch.zeros_like(order))
+    prior = torch.where(kept, p.gather(1, flat), torch.zeros((), dtype=torch.float32, device=p.device))
+    o, rem = torch.div(flat, H * W, rounding_mode="floor"), flat % (H * W)
+    actions = torch.stack([o, torch.div(rem, W, rounding_mode="floor"), rem % W], dim=2).to(torch.int32)
+    return count.to(torch.int32), actions.contiguous(), prior.contiguous()
+
+
+def network_evaluator(root, planner, logits_fn, value_fn=None, max_children: int = 16):
+    """An `evaluate` for `puct_search` / `puct_search_device` that scores a node with a network:
+    `(paths, path_len, step_index0) -> Evaluation`.  planner: P = root.num_envs environments of the root's definition
+    with auto_reset=False, the root's run_seed and first_env_index 0 (the constraints of `policy_backend`).
+
+    One call: `planner.gather_(arange(P), source=root, paths=paths, path_len=path_len)` materialises the P nodes the paths
+    name (pcbenv_gather_paths, one launch); a node is terminal if a transition of its path reported done, `(gather_length
+    > 0) & done`.  The candidates are `top_priors(logits_fn(planner.obs), planner.obs["action_mask"], max_children)`.  The
+    value is `planner.reward` where the node is terminal; elsewhere `value_fn(planner.obs)` [P], or, without a value_fn,
+    the final reward of a uniform rollout from the node: `root.playout(k=1, step_index=step_index0, paths=paths,
+    path_len=path_len, max_steps=paths.shape[0])` (pcbenv_playout_paths, one launch).  No host synchronisation."""
+    P = int(planner.num_envs)
+    if P != int(root.num_envs):
+        raise ValueError(f"the planner needs {int(root.num_envs)} environments, it has {P}")
+    if planner.auto_reset:
+        raise ValueError("the planner must be created with auto_reset=False (a node's episode ends at its first done)")
+    if planner.run_seed != root.run_seed or planner.first_env_index != 0:
+        raise ValueError("the planner must have the root's run_seed and first_env_index 0 (the keys of the draws)")
+    K = int(max_children)
+
+    def evaluate(paths, path_len, step_index0):
+        dev, T = planner.device, int(paths.shape[0])
+        planner.gather_(torch.arange(P, dtype=torch.int32, device=dev), source=root, paths=paths, path_len=path_len)
+        obs = planner.obs
+        over = (planner.gather_length > 0) & planner.done.bool()
+        count, actions, prior = top_priors(logits_fn(obs), obs["action_mask"], K)
+        if value_fn is not None:
+            leaf = value_fn(obs).to(torch.float64).reshape(P)
+        else:
+            leaf = root.playout(k=1, step_index=int(step_index0), paths=paths, path_len=path_len, max_steps=T).reward
+        value = torch.where(over, planner.reward.to(torch.float64), leaf)
+        return Evaluation(value, over.to(torch.uint8), count, actions, prior)
+    return evaluate

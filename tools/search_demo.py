@@ -1,5 +1,5 @@
 """Receding-horizon Monte-Carlo lookahead with pcbenv.search.best_of_k against the plain uniform-random policy, c3.
-python tools/search_demo.py [--roots 256] [--k 16] [--playouts | --tree [--device-tree] [--policy]]
+python tools/search_demo.py [--roots 256] [--k 16] [--playouts | --tree [--device-tree] [--policy] | --puct]
 
 Both play the same instances (one episode per root environment).  The search forks every root k times into a planner
 batch (one device-side gather), plays every child to its end with the on-device sampler, and applies the best child's
@@ -11,7 +11,10 @@ the most-visited first action is applied.  --tree --device-tree: the same search
 tree kept by the device (pcbenv_tree_advance): two launches per iteration.  --tree --policy (a spatial configuration:
 --config c4): the rollout behind every path is played by a policy instead of the uniform draw -- pcbenv.search.policy_backend
 materialises the nodes in a planner batch (pcbenv_gather_paths) and draws from the logits of pcbenv/policy.py's model with
-its initial weights (seeded, untrained: the demo shows the plumbing, not a trained policy's strength)."""
+its initial weights (seeded, untrained: the demo shows the plumbing, not a trained policy's strength).  --puct:
+pcbenv.search.puct_search_device with k iterations per move -- the tree kept by the device (pcbenv_puct_advance), a node
+expanded with the 16 most probable legal actions of pcbenv.search.network_evaluator (constant logits: uniform priors) and
+scored by one uniform rollout from it; the most-visited first action is applied."""
 import argparse
 import json
 import os
@@ -24,7 +27,8 @@ import torch  # noqa: E402
 from pcbenv import named_config  # noqa: E402
 from pcbenv.batched_env import BatchedPlacementEnv  # noqa: E402
 from pcbenv.config import KIND_SPATIAL  # noqa: E402
-from pcbenv.search import best_of_k, best_of_k_playouts, policy_backend, tree_search, tree_search_device  # noqa: E402
+from pcbenv.search import (best_of_k, best_of_k_playouts, network_evaluator, policy_backend, puct_search_device, tree_search,  # noqa: E402
+                           tree_search_device)
 
 
 def final_rewards(env, act, T):
@@ -49,7 +53,10 @@ def main():
     ap.add_argument("--tree", action="store_true", help="search with tree_search, k iterations per move (no planner batch)")
     ap.add_argument("--device-tree", action="store_true", help="with --tree: tree_search_device (the tree on the device)")
     ap.add_argument("--policy", action="store_true", help="with --tree: rollouts by pcbenv/policy.py's model (initial weights) through policy_backend")
+    ap.add_argument("--puct", action="store_true", help="search with puct_search_device, k iterations per move, network_evaluator with constant logits")
     a = ap.parse_args()
+    if a.puct and (a.tree or a.playouts):
+        ap.error("--puct goes alone")
     if a.device_tree and not a.tree:
         ap.error("--device-tree goes with --tree")
     if a.policy and not a.tree:
@@ -65,8 +72,11 @@ def main():
         e.reset()
         return e
     rand_root, search_root = make(P, 11), make(P, 11)
-    planner = make(P, 11) if a.policy else None if a.playouts or a.tree else make(P * k, 12)  # (policy_backend: the root's run seed)
+    planner = make(P, 11) if a.policy or a.puct else None if a.playouts or a.tree else make(P * k, 12)  # (policy_backend, network_evaluator: the root's run seed)
     backend = None
+    if a.puct:
+        zeros = torch.zeros((P, cfg.num_orientations * cfg.height * cfg.width), dtype=torch.float32, device=search_root.device)
+        evaluate = network_evaluator(search_root, planner, lambda obs: zeros, max_children=16)
     if a.policy:
         from pcbenv.policy import SpatialPolicy
         torch.manual_seed(0)
@@ -85,7 +95,9 @@ def main():
         nonlocal spent, planner_steps
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        if a.tree:
+        if a.puct:
+            first = puct_search_device(search_root, k, 1000 + t * T * k, evaluate, max_children=16).action
+        elif a.tree:
             first = (tree_search_device if a.device_tree else tree_search)(search_root, k, step_index=1000 + t * T * k, backend=backend).action
         elif a.playouts:
             res = best_of_k_playouts(search_root, k, step_index=1000 + t * T)
@@ -94,10 +106,10 @@ def main():
         torch.cuda.synchronize()
         spent += time.perf_counter() - t0
         planner_steps += P * k * T
-        _, r, d, _ = search_root.step(first if a.tree else res.actions[0])
+        _, r, d, _ = search_root.step(first if a.tree or a.puct else res.actions[0])
         return r, d
     search_final = final_rewards(search_root, search_step, T)
-    out = {"config": a.config, "roots": P, "k": k, "search": ("tree_search_device" if a.device_tree else "tree_search") + ("+policy_backend" if a.policy else "") if a.tree else "best_of_k_playouts" if a.playouts else "best_of_k",
+    out = {"config": a.config, "roots": P, "k": k, "search": "puct_search_device+network_evaluator" if a.puct else ("tree_search_device" if a.device_tree else "tree_search") + ("+policy_backend" if a.policy else "") if a.tree else "best_of_k_playouts" if a.playouts else "best_of_k",
            "random_policy_mean_final_reward": float(random_final.mean()),
            "best_of_k_mean_final_reward": float(search_final.mean()),
            "search_env_steps_per_sec": round(planner_steps / spent), "search_seconds": round(spent, 3)}
