@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, _search_lib
+from . import _lib, _priors_lib, _search_lib
 from .config import EnvConfig, KIND_PIN, KIND_RECT, KIND_SPATIAL, KIND_SQUARE
 from .instances import Instance, InstanceStream, env_seed, pack_instances
 
@@ -152,7 +152,7 @@ class BatchedPlacementEnv:
             raise RuntimeError("BatchedPlacementEnv needs a GPU device (there is no CPU fallback)")
         # the device the handle lives on, index included: one named without an index is the current device, now and for good
         self.device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
-        self._L = _search_lib.bind(_lib.load())
+        self._L = _priors_lib.bind(_search_lib.bind(_lib.load()))
         # per-environment spaces (the reference constructors' declarations); every tensor adds a leading batch dim
         from .spaces import action_space_for, observation_space_for
         self.action_space = self.single_action_space = action_space_for(cfg)
@@ -840,6 +840,44 @@ class BatchedPlacementEnv:
             setattr(req, name, _ptr(t))
         req.stream = self._stream().value
         _lib.check(self._L.pcbenv_puct_advance(self._h, C.byref(req)), self._h)
+
+    def top_priors(self, logits: torch.Tensor, K: int, mask_bits: Optional[torch.Tensor] = None,
+                   out: Optional[Sequence[torch.Tensor]] = None, errors: Optional[torch.Tensor] = None):
+        """The K largest legal logits of every row and their probabilities (`pcbenv_top_priors`, one kernel launch on the
+        current stream): `(cand_count int32 [N], cand_actions int32 [N, K, 3], cand_prior float32 [N, K])`, the tensors
+        `puct_advance` takes.  logits: float32 or bfloat16 `[N, A]`, A = O*H*W in the flat action order; illegal entries
+        have no influence.  mask_bits: int64 `[N, 2, H, WW]` (what `mask_bits()` returns) for arbitrary rows; None: row e
+        is environment e (N = num_envs) and the legal set is the current `action_mask`, read from the state on the
+        device.  Candidates come by logit descending, ties by flat index; the prior is float32(exp(l - max) / sum) over the
+        whole legal set, not renormalised over the K kept; entries behind cand_count are zero.  out: three tensors of
+        those shapes to write into (every element is written).  errors: int32 [1] the error bits are ORed into (1: a
+        legal logit was NaN or +inf, 2: every legal logit was -inf; those rows list their first legal actions with
+        prior 1/n), or None.  See include/pcbenv_priors.h."""
+        cfg, K = self.cfg, int(K)
+        dtype = _logits_dtype(logits)
+        N = logits.shape[0] if logits.dim() == 2 else "N"
+        if mask_bits is None:
+            N = self.num_envs
+        check_tensor(self.device, "logits", logits, LOGITS_DTYPES, (N, cfg.num_orientations * cfg.height * cfg.width))
+        if mask_bits is not None:
+            check_tensor(self.device, "mask_bits", mask_bits, torch.int64, (N, 2, cfg.height, (cfg.width + 63) // 64))
+        if errors is not None:
+            check_tensor(self.device, "errors", errors, torch.int32, (1,))
+        if out is None:
+            out = (torch.empty(N, dtype=torch.int32, device=self.device), torch.empty((N, K, 3), dtype=torch.int32, device=self.device),
+                   torch.empty((N, K), dtype=torch.float32, device=self.device))
+        count, actions, prior = out
+        for name, t, dt, shape in (("out[0] (cand_count)", count, torch.int32, (N,)), ("out[1] (cand_actions)", actions, torch.int32, (N, K, 3)),
+                                   ("out[2] (cand_prior)", prior, torch.float32, (N, K))):
+            check_tensor(self.device, name, t, dt, shape)
+        if N == 0:  # torch gives empty tensors a null pointer
+            return count, actions, prior
+        R = _priors_lib.PcbenvTopPriorsRequest
+        req = R(struct_size=C.sizeof(R), logits_dtype=dtype, num_candidates=K, reserved=0, num_rows=N, logits=logits.data_ptr(),
+                mask_bits=_ptr(mask_bits), cand_count=count.data_ptr(), cand_actions=actions.data_ptr(), cand_prior=prior.data_ptr(),
+                errors_dev=_ptr(errors), stream=self._stream().value)
+        _lib.check(self._L.pcbenv_top_priors(self._h, C.byref(req)), self._h)
+        return count, actions, prior
 
     def queue_cursors(self):
         """(min, max) over the environments of the number of resets performed so far (synchronises)."""

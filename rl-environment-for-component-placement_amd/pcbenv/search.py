@@ -632,7 +632,7 @@ def top_priors(logits: torch.Tensor, action_mask: torch.Tensor, K: int):
     return count.to(torch.int32), actions.contiguous(), prior.contiguous()
 
 
-def network_evaluator(root, planner, logits_fn, value_fn=None, max_children: int = 16):
+def network_evaluator(root, planner, logits_fn, value_fn=None, max_children: int = 16, priors: str = "torch"):
     """An `evaluate` for `puct_search` / `puct_search_device` that scores a node with a network:
     `(paths, path_len, step_index0) -> Evaluation`.  planner: P = root.num_envs environments of the root's definition
     with auto_reset=False, the root's run_seed and first_env_index 0 (the constraints of `policy_backend`).
@@ -642,7 +642,16 @@ def network_evaluator(root, planner, logits_fn, value_fn=None, max_children: int
     > 0) & done`.  The candidates are `top_priors(logits_fn(planner.obs), planner.obs["action_mask"], max_children)`.  The
     value is `planner.reward` where the node is terminal; elsewhere `value_fn(planner.obs)` [P], or, without a value_fn,
     the final reward of a uniform rollout from the node: `root.playout(k=1, step_index=step_index0, paths=paths,
-    path_len=path_len, max_steps=paths.shape[0])` (pcbenv_playout_paths, one launch).  No host synchronisation."""
+    path_len=path_len, max_steps=paths.shape[0])` (pcbenv_playout_paths, one launch).  No host synchronisation.
+
+    priors="device": the candidates are `planner.top_priors(logits_fn(planner.obs), max_children)` instead
+    (pcbenv_top_priors, one launch): the legal set is read from the planner's state, no mask is copied and nothing is
+    sorted.  The two differ where float32 `exp` makes unequal logits equally probable, or zero: there the torch chain,
+    which orders probabilities, falls back to index order, and the device, which orders the logits themselves, keeps logit
+    order; the priors differ in their last bits (the device forms them in float64 and rounds once).  With constant logits
+    the two are bit-identical: Z = n exactly and every prior is float32(1 / n) on both sides."""
+    if priors not in ("torch", "device"):
+        raise ValueError(f'priors must be "torch" or "device", got {priors!r}')
     P = int(planner.num_envs)
     if P != int(root.num_envs):
         raise ValueError(f"the planner needs {int(root.num_envs)} environments, it has {P}")
@@ -657,7 +666,10 @@ def network_evaluator(root, planner, logits_fn, value_fn=None, max_children: int
         planner.gather_(torch.arange(P, dtype=torch.int32, device=dev), source=root, paths=paths, path_len=path_len)
         obs = planner.obs
         over = (planner.gather_length > 0) & planner.done.bool()
-        count, actions, prior = top_priors(logits_fn(obs), obs["action_mask"], K)
+        if priors == "device":
+            count, actions, prior = planner.top_priors(logits_fn(obs).reshape(P, -1), K)
+        else:
+            count, actions, prior = top_priors(logits_fn(obs), obs["action_mask"], K)
         if value_fn is not None:
             leaf = value_fn(obs).to(torch.float64).reshape(P)
         else:

@@ -15,7 +15,8 @@ Per case, one JSON line:
       as it is expanded -- so each launch comes with the levels its descents took on average, and the PUCT launch is timed
       once more on a search whose nodes below the root are all terminal ("flat": every descent is one level);
   (c) a whole iteration with network_evaluator and constant logits, split by HIP events into the gather
-      (pcbenv_gather_paths), top_priors, the playout (pcbenv_playout_paths) and the tree step."""
+      (pcbenv_gather_paths), top_priors, the playout (pcbenv_playout_paths) and the tree step; and the same iteration with
+      the candidates from pcbenv_top_priors (network_evaluator(priors="device")), reported as top_priors_device."""
 import argparse
 import json
 import os
@@ -101,9 +102,9 @@ def uct_advance_ms(root, M, T, C):
     return sum(a.elapsed_time(b) for a, b in ev[:-1]) / max(M - 1, 1), float(levels) / max(M - 1, 1)
 
 
-def whole_iteration_ms(root, planner, M, T, C):
+def whole_iteration_ms(root, planner, M, T, C, device_priors=False):
     """puct_search_device with network_evaluator's steps spelled out and HIP events between them -> ms per iteration of
-    (gather, top_priors, playout, tree step)."""
+    (gather, top_priors, playout, tree step).  device_priors: the candidates come from planner.top_priors."""
     P, dev = root.num_envs, root.device
     zeros = torch.zeros((P, root.cfg.num_orientations * root.cfg.height * root.cfg.width), dtype=torch.float32, device=dev)
     tree = new_puct_tree(P, 1 + M * C, T, dev)
@@ -116,7 +117,7 @@ def whole_iteration_ms(root, planner, M, T, C):
         planner.gather_(index, source=root, paths=tree["paths"], path_len=tree["path_len"])
         over = (planner.gather_length > 0) & planner.done.bool()
         ev[m][1].record()
-        count, actions, prior = top_priors(zeros, planner.obs["action_mask"], C)
+        count, actions, prior = planner.top_priors(zeros, C) if device_priors else top_priors(zeros, planner.obs["action_mask"], C)
         ev[m][2].record()
         leaf = root.playout(k=1, step_index=STEP_INDEX + m * T, paths=tree["paths"], path_len=tree["path_len"], max_steps=T).reward
         value = torch.where(over, planner.reward, leaf)
@@ -165,6 +166,8 @@ def main():
                 tu.append(uct_advance_ms(root, M, T, C)[0])
             whole_iteration_ms(root, planner, 2, T, C)  # warm-up of its shapes
             parts = whole_iteration_ms(root, planner, M, T, C)
+            whole_iteration_ms(root, planner, 2, T, C, device_priors=True)
+            parts_dev = whole_iteration_ms(root, planner, M, T, C, device_priors=True)
             print(json.dumps({
                 "config": name, "reward_type": "centroid", "roots": a.roots, "iterations": M, "max_children": C, "equal_trees": equal,
                 "nodes_in_use_max": int(d.num_nodes.max()), "depth_max": int(d.depth.max()),
@@ -178,7 +181,7 @@ def main():
                 "tree_advance_launch_ms": [round(x, 4) for x in tu], "tree_advance_launch_ms_median": round(med(tu), 4),
                 "tree_advance_levels_per_descent": round(uct_levels, 2),
                 "chain_over_launch": round(med(tc) / M / med(tl), 1),
-                "iteration_ms": {"gather": round(parts[0], 4), "top_priors": round(parts[1], 4), "playout": round(parts[2], 4),
+                "iteration_ms": {"gather": round(parts[0], 4), "top_priors": round(parts[1], 4), "top_priors_device": round(parts_dev[1], 4), "playout": round(parts[2], 4),
                                  "tree_step": round(parts[3], 4)}}), flush=True)
         root.close()
         planner.close()

@@ -1,5 +1,5 @@
 """Receding-horizon Monte-Carlo lookahead with pcbenv.search.best_of_k against the plain uniform-random policy, c3.
-python tools/search_demo.py [--roots 256] [--k 16] [--playouts | --tree [--device-tree] [--policy] | --puct]
+python tools/search_demo.py [--roots 256] [--k 16] [--playouts | --tree [--device-tree] [--policy] | --puct [--device-priors]]
 
 Both play the same instances (one episode per root environment).  The search forks every root k times into a planner
 batch (one device-side gather), plays every child to its end with the on-device sampler, and applies the best child's
@@ -54,7 +54,10 @@ def main():
     ap.add_argument("--device-tree", action="store_true", help="with --tree: tree_search_device (the tree on the device)")
     ap.add_argument("--policy", action="store_true", help="with --tree: rollouts by pcbenv/policy.py's model (initial weights) through policy_backend")
     ap.add_argument("--puct", action="store_true", help="search with puct_search_device, k iterations per move, network_evaluator with constant logits")
+    ap.add_argument("--device-priors", action="store_true", help="with --puct: the candidates from pcbenv_top_priors (network_evaluator(priors=\"device\"))")
     a = ap.parse_args()
+    if a.device_priors and not a.puct:
+        ap.error("--device-priors goes with --puct")
     if a.puct and (a.tree or a.playouts):
         ap.error("--puct goes alone")
     if a.device_tree and not a.tree:
@@ -76,7 +79,7 @@ def main():
     backend = None
     if a.puct:
         zeros = torch.zeros((P, cfg.num_orientations * cfg.height * cfg.width), dtype=torch.float32, device=search_root.device)
-        evaluate = network_evaluator(search_root, planner, lambda obs: zeros, max_children=16)
+        evaluate = network_evaluator(search_root, planner, lambda obs: zeros, max_children=16, priors="device" if a.device_priors else "torch")
     if a.policy:
         from pcbenv.policy import SpatialPolicy
         torch.manual_seed(0)
@@ -109,7 +112,7 @@ def main():
         _, r, d, _ = search_root.step(first if a.tree or a.puct else res.actions[0])
         return r, d
     search_final = final_rewards(search_root, search_step, T)
-    out = {"config": a.config, "roots": P, "k": k, "search": "puct_search_device+network_evaluator" if a.puct else ("tree_search_device" if a.device_tree else "tree_search") + ("+policy_backend" if a.policy else "") if a.tree else "best_of_k_playouts" if a.playouts else "best_of_k",
+    out = {"config": a.config, "roots": P, "k": k, "search": "puct_search_device+network_evaluator" + ("(priors=device)" if a.device_priors else "") if a.puct else ("tree_search_device" if a.device_tree else "tree_search") + ("+policy_backend" if a.policy else "") if a.tree else "best_of_k_playouts" if a.playouts else "best_of_k",
            "random_policy_mean_final_reward": float(random_final.mean()),
            "best_of_k_mean_final_reward": float(search_final.mean()),
            "search_env_steps_per_sec": round(planner_steps / spent), "search_seconds": round(spent, 3)}
