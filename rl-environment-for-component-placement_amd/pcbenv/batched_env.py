@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, _priors_lib, _search_lib
+from . import _lib, _move_lib, _priors_lib, _search_lib
 from .config import EnvConfig, KIND_PIN, KIND_RECT, KIND_SPATIAL, KIND_SQUARE
 from .instances import Instance, InstanceStream, env_seed, pack_instances
 
@@ -152,7 +152,7 @@ class BatchedPlacementEnv:
             raise RuntimeError("BatchedPlacementEnv needs a GPU device (there is no CPU fallback)")
         # the device the handle lives on, index included: one named without an index is the current device, now and for good
         self.device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
-        self._L = _priors_lib.bind(_search_lib.bind(_lib.load()))
+        self._L = _move_lib.bind(_priors_lib.bind(_search_lib.bind(_lib.load())))
         # per-environment spaces (the reference constructors' declarations); every tensor adds a leading batch dim
         from .spaces import action_space_for, observation_space_for
         self.action_space = self.single_action_space = action_space_for(cfg)
@@ -840,6 +840,53 @@ class BatchedPlacementEnv:
             setattr(req, name, _ptr(t))
         req.stream = self._stream().value
         _lib.check(self._L.pcbenv_puct_advance(self._h, C.byref(req)), self._h)
+
+    def puct_move_request(self, tree: Dict[str, torch.Tensor], max_children: int = 16) -> "_move_lib.PcbenvPuctMoveRequest":
+        """The request of `puct_move` for the tensors in `tree`: the tree tensors of `puct_request` (`num_nodes` ...
+        `reward_hi`) and the members of pcbenv_puct_move_request (include/pcbenv_move.h) `move_slot` [P], `move_action`
+        [P, 3], `child_visits` [P, C], `child_actions` [P, C, 3], `root_value` float64 [P], `remap` [P, N] and optionally
+        `errors_dev` -- see `pcbenv.search.new_move_tensors` for a set of the right shapes -- on this device, contiguous, of
+        the dtypes and shapes the header gives; P and N are read off `parent` [P, N], C = max_children is an argument.  The
+        request holds addresses only: the caller keeps the tensors alive."""
+        i32, f64 = torch.int32, torch.float64
+        par = tree["parent"]
+        if par.dim() != 2:
+            raise ValueError(f"parent must be [P, N], got {tuple(par.shape)}")
+        (P, N), Cn = par.shape, int(max_children)
+        want = {"num_nodes": (i32, (P,)), "node_action": (i32, (P, N, 3)), "terminal": (torch.uint8, (P, N)), "reward_lo": (f64, (P,)),
+                "reward_hi": (f64, (P,)), "move_slot": (i32, (P,)), "move_action": (i32, (P, 3)), "child_visits": (i32, (P, Cn)),
+                "child_actions": (i32, (P, Cn, 3)), "root_value": (f64, (P,)), "remap": (i32, (P, N))}
+        want.update({n: (i32, (P, N)) for n in ("parent", "depth", "visits", "num_children", "first_child")})
+        want.update({n: (f64, (P, N)) for n in ("prior", "value_sum", "value_max")})
+        if tree.get("errors_dev") is not None:
+            want["errors_dev"] = (i32, (1,))
+        req = _move_lib.PcbenvPuctMoveRequest(struct_size=C.sizeof(_move_lib.PcbenvPuctMoveRequest), num_roots=P, capacity=N, max_children=Cn)
+        for name, (dtype, shape) in want.items():
+            check_tensor(self.device, name, tree[name], dtype, shape)
+            setattr(req, name, _ptr(tree[name]))
+        return req
+
+    def puct_move(self, req: "_move_lib.PcbenvPuctMoveRequest", phases: int, mode: int = _move_lib.MOVE_GREEDY, seed: Optional[int] = None,
+                  step_index: int = 0, reset: Optional[torch.Tensor] = None) -> None:
+        """The move of P PUCT trees on the device (`pcbenv_puct_move`, one kernel launch on the current stream, nothing
+        else): `phases` is a set of `_move_lib.MOVE_CHOOSE` and `MOVE_REROOT`, run in that order.  CHOOSE writes the root's
+        `child_visits`, `child_actions` and `root_value` and picks `move_slot` / `move_action`: the most-visited child
+        (`MOVE_GREEDY`) or a child drawn in proportion to the visit counts (`MOVE_PROPORTIONAL`) with the library's draw
+        hash of (seed, first_env_index + p, step_index); seed defaults to the environment's run_seed.  REROOT makes the
+        subtree of `move_slot` the tree, in place, and writes `remap`; a root with `reset` [P] uint8 non-zero (or without
+        children) gets an empty tree instead.  `req`: `puct_move_request(tree, max_children)`, reusable for every call on
+        the same tensors."""
+        P = req.num_roots
+        if P == 0:  # torch gives empty tensors a null pointer
+            return
+        req.phases, req.mode = int(phases), int(mode)
+        req.seed = (self.run_seed if seed is None else int(seed)) & (2 ** 64 - 1)
+        req.step_index, req.first_root = int(step_index) & (2 ** 64 - 1), self.first_env_index
+        if reset is not None:
+            check_tensor(self.device, "reset", reset, torch.uint8, (P,))
+        req.reset = _ptr(reset)
+        req.stream = self._stream().value
+        _lib.check(self._L.pcbenv_puct_move(self._h, C.byref(req)), self._h)
 
     def top_priors(self, logits: torch.Tensor, K: int, mask_bits: Optional[torch.Tensor] = None,
                    out: Optional[Sequence[torch.Tensor]] = None, errors: Optional[torch.Tensor] = None):

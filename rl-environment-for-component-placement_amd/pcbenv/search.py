@@ -19,6 +19,10 @@ batch, no node ever materialised.  `tree_search_device` is the same search with 
 by q + c * prior * sqrt(n) / (1 + n_c) and scored by a value -- and `puct_search_device` the same search with the tree
 kept by the device (pcbenv_puct_advance, include/pcbenv_search.h): one launch per iteration next to the evaluation.
 `network_evaluator` is the evaluation by a network on `gather_(paths=...)`'s observations; `top_priors` its candidates.
+`puct_choose` and `puct_reroot` are what stands between two searches of an episode -- the move, greedy or drawn in
+proportion to the visits, and the subtree below it as the next search's tree -- in tensor code, the specification of
+pcbenv_puct_move (include/pcbenv_move.h); `puct_selfplay` plays episodes with them on the device, two launches per move
+next to `step`.
 
 `policy_backend` replaces the uniform rollout of either search by a policy's: the node a path names is materialised
 in a planner batch by `gather_(paths=...)` (pcbenv_gather_paths, one launch), and the rollout behind it draws from the
@@ -469,20 +473,24 @@ def puct_result(tree: dict, max_children: int) -> PuctSearch:
                       tree["errors_dev"][0])
 
 
-def _puct_arguments(root, iterations, max_children, max_steps, capacity):
+def _puct_arguments(root, iterations, max_children, max_steps, capacity, tree=None):
     from .batched_env import default_max_steps
     P, C, M = int(root.num_envs), int(max_children), int(iterations)
     if M < 1 or C < 1 or C > 64:
         raise ValueError("a PUCT search needs iterations >= 1 and max_children in [1, 64]")
     T = default_max_steps(root.cfg) if max_steps is None else int(max_steps)
     N = 1 + M * C if capacity is None else int(capacity)
+    if tree is not None:  # the search goes on in the tree it is given: the capacity is that tree's
+        if tuple(tree["parent"].shape[:1]) != (P,) or tree["parent"].dim() != 2:
+            raise ValueError(f"tree: parent must be [{P}, N], got {list(tree['parent'].shape)}")
+        N = int(tree["parent"].shape[1])
     if T < 1 or N < 1:
         raise ValueError("a PUCT search needs max_steps >= 1 and capacity >= 1")
     return P, C, M, T, N
 
 
 def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float = 1.0, max_children: int = 16, max_steps=None,
-                capacity=None) -> PuctSearch:
+                capacity=None, tree=None) -> PuctSearch:
     """Batched PUCT (the AlphaZero search) over all P = root.num_envs roots in lock-step, the tree in tensors, one
     `evaluate` per iteration and no host synchronisation inside the loop: the specification of pcbenv_puct_advance
     (include/pcbenv_search.h), in tensor code for any device.  Iteration m:
@@ -498,8 +506,11 @@ def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float 
                  free.  With k = 0 the node stays a leaf and is evaluated again when it is selected again;
       backup     the value is added to visits / value_sum / value_max of the node and all its ancestors.
     capacity: node slots per root, default 1 + iterations * max_children (what the search can use at most).  max_steps: the
-    most transitions of an episode (default: that of root.cfg).  Needs iterations >= 1."""
-    P, C, M, T, N = _puct_arguments(root, iterations, max_children, max_steps, capacity)
+    most transitions of an episode (default: that of root.cfg).  Needs iterations >= 1.
+    tree: the search continues in this tree instead of an empty one -- a dict of PUCT_TREE_TENSORS (`search_tree` of an
+    earlier result, or what `puct_reroot` returns), integer tensors of any width, which is not modified; capacity is then
+    the tree's.  Such a tree may be deep from the first iteration on, so descent and backup are bounded by max_steps alone."""
+    P, C, M, T, N = _puct_arguments(root, iterations, max_children, max_steps, capacity, tree)
     dev = getattr(root, "device", "cpu")
     i64, f64 = dict(dtype=torch.int64, device=dev), dict(dtype=torch.float64, device=dev)
     # one slot and one path row more than used: where a root has nothing to write, the write goes there
@@ -512,6 +523,15 @@ def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float 
     count = torch.ones(P, **i64)
     lo, hi = torch.full((P,), float("inf"), **f64), torch.full((P,), float("-inf"), **f64)
     errors = torch.zeros(1, dtype=torch.int32, device=dev)
+    if tree is not None:
+        given = lambda n, like: tree[n].to(device=dev, dtype=like.dtype)
+        for n, t in (("parent", parent), ("first_child", first_child), ("depth", depth), ("visits", visits), ("num_children", nchild),
+                     ("node_action", node_action), ("prior", prior), ("value_sum", vsum), ("value_max", vmax), ("terminal", terminal)):
+            t[:, :N] = given(n, t)
+        count, lo, hi = given("num_nodes", count).clone(), given("reward_lo", lo).clone(), given("reward_hi", hi).clone()
+        if tree.get("errors_dev") is not None:
+            errors = tree["errors_dev"].to(device=dev, dtype=torch.int32).reshape(1).clone()
+    deepest = (lambda m: min(T, m)) if tree is None else (lambda m: T)  # an empty tree has no node deeper than m in iteration m
     rows, lane = torch.arange(P, **i64), torch.arange(C, **i64)
     trash = torch.full((P,), N, **i64)
     zero_r, ninf_r = torch.zeros(P, **f64), torch.full((P,), float("-inf"), **f64)
@@ -523,7 +543,7 @@ def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float 
         paths = torch.zeros((T + 1, P, 3), dtype=torch.int32, device=dev)
         wide = hi > lo
         span = torch.where(wide, hi - lo, torch.ones_like(hi))
-        for d in range(min(T, m)):
+        for d in range(deepest(m)):
             k = nchild[rows, node]
             stopped = stopped | terminal[rows, node] | (k == 0)
             fc = first_child[rows, node]
@@ -568,7 +588,7 @@ def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float 
         # backup
         lo, hi = torch.minimum(lo, value), torch.maximum(hi, value)
         cur = node
-        for _ in range(min(T, m) + 1):  # the node is at depth m at most
+        for _ in range(deepest(m) + 1):  # the node is at depth m at most
             on = cur >= 0
             idx = torch.where(on, cur, trash)[:, None]
             visits.scatter_add_(1, idx, on.to(torch.int64)[:, None])
@@ -581,26 +601,219 @@ def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float 
     return puct_result(tree, C)
 
 
+def _puct_iterations(root, req, tree, M, T, evaluate, step_index, first_phases):
+    """The launches of one device search of M iterations on `tree`: `first_phases` (INIT | SELECT, or SELECT alone in a tree
+    that is kept), then per iteration `evaluate` followed by ABSORB | SELECT, the last iteration by ABSORB alone."""
+    from . import _lib
+    root.puct_advance(req, first_phases)
+    for m in range(M):
+        ev = evaluate(tree["paths"], tree["path_len"], int(step_index) + m * T)
+        over = ev.terminal.view(torch.uint8) if ev.terminal.dtype == torch.bool else ev.terminal
+        root.puct_advance(req, _lib.TREE_ABSORB | (_lib.TREE_SELECT if m + 1 < M else 0), ev.value, over, ev.cand_count, ev.cand_actions,
+                          ev.cand_prior)
+
+
 def puct_search_device(root, iterations: int, step_index: int, evaluate, c_puct: float = 1.0, max_children: int = 16, max_steps=None,
-                       capacity=None) -> PuctSearch:
+                       capacity=None, tree=None) -> PuctSearch:
     """`puct_search` with the tree kept by the device: an iteration is `evaluate` and one kernel launch,
     `root.puct_advance` (pcbenv_puct_advance: expansion, backup, the next selection), with no tensor operation between
     them: INIT | SELECT first, then per iteration `evaluate(tree paths, path_len, step_index + m * max_steps)` followed by
     ABSORB | SELECT, the last iteration by ABSORB alone.  The same search as `puct_search` with the same arguments -- the
     same evaluations, the same tree, field by field, floats by their bits: the score has no logarithm, every operation of
     it is a single IEEE one on either side.  The evaluation's tensors must be on the root's device, contiguous, of the
-    dtypes `Evaluation` names (`terminal` may be bool)."""
+    dtypes `Evaluation` names (`terminal` may be bool).
+    tree: the search continues in this tree, in place -- the tensors of `new_puct_tree` as an earlier search or
+    `puct_move(MOVE_REROOT)` left them; capacity is then the tree's, INIT is skipped and the first launch is SELECT alone."""
     from . import _lib
-    P, C, M, T, N = _puct_arguments(root, iterations, max_children, max_steps, capacity)
-    tree = new_puct_tree(P, N, T, root.device)
+    P, C, M, T, N = _puct_arguments(root, iterations, max_children, max_steps, capacity, tree)
+    kept = tree is not None
+    if not kept:
+        tree = new_puct_tree(P, N, T, root.device)
     req = root.puct_request(tree, c_puct, C)
-    root.puct_advance(req, _lib.TREE_INIT | _lib.TREE_SELECT)
-    for m in range(M):
-        ev = evaluate(tree["paths"], tree["path_len"], int(step_index) + m * T)
-        over = ev.terminal.view(torch.uint8) if ev.terminal.dtype == torch.bool else ev.terminal
-        root.puct_advance(req, _lib.TREE_ABSORB | (_lib.TREE_SELECT if m + 1 < M else 0), ev.value, over, ev.cand_count, ev.cand_actions,
-                          ev.cand_prior)
+    _puct_iterations(root, req, tree, M, T, evaluate, step_index, _lib.TREE_SELECT if kept else _lib.TREE_INIT | _lib.TREE_SELECT)
     return puct_result(tree, C)
+
+
+# ---- the move of a searched game: the choice, and the subtree that stays ---------------------------------------------
+MOVE_GREEDY, MOVE_PROPORTIONAL = 0, 1  # include/pcbenv_move.h
+_M64, _GOLDEN = (1 << 64) - 1, 0x9E3779B97F4A7C15
+
+
+def _i64(x: int) -> int:
+    """The int64 with the bits of x mod 2^64."""
+    x &= _M64
+    return x - (1 << 64) if x >> 63 else x
+
+
+def _shr(z: torch.Tensor, k: int) -> torch.Tensor:
+    """Logical shift right of int64 bits."""
+    return (z >> k) & ((1 << (64 - k)) - 1)
+
+
+def _mix64(z: torch.Tensor) -> torch.Tensor:
+    """The splitmix64 finaliser on the bits of an int64 tensor (products wrap)."""
+    z = (z ^ _shr(z, 30)) * _i64(0xBF58476D1CE4E5B9)
+    z = (z ^ _shr(z, 27)) * _i64(0x94D049BB133111EB)
+    return z ^ _shr(z, 31)
+
+
+def draw_hi32(seed: int, genv: torch.Tensor, step_index: int) -> torch.Tensor:
+    """hi32(mix64(mix64(seed ^ GOLDEN * (genv + 1)) + step_index)) per entry of genv (int64): the library's draw hash, int64 in [0, 2^32)."""
+    inner = _mix64((genv.to(torch.int64) + 1) * _i64(_GOLDEN) ^ _i64(int(seed)))
+    return _shr(_mix64(inner + _i64(int(step_index))), 32)
+
+
+def search_tree(ps: PuctSearch) -> dict:
+    """The tree of a search result as the dict `puct_search(tree=)`, `puct_choose` and `puct_reroot` take."""
+    tree = {n: getattr(ps, n) for n in PUCT_TREE_TENSORS}
+    tree["errors_dev"] = ps.errors.reshape(1)
+    return tree
+
+
+def new_move_tensors(P: int, N: int, C: int, device) -> dict:
+    """The tensors pcbenv_puct_move writes, as `BatchedPlacementEnv.puct_move_request` takes them next to a tree's."""
+    i32 = dict(dtype=torch.int32, device=device)
+    return dict(move_slot=torch.empty(P, **i32), move_action=torch.empty((P, 3), **i32), child_visits=torch.empty((P, C), **i32),
+                child_actions=torch.empty((P, C, 3), **i32), root_value=torch.empty(P, dtype=torch.float64, device=device),
+                remap=torch.empty((P, N), **i32))
+
+
+def puct_choose(tree: dict, max_children: int, mode: int = MOVE_GREEDY, seed: int = 0, step_index: int = 0, first_root: int = 0) -> dict:
+    """The move of every root of a PUCT tree: the specification of pcbenv_puct_move's CHOOSE (include/pcbenv_move.h) in
+    tensor code for any device, no host synchronisation.  -> dict(move_slot int32 [P], move_action int32 [P, 3],
+    child_visits int32 [P, C], child_actions int32 [P, C, 3], root_value float64 [P]).  The children of the root, their
+    visits and root_value are `puct_result`'s.  MOVE_GREEDY: the most-visited child, ties to the lowest -- `puct_result`'s
+    `action`.  MOVE_PROPORTIONAL: with total = the sum of the children's visits and h = draw_hi32(seed, first_root + p,
+    step_index), the least child whose inclusive prefix sum of visits exceeds (h * total) >> 32 -- integers only; greedy
+    where total is 0.  A root without children: move_slot -1, action (0, 0, 0).  The tree is healthy (this is not where
+    damage is checked)."""
+    ps = puct_result(dict(tree, errors_dev=torch.zeros(1, dtype=torch.int32, device=tree["visits"].device)), max_children)
+    cv, ca = ps.child_visits, ps.child_actions
+    P = cv.shape[0]
+    rows = torch.arange(P, dtype=torch.int64, device=cv.device)
+    c = cv.argmax(dim=1)
+    if int(mode) == MOVE_PROPORTIONAL:
+        total = cv.sum(dim=1)
+        at = (draw_hi32(seed, rows + int(first_root), step_index) * total) >> 32
+        drawn = (cv.cumsum(dim=1) > at[:, None]).to(torch.int64).argmax(dim=1)
+        c = torch.where(total > 0, drawn, c)
+    has = ps.num_children[:, 0] > 0
+    slot = torch.where(has, ps.first_child[:, 0] + c, torch.full_like(c, -1))
+    action = torch.where(has[:, None], ca[rows, c], torch.zeros_like(ca[:, 0]))
+    return dict(move_slot=slot.to(torch.int32), move_action=action, child_visits=cv.to(torch.int32), child_actions=ca, root_value=ps.root_value)
+
+
+def puct_reroot(tree: dict, move_slot: torch.Tensor, reset=None):
+    """The subtree of node move_slot[p] as the tree of root p: the specification of pcbenv_puct_move's REROOT
+    (include/pcbenv_move.h) in tensor code for any device, no host synchronisation.  tree: a dict of PUCT_TREE_TENSORS
+    (healthy trees whose unused slots hold the INIT values), not modified.  -> (the new tree, tensors of the dtypes given,
+    and remap int32 [P, N]).  A slot is kept if it is move_slot or a descendant of it (pointer doubling over `parent`,
+    ceil(log2 N) rounds); remap is its rank among the kept slots and -1 elsewhere; a kept node moves to that slot with
+    parent and first_child renamed through remap and its depth taken from the new root, which gets parent -1, action 0
+    and prior 0; every other slot holds the INIT values.  reward_lo / reward_hi stay.  move_slot == 0 is the identity.
+    move_slot == -1, or reset[p] != 0: an empty tree (what PCBENV_TREE_INIT leaves) and remap -1."""
+    dev = tree["parent"].device
+    w = lambda n: tree[n].to(torch.int64)
+    parent, depth, visits, nchild, fchild, count = w("parent"), w("depth"), w("visits"), w("num_children"), w("first_child"), w("num_nodes")
+    P, N = parent.shape
+    i64 = dict(dtype=torch.int64, device=dev)
+    rows, slots = torch.arange(P, **i64), torch.arange(N, **i64)
+    m = move_slot.to(device=dev, dtype=torch.int64)
+    empty = m < 0
+    if reset is not None:
+        empty = empty | (reset.to(dev) != 0)
+    mc = m.clamp(0, N - 1)
+    below = slots[None, :] == mc[:, None]          # s is m or has m among its ancestors, so far
+    up = parent.clamp(min=0)                       # the root points at itself
+    for _ in range(max(1, (N - 1).bit_length())):
+        below = below | below.gather(1, up)
+        up = up.gather(1, up)
+    kept = below & (slots[None, :] < count[:, None]) & ~empty[:, None]
+    rank = kept.to(torch.int64).cumsum(dim=1) - 1
+    remap = torch.where(kept, rank, torch.full_like(rank, -1))
+    to = torch.where(kept, rank, torch.full_like(rank, N))    # a slot that is not kept writes into the spare column
+    is_root = kept & (slots[None, :] == mc[:, None])
+
+    def moved(values, init, dtype):
+        out = torch.full((P, N + 1) + tuple(values.shape[2:]), init, dtype=dtype, device=dev)
+        out[rows[:, None], to] = values.to(dtype)
+        return out[:, :N].contiguous()
+    new_parent = torch.where(is_root, torch.full_like(parent, -1), remap.gather(1, parent.clamp(min=0)))
+    new_first = torch.where(nchild > 0, remap.gather(1, fchild.clamp(0, N - 1)), torch.full_like(fchild, -1))
+    new_depth = depth - depth[rows, mc][:, None]
+    action = torch.where(is_root[:, :, None], torch.zeros_like(tree["node_action"]), tree["node_action"])
+    prior = torch.where(is_root, torch.zeros_like(tree["prior"]), tree["prior"])
+    like = lambda n: tree[n].dtype
+    inf = float("inf")
+    new = dict(num_nodes=torch.where(empty, torch.ones_like(count), kept.sum(dim=1)).to(like("num_nodes")),
+               parent=moved(new_parent, -1, like("parent")), depth=moved(new_depth, 0, like("depth")), visits=moved(visits, 0, like("visits")),
+               num_children=moved(nchild, 0, like("num_children")), first_child=moved(new_first, -1, like("first_child")),
+               node_action=moved(action, 0, like("node_action")), prior=moved(prior, 0.0, like("prior")),
+               value_sum=moved(tree["value_sum"], 0.0, like("value_sum")), value_max=moved(tree["value_max"], -inf, like("value_max")),
+               terminal=moved(tree["terminal"], 0, like("terminal")),
+               reward_lo=torch.where(empty, torch.full_like(tree["reward_lo"], inf), tree["reward_lo"]),
+               reward_hi=torch.where(empty, torch.full_like(tree["reward_hi"], -inf), tree["reward_hi"]))
+    for n in tree:
+        if n not in new:
+            new[n] = tree[n]
+    return new, remap.to(torch.int32)
+
+
+@dataclass
+class SelfPlay:
+    """What `puct_selfplay` returns: per move (the leading extent M = moves) and root."""
+    actions: torch.Tensor        # [M, P, 3] int32: the move played (zero for a root without children)
+    child_visits: torch.Tensor   # [M, P, C] int32: the visit counts of the root's children -- the policy target of the move
+    child_actions: torch.Tensor  # [M, P, C, 3] int32: their actions
+    root_value: torch.Tensor     # [M, P] float64: value_sum / visits of the root after the move's search
+    reward: torch.Tensor         # [M, P] float64: what `step` reported for the move
+    done: torch.Tensor           # [M, P] uint8
+    kept_visits: torch.Tensor    # [M, P] int32: the visits the next move's root started with (0: a fresh tree)
+    errors: torch.Tensor         # 0-dim int32: bit 0 = the children of a node did not fit into the free slots, bit 1 = a damaged tree
+    tree: dict                   # the tree and move tensors as the last move left them
+
+
+def puct_selfplay(root, evaluate, moves: int, iterations: int, step_index: int = 0, c_puct: float = 1.0, max_children: int = 16,
+                  max_steps=None, capacity=None, mode: int = MOVE_GREEDY, seed=None, on_move=None) -> SelfPlay:
+    """Plays `moves` moves of every root environment with a PUCT search whose tree stays on the device and is kept from
+    move to move.  Per move: `iterations` of search on the kept tree (`evaluate` and one pcbenv_puct_advance launch each,
+    as `puct_search_device(tree=)`); `root.puct_move(MOVE_CHOOSE)` -- the visit distribution of the root and the move,
+    greedy or in proportion to the visits (`mode`); `root.step(move_action)`; `root.puct_move(MOVE_REROOT, reset=done)` --
+    the subtree of the move becomes the tree, an episode that ended gets an empty one.  Two launches per move next to
+    `step`, nothing allocated inside the loop but the results' rows, no host synchronisation.
+    Iteration m of move j calls evaluate(paths, path_len, step_index + (j * iterations + m) * max_steps); the proportional
+    draw of move j has the key (seed, first_env_index + p, step_index + j), seed defaulting to run_seed ^ 0x6d6f7665 so that
+    it shares no key with the environment's own draws.
+    capacity: node slots per root, default 1 + 2 * iterations * max_children.  A kept subtree and the children the next
+    search adds have to fit: an overflow shows as bit 0 of `errors`, as in `puct_search_device`, and the search goes on in
+    the full tree.  The bound that can never overflow is 1 + moves * iterations * max_children.
+    on_move: called as on_move(j, tree) after move j's REROOT with the dict of the tree and move tensors (`remap` among
+    them), which the next move overwrites: a trainer copies what it keeps."""
+    from . import _lib, _move_lib
+    P, C, M, T, N = _puct_arguments(root, iterations, max_children, max_steps, 1 + 2 * int(iterations) * int(max_children) if capacity is None else capacity)
+    J = int(moves)
+    if J < 1:
+        raise ValueError("puct_selfplay needs moves >= 1")
+    dev = root.device
+    tree = new_puct_tree(P, N, T, dev)
+    tree.update(new_move_tensors(P, N, C, dev))
+    req, mreq = root.puct_request(tree, c_puct, C), root.puct_move_request(tree, C)
+    seed = (root.run_seed ^ 0x6d6f7665) if seed is None else int(seed)
+    i32 = dict(dtype=torch.int32, device=dev)
+    out = SelfPlay(torch.empty((J, P, 3), **i32), torch.empty((J, P, C), **i32), torch.empty((J, P, C, 3), **i32),
+                   torch.empty((J, P), dtype=torch.float64, device=dev), torch.empty((J, P), dtype=torch.float64, device=dev),
+                   torch.empty((J, P), dtype=torch.uint8, device=dev), torch.empty((J, P), **i32), tree["errors_dev"][0], tree)
+    for j in range(J):
+        _puct_iterations(root, req, tree, M, T, evaluate, int(step_index) + j * M * T, _lib.TREE_SELECT if j else _lib.TREE_INIT | _lib.TREE_SELECT)
+        root.puct_move(mreq, _move_lib.MOVE_CHOOSE, mode=mode, seed=seed, step_index=int(step_index) + j)
+        _, reward, done, _ = root.step(tree["move_action"])
+        out.actions[j], out.child_visits[j], out.child_actions[j], out.root_value[j] = tree["move_action"], tree["child_visits"], tree["child_actions"], tree["root_value"]
+        out.reward[j], out.done[j] = reward, done
+        root.puct_move(mreq, _move_lib.MOVE_REROOT, reset=done)
+        out.kept_visits[j] = tree["visits"][:, 0]
+        if on_move is not None:
+            on_move(j, tree)
+    return out
 
 
 def top_priors(logits: torch.Tensor, action_mask: torch.Tensor, K: int):

@@ -1,5 +1,5 @@
 """Receding-horizon Monte-Carlo lookahead with pcbenv.search.best_of_k against the plain uniform-random policy, c3.
-python tools/search_demo.py [--roots 256] [--k 16] [--playouts | --tree [--device-tree] [--policy] | --puct [--device-priors]]
+python tools/search_demo.py [--roots 256] [--k 16] [--playouts | --tree [--device-tree] [--policy] | --puct [--device-priors] [--reuse]]
 
 Both play the same instances (one episode per root environment).  The search forks every root k times into a planner
 batch (one device-side gather), plays every child to its end with the on-device sampler, and applies the best child's
@@ -14,7 +14,10 @@ materialises the nodes in a planner batch (pcbenv_gather_paths) and draws from t
 its initial weights (seeded, untrained: the demo shows the plumbing, not a trained policy's strength).  --puct:
 pcbenv.search.puct_search_device with k iterations per move -- the tree kept by the device (pcbenv_puct_advance), a node
 expanded with the 16 most probable legal actions of pcbenv.search.network_evaluator (constant logits: uniform priors) and
-scored by one uniform rollout from it; the most-visited first action is applied."""
+scored by one uniform rollout from it; the most-visited first action is applied.  --puct --reuse: the same search through
+pcbenv.search.puct_selfplay -- the tree stays on the device from move to move: pcbenv_puct_move picks the most-visited
+action and makes its subtree the next move's tree, so the k iterations of a move add to the visits already spent below it;
+the line then also reports the mean visits a move's root started with."""
 import argparse
 import json
 import os
@@ -27,7 +30,7 @@ import torch  # noqa: E402
 from pcbenv import named_config  # noqa: E402
 from pcbenv.batched_env import BatchedPlacementEnv  # noqa: E402
 from pcbenv.config import KIND_SPATIAL  # noqa: E402
-from pcbenv.search import (best_of_k, best_of_k_playouts, network_evaluator, policy_backend, puct_search_device, tree_search,  # noqa: E402
+from pcbenv.search import (best_of_k, best_of_k_playouts, network_evaluator, policy_backend, puct_search_device, puct_selfplay, tree_search,  # noqa: E402
                            tree_search_device)
 
 
@@ -55,9 +58,12 @@ def main():
     ap.add_argument("--policy", action="store_true", help="with --tree: rollouts by pcbenv/policy.py's model (initial weights) through policy_backend")
     ap.add_argument("--puct", action="store_true", help="search with puct_search_device, k iterations per move, network_evaluator with constant logits")
     ap.add_argument("--device-priors", action="store_true", help="with --puct: the candidates from pcbenv_top_priors (network_evaluator(priors=\"device\"))")
+    ap.add_argument("--reuse", action="store_true", help="with --puct: puct_selfplay, the subtree of the move played is kept (pcbenv_puct_move)")
     a = ap.parse_args()
     if a.device_priors and not a.puct:
         ap.error("--device-priors goes with --puct")
+    if a.reuse and not a.puct:
+        ap.error("--reuse goes with --puct")
     if a.puct and (a.tree or a.playouts):
         ap.error("--puct goes alone")
     if a.device_tree and not a.tree:
@@ -111,11 +117,22 @@ def main():
         planner_steps += P * k * T
         _, r, d, _ = search_root.step(first if a.tree or a.puct else res.actions[0])
         return r, d
-    search_final = final_rewards(search_root, search_step, T)
-    out = {"config": a.config, "roots": P, "k": k, "search": "puct_search_device+network_evaluator" + ("(priors=device)" if a.device_priors else "") if a.puct else ("tree_search_device" if a.device_tree else "tree_search") + ("+policy_backend" if a.policy else "") if a.tree else "best_of_k_playouts" if a.playouts else "best_of_k",
+    kept = None
+    if a.reuse:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        sp = puct_selfplay(search_root, evaluate, T, k, step_index=1000, max_children=16)
+        torch.cuda.synchronize()
+        spent, planner_steps = time.perf_counter() - t0, P * k * T * T
+        search_final = final_rewards(search_root, lambda t: (sp.reward[t], sp.done[t]), T)
+        kept = {"mean_visits_kept_per_move": round(float(sp.kept_visits[:-1].double().mean()), 2), "tree_errors": int(sp.errors)}
+    else:
+        search_final = final_rewards(search_root, search_step, T)
+    out = {"config": a.config, "roots": P, "k": k, "search": ("puct_selfplay" if a.reuse else "puct_search_device") + "+network_evaluator" + ("(priors=device)" if a.device_priors else "") if a.puct else ("tree_search_device" if a.device_tree else "tree_search") + ("+policy_backend" if a.policy else "") if a.tree else "best_of_k_playouts" if a.playouts else "best_of_k",
            "random_policy_mean_final_reward": float(random_final.mean()),
            "best_of_k_mean_final_reward": float(search_final.mean()),
            "search_env_steps_per_sec": round(planner_steps / spent), "search_seconds": round(spent, 3)}
+    out.update(kept or {})
     print(json.dumps(out), flush=True)
     for e in (rand_root, search_root, planner):
         if e is not None:
