@@ -1,5 +1,6 @@
 // pcb_policy_common.h -- what the kernels that read a policy's logits through the legal-action bit rows share
-// (k_sample_logits in pcb_policy.hip; k_evaluate_logits and its backward in pcb_policy_eval.hip): the segment
+// (k_sample_logits in pcb_policy.hip; k_evaluate_logits and its backward in pcb_policy_eval.hip; k_evaluate_visits and
+// its backward in pcb_policy_visits.hip): the segment
 // addressing, the bit-row staging, the chunk loads, the weight of a logit, pass 1 of the forward kernels, the pieces of
 // their wavefront-0 combine, the DPP row / wavefront reductions and the launch selection.  The axis kernels
 // (pcb_policy_axis.hip) take the weight, the wavefront reductions and the gradient of one logit from here.
@@ -12,6 +13,7 @@
 #include "pcbenv.h"
 #include "pcb_device.h"
 #include "pcb_launch.h"
+#include "pcb_transition.h"
 
 namespace {
 
@@ -45,9 +47,14 @@ __device__ inline void store1(float *p, float v) { *p = v; }
 __device__ inline void store1(bf16_bits *p, float v) { *p = to_bf16(v); }
 // gradient of one legal logit.  c = M + log Z split as (M, log Z): lp = (l - M) - log Z keeps the cancellation in the
 // first, exact-or-nearly-exact difference.  p = 0 (a legal -inf logit, or underflow): the entropy term is 0, never NaN.
+__device__ inline float entropy_term(float l, float M, float logZ, float Hrow, float gH, float *p) {  // g_H p (log p + Hrow), and p
+    const float lp = (l - M) - logZ;
+    *p = exp2f(lp * LOG2E);
+    return *p > 0.f ? gH * (*p * (lp + Hrow)) : 0.f;
+}
 __device__ inline float grad_one(float l, float M, float logZ, float Hrow, float glp, float gH, bool is_action) {
-    const float lp = (l - M) - logZ, p = exp2f(lp * LOG2E);
-    const float ge = p > 0.f ? gH * (p * (lp + Hrow)) : 0.f;
+    float p;
+    const float ge = entropy_term(l, M, logZ, Hrow, gH, &p);
     return glp * ((is_action ? 1.f : 0.f) - p) - ge;
 }
 
@@ -90,6 +97,39 @@ __device__ inline Seg segment(int j, int H, int W, int WW) {
     return g;
 }
 __device__ inline u64 seg_word(const u64 *vml, const Seg &g, int H, int WW) { return vml[(g.o & 1) * H * WW + g.x * WW + g.w]; }
+
+// the gradient's vector stores: four consecutive elements to a 16-byte (float) / 8-byte (bf16) aligned address
+template <typename V> __device__ inline void store_vec(V *p, V v) {
+#ifdef PCB_EV_NT_STORES
+    __builtin_nontemporal_store(v, p);
+#else
+    *p = v;
+#endif
+}
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+__device__ inline void store4(float *p, const float v[4]) { store_vec((f32x4 *)p, f32x4{v[0], v[1], v[2], v[3]}); }
+__device__ inline void store4(bf16_bits *p, const float v[4]) {
+    store_vec((u32x2 *)p, u32x2{(unsigned)to_bf16(v[0]) | ((unsigned)to_bf16(v[1]) << 16), (unsigned)to_bf16(v[2]) | ((unsigned)to_bf16(v[3]) << 16)});
+}
+
+// A caller's action -- entry i of `actions`, [.., 3] (PCBENV_ACTION_TUPLE) or [..] (PCBENV_ACTION_FLAT) -- against the staged
+// bit rows: its flat index, or -1 when it is out of range; *legal: its bit.  (The stored action of k_evaluate_logits, a
+// target entry of k_evaluate_visits.)
+__device__ inline int stored_action(const u64 *vml, const EvalGeom &q, const int *actions, int fmt, size_t i, bool *legal) {
+    const int HW = q.H * q.W;
+    int o, x, y;
+    if (fmt == PCBENV_ACTION_FLAT) {
+        const int a = actions[i];
+        if (a < 0 || a >= q.O * HW) { *legal = false; return -1; }
+        split_action(a, HW, q.W, &o, &x, &y);
+    } else {
+        o = actions[3 * i]; x = actions[3 * i + 1]; y = actions[3 * i + 2];
+        if (o < 0 || o >= q.O || x < 0 || x >= q.H || y < 0 || y >= q.W) { *legal = false; return -1; }  // !PCB_ACTION_IN_RANGE, as it stood
+    }
+    *legal = PCB_LEGAL_BIT(vml, (o & 1) * q.H * q.WW, q.WW, x, y);
+    return PCB_FLATTEN_ACTION(o, x, y, HW, q.W);
+}
 
 // The LDS of the forward kernels, carved the same way by both: the bit rows [2][H][WW], then per segment slot m, s, t and
 // the first index of the max (the sampler's only), then the flag of a NaN / +inf legal logit.  The backward uses the

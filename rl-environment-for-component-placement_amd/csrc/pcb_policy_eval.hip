@@ -23,13 +23,12 @@
 #include "pcbenv.h"
 #include "pcb_launch.h"
 #include "pcb_policy_common.h"
-#include "pcb_transition.h"
 
 namespace {
 
 // Segments per lane whose loads are issued before the first is used (as PCB_SL_UNROLL), and the smallest A launched with
-// four wavefronts.  -DPCB_EV_NT_STORES: the gradient is written with non-temporal stores (A/B builds only;
-// profiles/evaluate_logits_ab.txt).
+// four wavefronts.  -DPCB_EV_NT_STORES: the gradient is written with non-temporal stores (store_vec in
+// pcb_policy_common.h; A/B builds only; profiles/evaluate_logits_ab.txt).
 #ifndef PCB_EV_UNROLL
 #define PCB_EV_UNROLL 4
 #endif
@@ -40,36 +39,6 @@ constexpr int UNROLL = PCB_EV_UNROLL;
 
 // row status in stats[4 r + 3]
 constexpr float ROW_OK = 0.f, ROW_ZERO = 1.f, ROW_NO_ONE_HOT = 2.f;
-
-template <typename V> __device__ inline void store_vec(V *p, V v) {
-#ifdef PCB_EV_NT_STORES
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-__device__ inline void store4(float *p, const float v[4]) { store_vec((f32x4 *)p, f32x4{v[0], v[1], v[2], v[3]}); }
-__device__ inline void store4(bf16_bits *p, const float v[4]) {
-    store_vec((u32x2 *)p, u32x2{(unsigned)to_bf16(v[0]) | ((unsigned)to_bf16(v[1]) << 16), (unsigned)to_bf16(v[2]) | ((unsigned)to_bf16(v[3]) << 16)});
-}
-
-// flat action of row e, or -1 when it is out of range; *legal: its bit
-__device__ inline int stored_action(const u64 *vml, const EvalGeom &q, const int *actions, int fmt, int e, bool *legal) {
-    const int HW = q.H * q.W;
-    int o, x, y;
-    if (fmt == PCBENV_ACTION_FLAT) {
-        const int a = actions[e];
-        if (a < 0 || a >= q.O * HW) { *legal = false; return -1; }
-        split_action(a, HW, q.W, &o, &x, &y);
-    } else {
-        o = actions[3 * (size_t)e]; x = actions[3 * (size_t)e + 1]; y = actions[3 * (size_t)e + 2];
-        if (o < 0 || o >= q.O || x < 0 || x >= q.H || y < 0 || y >= q.W) { *legal = false; return -1; }  // !PCB_ACTION_IN_RANGE, as it stood
-    }
-    *legal = PCB_LEGAL_BIT(vml, (o & 1) * q.H * q.WW, q.WW, x, y);
-    return PCB_FLATTEN_ACTION(o, x, y, HW, q.W);
-}
 
 template <typename T, bool VEC, int NW>
 __global__ __launch_bounds__(64 * NW) void k_evaluate_logits(EvalGeom q, EvalLogitsArgs g) {

@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, _move_lib, _priors_lib, _search_lib
+from . import _lib, _move_lib, _priors_lib, _search_lib, _train_lib
 from .config import EnvConfig, KIND_PIN, KIND_RECT, KIND_SPATIAL, KIND_SQUARE
 from .instances import Instance, InstanceStream, env_seed, pack_instances
 
@@ -152,7 +152,7 @@ class BatchedPlacementEnv:
             raise RuntimeError("BatchedPlacementEnv needs a GPU device (there is no CPU fallback)")
         # the device the handle lives on, index included: one named without an index is the current device, now and for good
         self.device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
-        self._L = _move_lib.bind(_priors_lib.bind(_search_lib.bind(_lib.load())))
+        self._L = _train_lib.bind(_move_lib.bind(_priors_lib.bind(_search_lib.bind(_lib.load()))))
         # per-environment spaces (the reference constructors' declarations); every tensor adds a leading batch dim
         from .spaces import action_space_for, observation_space_for
         self.action_space = self.single_action_space = action_space_for(cfg)
@@ -504,6 +504,62 @@ class BatchedPlacementEnv:
         [N].  N is arbitrary (a minibatch of stored steps).  `pcbenv.masked_categorical.evaluate` is the differentiable
         form."""
         return self.evaluate_logits_forward(logits, mask_bits, actions, None, errors)
+
+    # -- the AlphaZero policy loss: a masked policy against the visit counts of a searched move -------------------
+    def _visits_request(self, logits, mask_bits, visits, target_actions):
+        """The request both visit calls start from (include/pcbenv_train.h), its four inputs checked: logits [N, A]
+        float32 or bfloat16, mask_bits int64 [N, 2, H, WW], visits int32 [N, C], target_actions int32 [N, C, 3] or
+        [N, C] (flat) -> (N, request)."""
+        cfg = self.cfg
+        dtype = _logits_dtype(logits)
+        N = logits.shape[0] if logits.dim() == 2 else "N"
+        Cn = visits.shape[1] if isinstance(visits, torch.Tensor) and visits.dim() == 2 else "C"
+        check_tensor(self.device, "logits", logits, LOGITS_DTYPES, (N, cfg.num_orientations * cfg.height * cfg.width))
+        check_tensor(self.device, "mask_bits", mask_bits, torch.int64, (N, 2, cfg.height, (cfg.width + 63) // 64))
+        check_tensor(self.device, "visits", visits, torch.int32, (N, Cn))
+        flat = isinstance(target_actions, torch.Tensor) and target_actions.dim() == 2
+        check_tensor(self.device, "target_actions", target_actions, torch.int32, (N, Cn) if flat else (N, Cn, 3))
+        R = _train_lib.PcbenvVisitsRequest
+        req = R(struct_size=C.sizeof(R), logits_dtype=dtype, action_format=_lib.ACTION_FLAT if flat else _lib.ACTION_TUPLE, num_targets=Cn,
+                num_rows=N, reserved=0, logits=logits.data_ptr(), mask_bits=mask_bits.data_ptr(), visits=visits.data_ptr(),
+                target_actions=target_actions.data_ptr(), stream=self._stream().value)
+        return N, req
+
+    def evaluate_visits_forward(self, logits, mask_bits, visits, target_actions, stats: Optional[torch.Tensor] = None,
+                                errors: Optional[torch.Tensor] = None, out: Optional[Sequence[torch.Tensor]] = None):
+        """`pcbenv_evaluate_visits`, one kernel launch: (cross_entropy, entropy) float32 [N] of the masked categorical of
+        `logits` [N, A] with the legal sets `mask_bits` [N, 2, H, WW] against the visit distribution of `visits` int32
+        [N, C] over `target_actions` int32 [N, C, 3] or [N, C] (flat) -- what `puct_move` CHOOSE wrote as child_visits /
+        child_actions.  stats: float32 [N, 4] the backward call needs, or None.  errors: int32 [1] the error bits are ORed
+        into (1: a legal NaN or +inf, 2: every legal logit -inf, 4: an entry with negative visits or a visited action
+        that is out of range or not legal), or None.  out: two float32 [N] tensors to write into."""
+        N, req = self._visits_request(logits, mask_bits, visits, target_actions)
+        if stats is not None:
+            check_tensor(self.device, "stats", stats, torch.float32, (N, 4))
+        if errors is not None:
+            check_tensor(self.device, "errors", errors, torch.int32, (1,))
+        cross_entropy, entropy = self._log_prob_entropy(N) if out is None else out
+        check_tensor(self.device, "out[0] (cross_entropy)", cross_entropy, torch.float32, (N,))
+        check_tensor(self.device, "out[1] (entropy)", entropy, torch.float32, (N,))
+        if N == 0:  # torch gives empty tensors a null pointer
+            return cross_entropy, entropy
+        req.cross_entropy, req.entropy, req.stats, req.errors_dev = cross_entropy.data_ptr(), entropy.data_ptr(), _ptr(stats), _ptr(errors)
+        _lib.check(self._L.pcbenv_evaluate_visits(self._h, C.byref(req)), self._h)
+        return cross_entropy, entropy
+
+    def evaluate_visits_backward(self, logits, mask_bits, visits, target_actions, stats, grad_cross_entropy, grad_entropy,
+                                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`pcbenv_evaluate_visits_backward`, one kernel launch: the gradient with respect to `logits`, every element
+        written once (into `out`, or a fresh `torch.empty_like(logits)`).  stats: what the forward call wrote for these
+        rows.  grad_cross_entropy / grad_entropy: float32 [N] or None (zero)."""
+        N, req = self._visits_request(logits, mask_bits, visits, target_actions)
+        out = self._check_gradient_args(logits, out, (("stats", stats, (N, 4)), ("grad_cross_entropy", grad_cross_entropy, (N,)),
+                                                      ("grad_entropy", grad_entropy, (N,))))
+        if N == 0:
+            return out
+        req.stats, req.grad_cross_entropy, req.grad_entropy, req.grad_logits = _ptr(stats), _ptr(grad_cross_entropy), _ptr(grad_entropy), out.data_ptr()
+        _lib.check(self._L.pcbenv_evaluate_visits_backward(self._h, C.byref(req)), self._h)
+        return out
 
     # -- factorised policies: one action coordinate at a time ---------------------------------------------------
     def _axis_stage(self, axis, given):

@@ -1,5 +1,5 @@
 """Receding-horizon Monte-Carlo lookahead with pcbenv.search.best_of_k against the plain uniform-random policy, c3.
-python tools/search_demo.py [--roots 256] [--k 16] [--playouts | --tree [--device-tree] [--policy] | --puct [--device-priors] [--reuse]]
+python tools/search_demo.py [--roots 256] [--k 16] [--playouts | --tree [--device-tree] [--policy] | --puct [--device-priors] [--reuse] [--train N [--moves M] [--torch-loss]]]
 
 Both play the same instances (one episode per root environment).  The search forks every root k times into a planner
 batch (one device-side gather), plays every child to its end with the on-device sampler, and applies the best child's
@@ -17,7 +17,11 @@ expanded with the 16 most probable legal actions of pcbenv.search.network_evalua
 scored by one uniform rollout from it; the most-visited first action is applied.  --puct --reuse: the same search through
 pcbenv.search.puct_selfplay -- the tree stays on the device from move to move: pcbenv_puct_move picks the most-visited
 action and makes its subtree the next move's tree, so the k iterations of a move add to the visits already spent below it;
-the line then also reports the mean visits a move's root started with."""
+the line then also reports the mean visits a move's root started with.  --puct --train N (a spatial configuration: --config
+c4): N rounds of pcbenv.alphazero.AlphaZeroTrainer -- collect() plays --moves moves of every root with puct_selfplay, k
+iterations each, pcbenv/policy.py's model behind network_evaluator(priors="device"); update() trains the model on the visit
+counts with pcbenv_evaluate_visits (--torch-loss: the torch chain instead) -- and one line per round: the mean final reward
+of the episodes that ended in the round and the mean cross entropy of the update."""
 import argparse
 import json
 import os
@@ -47,6 +51,40 @@ def final_rewards(env, act, T):
     return final
 
 
+def train(a, cfg):
+    """--puct --train N: one JSON line per collect/update round."""
+    from pcbenv.alphazero import AlphaZeroConfig, AlphaZeroTrainer
+    from pcbenv.policy import SpatialPolicy
+    moves = a.moves or cfg.max_num_components
+    episodes = -(-a.train * moves // cfg.max_num_components) + 1  # per root: one instance record each
+    root = BatchedPlacementEnv(cfg, a.roots, queue_depth=episodes, run_seed=11, auto_reset=True)
+    root.generate_instances()
+    root.reset()
+    planner = BatchedPlacementEnv(cfg, a.roots, queue_depth=1, run_seed=11)
+    planner.generate_instances()
+    planner.reset()
+    torch.manual_seed(0)
+    trainer = AlphaZeroTrainer(root, planner, SpatialPolicy(cfg).to(root.device),
+                               AlphaZeroConfig(moves=moves, iterations=a.k, max_children=16, capacity=1 + moves * a.k * 16, device_loss=not a.torch_loss))
+    for it in range(a.train):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        batch = trainer.collect()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        stats = trainer.update(batch)
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        over = batch["done"].bool()
+        print(json.dumps({"round": it, "episodes_ended": int(over.sum()),
+                          "mean_final_reward": float(batch["reward"][over].mean()) if bool(over.any()) else None,
+                          "mean_cross_entropy": round(stats["policy"], 4), "value_loss": round(stats["value"], 4),
+                          "policy_entropy": round(stats["entropy"], 4), "tree_errors": int(batch["errors"]),
+                          "collect_s": round(t1 - t0, 3), "update_s": round(t2 - t1, 3)}), flush=True)
+    root.close()
+    planner.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--roots", type=int, default=256)
@@ -59,7 +97,12 @@ def main():
     ap.add_argument("--puct", action="store_true", help="search with puct_search_device, k iterations per move, network_evaluator with constant logits")
     ap.add_argument("--device-priors", action="store_true", help="with --puct: the candidates from pcbenv_top_priors (network_evaluator(priors=\"device\"))")
     ap.add_argument("--reuse", action="store_true", help="with --puct: puct_selfplay, the subtree of the move played is kept (pcbenv_puct_move)")
+    ap.add_argument("--train", type=int, default=0, metavar="N", help="with --puct: N collect/update rounds of pcbenv.alphazero.AlphaZeroTrainer")
+    ap.add_argument("--moves", type=int, default=0, help="with --train: moves of every root per round (default: one episode)")
+    ap.add_argument("--torch-loss", action="store_true", help="with --train: the policy loss through the torch chain (device_loss off)")
     a = ap.parse_args()
+    if a.train and not a.puct:
+        ap.error("--train goes with --puct")
     if a.device_priors and not a.puct:
         ap.error("--device-priors goes with --puct")
     if a.reuse and not a.puct:
@@ -74,6 +117,10 @@ def main():
     if a.policy and cfg.kind != KIND_SPATIAL:
         ap.error("--policy needs a spatial configuration, the one pcbenv/policy.py's model reads (--config c4)")
     P, k, T = a.roots, a.k, cfg.max_num_components
+    if a.train:
+        if cfg.kind != KIND_SPATIAL:
+            ap.error("--train needs a spatial configuration, the one pcbenv/policy.py's model reads (--config c4)")
+        return train(a, cfg)
 
     def make(n, seed):
         e = BatchedPlacementEnv(cfg, n, queue_depth=1, run_seed=seed)

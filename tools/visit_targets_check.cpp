@@ -1,0 +1,80 @@
+// visit_targets_check.cpp -- csrc/pcb_visit_targets.h on the CPU: reduces the (visits, actions) entries of rows it is
+// handed through pcb_visits::reduce_row, build_slots, slot_of and pi_of and writes what the kernels would use
+// (tests/test_visit_targets_model.py compares it with tests/visits_contract.py:target_rows, the float64 restatement of
+// include/pcbenv_train.h).  The legality callback here is this program's own, built from csrc/pcb_transition.h
+// (unflatten_action, action_in_range, legal_bit); the kernels' callback is stored_action of csrc/pcb_policy_common.h, which
+// only the GPU tests run (the out-of-range and illegal rows of tests/test_evaluate_visits_gpu.py).  A stand-alone program:
+//   g++ -std=c++17 -O1 -g -Wall -Wextra -Werror -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all
+//       -Iinclude -Irl-environment-for-component-placement_amd/csrc -o visit_targets_check tools/visit_targets_check.cpp
+//
+// stdin and stdout are streams of little-endian int64 words (a float32 travels as its bits, zero-extended).
+//   in:   O H W fmt C rows | per row: the bit rows [2 H WW] visits[C] actions[C 3] (fmt 0, tuple) or [C] (fmt 1, flat)
+//   out:  per row: error bits | T | index[C] | kept[C] (the visits of the valid entries) | pi[C] (the weight of the logit entry c
+//         names, every entry that names it counted; 0 where index < 0)
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <vector>
+
+#include "pcb_transition.h"
+#include "pcb_visit_targets.h"
+
+namespace {
+
+bool read_words(int64_t *dst, size_t n) { return fread(dst, sizeof(int64_t), n, stdin) == n; }
+int64_t float_bits(float v) { uint32_t u; memcpy(&u, &v, 4); return (int64_t)u; }
+
+}  // namespace
+
+int main() {
+    int64_t head[6];
+    if (!read_words(head, 6)) { fprintf(stderr, "no header\n"); return 2; }
+    const int O = (int)head[0], H = (int)head[1], W = (int)head[2], fmt = (int)head[3], C = (int)head[4];
+    const int64_t rows = head[5];
+    if (O < 1 || O > 4 || H < 1 || W < 1 || W > 128 || (fmt != PCBENV_ACTION_TUPLE && fmt != PCBENV_ACTION_FLAT) || C < 1 || C > pcb_visits::MAX_TARGETS || rows < 0) {
+        fprintf(stderr, "bad header\n");
+        return 2;
+    }
+    const int WW = (W + 63) / 64, HW = H * W, per_action = fmt == PCBENV_ACTION_FLAT ? 1 : 3;
+    std::vector<int64_t> in((size_t)2 * H * WW + (size_t)C + (size_t)C * per_action), out;
+    std::vector<u64> vm((size_t)2 * H * WW);
+    std::vector<int32_t> visits(C), actions((size_t)C * per_action);
+    std::vector<int> index(C), kept(C);
+    const int S = O * H * WW;
+    std::vector<uint64_t> map(S);
+    std::vector<unsigned char> before(S);
+    int64_t sums[pcb_visits::MAX_TARGETS];
+    for (int64_t r = 0; r < rows; r++) {
+        if (!read_words(in.data(), in.size())) { fprintf(stderr, "row %lld: input ends early\n", (long long)r); return 2; }
+        size_t at = 0;
+        for (auto &w : vm) w = (u64)in[at++];
+        for (auto &v : visits) v = (int32_t)in[at++];
+        for (auto &a : actions) a = (int32_t)in[at++];
+        auto legal_action = [&](int c) {
+            int o, x, y;
+            if (fmt == PCBENV_ACTION_FLAT) unflatten_action(actions[c], O, HW, W, &o, &x, &y);
+            else { o = actions[3 * (size_t)c]; x = actions[3 * (size_t)c + 1]; y = actions[3 * (size_t)c + 2]; }
+            if (!action_in_range(o, x, y, O, H, W) || !legal_bit(vm.data(), H, WW, o, x, y)) return -1;
+            return flatten_action(o, x, y, HW, W);
+        };
+        int64_t T = 0;
+        const unsigned bits = pcb_visits::reduce_row(visits.data(), C, legal_action, index.data(), kept.data(), &T);
+        out.push_back((int64_t)bits);
+        out.push_back(T);
+        for (int c = 0; c < C; c++) out.push_back((int64_t)index[c]);
+        for (int c = 0; c < C; c++) out.push_back((int64_t)kept[c]);
+        pcb_visits::build_slots(index.data(), kept.data(), C, W, WW, S, map.data(), before.data(), sums);
+        for (int c = 0; c < C; c++) {  // as a gradient element finds it: from the map alone
+            float pi = 0.f;
+            if (index[c] >= 0) {
+                int word, bit;
+                pcb_visits::map_place(index[c], W, WW, &word, &bit);
+                pi = pcb_visits::pi_of(sums[pcb_visits::slot_of(before[word], map[word], bit)], T);
+            }
+            out.push_back(float_bits(pi));
+        }
+    }
+    if (fwrite(out.data(), sizeof(int64_t), out.size(), stdout) != out.size()) { fprintf(stderr, "short write\n"); return 2; }
+    return 0;
+}
