@@ -63,9 +63,9 @@ def program():
     return exe
 
 
-def record(P, T, iterations, c_puct, max_children, evaluate, step_index=0, capacity=None, cfg=None):
+def record(P, T, iterations, c_puct, max_children, evaluate, step_index=0, capacity=None, cfg=None, tree=None):
     """puct_search on the CPU -> (its result, [(paths, path_len, value float64 [P], leaf_terminal uint8 [P], cand_count int32
-    [P], cand_actions int32 [P, K, 3], cand_prior float32 [P, K])])."""
+    [P], cand_actions int32 [P, K, 3], cand_prior float32 [P, K])]).  tree: the search goes on in that tree."""
     calls = []
 
     def recording(paths, path_len, s):
@@ -75,7 +75,7 @@ def record(P, T, iterations, c_puct, max_children, evaluate, step_index=0, capac
                       ev.cand_actions.to(torch.int32).numpy().copy(), ev.cand_prior.to(torch.float32).numpy().copy()))
         return ev
     root = SimpleNamespace(num_envs=P, device="cpu", cfg=cfg)
-    ps = puct_search(root, iterations, step_index, recording, c_puct=c_puct, max_children=max_children, max_steps=T, capacity=capacity)
+    ps = puct_search(root, iterations, step_index, recording, c_puct=c_puct, max_children=max_children, max_steps=T, capacity=capacity, tree=tree)
     return ps, calls
 
 

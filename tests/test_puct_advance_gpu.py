@@ -36,17 +36,19 @@ class Guarded:
 
     def __init__(self, P, N, T, K, device):
         shp = dict(pc.shapes(P, N, T), value=(P,), leaf_terminal=(P,), cand_count=(P,), cand_actions=(P, K, 3), cand_prior=(P, K), errors_dev=(1,))
-        self.back, self.t, self.meta = {}, {}, {}
+        self.device, self.back, self.t, self.meta = device, {}, {}, {}
         for name, shape in shp.items():
-            dtype = DTYPES.get(name, torch.int32)
-            n = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
-            buf = torch.full((GUARD + n + GUARD,), SENTINEL, dtype=torch.uint8, device=device)
-            self.back[name] = buf
-            self.t[name] = buf[GUARD:GUARD + n].view(dtype).view(shape)
-            self.meta[name] = (self.t[name].cpu().numpy().dtype, tuple(shape))
-            if dtype == torch.int32:
-                self.t[name].fill_(pc.FILL)
+            self.add(name, shape, DTYPES.get(name, torch.int32))
         self.t["errors_dev"].zero_()
+
+    def add(self, name, shape, dtype):
+        n = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
+        buf = torch.full((GUARD + n + GUARD,), SENTINEL, dtype=torch.uint8, device=self.device)
+        self.back[name] = buf
+        self.t[name] = buf[GUARD:GUARD + n].view(dtype).view(shape)
+        self.meta[name] = (self.t[name].cpu().numpy().dtype, tuple(shape))
+        if dtype == torch.int32:
+            self.t[name].fill_(pc.FILL)
 
     def snapshot(self):
         return {name: buf.cpu().numpy().copy() for name, buf in self.back.items()}
@@ -76,6 +78,45 @@ def handle():
     env.close()
 
 
+def advance_and_compare(handle, req, g, i, call, want, before, errors_dev=True):
+    """Call i through puct_advance into the guarded tensors of g; want: the model's state after it; before: the snapshot after
+    the call before.  -> (the snapshot the call started from, the one it left)."""
+    inputs = {}
+    for name, at, value in call.get("pokes", ()):  # the damage a caller does between two calls
+        g.t[name].view(-1)[at] = value
+    if call.get("pokes") and not call["phases"] & pc.ABSORB:
+        before = g.snapshot()
+    if call["phases"] & pc.ABSORB:
+        for name, a in zip(pc.INPUTS, call["evaluation"]):
+            g.t[name].copy_(torch.from_numpy(np.ascontiguousarray(a)))
+            inputs[name] = g.t[name]
+        before = g.snapshot()
+    handle.puct_advance(req, call["phases"], **inputs)
+    after = g.snapshot()
+    for name in after:  # the guards, and what the call only reads
+        assert np.array_equal(after[name][:GUARD], before[name][:GUARD]) and np.array_equal(after[name][-GUARD:], before[name][-GUARD:]), (i, name)
+        if name in pc.INPUTS:
+            assert np.array_equal(after[name], before[name]), (i, name)
+    # every tensor against the model: that includes the paths rows >= path_len, which hold what they held before (the
+    # model's tensors start with the same fill)
+    for f in pc.STATE_FIELDS:
+        model = want[f]
+        got = g.inside(after, f)
+        if f in pc.FLOATS:
+            assert pc.same_bits(got, model), (i, f)
+        else:
+            assert np.array_equal(got.astype(np.int64), model), (i, f)
+    assert int(g.inside(after, "errors_dev")[0]) == (want["errors"] if errors_dev else 0), i
+    untouched = ()
+    if call["phases"] == pc.SELECT:
+        untouched = pc.TREE_FIELDS
+    elif call["phases"] in (pc.ABSORB, pc.INIT):
+        untouched = ("selected", "path_len", "paths")
+    for f in untouched:  # a phase that was not asked for wrote nothing
+        assert np.array_equal(after[f], before[f]), (i, f)
+    return before, after
+
+
 def assert_equals_the_model_after_every_call(handle, case, errors_dev=True):
     """case.seq call by call through puct_advance into guarded tensors; case.states: the model's state after each call.
     errors_dev=False: the request names no error word (the guarded one must keep its zero)."""
@@ -85,40 +126,7 @@ def assert_equals_the_model_after_every_call(handle, case, errors_dev=True):
     assert (req.errors_dev is not None) == errors_dev and req.max_children == C and req.capacity == case.N and req.max_steps == T
     before = g.snapshot()
     for i, (call, want) in enumerate(zip(case.seq, case.states)):
-        inputs = {}
-        for name, at, value in call.get("pokes", ()):  # the damage a caller does between two calls
-            g.t[name].view(-1)[at] = value
-        if call.get("pokes") and not call["phases"] & pc.ABSORB:
-            before = g.snapshot()
-        if call["phases"] & pc.ABSORB:
-            for name, a in zip(pc.INPUTS, call["evaluation"]):
-                g.t[name].copy_(torch.from_numpy(np.ascontiguousarray(a)))
-                inputs[name] = g.t[name]
-            before = g.snapshot()
-        handle.puct_advance(req, call["phases"], **inputs)
-        after = g.snapshot()
-        for name in after:  # the guards, and what the call only reads
-            assert np.array_equal(after[name][:GUARD], before[name][:GUARD]) and np.array_equal(after[name][-GUARD:], before[name][-GUARD:]), (i, name)
-            if name in pc.INPUTS:
-                assert np.array_equal(after[name], before[name]), (i, name)
-        # every tensor against the model: that includes the paths rows >= path_len, which hold what they held before (the
-        # model's tensors start with the same fill)
-        for f in pc.STATE_FIELDS:
-            model = want[f]
-            got = g.inside(after, f)
-            if f in pc.FLOATS:
-                assert pc.same_bits(got, model), (i, f)
-            else:
-                assert np.array_equal(got.astype(np.int64), model), (i, f)
-        assert int(g.inside(after, "errors_dev")[0]) == (want["errors"] if errors_dev else 0), i
-        untouched = ()
-        if call["phases"] == pc.SELECT:
-            untouched = pc.TREE_FIELDS
-        elif call["phases"] in (pc.ABSORB, pc.INIT):
-            untouched = ("selected", "path_len", "paths")
-        for f in untouched:  # a phase that was not asked for wrote nothing
-            assert np.array_equal(after[f], before[f]), (i, f)
-        before = after
+        _, before = advance_and_compare(handle, req, g, i, call, want, before, errors_dev)
 
 
 @pytest.mark.parametrize("what", list(REPLAYS))

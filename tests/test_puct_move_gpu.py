@@ -71,42 +71,49 @@ def handle():
     env.close()
 
 
+def move_and_compare(handle, req, g, i, call, want, errors_dev=True, first_root=0):
+    """Call i through puct_move into the guarded tensors of g; want: the model's state after it.  -> (the snapshot the call
+    started from, the one it left)."""
+    for name, at, value in call.get("pokes", ()):  # the damage a caller does before the call
+        g.t[name].view(-1)[at] = value
+    if call.get("move_slot") is not None:
+        g.t["move_slot"].copy_(torch.from_numpy(call["move_slot"]))
+    if call["reset"] is not None:
+        g.t["reset"].copy_(torch.from_numpy(call["reset"]))
+    g.t["errors_dev"].zero_()  # the model reports the bits of each call
+    before = g.snapshot()
+    handle.puct_move(req, call["phases"], mode=call["mode"], seed=call["seed"], step_index=call["step_index"],
+                     reset=g.t["reset"] if call["reset"] is not None else None)
+    assert req.first_root == handle.first_env_index == first_root
+    after = g.snapshot()
+    for name in after:  # the guards, and what the call only reads
+        assert np.array_equal(after[name][:GUARD], before[name][:GUARD]) and np.array_equal(after[name][-GUARD:], before[name][-GUARD:]), (i, name)
+        if name in INPUTS:
+            assert np.array_equal(after[name], before[name]), (i, name)
+    for f in mc.STATE_FIELDS:
+        got = g.inside(after, f)
+        if f in mc.FLOATS:
+            assert pc.same_bits(got, want[f]), (i, f)
+        else:
+            assert np.array_equal(got.astype(np.int64), want[f]), (i, f)
+    assert int(g.inside(after, "errors_dev")[0]) == (want["errors"] if errors_dev else 0), i
+    untouched = ()
+    if call["phases"] == mc.CHOOSE:
+        untouched = mc.TREE_FIELDS + ("remap",)
+    elif call["phases"] == mc.REROOT:
+        untouched = ("move_slot", "move_action", "child_visits", "child_actions", "root_value")
+    for f in untouched:  # a phase that was not asked for wrote nothing
+        assert np.array_equal(after[f], before[f]), (i, f)
+    return before, after
+
+
 def assert_equals_the_model_after_every_call(handle, tree, C, seq, states, errors_dev=True):
     """seq call by call through puct_move into guarded tensors; states: the model's state after each call."""
     g = Guarded(tree, C, handle.device)
     req = handle.puct_move_request(g.t if errors_dev else {n: t for n, t in g.t.items() if n != "errors_dev"}, C)
     assert (req.errors_dev is not None) == errors_dev and req.max_children == C and req.capacity == tree["parent"].shape[1]
     for i, (call, want) in enumerate(zip(seq, states)):
-        for name, at, value in call["pokes"]:  # the damage a caller does before the call
-            g.t[name].view(-1)[at] = value
-        if call["move_slot"] is not None:
-            g.t["move_slot"].copy_(torch.from_numpy(call["move_slot"]))
-        if call["reset"] is not None:
-            g.t["reset"].copy_(torch.from_numpy(call["reset"]))
-        g.t["errors_dev"].zero_()  # the model reports the bits of each call
-        before = g.snapshot()
-        handle.puct_move(req, call["phases"], mode=call["mode"], seed=call["seed"], step_index=call["step_index"],
-                         reset=g.t["reset"] if call["reset"] is not None else None)
-        assert req.first_root == handle.first_env_index == 0
-        after = g.snapshot()
-        for name in after:  # the guards, and what the call only reads
-            assert np.array_equal(after[name][:GUARD], before[name][:GUARD]) and np.array_equal(after[name][-GUARD:], before[name][-GUARD:]), (i, name)
-            if name in INPUTS:
-                assert np.array_equal(after[name], before[name]), (i, name)
-        for f in mc.STATE_FIELDS:
-            got = g.inside(after, f)
-            if f in mc.FLOATS:
-                assert pc.same_bits(got, want[f]), (i, f)
-            else:
-                assert np.array_equal(got.astype(np.int64), want[f]), (i, f)
-        assert int(g.inside(after, "errors_dev")[0]) == (want["errors"] if errors_dev else 0), i
-        untouched = ()
-        if call["phases"] == mc.CHOOSE:
-            untouched = mc.TREE_FIELDS + ("remap",)
-        elif call["phases"] == mc.REROOT:
-            untouched = ("move_slot", "move_action", "child_visits", "child_actions", "root_value")
-        for f in untouched:  # a phase that was not asked for wrote nothing
-            assert np.array_equal(after[f], before[f]), (i, f)
+        move_and_compare(handle, req, g, i, call, want, errors_dev)
 
 
 def _first_root_0(seq):
@@ -115,9 +122,11 @@ def _first_root_0(seq):
 
 
 @pytest.mark.parametrize("way", mc.WAYS)
-@pytest.mark.parametrize("name", list(mc.SHAPES))
+@pytest.mark.parametrize("name", mc.ALL_SHAPES)
 def test_the_kernel_alone_equals_the_model_after_every_call(handle, name, way):
     mc.check_cases()
+    if name in mc.CONSTRUCTED:  # with the checks, made on the CPU, that the shape reaches the spans and chunks it is there for
+        mc.check_constructed()
     c = mc.case(name)
     seq = _first_root_0(mc.ways(c)[way])
     assert_equals_the_model_after_every_call(handle, c.tree, c.C, seq, mc.run(c.tree, c.C, seq))
@@ -146,6 +155,21 @@ def test_a_damaged_tree_is_handled_as_the_model_handles_it(handle, name):
     for f, at, value in d.pokes:
         assert value in allowed[f], (f, value)
     assert int(d.move_slot[d.p]) in (d.m, c.N, -2)
+    seq = _first_root_0(d.seq)
+    assert_equals_the_model_after_every_call(handle, c.tree, c.C, seq, d.states)
+    assert_equals_the_model_after_every_call(handle, c.tree, c.C, seq, d.states, errors_dev=False)
+
+
+@pytest.mark.parametrize("shape, name", mc.DEEP_CASES)
+def test_a_tree_damaged_in_its_third_span_is_handled_as_the_model_handles_it(handle, shape, name):
+    """The same bounds, where the early exit follows two spans that have stored their ranks: a slot of the third span of a
+    long chain and of a C = 64 tree, in a root between two others, damaged by values next to the valid range."""
+    d = mc.damaged_deep(shape, name)
+    c = d.case
+    assert 0 < d.p < c.P - 1 and d.states[0]["errors"] == mc.ERR_TREE and (d.states[0]["remap"][d.p] == -1).all()
+    allowed = dict(parent=(d.s, c.N), first_child=(mc.DEEP[shape][4], d.n))
+    for f, at, value in d.pokes:
+        assert value in allowed[f], (f, value)
     seq = _first_root_0(d.seq)
     assert_equals_the_model_after_every_call(handle, c.tree, c.C, seq, d.states)
     assert_equals_the_model_after_every_call(handle, c.tree, c.C, seq, d.states, errors_dev=False)

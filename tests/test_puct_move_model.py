@@ -44,8 +44,23 @@ def test_the_cases_are_what_they_are_there_for():
     assert max(blocks) > 1 and any(c.P % 4 for c in cases)
 
 
+def test_the_constructed_shapes_are_what_they_are_there_for():
+    """The spans, chunks and chains of REROOT's three passes that each constructed shape reaches, counted from the trees and
+    the moves (puct_move_cases.coverage); and the old shapes' counts, which say why they do not do."""
+    cov = mc.check_constructed()
+    assert set(cov) == set(mc.CONSTRUCTED) and mc.ALL_SHAPES == tuple(mc.SHAPES) + tuple(mc.CONSTRUCTED)
+    old = [mc.coverage(mc.case(n)) for n in mc.SHAPES]
+    assert sum(len(v.below_kept) for v in old) < 64 and max(v.longest for v in old) < mc.LANES - 1 and max(max(v.num_nodes) for v in old) <= 2 * mc.SPAN
+    for name in mc.CONSTRUCTED:
+        c = mc.case(name)
+        for p in range(c.P):
+            _well_formed({f: c.tree[f][p] for f in mc.TREE_FIELDS}, c.C)
+            n = int(c.tree["num_nodes"][p])
+            assert set(c.tree["visits"][p, :n][c.tree["num_children"][p, :n] == 0]) <= {0, 1, 2, 3} and set(c.tree["prior"][p, 1:n]) <= set(pc.PRIORS)
+
+
 @pytest.mark.parametrize("way", mc.WAYS)
-@pytest.mark.parametrize("name", list(mc.SHAPES))
+@pytest.mark.parametrize("name", mc.ALL_SHAPES)
 def test_the_model_is_the_specification(name, way):
     c = mc.case(name)
     states = mc.modelled(name, way)
@@ -217,6 +232,31 @@ def test_a_damaged_tree_is_left_alone(name):
         assert pc.same_bits(st[f][p], before[f][p].astype(st[f].dtype)), f
     others = [q for q in range(c.P) if q != p]
     for f in mc.TREE_FIELDS + ("remap",):  # the neighbouring roots exact
+        assert pc.same_bits(np.take(st[f], others, 0), np.take(healthy[f], others, 0)), f
+
+
+@pytest.mark.parametrize("shape, name", mc.DEEP_CASES)
+def test_a_tree_damaged_in_its_third_span_is_left_alone(shape, name):
+    """The damage is found after two spans of ranks are in remap: ERR_TREE, remap all -1, the root and its neighbours as they were."""
+    d = mc.damaged_deep(shape, name)
+    c, p, st, healthy = d.case, d.p, d.states[0], d.healthy[0]
+    keep = mc.subtree(c.tree, p, d.m)
+    assert 0 < p < c.P - 1 and 2 * mc.SPAN <= d.s < 3 * mc.SPAN and 2 * mc.SPAN <= d.node < 3 * mc.SPAN and d.s in keep and d.node in keep
+    assert sum(s < 2 * mc.SPAN for s in keep) > 0 and c.tree["num_children"][p, d.node] > 0  # kept slots in the spans before: remap held ranks
+    assert healthy["errors"] == 0 and healthy["num_nodes"][p] == len(keep) and (healthy["remap"][p, keep] == np.arange(len(keep))).all()
+    before = {f: np.array(c.tree[f]) for f in mc.TREE_FIELDS}
+    for f, at, value in d.pokes:
+        before[f].reshape(-1)[at] = value
+    if name == "child_range_not_kept":
+        k, fc = int(c.tree["num_children"][p, d.node]), d.pokes[0][2]
+        assert 1 <= fc <= d.n - k and not set(range(fc, fc + k)) & set(keep)  # a range of the tree, none of it kept
+    assert st["errors"] == mc.ERR_TREE
+    assert (st["remap"][p] == -1).all()
+    for q in (p - 1, p, p + 1):  # untouched: what the caller wrote is still there
+        for f in mc.TREE_FIELDS:
+            assert pc.same_bits(st[f][q], before[f][q].astype(st[f].dtype)), (q, f)
+    others = [q for q in range(c.P) if q != p]
+    for f in mc.TREE_FIELDS + ("remap",):  # every other root as in the healthy call
         assert pc.same_bits(np.take(st[f], others, 0), np.take(healthy[f], others, 0)), f
 
 

@@ -1,0 +1,131 @@
+// puct_game_check.cpp -- csrc/pcb_puct.h and csrc/pcb_puct_move.h on the CPU, on ONE state: runs a sequence of
+// pcbenv_puct_advance and pcbenv_puct_move calls -- the searches and moves of a game whose tree is kept from move to move
+// -- through puct_init / puct_absorb / puct_select and move_choose / move_reroot, root by root, checks every selection
+// against the one pcbenv/search.py:puct_search made when the game was recorded, and writes the state after every call
+// (tests/test_puct_game_model.py compares it with puct_search(tree=), puct_choose and puct_reroot, the specification,
+// tests/test_puct_game_gpu.py with the kernels').  Nothing of either step is restated here.  A stand-alone program:
+//   g++ -std=c++17 -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -I rl-environment-for-component-placement_amd/csrc
+//
+// stdin and stdout are streams of little-endian int64 words (a float64 travels as its bits, a float32 as its bits in the
+// low half of a word).
+//   in:   P N C T K calls c_puct | per call: kind, then
+//           kind 0, pcbenv_puct_advance: phases check
+//             [ABSORB: value[P] leaf_terminal[P] cand_count[P] cand_actions[P K 3] cand_prior[P K]]
+//             [SELECT and check: path_len[P] paths[T P 3] as recorded]
+//           kind 1, pcbenv_puct_move: phases mode seed step_index first_root has_reset [has_reset: reset[P]]
+//         phases: the PHASE_ bits of csrc/pcb_tree.h, or those of csrc/pcb_puct_move.h.
+//   out:  per call: the error bits of that call | selected[P] path_len[P] paths[T P 3] | move_slot[P] move_action[P 3]
+//           child_visits[P C] child_actions[P C 3] root_value[P] remap[P N] | num_nodes[P] parent depth visits num_children
+//           first_child [P N] node_action[P N 3] prior value_sum value_max terminal [P N] reward_lo reward_hi [P]
+// Before the first call every int32 tensor holds -7, every float64 one -7.0 and terminal 0xf9 (what a test puts into the
+// device tensors the kernels must leave alone): the first call brings INIT.
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <vector>
+
+#include "pcb_puct_move.h"
+
+namespace {
+
+bool read_words(int64_t *dst, size_t n) { return fread(dst, sizeof(int64_t), n, stdin) == n; }
+int64_t read_word(bool *ok) { int64_t v = 0; *ok = *ok && read_words(&v, 1); return v; }
+double as_double(int64_t bits) { double d; memcpy(&d, &bits, 8); return d; }
+float as_float(int64_t bits) { const uint32_t b = (uint32_t)bits; float f; memcpy(&f, &b, 4); return f; }
+int64_t as_bits(double d) { int64_t b; memcpy(&b, &d, 8); return b; }
+
+std::vector<int64_t> out;
+template <class V> void put(const V &v) { for (auto x : v) out.push_back((int64_t)x); }
+void put_bits(const std::vector<double> &v) { for (double x : v) out.push_back(as_bits(x)); }
+
+bool read_ints(std::vector<int> &dst) {
+    std::vector<int64_t> w(dst.size());
+    if (!read_words(w.data(), w.size())) return false;
+    for (size_t i = 0; i < w.size(); i++) dst[i] = (int)w[i];
+    return true;
+}
+
+}  // namespace
+
+int main() {
+    using namespace pcb_puct;
+    using namespace pcb_move;
+    bool ok = true;
+    const int P = (int)read_word(&ok), N = (int)read_word(&ok), C = (int)read_word(&ok), T = (int)read_word(&ok), K = (int)read_word(&ok),
+              calls = (int)read_word(&ok);
+    const double c_puct = as_double(read_word(&ok));
+    if (!ok || P < 0 || N < 1 || C < 1 || C > pcb_tree::MAX_CHILDREN || T < 1 || K < 1 || calls < 0) { fprintf(stderr, "bad header\n"); return 2; }
+    const size_t PN = (size_t)P * N, TP3 = (size_t)T * P * 3, PK = (size_t)P * K, PC = (size_t)P * C;
+    const int FILL = -7;
+    std::vector<int> num_nodes(P, FILL), parent(PN, FILL), depth(PN, FILL), visits(PN, FILL), num_children(PN, FILL), first_child(PN, FILL),
+        node_action(PN * 3, FILL), selected(P, FILL), path_len(P, FILL), paths(TP3, FILL);
+    std::vector<double> prior(PN, -7.0), value_sum(PN, -7.0), value_max(PN, -7.0), lo(P, -7.0), hi(P, -7.0);
+    std::vector<uint8_t> terminal(PN, 0xf9);
+    std::vector<int> move_slot(P, FILL), move_action((size_t)P * 3, FILL), child_visits(PC, FILL), child_actions(PC * 3, FILL), remap(PN, FILL), reset(P, 0);
+    std::vector<double> root_value(P, -7.0);
+    std::vector<double> value(P);
+    std::vector<int> leaf_terminal(P), cand_count(P), cand_actions(PK * 3), want_len(P), want_paths(TP3);
+    std::vector<float> cand_prior(PK);
+    for (int call = 0; call < calls; call++) {
+        const int kind = (int)read_word(&ok), phases = (int)read_word(&ok);
+        unsigned errors = 0u;
+        int check = 0;
+        if (!ok || (kind != 0 && kind != 1)) { fprintf(stderr, "call %d: bad kind\n", call); return 2; }
+        if (kind == 0) {
+            check = (int)read_word(&ok);
+            if (!ok || phases <= 0 || phases > 7 || ((phases & PHASE_INIT) && (phases & PHASE_ABSORB))) { fprintf(stderr, "call %d: bad phases\n", call); return 2; }
+            if (phases & PHASE_ABSORB) {
+                for (double &x : value) x = as_double(read_word(&ok));
+                ok = ok && read_ints(leaf_terminal) && read_ints(cand_count) && read_ints(cand_actions);
+                for (float &x : cand_prior) x = as_float(read_word(&ok));
+            }
+            if ((phases & PHASE_SELECT) && check) ok = ok && read_ints(want_len) && read_ints(want_paths);
+            if (!ok) { fprintf(stderr, "call %d: input ends early\n", call); return 2; }
+        } else {
+            if (!ok || phases < 1 || phases > 3) { fprintf(stderr, "call %d: bad phases\n", call); return 2; }
+        }
+        int mode = 0, first_root = 0, has_reset = 0;
+        uint64_t seed = 0, step_index = 0;
+        if (kind == 1) {
+            mode = (int)read_word(&ok);
+            seed = (uint64_t)read_word(&ok);
+            step_index = (uint64_t)read_word(&ok);
+            first_root = (int)read_word(&ok);
+            has_reset = (int)read_word(&ok);
+            if (has_reset) ok = ok && read_ints(reset);
+            if (!ok || (mode != MODE_GREEDY && mode != MODE_PROPORTIONAL)) { fprintf(stderr, "call %d: bad mode, or the input ends early\n", call); return 2; }
+        }
+        for (int p = 0; p < P; p++) {
+            const size_t s = (size_t)p * N;
+            const Root r{N, C, T, P, p, &num_nodes[p], &parent[s], &depth[s], &visits[s], &num_children[s], &first_child[s], &node_action[3 * s],
+                         &prior[s], &value_sum[s], &value_max[s], &terminal[s], &lo[p], &hi[p]};
+            if (kind == 1) {
+                if (phases & PHASE_CHOOSE)
+                    errors |= move_choose(r, mode, seed, step_index, first_root, &child_visits[(size_t)p * C], &child_actions[(size_t)p * C * 3], &root_value[p],
+                                          &move_slot[p], &move_action[(size_t)p * 3]);
+                if (phases & PHASE_REROOT) errors |= move_reroot(r, move_slot[p], has_reset ? reset[p] : 0, &remap[s]);
+                continue;
+            }
+            if (phases & PHASE_INIT) puct_init(r);
+            if (phases & PHASE_ABSORB)
+                errors |= puct_absorb(r, selected[p], value[p], leaf_terminal[p], cand_count[p], K, &cand_actions[(size_t)p * K * 3], &cand_prior[(size_t)p * K]);
+            if (phases & PHASE_SELECT) {
+                errors |= puct_select(r, c_puct, paths.data(), &path_len[p], &selected[p]);
+                if (path_len[p] != r.depth[selected[p]]) { fprintf(stderr, "call %d root %d: path_len %d, depth of the selected node %d\n", call, p, path_len[p], r.depth[selected[p]]); return 1; }
+                if (!check) continue;
+                if (path_len[p] != want_len[p]) { fprintf(stderr, "call %d root %d: path_len %d, recorded %d\n", call, p, path_len[p], want_len[p]); return 1; }
+                for (int d = 0; d < path_len[p]; d++)
+                    for (int k = 0; k < 3; k++)
+                        if (paths[step_major(d, P, p, k)] != want_paths[step_major(d, P, p, k)]) { fprintf(stderr, "call %d root %d: path row %d differs from the recorded one\n", call, p, d); return 1; }
+            }
+        }
+        out.push_back((int64_t)errors);
+        put(selected); put(path_len); put(paths);
+        put(move_slot); put(move_action); put(child_visits); put(child_actions); put_bits(root_value); put(remap);
+        put(num_nodes); put(parent); put(depth); put(visits); put(num_children); put(first_child); put(node_action);
+        put_bits(prior); put_bits(value_sum); put_bits(value_max); put(terminal); put_bits(lo); put_bits(hi);
+    }
+    if (fwrite(out.data(), sizeof(int64_t), out.size(), stdout) != out.size()) { fprintf(stderr, "short write\n"); return 2; }
+    return 0;
+}
