@@ -26,7 +26,8 @@ class AlphaZeroConfig:
     iterations: int = 16      # search iterations per move
     max_children: int = 16    # C: candidates per node, and entries of a policy target
     c_puct: float = 1.0
-    capacity: Optional[int] = None  # node slots per root (puct_selfplay's default: 1 + 2 * iterations * max_children)
+    capacity: Optional[int] = None  # node slots per root (puct_selfplay's default: 1 + 2 * iterations * leaves * max_children)
+    leaves: int = 1           # L: leaves selected per root and iteration; the planner then has P * L environments
     mode: int = MOVE_PROPORTIONAL  # how the move is picked from the root's visits (MOVE_GREEDY: the most visited)
     epochs: int = 1
     minibatches: int = 1
@@ -63,7 +64,7 @@ def alphazero_loss(ce, entropy, value, z, weight, cfg: AlphaZeroConfig):
 
 class AlphaZeroTrainer:
     """root: the self-play environments (auto_reset=True: an episode that ends is followed by the next).  planner: as many
-    environments of the root's definition with auto_reset=False, the root's run_seed and first_env_index 0
+    environments (cfg.leaves times as many with leaf-parallel search) of the root's definition with auto_reset=False, the root's run_seed and first_env_index 0
     (`network_evaluator`).  policy: `(obs, mask=False) -> (raw logits [B, A], value [B])`, e.g. pcbenv/policy.py's."""
 
     def __init__(self, root, planner, policy, cfg: AlphaZeroConfig = AlphaZeroConfig(),
@@ -79,7 +80,8 @@ class AlphaZeroTrainer:
             with torch.no_grad():
                 logits, cache["value"] = self.policy(obs, mask=False)
             return logits.contiguous()
-        self.evaluate = network_evaluator(root, planner, logits_fn, lambda obs: cache["value"], max_children=cfg.max_children, priors="device")
+        self.evaluate = network_evaluator(root, planner, logits_fn, lambda obs: cache["value"], max_children=cfg.max_children, priors="device",
+                                          leaves=cfg.leaves)
 
     @torch.no_grad()
     def collect(self) -> Dict[str, torch.Tensor]:
@@ -99,7 +101,7 @@ class AlphaZeroTrainer:
         self.policy.eval()
         sp = puct_selfplay(root, self.evaluate, M, self.cfg.iterations, step_index=self.step_index, c_puct=self.cfg.c_puct,
                            max_children=self.cfg.max_children, capacity=self.cfg.capacity, mode=self.cfg.mode,
-                           on_move=lambda j, tree: keep_root(j + 1) if j + 1 < M else None)
+                           on_move=lambda j, tree: keep_root(j + 1) if j + 1 < M else None, leaves=self.cfg.leaves)
         from .batched_env import default_max_steps
         self.step_index += M * self.cfg.iterations * default_max_steps(root.cfg)
         z, weight = value_targets(sp.reward.float(), sp.done)

@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, _move_lib, _priors_lib, _search_lib, _train_lib
+from . import _leaves_lib, _lib, _move_lib, _priors_lib, _search_lib, _train_lib
 from .config import EnvConfig, KIND_PIN, KIND_RECT, KIND_SPATIAL, KIND_SQUARE
 from .instances import Instance, InstanceStream, env_seed, pack_instances
 
@@ -152,7 +152,7 @@ class BatchedPlacementEnv:
             raise RuntimeError("BatchedPlacementEnv needs a GPU device (there is no CPU fallback)")
         # the device the handle lives on, index included: one named without an index is the current device, now and for good
         self.device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
-        self._L = _train_lib.bind(_move_lib.bind(_priors_lib.bind(_search_lib.bind(_lib.load()))))
+        self._L = _leaves_lib.bind(_train_lib.bind(_move_lib.bind(_priors_lib.bind(_search_lib.bind(_lib.load())))))
         # per-environment spaces (the reference constructors' declarations); every tensor adds a leading batch dim
         from .spaces import action_space_for, observation_space_for
         self.action_space = self.single_action_space = action_space_for(cfg)
@@ -896,6 +896,62 @@ class BatchedPlacementEnv:
             setattr(req, name, _ptr(t))
         req.stream = self._stream().value
         _lib.check(self._L.pcbenv_puct_advance(self._h, C.byref(req)), self._h)
+
+    def puct_leaves_request(self, tree: Dict[str, torch.Tensor], c_puct: float = 1.0, max_children: int = 16,
+                            leaves: int = 1) -> "_leaves_lib.PcbenvPuctLeavesRequest":
+        """The request of `puct_advance_leaves` for the tensors in `tree` (see `pcbenv.search.new_puct_tree(leaves=L)` for a
+        set of the right shapes): the keys are the members of pcbenv_puct_leaves_request (include/pcbenv_leaves.h) -- the
+        tree tensors `num_nodes` ... `reward_hi` and `pending`, `selected`, `path_len`, `paths` and optionally `errors_dev`
+        -- on this device, contiguous, of the dtypes and shapes the header gives; P, N and T are read off `parent` [P, N]
+        and `paths` [T, P * L, 3], C = max_children and L = leaves are arguments.  The request holds addresses only: the
+        caller keeps the tensors alive."""
+        i32, f64 = torch.int32, torch.float64
+        par, paths, L = tree["parent"], tree["paths"], int(leaves)
+        if L < 1 or L > _leaves_lib.MAX_PUCT_LEAVES:
+            raise ValueError(f"leaves must be in [1, {_leaves_lib.MAX_PUCT_LEAVES}], got {L}")
+        if par.dim() != 2 or paths.dim() != 3 or paths.shape[1:] != (par.shape[0] * L, 3):
+            raise ValueError(f"parent must be [P, N] and paths [T, P * {L}, 3], got {tuple(par.shape)} and {tuple(paths.shape)}")
+        (P, N), T = par.shape, paths.shape[0]
+        want = {"num_nodes": (i32, (P,)), "node_action": (i32, (P, N, 3)), "terminal": (torch.uint8, (P, N)), "reward_lo": (f64, (P,)),
+                "reward_hi": (f64, (P,)), "selected": (i32, (P * L,)), "path_len": (i32, (P * L,)), "paths": (i32, (T, P * L, 3))}
+        want.update({n: (i32, (P, N)) for n in ("parent", "depth", "visits", "num_children", "first_child", "pending")})
+        want.update({n: (f64, (P, N)) for n in ("prior", "value_sum", "value_max")})
+        if tree.get("errors_dev") is not None:
+            want["errors_dev"] = (i32, (1,))
+        req = _leaves_lib.PcbenvPuctLeavesRequest(struct_size=C.sizeof(_leaves_lib.PcbenvPuctLeavesRequest), num_roots=P, capacity=N,
+                                                  max_children=int(max_children), max_steps=T, c_puct=float(c_puct), num_leaves=L)
+        for name, (dtype, shape) in want.items():
+            check_tensor(self.device, name, tree[name], dtype, shape)
+            setattr(req, name, _ptr(tree[name]))
+        return req
+
+    def puct_advance_leaves(self, req: "_leaves_lib.PcbenvPuctLeavesRequest", phases: int, value: Optional[torch.Tensor] = None,
+                            leaf_terminal: Optional[torch.Tensor] = None, cand_count: Optional[torch.Tensor] = None,
+                            cand_actions: Optional[torch.Tensor] = None, cand_prior: Optional[torch.Tensor] = None) -> None:
+        """One step of P PUCT search trees with L = req.num_leaves leaves per root on the device
+        (`pcbenv_puct_advance_leaves`, one kernel launch on the current stream, nothing else): `phases` is a set of
+        `_lib.TREE_INIT`, `TREE_ABSORB`, `TREE_SELECT`, run in that order.  SELECT descends every tree L times, each descent
+        leaving a pending visit on its path, and writes `selected`, `path_len` [P * L] and `paths` [T, P * L, 3], row
+        p * L + l the leaf l of root p (-1 in `selected` and `path_len`: no leaf) -- the `paths=` / `path_len=` of the next
+        `gather_` or `playout(k=L)` call; ABSORB takes the evaluation of those rows -- `value` [P * L] float64,
+        `leaf_terminal` [P * L] uint8, `cand_count` [P * L] int32, `cand_actions` [P * L, K, 3] int32, `cand_prior`
+        [P * L, K] float32; K is read off `cand_prior` -- expands and backs up, leaf after leaf.  `req`:
+        `puct_leaves_request(tree, c_puct, max_children, leaves)`, reusable for every call on the same tensors."""
+        P = req.num_roots
+        if P == 0:  # torch gives empty tensors a null pointer
+            return
+        R = P * req.num_leaves
+        req.phases = int(phases)
+        K = int(cand_prior.shape[1]) if isinstance(cand_prior, torch.Tensor) and cand_prior.dim() == 2 else "K"
+        req.num_candidates = K if isinstance(K, int) else 0
+        for name, t, dtype, shape in (("value", value, torch.float64, (R,)), ("leaf_terminal", leaf_terminal, torch.uint8, (R,)),
+                                      ("cand_count", cand_count, torch.int32, (R,)), ("cand_actions", cand_actions, torch.int32, (R, K, 3)),
+                                      ("cand_prior", cand_prior, torch.float32, (R, K))):
+            if t is not None:
+                check_tensor(self.device, name, t, dtype, shape)
+            setattr(req, name, _ptr(t))
+        req.stream = self._stream().value
+        _lib.check(self._L.pcbenv_puct_advance_leaves(self._h, C.byref(req)), self._h)
 
     def puct_move_request(self, tree: Dict[str, torch.Tensor], max_children: int = 16) -> "_move_lib.PcbenvPuctMoveRequest":
         """The request of `puct_move` for the tensors in `tree`: the tree tensors of `puct_request` (`num_nodes` ...

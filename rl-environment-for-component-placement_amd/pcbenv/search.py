@@ -24,6 +24,11 @@ proportion to the visits, and the subtree below it as the next search's tree -- 
 pcbenv_puct_move (include/pcbenv_move.h); `puct_selfplay` plays episodes with them on the device, two launches per move
 next to `step`.
 
+Every PUCT function takes `leaves=L`: leaf-parallel selection with virtual visits -- a root descends L times before
+anything is evaluated, each descent leaving a pending visit on its path, the evaluator sees P * L nodes at once and one
+launch backs them up (pcbenv_puct_advance_leaves, include/pcbenv_leaves.h).  With leaves == 1 each of them does what it
+did before that keyword existed.
+
 `policy_backend` replaces the uniform rollout of either search by a policy's: the node a path names is materialised
 in a planner batch by `gather_(paths=...)` (pcbenv_gather_paths, one launch), and the rollout behind it draws from the
 logits a network gives for the planner's observations.
@@ -439,16 +444,18 @@ class PuctSearch:
     errors: torch.Tensor         # 0-dim int32: bit 0 = the children of a node did not fit into the free slots
 
 
-def new_puct_tree(P: int, N: int, T: int, device) -> dict:
-    """The tensors of P PUCT trees of N node slots and T steps, as `BatchedPlacementEnv.puct_request` takes them.
-    Uninitialised but for `paths` and `errors_dev`: PCBENV_TREE_INIT fills the rest."""
+def new_puct_tree(P: int, N: int, T: int, device, leaves: int = 1) -> dict:
+    """The tensors of P PUCT trees of N node slots and T steps, as `BatchedPlacementEnv.puct_request` takes them -- and,
+    with `pending` [P, N] and the exchange tensors `selected`, `path_len` and `paths` of P * leaves rows, as
+    `puct_leaves_request` does.  Uninitialised but for `paths`, `pending` and `errors_dev`: PCBENV_TREE_INIT fills the rest."""
     i32, f64 = dict(dtype=torch.int32, device=device), dict(dtype=torch.float64, device=device)
+    R = P * int(leaves)
     tree = {n: torch.empty((P, N), **i32) for n in ("parent", "depth", "visits", "num_children", "first_child")}
     tree.update({n: torch.empty((P, N), **f64) for n in ("prior", "value_sum", "value_max")})
     tree.update({n: torch.empty(P, **f64) for n in ("reward_lo", "reward_hi")})
-    tree.update({n: torch.empty(P, **i32) for n in ("num_nodes", "selected", "path_len")})
+    tree.update(num_nodes=torch.empty(P, **i32), selected=torch.empty(R, **i32), path_len=torch.empty(R, **i32))
     tree.update(node_action=torch.empty((P, N, 3), **i32), terminal=torch.empty((P, N), dtype=torch.uint8, device=device),
-                paths=torch.zeros((T, P, 3), **i32), errors_dev=torch.zeros(1, **i32))
+                paths=torch.zeros((T, R, 3), **i32), errors_dev=torch.zeros(1, **i32), pending=torch.zeros((P, N), **i32))
     return tree
 
 
@@ -473,13 +480,32 @@ def puct_result(tree: dict, max_children: int) -> PuctSearch:
                       tree["errors_dev"][0])
 
 
-def _puct_arguments(root, iterations, max_children, max_steps, capacity, tree=None):
+def sqrt_rn(x: torch.Tensor) -> torch.Tensor:
+    """The correctly rounded float64 square root of a count (x >= 1, integer-valued): what sqrt() of csrc/pcb_tree.h:root_of
+    gives on the host and __dsqrt_rn on the device.  On a device this is torch.sqrt.  torch's CPU kernel is off by one unit
+    in the last place for some arguments (2, 8, 19, 32, ...), which decides a PUCT selection whose two best scores tie, so
+    on the CPU the result is corrected once: s * s as an exact sum p + e of two doubles (Dekker's product over Veltkamp's
+    split), the residual x - p - e, and s + residual / (2 s)."""
+    s = torch.sqrt(x)
+    if x.device.type != "cpu":
+        return s
+    t = 134217729.0 * s
+    hi = t - (t - s)
+    lo = s - hi
+    p = s * s
+    e = ((hi * hi - p) + 2.0 * hi * lo) + lo * lo
+    return s + ((x - p) - e) / (2.0 * s)
+
+
+def _puct_arguments(root, iterations, max_children, max_steps, capacity, tree=None, leaves=1):
     from .batched_env import default_max_steps
     P, C, M = int(root.num_envs), int(max_children), int(iterations)
     if M < 1 or C < 1 or C > 64:
         raise ValueError("a PUCT search needs iterations >= 1 and max_children in [1, 64]")
+    if int(leaves) < 1 or int(leaves) > 64:
+        raise ValueError("a PUCT search needs leaves in [1, 64]")
     T = default_max_steps(root.cfg) if max_steps is None else int(max_steps)
-    N = 1 + M * C if capacity is None else int(capacity)
+    N = 1 + M * int(leaves) * C if capacity is None else int(capacity)
     if tree is not None:  # the search goes on in the tree it is given: the capacity is that tree's
         if tuple(tree["parent"].shape[:1]) != (P,) or tree["parent"].dim() != 2:
             raise ValueError(f"tree: parent must be [{P}, N], got {list(tree['parent'].shape)}")
@@ -490,7 +516,7 @@ def _puct_arguments(root, iterations, max_children, max_steps, capacity, tree=No
 
 
 def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float = 1.0, max_children: int = 16, max_steps=None,
-                capacity=None, tree=None) -> PuctSearch:
+                capacity=None, tree=None, leaves: int = 1) -> PuctSearch:
     """Batched PUCT (the AlphaZero search) over all P = root.num_envs roots in lock-step, the tree in tensors, one
     `evaluate` per iteration and no host synchronisation inside the loop: the specification of pcbenv_puct_advance
     (include/pcbenv_search.h), in tensor code for any device.  Iteration m:
@@ -509,8 +535,19 @@ def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float 
     most transitions of an episode (default: that of root.cfg).  Needs iterations >= 1.
     tree: the search continues in this tree instead of an empty one -- a dict of PUCT_TREE_TENSORS (`search_tree` of an
     earlier result, or what `puct_reroot` returns), integer tensors of any width, which is not modified; capacity is then
-    the tree's.  Such a tree may be deep from the first iteration on, so descent and backup are bounded by max_steps alone."""
-    P, C, M, T, N = _puct_arguments(root, iterations, max_children, max_steps, capacity, tree)
+    the tree's.  Such a tree may be deep from the first iteration on, so descent and backup are bounded by max_steps alone.
+    leaves = L > 1: leaf-parallel selection with virtual visits, the specification of pcbenv_puct_advance_leaves
+    (include/pcbenv_leaves.h).  Iteration m selects L times, leaf after leaf, before anything is evaluated.  A descent
+    adds one pending visit to every node it passes, the root and the node it ends at included, and the next one scores a
+    child with n_c = visits + pending, q * (visits / n_c) in the place of q -- a pending visit counts as one that returned
+    the smallest value seen -- and sqrt(max(visits + pending of the node, 1)).  A descent that ends at a node that is not
+    terminal, has no children and has a pending visit already is a repeat: it takes its pending visits back, and this and
+    all later leaves of the root are no leaf -- path_len -1, their evaluation is not looked at.  Then ONE evaluate(paths
+    [max_steps, P * L, 3], path_len [P * L], step_index + m * max_steps), row p * L + l the leaf l of root p, and the
+    leaves are expanded and backed up in the same order, each backup taking the pending visit off its chain.  capacity
+    defaults to 1 + iterations * L * max_children."""
+    P, C, M, T, N = _puct_arguments(root, iterations, max_children, max_steps, capacity, tree, leaves)
+    L = int(leaves)
     dev = getattr(root, "device", "cpu")
     i64, f64 = dict(dtype=torch.int64, device=dev), dict(dtype=torch.float64, device=dev)
     # one slot and one path row more than used: where a root has nothing to write, the write goes there
@@ -521,6 +558,7 @@ def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float 
     vmax = torch.full((P, N + 1), float("-inf"), **f64)
     terminal = torch.zeros((P, N + 1), dtype=torch.bool, device=dev)
     count = torch.ones(P, **i64)
+    pending = torch.zeros((P, N + 1), **i64)  # zero between iterations: every selection is absorbed
     lo, hi = torch.full((P,), float("inf"), **f64), torch.full((P,), float("-inf"), **f64)
     errors = torch.zeros(1, dtype=torch.int32, device=dev)
     if tree is not None:
@@ -535,86 +573,114 @@ def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float 
     rows, lane = torch.arange(P, **i64), torch.arange(C, **i64)
     trash = torch.full((P,), N, **i64)
     zero_r, ninf_r = torch.zeros(P, **f64), torch.full((P,), float("-inf"), **f64)
+    none = torch.full((P,), -1, **i64)
     for m in range(M):
         # selection (iteration m finds no node deeper than m: a bound the host knows without asking the device)
-        node = torch.zeros(P, **i64)
-        plen = torch.zeros(P, **i64)
-        stopped = torch.zeros(P, dtype=torch.bool, device=dev)
-        paths = torch.zeros((T + 1, P, 3), dtype=torch.int32, device=dev)
+        paths = torch.zeros((T + 1, P, L, 3), dtype=torch.int32, device=dev)
         wide = hi > lo
         span = torch.where(wide, hi - lo, torch.ones_like(hi))
-        for d in range(deepest(m)):
-            k = nchild[rows, node]
-            stopped = stopped | terminal[rows, node] | (k == 0)
-            fc = first_child[rows, node]
-            mine = (lane[None, :] < k[:, None]) & ~stopped[:, None]
-            ch = torch.where(mine, fc[:, None] + lane[None, :], trash[:, None])
-            n_c = visits[rows[:, None], ch]
-            n_cf = n_c.to(torch.float64)
-            q = (vsum[rows[:, None], ch] / n_cf.clamp(min=1.0) - lo[:, None]) / span[:, None]
-            q = torch.where((n_c > 0) & wide[:, None], q, torch.zeros_like(q))
-            n_p = visits[rows, node].clamp(min=1).to(torch.float64)
-            u = c_puct * prior[rows[:, None], ch] * torch.sqrt(n_p)[:, None] / (1.0 + n_cf)
-            score = torch.where(mine, q + u, torch.full_like(q, float("-inf")))
-            nxt = fc + score.argmax(dim=1)                         # the first maximum: the lowest child
-            node = torch.where(stopped, node, nxt)
-            paths[torch.where(stopped, torch.full_like(node, T), torch.full_like(node, d)), rows] = node_action[rows, node]
-            plen = plen + (~stopped).to(torch.int64)
+        alive = torch.ones(P, dtype=torch.bool, device=dev)  # no repeat so far
+        chosen, levels = [], []
+        for l in range(L):
+            node = torch.zeros(P, **i64)
+            plen = torch.zeros(P, **i64)
+            stopped = ~alive
+            for d in range(deepest(m)):
+                k = nchild[rows, node]
+                stopped = stopped | terminal[rows, node] | (k == 0)
+                fc = first_child[rows, node]
+                mine = (lane[None, :] < k[:, None]) & ~stopped[:, None]
+                ch = torch.where(mine, fc[:, None] + lane[None, :], trash[:, None])
+                n_c = visits[rows[:, None], ch]
+                n_vf = n_c.to(torch.float64)
+                n_cf = (n_c + pending[rows[:, None], ch]).to(torch.float64)
+                q = ((vsum[rows[:, None], ch] / n_vf.clamp(min=1.0) - lo[:, None]) / span[:, None]) * (n_vf / n_cf)
+                q = torch.where((n_c > 0) & wide[:, None], q, torch.zeros_like(q))
+                n_p = (visits[rows, node] + pending[rows, node]).clamp(min=1).to(torch.float64)
+                u = c_puct * prior[rows[:, None], ch] * sqrt_rn(n_p)[:, None] / (1.0 + n_cf)
+                score = torch.where(mine, q + u, torch.full_like(q, float("-inf")))
+                nxt = fc + score.argmax(dim=1)                         # the first maximum: the lowest child
+                pending[rows, torch.where(stopped, trash, node)] += 1  # the node the descent leaves
+                node = torch.where(stopped, node, nxt)
+                paths[torch.where(stopped, torch.full_like(node, T), torch.full_like(node, d)), rows, l] = node_action[rows, node]
+                plen = plen + (~stopped).to(torch.int64)
+            # a repeat takes back what it added above the node it ended at, and ends the selection of its root
+            repeat = alive & ~terminal[rows, node] & (nchild[rows, node] == 0) & (pending[rows, node] > 0)
+            cur = torch.where(repeat, parent[rows, node], none)
+            for _ in range(deepest(m)):
+                on = cur >= 0
+                idx = torch.where(on, cur, trash)
+                pending[rows, idx] -= on.to(torch.int64)
+                cur = torch.where(on, parent[rows, idx], none)
+            alive = alive & ~repeat
+            pending[rows, torch.where(alive, node, trash)] += 1
+            chosen.append(torch.where(alive, node, none))
+            levels.append(torch.where(alive, plen, none))
         # evaluation
-        ev = evaluate(paths[:T], plen.to(torch.int32), int(step_index) + m * T)
-        value = ev.value.to(device=dev, dtype=torch.float64)
-        over = ev.terminal.to(device=dev).bool()
+        ev = evaluate(paths[:T].reshape(T, P * L, 3), torch.stack(levels, dim=1).reshape(P * L).to(torch.int32), int(step_index) + m * T)
         K = int(ev.cand_prior.shape[1])
         Kc = min(K, C)
-        # expansion: all the children at once, or none
-        terminal[rows, node] = terminal[rows, node] | over
-        k = ev.cand_count.to(device=dev, dtype=torch.int64).clamp(0, Kc)
-        due = ~over & (nchild[rows, node] == 0) & ~terminal[rows, node] & (k > 0)
-        fits = count + k <= N
-        make = due & fits
-        errors = errors | ((due & ~fits).any().to(torch.int32) * 1)
-        on = make[:, None] & (lane[None, :Kc] < k[:, None])
-        slot = torch.where(on, count[:, None] + lane[None, :Kc], trash[:, None])
-        parent[rows[:, None], slot] = torch.where(on, node[:, None], torch.full_like(slot, -1))
-        depth[rows[:, None], slot] = torch.where(on, depth[rows, node][:, None] + 1, torch.zeros_like(slot))
-        acts = ev.cand_actions.to(device=dev, dtype=torch.int32)[:, :Kc]
-        node_action[rows[:, None], slot] = torch.where(on[:, :, None], acts, torch.zeros_like(acts))
-        pri = ev.cand_prior.to(device=dev, dtype=torch.float32)[:, :Kc].to(torch.float64)
-        prior[rows[:, None], slot] = torch.where(on, pri, torch.zeros_like(pri))
-        at = torch.where(make, node, trash)
-        first_child[rows, at] = torch.where(make, count, torch.full_like(count, -1))
-        nchild[rows, at] = torch.where(make, k, torch.zeros_like(k))
-        count = count + torch.where(make, k, torch.zeros_like(k))
-        # backup
-        lo, hi = torch.minimum(lo, value), torch.maximum(hi, value)
-        cur = node
-        for _ in range(deepest(m) + 1):  # the node is at depth m at most
-            on = cur >= 0
-            idx = torch.where(on, cur, trash)[:, None]
-            visits.scatter_add_(1, idx, on.to(torch.int64)[:, None])
-            vsum.scatter_add_(1, idx, torch.where(on, value, zero_r)[:, None])
-            vmax.scatter_reduce_(1, idx, torch.where(on, value, ninf_r)[:, None], reduce="amax")
-            cur = torch.where(on, parent[rows, idx[:, 0]], torch.full_like(cur, -1))
+        ev_value = ev.value.to(device=dev, dtype=torch.float64).reshape(P, L)
+        ev_over = ev.terminal.to(device=dev).bool().reshape(P, L)
+        ev_count = ev.cand_count.to(device=dev, dtype=torch.int64).reshape(P, L)
+        ev_actions = ev.cand_actions.to(device=dev, dtype=torch.int32).reshape(P, L, K, 3)
+        ev_prior = ev.cand_prior.to(device=dev, dtype=torch.float32).reshape(P, L, K)
+        for l in range(L):
+            live = chosen[l] >= 0
+            node = chosen[l].clamp(min=0)
+            value = torch.where(live, ev_value[:, l], zero_r)
+            over = ev_over[:, l] & live
+            # expansion: all the children at once, or none
+            terminal[rows, node] = terminal[rows, node] | over
+            k = ev_count[:, l].clamp(0, Kc)
+            due = live & ~over & (nchild[rows, node] == 0) & ~terminal[rows, node] & (k > 0)
+            fits = count + k <= N
+            make = due & fits
+            errors = errors | ((due & ~fits).any().to(torch.int32) * 1)
+            on = make[:, None] & (lane[None, :Kc] < k[:, None])
+            slot = torch.where(on, count[:, None] + lane[None, :Kc], trash[:, None])
+            parent[rows[:, None], slot] = torch.where(on, node[:, None], torch.full_like(slot, -1))
+            depth[rows[:, None], slot] = torch.where(on, depth[rows, node][:, None] + 1, torch.zeros_like(slot))
+            acts = ev_actions[:, l, :Kc]
+            node_action[rows[:, None], slot] = torch.where(on[:, :, None], acts, torch.zeros_like(acts))
+            pri = ev_prior[:, l, :Kc].to(torch.float64)
+            prior[rows[:, None], slot] = torch.where(on, pri, torch.zeros_like(pri))
+            at = torch.where(make, node, trash)
+            first_child[rows, at] = torch.where(make, count, torch.full_like(count, -1))
+            nchild[rows, at] = torch.where(make, k, torch.zeros_like(k))
+            count = count + torch.where(make, k, torch.zeros_like(k))
+            # backup
+            lo, hi = torch.where(live, torch.minimum(lo, value), lo), torch.where(live, torch.maximum(hi, value), hi)
+            cur = torch.where(live, node, none)
+            for _ in range(deepest(m) + 1):  # the node is at depth m at most
+                on = cur >= 0
+                idx = torch.where(on, cur, trash)[:, None]
+                visits.scatter_add_(1, idx, on.to(torch.int64)[:, None])
+                vsum.scatter_add_(1, idx, torch.where(on, value, zero_r)[:, None])
+                vmax.scatter_reduce_(1, idx, torch.where(on, value, ninf_r)[:, None], reduce="amax")
+                pending.scatter_add_(1, idx, -on.to(torch.int64)[:, None])
+                cur = torch.where(on, parent[rows, idx[:, 0]], torch.full_like(cur, -1))
     tree = dict(num_nodes=count, parent=parent[:, :N], depth=depth[:, :N], visits=visits[:, :N], num_children=nchild[:, :N],
                 first_child=first_child[:, :N], node_action=node_action[:, :N], prior=prior[:, :N], value_sum=vsum[:, :N],
                 value_max=vmax[:, :N], terminal=terminal[:, :N], reward_lo=lo, reward_hi=hi, errors_dev=errors)
     return puct_result(tree, C)
 
 
-def _puct_iterations(root, req, tree, M, T, evaluate, step_index, first_phases):
+def _puct_iterations(root, req, tree, M, T, evaluate, step_index, first_phases, leaves=1):
     """The launches of one device search of M iterations on `tree`: `first_phases` (INIT | SELECT, or SELECT alone in a tree
-    that is kept), then per iteration `evaluate` followed by ABSORB | SELECT, the last iteration by ABSORB alone."""
+    that is kept), then per iteration `evaluate` followed by ABSORB | SELECT, the last iteration by ABSORB alone.  With
+    leaves > 1 the launches are pcbenv_puct_advance_leaves' and `req` is a `puct_leaves_request`."""
     from . import _lib
-    root.puct_advance(req, first_phases)
+    advance = root.puct_advance if int(leaves) == 1 else root.puct_advance_leaves
+    advance(req, first_phases)
     for m in range(M):
         ev = evaluate(tree["paths"], tree["path_len"], int(step_index) + m * T)
         over = ev.terminal.view(torch.uint8) if ev.terminal.dtype == torch.bool else ev.terminal
-        root.puct_advance(req, _lib.TREE_ABSORB | (_lib.TREE_SELECT if m + 1 < M else 0), ev.value, over, ev.cand_count, ev.cand_actions,
-                          ev.cand_prior)
+        advance(req, _lib.TREE_ABSORB | (_lib.TREE_SELECT if m + 1 < M else 0), ev.value, over, ev.cand_count, ev.cand_actions, ev.cand_prior)
 
 
 def puct_search_device(root, iterations: int, step_index: int, evaluate, c_puct: float = 1.0, max_children: int = 16, max_steps=None,
-                       capacity=None, tree=None) -> PuctSearch:
+                       capacity=None, tree=None, leaves: int = 1) -> PuctSearch:
     """`puct_search` with the tree kept by the device: an iteration is `evaluate` and one kernel launch,
     `root.puct_advance` (pcbenv_puct_advance: expansion, backup, the next selection), with no tensor operation between
     them: INIT | SELECT first, then per iteration `evaluate(tree paths, path_len, step_index + m * max_steps)` followed by
@@ -623,14 +689,18 @@ def puct_search_device(root, iterations: int, step_index: int, evaluate, c_puct:
     it is a single IEEE one on either side.  The evaluation's tensors must be on the root's device, contiguous, of the
     dtypes `Evaluation` names (`terminal` may be bool).
     tree: the search continues in this tree, in place -- the tensors of `new_puct_tree` as an earlier search or
-    `puct_move(MOVE_REROOT)` left them; capacity is then the tree's, INIT is skipped and the first launch is SELECT alone."""
+    `puct_move(MOVE_REROOT)` left them; capacity is then the tree's, INIT is skipped and the first launch is SELECT alone.
+    leaves = L > 1: `puct_search(leaves=L)` with `root.puct_advance_leaves` (pcbenv_puct_advance_leaves,
+    include/pcbenv_leaves.h) as the one launch per iteration; `evaluate` sees P * L rows, row p * L + l the leaf l of root
+    p, path_len -1 where there is no leaf.  A tree that is kept is one of `new_puct_tree(leaves=L)`."""
     from . import _lib
-    P, C, M, T, N = _puct_arguments(root, iterations, max_children, max_steps, capacity, tree)
+    P, C, M, T, N = _puct_arguments(root, iterations, max_children, max_steps, capacity, tree, leaves)
+    L = int(leaves)
     kept = tree is not None
     if not kept:
-        tree = new_puct_tree(P, N, T, root.device)
-    req = root.puct_request(tree, c_puct, C)
-    _puct_iterations(root, req, tree, M, T, evaluate, step_index, _lib.TREE_SELECT if kept else _lib.TREE_INIT | _lib.TREE_SELECT)
+        tree = new_puct_tree(P, N, T, root.device, L)
+    req = root.puct_request(tree, c_puct, C) if L == 1 else root.puct_leaves_request(tree, c_puct, C, L)
+    _puct_iterations(root, req, tree, M, T, evaluate, step_index, _lib.TREE_SELECT if kept else _lib.TREE_INIT | _lib.TREE_SELECT, L)
     return puct_result(tree, C)
 
 
@@ -774,7 +844,7 @@ class SelfPlay:
 
 
 def puct_selfplay(root, evaluate, moves: int, iterations: int, step_index: int = 0, c_puct: float = 1.0, max_children: int = 16,
-                  max_steps=None, capacity=None, mode: int = MOVE_GREEDY, seed=None, on_move=None) -> SelfPlay:
+                  max_steps=None, capacity=None, mode: int = MOVE_GREEDY, seed=None, on_move=None, leaves: int = 1) -> SelfPlay:
     """Plays `moves` moves of every root environment with a PUCT search whose tree stays on the device and is kept from
     move to move.  Per move: `iterations` of search on the kept tree (`evaluate` and one pcbenv_puct_advance launch each,
     as `puct_search_device(tree=)`); `root.puct_move(MOVE_CHOOSE)` -- the visit distribution of the root and the move,
@@ -788,23 +858,28 @@ def puct_selfplay(root, evaluate, moves: int, iterations: int, step_index: int =
     search adds have to fit: an overflow shows as bit 0 of `errors`, as in `puct_search_device`, and the search goes on in
     the full tree.  The bound that can never overflow is 1 + moves * iterations * max_children.
     on_move: called as on_move(j, tree) after move j's REROOT with the dict of the tree and move tensors (`remap` among
-    them), which the next move overwrites: a trainer copies what it keeps."""
+    them), which the next move overwrites: a trainer copies what it keeps.
+    leaves = L > 1: every iteration selects and evaluates L leaves per root (`puct_search_device(leaves=L)`); `evaluate`
+    sees P * L rows and the default capacity is 1 + 2 * iterations * L * max_children.  `pending` is zero after every
+    search, so the move's two launches take the tree as it is."""
     from . import _lib, _move_lib
-    P, C, M, T, N = _puct_arguments(root, iterations, max_children, max_steps, 1 + 2 * int(iterations) * int(max_children) if capacity is None else capacity)
+    L = int(leaves)
+    P, C, M, T, N = _puct_arguments(root, iterations, max_children, max_steps,
+                                    1 + 2 * int(iterations) * L * int(max_children) if capacity is None else capacity, leaves=L)
     J = int(moves)
     if J < 1:
         raise ValueError("puct_selfplay needs moves >= 1")
     dev = root.device
-    tree = new_puct_tree(P, N, T, dev)
+    tree = new_puct_tree(P, N, T, dev, L)
     tree.update(new_move_tensors(P, N, C, dev))
-    req, mreq = root.puct_request(tree, c_puct, C), root.puct_move_request(tree, C)
+    req, mreq = root.puct_request(tree, c_puct, C) if L == 1 else root.puct_leaves_request(tree, c_puct, C, L), root.puct_move_request(tree, C)
     seed = (root.run_seed ^ 0x6d6f7665) if seed is None else int(seed)
     i32 = dict(dtype=torch.int32, device=dev)
     out = SelfPlay(torch.empty((J, P, 3), **i32), torch.empty((J, P, C), **i32), torch.empty((J, P, C, 3), **i32),
                    torch.empty((J, P), dtype=torch.float64, device=dev), torch.empty((J, P), dtype=torch.float64, device=dev),
                    torch.empty((J, P), dtype=torch.uint8, device=dev), torch.empty((J, P), **i32), tree["errors_dev"][0], tree)
     for j in range(J):
-        _puct_iterations(root, req, tree, M, T, evaluate, int(step_index) + j * M * T, _lib.TREE_SELECT if j else _lib.TREE_INIT | _lib.TREE_SELECT)
+        _puct_iterations(root, req, tree, M, T, evaluate, int(step_index) + j * M * T, _lib.TREE_SELECT if j else _lib.TREE_INIT | _lib.TREE_SELECT, L)
         root.puct_move(mreq, _move_lib.MOVE_CHOOSE, mode=mode, seed=seed, step_index=int(step_index) + j)
         _, reward, done, _ = root.step(tree["move_action"])
         out.actions[j], out.child_visits[j], out.child_actions[j], out.root_value[j] = tree["move_action"], tree["child_visits"], tree["child_actions"], tree["root_value"]
@@ -845,7 +920,7 @@ def top_priors(logits: torch.Tensor, action_mask: torch.Tensor, K: int):
     return count.to(torch.int32), actions.contiguous(), prior.contiguous()
 
 
-def network_evaluator(root, planner, logits_fn, value_fn=None, max_children: int = 16, priors: str = "torch"):
+def network_evaluator(root, planner, logits_fn, value_fn=None, max_children: int = 16, priors: str = "torch", leaves: int = 1):
     """An `evaluate` for `puct_search` / `puct_search_device` that scores a node with a network:
     `(paths, path_len, step_index0) -> Evaluation`.  planner: P = root.num_envs environments of the root's definition
     with auto_reset=False, the root's run_seed and first_env_index 0 (the constraints of `policy_backend`).
@@ -862,12 +937,17 @@ def network_evaluator(root, planner, logits_fn, value_fn=None, max_children: int
     sorted.  The two differ where float32 `exp` makes unequal logits equally probable, or zero: there the torch chain,
     which orders probabilities, falls back to index order, and the device, which orders the logits themselves, keeps logit
     order; the priors differ in their last bits (the device forms them in float64 and rounds once).  With constant logits
-    the two are bit-identical: Z = n exactly and every prior is float32(1 / n) on both sides."""
+    the two are bit-identical: Z = n exactly and every prior is float32(1 / n) on both sides.
+
+    leaves = L > 1, for the searches' `leaves=L`: the planner has P * L environments, row p * L + l forks root p
+    (`gather_` with the index arange(P * L) // L), and the rollout without a value_fn is `root.playout(k=L, paths=...)`.
+    A row with path_len == -1 is no leaf: it keeps its episode, and what comes back for it is ignored by the search."""
     if priors not in ("torch", "device"):
         raise ValueError(f'priors must be "torch" or "device", got {priors!r}')
+    L = int(leaves)
     P = int(planner.num_envs)
-    if P != int(root.num_envs):
-        raise ValueError(f"the planner needs {int(root.num_envs)} environments, it has {P}")
+    if L < 1 or P != int(root.num_envs) * L:
+        raise ValueError(f"the planner needs {int(root.num_envs)}" + (f" x {L}" if L != 1 else "") + f" environments, it has {P}")
     if planner.auto_reset:
         raise ValueError("the planner must be created with auto_reset=False (a node's episode ends at its first done)")
     if planner.run_seed != root.run_seed or planner.first_env_index != 0:
@@ -876,7 +956,8 @@ def network_evaluator(root, planner, logits_fn, value_fn=None, max_children: int
 
     def evaluate(paths, path_len, step_index0):
         dev, T = planner.device, int(paths.shape[0])
-        planner.gather_(torch.arange(P, dtype=torch.int32, device=dev), source=root, paths=paths, path_len=path_len)
+        index = torch.arange(P, dtype=torch.int32, device=dev) if L == 1 else child_index(P // L, L, dev)
+        planner.gather_(index, source=root, paths=paths, path_len=path_len)
         obs = planner.obs
         over = (planner.gather_length > 0) & planner.done.bool()
         if priors == "device":
@@ -886,7 +967,7 @@ def network_evaluator(root, planner, logits_fn, value_fn=None, max_children: int
         if value_fn is not None:
             leaf = value_fn(obs).to(torch.float64).reshape(P)
         else:
-            leaf = root.playout(k=1, step_index=int(step_index0), paths=paths, path_len=path_len, max_steps=T).reward
+            leaf = root.playout(k=L, step_index=int(step_index0), paths=paths, path_len=path_len, max_steps=T).reward
         value = torch.where(over, planner.reward.to(torch.float64), leaf)
         return Evaluation(value, over.to(torch.uint8), count, actions, prior)
     return evaluate

@@ -1,5 +1,5 @@
 """Receding-horizon Monte-Carlo lookahead with pcbenv.search.best_of_k against the plain uniform-random policy, c3.
-python tools/search_demo.py [--roots 256] [--k 16] [--playouts | --tree [--device-tree] [--policy] | --puct [--device-priors] [--reuse] [--train N [--moves M] [--torch-loss]]]
+python tools/search_demo.py [--roots 256] [--k 16] [--playouts | --tree [--device-tree] [--policy] | --puct [--device-priors] [--reuse] [--leaves L] [--train N [--moves M] [--torch-loss]]]
 
 Both play the same instances (one episode per root environment).  The search forks every root k times into a planner
 batch (one device-side gather), plays every child to its end with the on-device sampler, and applies the best child's
@@ -17,7 +17,9 @@ expanded with the 16 most probable legal actions of pcbenv.search.network_evalua
 scored by one uniform rollout from it; the most-visited first action is applied.  --puct --reuse: the same search through
 pcbenv.search.puct_selfplay -- the tree stays on the device from move to move: pcbenv_puct_move picks the most-visited
 action and makes its subtree the next move's tree, so the k iterations of a move add to the visits already spent below it;
-the line then also reports the mean visits a move's root started with.  --puct --train N (a spatial configuration: --config
+the line then also reports the mean visits a move's root started with.  --puct --leaves L: every iteration selects L leaves
+per root (pcbenv_puct_advance_leaves) and the evaluator sees roots x L nodes at once; k stays the iterations per move, so a
+move costs k x L evaluations.  --puct --train N (a spatial configuration: --config
 c4): N rounds of pcbenv.alphazero.AlphaZeroTrainer -- collect() plays --moves moves of every root with puct_selfplay, k
 iterations each, pcbenv/policy.py's model behind network_evaluator(priors="device"); update() trains the model on the visit
 counts with pcbenv_evaluate_visits (--torch-loss: the torch chain instead) -- and one line per round: the mean final reward
@@ -60,12 +62,13 @@ def train(a, cfg):
     root = BatchedPlacementEnv(cfg, a.roots, queue_depth=episodes, run_seed=11, auto_reset=True)
     root.generate_instances()
     root.reset()
-    planner = BatchedPlacementEnv(cfg, a.roots, queue_depth=1, run_seed=11)
+    planner = BatchedPlacementEnv(cfg, a.roots * a.leaves, queue_depth=1, run_seed=11)
     planner.generate_instances()
     planner.reset()
     torch.manual_seed(0)
     trainer = AlphaZeroTrainer(root, planner, SpatialPolicy(cfg).to(root.device),
-                               AlphaZeroConfig(moves=moves, iterations=a.k, max_children=16, capacity=1 + moves * a.k * 16, device_loss=not a.torch_loss))
+                               AlphaZeroConfig(moves=moves, iterations=a.k, max_children=16, capacity=1 + moves * a.k * a.leaves * 16, device_loss=not a.torch_loss,
+                                               leaves=a.leaves))
     for it in range(a.train):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -97,6 +100,7 @@ def main():
     ap.add_argument("--puct", action="store_true", help="search with puct_search_device, k iterations per move, network_evaluator with constant logits")
     ap.add_argument("--device-priors", action="store_true", help="with --puct: the candidates from pcbenv_top_priors (network_evaluator(priors=\"device\"))")
     ap.add_argument("--reuse", action="store_true", help="with --puct: puct_selfplay, the subtree of the move played is kept (pcbenv_puct_move)")
+    ap.add_argument("--leaves", type=int, default=1, metavar="L", help="with --puct: L leaves per root and iteration (pcbenv_puct_advance_leaves); k stays the iterations per move")
     ap.add_argument("--train", type=int, default=0, metavar="N", help="with --puct: N collect/update rounds of pcbenv.alphazero.AlphaZeroTrainer")
     ap.add_argument("--moves", type=int, default=0, help="with --train: moves of every root per round (default: one episode)")
     ap.add_argument("--torch-loss", action="store_true", help="with --train: the policy loss through the torch chain (device_loss off)")
@@ -107,6 +111,8 @@ def main():
         ap.error("--device-priors goes with --puct")
     if a.reuse and not a.puct:
         ap.error("--reuse goes with --puct")
+    if a.leaves != 1 and not a.puct:
+        ap.error("--leaves goes with --puct")
     if a.puct and (a.tree or a.playouts):
         ap.error("--puct goes alone")
     if a.device_tree and not a.tree:
@@ -128,11 +134,11 @@ def main():
         e.reset()
         return e
     rand_root, search_root = make(P, 11), make(P, 11)
-    planner = make(P, 11) if a.policy or a.puct else None if a.playouts or a.tree else make(P * k, 12)  # (policy_backend, network_evaluator: the root's run seed)
+    planner = make(P * a.leaves, 11) if a.puct else make(P, 11) if a.policy else None if a.playouts or a.tree else make(P * k, 12)  # (policy_backend, network_evaluator: the root's run seed)
     backend = None
     if a.puct:
-        zeros = torch.zeros((P, cfg.num_orientations * cfg.height * cfg.width), dtype=torch.float32, device=search_root.device)
-        evaluate = network_evaluator(search_root, planner, lambda obs: zeros, max_children=16, priors="device" if a.device_priors else "torch")
+        zeros = torch.zeros((P * a.leaves, cfg.num_orientations * cfg.height * cfg.width), dtype=torch.float32, device=search_root.device)
+        evaluate = network_evaluator(search_root, planner, lambda obs: zeros, max_children=16, priors="device" if a.device_priors else "torch", leaves=a.leaves)
     if a.policy:
         from pcbenv.policy import SpatialPolicy
         torch.manual_seed(0)
@@ -152,7 +158,7 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if a.puct:
-            first = puct_search_device(search_root, k, 1000 + t * T * k, evaluate, max_children=16).action
+            first = puct_search_device(search_root, k, 1000 + t * T * k, evaluate, max_children=16, leaves=a.leaves).action
         elif a.tree:
             first = (tree_search_device if a.device_tree else tree_search)(search_root, k, step_index=1000 + t * T * k, backend=backend).action
         elif a.playouts:
@@ -161,16 +167,16 @@ def main():
             res = best_of_k(search_root, planner, k, step_index=1000 + t * T)
         torch.cuda.synchronize()
         spent += time.perf_counter() - t0
-        planner_steps += P * k * T
+        planner_steps += P * k * a.leaves * T
         _, r, d, _ = search_root.step(first if a.tree or a.puct else res.actions[0])
         return r, d
     kept = None
     if a.reuse:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        sp = puct_selfplay(search_root, evaluate, T, k, step_index=1000, max_children=16)
+        sp = puct_selfplay(search_root, evaluate, T, k, step_index=1000, max_children=16, leaves=a.leaves)
         torch.cuda.synchronize()
-        spent, planner_steps = time.perf_counter() - t0, P * k * T * T
+        spent, planner_steps = time.perf_counter() - t0, P * k * a.leaves * T * T
         search_final = final_rewards(search_root, lambda t: (sp.reward[t], sp.done[t]), T)
         kept = {"mean_visits_kept_per_move": round(float(sp.kept_visits[:-1].double().mean()), 2), "tree_errors": int(sp.errors)}
     else:
@@ -180,6 +186,8 @@ def main():
            "best_of_k_mean_final_reward": float(search_final.mean()),
            "search_env_steps_per_sec": round(planner_steps / spent), "search_seconds": round(spent, 3)}
     out.update(kept or {})
+    if a.leaves != 1:
+        out["leaves"] = a.leaves
     print(json.dumps(out), flush=True)
     for e in (rand_root, search_root, planner):
         if e is not None:
