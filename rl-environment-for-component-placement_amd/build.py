@@ -10,7 +10,9 @@ the host side -- the C ABI
 (csrc/pcbenv_api.hip), the layout derivation (csrc/pcb_config.hip) and the on-device instance generator with its kernels
 (csrc/pcb_gen.hip), which share csrc/pcb_host.h -- the two kernels every kind uses (csrc/pcb_sample.hip), the policy kernels
 (csrc/pcb_policy*.hip), the tree steps with their entry points (csrc/pcb_tree.hip, and csrc/pcb_puct.hip
-for include/pcbenv_search.h, csrc/pcb_puct_leaves.hip for include/pcbenv_leaves.h, csrc/pcb_puct_move.hip for include/pcbenv_move.h), the masked top-K of a policy's logits (csrc/pcb_top_priors.hip for include/pcbenv_priors.h)
+for include/pcbenv_search.h, csrc/pcb_puct_leaves.hip for include/pcbenv_leaves.h, csrc/pcb_puct_move.hip for include/pcbenv_move.h;
+what they share is csrc/pcb_group.h, the lane-group kernel skeleton and its launch, and csrc/pcb_tree_host.h, the argument
+checks of their entry points), the masked top-K of a policy's logits (csrc/pcb_top_priors.hip for include/pcbenv_priors.h)
 and the host instance generator
 (csrc/instance_gen.cpp).  csrc/pcb_layout.h is the layout contract both sides compile.
 """

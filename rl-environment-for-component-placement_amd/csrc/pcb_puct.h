@@ -20,6 +20,7 @@
 
 namespace pcb_puct {
 
+using pcb_tree::back_up;  // visits, value_sum and value_max of the node and every ancestor: at most T + 1 nodes
 using pcb_tree::beats;
 using pcb_tree::neg_inf;
 using pcb_tree::root_of;
@@ -40,6 +41,12 @@ struct Root {
     uint8_t *terminal;
     double *lo, *hi;
 };
+// Root p of a batch: `a` is a kernel's argument block, the tensors of all P roots under the names above.
+template <class Args> PCB_TREE_HD inline Root root_of_group(const Args &a, int p, int T) {
+    const long long s = (long long)p * a.N;
+    return Root{a.N, a.C, T, a.P, p, a.num_nodes + p, a.parent + s, a.depth + s, a.visits + s, a.num_children + s, a.first_child + s,
+                a.node_action + 3 * s, a.prior + s, a.value_sum + s, a.value_max + s, a.terminal + s, a.lo + p, a.hi + p};
+}
 
 // ---- init ----------------------------------------------------------------------------------------------------------
 // What one node slot holds before it is used; slot 0 is the root and holds the same.
@@ -114,20 +121,6 @@ PCB_TREE_HD inline void make_child(const Root &r, int node, int slot, int depth,
 PCB_TREE_HD inline void link_children(const Root &r, int node, int first, int k) {
     r.first_child[node] = first; r.num_children[node] = k; *r.num_nodes = first + k;
 }
-// visits, value_sum and value_max of the node and every ancestor: at most T + 1 nodes
-PCB_TREE_HD inline unsigned back_up(const Root &r, int leaf, double value) {
-    int cur = leaf;
-    for (int i = 0; i <= r.T && cur >= 0; i++) {
-        if (!slot_ok(cur, r.N)) return ERR_TREE;
-        const int up = r.parent[cur];
-        r.visits[cur] = r.visits[cur] + 1;
-        r.value_sum[cur] = r.value_sum[cur] + value;
-        r.value_max[cur] = value > r.value_max[cur] ? value : r.value_max[cur];
-        cur = up;
-    }
-    return 0u;
-}
-
 // value, leaf_terminal, cand_count: what the caller found at `selected`; cand_actions [K, 3] and cand_prior [K]: this root's rows.
 PCB_TREE_HD inline unsigned puct_absorb(const Root &r, int selected, double value, int leaf_terminal, int cand_count, int K,
                                         const int *cand_actions, const float *cand_prior) {

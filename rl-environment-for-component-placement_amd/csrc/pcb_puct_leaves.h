@@ -112,7 +112,7 @@ PCB_TREE_HD inline unsigned leaves_select(const Root &r, int *pending, int L, do
 }
 
 // ---- absorb --------------------------------------------------------------------------------------------------------
-// The pending visit taken off every node of the chain back_up of pcb_puct.h walks: the same bound, the same checks, so the
+// The pending visit taken off every node of the chain back_up (pcb_tree.h) walks: the same bound, the same checks, so the
 // two walks pass the same nodes and stop at the same one.
 PCB_TREE_HD inline void take_pending(const Root &r, int *pending, int leaf) {
     int cur = leaf;
@@ -132,17 +132,7 @@ PCB_TREE_HD inline unsigned leaves_absorb_one(const Root &r, int *pending, int s
 // back_up and take_pending as ONE walk: what lane 0 of k_puct_leaves runs, where a second walk would be a second chain of
 // dependent loads.  tests/test_puct_leaves_gpu.py holds it to the two walks above in every tensor after every call.
 PCB_TREE_HD inline unsigned leaves_back_up(const Root &r, int *pending, int leaf, double value) {
-    int cur = leaf;
-    for (int i = 0; i <= r.T && cur >= 0; i++) {
-        if (!slot_ok(cur, r.N)) return ERR_TREE;
-        const int up = r.parent[cur];
-        r.visits[cur] = r.visits[cur] + 1;
-        r.value_sum[cur] = r.value_sum[cur] + value;
-        r.value_max[cur] = value > r.value_max[cur] ? value : r.value_max[cur];
-        pending[cur] = one_less(pending[cur]);
-        cur = up;
-    }
-    return 0u;
+    return back_up(r, leaf, value, [pending](int cur) { pending[cur] = one_less(pending[cur]); });
 }
 // The leaves in order.  selected == -1: the leaf is skipped and none of its inputs is read.  A leaf that reports ERR_TREE
 // (selected outside [-1, N), num_nodes out of range, a parent out of range) ends the root's phase.

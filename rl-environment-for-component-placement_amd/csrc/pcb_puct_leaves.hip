@@ -5,10 +5,9 @@
 // k_puct_advance or of the other entry points.
 //
 // The step of one root is pcb_puct_leaves.h (leaves_init, leaves_select, leaves_absorb: the text
-// tools/puct_leaves_check.cpp replays on the CPU); the kernel composes the same pieces with k_puct_advance's mapping: a
-// group of G lanes per root, G the power of two >= max(C, 4), child c of the current node in lane c, the argmax a shuffle
-// butterfly.  Groups share nothing: no LDS, no barrier, and a group whose root does not exist exits whole.  The L leaves
-// of a root run one after the other inside its group.
+// tools/puct_leaves_check.cpp replays on the CPU); the kernel composes the same pieces with a group of G lanes per root
+// (pcb_group.h: the mapping, the phases, the fence), child c of the current node in lane c as in k_puct_advance.  The L
+// leaves of a root run one after the other inside its group.
 //   select   lo, hi, c_puct and the root's own fields stay in registers across the leaves.  Per level ONE load round trip:
 //            lane c loads, next to what the score of child c needs (visits, pending, value_sum, prior), that child's
 //            terminal, num_children, first_child and action, so that the winner's are at hand -- a shuffle from its lane
@@ -20,11 +19,11 @@
 //            across the leaves; the next leaf's `selected` is loaded while the current one is taken.
 //   init     the slots of a root are contiguous: the lanes stride them.
 // A leaf reads what the leaf before it stored through other lanes of the same wavefront -- pending in SELECT, the tree in
-// ABSORB -- as a later phase reads an earlier one's: a wavefront-scope fence between leaves and between phases keeps the
-// compiler from moving those loads up; the memory operations of one wavefront reach the cache in order.
+// ABSORB -- as a later phase reads an earlier one's: the same fence stands between leaves as between phases.
 #include <hip/hip_runtime.h>
 
-#include "pcb_host.h"
+#include "pcb_group.h"
+#include "pcb_tree_host.h"
 #include "pcbenv_leaves.h"
 #include "pcb_puct_leaves.h"
 
@@ -37,7 +36,7 @@ static_assert(sizeof(pcbenv_puct_leaves_request) == 240 && offsetof(pcbenv_puct_
 namespace {
 
 using namespace pcb_puct_leaves;
-constexpr int BLOCK = 256;
+using pcb_group::BLOCK;
 
 // what the kernel needs of a request
 struct LeavesArgs {
@@ -55,14 +54,6 @@ struct LeavesArgs {
     const float *cand_prior;
     unsigned *errors;
 };
-
-__device__ inline Root root_of_group(const LeavesArgs &a, int p) {
-    const long long s = (long long)p * a.N;
-    return Root{a.N, a.C, a.T, a.P, p, a.num_nodes + p, a.parent + s, a.depth + s, a.visits + s, a.num_children + s, a.first_child + s,
-                a.node_action + 3 * s, a.prior + s, a.value_sum + s, a.value_max + s, a.terminal + s, a.lo + p, a.hi + p};
-}
-
-__device__ inline void leaf_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
 
 template <int G> __device__ inline void init_phase(const Root &r, int *pending, int lane) {
     for (int s = lane; s < r.N; s += G) { init_slot(r, s); pending[s] = 0; }
@@ -82,7 +73,7 @@ template <int G> __device__ inline unsigned absorb_phase(const Root &r, const Le
         if (l + 1 < a.L) next = a.selected[row + 1];
         if (selected == -1) continue;
         if (!slot_ok(selected, r.N) || count < 1 || count > r.N) { err |= ERR_TREE; break; }
-        if (l > 0) leaf_fence();
+        if (l > 0) pcb_group::fence();
         const int node = selected, depth = r.depth[node], nch = r.num_children[node], term = r.terminal[node];
         const int leaf_terminal = a.leaf_terminal[row], cand_count = a.cand_count[row];
         const double value = a.value[row];
@@ -119,7 +110,7 @@ template <int G> __device__ inline unsigned select_phase(const Root &r, const Le
     int pend0 = pending[0];
     int l = 0;
     for (; l < a.L; l++) {
-        if (l > 0) leaf_fence();
+        if (l > 0) pcb_group::fence();
         const int row = row0 + l;
         int node = 0, d = 0, term = term0, k = k0, fc = fc0, vis = vis0, pend = pend0;
         for (;; d++) {
@@ -130,15 +121,7 @@ template <int G> __device__ inline unsigned select_phase(const Root &r, const Le
             const int vis_c = r.visits[ch], pend_c = pending[ch], term_c = r.terminal[ch], k_c = r.num_children[ch], fc_c = r.first_child[ch];
             const int a0 = r.node_action[3 * ch], a1 = r.node_action[3 * ch + 1], a2 = r.node_action[3 * ch + 2];
             double s = mine ? leaves_score(r.value_sum[ch], vis_c, pend_c, r.prior[ch], lo, hi, c_puct, vis, pend) : neg_inf();
-            int c = mine ? lane : MAX_CHILDREN + lane;  // a lane without a child loses against any child, whatever its score
-            #pragma unroll
-            for (int o = G / 2; o > 0; o >>= 1) {
-                const double so = __shfl_xor(s, o);
-                const int co = __shfl_xor(c, o);
-                const bool other = co < MAX_CHILDREN && (c >= MAX_CHILDREN || beats(so, co, s, c));
-                s = other ? so : s;
-                c = other ? co : c;
-            }
+            PCB_GROUP_ARGMAX(G, mine, lane, s, c, beats)
             const int win = __shfl(c, base) & (G - 1);  // lane 0's verdict: one node per group whatever the scores were
             if (lane == 0) pending[node] = one_more(pend);
             if (lane == win) {
@@ -162,78 +145,35 @@ template <int G> __device__ inline unsigned select_phase(const Root &r, const Le
 }
 
 template <int G> __global__ __launch_bounds__(BLOCK) void k_puct_leaves(const LeavesArgs a) {
-    static_assert(G >= 4 && G <= 64 && (G & (G - 1)) == 0, "a group is a power-of-two part of a wavefront");
-    const unsigned p = blockIdx.x * (BLOCK / G) + threadIdx.x / G;
-    if (p >= (unsigned)a.P) return;
-    const int lane = threadIdx.x % G, base = (threadIdx.x & 63) - lane;
-    const Root r = root_of_group(a, (int)p);
+    PCB_GROUP_ENTER(G, a);
+    const Root r = root_of_group(a, (int)p, a.T);
     int *const pending = a.pending + (long long)p * a.N;
-    unsigned err = 0u;
-    if (a.phases & PHASE_INIT) {
-        init_phase<G>(r, pending, lane);
-        leaf_fence();
-    }
-    if (a.phases & PHASE_ABSORB) {
-        err |= absorb_phase<G>(r, a, pending, lane, base);
-        leaf_fence();
-    }
-    if (a.phases & PHASE_SELECT) err |= select_phase<G>(r, a, pending, lane, base);
-    if (err != 0u && lane == 0 && a.errors) atomicOr(a.errors, err);
+    PCB_GROUP_PHASES(a, init_phase<G>(r, pending, lane), absorb_phase<G>(r, a, pending, lane, base), select_phase<G>(r, a, pending, lane, base));
 }
-
-int group_lanes(int C) { int g = 4; while (g < C) g <<= 1; return g; }
 
 }  // namespace
 
 // ---- pcbenv_puct_advance_leaves ----------------------------------------------------------------------------------
 // As pcbenv_puct_advance: every argument check before a device is touched, the null handle last; then one launch.
 extern "C" int pcbenv_puct_advance_leaves(const pcbenv *cenv, const pcbenv_puct_leaves_request *q) {
+    using namespace pcb_tree_host;
     pcbenv *env = const_cast<pcbenv *>(cenv);  // the error text only
-    if (!q) return fail(env, PCBENV_EINVAL, "null request");
-    if (q->struct_size != (uint32_t)sizeof(pcbenv_puct_leaves_request)) return fail(env, PCBENV_EINVAL, "struct_size is not sizeof(pcbenv_puct_leaves_request)");
-    const int ph = q->phases;
-    const bool init = ph & PCBENV_TREE_INIT, absorb = ph & PCBENV_TREE_ABSORB, select = ph & PCBENV_TREE_SELECT;
-    if (ph == 0 || (ph & ~(PCBENV_TREE_INIT | PCBENV_TREE_ABSORB | PCBENV_TREE_SELECT)) != 0) return fail(env, PCBENV_EINVAL, "phases must be a non-empty set of INIT, ABSORB, SELECT");
-    if (init && absorb) return fail(env, PCBENV_EINVAL, "phases: INIT cannot be combined with ABSORB");
-    if (q->num_roots < 0) return fail(env, PCBENV_EINVAL, "num_roots must not be negative");
-    if (q->capacity < 1) return fail(env, PCBENV_EINVAL, "capacity must be at least 1");
-    if (q->max_children < 1 || q->max_children > PCBENV_MAX_TREE_CHILDREN) return fail(env, PCBENV_EINVAL, "max_children must be in [1, 64]");
-    if (q->max_steps < 1) return fail(env, PCBENV_EINVAL, "max_steps must be at least 1");
+    PCB_TRY(check_search_request(env, q, "pcbenv_puct_leaves_request"));
+    const Phases ph = phases_of(q->phases);
     if (q->num_leaves < 1 || q->num_leaves > PCBENV_MAX_PUCT_LEAVES) return fail(env, PCBENV_EINVAL, "num_leaves must be in [1, 64]");
     if ((long long)q->num_roots * q->num_leaves > 0x7fffffffLL) return fail(env, PCBENV_EINVAL, "num_roots * num_leaves must not exceed 2^31 - 1");
-    if (absorb && q->num_candidates < 1) return fail(env, PCBENV_EINVAL, "num_candidates must be at least 1 with ABSORB");
+    PCB_TRY(check_puct_candidates(env, q, ph));
     if (q->reserved != 0 || q->reserved2 != 0) return fail(env, PCBENV_EINVAL, "reserved and reserved2 must be 0");
-    if (!q->num_nodes || !q->parent || !q->depth || !q->visits || !q->num_children || !q->first_child || !q->node_action || !q->prior ||
-        !q->value_sum || !q->value_max || !q->terminal || !q->reward_lo || !q->reward_hi || !q->pending) return fail(env, PCBENV_EINVAL, "null tree tensor");
-    if ((absorb || select) && !q->selected) return fail(env, PCBENV_EINVAL, "null selected");
-    if (select && (!q->path_len || !q->paths)) return fail(env, PCBENV_EINVAL, "null path_len or paths with SELECT");
-    if (absorb && (!q->value || !q->leaf_terminal || !q->cand_count || !q->cand_actions || !q->cand_prior))
-        return fail(env, PCBENV_EINVAL, "null value, leaf_terminal, cand_count, cand_actions or cand_prior with ABSORB");
-    const uintptr_t doubles = (uintptr_t)q->prior | (uintptr_t)q->value_sum | (uintptr_t)q->value_max | (uintptr_t)q->reward_lo |
-                              (uintptr_t)q->reward_hi | (absorb ? (uintptr_t)q->value : 0);
-    if ((doubles & 7u) != 0) return fail(env, PCBENV_EINVAL, "the float64 tensors must be 8-byte aligned");
-    if (absorb && ((uintptr_t)q->cand_prior & 3u) != 0) return fail(env, PCBENV_EINVAL, "cand_prior must be 4-byte aligned");
-    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
-    if (q->num_roots == 0) return PCBENV_OK;
-    DEVICE_GUARD(env);
+    PCB_TRY(check_puct_tree(env, q, !q->pending));
+    PCB_TRY(check_exchange(env, q, ph));
+    PCB_TRY(check_puct_inputs(env, q, ph));
+    PCB_TRY(check_puct_doubles(env, q, ph.absorb ? q->value : 0));
+    PCB_TRY(check_cand_prior(env, q, ph));
+    PCB_TREE_CHECKS_END(env, q);
     LeavesArgs a;
-    a.phases = ph; a.P = q->num_roots; a.N = q->capacity; a.C = q->max_children; a.T = q->max_steps; a.K = q->num_candidates; a.L = q->num_leaves;
-    a.c_puct = q->c_puct;
-    a.num_nodes = q->num_nodes; a.parent = q->parent; a.depth = q->depth; a.visits = q->visits; a.num_children = q->num_children;
-    a.first_child = q->first_child; a.node_action = q->node_action; a.prior = q->prior; a.value_sum = q->value_sum; a.value_max = q->value_max;
-    a.terminal = q->terminal; a.lo = q->reward_lo; a.hi = q->reward_hi; a.pending = q->pending; a.selected = q->selected; a.path_len = q->path_len;
-    a.paths = q->paths; a.value = q->value; a.leaf_terminal = q->leaf_terminal; a.cand_count = q->cand_count; a.cand_actions = q->cand_actions;
-    a.cand_prior = q->cand_prior; a.errors = (unsigned *)q->errors_dev;
-    const int G = group_lanes(a.C);
-    const unsigned grid = (unsigned)(((long long)a.P + BLOCK / G - 1) / (BLOCK / G));
-    hipStream_t s = (hipStream_t)q->stream;
-    switch (G) {
-    case 4: hipLaunchKernelGGL(k_puct_leaves<4>, dim3(grid), dim3(BLOCK), 0, s, a); break;
-    case 8: hipLaunchKernelGGL(k_puct_leaves<8>, dim3(grid), dim3(BLOCK), 0, s, a); break;
-    case 16: hipLaunchKernelGGL(k_puct_leaves<16>, dim3(grid), dim3(BLOCK), 0, s, a); break;
-    case 32: hipLaunchKernelGGL(k_puct_leaves<32>, dim3(grid), dim3(BLOCK), 0, s, a); break;
-    default: hipLaunchKernelGGL(k_puct_leaves<64>, dim3(grid), dim3(BLOCK), 0, s, a); break;
-    }
+    puct_search_args(a, q);
+    a.L = q->num_leaves; a.pending = q->pending;
+    PCB_GROUP_LAUNCH(k_puct_leaves, a, (hipStream_t)q->stream);
     HIP_TRY(env, hipGetLastError());
     return PCBENV_OK;
 }

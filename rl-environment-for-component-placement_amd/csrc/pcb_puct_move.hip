@@ -30,7 +30,8 @@
 // be done before its stores: a wavefront-scope fence between them keeps the compiler from moving loads across.
 #include <hip/hip_runtime.h>
 
-#include "pcb_host.h"
+#include "pcb_group.h"
+#include "pcb_tree_host.h"
 #include "pcbenv_move.h"
 #include "pcb_puct_move.h"
 
@@ -43,7 +44,9 @@ static_assert(sizeof(pcbenv_puct_move_request) == 224 && offsetof(pcbenv_puct_mo
 namespace {
 
 using namespace pcb_move;
-constexpr int BLOCK = 256, LANES = 64, UNROLL = 4, SPAN = UNROLL * LANES;  // a lane holds UNROLL slots of a span at a time
+using pcb_group::BLOCK;
+using pcb_group::fence;
+constexpr int LANES = 64, UNROLL = 4, SPAN = UNROLL * LANES;  // a lane holds UNROLL slots of a span at a time
 static_assert(MAX_CHILDREN <= LANES, "one lane per child of the root");
 
 // what the kernel needs of a request
@@ -60,13 +63,6 @@ struct MoveArgs {
     const uint8_t *reset;
     unsigned *errors;
 };
-
-__device__ inline Root root_of_wave(const MoveArgs &a, int p) {
-    const long long s = (long long)p * a.N;
-    return Root{a.N, a.C, 0, a.P, p, a.num_nodes + p, a.parent + s, a.depth + s, a.visits + s, a.num_children + s, a.first_child + s,
-                a.node_action + 3 * s, a.prior + s, a.value_sum + s, a.value_max + s, a.terminal + s, a.lo + p, a.hi + p};
-}
-__device__ inline void fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
 
 // move_choose, child first_child(0) + c in lane c; returns move_slot (the same in every lane)
 __device__ inline int choose_phase(const Root &r, const MoveArgs &a, int lane, unsigned *err) {
@@ -86,14 +82,8 @@ __device__ inline int choose_phase(const Root &r, const MoveArgs &a, int lane, u
         #pragma unroll
         for (int i = 0; i < 3; i++) a.child_actions[3 * row + i] = act[i];
     }
-    int bv = v, bc = mine ? lane : MAX_CHILDREN + lane;  // a lane without a child loses against any child
-    #pragma unroll
-    for (int o = LANES / 2; o > 0; o >>= 1) {
-        const int vo = __shfl_xor(bv, o), co = __shfl_xor(bc, o);
-        const bool other = co < MAX_CHILDREN && (bc >= MAX_CHILDREN || more_visits(vo, co, bv, bc));
-        bv = other ? vo : bv;
-        bc = other ? co : bc;
-    }
+    int bv = v;
+    PCB_GROUP_ARGMAX(LANES, mine, lane, bv, bc, more_visits)
     bc = __shfl(bc, 0);
     long long prefix = v;
     #pragma unroll
@@ -243,7 +233,7 @@ __global__ __launch_bounds__(BLOCK) void k_puct_move(const MoveArgs a) {
     const unsigned p = blockIdx.x * (BLOCK / LANES) + threadIdx.x / LANES;
     if (p >= (unsigned)a.P) return;
     const int lane = threadIdx.x % LANES;
-    const Root r = root_of_wave(a, (int)p);
+    const Root r = pcb_puct::root_of_group(a, (int)p, 0);
     unsigned err = 0u;
     int m = 0;
     if (a.phases & PHASE_CHOOSE) {
@@ -259,37 +249,27 @@ __global__ __launch_bounds__(BLOCK) void k_puct_move(const MoveArgs a) {
 // ---- pcbenv_puct_move --------------------------------------------------------------------------------------------
 // As pcbenv_puct_advance: every argument check before a device is touched, the null handle last; then one launch.
 extern "C" int pcbenv_puct_move(const pcbenv *cenv, const pcbenv_puct_move_request *q) {
+    using namespace pcb_tree_host;
     pcbenv *env = const_cast<pcbenv *>(cenv);  // the error text only
-    if (!q) return fail(env, PCBENV_EINVAL, "null request");
-    if (q->struct_size != (uint32_t)sizeof(pcbenv_puct_move_request)) return fail(env, PCBENV_EINVAL, "struct_size is not sizeof(pcbenv_puct_move_request)");
+    PCB_TRY(check_request(env, q, "pcbenv_puct_move_request"));
     const int ph = q->phases;
     const bool choose = ph & PCBENV_MOVE_CHOOSE, reroot = ph & PCBENV_MOVE_REROOT;
     if (ph == 0 || (ph & ~(PCBENV_MOVE_CHOOSE | PCBENV_MOVE_REROOT)) != 0) return fail(env, PCBENV_EINVAL, "phases must be a non-empty set of CHOOSE, REROOT");
     if (choose && q->mode != PCBENV_MOVE_GREEDY && q->mode != PCBENV_MOVE_PROPORTIONAL) return fail(env, PCBENV_EINVAL, "unknown mode");
-    if (q->num_roots < 0) return fail(env, PCBENV_EINVAL, "num_roots must not be negative");
-    if (q->capacity < 1) return fail(env, PCBENV_EINVAL, "capacity must be at least 1");
-    if (q->max_children < 1 || q->max_children > PCBENV_MAX_TREE_CHILDREN) return fail(env, PCBENV_EINVAL, "max_children must be in [1, 64]");
+    PCB_TRY(check_extents(env, q));
     if (q->reserved != 0) return fail(env, PCBENV_EINVAL, "reserved must be 0");
-    if (!q->num_nodes || !q->parent || !q->depth || !q->visits || !q->num_children || !q->first_child || !q->node_action || !q->prior ||
-        !q->value_sum || !q->value_max || !q->terminal || !q->reward_lo || !q->reward_hi) return fail(env, PCBENV_EINVAL, "null tree tensor");
+    PCB_TRY(check_puct_tree(env, q));
     if (!q->move_slot) return fail(env, PCBENV_EINVAL, "null move_slot");
     if (choose && (!q->move_action || !q->child_visits || !q->child_actions || !q->root_value))
         return fail(env, PCBENV_EINVAL, "null move_action, child_visits, child_actions or root_value with CHOOSE");
     if (reroot && !q->remap) return fail(env, PCBENV_EINVAL, "null remap with REROOT");
-    const uintptr_t doubles = (uintptr_t)q->prior | (uintptr_t)q->value_sum | (uintptr_t)q->value_max | (uintptr_t)q->reward_lo |
-                              (uintptr_t)q->reward_hi | (choose ? (uintptr_t)q->root_value : 0);
-    if ((doubles & 7u) != 0) return fail(env, PCBENV_EINVAL, "the float64 tensors must be 8-byte aligned");
-    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
-    if (q->num_roots == 0) return PCBENV_OK;
-    DEVICE_GUARD(env);
+    PCB_TRY(check_puct_doubles(env, q, choose ? q->root_value : 0));
+    PCB_TREE_CHECKS_END(env, q);
     MoveArgs a;
-    a.phases = ph; a.P = q->num_roots; a.N = q->capacity; a.C = q->max_children; a.mode = q->mode; a.first_root = q->first_root;
-    a.seed = q->seed; a.step_index = q->step_index;
-    a.num_nodes = q->num_nodes; a.parent = q->parent; a.depth = q->depth; a.visits = q->visits; a.num_children = q->num_children;
-    a.first_child = q->first_child; a.node_action = q->node_action; a.prior = q->prior; a.value_sum = q->value_sum; a.value_max = q->value_max;
-    a.terminal = q->terminal; a.lo = q->reward_lo; a.hi = q->reward_hi; a.move_slot = q->move_slot; a.move_action = q->move_action;
-    a.child_visits = q->child_visits; a.child_actions = q->child_actions; a.root_value = q->root_value; a.remap = q->remap; a.reset = q->reset;
-    a.errors = (unsigned *)q->errors_dev;
+    puct_tree_args(a, q);
+    a.mode = q->mode; a.first_root = q->first_root; a.seed = q->seed; a.step_index = q->step_index;
+    a.move_slot = q->move_slot; a.move_action = q->move_action; a.child_visits = q->child_visits; a.child_actions = q->child_actions;
+    a.root_value = q->root_value; a.remap = q->remap; a.reset = q->reset;
     const unsigned grid = (unsigned)(((long long)a.P + BLOCK / LANES - 1) / (BLOCK / LANES));
     hipLaunchKernelGGL(k_puct_move, dim3(grid), dim3(BLOCK), 0, (hipStream_t)q->stream, a);
     HIP_TRY(env, hipGetLastError());

@@ -124,8 +124,9 @@ PCB_TREE_HD inline void make_child(const Root &r, int node, int slot, int depth,
     r.num_children[node] = nch + 1;
     *r.num_nodes = slot + 1;
 }
-// visits, value_sum and value_max of the leaf and every ancestor: at most T + 1 nodes
-PCB_TREE_HD inline unsigned back_up(const Root &r, int leaf, double reward) {
+// visits, value_sum and value_max of the leaf and every ancestor: at most T + 1 nodes.  The one backup walk of every tree
+// here (R: this Root or pcb_puct.h's); also(cur): what else the walk does at a node (pcb_puct_leaves.h: its pending visit).
+template <class R, class Also> PCB_TREE_HD inline unsigned back_up(const R &r, int leaf, double reward, Also also) {
     int cur = leaf;
     for (int i = 0; i <= r.T && cur >= 0; i++) {
         if (!slot_ok(cur, r.N)) return ERR_TREE;
@@ -133,10 +134,12 @@ PCB_TREE_HD inline unsigned back_up(const Root &r, int leaf, double reward) {
         r.visits[cur] = r.visits[cur] + 1;
         r.value_sum[cur] = r.value_sum[cur] + reward;
         r.value_max[cur] = reward > r.value_max[cur] ? reward : r.value_max[cur];
+        also(cur);
         cur = up;
     }
     return 0u;
 }
+template <class R> PCB_TREE_HD inline unsigned back_up(const R &r, int leaf, double reward) { return back_up(r, leaf, reward, [](int) {}); }
 PCB_TREE_HD inline int rows_to_copy(int length, int T) { return length < 0 ? 0 : length > T ? T : length; }
 
 // reward, length, actions [T, P, 3]: what the playout from `selected` returned for this root.

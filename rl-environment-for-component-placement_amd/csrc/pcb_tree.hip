@@ -4,9 +4,8 @@
 // nothing here can change the builds of the other kernels or of the other entry points.
 //
 // The step of one root is pcb_tree.h (tree_init, tree_select, tree_absorb: the text tools/tree_model_check.cpp replays on
-// the CPU); the kernel composes the same pieces with a group of G lanes per root, G the power of two >= max(C, 4), so a
-// wavefront carries 64 / G roots and a 256-thread workgroup 256 / G.  Groups share nothing: no LDS, no barrier, and a
-// group whose root does not exist exits whole.
+// the CPU); the kernel composes the same pieces with a group of G lanes per root: the mapping, the phases and the fence
+// between them are pcb_group.h's.  What a lane loads and stores:
 //   select   lane c of the group owns child slot c of the current node.  Per level two load round trips: the node's flags,
 //            its visits and the lane's child slot together, then the child's visits and value_sum and ln[visits(node)]
 //            together.  The group argmax (pcb_tree::beats: the lowest slot on ties) is a shuffle butterfly; the winner's
@@ -15,12 +14,10 @@
 //            child and walks the backup chain -- one round trip per level: a node's parent, visits, value_sum and
 //            value_max are loaded together.  The best_actions copy is spread over the group.
 //   init     the slots and the child entries of a root are contiguous: the lanes stride them.
-// A later phase of one launch reads what an earlier one stored through other lanes of the same wavefront; a
-// wavefront-scope fence between the phases keeps the compiler from moving those loads up.
 #include <hip/hip_runtime.h>
 
-#include "pcb_host.h"
-#include "pcb_tree.h"
+#include "pcb_group.h"
+#include "pcb_tree_host.h"
 
 static_assert(PCBENV_TREE_INIT == pcb_tree::PHASE_INIT && PCBENV_TREE_ABSORB == pcb_tree::PHASE_ABSORB &&
               PCBENV_TREE_SELECT == pcb_tree::PHASE_SELECT && PCBENV_MAX_TREE_CHILDREN == pcb_tree::MAX_CHILDREN,
@@ -30,7 +27,8 @@ static_assert(sizeof(pcbenv_tree_request) == 224 && offsetof(pcbenv_tree_request
 namespace {
 
 using namespace pcb_tree;
-constexpr int BLOCK = 256;
+using pcb_group::BLOCK;
+using pcb_group::group_ballot;
 
 // what the kernel needs of a request
 struct TreeArgs {
@@ -52,13 +50,6 @@ __device__ inline Root root_of_group(const TreeArgs &a, int p) {
     return Root{a.N, a.C, a.T, a.P, p, a.num_nodes + p, a.parent + s, a.depth + s, a.visits + s, a.num_children + s,
                 a.node_action + 3 * s, a.children + s * a.C, a.value_sum + s, a.value_max + s, a.terminal + s,
                 a.lo + p, a.hi + p, a.best_reward + p, a.best_length + p, a.best_actions};
-}
-
-// the ballot of this lane's group, bit c = lane c of the group
-template <int G> __device__ inline unsigned long long group_ballot(bool v, int base) {
-    const unsigned long long b = __ballot(v);
-    if constexpr (G == 64) return b;
-    else return (b >> base) & ((1ull << G) - 1ull);
 }
 
 template <int G> __device__ inline void init_phase(const Root &r, int lane) {
@@ -131,15 +122,7 @@ template <int G> __device__ inline unsigned select_phase(const Root &r, const Tr
         const int n_p = at_least_1(vis);
         const double ln_p = a.ln[n_p > r.N ? r.N : n_p];
         double s = mine ? uct_score(r.value_sum[ch], r.visits[ch], lo, hi, a.c_uct, ln_p) : neg_inf();
-        int c = mine ? lane : MAX_CHILDREN + lane;  // a lane without a child loses against any child, whatever its score
-        #pragma unroll
-        for (int o = G / 2; o > 0; o >>= 1) {
-            const double so = __shfl_xor(s, o);
-            const int co = __shfl_xor(c, o);
-            const bool other = co < MAX_CHILDREN && (c >= MAX_CHILDREN || beats(so, co, s, c));
-            s = other ? so : s;
-            c = other ? co : c;
-        }
+        PCB_GROUP_ARGMAX(G, mine, lane, s, c, beats)
         node = __shfl(ch, base + __shfl(c, base));  // lane 0's verdict: one node per group whatever the scores were
         if (lane < 3) a.paths[step_major(d, r.P, r.p, lane)] = r.node_action[3 * node + lane];
     }
@@ -148,74 +131,40 @@ template <int G> __device__ inline unsigned select_phase(const Root &r, const Tr
 }
 
 template <int G> __global__ __launch_bounds__(BLOCK) void k_tree_advance(const TreeArgs a) {
-    static_assert(G >= 4 && G <= 64 && (G & (G - 1)) == 0, "a group is a power-of-two part of a wavefront");
-    const unsigned p = blockIdx.x * (BLOCK / G) + threadIdx.x / G;
-    if (p >= (unsigned)a.P) return;
-    const int lane = threadIdx.x % G, base = (threadIdx.x & 63) - lane;
+    PCB_GROUP_ENTER(G, a);
     const Root r = root_of_group(a, (int)p);
-    unsigned err = 0u;
-    if (a.phases & PHASE_INIT) {
-        init_phase<G>(r, lane);
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    }
-    if (a.phases & PHASE_ABSORB) {
-        err |= absorb_phase<G>(r, a, lane, base);
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    }
-    if (a.phases & PHASE_SELECT) err |= select_phase<G>(r, a, lane, base);
-    if (err != 0u && lane == 0 && a.errors) atomicOr(a.errors, err);
+    PCB_GROUP_PHASES(a, init_phase<G>(r, lane), absorb_phase<G>(r, a, lane, base), select_phase<G>(r, a, lane, base));
 }
-
-int group_lanes(int C) { int g = 4; while (g < C) g <<= 1; return g; }
 
 }  // namespace
 
 // ---- pcbenv_tree_advance -----------------------------------------------------------------------------------------
 // As pcbenv_playout_paths: every argument check before a device is touched, the null handle last; then one launch.
 extern "C" int pcbenv_tree_advance(const pcbenv *cenv, const pcbenv_tree_request *q) {
+    using namespace pcb_tree_host;
     pcbenv *env = const_cast<pcbenv *>(cenv);  // the error text only
-    if (!q) return fail(env, PCBENV_EINVAL, "null request");
-    if (q->struct_size != (uint32_t)sizeof(pcbenv_tree_request)) return fail(env, PCBENV_EINVAL, "struct_size is not sizeof(pcbenv_tree_request)");
-    const int ph = q->phases;
-    const bool init = ph & PCBENV_TREE_INIT, absorb = ph & PCBENV_TREE_ABSORB, select = ph & PCBENV_TREE_SELECT;
-    if (ph == 0 || (ph & ~(PCBENV_TREE_INIT | PCBENV_TREE_ABSORB | PCBENV_TREE_SELECT)) != 0) return fail(env, PCBENV_EINVAL, "phases must be a non-empty set of INIT, ABSORB, SELECT");
-    if (init && absorb) return fail(env, PCBENV_EINVAL, "phases: INIT cannot be combined with ABSORB");
-    if (q->num_roots < 0) return fail(env, PCBENV_EINVAL, "num_roots must not be negative");
-    if (q->capacity < 1) return fail(env, PCBENV_EINVAL, "capacity must be at least 1");
-    if (q->max_children < 1 || q->max_children > PCBENV_MAX_TREE_CHILDREN) return fail(env, PCBENV_EINVAL, "max_children must be in [1, 64]");
-    if (q->max_steps < 1) return fail(env, PCBENV_EINVAL, "max_steps must be at least 1");
+    PCB_TRY(check_search_request(env, q, "pcbenv_tree_request"));
+    const Phases ph = phases_of(q->phases);
     if (!q->num_nodes || !q->parent || !q->depth || !q->visits || !q->num_children || !q->node_action || !q->children ||
         !q->value_sum || !q->value_max || !q->terminal || !q->reward_lo || !q->reward_hi) return fail(env, PCBENV_EINVAL, "null tree tensor");
-    if ((init || absorb) && (!q->best_reward || !q->best_length)) return fail(env, PCBENV_EINVAL, "null tree tensor");
-    if (absorb && !q->best_actions) return fail(env, PCBENV_EINVAL, "null tree tensor");
-    if ((absorb || select) && !q->selected) return fail(env, PCBENV_EINVAL, "null selected");
-    if (select && (!q->path_len || !q->paths)) return fail(env, PCBENV_EINVAL, "null path_len or paths with SELECT");
-    if (select && !q->ln_dev) return fail(env, PCBENV_EINVAL, "null ln with SELECT");
-    if (absorb && (!q->reward || !q->length || !q->actions)) return fail(env, PCBENV_EINVAL, "null reward, length or actions with ABSORB");
+    if ((ph.init || ph.absorb) && (!q->best_reward || !q->best_length)) return fail(env, PCBENV_EINVAL, "null tree tensor");
+    if (ph.absorb && !q->best_actions) return fail(env, PCBENV_EINVAL, "null tree tensor");
+    PCB_TRY(check_exchange(env, q, ph));
+    if (ph.select && !q->ln_dev) return fail(env, PCBENV_EINVAL, "null ln with SELECT");
+    if (ph.absorb && (!q->reward || !q->length || !q->actions)) return fail(env, PCBENV_EINVAL, "null reward, length or actions with ABSORB");
     const uintptr_t doubles = (uintptr_t)q->ln_dev | (uintptr_t)q->value_sum | (uintptr_t)q->value_max | (uintptr_t)q->reward_lo |
                               (uintptr_t)q->reward_hi | (uintptr_t)q->best_reward | (uintptr_t)q->reward;
     if ((doubles & 7u) != 0) return fail(env, PCBENV_EINVAL, "ln and the float64 tensors must be 8-byte aligned");
-    if (!env) return fail(0, PCBENV_EINVAL, "null handle");
-    if (q->num_roots == 0) return PCBENV_OK;
-    DEVICE_GUARD(env);
+    PCB_TREE_CHECKS_END(env, q);
     TreeArgs a;
-    a.phases = ph; a.P = q->num_roots; a.N = q->capacity; a.C = q->max_children; a.T = q->max_steps;
+    a.phases = q->phases; a.P = q->num_roots; a.N = q->capacity; a.C = q->max_children; a.T = q->max_steps;
     a.c_uct = q->c_uct; a.ln = q->ln_dev;
     a.num_nodes = q->num_nodes; a.parent = q->parent; a.depth = q->depth; a.visits = q->visits; a.num_children = q->num_children;
     a.node_action = q->node_action; a.children = q->children; a.value_sum = q->value_sum; a.value_max = q->value_max;
     a.terminal = q->terminal; a.lo = q->reward_lo; a.hi = q->reward_hi; a.best_reward = q->best_reward;
     a.best_length = q->best_length; a.best_actions = q->best_actions; a.selected = q->selected; a.path_len = q->path_len;
     a.paths = q->paths; a.reward = q->reward; a.length = q->length; a.actions = q->actions; a.errors = (unsigned *)q->errors_dev;
-    const int G = group_lanes(a.C);
-    const unsigned grid = (unsigned)(((long long)a.P + BLOCK / G - 1) / (BLOCK / G));
-    hipStream_t s = (hipStream_t)q->stream;
-    switch (G) {
-    case 4: hipLaunchKernelGGL(k_tree_advance<4>, dim3(grid), dim3(BLOCK), 0, s, a); break;
-    case 8: hipLaunchKernelGGL(k_tree_advance<8>, dim3(grid), dim3(BLOCK), 0, s, a); break;
-    case 16: hipLaunchKernelGGL(k_tree_advance<16>, dim3(grid), dim3(BLOCK), 0, s, a); break;
-    case 32: hipLaunchKernelGGL(k_tree_advance<32>, dim3(grid), dim3(BLOCK), 0, s, a); break;
-    default: hipLaunchKernelGGL(k_tree_advance<64>, dim3(grid), dim3(BLOCK), 0, s, a); break;
-    }
+    PCB_GROUP_LAUNCH(k_tree_advance, a, (hipStream_t)q->stream);
     HIP_TRY(env, hipGetLastError());
     return PCBENV_OK;
 }

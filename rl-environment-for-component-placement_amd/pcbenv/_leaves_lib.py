@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import ctypes as C
 
+from ._lib import bind_exports
 from ._search_lib import PUCT_EXCHANGE, PUCT_INPUTS, PUCT_TREE_TENSORS
 
 EXPORTS = ("pcbenv_puct_advance_leaves",)
@@ -23,9 +24,4 @@ class PcbenvPuctLeavesRequest(C.Structure):
 
 def bind(L):
     """Prototypes of EXPORTS on the loaded library; ImportError if it lacks one (there is no fallback).  Returns L."""
-    missing = [n for n in EXPORTS if not hasattr(L, n)]
-    if missing:
-        raise ImportError(f"libpcbenv.so lacks {missing}: rebuild it with `python rl-environment-for-component-placement_amd/build.py`")
-    L.pcbenv_puct_advance_leaves.argtypes = [C.c_void_p, C.POINTER(PcbenvPuctLeavesRequest)]
-    L.pcbenv_puct_advance_leaves.restype = C.c_int
-    return L
+    return bind_exports(L, {name: PcbenvPuctLeavesRequest for name in EXPORTS})

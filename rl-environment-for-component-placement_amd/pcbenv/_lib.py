@@ -159,6 +159,20 @@ def load():
     return L
 
 
+def bind_exports(L, requests):
+    """Prototypes `int name(handle, const request *)` on the loaded library for `requests`, {export name: request type}:
+    what the bindings of the further headers (`_search_lib`, `_priors_lib`, `_move_lib`, `_train_lib`, `_leaves_lib`)
+    share.  ImportError if the library lacks one (there is no fallback).  Returns L."""
+    missing = [n for n in requests if not hasattr(L, n)]
+    if missing:
+        raise ImportError(f"libpcbenv.so lacks {missing}: rebuild it with `python rl-environment-for-component-placement_amd/build.py`")
+    for name, request in requests.items():
+        f = getattr(L, name)
+        f.argtypes = [C.c_void_p, C.POINTER(request)]
+        f.restype = C.c_int
+    return L
+
+
 def make_config(cfg, num_envs: int, queue_depth: int = 1, flags: int = 0) -> PcbenvConfig:
     c = PcbenvConfig()
     for name, _ in PcbenvConfig._fields_:

@@ -5,6 +5,8 @@ from __future__ import annotations
 
 import ctypes as C
 
+from ._lib import bind_exports
+
 EXPORTS = ("pcbenv_puct_move",)
 
 MOVE_CHOOSE, MOVE_REROOT = 1, 2          # phases
@@ -25,9 +27,4 @@ class PcbenvPuctMoveRequest(C.Structure):
 
 def bind(L):
     """Prototypes of EXPORTS on the loaded library; ImportError if it lacks one (there is no fallback).  Returns L."""
-    missing = [n for n in EXPORTS if not hasattr(L, n)]
-    if missing:
-        raise ImportError(f"libpcbenv.so lacks {missing}: rebuild it with `python rl-environment-for-component-placement_amd/build.py`")
-    L.pcbenv_puct_move.argtypes = [C.c_void_p, C.POINTER(PcbenvPuctMoveRequest)]
-    L.pcbenv_puct_move.restype = C.c_int
-    return L
+    return bind_exports(L, {name: PcbenvPuctMoveRequest for name in EXPORTS})

@@ -5,6 +5,8 @@ from __future__ import annotations
 
 import ctypes as C
 
+from ._lib import bind_exports
+
 EXPORTS = ("pcbenv_top_priors",)
 
 TOP_PRIORS_INPUTS = ("logits", "mask_bits")
@@ -20,9 +22,4 @@ class PcbenvTopPriorsRequest(C.Structure):
 
 def bind(L):
     """Prototypes of EXPORTS on the loaded library; ImportError if it lacks one (there is no fallback).  Returns L."""
-    missing = [n for n in EXPORTS if not hasattr(L, n)]
-    if missing:
-        raise ImportError(f"libpcbenv.so lacks {missing}: rebuild it with `python rl-environment-for-component-placement_amd/build.py`")
-    L.pcbenv_top_priors.argtypes = [C.c_void_p, C.POINTER(PcbenvTopPriorsRequest)]
-    L.pcbenv_top_priors.restype = C.c_int
-    return L
+    return bind_exports(L, {name: PcbenvTopPriorsRequest for name in EXPORTS})

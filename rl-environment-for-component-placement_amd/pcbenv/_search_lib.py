@@ -4,6 +4,8 @@ from __future__ import annotations
 
 import ctypes as C
 
+from ._lib import bind_exports
+
 EXPORTS = ("pcbenv_puct_advance",)
 
 PUCT_TREE_TENSORS = ("num_nodes", "parent", "depth", "visits", "num_children", "first_child", "node_action", "prior", "value_sum", "value_max",
@@ -22,9 +24,4 @@ class PcbenvPuctRequest(C.Structure):
 
 def bind(L):
     """Prototypes of EXPORTS on the loaded library; ImportError if it lacks one (there is no fallback).  Returns L."""
-    missing = [n for n in EXPORTS if not hasattr(L, n)]
-    if missing:
-        raise ImportError(f"libpcbenv.so lacks {missing}: rebuild it with `python rl-environment-for-component-placement_amd/build.py`")
-    L.pcbenv_puct_advance.argtypes = [C.c_void_p, C.POINTER(PcbenvPuctRequest)]
-    L.pcbenv_puct_advance.restype = C.c_int
-    return L
+    return bind_exports(L, {name: PcbenvPuctRequest for name in EXPORTS})

@@ -5,6 +5,8 @@ from __future__ import annotations
 
 import ctypes as C
 
+from ._lib import bind_exports
+
 EXPORTS = ("pcbenv_evaluate_visits", "pcbenv_evaluate_visits_backward")
 
 ROW_OK, ROW_ZERO, ROW_NO_TARGET = 0, 1, 2                 # stats[:, 3]
@@ -24,11 +26,4 @@ class PcbenvVisitsRequest(C.Structure):
 
 def bind(L):
     """Prototypes of EXPORTS on the loaded library; ImportError if it lacks one (there is no fallback).  Returns L."""
-    missing = [n for n in EXPORTS if not hasattr(L, n)]
-    if missing:
-        raise ImportError(f"libpcbenv.so lacks {missing}: rebuild it with `python rl-environment-for-component-placement_amd/build.py`")
-    for name in EXPORTS:
-        f = getattr(L, name)
-        f.argtypes = [C.c_void_p, C.POINTER(PcbenvVisitsRequest)]
-        f.restype = C.c_int
-    return L
+    return bind_exports(L, {name: PcbenvVisitsRequest for name in EXPORTS})

@@ -123,6 +123,23 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def _puct_tree_want(P, N, own, slots=()):
+    """dtype and shape of every tensor of a PUCT tree of P roots with N slots each (include/pcbenv_search.h), in the order
+    the requests check them: the per-root tensors, `own` -- the request's own tensors, name -> (dtype, shape) -- then the
+    [P, N] ones, `slots` naming further int32 ones."""
+    i32, f64 = torch.int32, torch.float64
+    want = {"num_nodes": (i32, (P,)), "node_action": (i32, (P, N, 3)), "terminal": (torch.uint8, (P, N)), "reward_lo": (f64, (P,)),
+            "reward_hi": (f64, (P,)), **own}
+    want.update({n: (i32, (P, N)) for n in ("parent", "depth", "visits", "num_children", "first_child") + tuple(slots)})
+    want.update({n: (f64, (P, N)) for n in ("prior", "value_sum", "value_max")})
+    return want
+
+
+def _exchange_want(T, R):
+    """dtype and shape of what SELECT writes for R rows: `selected`, `path_len` and `paths` of at most T levels."""
+    return {"selected": (torch.int32, (R,)), "path_len": (torch.int32, (R,)), "paths": (torch.int32, (T, R, 3))}
+
+
 class BatchedPlacementEnv:
     is_batched = True
 
@@ -803,6 +820,28 @@ class BatchedPlacementEnv:
             raise IndexError(f"playout: an index is outside [0, {self.num_envs}) (those playouts report length 0)")
         return Playout(reward, done, length, info, actions)
 
+    def _tree_request(self, Request, tree, want, **scalars):
+        """A `Request` with `scalars` and the address of every tensor `want` names (name -> (dtype, shape)) taken from `tree`
+        after `check_tensor`; `errors_dev` is optional."""
+        if tree.get("errors_dev") is not None:
+            want["errors_dev"] = (torch.int32, (1,))
+        req = Request(struct_size=C.sizeof(Request), **scalars)
+        for name, (dtype, shape) in want.items():
+            check_tensor(self.device, name, tree[name], dtype, shape)
+            setattr(req, name, _ptr(tree[name]))
+        return req
+
+    def _advance(self, call, req, phases, inputs) -> None:
+        """One launch of a tree entry point: `phases` and the optional tensors of this call, `inputs` = (name, tensor or
+        None, dtype, shape) ..., into `req`, then the library's `call` on the current stream."""
+        req.phases = int(phases)
+        for name, t, dtype, shape in inputs:
+            if t is not None:
+                check_tensor(self.device, name, t, dtype, shape)
+            setattr(req, name, _ptr(t))
+        req.stream = self._stream().value
+        _lib.check(call(self._h, C.byref(req)), self._h)
+
     def tree_request(self, tree: Dict[str, torch.Tensor], c_uct: float = 1.0) -> "_lib.PcbenvTreeRequest":
         """The request of `tree_advance` for the tensors in `tree` (see `pcbenv.search.new_tree` for a set of the right
         shapes): the keys are the members of pcbenv_tree_request -- `ln_dev`, the tree tensors `num_nodes` ... `best_actions`,
@@ -817,16 +856,8 @@ class BatchedPlacementEnv:
         want = {"ln_dev": (f64, (N + 1,)), "num_nodes": (i32, (P,)), "parent": (i32, (P, N)), "depth": (i32, (P, N)), "visits": (i32, (P, N)),
                 "num_children": (i32, (P, N)), "node_action": (i32, (P, N, 3)), "children": (i32, (P, N, Cc)), "value_sum": (f64, (P, N)),
                 "value_max": (f64, (P, N)), "terminal": (torch.uint8, (P, N)), "reward_lo": (f64, (P,)), "reward_hi": (f64, (P,)),
-                "best_reward": (f64, (P,)), "best_length": (i32, (P,)), "best_actions": (i32, (T, P, 3)), "selected": (i32, (P,)),
-                "path_len": (i32, (P,)), "paths": (i32, (T, P, 3))}
-        if tree.get("errors_dev") is not None:
-            want["errors_dev"] = (i32, (1,))
-        req = _lib.PcbenvTreeRequest(struct_size=C.sizeof(_lib.PcbenvTreeRequest), num_roots=P, capacity=N, max_children=Cc, max_steps=T,
-                                     c_uct=float(c_uct))
-        for name, (dtype, shape) in want.items():
-            check_tensor(self.device, name, tree[name], dtype, shape)
-            setattr(req, name, _ptr(tree[name]))
-        return req
+                "best_reward": (f64, (P,)), "best_length": (i32, (P,)), "best_actions": (i32, (T, P, 3)), **_exchange_want(T, P)}
+        return self._tree_request(_lib.PcbenvTreeRequest, tree, want, num_roots=P, capacity=N, max_children=Cc, max_steps=T, c_uct=float(c_uct))
 
     def tree_advance(self, req: "_lib.PcbenvTreeRequest", phases: int, reward: Optional[torch.Tensor] = None,
                      length: Optional[torch.Tensor] = None, actions: Optional[torch.Tensor] = None) -> None:
@@ -838,14 +869,16 @@ class BatchedPlacementEnv:
         P, T = req.num_roots, req.max_steps
         if P == 0:  # torch gives empty tensors a null pointer
             return
-        req.phases = int(phases)
-        for name, t, dtype, shape in (("reward", reward, torch.float64, (P,)), ("length", length, torch.int32, (P,)),
-                                      ("actions", actions, torch.int32, (T, P, 3))):
-            if t is not None:
-                check_tensor(self.device, name, t, dtype, shape)
-            setattr(req, name, _ptr(t))
-        req.stream = self._stream().value
-        _lib.check(self._L.pcbenv_tree_advance(self._h, C.byref(req)), self._h)
+        self._advance(self._L.pcbenv_tree_advance, req, phases, (("reward", reward, torch.float64, (P,)), ("length", length, torch.int32, (P,)),
+                                                                 ("actions", actions, torch.int32, (T, P, 3))))
+
+    def _puct_absorb(self, call, req, R, phases, value, leaf_terminal, cand_count, cand_actions, cand_prior) -> None:
+        """`puct_advance` and `puct_advance_leaves` past their empty batch: the ABSORB inputs, R rows of them."""
+        K = int(cand_prior.shape[1]) if isinstance(cand_prior, torch.Tensor) and cand_prior.dim() == 2 else "K"
+        req.num_candidates = K if isinstance(K, int) else 0
+        self._advance(call, req, phases, (("value", value, torch.float64, (R,)), ("leaf_terminal", leaf_terminal, torch.uint8, (R,)),
+                                          ("cand_count", cand_count, torch.int32, (R,)), ("cand_actions", cand_actions, torch.int32, (R, K, 3)),
+                                          ("cand_prior", cand_prior, torch.float32, (R, K))))
 
     def puct_request(self, tree: Dict[str, torch.Tensor], c_puct: float = 1.0, max_children: int = 16) -> "_search_lib.PcbenvPuctRequest":
         """The request of `puct_advance` for the tensors in `tree` (see `pcbenv.search.new_puct_tree` for a set of the right
@@ -854,23 +887,12 @@ class BatchedPlacementEnv:
         dtypes and shapes the header gives; P, N and T are read off `parent` [P, N] and `paths` [T, P, 3], C = max_children
         is an argument (the tree has no tensor with that extent).  The request holds addresses only: the caller keeps the
         tensors alive."""
-        i32, f64 = torch.int32, torch.float64
         par, paths = tree["parent"], tree["paths"]
         if par.dim() != 2 or paths.dim() != 3 or paths.shape[1:] != (par.shape[0], 3):
             raise ValueError(f"parent must be [P, N] and paths [T, P, 3], got {tuple(par.shape)} and {tuple(paths.shape)}")
         (P, N), T = par.shape, paths.shape[0]
-        want = {"num_nodes": (i32, (P,)), "node_action": (i32, (P, N, 3)), "terminal": (torch.uint8, (P, N)), "reward_lo": (f64, (P,)),
-                "reward_hi": (f64, (P,)), "selected": (i32, (P,)), "path_len": (i32, (P,)), "paths": (i32, (T, P, 3))}
-        want.update({n: (i32, (P, N)) for n in ("parent", "depth", "visits", "num_children", "first_child")})
-        want.update({n: (f64, (P, N)) for n in ("prior", "value_sum", "value_max")})
-        if tree.get("errors_dev") is not None:
-            want["errors_dev"] = (i32, (1,))
-        req = _search_lib.PcbenvPuctRequest(struct_size=C.sizeof(_search_lib.PcbenvPuctRequest), num_roots=P, capacity=N,
-                                            max_children=int(max_children), max_steps=T, c_puct=float(c_puct))
-        for name, (dtype, shape) in want.items():
-            check_tensor(self.device, name, tree[name], dtype, shape)
-            setattr(req, name, _ptr(tree[name]))
-        return req
+        return self._tree_request(_search_lib.PcbenvPuctRequest, tree, _puct_tree_want(P, N, _exchange_want(T, P)), num_roots=P, capacity=N,
+                                  max_children=int(max_children), max_steps=T, c_puct=float(c_puct))
 
     def puct_advance(self, req: "_search_lib.PcbenvPuctRequest", phases: int, value: Optional[torch.Tensor] = None,
                      leaf_terminal: Optional[torch.Tensor] = None, cand_count: Optional[torch.Tensor] = None,
@@ -885,17 +907,7 @@ class BatchedPlacementEnv:
         P = req.num_roots
         if P == 0:  # torch gives empty tensors a null pointer
             return
-        req.phases = int(phases)
-        K = int(cand_prior.shape[1]) if isinstance(cand_prior, torch.Tensor) and cand_prior.dim() == 2 else "K"
-        req.num_candidates = K if isinstance(K, int) else 0
-        for name, t, dtype, shape in (("value", value, torch.float64, (P,)), ("leaf_terminal", leaf_terminal, torch.uint8, (P,)),
-                                      ("cand_count", cand_count, torch.int32, (P,)), ("cand_actions", cand_actions, torch.int32, (P, K, 3)),
-                                      ("cand_prior", cand_prior, torch.float32, (P, K))):
-            if t is not None:
-                check_tensor(self.device, name, t, dtype, shape)
-            setattr(req, name, _ptr(t))
-        req.stream = self._stream().value
-        _lib.check(self._L.pcbenv_puct_advance(self._h, C.byref(req)), self._h)
+        self._puct_absorb(self._L.pcbenv_puct_advance, req, P, phases, value, leaf_terminal, cand_count, cand_actions, cand_prior)
 
     def puct_leaves_request(self, tree: Dict[str, torch.Tensor], c_puct: float = 1.0, max_children: int = 16,
                             leaves: int = 1) -> "_leaves_lib.PcbenvPuctLeavesRequest":
@@ -905,25 +917,15 @@ class BatchedPlacementEnv:
         -- on this device, contiguous, of the dtypes and shapes the header gives; P, N and T are read off `parent` [P, N]
         and `paths` [T, P * L, 3], C = max_children and L = leaves are arguments.  The request holds addresses only: the
         caller keeps the tensors alive."""
-        i32, f64 = torch.int32, torch.float64
         par, paths, L = tree["parent"], tree["paths"], int(leaves)
         if L < 1 or L > _leaves_lib.MAX_PUCT_LEAVES:
             raise ValueError(f"leaves must be in [1, {_leaves_lib.MAX_PUCT_LEAVES}], got {L}")
         if par.dim() != 2 or paths.dim() != 3 or paths.shape[1:] != (par.shape[0] * L, 3):
             raise ValueError(f"parent must be [P, N] and paths [T, P * {L}, 3], got {tuple(par.shape)} and {tuple(paths.shape)}")
         (P, N), T = par.shape, paths.shape[0]
-        want = {"num_nodes": (i32, (P,)), "node_action": (i32, (P, N, 3)), "terminal": (torch.uint8, (P, N)), "reward_lo": (f64, (P,)),
-                "reward_hi": (f64, (P,)), "selected": (i32, (P * L,)), "path_len": (i32, (P * L,)), "paths": (i32, (T, P * L, 3))}
-        want.update({n: (i32, (P, N)) for n in ("parent", "depth", "visits", "num_children", "first_child", "pending")})
-        want.update({n: (f64, (P, N)) for n in ("prior", "value_sum", "value_max")})
-        if tree.get("errors_dev") is not None:
-            want["errors_dev"] = (i32, (1,))
-        req = _leaves_lib.PcbenvPuctLeavesRequest(struct_size=C.sizeof(_leaves_lib.PcbenvPuctLeavesRequest), num_roots=P, capacity=N,
-                                                  max_children=int(max_children), max_steps=T, c_puct=float(c_puct), num_leaves=L)
-        for name, (dtype, shape) in want.items():
-            check_tensor(self.device, name, tree[name], dtype, shape)
-            setattr(req, name, _ptr(tree[name]))
-        return req
+        want = _puct_tree_want(P, N, _exchange_want(T, P * L), slots=("pending",))
+        return self._tree_request(_leaves_lib.PcbenvPuctLeavesRequest, tree, want, num_roots=P, capacity=N, max_children=int(max_children),
+                                  max_steps=T, c_puct=float(c_puct), num_leaves=L)
 
     def puct_advance_leaves(self, req: "_leaves_lib.PcbenvPuctLeavesRequest", phases: int, value: Optional[torch.Tensor] = None,
                             leaf_terminal: Optional[torch.Tensor] = None, cand_count: Optional[torch.Tensor] = None,
@@ -940,18 +942,8 @@ class BatchedPlacementEnv:
         P = req.num_roots
         if P == 0:  # torch gives empty tensors a null pointer
             return
-        R = P * req.num_leaves
-        req.phases = int(phases)
-        K = int(cand_prior.shape[1]) if isinstance(cand_prior, torch.Tensor) and cand_prior.dim() == 2 else "K"
-        req.num_candidates = K if isinstance(K, int) else 0
-        for name, t, dtype, shape in (("value", value, torch.float64, (R,)), ("leaf_terminal", leaf_terminal, torch.uint8, (R,)),
-                                      ("cand_count", cand_count, torch.int32, (R,)), ("cand_actions", cand_actions, torch.int32, (R, K, 3)),
-                                      ("cand_prior", cand_prior, torch.float32, (R, K))):
-            if t is not None:
-                check_tensor(self.device, name, t, dtype, shape)
-            setattr(req, name, _ptr(t))
-        req.stream = self._stream().value
-        _lib.check(self._L.pcbenv_puct_advance_leaves(self._h, C.byref(req)), self._h)
+        self._puct_absorb(self._L.pcbenv_puct_advance_leaves, req, P * req.num_leaves, phases, value, leaf_terminal, cand_count, cand_actions,
+                          cand_prior)
 
     def puct_move_request(self, tree: Dict[str, torch.Tensor], max_children: int = 16) -> "_move_lib.PcbenvPuctMoveRequest":
         """The request of `puct_move` for the tensors in `tree`: the tree tensors of `puct_request` (`num_nodes` ...
@@ -965,18 +957,9 @@ class BatchedPlacementEnv:
         if par.dim() != 2:
             raise ValueError(f"parent must be [P, N], got {tuple(par.shape)}")
         (P, N), Cn = par.shape, int(max_children)
-        want = {"num_nodes": (i32, (P,)), "node_action": (i32, (P, N, 3)), "terminal": (torch.uint8, (P, N)), "reward_lo": (f64, (P,)),
-                "reward_hi": (f64, (P,)), "move_slot": (i32, (P,)), "move_action": (i32, (P, 3)), "child_visits": (i32, (P, Cn)),
-                "child_actions": (i32, (P, Cn, 3)), "root_value": (f64, (P,)), "remap": (i32, (P, N))}
-        want.update({n: (i32, (P, N)) for n in ("parent", "depth", "visits", "num_children", "first_child")})
-        want.update({n: (f64, (P, N)) for n in ("prior", "value_sum", "value_max")})
-        if tree.get("errors_dev") is not None:
-            want["errors_dev"] = (i32, (1,))
-        req = _move_lib.PcbenvPuctMoveRequest(struct_size=C.sizeof(_move_lib.PcbenvPuctMoveRequest), num_roots=P, capacity=N, max_children=Cn)
-        for name, (dtype, shape) in want.items():
-            check_tensor(self.device, name, tree[name], dtype, shape)
-            setattr(req, name, _ptr(tree[name]))
-        return req
+        own = {"move_slot": (i32, (P,)), "move_action": (i32, (P, 3)), "child_visits": (i32, (P, Cn)), "child_actions": (i32, (P, Cn, 3)),
+               "root_value": (f64, (P,)), "remap": (i32, (P, N))}
+        return self._tree_request(_move_lib.PcbenvPuctMoveRequest, tree, _puct_tree_want(P, N, own), num_roots=P, capacity=N, max_children=Cn)
 
     def puct_move(self, req: "_move_lib.PcbenvPuctMoveRequest", phases: int, mode: int = _move_lib.MOVE_GREEDY, seed: Optional[int] = None,
                   step_index: int = 0, reset: Optional[torch.Tensor] = None) -> None:
@@ -991,14 +974,9 @@ class BatchedPlacementEnv:
         P = req.num_roots
         if P == 0:  # torch gives empty tensors a null pointer
             return
-        req.phases, req.mode = int(phases), int(mode)
-        req.seed = (self.run_seed if seed is None else int(seed)) & (2 ** 64 - 1)
+        req.mode, req.seed = int(mode), (self.run_seed if seed is None else int(seed)) & (2 ** 64 - 1)
         req.step_index, req.first_root = int(step_index) & (2 ** 64 - 1), self.first_env_index
-        if reset is not None:
-            check_tensor(self.device, "reset", reset, torch.uint8, (P,))
-        req.reset = _ptr(reset)
-        req.stream = self._stream().value
-        _lib.check(self._L.pcbenv_puct_move(self._h, C.byref(req)), self._h)
+        self._advance(self._L.pcbenv_puct_move, req, phases, (("reset", reset, torch.uint8, (P,)),))
 
     def top_priors(self, logits: torch.Tensor, K: int, mask_bits: Optional[torch.Tensor] = None,
                    out: Optional[Sequence[torch.Tensor]] = None, errors: Optional[torch.Tensor] = None):

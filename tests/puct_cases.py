@@ -29,6 +29,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
+import tree_cases
 from pcbenv.search import Evaluation, puct_search
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -227,12 +228,7 @@ def synthetic(P, T, C, K, iterations, c_puct=1.25, seed=11, capacity=None, split
 
 
 # ---- every group width, more than one block ------------------------------------------------------------------------
-def group_lanes(C):
-    """csrc/pcb_puct.hip:group_lanes -- the lanes per root of the k_puct_advance<G> the host picks for max_children = C."""
-    g = 4
-    while g < C:
-        g <<= 1
-    return g
+group_lanes = tree_cases.group_lanes  # csrc/pcb_group.h:group_lanes -- the lanes per root of the k_puct_advance<G> the host picks for max_children = C
 
 
 BLOCK = 256  # threads of a k_puct_advance workgroup: 256 / G roots

@@ -138,7 +138,7 @@ def test_a_damaged_tree_ends_as_pcb_puct_h_promises(G, name):
 
 def test_every_group_width_has_its_cases():
     """Which k_puct_advance<G> a GPU test runs cannot be seen without a device, so the mapping is recorded: the host picks
-    G = group_lanes(max_children) (csrc/pcb_puct.hip, mirrored by puct_cases.group_lanes)."""
+    G = group_lanes(max_children) (csrc/pcb_group.h, mirrored by puct_cases.group_lanes)."""
     assert [pc.group_lanes(C) for C in (1, 3, 4, 5, 8, 9, 16, 17, 32, 33, 63, 64)] == [4, 4, 4, 8, 8, 16, 16, 32, 32, 64, 64, 64]
     by_width = {}
     for name, (P, C, K, iterations, G, blocks) in pc.WIDTHS.items():

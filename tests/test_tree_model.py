@@ -160,7 +160,7 @@ def test_a_damaged_tree_ends_as_pcb_tree_h_promises(G, name):
 
 def test_every_group_width_has_its_cases():
     """Which k_tree_advance<G> a GPU test runs cannot be seen without a device, so the mapping is recorded: the host picks
-    G = group_lanes(max_children) (csrc/pcb_tree.hip, mirrored by tree_cases.group_lanes), and the cases of
+    G = group_lanes(max_children) (csrc/pcb_group.h, mirrored by tree_cases.group_lanes), and the cases of
     tests/test_tree_advance_gpu.py are these (DESIGN.md lists them under k_tree_advance)."""
     from test_tree_advance_gpu import REPLAYS
     assert [tc.group_lanes(C) for C in (1, 3, 4, 5, 8, 9, 16, 17, 32, 33, 63, 64)] == [4, 4, 4, 8, 8, 16, 16, 32, 32, 64, 64, 64]

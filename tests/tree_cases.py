@@ -260,7 +260,7 @@ def synthetic(P, T, C, iterations, c_uct=0.9, seed=11, capacity=None, split=Fals
 
 # ---- every group width, more than one block ------------------------------------------------------------------------
 def group_lanes(C):
-    """csrc/pcb_tree.hip:group_lanes -- the lanes per root of the k_tree_advance<G> the host picks for max_children = C."""
+    """csrc/pcb_group.h:group_lanes -- the lanes per root of the kernel<G> the host picks for max_children = C (every tree step)."""
     g = 4
     while g < C:
         g <<= 1
