@@ -38,6 +38,10 @@ class AlphaZeroConfig:
     # update() evaluates the policy loss with visit_targets.cross_entropy on the raw logits (pcbenv_evaluate_visits and its
     # backward) instead of the torch chain cross_entropy_torch.  Both read the same stored mask_bits and targets.
     device_loss: bool = False
+    # Exploration noise on the root's priors, once per root and move (puct_selfplay's root_noise): a draw from
+    # Dir(noise_alpha) mixed in with weight noise_eps.  None: no noise.
+    noise_alpha: Optional[float] = None
+    noise_eps: float = 0.25
 
 
 def value_targets(reward: torch.Tensor, done: torch.Tensor):
@@ -101,7 +105,8 @@ class AlphaZeroTrainer:
         self.policy.eval()
         sp = puct_selfplay(root, self.evaluate, M, self.cfg.iterations, step_index=self.step_index, c_puct=self.cfg.c_puct,
                            max_children=self.cfg.max_children, capacity=self.cfg.capacity, mode=self.cfg.mode,
-                           on_move=lambda j, tree: keep_root(j + 1) if j + 1 < M else None, leaves=self.cfg.leaves)
+                           on_move=lambda j, tree: keep_root(j + 1) if j + 1 < M else None, leaves=self.cfg.leaves,
+                           root_noise=None if self.cfg.noise_alpha is None else (self.cfg.noise_alpha, self.cfg.noise_eps))
         from .batched_env import default_max_steps
         self.step_index += M * self.cfg.iterations * default_max_steps(root.cfg)
         z, weight = value_targets(sp.reward.float(), sp.done)

@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _leaves_lib, _lib, _move_lib, _priors_lib, _search_lib, _train_lib
+from . import _leaves_lib, _lib, _move_lib, _noise_lib, _priors_lib, _search_lib, _train_lib
 from .config import EnvConfig, KIND_PIN, KIND_RECT, KIND_SPATIAL, KIND_SQUARE
 from .instances import Instance, InstanceStream, env_seed, pack_instances
 
@@ -169,7 +169,7 @@ class BatchedPlacementEnv:
             raise RuntimeError("BatchedPlacementEnv needs a GPU device (there is no CPU fallback)")
         # the device the handle lives on, index included: one named without an index is the current device, now and for good
         self.device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
-        self._L = _leaves_lib.bind(_train_lib.bind(_move_lib.bind(_priors_lib.bind(_search_lib.bind(_lib.load())))))
+        self._L = _noise_lib.bind(_leaves_lib.bind(_train_lib.bind(_move_lib.bind(_priors_lib.bind(_search_lib.bind(_lib.load()))))))
         # per-environment spaces (the reference constructors' declarations); every tensor adds a leading batch dim
         from .spaces import action_space_for, observation_space_for
         self.action_space = self.single_action_space = action_space_for(cfg)
@@ -977,6 +977,35 @@ class BatchedPlacementEnv:
         req.mode, req.seed = int(mode), (self.run_seed if seed is None else int(seed)) & (2 ** 64 - 1)
         req.step_index, req.first_root = int(step_index) & (2 ** 64 - 1), self.first_env_index
         self._advance(self._L.pcbenv_puct_move, req, phases, (("reset", reset, torch.uint8, (P,)),))
+
+    def puct_noise_request(self, tree: Dict[str, torch.Tensor], max_children: int = 16) -> "_noise_lib.PcbenvPuctNoiseRequest":
+        """The request of `puct_root_noise` for the tensors in `tree`: the members of pcbenv_puct_noise_request
+        (include/pcbenv_noise.h) `num_children`, `first_child` [P, N] int32, `prior` [P, N] float64, `noised` [P] int32 and
+        optionally `errors_dev` -- `pcbenv.search.new_puct_tree` has a set of the right shapes -- on this device,
+        contiguous, of the dtypes and shapes the header gives; P and N are read off `prior` [P, N], C = max_children is an
+        argument.  The request holds addresses only: the caller keeps the tensors alive."""
+        i32 = torch.int32
+        pri = tree["prior"]
+        if pri.dim() != 2:
+            raise ValueError(f"prior must be [P, N], got {tuple(pri.shape)}")
+        P, N = pri.shape
+        want = {"num_children": (i32, (P, N)), "first_child": (i32, (P, N)), "prior": (torch.float64, (P, N)), "noised": (i32, (P,))}
+        return self._tree_request(_noise_lib.PcbenvPuctNoiseRequest, tree, want, num_roots=P, capacity=N, max_children=int(max_children))
+
+    def puct_root_noise(self, req: "_noise_lib.PcbenvPuctNoiseRequest", alpha: float, eps: float, seed: Optional[int] = None,
+                        step_index: int = 0) -> None:
+        """Dirichlet noise on the root priors of P PUCT trees on the device (`pcbenv_puct_root_noise`, one kernel launch on
+        the current stream, nothing else): every root with `noised` 0 and children gets prior = float32((1 - eps) * prior +
+        eps * eta) on its children, eta a draw from Dir(alpha) keyed by the library's draw hash of (seed, first_env_index +
+        p, step_index), and `noised` 1; seed defaults to the environment's run_seed.  alpha in [0.01, 100], eps in [0, 1].
+        `req`: `puct_noise_request(tree, max_children)`, reusable for every call on the same tensors."""
+        if req.num_roots == 0:  # torch gives empty tensors a null pointer
+            return
+        req.alpha, req.eps = float(alpha), float(eps)
+        req.seed = (self.run_seed if seed is None else int(seed)) & (2 ** 64 - 1)
+        req.step_index, req.first_root = int(step_index) & (2 ** 64 - 1), self.first_env_index
+        req.stream = self._stream().value
+        _lib.check(self._L.pcbenv_puct_root_noise(self._h, C.byref(req)), self._h)
 
     def top_priors(self, logits: torch.Tensor, K: int, mask_bits: Optional[torch.Tensor] = None,
                    out: Optional[Sequence[torch.Tensor]] = None, errors: Optional[torch.Tensor] = None):

@@ -447,7 +447,8 @@ class PuctSearch:
 def new_puct_tree(P: int, N: int, T: int, device, leaves: int = 1) -> dict:
     """The tensors of P PUCT trees of N node slots and T steps, as `BatchedPlacementEnv.puct_request` takes them -- and,
     with `pending` [P, N] and the exchange tensors `selected`, `path_len` and `paths` of P * leaves rows, as
-    `puct_leaves_request` does.  Uninitialised but for `paths`, `pending` and `errors_dev`: PCBENV_TREE_INIT fills the rest."""
+    `puct_leaves_request` does; `noised` [P] is `puct_noise_request`'s.  Uninitialised but for `paths`, `pending`, `noised` and
+    `errors_dev`: PCBENV_TREE_INIT fills the rest."""
     i32, f64 = dict(dtype=torch.int32, device=device), dict(dtype=torch.float64, device=device)
     R = P * int(leaves)
     tree = {n: torch.empty((P, N), **i32) for n in ("parent", "depth", "visits", "num_children", "first_child")}
@@ -455,7 +456,8 @@ def new_puct_tree(P: int, N: int, T: int, device, leaves: int = 1) -> dict:
     tree.update({n: torch.empty(P, **f64) for n in ("reward_lo", "reward_hi")})
     tree.update(num_nodes=torch.empty(P, **i32), selected=torch.empty(R, **i32), path_len=torch.empty(R, **i32))
     tree.update(node_action=torch.empty((P, N, 3), **i32), terminal=torch.empty((P, N), dtype=torch.uint8, device=device),
-                paths=torch.zeros((T, R, 3), **i32), errors_dev=torch.zeros(1, **i32), pending=torch.zeros((P, N), **i32))
+                paths=torch.zeros((T, R, 3), **i32), errors_dev=torch.zeros(1, **i32), pending=torch.zeros((P, N), **i32),
+                noised=torch.zeros(P, **i32))
     return tree
 
 
@@ -516,7 +518,8 @@ def _puct_arguments(root, iterations, max_children, max_steps, capacity, tree=No
 
 
 def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float = 1.0, max_children: int = 16, max_steps=None,
-                capacity=None, tree=None, leaves: int = 1) -> PuctSearch:
+                capacity=None, tree=None, leaves: int = 1, root_noise=None, noise_seed=None, noise_first_root=None,
+                noise_step_index=None) -> PuctSearch:
     """Batched PUCT (the AlphaZero search) over all P = root.num_envs roots in lock-step, the tree in tensors, one
     `evaluate` per iteration and no host synchronisation inside the loop: the specification of pcbenv_puct_advance
     (include/pcbenv_search.h), in tensor code for any device.  Iteration m:
@@ -545,9 +548,17 @@ def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float 
     all later leaves of the root are no leaf -- path_len -1, their evaluation is not looked at.  Then ONE evaluate(paths
     [max_steps, P * L, 3], path_len [P * L], step_index + m * max_steps), row p * L + l the leaf l of root p, and the
     leaves are expanded and backed up in the same order, each backup taking the pending visit off its chain.  capacity
-    defaults to 1 + iterations * L * max_children."""
+    defaults to 1 + iterations * L * max_children.
+    root_noise = (alpha, eps): exploration noise on the root's priors, `puct_root_noise` with the key (noise_seed,
+    noise_first_root + p, step_index), once per root and search: before the first selection in a tree that is kept, and
+    again after the first iteration's expansion for the roots that had no children then (a fresh root, whose first
+    evaluation has just expanded it).  A root that is still without children after that stays without noise for this
+    search.  noise_seed defaults to root.run_seed ^ 0x6e6f6973 and noise_first_root to root.first_env_index; a root that
+    is no BatchedPlacementEnv gives the seed explicitly (the first root then defaults to 0).  noise_step_index: the step
+    index of the key where it is not the search's own (move j of `puct_selfplay` has step_index + j).  None: no noise."""
     P, C, M, T, N = _puct_arguments(root, iterations, max_children, max_steps, capacity, tree, leaves)
     L = int(leaves)
+    noise = _noise_arguments(root, root_noise, noise_seed, noise_first_root)
     dev = getattr(root, "device", "cpu")
     i64, f64 = dict(dtype=torch.int64, device=dev), dict(dtype=torch.float64, device=dev)
     # one slot and one path row more than used: where a root has nothing to write, the write goes there
@@ -574,6 +585,15 @@ def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float 
     trash = torch.full((P,), N, **i64)
     zero_r, ninf_r = torch.zeros(P, **f64), torch.full((P,), float("-inf"), **f64)
     none = torch.full((P,), -1, **i64)
+    noised = torch.zeros(P, dtype=torch.int32, device=dev)
+
+    def add_noise(noised, errors):
+        now = dict(num_children=nchild[:, :N], first_child=first_child[:, :N], prior=prior[:, :N])
+        prior[:, :N], done = puct_root_noise(now, noised, C, noise[0], noise[1], noise[2], step_index if noise_step_index is None else noise_step_index,
+                                             noise[3])
+        return done, errors | puct_noise_errors(now, noised, C)
+    if noise is not None and tree is not None:
+        noised, errors = add_noise(noised, errors)
     for m in range(M):
         # selection (iteration m finds no node deeper than m: a bound the host knows without asking the device)
         paths = torch.zeros((T + 1, P, L, 3), dtype=torch.int32, device=dev)
@@ -660,27 +680,40 @@ def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float 
                 vmax.scatter_reduce_(1, idx, torch.where(on, value, ninf_r)[:, None], reduce="amax")
                 pending.scatter_add_(1, idx, -on.to(torch.int64)[:, None])
                 cur = torch.where(on, parent[rows, idx[:, 0]], torch.full_like(cur, -1))
+        if noise is not None and m == 0:  # the first expansion has given a fresh root its children
+            noised, errors = add_noise(noised, errors)
     tree = dict(num_nodes=count, parent=parent[:, :N], depth=depth[:, :N], visits=visits[:, :N], num_children=nchild[:, :N],
                 first_child=first_child[:, :N], node_action=node_action[:, :N], prior=prior[:, :N], value_sum=vsum[:, :N],
                 value_max=vmax[:, :N], terminal=terminal[:, :N], reward_lo=lo, reward_hi=hi, errors_dev=errors)
     return puct_result(tree, C)
 
 
-def _puct_iterations(root, req, tree, M, T, evaluate, step_index, first_phases, leaves=1):
+def _puct_iterations(root, req, tree, M, T, evaluate, step_index, first_phases, leaves=1, noise=None):
     """The launches of one device search of M iterations on `tree`: `first_phases` (INIT | SELECT, or SELECT alone in a tree
     that is kept), then per iteration `evaluate` followed by ABSORB | SELECT, the last iteration by ABSORB alone.  With
-    leaves > 1 the launches are pcbenv_puct_advance_leaves' and `req` is a `puct_leaves_request`."""
+    leaves > 1 the launches are pcbenv_puct_advance_leaves' and `req` is a `puct_leaves_request`.
+    noise = (noise request, alpha, eps, seed, step index of the key): `noised` is zeroed, NOISE (pcbenv_puct_root_noise)
+    goes before the first SELECT of a tree that is kept, and the first iteration is ABSORB alone, NOISE, SELECT."""
     from . import _lib
     advance = root.puct_advance if int(leaves) == 1 else root.puct_advance_leaves
+    if noise is not None:
+        tree["noised"].zero_()
+        if not first_phases & _lib.TREE_INIT:
+            root.puct_root_noise(*noise)
     advance(req, first_phases)
     for m in range(M):
         ev = evaluate(tree["paths"], tree["path_len"], int(step_index) + m * T)
         over = ev.terminal.view(torch.uint8) if ev.terminal.dtype == torch.bool else ev.terminal
-        advance(req, _lib.TREE_ABSORB | (_lib.TREE_SELECT if m + 1 < M else 0), ev.value, over, ev.cand_count, ev.cand_actions, ev.cand_prior)
+        fused = noise is None or m > 0
+        advance(req, _lib.TREE_ABSORB | (_lib.TREE_SELECT if m + 1 < M and fused else 0), ev.value, over, ev.cand_count, ev.cand_actions, ev.cand_prior)
+        if not fused:
+            root.puct_root_noise(*noise)
+            if m + 1 < M:
+                advance(req, _lib.TREE_SELECT)
 
 
 def puct_search_device(root, iterations: int, step_index: int, evaluate, c_puct: float = 1.0, max_children: int = 16, max_steps=None,
-                       capacity=None, tree=None, leaves: int = 1) -> PuctSearch:
+                       capacity=None, tree=None, leaves: int = 1, root_noise=None, noise_seed=None, noise_step_index=None) -> PuctSearch:
     """`puct_search` with the tree kept by the device: an iteration is `evaluate` and one kernel launch,
     `root.puct_advance` (pcbenv_puct_advance: expansion, backup, the next selection), with no tensor operation between
     them: INIT | SELECT first, then per iteration `evaluate(tree paths, path_len, step_index + m * max_steps)` followed by
@@ -692,7 +725,10 @@ def puct_search_device(root, iterations: int, step_index: int, evaluate, c_puct:
     `puct_move(MOVE_REROOT)` left them; capacity is then the tree's, INIT is skipped and the first launch is SELECT alone.
     leaves = L > 1: `puct_search(leaves=L)` with `root.puct_advance_leaves` (pcbenv_puct_advance_leaves,
     include/pcbenv_leaves.h) as the one launch per iteration; `evaluate` sees P * L rows, row p * L + l the leaf l of root
-    p, path_len -1 where there is no leaf.  A tree that is kept is one of `new_puct_tree(leaves=L)`."""
+    p, path_len -1 where there is no leaf.  A tree that is kept is one of `new_puct_tree(leaves=L)`.
+    root_noise = (alpha, eps), noise_seed, noise_step_index: `puct_search`'s, as launches of `root.puct_root_noise` (pcbenv_puct_root_noise,
+    include/pcbenv_noise.h) on the tree's `noised`: one before the first SELECT of a tree that is kept; the first iteration
+    is ABSORB alone, NOISE, SELECT.  None: no noise, and the launches are what they are without this argument."""
     from . import _lib
     P, C, M, T, N = _puct_arguments(root, iterations, max_children, max_steps, capacity, tree, leaves)
     L = int(leaves)
@@ -700,7 +736,10 @@ def puct_search_device(root, iterations: int, step_index: int, evaluate, c_puct:
     if not kept:
         tree = new_puct_tree(P, N, T, root.device, L)
     req = root.puct_request(tree, c_puct, C) if L == 1 else root.puct_leaves_request(tree, c_puct, C, L)
-    _puct_iterations(root, req, tree, M, T, evaluate, step_index, _lib.TREE_SELECT if kept else _lib.TREE_INIT | _lib.TREE_SELECT, L)
+    noise = _noise_arguments(root, root_noise, noise_seed, None)
+    if noise is not None:
+        noise = (root.puct_noise_request(tree, C), noise[0], noise[1], noise[2], int(step_index if noise_step_index is None else noise_step_index))
+    _puct_iterations(root, req, tree, M, T, evaluate, step_index, _lib.TREE_SELECT if kept else _lib.TREE_INIT | _lib.TREE_SELECT, L, noise)
     return puct_result(tree, C)
 
 
@@ -829,6 +868,161 @@ def puct_reroot(tree: dict, move_slot: torch.Tensor, reset=None):
     return new, remap.to(torch.int32)
 
 
+# ---- exploration noise on the root's priors ---------------------------------------------------------------------------
+# ln, exp and the square root in IEEE + - * / alone: csrc/pcb_ieee_math.h, line by line.  torch's own differ from libm's and
+# ocml's in the last place; these are the same bits on every device.
+_LN2_HI, _LN2_LO = 6.93147180369123816490e-01, 1.90821492927058770002e-10
+_LOG2_E, _SQRT_HALF = 1.44269504088896338700e+00, 7.07106781186547524401e-01
+NOISE_ATTEMPTS, NOISE_BOOST_DRAW = 32, 96
+NOISE_ALPHA_MIN, NOISE_ALPHA_MAX = 0.01, 100.0
+
+
+def _pow2(k: torch.Tensor) -> torch.Tensor:
+    """2^k for an integer tensor, -1022 <= k <= 1023, through the bits."""
+    return ((k.to(torch.int64) + 1023) << 52).view(torch.float64)
+
+
+def ieee_ln(x: torch.Tensor) -> torch.Tensor:
+    """ln of positive normal float64 numbers: csrc/pcb_ieee_math.h:ieee_ln, the same operations."""
+    m, e = torch.frexp(x)
+    low = m < _SQRT_HALF
+    m = torch.where(low, 2.0 * m, m)
+    e = e - low.to(e.dtype)
+    t = (m - 1.0) / (m + 1.0)
+    t2 = t * t
+    p = (1.0 / 27.0) * t2 + 1.0 / 25.0
+    for n in (23.0, 21.0, 19.0, 17.0, 15.0, 13.0, 11.0, 9.0, 7.0, 5.0, 3.0, 1.0):
+        p = p * t2 + 1.0 / n
+    ef = e.to(torch.float64)
+    return ef * _LN2_HI + (ef * _LN2_LO + (2.0 * t) * p)
+
+
+def ieee_exp(x: torch.Tensor) -> torch.Tensor:
+    """exp of float64 numbers <= 0, exactly 0 below -708: csrc/pcb_ieee_math.h:ieee_exp, the same operations."""
+    under = x < -708.0
+    x = torch.where(under, torch.zeros_like(x), x)
+    kf = (x * _LOG2_E - 0.5).to(torch.int64).to(torch.float64)  # the conversion cuts towards 0
+    r = (x - kf * _LN2_HI) - kf * _LN2_LO
+    p = (1.0 / 6227020800.0) * r + 1.0 / 479001600.0
+    for f in (39916800.0, 3628800.0, 362880.0, 40320.0, 5040.0, 720.0, 120.0, 24.0, 6.0, 2.0, 1.0, 1.0):
+        p = p * r + 1.0 / f
+    return torch.where(under, torch.zeros_like(x), p * _pow2(kf))
+
+
+def ieee_sqrt(x: torch.Tensor) -> torch.Tensor:
+    """The square root of positive normal float64 numbers: csrc/pcb_ieee_math.h:ieee_sqrt, the same operations."""
+    m, e = torch.frexp(x)
+    odd = (e & 1) != 0
+    m = torch.where(odd, 2.0 * m, m)
+    e = e - odd.to(e.dtype)
+    y = torch.ones_like(m)
+    for _ in range(6):
+        y = 0.5 * (y + m / y)
+    return y * _pow2(torch.div(e, 2, rounding_mode="floor"))
+
+
+def noise_uniform(base: torch.Tensor, c: torch.Tensor, t: int) -> torch.Tensor:
+    """Draw number t of child c under `base` (int64 bits): ((w >> 12) + 0.5) * 2^-52, w = mix64(base + GOLDEN * (64 t + c + 1))."""
+    w = _mix64(base + (c + (64 * int(t) + 1)) * _i64(_GOLDEN))
+    return (_shr(w, 12).to(torch.float64) + 0.5) * (1.0 / 4503599627370496.0)
+
+
+def noise_base(seed: int, genv: torch.Tensor, step_index: int) -> torch.Tensor:
+    """The 64 bits behind the library's draw for (seed, genv, step_index): `draw_hi32` before its shift."""
+    return _mix64(_mix64((genv.to(torch.int64) + 1) * _i64(_GOLDEN) ^ _i64(int(seed))) + _i64(int(step_index)))
+
+
+def noise_gammas(base: torch.Tensor, c: torch.Tensor, alpha: float):
+    """Gamma(alpha) draws for the children c (int64, broadcast against base): csrc/pcb_puct_noise.h:gamma_draw as
+    NOISE_ATTEMPTS masked rounds.  -> (g float64, exhausted bool: no attempt accepted and g = d)."""
+    alpha = float(alpha)
+    a = alpha if alpha >= 1.0 else alpha + 1.0
+    d = a - 1.0 / 3.0
+    cc = (1.0 / 3.0) / ieee_sqrt(torch.full((), d, dtype=torch.float64, device=base.device))
+    g = torch.full(torch.broadcast_shapes(base.shape, c.shape), d, dtype=torch.float64, device=base.device)
+    done = torch.zeros_like(g, dtype=torch.bool)
+    for t in range(NOISE_ATTEMPTS):
+        v1, v2 = 2.0 * noise_uniform(base, c, 3 * t) - 1.0, 2.0 * noise_uniform(base, c, 3 * t + 1) - 1.0
+        s = v1 * v1 + v2 * v2
+        inside = s < 1.0
+        s = torch.where(inside, s, torch.full_like(s, 0.5))
+        x = v1 * ieee_sqrt((-2.0 * ieee_ln(s)) / s)
+        w = 1.0 + cc * x
+        v = (w * w) * w
+        positive = v > 0.0
+        lnv = ieee_ln(torch.where(positive, v, torch.ones_like(v)))
+        accept = ieee_ln(noise_uniform(base, c, 3 * t + 2)) < ((0.5 * (x * x) + d) - d * v) + d * lnv
+        now = inside & positive & accept & ~done
+        g = torch.where(now, d * v, g)
+        done = done | now
+    if alpha < 1.0:
+        g = g * ieee_exp(ieee_ln(noise_uniform(base, c, NOISE_BOOST_DRAW)) / alpha)
+    return g, ~done
+
+
+def _noise_roots(tree, noised, C):
+    """(k, fc, due, ok) of slot 0 of every root: the root is due (not noised yet, has children) and its child range is one."""
+    k, fc = tree["num_children"][:, 0].to(torch.int64), tree["first_child"][:, 0].to(torch.int64)
+    N = tree["prior"].shape[1]
+    due = (noised.to(k.device) == 0) & (k >= 1)
+    return k, fc, due, (k <= C) & (fc >= 1) & (fc <= N - k)
+
+
+def puct_noise_errors(tree: dict, noised: torch.Tensor, max_children: int) -> torch.Tensor:
+    """The error bits of `puct_root_noise` on the same arguments, int32 [1]: bit 1 (value 2) if a root that is due has a
+    child range outside the tree."""
+    _, _, due, ok = _noise_roots(tree, noised, int(max_children))
+    return ((due & ~ok).any().to(torch.int32) * 2).reshape(1)
+
+
+def puct_root_noise(tree: dict, noised: torch.Tensor, max_children: int, alpha: float, eps: float, seed: int, step_index: int,
+                    first_root: int = 0):
+    """Dirichlet noise on the priors of every root's children: the specification of pcbenv_puct_root_noise
+    (include/pcbenv_noise.h) in tensor code for any device, no host synchronisation, which the kernel matches bit for bit.
+    tree: a dict with `num_children`, `first_child` (integers of any width) and `prior` float64, [P, N]; noised: integers
+    [P].  Neither is modified.  -> (prior float64 [P, N], noised int32 [P]).  A root with noised 0 and k >= 1 children in a
+    healthy range gets prior(fc + c) = float32((1 - eps) * prior(fc + c) + eps * eta_c), eta = g / (g_0 + ... + g_(k-1))
+    summed in that order (1 / k if the sum is not a finite number > 0), g_c a Gamma(alpha) draw by Marsaglia and Tsang's
+    method with at most 32 attempts from the uniform stream of (seed, first_root + p, step_index, c) -- every elementary
+    function in IEEE + - * / (`ieee_ln`, `ieee_exp`, `ieee_sqrt`) -- and noised 1.  Every other root is left as it is."""
+    C, alpha, eps = int(max_children), float(alpha), float(eps)
+    if not (NOISE_ALPHA_MIN <= alpha <= NOISE_ALPHA_MAX) or not (0.0 <= eps <= 1.0) or C < 1 or C > 64:
+        raise ValueError("puct_root_noise needs alpha in [0.01, 100], eps in [0, 1] and max_children in [1, 64]")
+    prior = tree["prior"]
+    dev = prior.device
+    P, N = prior.shape
+    i64 = dict(dtype=torch.int64, device=dev)
+    k, fc, due, ok = _noise_roots(tree, noised, C)
+    handled = due & ok
+    rows, lane = torch.arange(P, **i64), torch.arange(C, **i64)
+    g, _ = noise_gammas(noise_base(seed, rows + int(first_root), step_index)[:, None], lane[None, :], alpha)
+    S = torch.zeros(P, dtype=torch.float64, device=dev)
+    for c in range(C):  # in this order: it is the contract
+        S = torch.where(c < k, S + g[:, c], S)
+    kf = k.clamp(min=1).to(torch.float64)
+    eta = torch.where(((S > 0.0) & (S <= 1.7976931348623157e308))[:, None], g / S[:, None], (1.0 / kf)[:, None].expand(P, C))
+    mine = handled[:, None] & (lane[None, :] < k[:, None])
+    ch = torch.where(mine, fc[:, None] + lane[None, :], torch.full((), N, **i64))
+    wide = torch.cat([prior, torch.zeros((P, 1), dtype=prior.dtype, device=dev)], dim=1)  # a spare column for what is not written
+    old = wide[rows[:, None], ch]
+    new = ((1.0 - eps) * old + eps * eta).to(torch.float32).to(torch.float64)
+    wide[rows[:, None], ch] = torch.where(mine, new, old)
+    return wide[:, :N].contiguous(), torch.where(handled, torch.ones_like(k), noised.to(dev).to(torch.int64)).to(torch.int32)
+
+
+def _noise_arguments(root, root_noise, noise_seed, first_root):
+    """(alpha, eps, seed, first root) of a search's `root_noise=` / `noise_seed=`, None without noise."""
+    if root_noise is None:
+        return None
+    alpha, eps = (float(v) for v in root_noise)
+    if not (NOISE_ALPHA_MIN <= alpha <= NOISE_ALPHA_MAX) or not (0.0 <= eps <= 1.0):
+        raise ValueError("root_noise = (alpha, eps) needs alpha in [0.01, 100] and eps in [0, 1]")
+    if noise_seed is None and not hasattr(root, "run_seed"):
+        raise ValueError("root_noise: a root without run_seed needs noise_seed")
+    seed = (int(root.run_seed) ^ 0x6e6f6973) if noise_seed is None else int(noise_seed)
+    return alpha, eps, seed, int(getattr(root, "first_env_index", 0) if first_root is None else first_root)
+
+
 @dataclass
 class SelfPlay:
     """What `puct_selfplay` returns: per move (the leading extent M = moves) and root."""
@@ -844,7 +1038,8 @@ class SelfPlay:
 
 
 def puct_selfplay(root, evaluate, moves: int, iterations: int, step_index: int = 0, c_puct: float = 1.0, max_children: int = 16,
-                  max_steps=None, capacity=None, mode: int = MOVE_GREEDY, seed=None, on_move=None, leaves: int = 1) -> SelfPlay:
+                  max_steps=None, capacity=None, mode: int = MOVE_GREEDY, seed=None, on_move=None, leaves: int = 1, root_noise=None,
+                  noise_seed=None) -> SelfPlay:
     """Plays `moves` moves of every root environment with a PUCT search whose tree stays on the device and is kept from
     move to move.  Per move: `iterations` of search on the kept tree (`evaluate` and one pcbenv_puct_advance launch each,
     as `puct_search_device(tree=)`); `root.puct_move(MOVE_CHOOSE)` -- the visit distribution of the root and the move,
@@ -861,7 +1056,11 @@ def puct_selfplay(root, evaluate, moves: int, iterations: int, step_index: int =
     them), which the next move overwrites: a trainer copies what it keeps.
     leaves = L > 1: every iteration selects and evaluates L leaves per root (`puct_search_device(leaves=L)`); `evaluate`
     sees P * L rows and the default capacity is 1 + 2 * iterations * L * max_children.  `pending` is zero after every
-    search, so the move's two launches take the tree as it is."""
+    search, so the move's two launches take the tree as it is.
+    root_noise = (alpha, eps): exploration noise on the root's priors, once per root and move
+    (`puct_search_device(root_noise=)`): the kept, expanded root of a move before its first descent, a fresh one as soon as
+    its first evaluation has expanded it.  The draws of move j have the key (noise_seed, first_env_index + p, step_index
+    + j), noise_seed defaulting to run_seed ^ 0x6e6f6973, so they share no key with the step draws or the move draw."""
     from . import _lib, _move_lib
     L = int(leaves)
     P, C, M, T, N = _puct_arguments(root, iterations, max_children, max_steps,
@@ -874,12 +1073,15 @@ def puct_selfplay(root, evaluate, moves: int, iterations: int, step_index: int =
     tree.update(new_move_tensors(P, N, C, dev))
     req, mreq = root.puct_request(tree, c_puct, C) if L == 1 else root.puct_leaves_request(tree, c_puct, C, L), root.puct_move_request(tree, C)
     seed = (root.run_seed ^ 0x6d6f7665) if seed is None else int(seed)
+    noise = _noise_arguments(root, root_noise, noise_seed, None)
+    nreq = root.puct_noise_request(tree, C) if noise is not None else None
     i32 = dict(dtype=torch.int32, device=dev)
     out = SelfPlay(torch.empty((J, P, 3), **i32), torch.empty((J, P, C), **i32), torch.empty((J, P, C, 3), **i32),
                    torch.empty((J, P), dtype=torch.float64, device=dev), torch.empty((J, P), dtype=torch.float64, device=dev),
                    torch.empty((J, P), dtype=torch.uint8, device=dev), torch.empty((J, P), **i32), tree["errors_dev"][0], tree)
     for j in range(J):
-        _puct_iterations(root, req, tree, M, T, evaluate, int(step_index) + j * M * T, _lib.TREE_SELECT if j else _lib.TREE_INIT | _lib.TREE_SELECT, L)
+        _puct_iterations(root, req, tree, M, T, evaluate, int(step_index) + j * M * T, _lib.TREE_SELECT if j else _lib.TREE_INIT | _lib.TREE_SELECT, L,
+                         None if noise is None else (nreq, noise[0], noise[1], noise[2], int(step_index) + j))
         root.puct_move(mreq, _move_lib.MOVE_CHOOSE, mode=mode, seed=seed, step_index=int(step_index) + j)
         _, reward, done, _ = root.step(tree["move_action"])
         out.actions[j], out.child_visits[j], out.child_actions[j], out.root_value[j] = tree["move_action"], tree["child_visits"], tree["child_actions"], tree["root_value"]

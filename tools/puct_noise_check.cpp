@@ -1,0 +1,96 @@
+// puct_noise_check.cpp -- csrc/pcb_puct_noise.h and csrc/pcb_ieee_math.h on the CPU: runs a sequence of
+// pcbenv_puct_root_noise calls through noise_root, root by root, on the tensors it is handed, and writes the state after
+// every call (tests/test_puct_noise_model.py compares it with pcbenv/search.py:puct_root_noise, the specification,
+// tests/test_puct_noise_gpu.py with the kernel's); or evaluates the three elementary functions.  A stand-alone program:
+//   g++ -std=c++17 -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -I rl-environment-for-component-placement_amd/csrc
+//
+// stdin and stdout are streams of little-endian int64 words (a float64 travels as its bits).  The first word is the mode.
+//   mode 0, calls.
+//     in:   P N C calls | num_children first_child [P N] prior [P N] noised [P]
+//           per call: seed step_index first_root alpha eps
+//     out:  per call: the error bits of that call | prior [P N] noised [P]
+//   mode 1, functions.
+//     in:   n | n x (function, argument): 0 ieee_ln, 1 ieee_exp, 2 ieee_sqrt
+//     out:  n results
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <vector>
+
+#include "pcb_puct_noise.h"
+
+namespace {
+
+bool read_words(int64_t *dst, size_t n) { return fread(dst, sizeof(int64_t), n, stdin) == n; }
+int64_t read_word(bool *ok) { int64_t v = 0; *ok = *ok && read_words(&v, 1); return v; }
+double as_double(int64_t bits) { double d; memcpy(&d, &bits, 8); return d; }
+int64_t as_bits(double d) { int64_t b; memcpy(&b, &d, 8); return b; }
+
+std::vector<int64_t> out;
+template <class V> void put(const V &v) { for (auto x : v) out.push_back((int64_t)x); }
+void put_bits(const std::vector<double> &v) { for (double x : v) out.push_back(as_bits(x)); }
+
+bool read_ints(std::vector<int> &dst) {
+    std::vector<int64_t> w(dst.size());
+    if (!read_words(w.data(), w.size())) return false;
+    for (size_t i = 0; i < w.size(); i++) dst[i] = (int)w[i];
+    return true;
+}
+bool read_doubles(std::vector<double> &dst) {
+    std::vector<int64_t> w(dst.size());
+    if (!read_words(w.data(), w.size())) return false;
+    for (size_t i = 0; i < w.size(); i++) dst[i] = as_double(w[i]);
+    return true;
+}
+
+int functions() {
+    bool ok = true;
+    const int64_t n = read_word(&ok);
+    if (!ok || n < 0) { fprintf(stderr, "bad header\n"); return 2; }
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t f = read_word(&ok);
+        const double x = as_double(read_word(&ok));
+        if (!ok || f < 0 || f > 2) { fprintf(stderr, "bad function\n"); return 2; }
+        out.push_back(as_bits(f == 0 ? pcb_ieee::ieee_ln(x) : f == 1 ? pcb_ieee::ieee_exp(x) : pcb_ieee::ieee_sqrt(x)));
+    }
+    return 0;
+}
+
+int calls() {
+    using namespace pcb_noise;
+    bool ok = true;
+    const int P = (int)read_word(&ok), N = (int)read_word(&ok), C = (int)read_word(&ok), calls = (int)read_word(&ok);
+    if (!ok || P < 0 || N < 1 || C < 1 || C > MAX_CHILDREN || calls < 0) { fprintf(stderr, "bad header\n"); return 2; }
+    const size_t PN = (size_t)P * N;
+    std::vector<int> num_children(PN), first_child(PN), noised(P);
+    std::vector<double> prior(PN);
+    if (!(read_ints(num_children) && read_ints(first_child) && read_doubles(prior) && read_ints(noised))) { fprintf(stderr, "the tree ends early\n"); return 2; }
+    for (int call = 0; call < calls; call++) {
+        const uint64_t seed = (uint64_t)read_word(&ok), step_index = (uint64_t)read_word(&ok);
+        const int first_root = (int)read_word(&ok);
+        const double alpha = as_double(read_word(&ok)), eps = as_double(read_word(&ok));
+        if (!ok || !(alpha >= ALPHA_MIN && alpha <= ALPHA_MAX) || !(eps >= 0.0 && eps <= 1.0)) { fprintf(stderr, "call %d: bad arguments\n", call); return 2; }
+        const Params q = noise_params(alpha, eps);
+        unsigned errors = 0u;
+        for (int p = 0; p < P; p++) {
+            const size_t s = (size_t)p * N;
+            errors |= noise_root(N, C, first_root + p, seed, step_index, q, &num_children[s], &first_child[s], &prior[s], &noised[p]);
+        }
+        out.push_back((int64_t)errors);
+        put_bits(prior); put(noised);
+    }
+    return 0;
+}
+
+}  // namespace
+
+int main() {
+    bool ok = true;
+    const int64_t mode = read_word(&ok);
+    if (!ok || mode < 0 || mode > 1) { fprintf(stderr, "bad mode\n"); return 2; }
+    const int rc = mode == 0 ? calls() : functions();
+    if (rc != 0) return rc;
+    if (fwrite(out.data(), sizeof(int64_t), out.size(), stdout) != out.size()) { fprintf(stderr, "short write\n"); return 2; }
+    return 0;
+}

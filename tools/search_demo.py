@@ -1,5 +1,5 @@
 """Receding-horizon Monte-Carlo lookahead with pcbenv.search.best_of_k against the plain uniform-random policy, c3.
-python tools/search_demo.py [--roots 256] [--k 16] [--playouts | --tree [--device-tree] [--policy] | --puct [--device-priors] [--reuse] [--leaves L] [--train N [--moves M] [--torch-loss]]]
+python tools/search_demo.py [--roots 256] [--k 16] [--playouts | --tree [--device-tree] [--policy] | --puct [--device-priors] [--reuse] [--leaves L] [--noise ALPHA EPS] [--train N [--moves M] [--torch-loss]]]
 
 Both play the same instances (one episode per root environment).  The search forks every root k times into a planner
 batch (one device-side gather), plays every child to its end with the on-device sampler, and applies the best child's
@@ -19,7 +19,9 @@ pcbenv.search.puct_selfplay -- the tree stays on the device from move to move: p
 action and makes its subtree the next move's tree, so the k iterations of a move add to the visits already spent below it;
 the line then also reports the mean visits a move's root started with.  --puct --leaves L: every iteration selects L leaves
 per root (pcbenv_puct_advance_leaves) and the evaluator sees roots x L nodes at once; k stays the iterations per move, so a
-move costs k x L evaluations.  --puct --train N (a spatial configuration: --config
+move costs k x L evaluations.  --puct --noise ALPHA EPS: exploration noise on the root's priors, once per root and move
+(pcbenv_puct_root_noise: a draw from Dir(ALPHA) mixed in with weight EPS); with --reuse the line also reports the share of
+the 16 child entries of a move's root that got no visit (entries behind the root's children included).  --puct --train N (a spatial configuration: --config
 c4): N rounds of pcbenv.alphazero.AlphaZeroTrainer -- collect() plays --moves moves of every root with puct_selfplay, k
 iterations each, pcbenv/policy.py's model behind network_evaluator(priors="device"); update() trains the model on the visit
 counts with pcbenv_evaluate_visits (--torch-loss: the torch chain instead) -- and one line per round: the mean final reward
@@ -68,7 +70,7 @@ def train(a, cfg):
     torch.manual_seed(0)
     trainer = AlphaZeroTrainer(root, planner, SpatialPolicy(cfg).to(root.device),
                                AlphaZeroConfig(moves=moves, iterations=a.k, max_children=16, capacity=1 + moves * a.k * a.leaves * 16, device_loss=not a.torch_loss,
-                                               leaves=a.leaves))
+                                               leaves=a.leaves, noise_alpha=a.noise[0] if a.noise else None, noise_eps=a.noise[1] if a.noise else 0.25))
     for it in range(a.train):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -101,6 +103,7 @@ def main():
     ap.add_argument("--device-priors", action="store_true", help="with --puct: the candidates from pcbenv_top_priors (network_evaluator(priors=\"device\"))")
     ap.add_argument("--reuse", action="store_true", help="with --puct: puct_selfplay, the subtree of the move played is kept (pcbenv_puct_move)")
     ap.add_argument("--leaves", type=int, default=1, metavar="L", help="with --puct: L leaves per root and iteration (pcbenv_puct_advance_leaves); k stays the iterations per move")
+    ap.add_argument("--noise", type=float, nargs=2, default=None, metavar=("ALPHA", "EPS"), help="with --puct: Dir(ALPHA) noise of weight EPS on the root's priors (pcbenv_puct_root_noise)")
     ap.add_argument("--train", type=int, default=0, metavar="N", help="with --puct: N collect/update rounds of pcbenv.alphazero.AlphaZeroTrainer")
     ap.add_argument("--moves", type=int, default=0, help="with --train: moves of every root per round (default: one episode)")
     ap.add_argument("--torch-loss", action="store_true", help="with --train: the policy loss through the torch chain (device_loss off)")
@@ -113,6 +116,8 @@ def main():
         ap.error("--reuse goes with --puct")
     if a.leaves != 1 and not a.puct:
         ap.error("--leaves goes with --puct")
+    if a.noise and not a.puct:
+        ap.error("--noise goes with --puct")
     if a.puct and (a.tree or a.playouts):
         ap.error("--puct goes alone")
     if a.device_tree and not a.tree:
@@ -158,7 +163,7 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if a.puct:
-            first = puct_search_device(search_root, k, 1000 + t * T * k, evaluate, max_children=16, leaves=a.leaves).action
+            first = puct_search_device(search_root, k, 1000 + t * T * k, evaluate, max_children=16, leaves=a.leaves, root_noise=a.noise).action
         elif a.tree:
             first = (tree_search_device if a.device_tree else tree_search)(search_root, k, step_index=1000 + t * T * k, backend=backend).action
         elif a.playouts:
@@ -174,11 +179,13 @@ def main():
     if a.reuse:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        sp = puct_selfplay(search_root, evaluate, T, k, step_index=1000, max_children=16, leaves=a.leaves)
+        sp = puct_selfplay(search_root, evaluate, T, k, step_index=1000, max_children=16, leaves=a.leaves, root_noise=a.noise)
         torch.cuda.synchronize()
         spent, planner_steps = time.perf_counter() - t0, P * k * a.leaves * T * T
         search_final = final_rewards(search_root, lambda t: (sp.reward[t], sp.done[t]), T)
         kept = {"mean_visits_kept_per_move": round(float(sp.kept_visits[:-1].double().mean()), 2), "tree_errors": int(sp.errors)}
+        searched = sp.child_visits.sum(dim=2) > 0
+        kept["zero_visit_share"] = round(float((sp.child_visits[searched] == 0).double().mean()), 4)
     else:
         search_final = final_rewards(search_root, search_step, T)
     out = {"config": a.config, "roots": P, "k": k, "search": ("puct_selfplay" if a.reuse else "puct_search_device") + "+network_evaluator" + ("(priors=device)" if a.device_priors else "") if a.puct else ("tree_search_device" if a.device_tree else "tree_search") + ("+policy_backend" if a.policy else "") if a.tree else "best_of_k_playouts" if a.playouts else "best_of_k",
@@ -188,6 +195,8 @@ def main():
     out.update(kept or {})
     if a.leaves != 1:
         out["leaves"] = a.leaves
+    if a.noise:
+        out["noise"] = a.noise
     print(json.dumps(out), flush=True)
     for e in (rand_root, search_root, planner):
         if e is not None:
