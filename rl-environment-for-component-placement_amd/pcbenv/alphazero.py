@@ -42,6 +42,13 @@ class AlphaZeroConfig:
     # Dir(noise_alpha) mixed in with weight noise_eps.  None: no noise.
     noise_alpha: Optional[float] = None
     noise_eps: float = 0.25
+    # Gumbel root search (puct_selfplay's gumbel): every move is a search of `iterations` simulations spent by Sequential
+    # Halving over gumbel_considered candidates, and the policy target is softmax(logit + sigma(completed q)) in the place of
+    # the visit counts; sigma(q) = (gumbel_c_visit + the most visits of a root child) * gumbel_c_scale * q.  `mode` is then not
+    # read.  None: PUCT at the root.  Not together with noise_alpha or leaves > 1.
+    gumbel_considered: Optional[int] = None
+    gumbel_c_visit: float = 50.0
+    gumbel_c_scale: float = 1.0
 
 
 def value_targets(reward: torch.Tensor, done: torch.Tensor):
@@ -106,9 +113,10 @@ class AlphaZeroTrainer:
         sp = puct_selfplay(root, self.evaluate, M, self.cfg.iterations, step_index=self.step_index, c_puct=self.cfg.c_puct,
                            max_children=self.cfg.max_children, capacity=self.cfg.capacity, mode=self.cfg.mode,
                            on_move=lambda j, tree: keep_root(j + 1) if j + 1 < M else None, leaves=self.cfg.leaves,
-                           root_noise=None if self.cfg.noise_alpha is None else (self.cfg.noise_alpha, self.cfg.noise_eps))
+                           root_noise=None if self.cfg.noise_alpha is None else (self.cfg.noise_alpha, self.cfg.noise_eps),
+                           gumbel=None if self.cfg.gumbel_considered is None else (self.cfg.gumbel_considered, self.cfg.gumbel_c_visit, self.cfg.gumbel_c_scale))
         from .batched_env import default_max_steps
-        self.step_index += M * self.cfg.iterations * default_max_steps(root.cfg)
+        self.step_index += M * (self.cfg.iterations + (self.cfg.gumbel_considered is not None)) * default_max_steps(root.cfg)
         z, weight = value_targets(sp.reward.float(), sp.done)
         return {"obs": obs, "mask_bits": bits, "child_visits": sp.child_visits, "child_actions": sp.child_actions, "z": z, "weight": weight,
                 "reward": sp.reward, "done": sp.done, "errors": sp.errors}

@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _leaves_lib, _lib, _move_lib, _noise_lib, _priors_lib, _search_lib, _train_lib
+from . import _gumbel_lib, _leaves_lib, _lib, _move_lib, _noise_lib, _priors_lib, _search_lib, _train_lib
 from .config import EnvConfig, KIND_PIN, KIND_RECT, KIND_SPATIAL, KIND_SQUARE
 from .instances import Instance, InstanceStream, env_seed, pack_instances
 
@@ -169,7 +169,7 @@ class BatchedPlacementEnv:
             raise RuntimeError("BatchedPlacementEnv needs a GPU device (there is no CPU fallback)")
         # the device the handle lives on, index included: one named without an index is the current device, now and for good
         self.device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
-        self._L = _noise_lib.bind(_leaves_lib.bind(_train_lib.bind(_move_lib.bind(_priors_lib.bind(_search_lib.bind(_lib.load()))))))
+        self._L = _gumbel_lib.bind(_noise_lib.bind(_leaves_lib.bind(_train_lib.bind(_move_lib.bind(_priors_lib.bind(_search_lib.bind(_lib.load())))))))
         # per-environment spaces (the reference constructors' declarations); every tensor adds a leading batch dim
         from .spaces import action_space_for, observation_space_for
         self.action_space = self.single_action_space = action_space_for(cfg)
@@ -1006,6 +1006,51 @@ class BatchedPlacementEnv:
         req.step_index, req.first_root = int(step_index) & (2 ** 64 - 1), self.first_env_index
         req.stream = self._stream().value
         _lib.check(self._L.pcbenv_puct_root_noise(self._h, C.byref(req)), self._h)
+
+    def gumbel_request(self, tree: Dict[str, torch.Tensor], c_puct: float = 1.0, max_children: int = 16, c_visit: float = 50.0,
+                       c_scale: float = 1.0) -> "_gumbel_lib.PcbenvGumbelRequest":
+        """The request of `gumbel_advance` for the tensors in `tree`: the tensors of `puct_request` (`num_nodes` ...
+        `reward_hi`, `selected`, `path_len`, `paths`) and the members of pcbenv_gumbel_request (include/pcbenv_gumbel.h)
+        `sim_index` [P], `sim_visits` [P, C], `considered` [Mc + 1, n], `move_slot` [P], `move_action` [P, 3], `child_weights`
+        [P, C], `child_policy` float32 [P, C], `child_actions` [P, C, 3], `root_value` float64 [P] and optionally `errors_dev`
+        -- `pcbenv.search.new_puct_tree` and `new_gumbel_tensors` have a set of the right shapes -- on this device,
+        contiguous, of the dtypes and shapes the header gives; P, N and T are read off `parent` [P, N] and `paths` [T, P, 3],
+        Mc = max_considered and n = num_simulations off `considered`, C = max_children is an argument.  The request holds
+        addresses only: the caller keeps the tensors alive."""
+        i32, f64 = torch.int32, torch.float64
+        par, paths, table = tree["parent"], tree["paths"], tree["considered"]
+        if par.dim() != 2 or paths.dim() != 3 or paths.shape[1:] != (par.shape[0], 3):
+            raise ValueError(f"parent must be [P, N] and paths [T, P, 3], got {tuple(par.shape)} and {tuple(paths.shape)}")
+        if table.dim() != 2 or table.shape[0] < 2 or table.shape[0] > _gumbel_lib.MAX_CONSIDERED + 1 or table.shape[1] < 1:
+            raise ValueError(f"considered must be [Mc + 1, n] with Mc in [1, {_gumbel_lib.MAX_CONSIDERED}] and n >= 1, got {tuple(table.shape)}")
+        (P, N), T, Cn, (rows, n) = par.shape, paths.shape[0], int(max_children), table.shape
+        own = {**_exchange_want(T, P), "sim_index": (i32, (P,)), "sim_visits": (i32, (P, Cn)), "considered": (i32, (rows, n)), "move_slot": (i32, (P,)),
+               "move_action": (i32, (P, 3)), "child_weights": (i32, (P, Cn)), "child_policy": (torch.float32, (P, Cn)),
+               "child_actions": (i32, (P, Cn, 3)), "root_value": (f64, (P,))}
+        return self._tree_request(_gumbel_lib.PcbenvGumbelRequest, tree, _puct_tree_want(P, N, own), num_roots=P, capacity=N, max_children=Cn,
+                                  max_steps=T, num_simulations=n, max_considered=rows - 1, c_puct=float(c_puct), c_visit=float(c_visit),
+                                  c_scale=float(c_scale))
+
+    def gumbel_advance(self, req: "_gumbel_lib.PcbenvGumbelRequest", phases: int, value: Optional[torch.Tensor] = None,
+                       leaf_terminal: Optional[torch.Tensor] = None, cand_count: Optional[torch.Tensor] = None,
+                       cand_actions: Optional[torch.Tensor] = None, cand_prior: Optional[torch.Tensor] = None, seed: Optional[int] = None,
+                       step_index: int = 0) -> None:
+        """One step of P search trees whose root level is a Gumbel search with Sequential Halving on the device
+        (`pcbenv_gumbel_advance`, one kernel launch on the current stream, nothing else): `phases` is a set of
+        `_gumbel_lib.GUMBEL_BEGIN`, `GUMBEL_ABSORB`, `GUMBEL_SELECT`, `GUMBEL_CHOOSE`, run in that order.  BEGIN zeroes the
+        budget of a move (`sim_index`, `sim_visits`); ABSORB is `puct_advance`'s, with the same inputs; SELECT descends
+        every tree -- level 0 by the schedule in `considered` on g + logit + sigma(q) while `sim_index` < n, every other
+        level by PUCT -- and writes `selected`, `path_len` and `paths`; CHOOSE writes the move (`move_slot`, `move_action`),
+        the policy target softmax(logit + sigma(completed q)) (`child_policy`, and `child_weights` in units of 2^-24, which
+        `evaluate_visits` takes as it takes visit counts), `child_actions` and `root_value`.  The Gumbel draws have the key
+        (seed, first_env_index + p, step_index), the same for every launch of a move; seed defaults to the environment's
+        run_seed.  `req`: `gumbel_request(tree, ...)`, reusable for every call on the same tensors."""
+        P = req.num_roots
+        if P == 0:  # torch gives empty tensors a null pointer
+            return
+        req.seed = (self.run_seed if seed is None else int(seed)) & (2 ** 64 - 1)
+        req.step_index, req.first_root = int(step_index) & (2 ** 64 - 1), self.first_env_index
+        self._puct_absorb(self._L.pcbenv_gumbel_advance, req, P, phases, value, leaf_terminal, cand_count, cand_actions, cand_prior)
 
     def top_priors(self, logits: torch.Tensor, K: int, mask_bits: Optional[torch.Tensor] = None,
                    out: Optional[Sequence[torch.Tensor]] = None, errors: Optional[torch.Tensor] = None):

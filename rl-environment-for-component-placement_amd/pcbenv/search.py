@@ -519,7 +519,7 @@ def _puct_arguments(root, iterations, max_children, max_steps, capacity, tree=No
 
 def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float = 1.0, max_children: int = 16, max_steps=None,
                 capacity=None, tree=None, leaves: int = 1, root_noise=None, noise_seed=None, noise_first_root=None,
-                noise_step_index=None) -> PuctSearch:
+                noise_step_index=None, root_select=None) -> PuctSearch:
     """Batched PUCT (the AlphaZero search) over all P = root.num_envs roots in lock-step, the tree in tensors, one
     `evaluate` per iteration and no host synchronisation inside the loop: the specification of pcbenv_puct_advance
     (include/pcbenv_search.h), in tensor code for any device.  Iteration m:
@@ -555,9 +555,14 @@ def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float 
     evaluation has just expanded it).  A root that is still without children after that stays without noise for this
     search.  noise_seed defaults to root.run_seed ^ 0x6e6f6973 and noise_first_root to root.first_env_index; a root that
     is no BatchedPlacementEnv gives the seed explicitly (the first root then defaults to 0).  noise_step_index: the step
-    index of the key where it is not the search's own (move j of `puct_selfplay` has step_index + j).  None: no noise."""
+    index of the key where it is not the search's own (move j of `puct_selfplay` has step_index + j).  None: no noise.
+    root_select: another rule for level 0 (`gumbel_search`'s), leaves == 1 only: root_select(tree, stopped, nxt) -> the node
+    every root goes to from slot 0, given the tree as it stands (a dict of views that must not be modified), the roots
+    that stop at slot 0 and the node PUCT would go to.  None: PUCT at every level."""
     P, C, M, T, N = _puct_arguments(root, iterations, max_children, max_steps, capacity, tree, leaves)
     L = int(leaves)
+    if root_select is not None and L != 1:
+        raise ValueError("root_select needs leaves == 1")
     noise = _noise_arguments(root, root_noise, noise_seed, noise_first_root)
     dev = getattr(root, "device", "cpu")
     i64, f64 = dict(dtype=torch.int64, device=dev), dict(dtype=torch.float64, device=dev)
@@ -620,6 +625,10 @@ def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float 
                 u = c_puct * prior[rows[:, None], ch] * sqrt_rn(n_p)[:, None] / (1.0 + n_cf)
                 score = torch.where(mine, q + u, torch.full_like(q, float("-inf")))
                 nxt = fc + score.argmax(dim=1)                         # the first maximum: the lowest child
+                if root_select is not None and d == 0:
+                    nxt = root_select(dict(num_nodes=count, parent=parent[:, :N], depth=depth[:, :N], visits=visits[:, :N], num_children=nchild[:, :N],
+                                           first_child=first_child[:, :N], node_action=node_action[:, :N], prior=prior[:, :N], value_sum=vsum[:, :N],
+                                           value_max=vmax[:, :N], terminal=terminal[:, :N], reward_lo=lo, reward_hi=hi), stopped, nxt)
                 pending[rows, torch.where(stopped, trash, node)] += 1  # the node the descent leaves
                 node = torch.where(stopped, node, nxt)
                 paths[torch.where(stopped, torch.full_like(node, T), torch.full_like(node, d)), rows, l] = node_action[rows, node]
@@ -1023,6 +1032,251 @@ def _noise_arguments(root, root_noise, noise_seed, first_root):
     return alpha, eps, seed, int(getattr(root, "first_env_index", 0) if first_root is None else first_root)
 
 
+# ---- Gumbel root search with sequential halving (include/pcbenv_gumbel.h) ---------------------------------------------
+GUMBEL_BEGIN, GUMBEL_ABSORB, GUMBEL_SELECT, GUMBEL_CHOOSE = 1, 2, 4, 8
+GUMBEL_DRAW = 128             # the number of the Gumbel draw in a child's uniform stream; the noise draws are 0 .. 96
+GUMBEL_PRIOR_FLOOR = 2.0 ** -149
+GUMBEL_WEIGHT_ONE = 16777216.0
+
+
+def considered_visits(max_considered: int, simulations: int) -> torch.Tensor:
+    """The table of Sequential Halving, int32 [Mc + 1, n] on the CPU: row m, simulation t -> the number of simulations a root
+    child must have had to be considered at t, for m candidates and n simulations (csrc/pcb_gumbel.h:considered_row, the
+    schedule of "Policy improvement by planning with Gumbel").  Row 0 is zeros, row 1 is 0 .. n - 1; otherwise, with e the
+    least integer with 2^e >= m, visits[0 .. m) = 0 and nc = m, until n entries exist: extra = max(1, n // (e * nc)); extra
+    times, append visits[0 .. nc) and add 1 to each of them; nc = max(2, nc // 2)."""
+    Mc, n = int(max_considered), int(simulations)
+    if Mc < 1 or Mc > 64 or n < 1:
+        raise ValueError("considered_visits needs max_considered in [1, 64] and simulations >= 1")
+    rows = [[0] * n, list(range(n))]
+    for m in range(2, Mc + 1):
+        e = (m - 1).bit_length()
+        visits, nc, row = [0] * m, m, []
+        while len(row) < n:
+            for _ in range(max(1, n // (e * nc))):
+                row += visits[:nc]
+                visits[:nc] = [v + 1 for v in visits[:nc]]
+            nc = max(2, nc // 2)
+        rows.append(row[:n])
+    return torch.tensor(rows[:Mc + 1], dtype=torch.int32)
+
+
+def _gumbel_rule(max_children, c_visit, c_scale):
+    C, c_visit, c_scale = int(max_children), float(c_visit), float(c_scale)
+    if C < 1 or C > 64 or not (0.0 <= c_visit < float("inf")) or not (0.0 <= c_scale < float("inf")):
+        raise ValueError("the Gumbel rule needs max_children in [1, 64] and finite c_visit, c_scale >= 0")
+    return C, c_visit, c_scale
+
+
+def gumbel_scores(tree: dict, max_children: int, c_visit: float, c_scale: float, seed: int, step_index: int, first_root: int = 0) -> dict:
+    """The quantities of every root's children under the Gumbel rule: the specification of include/pcbenv_gumbel.h's
+    "quantities of a root" in tensor code for any device, no host synchronisation, which csrc/pcb_gumbel.h and the kernel
+    match bit for bit.  tree: a dict with `num_children`, `first_child`, `visits` (integers of any width), `prior`,
+    `value_sum` float64 [P, N] and `reward_lo`, `reward_hi` float64 [P]; not modified.  -> dict(k, fc int64 [P]; ok bool [P]:
+    the root has children in a healthy range; mine bool [P, C]: child c exists; g, logit, qhat, sigma, x = logit + sigma,
+    score = (g + logit) + sigma float64 [P, C], meaningless where mine is False; actions int32 [P, C, 3], zero there).
+    g_c = -ln(-ln u) with u draw number 128 of child c in the uniform stream of (seed, first_root + p, step_index) --
+    `noise_uniform`'s; logit_c = ln(min(prior, 1)), a prior that is not above 2^-149 at that floor; qhat_c = the child's mean
+    value -- the root's where the child has no visit, reward_lo where the root has none either -- normalised by
+    [reward_lo, reward_hi], 0 while that is no range; sigma_c = ((c_visit + the most visits among the children) * c_scale)
+    * qhat_c.  ln is `ieee_ln`."""
+    C, c_visit, c_scale = _gumbel_rule(max_children, c_visit, c_scale)
+    prior, vsum = tree["prior"], tree["value_sum"]
+    dev = prior.device
+    P, N = prior.shape
+    i64 = dict(dtype=torch.int64, device=dev)
+    visits = tree["visits"].to(torch.int64)
+    k, fc = tree["num_children"][:, 0].to(torch.int64), tree["first_child"][:, 0].to(torch.int64)
+    ok = (k >= 1) & (k <= C) & (fc >= 1) & (fc <= N - k)
+    rows, lane = torch.arange(P, **i64), torch.arange(C, **i64)
+    mine = ok[:, None] & (lane[None, :] < k[:, None])
+    ch = torch.where(mine, fc[:, None] + lane[None, :], torch.zeros((), **i64))
+    n_c = visits[rows[:, None], ch]
+    most = torch.where(mine, n_c, torch.full((), -2 ** 31, **i64)).max(dim=1).values
+    lo, hi = tree["reward_lo"], tree["reward_hi"]
+    n_0 = visits[:, 0]
+    vbar = torch.where(n_0 > 0, vsum[:, 0] / n_0.clamp(min=1).to(torch.float64), lo)
+    mean = torch.where(n_c > 0, vsum[rows[:, None], ch] / n_c.clamp(min=1).to(torch.float64), vbar[:, None])
+    wide = hi > lo
+    span = torch.where(wide, hi - lo, torch.ones_like(hi))
+    lo_ = torch.where(wide, lo, torch.zeros_like(lo))
+    qhat = torch.where(wide[:, None], (mean - lo_[:, None]) / span[:, None], torch.zeros_like(mean))
+    pr = prior[rows[:, None], ch]
+    floor = torch.full_like(pr, GUMBEL_PRIOR_FLOOR)
+    logit = ieee_ln(torch.where(pr > floor, torch.where(pr < 1.0, pr, torch.ones_like(pr)), floor))
+    sigma = ((c_visit + most.to(torch.float64)) * c_scale)[:, None] * qhat
+    u = noise_uniform(noise_base(seed, rows + int(first_root), step_index)[:, None], lane[None, :], GUMBEL_DRAW)
+    g = -ieee_ln(-ieee_ln(u))
+    na = tree.get("node_action")
+    actions = None if na is None else torch.where(mine[:, :, None], na[rows[:, None], ch], torch.zeros_like(na[:, :1]).expand(P, C, 3))
+    return dict(k=k, fc=fc, ok=ok, mine=mine, g=g, logit=logit, qhat=qhat, sigma=sigma, x=logit + sigma, score=(g + logit) + sigma, actions=actions)
+
+
+def _best_of(score, within):
+    """The first maximum of score over `within` [P, C] (bool), per row: the lowest child on ties."""
+    return torch.where(within, score, torch.full_like(score, float("-inf"))).argmax(dim=1)
+
+
+def gumbel_select_root(tree: dict, sim_index: torch.Tensor, sim_visits: torch.Tensor, considered: torch.Tensor, max_children: int,
+                       c_visit: float, c_scale: float, seed: int, step_index: int, first_root: int = 0) -> dict:
+    """Level 0 of pcbenv_gumbel_advance's SELECT: its specification in tensor code for any device, no host synchronisation.
+    tree: `gumbel_scores`' and `terminal` [P, N]; sim_index [P], sim_visits [P, C] integers; considered int32 [Mc + 1, n]
+    (`considered_visits`) on the tree's device.  Nothing is modified.  -> dict(scheduled bool [P]: the root makes a scheduled
+    simulation; child int64 [P]: the root child it goes to, 0 elsewhere; sim_index int32 [P], sim_visits int32 [P, C]: the
+    counters afterwards; errors int32 [1]: bit 1 (value 2) if a root that does not stop at slot 0 has a child range outside
+    the tree or a negative sim_index).  A root stops at slot 0 if it is terminal or has no children.  With t = sim_index,
+    0 <= t < n: v = considered[min(Mc, k), t], S = the children with sim_visits == v, or all k if there is none, the child
+    is the argmax of `gumbel_scores`' score over S, ties to the lowest; its counter and sim_index go up by one.  With t >= n
+    the root level is PUCT's and the counters stay."""
+    sc = gumbel_scores(tree, max_children, c_visit, c_scale, seed, step_index, first_root)
+    Mc, n = int(considered.shape[0]) - 1, int(considered.shape[1])
+    k, ok, mine = sc["k"], sc["ok"], sc["mine"]
+    dev = k.device
+    t = sim_index.to(device=dev, dtype=torch.int64)
+    sv = sim_visits.to(device=dev, dtype=torch.int64)
+    goes = ~((tree["terminal"][:, 0] != 0) | (k == 0))
+    scheduled = goes & ok & (t >= 0) & (t < n)
+    v = considered.to(torch.int64)[k.clamp(0, Mc), t.clamp(0, n - 1)]
+    at = mine & (sv == v[:, None])
+    within = mine & (~at.any(dim=1, keepdim=True) | at)
+    child = torch.where(scheduled, _best_of(sc["score"], within), torch.zeros_like(k))
+    lane = torch.arange(sv.shape[1], dtype=torch.int64, device=dev)
+    hit = scheduled[:, None] & (lane[None, :] == child[:, None])
+    errors = ((goes & (~ok | (t < 0))).any().to(torch.int32) * 2).reshape(1)
+    return dict(scheduled=scheduled, child=child, sim_index=(t + scheduled.to(torch.int64)).to(torch.int32),
+                sim_visits=(sv + hit.to(torch.int64)).to(torch.int32), errors=errors)
+
+
+def gumbel_choose(tree: dict, sim_visits: torch.Tensor, max_children: int, c_visit: float, c_scale: float, seed: int, step_index: int,
+                  first_root: int = 0) -> dict:
+    """The move and the policy target of every root under the Gumbel rule: the specification of pcbenv_gumbel_advance's
+    CHOOSE (include/pcbenv_gumbel.h) in tensor code for any device, no host synchronisation.  tree: `gumbel_scores`' and
+    `node_action`; sim_visits [P, C] integers.  Nothing is modified.  -> dict(move_slot int32 [P], move_action int32 [P, 3],
+    child_weights int32 [P, C], child_policy float32 [P, C], child_actions int32 [P, C, 3], root_value float64 [P], errors
+    int32 [1]).  The move is the best score among the children with the most scheduled simulations, ties to the lowest.
+    The target is pi = softmax(logit + sigma) over the k children: e_c = `ieee_exp`(x_c - max x), Z their sum in child
+    order, pi_c = e_c / Z; child_policy = float32(pi), child_weights = int32(pi * 2^24 + 0.5), zero behind k.  A root
+    without children, or with a child range outside the tree (bit 1 of errors): move_slot -1 and zeros."""
+    sc = gumbel_scores(tree, max_children, c_visit, c_scale, seed, step_index, first_root)
+    k, fc, ok, mine, x = sc["k"], sc["fc"], sc["ok"], sc["mine"], sc["x"]
+    dev = k.device
+    P, C = mine.shape
+    sv = sim_visits.to(device=dev, dtype=torch.int64)
+    most = torch.where(mine, sv, torch.full((), -2 ** 31, dtype=torch.int64, device=dev)).max(dim=1).values
+    c = _best_of(sc["score"], mine & (sv == most[:, None]))
+    mx = torch.where(mine, x, torch.full_like(x, float("-inf"))).max(dim=1).values
+    e = torch.where(mine, ieee_exp(torch.where(mine, x - mx[:, None], torch.zeros_like(x))), torch.zeros_like(x))
+    Z = torch.zeros(P, dtype=torch.float64, device=dev)
+    for b in range(C):  # in this order: it is the contract
+        Z = torch.where(mine[:, b], Z + e[:, b], Z)
+    pi = torch.where(mine, e / torch.where(ok, Z, torch.ones_like(Z))[:, None], torch.zeros_like(e))
+    rows = torch.arange(P, dtype=torch.int64, device=dev)
+    slot = torch.where(ok, fc + c, torch.full_like(c, -1))
+    action = torch.where(ok[:, None], sc["actions"][rows, c], torch.zeros_like(sc["actions"][:, 0]))
+    errors = (((k != 0) & ~ok).any().to(torch.int32) * 2).reshape(1)
+    return dict(move_slot=slot.to(torch.int32), move_action=action, child_weights=(pi * GUMBEL_WEIGHT_ONE + 0.5).to(torch.int32),
+                child_policy=pi.to(torch.float32), child_actions=sc["actions"],
+                root_value=tree["value_sum"][:, 0] / tree["visits"][:, 0].to(torch.float64), errors=errors)
+
+
+def new_gumbel_tensors(P: int, C: int, max_considered: int, simulations: int, device) -> dict:
+    """The tensors pcbenv_gumbel_advance takes next to a PUCT tree's, as `BatchedPlacementEnv.gumbel_request` does: the budget
+    of a move `sim_index` [P], `sim_visits` [P, C] (BEGIN zeroes them), the table `considered` [Mc + 1, n], and what CHOOSE
+    writes: `move_slot`, `move_action`, `child_weights`, `child_policy` float32, `child_actions`, `root_value` float64."""
+    i32 = dict(dtype=torch.int32, device=device)
+    return dict(sim_index=torch.zeros(P, **i32), sim_visits=torch.zeros((P, C), **i32), considered=considered_visits(max_considered, simulations).to(device),
+                move_slot=torch.empty(P, **i32), move_action=torch.empty((P, 3), **i32), child_weights=torch.empty((P, C), **i32),
+                child_policy=torch.empty((P, C), dtype=torch.float32, device=device), child_actions=torch.empty((P, C, 3), **i32),
+                root_value=torch.empty(P, dtype=torch.float64, device=device))
+
+
+@dataclass
+class GumbelSearch:
+    """What `gumbel_search` and `gumbel_search_device` return."""
+    search: PuctSearch           # the tree after the search, as `puct_search` reports it
+    sim_index: torch.Tensor      # [P] int32: scheduled simulations made
+    sim_visits: torch.Tensor     # [P, C] int32: of them, per root child
+    move_slot: torch.Tensor      # [P] int32: the slot of the move's child, -1 for a root without children
+    move_action: torch.Tensor    # [P, 3] int32
+    child_weights: torch.Tensor  # [P, C] int32: the policy target in units of 2^-24
+    child_policy: torch.Tensor   # [P, C] float32: the policy target
+    child_actions: torch.Tensor  # [P, C, 3] int32
+    root_value: torch.Tensor     # [P] float64
+
+
+def _gumbel_arguments(root, simulations, max_considered, seed, first_root):
+    n, Mc = int(simulations), int(max_considered)
+    if n < 1 or Mc < 1 or Mc > 64:
+        raise ValueError("a Gumbel search needs simulations >= 1 and max_considered in [1, 64]")
+    if seed is None and not hasattr(root, "run_seed"):
+        raise ValueError("a root without run_seed needs seed")
+    return n, Mc, (int(root.run_seed) ^ 0x67756d62) if seed is None else int(seed), int(getattr(root, "first_env_index", 0) if first_root is None else first_root)
+
+
+def gumbel_search(root, simulations: int, step_index: int, evaluate, max_considered: int = 16, c_visit: float = 50.0, c_scale: float = 1.0,
+                  c_puct: float = 1.0, max_children: int = 16, max_steps=None, capacity=None, tree=None, seed=None, first_root=None,
+                  gumbel_step_index=None) -> GumbelSearch:
+    """The search of one move under the Gumbel rule, the whole of it as specification: `puct_search` with n + 1 =
+    simulations + 1 evaluations whose level 0 is `gumbel_select_root`'s while the budget lasts, then `gumbel_choose`.  A fresh
+    root spends evaluation 0 on its own expansion and then makes exactly n scheduled simulations; a kept root (tree=) makes n
+    scheduled simulations and one PUCT descent.  Below the root every level is PUCT's.  The draws have the key (seed,
+    first_root + p, gumbel_step_index), defaulting to root.run_seed ^ 0x67756d62, root.first_env_index and step_index;
+    capacity defaults to 1 + (n + 1) * max_children."""
+    n, Mc, seed, first = _gumbel_arguments(root, simulations, max_considered, seed, first_root)
+    C, c_visit, c_scale = _gumbel_rule(max_children, c_visit, c_scale)
+    key = int(step_index if gumbel_step_index is None else gumbel_step_index)
+    P, dev = int(root.num_envs), getattr(root, "device", "cpu")
+    table = considered_visits(Mc, n).to(dev)
+    state = dict(sim_index=torch.zeros(P, dtype=torch.int32, device=dev), sim_visits=torch.zeros((P, C), dtype=torch.int32, device=dev))
+
+    def root_select(now, stopped, nxt):
+        sel = gumbel_select_root(now, state["sim_index"], state["sim_visits"], table, C, c_visit, c_scale, seed, key, first)
+        state.update(sim_index=sel["sim_index"], sim_visits=sel["sim_visits"])
+        return torch.where(sel["scheduled"], now["first_child"][:, 0].to(torch.int64) + sel["child"], nxt)
+    ps = puct_search(root, n + 1, step_index, evaluate, c_puct=c_puct, max_children=C, max_steps=max_steps, capacity=capacity, tree=tree,
+                     root_select=root_select)
+    ch = gumbel_choose(search_tree(ps), state["sim_visits"], C, c_visit, c_scale, seed, key, first)
+    return GumbelSearch(ps, state["sim_index"], state["sim_visits"], ch["move_slot"], ch["move_action"], ch["child_weights"], ch["child_policy"],
+                        ch["child_actions"], ch["root_value"])
+
+
+def _gumbel_iterations(root, greq, tree, n, T, evaluate, step_index, seed, key):
+    """The launches of one device Gumbel search on `tree`: BEGIN | SELECT, then n + 1 times `evaluate` followed by ABSORB |
+    SELECT, the last time by ABSORB alone."""
+    root.gumbel_advance(greq, GUMBEL_BEGIN | GUMBEL_SELECT, seed=seed, step_index=key)
+    for m in range(n + 1):
+        ev = evaluate(tree["paths"], tree["path_len"], int(step_index) + m * T)
+        over = ev.terminal.view(torch.uint8) if ev.terminal.dtype == torch.bool else ev.terminal
+        root.gumbel_advance(greq, GUMBEL_ABSORB | (GUMBEL_SELECT if m < n else 0), ev.value, over, ev.cand_count, ev.cand_actions, ev.cand_prior,
+                            seed=seed, step_index=key)
+
+
+def gumbel_search_device(root, simulations: int, step_index: int, evaluate, max_considered: int = 16, c_visit: float = 50.0, c_scale: float = 1.0,
+                         c_puct: float = 1.0, max_children: int = 16, max_steps=None, capacity=None, tree=None, seed=None,
+                         gumbel_step_index=None) -> GumbelSearch:
+    """`gumbel_search` with the tree kept by the device: `root.gumbel_advance` (pcbenv_gumbel_advance) is the one launch per
+    evaluation, with no tensor operation between them: BEGIN | SELECT first -- a fresh tree gets `puct_advance(INIT)` before
+    it -- then n + 1 times `evaluate(tree paths, path_len, step_index + m * max_steps)` followed by ABSORB | SELECT, the last
+    time by ABSORB alone, then CHOOSE.  The same search as `gumbel_search` with the same arguments: the same evaluations, the
+    same tree, counters, move and target, field by field, floats by their bits.
+    tree: the search continues in this tree, in place -- the tensors of `new_puct_tree` and `new_gumbel_tensors` (for this
+    max_considered and simulations) as an earlier search or `puct_move(MOVE_REROOT)` left them."""
+    from . import _lib
+    n, Mc, seed, _ = _gumbel_arguments(root, simulations, max_considered, seed, None)
+    P, C, M, T, N = _puct_arguments(root, n + 1, max_children, max_steps, capacity, tree)
+    key = int(step_index if gumbel_step_index is None else gumbel_step_index)
+    kept = tree is not None
+    if not kept:
+        tree = new_puct_tree(P, N, T, root.device)
+        tree.update(new_gumbel_tensors(P, C, Mc, n, root.device))
+        root.puct_advance(root.puct_request(tree, c_puct, C), _lib.TREE_INIT)
+    greq = root.gumbel_request(tree, c_puct, C, c_visit, c_scale)
+    _gumbel_iterations(root, greq, tree, n, T, evaluate, step_index, seed, key)
+    root.gumbel_advance(greq, GUMBEL_CHOOSE, seed=seed, step_index=key)
+    return GumbelSearch(puct_result(tree, C), tree["sim_index"], tree["sim_visits"], tree["move_slot"], tree["move_action"], tree["child_weights"],
+                        tree["child_policy"], tree["child_actions"], tree["root_value"])
+
+
 @dataclass
 class SelfPlay:
     """What `puct_selfplay` returns: per move (the leading extent M = moves) and root."""
@@ -1039,7 +1293,7 @@ class SelfPlay:
 
 def puct_selfplay(root, evaluate, moves: int, iterations: int, step_index: int = 0, c_puct: float = 1.0, max_children: int = 16,
                   max_steps=None, capacity=None, mode: int = MOVE_GREEDY, seed=None, on_move=None, leaves: int = 1, root_noise=None,
-                  noise_seed=None) -> SelfPlay:
+                  noise_seed=None, gumbel=None, gumbel_seed=None) -> SelfPlay:
     """Plays `moves` moves of every root environment with a PUCT search whose tree stays on the device and is kept from
     move to move.  Per move: `iterations` of search on the kept tree (`evaluate` and one pcbenv_puct_advance launch each,
     as `puct_search_device(tree=)`); `root.puct_move(MOVE_CHOOSE)` -- the visit distribution of the root and the move,
@@ -1060,18 +1314,35 @@ def puct_selfplay(root, evaluate, moves: int, iterations: int, step_index: int =
     root_noise = (alpha, eps): exploration noise on the root's priors, once per root and move
     (`puct_search_device(root_noise=)`): the kept, expanded root of a move before its first descent, a fresh one as soon as
     its first evaluation has expanded it.  The draws of move j have the key (noise_seed, first_env_index + p, step_index
-    + j), noise_seed defaulting to run_seed ^ 0x6e6f6973, so they share no key with the step draws or the move draw."""
+    + j), noise_seed defaulting to run_seed ^ 0x6e6f6973, so they share no key with the step draws or the move draw.
+    gumbel = (max_considered, c_visit, c_scale): every move is a Gumbel search (`gumbel_search_device`) of n = `iterations`
+    simulations, n + 1 evaluations -- iteration m of move j calls evaluate(paths, path_len, step_index + (j * (n + 1) + m) *
+    max_steps) -- and pcbenv_gumbel_advance's CHOOSE stands in the place of `puct_move(MOVE_CHOOSE)`: the move is the best
+    of the most-simulated root children, `child_visits` holds `child_weights`, the policy target softmax(logit +
+    sigma(completed q)) in units of 2^-24, which `visit_targets.cross_entropy` takes as it takes visit counts.  `mode` is not
+    read: the choice is the sample.  The draws of move j have the key (gumbel_seed, first_env_index + p, step_index + j),
+    gumbel_seed defaulting to run_seed ^ 0x67756d62.  The default capacity is 1 + 2 * (n + 1) * max_children; leaves must be
+    1, and together with root_noise it raises ValueError."""
     from . import _lib, _move_lib
     L = int(leaves)
-    P, C, M, T, N = _puct_arguments(root, iterations, max_children, max_steps,
-                                    1 + 2 * int(iterations) * L * int(max_children) if capacity is None else capacity, leaves=L)
+    if gumbel is not None and (root_noise is not None or L != 1):
+        raise ValueError("gumbel= goes with neither root_noise nor leaves > 1")
+    E = int(iterations) + (1 if gumbel is not None else 0)  # evaluations per move
+    P, C, M, T, N = _puct_arguments(root, E, max_children, max_steps, 1 + 2 * E * L * int(max_children) if capacity is None else capacity, leaves=L)
     J = int(moves)
     if J < 1:
         raise ValueError("puct_selfplay needs moves >= 1")
     dev = root.device
     tree = new_puct_tree(P, N, T, dev, L)
     tree.update(new_move_tensors(P, N, C, dev))
+    greq = None
+    if gumbel is not None:
+        n, Mc, gseed, _ = _gumbel_arguments(root, iterations, gumbel[0], gumbel_seed, None)
+        tree.update(new_gumbel_tensors(P, C, Mc, n, dev))
+        greq = root.gumbel_request(tree, c_puct, C, gumbel[1], gumbel[2])
     req, mreq = root.puct_request(tree, c_puct, C) if L == 1 else root.puct_leaves_request(tree, c_puct, C, L), root.puct_move_request(tree, C)
+    if gumbel is not None:
+        root.puct_advance(req, _lib.TREE_INIT)
     seed = (root.run_seed ^ 0x6d6f7665) if seed is None else int(seed)
     noise = _noise_arguments(root, root_noise, noise_seed, None)
     nreq = root.puct_noise_request(tree, C) if noise is not None else None
@@ -1080,11 +1351,16 @@ def puct_selfplay(root, evaluate, moves: int, iterations: int, step_index: int =
                    torch.empty((J, P), dtype=torch.float64, device=dev), torch.empty((J, P), dtype=torch.float64, device=dev),
                    torch.empty((J, P), dtype=torch.uint8, device=dev), torch.empty((J, P), **i32), tree["errors_dev"][0], tree)
     for j in range(J):
-        _puct_iterations(root, req, tree, M, T, evaluate, int(step_index) + j * M * T, _lib.TREE_SELECT if j else _lib.TREE_INIT | _lib.TREE_SELECT, L,
-                         None if noise is None else (nreq, noise[0], noise[1], noise[2], int(step_index) + j))
-        root.puct_move(mreq, _move_lib.MOVE_CHOOSE, mode=mode, seed=seed, step_index=int(step_index) + j)
+        if gumbel is not None:
+            _gumbel_iterations(root, greq, tree, n, T, evaluate, int(step_index) + j * M * T, gseed, int(step_index) + j)
+            root.gumbel_advance(greq, GUMBEL_CHOOSE, seed=gseed, step_index=int(step_index) + j)
+        else:
+            _puct_iterations(root, req, tree, M, T, evaluate, int(step_index) + j * M * T, _lib.TREE_SELECT if j else _lib.TREE_INIT | _lib.TREE_SELECT, L,
+                             None if noise is None else (nreq, noise[0], noise[1], noise[2], int(step_index) + j))
+            root.puct_move(mreq, _move_lib.MOVE_CHOOSE, mode=mode, seed=seed, step_index=int(step_index) + j)
         _, reward, done, _ = root.step(tree["move_action"])
-        out.actions[j], out.child_visits[j], out.child_actions[j], out.root_value[j] = tree["move_action"], tree["child_visits"], tree["child_actions"], tree["root_value"]
+        out.actions[j], out.child_visits[j], out.child_actions[j], out.root_value[j] = (tree["move_action"], tree["child_weights" if gumbel is not None else "child_visits"],
+                                                                                         tree["child_actions"], tree["root_value"])
         out.reward[j], out.done[j] = reward, done
         root.puct_move(mreq, _move_lib.MOVE_REROOT, reset=done)
         out.kept_visits[j] = tree["visits"][:, 0]

@@ -1,5 +1,5 @@
 """Receding-horizon Monte-Carlo lookahead with pcbenv.search.best_of_k against the plain uniform-random policy, c3.
-python tools/search_demo.py [--roots 256] [--k 16] [--playouts | --tree [--device-tree] [--policy] | --puct [--device-priors] [--reuse] [--leaves L] [--noise ALPHA EPS] [--train N [--moves M] [--torch-loss]]]
+python tools/search_demo.py [--roots 256] [--k 16] [--playouts | --tree [--device-tree] [--policy] | --puct [--device-priors] [--reuse] [--leaves L] [--noise ALPHA EPS | --gumbel M] [--train N [--moves M] [--torch-loss]]]
 
 Both play the same instances (one episode per root environment).  The search forks every root k times into a planner
 batch (one device-side gather), plays every child to its end with the on-device sampler, and applies the best child's
@@ -21,7 +21,11 @@ the line then also reports the mean visits a move's root started with.  --puct -
 per root (pcbenv_puct_advance_leaves) and the evaluator sees roots x L nodes at once; k stays the iterations per move, so a
 move costs k x L evaluations.  --puct --noise ALPHA EPS: exploration noise on the root's priors, once per root and move
 (pcbenv_puct_root_noise: a draw from Dir(ALPHA) mixed in with weight EPS); with --reuse the line also reports the share of
-the 16 child entries of a move's root that got no visit (entries behind the root's children included).  --puct --train N (a spatial configuration: --config
+the 16 child entries of a move's root that got no visit (entries behind the root's children included).  --puct --gumbel M:
+the root level of every search is a Gumbel search (pcbenv_gumbel_advance): k simulations per move, k + 1 evaluations, spent by
+Sequential Halving over M candidates, c_visit 50 and c_scale 1; the move is the best of the most-simulated children, and with
+--reuse the policy target is softmax(logit + sigma(completed q)), whose entries without weight zero_visit_share then counts.
+--puct --train N (a spatial configuration: --config
 c4): N rounds of pcbenv.alphazero.AlphaZeroTrainer -- collect() plays --moves moves of every root with puct_selfplay, k
 iterations each, pcbenv/policy.py's model behind network_evaluator(priors="device"); update() trains the model on the visit
 counts with pcbenv_evaluate_visits (--torch-loss: the torch chain instead) -- and one line per round: the mean final reward
@@ -38,7 +42,7 @@ import torch  # noqa: E402
 from pcbenv import named_config  # noqa: E402
 from pcbenv.batched_env import BatchedPlacementEnv  # noqa: E402
 from pcbenv.config import KIND_SPATIAL  # noqa: E402
-from pcbenv.search import (best_of_k, best_of_k_playouts, network_evaluator, policy_backend, puct_search_device, puct_selfplay, tree_search,  # noqa: E402
+from pcbenv.search import (best_of_k, best_of_k_playouts, gumbel_search_device, network_evaluator, policy_backend, puct_search_device, puct_selfplay, tree_search,  # noqa: E402
                            tree_search_device)
 
 
@@ -69,8 +73,9 @@ def train(a, cfg):
     planner.reset()
     torch.manual_seed(0)
     trainer = AlphaZeroTrainer(root, planner, SpatialPolicy(cfg).to(root.device),
-                               AlphaZeroConfig(moves=moves, iterations=a.k, max_children=16, capacity=1 + moves * a.k * a.leaves * 16, device_loss=not a.torch_loss,
-                                               leaves=a.leaves, noise_alpha=a.noise[0] if a.noise else None, noise_eps=a.noise[1] if a.noise else 0.25))
+                               AlphaZeroConfig(moves=moves, iterations=a.k, max_children=16, capacity=1 + moves * (a.k + 1) * a.leaves * 16, device_loss=not a.torch_loss,
+                                               leaves=a.leaves, noise_alpha=a.noise[0] if a.noise else None, noise_eps=a.noise[1] if a.noise else 0.25,
+                                               gumbel_considered=a.gumbel))
     for it in range(a.train):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -104,6 +109,7 @@ def main():
     ap.add_argument("--reuse", action="store_true", help="with --puct: puct_selfplay, the subtree of the move played is kept (pcbenv_puct_move)")
     ap.add_argument("--leaves", type=int, default=1, metavar="L", help="with --puct: L leaves per root and iteration (pcbenv_puct_advance_leaves); k stays the iterations per move")
     ap.add_argument("--noise", type=float, nargs=2, default=None, metavar=("ALPHA", "EPS"), help="with --puct: Dir(ALPHA) noise of weight EPS on the root's priors (pcbenv_puct_root_noise)")
+    ap.add_argument("--gumbel", type=int, default=None, metavar="M", help="with --puct: Gumbel root search, Sequential Halving over M candidates (pcbenv_gumbel_advance)")
     ap.add_argument("--train", type=int, default=0, metavar="N", help="with --puct: N collect/update rounds of pcbenv.alphazero.AlphaZeroTrainer")
     ap.add_argument("--moves", type=int, default=0, help="with --train: moves of every root per round (default: one episode)")
     ap.add_argument("--torch-loss", action="store_true", help="with --train: the policy loss through the torch chain (device_loss off)")
@@ -118,6 +124,8 @@ def main():
         ap.error("--leaves goes with --puct")
     if a.noise and not a.puct:
         ap.error("--noise goes with --puct")
+    if a.gumbel is not None and (not a.puct or a.noise or a.leaves != 1):
+        ap.error("--gumbel goes with --puct, without --noise and --leaves")
     if a.puct and (a.tree or a.playouts):
         ap.error("--puct goes alone")
     if a.device_tree and not a.tree:
@@ -162,7 +170,10 @@ def main():
         nonlocal spent, planner_steps
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        if a.puct:
+        if a.puct and a.gumbel is not None:
+            first = gumbel_search_device(search_root, k, 1000 + t * T * (k + 1), evaluate, max_considered=a.gumbel, max_children=16,
+                                         gumbel_step_index=1000 + t).move_action
+        elif a.puct:
             first = puct_search_device(search_root, k, 1000 + t * T * k, evaluate, max_children=16, leaves=a.leaves, root_noise=a.noise).action
         elif a.tree:
             first = (tree_search_device if a.device_tree else tree_search)(search_root, k, step_index=1000 + t * T * k, backend=backend).action
@@ -179,7 +190,8 @@ def main():
     if a.reuse:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        sp = puct_selfplay(search_root, evaluate, T, k, step_index=1000, max_children=16, leaves=a.leaves, root_noise=a.noise)
+        sp = puct_selfplay(search_root, evaluate, T, k, step_index=1000, max_children=16, leaves=a.leaves, root_noise=a.noise,
+                           gumbel=None if a.gumbel is None else (a.gumbel, 50.0, 1.0))
         torch.cuda.synchronize()
         spent, planner_steps = time.perf_counter() - t0, P * k * a.leaves * T * T
         search_final = final_rewards(search_root, lambda t: (sp.reward[t], sp.done[t]), T)
@@ -197,6 +209,9 @@ def main():
         out["leaves"] = a.leaves
     if a.noise:
         out["noise"] = a.noise
+    if a.gumbel is not None:
+        out["gumbel"] = a.gumbel
+    out["seconds_per_move"] = round(spent / T, 4)
     print(json.dumps(out), flush=True)
     for e in (rand_root, search_root, planner):
         if e is not None:
