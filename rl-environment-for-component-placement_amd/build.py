@@ -12,8 +12,8 @@ the host side -- the C ABI
 (csrc/pcb_policy*.hip), the tree steps with their entry points (csrc/pcb_tree.hip, and csrc/pcb_puct.hip
 for include/pcbenv_search.h, csrc/pcb_puct_leaves.hip for include/pcbenv_leaves.h, csrc/pcb_puct_move.hip for include/pcbenv_move.h,
 csrc/pcb_puct_noise.hip for include/pcbenv_noise.h, csrc/pcb_gumbel.hip for include/pcbenv_gumbel.h;
-what they share is csrc/pcb_group.h, the lane-group kernel skeleton and its launch, and csrc/pcb_tree_host.h, the argument
-checks of their entry points), the masked top-K of a policy's logits (csrc/pcb_top_priors.hip for include/pcbenv_priors.h)
+what they share is csrc/pcb_group.h, the lane-group kernel skeleton and its launch, csrc/pcb_puct_group.h, the PUCT absorb
+and descent of pcb_puct.hip and pcb_gumbel.hip, and csrc/pcb_tree_host.h, the argument checks of their entry points), the masked top-K of a policy's logits (csrc/pcb_top_priors.hip for include/pcbenv_priors.h)
 and the host instance generator
 (csrc/instance_gen.cpp).  csrc/pcb_layout.h is the layout contract both sides compile.
 """

@@ -14,16 +14,16 @@
 //                    at the considered count; the argmax is pcb_group.h's.
 //   choose           Z is formed by every lane of the group with the same loop over a lane shuffle of e, child after child:
 //                    the order of the sum is the contract, so there is no tree reduction, and all lanes hold the same bits.
-//   levels d >= 1    k_puct_advance's select, the same text.
-//   absorb           k_puct_advance's absorb.  That one lives in pcb_puct.hip's unnamed namespace and stays there, so that
-//                    unit's instructions cannot move: pcb_puct.h's pieces are composed a second time below, line by line as
-//                    pcb_puct.hip composes them.
+//   levels d >= 1    k_puct_advance's descent: pcb_puct_group.h's PCB_PUCT_DESCEND, from level 1 on.
+//   absorb           k_puct_advance's absorb: pcb_puct_group.h's absorb_phase, over this unit's argument block.  Neither
+//                    unit's instructions moved when the two copies became one (profiles/model_harness_refactor.txt).
 #include <hip/hip_runtime.h>
 
 #include "pcb_group.h"
 #include "pcb_tree_host.h"
 #include "pcbenv_gumbel.h"
 #include "pcb_gumbel.h"
+#include "pcb_puct_group.h"
 
 static_assert(PCBENV_GUMBEL_BEGIN == pcb_gumbel::PHASE_BEGIN && PCBENV_GUMBEL_ABSORB == pcb_gumbel::PHASE_ABSORB &&
               PCBENV_GUMBEL_SELECT == pcb_gumbel::PHASE_SELECT && PCBENV_GUMBEL_CHOOSE == pcb_gumbel::PHASE_CHOOSE &&
@@ -92,34 +92,6 @@ template <int G> __device__ inline void begin_phase(const Root &r, const GumbelA
     if (lane < r.C) a.sim_visits[(long long)r.p * r.C + lane] = 0;
 }
 
-// puct_absorb, the new children over the lanes; returns the error bits (the same in every lane)
-template <int G> __device__ inline unsigned absorb_phase(const Root &r, const GumbelArgs &a, int lane, int base) {
-    const int selected = a.selected[r.p], count = *r.num_nodes;
-    if (!slot_ok(selected, r.N) || count < 1 || count > r.N) return ERR_TREE;
-    unsigned err = 0u;
-    const int node = selected, depth = r.depth[node], nch = r.num_children[node], term = r.terminal[node];
-    const int leaf_terminal = a.leaf_terminal[r.p], cand_count = a.cand_count[r.p];
-    const double value = a.value[r.p], lo = *r.lo, hi = *r.hi;
-    if (leaf_terminal != 0) {
-        if (lane == 0) r.terminal[node] = 1;
-    } else if (expands(leaf_terminal, nch, term)) {
-        const int k = kept_candidates(cand_count, a.K, r.C);
-        if (k > 0 && count + k <= r.N) {
-            const long long row = (long long)r.p * a.K;
-            if (lane < k) make_child(r, node, count + lane, depth, a.cand_actions + 3 * (row + lane), a.cand_prior[row + lane]);
-            if (lane == 0) link_children(r, node, count, k);
-        } else if (k > 0) err |= ERR_FULL;
-    }
-    unsigned up = 0u;
-    if (lane == 0) {
-        *r.lo = value < lo ? value : lo;
-        *r.hi = value > hi ? value : hi;
-        up = back_up(r, node, value);
-    }
-    err |= __shfl(up, base);
-    return err;
-}
-
 // gumbel_select: the root level by the schedule, then puct_select's levels, child first_child + c of the current node in lane c
 template <int G> __device__ inline unsigned select_phase(const Root &r, const GumbelArgs &a, int lane, int base) {
     unsigned err = 0u;
@@ -146,17 +118,7 @@ template <int G> __device__ inline unsigned select_phase(const Root &r, const Gu
         }
     }
     if (go) {
-        for (; d < r.T; d++) {
-            const int term = r.terminal[node], k = r.num_children[node], fc = r.first_child[node], vis = r.visits[node];
-            if (stops(term, k)) break;
-            if (!children_ok(fc, k, r.N, r.C)) { err |= ERR_TREE; break; }
-            const bool mine = lane < k;
-            const int ch = fc + (mine ? lane : 0);
-            double s = mine ? puct_score(r.value_sum[ch], r.visits[ch], r.prior[ch], lo, hi, a.c_puct, vis) : neg_inf();
-            PCB_GROUP_ARGMAX(G, mine, lane, s, c, beats)
-            node = fc + __shfl(c, base);  // lane 0's verdict: one node per group whatever the scores were
-            if (lane < 3) a.paths[step_major(d, r.P, r.p, lane)] = r.node_action[3 * node + lane];
-        }
+        PCB_PUCT_DESCEND(G, r, a, lane, base, lo, hi, node, d, err)
     }
     if (lane == 0) { a.selected[r.p] = node; a.path_len[r.p] = d; }
     return err;

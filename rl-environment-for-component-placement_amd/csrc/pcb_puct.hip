@@ -5,21 +5,15 @@
 //
 // The step of one root is pcb_puct.h (puct_init, puct_select, puct_absorb: the text tools/puct_model_check.cpp replays
 // on the CPU); the kernel composes the same pieces with a group of G lanes per root: the mapping, the phases and the
-// fence between them are pcb_group.h's.  What a lane loads and stores:
-//   select   lane c of the group owns child first_child + c of the current node.  Per level two load round trips: the
-//            node's terminal, num_children, first_child and visits together, then the children's visits, value_sum and
-//            prior -- consecutive slots, so a group's loads are contiguous; k_tree_advance has to gather them.  The group
-//            argmax (pcb_tree::beats: the lowest child on ties) is a shuffle butterfly; the winner's action is copied to
-//            the path row by lanes 0..2 while the next level's loads are already under way.
-//   absorb   lanes c < k write one child slot each; lane 0 writes the node's fields and the scalars and walks the backup
-//            chain -- one round trip per level: a node's parent, visits, value_sum and value_max are loaded together.
-//   init     the slots of a root are contiguous: the lanes stride them.
+// fence between them are pcb_group.h's.  The absorb and the descent of the select are pcb_puct_group.h's, which says what
+// a lane loads and stores in them (k_gumbel_advance runs the same two); init is here: the slots of a root are contiguous,
+// the lanes stride them.
 #include <hip/hip_runtime.h>
 
 #include "pcb_group.h"
 #include "pcb_tree_host.h"
 #include "pcbenv_search.h"
-#include "pcb_puct.h"
+#include "pcb_puct_group.h"
 
 static_assert(PCBENV_TREE_INIT == pcb_puct::PHASE_INIT && PCBENV_TREE_ABSORB == pcb_puct::PHASE_ABSORB &&
               PCBENV_TREE_SELECT == pcb_puct::PHASE_SELECT && PCBENV_MAX_TREE_CHILDREN == pcb_puct::MAX_CHILDREN,
@@ -52,50 +46,12 @@ template <int G> __device__ inline void init_phase(const Root &r, int lane) {
     if (lane == 0) init_scalars(r);
 }
 
-// puct_absorb, the new children over the lanes; returns the error bits (the same in every lane)
-template <int G> __device__ inline unsigned absorb_phase(const Root &r, const PuctArgs &a, int lane, int base) {
-    const int selected = a.selected[r.p], count = *r.num_nodes;
-    if (!slot_ok(selected, r.N) || count < 1 || count > r.N) return ERR_TREE;
-    unsigned err = 0u;
-    const int node = selected, depth = r.depth[node], nch = r.num_children[node], term = r.terminal[node];
-    const int leaf_terminal = a.leaf_terminal[r.p], cand_count = a.cand_count[r.p];
-    const double value = a.value[r.p], lo = *r.lo, hi = *r.hi;
-    if (leaf_terminal != 0) {
-        if (lane == 0) r.terminal[node] = 1;
-    } else if (expands(leaf_terminal, nch, term)) {
-        const int k = kept_candidates(cand_count, a.K, r.C);
-        if (k > 0 && count + k <= r.N) {
-            const long long row = (long long)r.p * a.K;
-            if (lane < k) make_child(r, node, count + lane, depth, a.cand_actions + 3 * (row + lane), a.cand_prior[row + lane]);
-            if (lane == 0) link_children(r, node, count, k);
-        } else if (k > 0) err |= ERR_FULL;
-    }
-    unsigned up = 0u;
-    if (lane == 0) {
-        *r.lo = value < lo ? value : lo;
-        *r.hi = value > hi ? value : hi;
-        up = back_up(r, node, value);
-    }
-    err |= __shfl(up, base);
-    return err;
-}
-
 // puct_select, child first_child + c of the current node in lane c
 template <int G> __device__ inline unsigned select_phase(const Root &r, const PuctArgs &a, int lane, int base) {
     unsigned err = 0u;
     const double lo = *r.lo, hi = *r.hi;
     int node = 0, d = 0;
-    for (; d < r.T; d++) {
-        const int term = r.terminal[node], k = r.num_children[node], fc = r.first_child[node], vis = r.visits[node];
-        if (stops(term, k)) break;
-        if (!children_ok(fc, k, r.N, r.C)) { err |= ERR_TREE; break; }
-        const bool mine = lane < k;
-        const int ch = fc + (mine ? lane : 0);
-        double s = mine ? puct_score(r.value_sum[ch], r.visits[ch], r.prior[ch], lo, hi, a.c_puct, vis) : neg_inf();
-        PCB_GROUP_ARGMAX(G, mine, lane, s, c, beats)
-        node = fc + __shfl(c, base);  // lane 0's verdict: one node per group whatever the scores were
-        if (lane < 3) a.paths[step_major(d, r.P, r.p, lane)] = r.node_action[3 * node + lane];
-    }
+    PCB_PUCT_DESCEND(G, r, a, lane, base, lo, hi, node, d, err)
     if (lane == 0) { a.selected[r.p] = node; a.path_len[r.p] = d; }
     return err;
 }

@@ -22,16 +22,12 @@ puct_cases.PRIORS -- equal priors, hence equal PUCT scores below the root -- and
 enough for the larger roots to run out of slots: ERR_FULL.  ERR_TREE comes from the damage cases: the caller stores one
 out-of-range value into root DAMAGE_ROOT before a call."""
 import functools
-import os
-import shutil
-import struct
-import subprocess
-import tempfile
 from types import SimpleNamespace
 
 import numpy as np
 import torch
 
+import model_harness as mh
 import puct_cases as pc
 from pcbenv.search import considered_visits
 
@@ -84,36 +80,14 @@ def shapes(P, N, C, levels=T):
     return s
 
 
-@functools.lru_cache(maxsize=None)
 def program():
-    """tools/gumbel_check.cpp built with the sanitizers, a program of its own; None without g++."""
-    if shutil.which("g++") is None:
-        return None
-    exe = os.path.join(tempfile.mkdtemp(prefix="gumbel_"), "gumbel_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(REPO, "rl-environment-for-component-placement_amd", "csrc"),
-                    "-o", exe, os.path.join(REPO, "tools", "gumbel_check.cpp")], check=True)
-    return exe
-
-
-def _program_words(words):
-    done = subprocess.run([program()], input=np.concatenate(words).tobytes(), capture_output=True)
-    assert done.returncode == 0 and done.stderr == b"", done.stderr.decode()
-    return np.frombuffer(done.stdout, np.int64)
+    """tools/gumbel_check.cpp as tests/model_harness.py:tool builds it; None without g++."""
+    return mh.tool("gumbel_check")
 
 
 def model_row(m, n):
     """csrc/pcb_gumbel.h:considered_row(m, n)."""
-    return _program_words([np.array([1, m, n], np.int64)]).tolist()
-
-
-def _bits(x):
-    return struct.unpack("<q", struct.pack("<d", float(x)))[0]
-
-
-def _u64(x):
-    return int(np.uint64(x & (2 ** 64 - 1)).astype(np.int64))
+    return mh.run_words(program(), [np.array([1, m, n], np.int64)]).tolist()
 
 
 def call(phases, evaluation=None, pokes=(), seed=SEED, step_index=77, first_root=0):
@@ -127,30 +101,16 @@ def run(state, C, K, n, Mc, rule, seq, levels=T):
     on anything on stderr.  levels: T, read off nothing: `paths` is [levels, P, 3]."""
     P, N = state["parent"].shape
     table = considered_visits(Mc, n).numpy()
-    words = [np.array([0, P, N, C, levels, K, n, Mc, len(seq)] + [_bits(x) for x in rule], np.int64), table.astype(np.int64).ravel()]
-    words += [pc._words(state[f], f in FLOATS) for f in STATE_FIELDS]
+    words = [np.array([0, P, N, C, levels, K, n, Mc, len(seq)] + [mh.bits(x) for x in rule], np.int64), table.astype(np.int64).ravel()]
+    words += [mh.words(state[f], f in FLOATS) for f in STATE_FIELDS]
     for c in seq:
-        words.append(np.array([c["phases"], _u64(c["seed"]), _u64(c["step_index"]), c["first_root"], len(c["pokes"])] +
+        words.append(np.array([c["phases"], mh.u64(c["seed"]), mh.u64(c["step_index"]), c["first_root"], len(c["pokes"])] +
                               [w for name, at, value in c["pokes"] for w in (POKED.index(name), at, value)], np.int64))
         if c["phases"] & ABSORB:
             value, over, count, actions, prior = c["evaluation"]
             assert actions.shape == (P, K, 3) and prior.shape == (P, K) and prior.dtype == np.float32
-            words += [pc._words(value, True), pc._words(over), pc._words(count), pc._words(actions), np.ascontiguousarray(prior).view(np.uint32).astype(np.int64).ravel()]
-    out = _program_words(words)
-    shp = shapes(P, N, C, levels)
-    per_call = 1 + sum(int(np.prod(shp[f])) for f in STATE_FIELDS + OUT_FIELDS)
-    assert len(out) == per_call * len(seq)
-    states = []
-    for i in range(len(seq)):
-        w = out[i * per_call:(i + 1) * per_call]
-        st, at = {"errors": int(w[0])}, 1
-        for f in STATE_FIELDS + OUT_FIELDS:
-            size = int(np.prod(shp[f]))
-            part = w[at:at + size]
-            st[f] = (part.view(np.float64) if f in FLOATS else part.astype(np.uint32).view(np.float32) if f == "child_policy" else part).reshape(shp[f])
-            at += size
-        states.append(st)
-    return states
+            words += [mh.words(value, True), mh.words(over), mh.words(count), mh.words(actions), mh.float32_words(prior)]
+    return mh.cut(mh.run_words(program(), words), len(seq), STATE_FIELDS + OUT_FIELDS, shapes(P, N, C, levels), FLOATS, ("child_policy",))
 
 
 def few_children(C, Mc, p):

@@ -19,20 +19,16 @@ healthy search with one call before which the caller has written out-of-range va
 csrc/pcb_puct.h's promise that such a tree stops the walk and reports ERR_TREE."""
 import functools
 import math
-import os
-import shutil
-import struct
-import subprocess
-import tempfile
 from types import SimpleNamespace
 
 import numpy as np
 import torch
 
+import model_harness as mh
 import tree_cases
+from model_harness import REPO, flat, same_bits, words as _words  # noqa: F401  (the other case modules and the tests take them from here)
 from pcbenv.search import Evaluation, puct_search
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INIT, ABSORB, SELECT = 1, 2, 4
 ERR_FULL, ERR_TREE = 1, 2  # the bits of the error word
 FILL = -7  # what the model's int32 tensors hold before the first call
@@ -51,17 +47,9 @@ def shapes(P, N, T):
     return s
 
 
-@functools.lru_cache(maxsize=None)
 def program():
-    """tools/puct_model_check.cpp built as tests/tree_cases.py builds its tool; None without g++."""
-    if shutil.which("g++") is None:
-        return None
-    exe = os.path.join(tempfile.mkdtemp(prefix="puct_model_"), "puct_model_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(REPO, "rl-environment-for-component-placement_amd", "csrc"),
-                    "-o", exe, os.path.join(REPO, "tools", "puct_model_check.cpp")], check=True)
-    return exe
+    """tools/puct_model_check.cpp as tests/model_harness.py:tool builds it; None without g++."""
+    return mh.tool("puct_model_check")
 
 
 def record(P, T, iterations, c_puct, max_children, evaluate, step_index=0, capacity=None, cfg=None, tree=None):
@@ -97,16 +85,11 @@ def search_calls(calls, split=False):
     return out
 
 
-def _words(a, floats=False):
-    a = np.ascontiguousarray(a)
-    return (a.astype(np.float64).view(np.int64) if floats else a.astype(np.int64)).ravel()
-
-
 def replay(P, N, C, T, K, c_puct, seq):
     """-> [state after call i]: dicts of STATE_FIELDS (int64; FLOATS as float64) and `errors`.  Raises if the program
     reports a selection that differs from the recorded one, or anything on stderr.  A call may carry `pokes`, a list of
     (tensor of POKED, flat index, value) stored into the state before its phases run."""
-    parts = [np.array([P, N, C, T, K, len(seq), struct.unpack("<q", struct.pack("<d", float(c_puct)))[0]], np.int64)]
+    parts = [np.array([P, N, C, T, K, len(seq), mh.bits(c_puct)], np.int64)]
     for c in seq:
         pokes = c.get("pokes", ())
         parts.append(np.array([c["phases"] | (POKED_CALL if pokes else 0), int(c["expect"] is not None)] +
@@ -114,30 +97,10 @@ def replay(P, N, C, T, K, c_puct, seq):
         if c["phases"] & ABSORB:
             value, over, count, actions, prior = c["evaluation"]
             assert actions.shape == (P, K, 3) and prior.shape == (P, K) and prior.dtype == np.float32
-            parts += [_words(value, True), _words(over), _words(count), _words(actions), np.ascontiguousarray(prior).view(np.uint32).astype(np.int64).ravel()]
+            parts += [_words(value, True), _words(over), _words(count), _words(actions), mh.float32_words(prior)]
         if c["expect"] is not None:
             parts += [_words(c["expect"][1]), _words(c["expect"][0])]
-    run = subprocess.run([program()], input=np.concatenate(parts).tobytes(), capture_output=True)
-    assert run.returncode == 0 and run.stderr == b"", run.stderr.decode()
-    words = np.frombuffer(run.stdout, np.int64)
-    shp = shapes(P, N, T)
-    per_call = 1 + sum(int(np.prod(shp[f])) for f in STATE_FIELDS)
-    assert len(words) == per_call * len(seq)
-    states = []
-    for i in range(len(seq)):
-        w = words[i * per_call:(i + 1) * per_call]
-        st, at = {"errors": int(w[0])}, 1
-        for f in STATE_FIELDS:
-            n = int(np.prod(shp[f]))
-            st[f] = (w[at:at + n].view(np.float64) if f in FLOATS else w[at:at + n]).reshape(shp[f])
-            at += n
-        states.append(st)
-    return states
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+    return mh.cut(mh.run_words(program(), parts), len(seq), STATE_FIELDS, shapes(P, N, T), FLOATS)
 
 
 def compare_with_search(state, ps):
@@ -278,10 +241,6 @@ DAMAGE_GAMES = {4: (9, 5, 3, 3, 12, (1, 2, 3)), 16: (7, 5, 9, 9, 12, (1, 2, 3)),
 DAMAGE = ("selected_N", "selected_minus_1", "num_nodes_0", "num_nodes_N_plus_1", "first_child_0", "first_child_N", "first_child_plus_k_over_N",
           "num_children_minus_1", "num_children_C_plus_5", "parent_N", "parent_self", "cand_count_minus_3", "cand_count_K_plus_5")
 DAMAGE_CASES = [(G, n) for G in DAMAGE_GAMES for n in DAMAGE]
-
-
-def flat(shape, *index):
-    return int(np.ravel_multi_index(index, shape))
 
 
 @functools.lru_cache(maxsize=None)

@@ -16,16 +16,12 @@ GAMES: one per group width of k_puct_advance that tests/puct_cases.py:damaged kn
 rows of puct_cases.WIDTHS, T = 5; and a C = 1 chain, T = 70, whose kept tree passes slot 64.  The capacity is chosen so that
 the tree fills: see `check_game` for what each game has to reach."""
 import functools
-import os
-import shutil
-import struct
-import subprocess
-import tempfile
 from types import SimpleNamespace
 
 import numpy as np
 import torch
 
+import model_harness as mh
 import puct_cases as pc
 import puct_move_cases as mc
 from pcbenv.search import puct_choose, puct_reroot, search_tree
@@ -55,17 +51,9 @@ def shapes(P, N, C, T):
     return dict(pc.shapes(P, N, T), **mc.shapes(P, N, C))
 
 
-@functools.lru_cache(maxsize=None)
 def program():
-    """tools/puct_game_check.cpp built with the sanitizers, a program of its own; None without g++."""
-    if shutil.which("g++") is None:
-        return None
-    exe = os.path.join(tempfile.mkdtemp(prefix="puct_game_"), "puct_game_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(REPO, "rl-environment-for-component-placement_amd", "csrc"),
-                    "-o", exe, os.path.join(REPO, "tools", "puct_game_check.cpp")], check=True)
-    return exe
+    """tools/puct_game_check.cpp as tests/model_harness.py:tool builds it; None without g++."""
+    return mh.tool("puct_game_check")
 
 
 def done_of(P, j):
@@ -111,38 +99,23 @@ def calls(game):
 def run(P, N, C, T, K, c_puct, seq):
     """-> [state after call i]: dicts of STATE_FIELDS (int64; FLOATS as float64) and `errors`, the error bits of that call.
     Raises if the program reports a selection that differs from the recorded one, or anything on stderr."""
-    w = pc._words
-    parts = [np.array([P, N, C, T, K, len(seq), struct.unpack("<q", struct.pack("<d", float(c_puct)))[0]], np.int64)]
+    w = mh.words
+    parts = [np.array([P, N, C, T, K, len(seq), mh.bits(c_puct)], np.int64)]
     for c in seq:
         if c["kind"] == ADVANCE:
             parts.append(np.array([ADVANCE, c["phases"], int(c["expect"] is not None)], np.int64))
             if c["phases"] & pc.ABSORB:
                 value, over, count, actions, prior = c["evaluation"]
                 assert actions.shape == (P, K, 3) and prior.shape == (P, K) and prior.dtype == np.float32
-                parts += [w(value, True), w(over), w(count), w(actions), np.ascontiguousarray(prior).view(np.uint32).astype(np.int64).ravel()]
+                parts += [w(value, True), w(over), w(count), w(actions), mh.float32_words(prior)]
             if c["expect"] is not None:
                 parts += [w(c["expect"][1]), w(c["expect"][0])]
         else:
-            parts.append(np.array([MOVE, c["phases"], c["mode"], np.uint64(c["seed"]).astype(np.int64), c["step_index"], c["first_root"],
+            parts.append(np.array([MOVE, c["phases"], c["mode"], mh.u64(c["seed"]), c["step_index"], c["first_root"],
                                    int(c["reset"] is not None)], np.int64))
             if c["reset"] is not None:
                 parts.append(w(c["reset"]))
-    done = subprocess.run([program()], input=np.concatenate(parts).tobytes(), capture_output=True)
-    assert done.returncode == 0 and done.stderr == b"", done.stderr.decode()
-    words = np.frombuffer(done.stdout, np.int64)
-    shp = shapes(P, N, C, T)
-    per_call = 1 + sum(int(np.prod(shp[f])) for f in STATE_FIELDS)
-    assert len(words) == per_call * len(seq)
-    states = []
-    for i in range(len(seq)):
-        wd = words[i * per_call:(i + 1) * per_call]
-        st, at = {"errors": int(wd[0])}, 1
-        for f in STATE_FIELDS:
-            n = int(np.prod(shp[f]))
-            st[f] = (wd[at:at + n].view(np.float64) if f in FLOATS else wd[at:at + n]).reshape(shp[f])
-            at += n
-        states.append(st)
-    return states
+    return mh.cut(mh.run_words(program(), parts), len(seq), STATE_FIELDS, shapes(P, N, C, T), FLOATS)
 
 
 @functools.lru_cache(maxsize=None)

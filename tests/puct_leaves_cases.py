@@ -16,16 +16,12 @@ csrc/pcb_puct_leaves.h:leaves_score one by one -- checks the model's choice on t
 assertions of tests/test_puct_leaves_model.py ask for."""
 import functools
 import math
-import os
-import shutil
-import struct
-import subprocess
-import tempfile
 from types import SimpleNamespace
 
 import numpy as np
 import torch
 
+import model_harness as mh
 from pcbenv.search import Evaluation, puct_search
 from puct_cases import ABSORB, INIT, SELECT, ERR_FULL, ERR_TREE, FLOATS, POKED_CALL, REPO, TREE_FIELDS, _words, flat, same_bits, search_calls, synthetic_evaluator  # noqa: F401
 from puct_cases import PRIORS, _mix
@@ -42,17 +38,9 @@ def shapes(P, N, T, L):
     return s
 
 
-@functools.lru_cache(maxsize=None)
 def program():
-    """tools/puct_leaves_check.cpp built exactly as tests/puct_cases.py:program builds its tool; None without g++."""
-    if shutil.which("g++") is None:
-        return None
-    exe = os.path.join(tempfile.mkdtemp(prefix="puct_leaves_"), "puct_leaves_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(REPO, "rl-environment-for-component-placement_amd", "csrc"),
-                    "-o", exe, os.path.join(REPO, "tools", "puct_leaves_check.cpp")], check=True)
-    return exe
+    """tools/puct_leaves_check.cpp as tests/model_harness.py:tool builds it; None without g++."""
+    return mh.tool("puct_leaves_check")
 
 
 def per_leaf(base, P, T, K, L):
@@ -128,7 +116,7 @@ def replay(P, N, C, T, K, L, c_puct, seq, via=0):
     via=1 (L == 1 only): the same calls through csrc/pcb_puct.h.  A call may carry `load`, a tree that replaces the state's
     before its phases run."""
     R = P * L
-    parts = [np.array([P, N, C, T, K, L, via, len(seq), struct.unpack("<q", struct.pack("<d", float(c_puct)))[0]], np.int64)]
+    parts = [np.array([P, N, C, T, K, L, via, len(seq), mh.bits(c_puct)], np.int64)]
     for c in seq:
         pokes = c.get("pokes", ())
         load = c.get("load")
@@ -140,25 +128,10 @@ def replay(P, N, C, T, K, L, c_puct, seq, via=0):
         if c["phases"] & ABSORB:
             value, over, count, actions, prior = c["evaluation"]
             assert actions.shape == (R, K, 3) and prior.shape == (R, K) and prior.dtype == np.float32
-            parts += [_words(value, True), _words(over), _words(count), _words(actions), np.ascontiguousarray(prior).view(np.uint32).astype(np.int64).ravel()]
+            parts += [_words(value, True), _words(over), _words(count), _words(actions), mh.float32_words(prior)]
         if c["expect"] is not None:
             parts += [_words(c["expect"][1]), _words(c["expect"][0])]
-    run = subprocess.run([program()], input=np.concatenate(parts).tobytes(), capture_output=True)
-    assert run.returncode == 0 and run.stderr == b"", run.stderr.decode()
-    words = np.frombuffer(run.stdout, np.int64)
-    shp = shapes(P, N, T, L)
-    per_call = 1 + sum(int(np.prod(shp[f])) for f in STATE_FIELDS)
-    assert len(words) == per_call * len(seq)
-    states = []
-    for i in range(len(seq)):
-        w = words[i * per_call:(i + 1) * per_call]
-        st, at = {"errors": int(w[0])}, 1
-        for f in STATE_FIELDS:
-            n = int(np.prod(shp[f]))
-            st[f] = (w[at:at + n].view(np.float64) if f in FLOATS else w[at:at + n]).reshape(shp[f])
-            at += n
-        states.append(st)
-    return states
+    return mh.cut(mh.run_words(program(), parts), len(seq), STATE_FIELDS, shapes(P, N, T, L), FLOATS)
 
 
 def compare_with_search(state, ps):

@@ -18,17 +18,15 @@ and dropped slots alternate in every chunk, and trees that fill N = 256, 257 and
 from a tree and its moves alone, where pass 1 of REROOT finds every verdict it has to ask for; `check_constructed` asserts
 what each shape is there for.  `damaged_deep` damages the third span of two of them."""
 import functools
-import os
-import shutil
-import subprocess
-import tempfile
 from types import SimpleNamespace
 
 import numpy as np
 import torch
 
+import model_harness as mh
 import puct_cases as pc
 import sampling_contract as sc
+from model_harness import flat, words as _words  # noqa: F401  (the tests take them from here)
 from pcbenv.search import Evaluation
 
 REPO = pc.REPO
@@ -52,22 +50,9 @@ def shapes(P, N, C):
     return s
 
 
-@functools.lru_cache(maxsize=None)
 def program():
-    """tools/puct_move_check.cpp built with the sanitizers, a program of its own; None without g++."""
-    if shutil.which("g++") is None:
-        return None
-    exe = os.path.join(tempfile.mkdtemp(prefix="puct_move_"), "puct_move_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(REPO, "rl-environment-for-component-placement_amd", "csrc"),
-                    "-o", exe, os.path.join(REPO, "tools", "puct_move_check.cpp")], check=True)
-    return exe
-
-
-def _words(a, floats=False):
-    a = np.ascontiguousarray(a)
-    return (a.astype(np.float64).view(np.int64) if floats else a.astype(np.int64)).ravel()
+    """tools/puct_move_check.cpp as tests/model_harness.py:tool builds it; None without g++."""
+    return mh.tool("puct_move_check")
 
 
 def call(phases, mode=GREEDY, move_slot=None, reset=None, pokes=(), seed=SEED, step_index=STEP, first_root=FIRST_ROOT):
@@ -80,25 +65,10 @@ def run(tree, C, seq):
     P, N = tree["parent"].shape
     parts = [np.array([P, N, C, len(seq)], np.int64)] + [_words(tree[f], f in FLOATS) for f in TREE_FIELDS]
     for c in seq:
-        parts.append(np.array([c["phases"], c["mode"], np.uint64(c["seed"]).astype(np.int64), c["step_index"], c["first_root"], int(c["move_slot"] is not None),
+        parts.append(np.array([c["phases"], c["mode"], mh.u64(c["seed"]), c["step_index"], c["first_root"], int(c["move_slot"] is not None),
                                int(c["reset"] is not None), len(c["pokes"])] + [w for name, at, value in c["pokes"] for w in (POKED.index(name), at, value)], np.int64))
         parts += [_words(c[f]) for f in ("move_slot", "reset") if c[f] is not None]
-    done = subprocess.run([program()], input=np.concatenate(parts).tobytes(), capture_output=True)
-    assert done.returncode == 0 and done.stderr == b"", done.stderr.decode()
-    words = np.frombuffer(done.stdout, np.int64)
-    shp = shapes(P, N, C)
-    per_call = 1 + sum(int(np.prod(shp[f])) for f in STATE_FIELDS)
-    assert len(words) == per_call * len(seq)
-    states = []
-    for i in range(len(seq)):
-        w = words[i * per_call:(i + 1) * per_call]
-        st, at = {"errors": int(w[0])}, 1
-        for f in STATE_FIELDS:
-            n = int(np.prod(shp[f]))
-            st[f] = (w[at:at + n].view(np.float64) if f in FLOATS else w[at:at + n]).reshape(shp[f])
-            at += n
-        states.append(st)
-    return states
+    return mh.cut(mh.run_words(program(), parts), len(seq), STATE_FIELDS, shapes(P, N, C), FLOATS)
 
 
 # ---- the trees -----------------------------------------------------------------------------------------------------
@@ -498,10 +468,6 @@ def modelled(name, way, reset=True):
 DAMAGE_SHAPE = "G16_C16_P35"
 DAMAGE = ("num_nodes_0", "num_nodes_N_plus_1", "move_slot_N", "move_slot_minus_2", "parent_self", "parent_N", "num_children_minus_1",
           "num_children_C_plus_5", "first_child_0", "first_child_n", "child_range_not_kept")
-
-
-def flat(shape, *index):
-    return int(np.ravel_multi_index(index, shape))
 
 
 @functools.lru_cache(maxsize=None)

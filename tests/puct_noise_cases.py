@@ -11,15 +11,12 @@ Child ranges start at varying slots, every prior of the [P, N] tensor -- childre
 a store to a slot that is no child of the root shows.  Every case is called twice with the same arguments: the second call
 is a no-op."""
 import functools
-import os
-import shutil
-import subprocess
-import tempfile
 from types import SimpleNamespace
 
 import numpy as np
 import torch
 
+import model_harness as mh
 import puct_cases as pc
 from pcbenv.search import noise_base, noise_gammas
 
@@ -59,27 +56,9 @@ def group_lanes(C):
     return g
 
 
-@functools.lru_cache(maxsize=None)
 def program():
-    """tools/puct_noise_check.cpp built with the sanitizers, a program of its own; None without g++."""
-    if shutil.which("g++") is None:
-        return None
-    exe = os.path.join(tempfile.mkdtemp(prefix="puct_noise_"), "puct_noise_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(REPO, "rl-environment-for-component-placement_amd", "csrc"),
-                    "-o", exe, os.path.join(REPO, "tools", "puct_noise_check.cpp")], check=True)
-    return exe
-
-
-def _bits(x):
-    return np.ascontiguousarray(x, dtype=np.float64).view(np.int64).ravel()
-
-
-def _program_words(words):
-    done = subprocess.run([program()], input=np.concatenate(words).tobytes(), capture_output=True)
-    assert done.returncode == 0 and done.stderr == b"", done.stderr.decode()
-    return np.frombuffer(done.stdout, np.int64)
+    """tools/puct_noise_check.cpp as tests/model_harness.py:tool builds it; None without g++."""
+    return mh.tool("puct_noise_check")
 
 
 def call(alpha, eps, seed=SEED, step_index=77, first_root=0):
@@ -91,18 +70,10 @@ def run(tree, C, seq):
     float64 [P, N], noised int64 [P] and `errors`, the error bits of that call.  Raises on anything on stderr."""
     P, N = tree["prior"].shape
     words = [np.array([0, P, N, C, len(seq)], np.int64), tree["num_children"].astype(np.int64).ravel(), tree["first_child"].astype(np.int64).ravel(),
-             _bits(tree["prior"]), tree["noised"].astype(np.int64).ravel()]
+             mh.words(tree["prior"], True), tree["noised"].astype(np.int64).ravel()]
     for c in seq:
-        words += [np.array([np.uint64(c["seed"]).astype(np.int64), np.uint64(c["step_index"]).astype(np.int64), c["first_root"]], np.int64),
-                  _bits([c["alpha"], c["eps"]])]
-    out = _program_words(words)
-    per_call = 1 + P * N + P
-    assert len(out) == per_call * len(seq)
-    states = []
-    for i in range(len(seq)):
-        w = out[i * per_call:(i + 1) * per_call]
-        states.append(dict(errors=int(w[0]), prior=w[1:1 + P * N].view(np.float64).reshape(P, N), noised=w[1 + P * N:].reshape(P)))
-    return states
+        words += [np.array([mh.u64(c["seed"]), mh.u64(c["step_index"]), c["first_root"], mh.bits(c["alpha"]), mh.bits(c["eps"])], np.int64)]
+    return mh.cut(mh.run_words(program(), words), len(seq), ("prior", "noised"), {"prior": (P, N), "noised": (P,)}, ("prior",))
 
 
 FUNCTIONS = ("ieee_ln", "ieee_exp", "ieee_sqrt")
@@ -112,7 +83,7 @@ def model_function(name, x):
     """csrc/pcb_ieee_math.h's function `name` of every element of x (float64), from the model program."""
     x = np.ascontiguousarray(x, dtype=np.float64).ravel()
     pairs = np.stack([np.full(len(x), FUNCTIONS.index(name), np.int64), x.view(np.int64)], axis=1).ravel()
-    return _program_words([np.array([1, len(x)], np.int64), pairs]).view(np.float64)
+    return mh.run_words(program(), [np.array([1, len(x)], np.int64), pairs]).view(np.float64)
 
 
 def part_children(C, p):

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 
 import logits_cases as lc
+import model_harness
 from pcbenv.config import KIND_PIN, KIND_RECT, KIND_SQUARE
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,13 +34,8 @@ def _rows_text():
     return "\n".join(lines) + "\n", rows
 
 
-def test_axis_set_check_program(tmp_path):
-    exe = str(tmp_path / "axis_set_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(REPO, "include"),
-                    "-I", os.path.join(REPO, "rl-environment-for-component-placement_amd", "csrc"),
-                    "-o", exe, os.path.join(REPO, "tools", "axis_set_check.cpp")], check=True)
+def test_axis_set_check_program():
+    exe = model_harness.tool("axis_set_check", include=True)
     text, rows = _rows_text()
     run = subprocess.run([exe], input=text, capture_output=True, text=True)
     assert run.returncode == 0, run.stdout + run.stderr

@@ -2,14 +2,13 @@
 prototype (argument count, every argument's ctypes type, the return type) and every struct (member names, member types
 and -- with a C compiler at hand -- size and every member's offset).  No compute call is made."""
 import ctypes as C
-import os
 import re
 import shutil
-import subprocess
 
 import pytest
 
 import abi_header
+import model_harness
 from pcbenv import _lib
 
 SCALARS = {"int": C.c_int, "int8_t": C.c_int8, "uint8_t": C.c_uint8, "int16_t": C.c_int16, "uint16_t": C.c_uint16, "int32_t": C.c_int32,
@@ -70,19 +69,11 @@ def test_the_structure_has_the_members(name):
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
-def test_every_structure_has_the_c_layout(tmp_path):
+def test_every_structure_has_the_c_layout():
     """A compiled probe: sizeof and every member's offset of every struct as a C compiler lays include/pcbenv.h out."""
-    lines = []
-    for name, members in abi_header.structs().items():
-        lines.append(f'    printf("{name} sizeof %zu\\n", sizeof({name}));\n')
-        lines += [f'    printf("{name} {m} %zu\\n", offsetof({name}, {m}));\n' for _, m in members]
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "pcbenv.h"\nint main(void) {\n' + "".join(lines) + "    return 0;\n}\n")
-    exe = str(tmp_path / "probe")
-    subprocess.run(["g++", "-x", "c", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(abi_header.REPO, "include"), "-o", exe, str(src)], check=True)
     got = {}
-    for line in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines():
-        struct, member, value = line.split()
-        got.setdefault(struct, {})[member] = int(value)
+    for name, members in abi_header.structs().items():
+        offsets, size = model_harness.layout("pcbenv.h", name, [m for _, m in members])
+        got[name] = dict(offsets, sizeof=size)
     want = {name: dict({n: getattr(cls, n).offset for n, _ in cls._fields_}, sizeof=C.sizeof(cls)) for name, cls in STRUCTURES.items()}
     assert got == want

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import emission_cases as ec
+import model_harness
 from pcbenv.config import KIND_PIN, KIND_RECT, KIND_SPATIAL, KIND_SQUARE
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -103,12 +104,8 @@ def test_both_pin_grid_arms_change_from_step_to_step():
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
-def test_predicates_agree_with_the_layout_header(tmp_path):
-    exe = str(tmp_path / "emission_predicates")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-I", os.path.join(REPO, "include"),
-                    "-I", os.path.join(REPO, "rl-environment-for-component-placement_amd", "csrc"),
-                    "-o", exe, os.path.join(REPO, "tools", "emission_predicates.cpp")], check=True)
+def test_predicates_agree_with_the_layout_header():
+    exe = model_harness.tool("emission_predicates", include=True, fp_contract_off=False, frame_pointer=True)
     shapes = []  # (the line for the program, the values the Python side gives: three predicates, the build's five fields, its part)
 
     def add(layout, enabled=True, num_steps=1):

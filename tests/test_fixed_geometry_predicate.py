@@ -8,16 +8,14 @@ import subprocess
 
 import pytest
 
+import model_harness
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
-def test_fixed_geometry_check_program(tmp_path):
-    exe = str(tmp_path / "fixed_geometry_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-I", os.path.join(REPO, "include"),
-                    "-I", os.path.join(REPO, "rl-environment-for-component-placement_amd", "csrc"),
-                    "-o", exe, os.path.join(REPO, "tools", "fixed_geometry_check.cpp")], check=True)
+def test_fixed_geometry_check_program():
+    exe = model_harness.tool("fixed_geometry_check", include=True, fp_contract_off=False, frame_pointer=True)
     run = subprocess.run([exe], capture_output=True, text=True)
     assert run.returncode == 0, run.stdout + run.stderr
     assert run.stdout.startswith("fixed_geometry_check ok:"), run.stdout

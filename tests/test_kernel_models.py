@@ -14,6 +14,8 @@ import sys
 import numpy as np
 import pytest
 
+import model_harness
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -44,13 +46,8 @@ def _live_orders(count):
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
-def test_kernel_models_check_program(tmp_path):
-    exe = str(tmp_path / "kernel_models_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off",
-                    "-fsanitize=address,undefined,float-cast-overflow", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(REPO, "include"),
-                    "-I", os.path.join(REPO, "rl-environment-for-component-placement_amd", "csrc"),
-                    "-o", exe, os.path.join(REPO, "tools", "kernel_models_check.cpp")], check=True)
+def test_kernel_models_check_program():
+    exe = model_harness.tool("kernel_models_check", include=True, more_checks=",float-cast-overflow")
     z = np.load(os.path.join(REPO, "tests", "golden", "setorder.npz"))
     lines = [f"H {int(x)} {int(y)} {int(h)}" for x, y, h in z["tuple_hash"]]
     for pts, mask, order in zip(z["points"], z["visited_mask"], z["order"]):

@@ -8,11 +8,11 @@ import math
 import os
 import re
 import shutil
-import subprocess
 
 import pytest
 
 from abi_header import REPO, _STRUCT, _declarator
+import model_harness
 from pcbenv import _lib, _move_lib, _noise_lib, _search_lib
 
 PATH = os.path.join(REPO, "include", "pcbenv_noise.h")
@@ -87,18 +87,12 @@ def test_exported_and_bound():
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
-def test_the_ctypes_structure_has_the_c_layout(tmp_path):
+def test_the_ctypes_structure_has_the_c_layout():
     """A compiled probe: sizeof and every member's offset as a C compiler lays include/pcbenv_noise.h out."""
-    src = tmp_path / "probe.c"
-    prints = "".join(f'    printf("{n} %zu\\n", offsetof(pcbenv_puct_noise_request, {n}));\n' for n in MEMBERS)
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "pcbenv_noise.h"\nint main(void) {\n'
-                   '    printf("sizeof %zu\\n", sizeof(pcbenv_puct_noise_request));\n' + prints + "    return 0;\n}\n")
-    exe = str(tmp_path / "probe")
-    subprocess.run(["g++", "-x", "c", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(REPO, "include"), "-o", exe, str(src)], check=True)
-    got = dict(line.split() for line in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines())
+    offsets, size = model_harness.layout("pcbenv_noise.h", "pcbenv_puct_noise_request", MEMBERS)
     R = _noise_lib.PcbenvPuctNoiseRequest
-    assert int(got.pop("sizeof")) == C.sizeof(R)
-    assert {n: int(v) for n, v in got.items()} == {n: getattr(R, n).offset for n in MEMBERS}
+    assert size == C.sizeof(R)
+    assert offsets == {n: getattr(R, n).offset for n in MEMBERS}
 
 
 _HOST = (C.c_uint64 * 8)()  # host memory: never dereferenced, every call below fails before a device is touched

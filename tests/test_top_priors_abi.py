@@ -7,12 +7,12 @@ import ctypes as C
 import os
 import re
 import shutil
-import subprocess
 
 import pytest
 
 import abi_header
 from abi_header import REPO, _STRUCT, _declarator
+import model_harness
 from pcbenv import _lib, _priors_lib, _search_lib
 
 PATH = os.path.join(REPO, "include", "pcbenv_priors.h")
@@ -99,18 +99,12 @@ def test_bind_refuses_a_library_without_the_symbol():
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
-def test_the_ctypes_structure_has_the_c_layout(tmp_path):
+def test_the_ctypes_structure_has_the_c_layout():
     """A compiled probe: sizeof and every member's offset as a C compiler lays include/pcbenv_priors.h out."""
-    src = tmp_path / "probe.c"
-    prints = "".join(f'    printf("{n} %zu\\n", offsetof(pcbenv_top_priors_request, {n}));\n' for n in MEMBERS)
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "pcbenv_priors.h"\nint main(void) {\n'
-                   '    printf("sizeof %zu\\n", sizeof(pcbenv_top_priors_request));\n' + prints + "    return 0;\n}\n")
-    exe = str(tmp_path / "probe")
-    subprocess.run(["g++", "-x", "c", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(REPO, "include"), "-o", exe, str(src)], check=True)
-    got = dict(line.split() for line in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines())
+    offsets, size = model_harness.layout("pcbenv_priors.h", "pcbenv_top_priors_request", MEMBERS)
     R = _priors_lib.PcbenvTopPriorsRequest
-    assert int(got.pop("sizeof")) == C.sizeof(R)
-    assert {n: int(v) for n, v in got.items()} == {n: getattr(R, n).offset for n in MEMBERS}
+    assert size == C.sizeof(R)
+    assert offsets == {n: getattr(R, n).offset for n in MEMBERS}
 
 
 _HOST = (C.c_uint64 * 8)()  # host memory: never dereferenced, every call below fails before a device is touched

@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import model_harness
 from golden_util import case_names, load_case
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -73,13 +74,8 @@ def _transition_lines():
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
-def test_transition_check_program(tmp_path):
-    exe = str(tmp_path / "transition_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(REPO, "include"),
-                    "-I", os.path.join(REPO, "rl-environment-for-component-placement_amd", "csrc"),
-                    "-o", exe, os.path.join(REPO, "tools", "transition_check.cpp")], check=True)
+def test_transition_check_program():
+    exe = model_harness.tool("transition_check", include=True)
     lines, invalid, pin_rows, geometries = _transition_lines()
     transitions = len(lines)
     assert transitions > 0 and invalid > 0 and pin_rows > 0

@@ -2,14 +2,13 @@
 it, pcbenv/_lib.py binds it with a structure of the C struct's size, and every argument check refuses what it must before
 anything touches a device -- in the order the header gives, the null handle last.  No compute call is made."""
 import ctypes as C
-import os
 import re
 import shutil
-import subprocess
 
 import pytest
 
 from abi_header import REPO, raw as _raw, structs as _structs, text as _text
+import model_harness
 from pcbenv import _lib
 
 POINTERS = ("ln_dev",) + _lib.TREE_TENSORS + ("selected", "path_len", "paths", "reward", "length", "actions", "errors_dev", "stream")
@@ -56,18 +55,12 @@ def test_exported_and_bound():
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
-def test_the_ctypes_structure_has_the_c_layout(tmp_path):
+def test_the_ctypes_structure_has_the_c_layout():
     """A compiled probe: sizeof and every member's offset as a C compiler lays include/pcbenv.h out."""
-    src = tmp_path / "probe.c"
-    prints = "".join(f'    printf("{n} %zu\\n", offsetof(pcbenv_tree_request, {n}));\n' for n in MEMBERS)
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "pcbenv.h"\nint main(void) {\n'
-                   '    printf("sizeof %zu\\n", sizeof(pcbenv_tree_request));\n' + prints + "    return 0;\n}\n")
-    exe = str(tmp_path / "probe")
-    subprocess.run(["g++", "-x", "c", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(REPO, "include"), "-o", exe, str(src)], check=True)
-    got = dict(line.split() for line in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines())
+    offsets, size = model_harness.layout("pcbenv.h", "pcbenv_tree_request", MEMBERS)
     R = _lib.PcbenvTreeRequest
-    assert int(got.pop("sizeof")) == C.sizeof(R)
-    assert {n: int(v) for n, v in got.items()} == {n: getattr(R, n).offset for n in MEMBERS}
+    assert size == C.sizeof(R)
+    assert offsets == {n: getattr(R, n).offset for n in MEMBERS}
 
 
 _HOST = (C.c_uint64 * 8)()  # host memory: never dereferenced, every call below fails before a device is touched

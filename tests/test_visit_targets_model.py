@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import model_harness
 import visits_cases as vc
 import visits_contract as vt
 from logits_cases import _pack
@@ -21,13 +22,8 @@ GEOMETRIES = ((1, 3, 128), (2, 9, 70), (4, 6, 10))  # two full words; a ragged s
 
 
 @pytest.fixture(scope="module")
-def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("visit_targets") / "visit_targets_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", os.path.join(REPO, "include"),
-                    "-I", os.path.join(REPO, "rl-environment-for-component-placement_amd", "csrc"),
-                    "-o", exe, os.path.join(REPO, "tools", "visit_targets_check.cpp")], check=True)
-    return exe
+def program():
+    return model_harness.tool("visit_targets_check", include=True)
 
 
 def _table(O, H, W, C, seed):

@@ -5,9 +5,7 @@ the logit regimes of tests/logits_cases.py, the regimes a selection needs on top
 zeros, denormals, -inf tails, bad rows) and bit rows with a legal count around K.  A plain module: nothing here touches a
 device."""
 import os
-import shutil
 import subprocess
-import tempfile
 import zlib
 
 import numpy as np
@@ -15,6 +13,7 @@ import torch
 
 import evaluate_contract as ec
 import logits_cases as lc
+import model_harness
 from pcbenv.rollout import masked_logits
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -210,22 +209,9 @@ def segment_of(a, O, H, W):
 
 
 # ---- csrc/pcb_topk.h on the CPU ---------------------------------------------------------------------------------------
-
-_PROGRAM = []
-
-
 def program():
-    """tools/topk_model_check.cpp built as tests/puct_cases.py builds its tool; None without g++."""
-    if shutil.which("g++") is None:
-        return None
-    if not _PROGRAM:
-        exe = os.path.join(tempfile.mkdtemp(prefix="topk_model_"), "topk_model_check")
-        subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off",
-                        "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                        "-I", os.path.join(REPO, "rl-environment-for-component-placement_amd", "csrc"),
-                        "-o", exe, os.path.join(REPO, "tools", "topk_model_check.cpp")], check=True)
-        _PROGRAM.append(exe)
-    return _PROGRAM[0]
+    """tools/topk_model_check.cpp as tests/model_harness.py:tool builds it; None without g++."""
+    return model_harness.tool("topk_model_check")
 
 
 def model(O, H, W, bits, l32, Ks):

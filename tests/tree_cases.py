@@ -19,20 +19,16 @@ healthy search with one call before which the caller has written out-of-range va
 csrc/pcb_tree.h's promise that such a tree stops the walk and reports ERR_TREE."""
 import functools
 import math
-import os
-import shutil
-import struct
-import subprocess
-import tempfile
 from types import SimpleNamespace
 
 import numpy as np
 import torch
 
+import model_harness as mh
+from model_harness import REPO, flat, same_bits, words as _words  # noqa: F401  (the tests take them from here)
 from pcbenv.batched_env import Playout
 from pcbenv.search import ln_table, tree_search
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INIT, ABSORB, SELECT = 1, 2, 4
 ERR_FULL, ERR_TREE = 1, 2  # the bits of the error word
 FILL = -7  # what the model's int32 tensors hold before the first call
@@ -54,17 +50,9 @@ def shapes(P, N, C, T):
     return s
 
 
-@functools.lru_cache(maxsize=None)
 def program():
-    """tools/tree_model_check.cpp built as tests/test_kernel_models.py builds its tool; None without g++."""
-    if shutil.which("g++") is None:
-        return None
-    exe = os.path.join(tempfile.mkdtemp(prefix="tree_model_"), "tree_model_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(REPO, "rl-environment-for-component-placement_amd", "csrc"),
-                    "-o", exe, os.path.join(REPO, "tools", "tree_model_check.cpp")], check=True)
-    return exe
+    """tools/tree_model_check.cpp as tests/model_harness.py:tool builds it; None without g++."""
+    return mh.tool("tree_model_check")
 
 
 def record(P, T, iterations, c_uct, max_children, backend, step_index=0, cfg=None):
@@ -100,16 +88,11 @@ def search_calls(calls, split=False):
     return out
 
 
-def _words(a, floats=False):
-    a = np.ascontiguousarray(a)
-    return (a.astype(np.float64).view(np.int64) if floats else a.astype(np.int64)).ravel()
-
-
 def replay(P, N, C, T, c_uct, seq):
     """-> [state after call i]: dicts of STATE_FIELDS (int64; FLOATS as float64) and `errors`.  Raises if the program
     reports a selection that differs from the recorded one, or anything on stderr.  A call may carry `pokes`, a list of
     (tensor of POKED, flat index, value) stored into the state before its phases run."""
-    parts = [np.array([P, N, C, T, len(seq), struct.unpack("<q", struct.pack("<d", float(c_uct)))[0]], np.int64), _words(ln_table(N).numpy(), True)]
+    parts = [np.array([P, N, C, T, len(seq), mh.bits(c_uct)], np.int64), _words(ln_table(N).numpy(), True)]
     for c in seq:
         pokes = c.get("pokes", ())
         parts.append(np.array([c["phases"] | (POKED_CALL if pokes else 0), int(c["expect"] is not None)] +
@@ -119,27 +102,7 @@ def replay(P, N, C, T, c_uct, seq):
             parts += [_words(r, True), _words(L), _words(a)]
         if c["expect"] is not None:
             parts += [_words(c["expect"][1]), _words(c["expect"][0])]
-    run = subprocess.run([program()], input=np.concatenate(parts).tobytes(), capture_output=True)
-    assert run.returncode == 0 and run.stderr == b"", run.stderr.decode()
-    words = np.frombuffer(run.stdout, np.int64)
-    shp = shapes(P, N, C, T)
-    per_call = 1 + sum(int(np.prod(shp[f])) for f in STATE_FIELDS)
-    assert len(words) == per_call * len(seq)
-    states = []
-    for i in range(len(seq)):
-        w = words[i * per_call:(i + 1) * per_call]
-        st, at = {"errors": int(w[0])}, 1
-        for f in STATE_FIELDS:
-            n = int(np.prod(shp[f]))
-            st[f] = (w[at:at + n].view(np.float64) if f in FLOATS else w[at:at + n]).reshape(shp[f])
-            at += n
-        states.append(st)
-    return states
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+    return mh.cut(mh.run_words(program(), parts), len(seq), STATE_FIELDS, shapes(P, N, C, T), FLOATS)
 
 
 def compare_with_search(state, ts, N):
@@ -315,10 +278,6 @@ DAMAGE = ("selected_N", "selected_minus_1", "num_nodes_0", "num_nodes_N_plus_1",
           "depth_minus_1", "depth_T", "depth_T_plus_3", "num_children_minus_1", "num_children_C_plus_5")
 DAMAGE_CASES = ([(4, n) for n in DAMAGE] + [(16, n) for n in DAMAGE[4:] if not n.endswith("absorb_alone")] +
                 [(64, n) for n in ("last_child_bad_match_below", "first_child_bad", "middle_child_bad_no_match")])
-
-
-def flat(shape, *index):
-    return int(np.ravel_multi_index(index, shape))
 
 
 @functools.lru_cache(maxsize=None)

@@ -20,39 +20,12 @@
 //     Before the first CHOOSE the six outputs hold -7 (what a test puts into the device tensors the kernel must leave alone).
 //   mode 1, the table.
 //     in:   m n      out:  considered_row(m, n), n words
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-
-#include <vector>
-
 #include "pcb_gumbel.h"
+#include "puct_state.h"
+
+using namespace puct_state;
 
 namespace {
-
-bool read_words(int64_t *dst, size_t n) { return fread(dst, sizeof(int64_t), n, stdin) == n; }
-int64_t read_word(bool *ok) { int64_t v = 0; *ok = *ok && read_words(&v, 1); return v; }
-double as_double(int64_t bits) { double d; memcpy(&d, &bits, 8); return d; }
-float as_float(int64_t bits) { const uint32_t b = (uint32_t)bits; float f; memcpy(&f, &b, 4); return f; }
-int64_t as_bits(double d) { int64_t b; memcpy(&b, &d, 8); return b; }
-int64_t as_bits32(float f) { uint32_t b; memcpy(&b, &f, 4); return (int64_t)b; }
-
-std::vector<int64_t> out;
-template <class V> void put(const V &v) { for (auto x : v) out.push_back((int64_t)x); }
-void put_bits(const std::vector<double> &v) { for (double x : v) out.push_back(as_bits(x)); }
-
-bool read_ints(std::vector<int> &dst) {
-    std::vector<int64_t> w(dst.size());
-    if (!read_words(w.data(), w.size())) return false;
-    for (size_t i = 0; i < w.size(); i++) dst[i] = (int)w[i];
-    return true;
-}
-bool read_doubles(std::vector<double> &dst) {
-    std::vector<int64_t> w(dst.size());
-    if (!read_words(w.data(), w.size())) return false;
-    for (size_t i = 0; i < w.size(); i++) dst[i] = as_double(w[i]);
-    return true;
-}
 
 int table() {
     bool ok = true;
@@ -66,69 +39,46 @@ int table() {
 
 int calls() {
     using namespace pcb_gumbel;
-    using pcb_puct::puct_absorb;
     bool ok = true;
     const int P = (int)read_word(&ok), N = (int)read_word(&ok), C = (int)read_word(&ok), T = (int)read_word(&ok), K = (int)read_word(&ok),
               n = (int)read_word(&ok), Mc = (int)read_word(&ok), calls = (int)read_word(&ok);
     const double c_puct = as_double(read_word(&ok)), c_visit = as_double(read_word(&ok)), c_scale = as_double(read_word(&ok));
     if (!ok || P < 0 || N < 1 || C < 1 || C > MAX_CHILDREN || T < 1 || K < 1 || n < 1 || Mc < 1 || Mc > MAX_CONSIDERED || calls < 0) { fprintf(stderr, "bad header\n"); return 2; }
-    const size_t PN = (size_t)P * N, TP3 = (size_t)T * P * 3, PK = (size_t)P * K, PC = (size_t)P * C;
-    std::vector<int> considered((size_t)(Mc + 1) * n);
-    std::vector<int> num_nodes(P), parent(PN), depth(PN), visits(PN), num_children(PN), first_child(PN), node_action(PN * 3), selected(P), path_len(P),
-        paths(TP3), terminal_in(PN), sim_index(P), sim_visits(PC);
-    std::vector<double> prior(PN), value_sum(PN), value_max(PN), lo(P), hi(P);
-    ok = read_ints(considered) && read_ints(selected) && read_ints(path_len) && read_ints(paths) && read_ints(num_nodes) && read_ints(parent) &&
-         read_ints(depth) && read_ints(visits) && read_ints(num_children) && read_ints(first_child) && read_ints(node_action) && read_doubles(prior) &&
-         read_doubles(value_sum) && read_doubles(value_max) && read_ints(terminal_in) && read_doubles(lo) && read_doubles(hi) && read_ints(sim_index) &&
-         read_ints(sim_visits);
-    if (!ok) { fprintf(stderr, "the state ends early\n"); return 2; }
-    std::vector<uint8_t> terminal(terminal_in.begin(), terminal_in.end());
+    const size_t PC = (size_t)P * C;
+    std::vector<int> considered((size_t)(Mc + 1) * n), sim_index(P), sim_visits(PC);
+    State st(P, N, C, T, (size_t)P);
+    if (!(read_ints(considered) && st.read_search() && st.read_tree() && read_ints(sim_index) && read_ints(sim_visits))) { fprintf(stderr, "the state ends early\n"); return 2; }
+    std::vector<int> &selected = st.selected, &path_len = st.path_len, &paths = st.paths;
     const int FILL = -7;
     std::vector<int> move_slot(P, FILL), move_action((size_t)P * 3, FILL), child_weights(PC, FILL), child_actions(PC * 3, FILL);
     std::vector<float> child_policy(PC, -7.0f);
     std::vector<double> root_value(P, -7.0);
-    std::vector<double> value(P);
-    std::vector<int> leaf_terminal(P), cand_count(P), cand_actions(PK * 3);
-    std::vector<float> cand_prior(PK);
-    std::vector<int> *const poked[] = {&selected, &num_nodes, &parent, &num_children, &first_child, &sim_index, &sim_visits};
+    Evaluation<> ev((size_t)P, K);
+    std::vector<int> *const poked[] = {&selected, &st.num_nodes, &st.parent, &st.num_children, &st.first_child, &sim_index, &sim_visits};
     for (int call = 0; call < calls; call++) {
         const int phases = (int)read_word(&ok);
         const uint64_t seed = (uint64_t)read_word(&ok), step_index = (uint64_t)read_word(&ok);
         const int first_root = (int)read_word(&ok);
         const int64_t pokes = read_word(&ok);
-        for (int64_t i = 0; ok && i < pokes; i++) {
-            const int64_t tensor = read_word(&ok), at = read_word(&ok), v = read_word(&ok);
-            if (!ok || tensor < 0 || tensor >= 7 || at < 0 || (uint64_t)at >= poked[tensor]->size() || v != (int)v) { fprintf(stderr, "call %d: bad poke\n", call); return 2; }
-            (*poked[tensor])[(size_t)at] = (int)v;
-        }
+        if (!poke(poked, pokes, &ok, call)) return 2;
         if (!ok || pokes < 0 || phases <= 0 || phases > 15 || ((phases & PHASE_SELECT) && (phases & PHASE_CHOOSE))) { fprintf(stderr, "call %d: bad phases\n", call); return 2; }
-        if (phases & PHASE_ABSORB) {
-            for (double &x : value) x = as_double(read_word(&ok));
-            ok = ok && read_ints(leaf_terminal) && read_ints(cand_count) && read_ints(cand_actions);
-            for (float &x : cand_prior) x = as_float(read_word(&ok));
-        }
+        if (phases & PHASE_ABSORB) ok = ok && ev.read();
         if (!ok) { fprintf(stderr, "call %d: input ends early\n", call); return 2; }
         const Rule q{c_puct, c_visit, c_scale, seed, step_index, first_root, n, Mc};
         unsigned errors = 0u;
         for (int p = 0; p < P; p++) {
-            const size_t s = (size_t)p * N, row = (size_t)p * C;
-            const Root r{N, C, T, P, p, &num_nodes[p], &parent[s], &depth[s], &visits[s], &num_children[s], &first_child[s], &node_action[3 * s],
-                         &prior[s], &value_sum[s], &value_max[s], &terminal[s], &lo[p], &hi[p]};
+            const size_t row = (size_t)p * C;
+            const Root r = st.root(p);
             if (phases & PHASE_BEGIN) gumbel_begin(C, &sim_index[p], &sim_visits[row]);
-            if (phases & PHASE_ABSORB)
-                errors |= puct_absorb(r, selected[p], value[p], leaf_terminal[p], cand_count[p], K, &cand_actions[(size_t)p * K * 3], &cand_prior[(size_t)p * K]);
+            if (phases & PHASE_ABSORB) errors |= ev.absorb(r, selected[p], (size_t)p);
             if (phases & PHASE_SELECT) errors |= gumbel_select(r, q, considered.data(), &sim_index[p], &sim_visits[row], paths.data(), &path_len[p], &selected[p]);
             if (phases & PHASE_CHOOSE)
                 errors |= gumbel_choose(r, q, &sim_visits[row], &move_slot[p], &move_action[(size_t)p * 3], &child_weights[row], &child_policy[row],
                                         &child_actions[3 * row], &root_value[p]);
         }
         out.push_back((int64_t)errors);
-        put(selected); put(path_len); put(paths); put(num_nodes); put(parent); put(depth); put(visits); put(num_children); put(first_child);
-        put(node_action); put_bits(prior); put_bits(value_sum); put_bits(value_max); put(terminal); put_bits(lo); put_bits(hi);
-        put(sim_index); put(sim_visits);
-        put(move_slot); put(move_action); put(child_weights);
-        for (float x : child_policy) out.push_back(as_bits32(x));
-        put(child_actions); put_bits(root_value);
+        st.put_search(); st.put_tree(); put(sim_index); put(sim_visits);
+        put(move_slot); put(move_action); put(child_weights); put_bits(child_policy); put(child_actions); put_bits(root_value);
     }
     return 0;
 }
@@ -140,7 +90,5 @@ int main() {
     const int64_t mode = read_word(&ok);
     if (!ok || mode < 0 || mode > 1) { fprintf(stderr, "bad mode\n"); return 2; }
     const int rc = mode == 0 ? calls() : table();
-    if (rc != 0) return rc;
-    if (fwrite(out.data(), sizeof(int64_t), out.size(), stdout) != out.size()) { fprintf(stderr, "short write\n"); return 2; }
-    return 0;
+    return rc != 0 ? rc : flush();
 }

@@ -19,34 +19,10 @@
 //           first_child [P N] node_action[P N 3] prior value_sum value_max terminal [P N] reward_lo reward_hi [P]
 // Before the first call every int32 tensor holds -7, every float64 one -7.0 and terminal 0xf9 (what a test puts into the
 // device tensors the kernels must leave alone): the first call brings INIT.
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-
-#include <vector>
-
 #include "pcb_puct_move.h"
+#include "puct_state.h"
 
-namespace {
-
-bool read_words(int64_t *dst, size_t n) { return fread(dst, sizeof(int64_t), n, stdin) == n; }
-int64_t read_word(bool *ok) { int64_t v = 0; *ok = *ok && read_words(&v, 1); return v; }
-double as_double(int64_t bits) { double d; memcpy(&d, &bits, 8); return d; }
-float as_float(int64_t bits) { const uint32_t b = (uint32_t)bits; float f; memcpy(&f, &b, 4); return f; }
-int64_t as_bits(double d) { int64_t b; memcpy(&b, &d, 8); return b; }
-
-std::vector<int64_t> out;
-template <class V> void put(const V &v) { for (auto x : v) out.push_back((int64_t)x); }
-void put_bits(const std::vector<double> &v) { for (double x : v) out.push_back(as_bits(x)); }
-
-bool read_ints(std::vector<int> &dst) {
-    std::vector<int64_t> w(dst.size());
-    if (!read_words(w.data(), w.size())) return false;
-    for (size_t i = 0; i < w.size(); i++) dst[i] = (int)w[i];
-    return true;
-}
-
-}  // namespace
+using namespace puct_state;
 
 int main() {
     using namespace pcb_puct;
@@ -56,17 +32,15 @@ int main() {
               calls = (int)read_word(&ok);
     const double c_puct = as_double(read_word(&ok));
     if (!ok || P < 0 || N < 1 || C < 1 || C > pcb_tree::MAX_CHILDREN || T < 1 || K < 1 || calls < 0) { fprintf(stderr, "bad header\n"); return 2; }
-    const size_t PN = (size_t)P * N, TP3 = (size_t)T * P * 3, PK = (size_t)P * K, PC = (size_t)P * C;
+    const size_t PN = (size_t)P * N, TP3 = (size_t)T * P * 3, PC = (size_t)P * C;
     const int FILL = -7;
-    std::vector<int> num_nodes(P, FILL), parent(PN, FILL), depth(PN, FILL), visits(PN, FILL), num_children(PN, FILL), first_child(PN, FILL),
-        node_action(PN * 3, FILL), selected(P, FILL), path_len(P, FILL), paths(TP3, FILL);
-    std::vector<double> prior(PN, -7.0), value_sum(PN, -7.0), value_max(PN, -7.0), lo(P, -7.0), hi(P, -7.0);
-    std::vector<uint8_t> terminal(PN, 0xf9);
+    State st(P, N, C, T, (size_t)P);
+    st.fill();
+    std::vector<int> &selected = st.selected, &path_len = st.path_len, &paths = st.paths;
     std::vector<int> move_slot(P, FILL), move_action((size_t)P * 3, FILL), child_visits(PC, FILL), child_actions(PC * 3, FILL), remap(PN, FILL), reset(P, 0);
     std::vector<double> root_value(P, -7.0);
-    std::vector<double> value(P);
-    std::vector<int> leaf_terminal(P), cand_count(P), cand_actions(PK * 3), want_len(P), want_paths(TP3);
-    std::vector<float> cand_prior(PK);
+    Evaluation<> ev((size_t)P, K);
+    std::vector<int> want_len(P), want_paths(TP3);
     for (int call = 0; call < calls; call++) {
         const int kind = (int)read_word(&ok), phases = (int)read_word(&ok);
         unsigned errors = 0u;
@@ -75,11 +49,7 @@ int main() {
         if (kind == 0) {
             check = (int)read_word(&ok);
             if (!ok || phases <= 0 || phases > 7 || ((phases & PHASE_INIT) && (phases & PHASE_ABSORB))) { fprintf(stderr, "call %d: bad phases\n", call); return 2; }
-            if (phases & PHASE_ABSORB) {
-                for (double &x : value) x = as_double(read_word(&ok));
-                ok = ok && read_ints(leaf_terminal) && read_ints(cand_count) && read_ints(cand_actions);
-                for (float &x : cand_prior) x = as_float(read_word(&ok));
-            }
+            if (phases & PHASE_ABSORB) ok = ok && ev.read();
             if ((phases & PHASE_SELECT) && check) ok = ok && read_ints(want_len) && read_ints(want_paths);
             if (!ok) { fprintf(stderr, "call %d: input ends early\n", call); return 2; }
         } else {
@@ -97,19 +67,16 @@ int main() {
             if (!ok || (mode != MODE_GREEDY && mode != MODE_PROPORTIONAL)) { fprintf(stderr, "call %d: bad mode, or the input ends early\n", call); return 2; }
         }
         for (int p = 0; p < P; p++) {
-            const size_t s = (size_t)p * N;
-            const Root r{N, C, T, P, p, &num_nodes[p], &parent[s], &depth[s], &visits[s], &num_children[s], &first_child[s], &node_action[3 * s],
-                         &prior[s], &value_sum[s], &value_max[s], &terminal[s], &lo[p], &hi[p]};
+            const Root r = st.root(p);
             if (kind == 1) {
                 if (phases & PHASE_CHOOSE)
                     errors |= move_choose(r, mode, seed, step_index, first_root, &child_visits[(size_t)p * C], &child_actions[(size_t)p * C * 3], &root_value[p],
                                           &move_slot[p], &move_action[(size_t)p * 3]);
-                if (phases & PHASE_REROOT) errors |= move_reroot(r, move_slot[p], has_reset ? reset[p] : 0, &remap[s]);
+                if (phases & PHASE_REROOT) errors |= move_reroot(r, move_slot[p], has_reset ? reset[p] : 0, &remap[(size_t)p * N]);
                 continue;
             }
             if (phases & PHASE_INIT) puct_init(r);
-            if (phases & PHASE_ABSORB)
-                errors |= puct_absorb(r, selected[p], value[p], leaf_terminal[p], cand_count[p], K, &cand_actions[(size_t)p * K * 3], &cand_prior[(size_t)p * K]);
+            if (phases & PHASE_ABSORB) errors |= ev.absorb(r, selected[p], (size_t)p);
             if (phases & PHASE_SELECT) {
                 errors |= puct_select(r, c_puct, paths.data(), &path_len[p], &selected[p]);
                 if (path_len[p] != r.depth[selected[p]]) { fprintf(stderr, "call %d root %d: path_len %d, depth of the selected node %d\n", call, p, path_len[p], r.depth[selected[p]]); return 1; }
@@ -121,11 +88,9 @@ int main() {
             }
         }
         out.push_back((int64_t)errors);
-        put(selected); put(path_len); put(paths);
+        st.put_search();
         put(move_slot); put(move_action); put(child_visits); put(child_actions); put_bits(root_value); put(remap);
-        put(num_nodes); put(parent); put(depth); put(visits); put(num_children); put(first_child); put(node_action);
-        put_bits(prior); put_bits(value_sum); put_bits(value_max); put(terminal); put_bits(lo); put_bits(hi);
+        st.put_tree();
     }
-    if (fwrite(out.data(), sizeof(int64_t), out.size(), stdout) != out.size()) { fprintf(stderr, "short write\n"); return 2; }
-    return 0;
+    return flush();
 }

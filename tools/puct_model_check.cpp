@@ -16,34 +16,9 @@
 //   out:  per call: errors | selected[P] path_len[P] paths[T P 3] | num_nodes[P] parent depth visits num_children first_child
 //           [P N] node_action[P N 3] prior value_sum value_max terminal [P N] reward_lo reward_hi [P]
 // Before the first call every int32 tensor holds -7 (what a test puts into the device tensors the kernel must leave alone).
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
+#include "puct_state.h"
 
-#include <vector>
-
-#include "pcb_puct.h"
-
-namespace {
-
-bool read_words(int64_t *dst, size_t n) { return fread(dst, sizeof(int64_t), n, stdin) == n; }
-int64_t read_word(bool *ok) { int64_t v = 0; *ok = *ok && read_words(&v, 1); return v; }
-double as_double(int64_t bits) { double d; memcpy(&d, &bits, 8); return d; }
-float as_float(int64_t bits) { const uint32_t b = (uint32_t)bits; float f; memcpy(&f, &b, 4); return f; }
-int64_t as_bits(double d) { int64_t b; memcpy(&b, &d, 8); return b; }
-
-std::vector<int64_t> out;
-template <class V> void put(const V &v) { for (auto x : v) out.push_back((int64_t)x); }
-void put_bits(const std::vector<double> &v) { for (double x : v) out.push_back(as_bits(x)); }
-
-bool read_ints(std::vector<int> &dst) {
-    std::vector<int64_t> w(dst.size());
-    if (!read_words(w.data(), w.size())) return false;
-    for (size_t i = 0; i < w.size(); i++) dst[i] = (int)w[i];
-    return true;
-}
-
-}  // namespace
+using namespace puct_state;
 
 int main() {
     using namespace pcb_puct;
@@ -52,16 +27,13 @@ int main() {
               calls = (int)read_word(&ok);
     const double c_puct = as_double(read_word(&ok));
     if (!ok || P < 0 || N < 1 || C < 1 || C > MAX_CHILDREN || T < 1 || K < 1 || calls < 0) { fprintf(stderr, "bad header\n"); return 2; }
-    const size_t PN = (size_t)P * N, TP3 = (size_t)T * P * 3, PK = (size_t)P * K;
-    const int FILL = -7;
-    std::vector<int> num_nodes(P, FILL), parent(PN, FILL), depth(PN, FILL), visits(PN, FILL), num_children(PN, FILL), first_child(PN, FILL),
-        node_action(PN * 3, FILL), selected(P, FILL), path_len(P, FILL), paths(TP3, FILL);
-    std::vector<double> prior(PN, -7.0), value_sum(PN, -7.0), value_max(PN, -7.0), lo(P, -7.0), hi(P, -7.0);
-    std::vector<uint8_t> terminal(PN, 0xf9);
-    std::vector<double> value(P);
-    std::vector<int> leaf_terminal(P), cand_count(P), cand_actions(PK * 3), want_len(P), want_paths(TP3);
-    std::vector<float> cand_prior(PK);
-    std::vector<int> *const poked[] = {&selected, &num_nodes, &parent, &num_children, &first_child};
+    const size_t TP3 = (size_t)T * P * 3;
+    State st(P, N, C, T, (size_t)P);
+    st.fill();
+    std::vector<int> &selected = st.selected, &path_len = st.path_len, &paths = st.paths;
+    Evaluation<> ev((size_t)P, K);
+    std::vector<int> want_len(P), want_paths(TP3);
+    std::vector<int> *const poked[] = {&selected, &st.num_nodes, &st.parent, &st.num_children, &st.first_child};
     enum { POKED = 8 };
     unsigned errors = 0u;
     bool damaged = false;
@@ -69,27 +41,16 @@ int main() {
         const int word = (int)read_word(&ok), check = (int)read_word(&ok);
         const int phases = word & ~POKED;
         const int64_t pokes = (word & POKED) ? read_word(&ok) : 0;
-        for (int64_t i = 0; ok && i < pokes; i++) {
-            const int64_t tensor = read_word(&ok), at = read_word(&ok), v = read_word(&ok);
-            if (!ok || tensor < 0 || tensor >= 5 || at < 0 || (uint64_t)at >= poked[tensor]->size() || v != (int)v) { fprintf(stderr, "call %d: bad poke\n", call); return 2; }
-            (*poked[tensor])[(size_t)at] = (int)v;
-            damaged = true;
-        }
+        if (!poke(poked, pokes, &ok, call)) return 2;
+        damaged = damaged || (ok && pokes > 0);
         if (!ok || pokes < 0 || phases <= 0 || phases > 7 || ((phases & PHASE_INIT) && (phases & PHASE_ABSORB))) { fprintf(stderr, "call %d: bad phases\n", call); return 2; }
-        if (phases & PHASE_ABSORB) {
-            for (double &x : value) x = as_double(read_word(&ok));
-            ok = ok && read_ints(leaf_terminal) && read_ints(cand_count) && read_ints(cand_actions);
-            for (float &x : cand_prior) x = as_float(read_word(&ok));
-        }
+        if (phases & PHASE_ABSORB) ok = ok && ev.read();
         if ((phases & PHASE_SELECT) && check) ok = ok && read_ints(want_len) && read_ints(want_paths);
         if (!ok) { fprintf(stderr, "call %d: input ends early\n", call); return 2; }
         for (int p = 0; p < P; p++) {
-            const size_t s = (size_t)p * N;
-            const Root r{N, C, T, P, p, &num_nodes[p], &parent[s], &depth[s], &visits[s], &num_children[s], &first_child[s], &node_action[3 * s],
-                         &prior[s], &value_sum[s], &value_max[s], &terminal[s], &lo[p], &hi[p]};
+            const Root r = st.root(p);
             if (phases & PHASE_INIT) puct_init(r);
-            if (phases & PHASE_ABSORB)
-                errors |= puct_absorb(r, selected[p], value[p], leaf_terminal[p], cand_count[p], K, &cand_actions[(size_t)p * K * 3], &cand_prior[(size_t)p * K]);
+            if (phases & PHASE_ABSORB) errors |= ev.absorb(r, selected[p], (size_t)p);
             if (phases & PHASE_SELECT) {
                 errors |= puct_select(r, c_puct, paths.data(), &path_len[p], &selected[p]);
                 if (!damaged && path_len[p] != r.depth[selected[p]]) { fprintf(stderr, "call %d root %d: path_len %d, depth of the selected node %d\n", call, p, path_len[p], r.depth[selected[p]]); return 1; }
@@ -101,9 +62,7 @@ int main() {
             }
         }
         out.push_back((int64_t)errors);
-        put(selected); put(path_len); put(paths); put(num_nodes); put(parent); put(depth); put(visits); put(num_children); put(first_child);
-        put(node_action); put_bits(prior); put_bits(value_sum); put_bits(value_max); put(terminal); put_bits(lo); put_bits(hi);
+        st.put_search(); st.put_tree();
     }
-    if (fwrite(out.data(), sizeof(int64_t), out.size(), stdout) != out.size()) { fprintf(stderr, "short write\n"); return 2; }
-    return 0;
+    return flush();
 }

@@ -16,39 +16,10 @@
 //           root_value[P] remap[P N] | the tree, in the order above
 // Before the first call every int32 output tensor holds -7 and root_value -7.0 (what a test puts into the device tensors
 // the kernel must leave alone).
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-
-#include <vector>
-
 #include "pcb_puct_move.h"
+#include "puct_state.h"
 
-namespace {
-
-bool read_words(int64_t *dst, size_t n) { return fread(dst, sizeof(int64_t), n, stdin) == n; }
-int64_t read_word(bool *ok) { int64_t v = 0; *ok = *ok && read_words(&v, 1); return v; }
-double as_double(int64_t bits) { double d; memcpy(&d, &bits, 8); return d; }
-int64_t as_bits(double d) { int64_t b; memcpy(&b, &d, 8); return b; }
-
-std::vector<int64_t> out;
-template <class V> void put(const V &v) { for (auto x : v) out.push_back((int64_t)x); }
-void put_bits(const std::vector<double> &v) { for (double x : v) out.push_back(as_bits(x)); }
-
-template <class V> bool read_ints(V &dst) {
-    std::vector<int64_t> w(dst.size());
-    if (!read_words(w.data(), w.size())) return false;
-    for (size_t i = 0; i < w.size(); i++) dst[i] = (typename V::value_type)w[i];
-    return true;
-}
-bool read_doubles(std::vector<double> &dst) {
-    std::vector<int64_t> w(dst.size());
-    if (!read_words(w.data(), w.size())) return false;
-    for (size_t i = 0; i < w.size(); i++) dst[i] = as_double(w[i]);
-    return true;
-}
-
-}  // namespace
+using namespace puct_state;
 
 int main() {
     using namespace pcb_move;
@@ -57,45 +28,32 @@ int main() {
     if (!ok || P < 0 || N < 1 || C < 1 || C > MAX_CHILDREN || calls < 0) { fprintf(stderr, "bad header\n"); return 2; }
     const size_t PN = (size_t)P * N, PC = (size_t)P * C;
     const int FILL = -7;
-    std::vector<int> num_nodes(P), parent(PN), depth(PN), visits(PN), num_children(PN), first_child(PN), node_action(PN * 3);
-    std::vector<double> prior(PN), value_sum(PN), value_max(PN), lo(P), hi(P);
-    std::vector<uint8_t> terminal(PN);
-    ok = read_ints(num_nodes) && read_ints(parent) && read_ints(depth) && read_ints(visits) && read_ints(num_children) && read_ints(first_child) &&
-         read_ints(node_action) && read_doubles(prior) && read_doubles(value_sum) && read_doubles(value_max) && read_ints(terminal) &&
-         read_doubles(lo) && read_doubles(hi);
-    if (!ok) { fprintf(stderr, "the tree ends early\n"); return 2; }
+    State st(P, N, C, 0, 0);  // the tree alone
+    if (!st.read_tree()) { fprintf(stderr, "the tree ends early\n"); return 2; }
     std::vector<int> move_slot(P, FILL), move_action((size_t)P * 3, FILL), child_visits(PC, FILL), child_actions(PC * 3, FILL), remap(PN, FILL), reset(P, 0);
     std::vector<double> root_value(P, -7.0);
-    std::vector<int> *const poked[] = {&move_slot, &num_nodes, &parent, &num_children, &first_child};
+    std::vector<int> *const poked[] = {&move_slot, &st.num_nodes, &st.parent, &st.num_children, &st.first_child};
     for (int call = 0; call < calls; call++) {
         const int phases = (int)read_word(&ok), mode = (int)read_word(&ok);
         const uint64_t seed = (uint64_t)read_word(&ok), step_index = (uint64_t)read_word(&ok);
         const int first_root = (int)read_word(&ok), has_move = (int)read_word(&ok), has_reset = (int)read_word(&ok);
         const int64_t pokes = read_word(&ok);
         if (!ok || pokes < 0 || phases < 1 || phases > 3 || (mode != MODE_GREEDY && mode != MODE_PROPORTIONAL)) { fprintf(stderr, "call %d: bad phases or mode\n", call); return 2; }
-        for (int64_t i = 0; i < pokes; i++) {
-            const int64_t tensor = read_word(&ok), at = read_word(&ok), v = read_word(&ok);
-            if (!ok || tensor < 0 || tensor >= 5 || at < 0 || (uint64_t)at >= poked[tensor]->size() || v != (int)v) { fprintf(stderr, "call %d: bad poke\n", call); return 2; }
-            (*poked[tensor])[(size_t)at] = (int)v;
-        }
+        if (!poke(poked, pokes, &ok, call)) return 2;
         if (has_move) ok = ok && read_ints(move_slot);
         if (has_reset) ok = ok && read_ints(reset);
         if (!ok) { fprintf(stderr, "call %d: input ends early\n", call); return 2; }
         unsigned errors = 0u;
         for (int p = 0; p < P; p++) {
-            const size_t s = (size_t)p * N;
-            const Root r{N, C, 0, P, p, &num_nodes[p], &parent[s], &depth[s], &visits[s], &num_children[s], &first_child[s], &node_action[3 * s],
-                         &prior[s], &value_sum[s], &value_max[s], &terminal[s], &lo[p], &hi[p]};
+            const Root r = st.root(p);
             if (phases & PHASE_CHOOSE)
                 errors |= move_choose(r, mode, seed, step_index, first_root, &child_visits[(size_t)p * C], &child_actions[(size_t)p * C * 3], &root_value[p],
                                       &move_slot[p], &move_action[(size_t)p * 3]);
-            if (phases & PHASE_REROOT) errors |= move_reroot(r, move_slot[p], has_reset ? reset[p] : 0, &remap[s]);
+            if (phases & PHASE_REROOT) errors |= move_reroot(r, move_slot[p], has_reset ? reset[p] : 0, &remap[(size_t)p * N]);
         }
         out.push_back((int64_t)errors);
         put(move_slot); put(move_action); put(child_visits); put(child_actions); put_bits(root_value); put(remap);
-        put(num_nodes); put(parent); put(depth); put(visits); put(num_children); put(first_child); put(node_action);
-        put_bits(prior); put_bits(value_sum); put_bits(value_max); put(terminal); put_bits(lo); put_bits(hi);
+        st.put_tree();
     }
-    if (fwrite(out.data(), sizeof(int64_t), out.size(), stdout) != out.size()) { fprintf(stderr, "short write\n"); return 2; }
-    return 0;
+    return flush();
 }

@@ -12,37 +12,12 @@
 //   mode 1, functions.
 //     in:   n | n x (function, argument): 0 ieee_ln, 1 ieee_exp, 2 ieee_sqrt
 //     out:  n results
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-
-#include <vector>
-
 #include "pcb_puct_noise.h"
+#include "word_stream.h"
+
+using namespace word_stream;
 
 namespace {
-
-bool read_words(int64_t *dst, size_t n) { return fread(dst, sizeof(int64_t), n, stdin) == n; }
-int64_t read_word(bool *ok) { int64_t v = 0; *ok = *ok && read_words(&v, 1); return v; }
-double as_double(int64_t bits) { double d; memcpy(&d, &bits, 8); return d; }
-int64_t as_bits(double d) { int64_t b; memcpy(&b, &d, 8); return b; }
-
-std::vector<int64_t> out;
-template <class V> void put(const V &v) { for (auto x : v) out.push_back((int64_t)x); }
-void put_bits(const std::vector<double> &v) { for (double x : v) out.push_back(as_bits(x)); }
-
-bool read_ints(std::vector<int> &dst) {
-    std::vector<int64_t> w(dst.size());
-    if (!read_words(w.data(), w.size())) return false;
-    for (size_t i = 0; i < w.size(); i++) dst[i] = (int)w[i];
-    return true;
-}
-bool read_doubles(std::vector<double> &dst) {
-    std::vector<int64_t> w(dst.size());
-    if (!read_words(w.data(), w.size())) return false;
-    for (size_t i = 0; i < w.size(); i++) dst[i] = as_double(w[i]);
-    return true;
-}
 
 int functions() {
     bool ok = true;
@@ -90,7 +65,5 @@ int main() {
     const int64_t mode = read_word(&ok);
     if (!ok || mode < 0 || mode > 1) { fprintf(stderr, "bad mode\n"); return 2; }
     const int rc = mode == 0 ? calls() : functions();
-    if (rc != 0) return rc;
-    if (fwrite(out.data(), sizeof(int64_t), out.size(), stdout) != out.size()) { fprintf(stderr, "short write\n"); return 2; }
-    return 0;
+    return rc != 0 ? rc : flush();
 }

@@ -11,13 +11,9 @@
 //         (bf16 logits travel widened: the widening is exact and belongs to the load)
 //   out:  int64 words, per K, per row: count | error bits | actions [K, 3] | prior [K] as float32 bits
 #include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-
-#include <vector>
 
 #include "pcb_topk.h"
+#include "word_stream.h"
 
 namespace {
 
@@ -151,21 +147,21 @@ Row top_priors_row(const Geom &q, const std::vector<uint64_t> &bits, const float
 
 int main() {
     int64_t head[5];
-    if (fread(head, 8, 5, stdin) != 5) { fprintf(stderr, "bad header\n"); return 2; }
+    if (!word_stream::read_words(head, 5)) { fprintf(stderr, "bad header\n"); return 2; }
     const int64_t rows = head[3], nK = head[4];
     if (head[0] < 1 || head[0] > 4 || head[1] < 1 || head[2] < 1 || head[2] > 128 || rows < 0 || nK < 1 || nK > 16) { fprintf(stderr, "bad header\n"); return 2; }
     Geom q;
     q.O = (int)head[0]; q.H = (int)head[1]; q.W = (int)head[2]; q.WW = (q.W + 63) / 64; q.A = q.O * q.H * q.W; q.S = q.O * q.H * q.WW;
     std::vector<int64_t> Ks((size_t)nK);
-    if (fread(Ks.data(), 8, (size_t)nK, stdin) != (size_t)nK) { fprintf(stderr, "bad header\n"); return 2; }
+    if (!word_stream::read_words(Ks.data(), Ks.size())) { fprintf(stderr, "bad header\n"); return 2; }
     for (int64_t K : Ks)
         if (K < 1 || K > MAX_K) { fprintf(stderr, "bad K\n"); return 2; }
     const size_t words = (size_t)2 * q.H * q.WW;
     std::vector<std::vector<uint64_t>> bits((size_t)rows, std::vector<uint64_t>(words));
     std::vector<std::vector<float>> logits((size_t)rows, std::vector<float>((size_t)q.A));
     for (int64_t r = 0; r < rows; r++)
-        if (fread(bits[r].data(), 8, words, stdin) != words || fread(logits[r].data(), 4, (size_t)q.A, stdin) != (size_t)q.A) { fprintf(stderr, "row %lld: input ends early\n", (long long)r); return 2; }
-    std::vector<int64_t> out;
+        if (!word_stream::read_raw(bits[r].data(), words) || !word_stream::read_raw(logits[r].data(), (size_t)q.A)) { fprintf(stderr, "row %lld: input ends early\n", (long long)r); return 2; }
+    std::vector<int64_t> &out = word_stream::out;
     for (int64_t K : Ks)
         for (int64_t r = 0; r < rows; r++) {
             const Row row = top_priors_row(q, bits[r], logits[r].data(), (int)K);
@@ -173,6 +169,5 @@ int main() {
             for (int a : row.actions) out.push_back(a);
             for (float p : row.prior) out.push_back((int64_t)bits_of(p));
         }
-    if (fwrite(out.data(), 8, out.size(), stdout) != out.size()) { fprintf(stderr, "short write\n"); return 2; }
-    return 0;
+    return word_stream::flush();
 }

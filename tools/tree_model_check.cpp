@@ -15,33 +15,10 @@
 //           node_action[P N 3] children[P N C] value_sum value_max terminal [P N] reward_lo reward_hi best_reward
 //           best_length [P] best_actions[T P 3]
 // Before the first call every int32 tensor holds -7 (what a test puts into the device tensors the kernel must leave alone).
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-
-#include <vector>
-
 #include "pcb_tree.h"
+#include "word_stream.h"
 
-namespace {
-
-bool read_words(int64_t *dst, size_t n) { return fread(dst, sizeof(int64_t), n, stdin) == n; }
-int64_t read_word(bool *ok) { int64_t v = 0; *ok = *ok && read_words(&v, 1); return v; }
-double as_double(int64_t bits) { double d; memcpy(&d, &bits, 8); return d; }
-int64_t as_bits(double d) { int64_t b; memcpy(&b, &d, 8); return b; }
-
-std::vector<int64_t> out;
-template <class V> void put(const V &v) { for (auto x : v) out.push_back((int64_t)x); }
-void put_bits(const std::vector<double> &v) { for (double x : v) out.push_back(as_bits(x)); }
-
-bool read_ints(std::vector<int> &dst) {
-    std::vector<int64_t> w(dst.size());
-    if (!read_words(w.data(), w.size())) return false;
-    for (size_t i = 0; i < w.size(); i++) dst[i] = (int)w[i];
-    return true;
-}
-
-}  // namespace
+using namespace word_stream;
 
 int main() {
     using namespace pcb_tree;
@@ -50,7 +27,7 @@ int main() {
     const double c_uct = as_double(read_word(&ok));
     if (!ok || P < 0 || N < 1 || C < 1 || C > MAX_CHILDREN || T < 1 || calls < 0) { fprintf(stderr, "bad header\n"); return 2; }
     std::vector<double> ln(N + 1);
-    for (double &x : ln) x = as_double(read_word(&ok));
+    ok = read_doubles(ln);
     const size_t PN = (size_t)P * N, TP3 = (size_t)T * P * 3;
     const int FILL = -7;
     std::vector<int> num_nodes(P, FILL), parent(PN, FILL), depth(PN, FILL), visits(PN, FILL), num_children(PN, FILL), node_action(PN * 3, FILL),
@@ -74,10 +51,7 @@ int main() {
             damaged = true;
         }
         if (!ok || pokes < 0 || phases <= 0 || phases > 7 || ((phases & PHASE_INIT) && (phases & PHASE_ABSORB))) { fprintf(stderr, "call %d: bad phases\n", call); return 2; }
-        if (phases & PHASE_ABSORB) {
-            for (double &x : reward) x = as_double(read_word(&ok));
-            ok = ok && read_ints(length) && read_ints(actions);
-        }
+        if (phases & PHASE_ABSORB) ok = ok && read_doubles(reward) && read_ints(length) && read_ints(actions);
         if ((phases & PHASE_SELECT) && check) ok = ok && read_ints(want_len) && read_ints(want_paths);
         if (!ok) { fprintf(stderr, "call %d: input ends early\n", call); return 2; }
         for (int p = 0; p < P; p++) {
@@ -100,6 +74,5 @@ int main() {
         put(selected); put(path_len); put(paths); put(num_nodes); put(parent); put(depth); put(visits); put(num_children); put(node_action); put(children);
         put_bits(value_sum); put_bits(value_max); put(terminal); put_bits(lo); put_bits(hi); put_bits(best_reward); put(best_length); put(best_actions);
     }
-    if (fwrite(out.data(), sizeof(int64_t), out.size(), stdout) != out.size()) { fprintf(stderr, "short write\n"); return 2; }
-    return 0;
+    return flush();
 }

@@ -11,21 +11,11 @@
 //   in:   O H W fmt C rows | per row: the bit rows [2 H WW] visits[C] actions[C 3] (fmt 0, tuple) or [C] (fmt 1, flat)
 //   out:  per row: error bits | T | index[C] | kept[C] (the visits of the valid entries) | pi[C] (the weight of the logit entry c
 //         names, every entry that names it counted; 0 where index < 0)
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-
-#include <vector>
-
 #include "pcb_transition.h"
 #include "pcb_visit_targets.h"
+#include "word_stream.h"
 
-namespace {
-
-bool read_words(int64_t *dst, size_t n) { return fread(dst, sizeof(int64_t), n, stdin) == n; }
-int64_t float_bits(float v) { uint32_t u; memcpy(&u, &v, 4); return (int64_t)u; }
-
-}  // namespace
+using namespace word_stream;
 
 int main() {
     int64_t head[6];
@@ -37,7 +27,7 @@ int main() {
         return 2;
     }
     const int WW = (W + 63) / 64, HW = H * W, per_action = fmt == PCBENV_ACTION_FLAT ? 1 : 3;
-    std::vector<int64_t> in((size_t)2 * H * WW + (size_t)C + (size_t)C * per_action), out;
+    std::vector<int64_t> in((size_t)2 * H * WW + (size_t)C + (size_t)C * per_action);
     std::vector<u64> vm((size_t)2 * H * WW);
     std::vector<int32_t> visits(C), actions((size_t)C * per_action);
     std::vector<int> index(C), kept(C);
@@ -72,9 +62,8 @@ int main() {
                 pcb_visits::map_place(index[c], W, WW, &word, &bit);
                 pi = pcb_visits::pi_of(sums[pcb_visits::slot_of(before[word], map[word], bit)], T);
             }
-            out.push_back(float_bits(pi));
+            out.push_back(as_bits(pi));
         }
     }
-    if (fwrite(out.data(), sizeof(int64_t), out.size(), stdout) != out.size()) { fprintf(stderr, "short write\n"); return 2; }
-    return 0;
+    return flush();
 }
