@@ -9,7 +9,8 @@ recorded one and returns the state after every call.  The GPU tests compare the 
 
 `synthetic_evaluator` is a seeded hash of (root, path): values from {0.25, 0.5, 0.75}, priors from a small set with
 repeats -- so that equal scores occur -- candidate counts over 0 .. K, a leaf terminal by hash and always at depth T; root
-p % 7 == 6 is terminal at the root and root p % 7 == 5 never has a candidate.
+p % 7 == 6 is terminal at the root and root p % 7 == 5 never has a candidate.  `real_evaluator` is its real-valued twin: values
+whose sums depend on the order of the additions, softmax priors (tests/near_tie_cases.py records searches with it).
 
 `exact_ties` walks the selections of a replay again in Python floats -- the operations of csrc/pcb_puct.h:puct_score one
 by one, each a single IEEE operation -- and counts the levels at which the best score occurs twice.
@@ -177,6 +178,46 @@ def synthetic_evaluator(P, T, K, seed):
             for c in range(K):  # all K rows are filled in whatever the count says: a clamped count reads them
                 actions[p, c] = ((h + c) % 2, 0, c)
                 prior[p, c] = PRIORS[_mix(h, c) % len(PRIORS)]
+        return Evaluation(torch.from_numpy(value), torch.from_numpy(over), torch.from_numpy(count), torch.from_numpy(actions), torch.from_numpy(prior))
+    return evaluate
+
+
+ONE_ULP_APART = (0.7310585786300049, math.nextafter(0.7310585786300049, 1.0))
+
+
+def real_evaluator(P, T, K, seed):
+    """A function of (root, path) as synthetic_evaluator, with real-valued evaluations: value sums depend on the order of
+    the additions, the range is no power of two and a prior times a root is rounded.  The values, by root p % 5:
+      0  -4 +- 1, all 53 mantissa bits hashed           1  1e9 plus multiples of 1e-3, which cancel in the normalisation
+      2  both signs over magnitudes 1e-12 .. 1e6        3  -3.57 always: reward_hi == reward_lo for the whole search
+      4  two values one ulp apart: the range is one ulp
+    The priors are the float32 softmax of hashed logits in [-12, 12] over the K candidates; every seventh node carries one
+    prior that is exactly 0 and one that is denormal (1e-40), and every third node's row is scaled by 1.7 and left
+    unnormalised.  A leaf is terminal by hash (one in five below the root) and always at depth T; one node in eight gets
+    fewer than K candidates."""
+    def evaluate(paths, path_len, step_index0):
+        paths, path_len = paths.numpy(), path_len.numpy()
+        value, over, count = np.zeros(P), np.zeros(P, np.uint8), np.zeros(P, np.int32)
+        actions, prior = np.zeros((P, K, 3), np.int32), np.zeros((P, K), np.float32)
+        for p in range(P):
+            h = _mix(seed, p)
+            for t in range(int(path_len[p])):
+                h = _mix(h, paths[t, p, 0], paths[t, p, 2])
+            frac = float(_mix(h, 1) >> 11) / 9007199254740992.0  # 53 hashed bits in [0, 1)
+            value[p] = (-5.0 + 2.0 * frac, 1e9 + 1e-3 * float((h >> 16) % 7), (1.0 if (h >> 20) & 1 else -1.0) * (1.0 + frac) * 10.0 ** ((h >> 24) % 19 - 12),
+                        -3.57, ONE_ULP_APART[(h >> 16) & 1])[p % 5]
+            over[p] = path_len[p] == T or (path_len[p] > 0 and (h >> 44) % 5 == 0)
+            count[p] = (h >> 32) % (K + 1) if (h >> 40) % 8 == 0 else K
+            logits = np.array([24.0 * float(_mix(h, 2, c) >> 11) / 9007199254740992.0 - 12.0 for c in range(K)], np.float32)
+            e = np.exp(logits - logits.max())
+            row = e / e.sum(dtype=np.float32)
+            if (h >> 48) % 3 == 0:
+                row = row * np.float32(1.7)
+            if (h >> 52) % 7 == 0 and K >= 2:
+                row[(h >> 56) % K], row[((h >> 56) + 1) % K] = 0.0, 1e-40
+            for c in range(K):  # all K rows are filled in whatever the count says: a clamped count reads them
+                actions[p, c] = ((h + c) % 2, 0, c)
+            prior[p] = row
         return Evaluation(torch.from_numpy(value), torch.from_numpy(over), torch.from_numpy(count), torch.from_numpy(actions), torch.from_numpy(prior))
     return evaluate
 
