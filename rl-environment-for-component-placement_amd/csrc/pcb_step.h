@@ -51,6 +51,66 @@ static __device__ __forceinline__ void draw_action(const DevParams &p, Lds &l, i
 #define MODE_FEATURES 3
 // REWARD_PARTS, the reward helpers per listed environment: pcb_layout.h (the host sizes the helper grid by it)
 
+// The plain transition of the geometry-fixed builds (PCB_GEO64_UNIT): a valid action that does not place the last
+// component, done by the environment's own one-wavefront team with one grid row per lane, in place, whole planes.
+// A lane's new occupancy row is a register expression of its old row and the action, so the grid plane -- 4 KB of the
+// 22.9 KB an environment writes -- is stored as soon as the action is known to be valid, and the rest of the update
+// (place_component's pin rotation with its float64 feature rows, lane 0's feature scalars, the cursor: all latency and a
+// few hundred bytes) runs while it drains.  The launch is bound by its store stream, which used to start only behind the
+// whole update.  The mask of the next component is then folded from the same register, with no LDS round trip of the
+// rows in front of it.  Where the update stands was measured: behind the grid plane it wins, behind some or all of the
+// mask planes it loses most of the gain again (profiles/step_dataflow.txt).  Its stores go to addresses nothing else
+// of the launch writes on this arm, so their order against the planes is free.  Same bytes and same state as the
+// general text in transition(), which every other case takes.  Returns `done`.
+template <int KIND, int WW>
+static __device__ __forceinline__ bool plain_transition_from_rows(const DevParams &p, Lds &l, int row, int lane, int o, int x, int y, int cur, int npins) {
+    static_assert(PCB_GEO64_UNIT && NT == WAVE && WW == 1 && pcb_layout::is_pin_kind(KIND), "one row per lane, pin kinds, the geometry-fixed units");
+    const int H = p.H, W = p.W, HW = H * W, plane = H * WW, next = cur + 1;
+    const u64 old_row = l.occ[lane];
+    const CompRec cr = l.comps[cur], nr = l.comps[next];
+    const int ph = PCB_PLACED_H(o, cr.h, cr.w), pw = PCB_PLACED_W(o, cr.h, cr.w);
+    // update_grid: rows x..x+ph-1, columns y..y+pw-1
+    const u64 mine = PCB_ROW_AFTER_UPDATE1(old_row, lane, x, ph, y, pw);
+    l.occ[lane] = mine;  // (one wavefront: the plane trips below read other lanes' rows in program order)
+    STAMP(3);
+    unsigned char *m = p.buf.action_mask ? p.buf.action_mask + (size_t)row * p.O * HW : 0;
+    if (p.buf.grid) emit_plane<WW>(p.buf.grid + (size_t)row * HW, l.occ, 0, H, W, lane, p.stream_stores);
+    // the rest of the update, as transition() has it, while the grid plane drains
+    if (lane == 0) { l.comps[cur].px = (signed char)x; l.comps[cur].py = (signed char)y; l.comps[cur].o = (unsigned char)o; }
+    const int ch = cr.h, cw = cr.w;
+    for (int q = lane; q < npins; q += NT) {  // S:149-190 place_component
+        PinRec pr = l.pins[q];
+        if (pr.comp != cur) continue;
+        PCB_PLACE_PIN(pr, o, ch, cw, x, y)
+        l.pins[q] = pr;
+        write_pin_num<KIND>(p, row, pr);
+    }
+    if (lane == 0) {
+        if (p.buf.all_components_feature) {
+            double *cf = p.buf.all_components_feature + ((size_t)row * p.C + cur) * p.F;
+            cf[2] = x; cf[3] = y;
+        }
+        if (p.buf.placement_mask) {
+            double *pm = p.buf.placement_mask + (size_t)row * p.C;
+            pm[cur] = 2.0; pm[next] = 3.0;
+        }
+        l.hdr->cur = (short)next;
+    }
+    // the mask of the next component, in mask_and_emit's order: fold, planes 0 / 2, fold (or copy), planes 1 / 3
+    const int h = nr.h, w = nr.w;
+    bool any = window_mask_row(mine, l.vm, H, W, h, w, lane);
+    if (m) emit_plane2<WW>(m, m + 2 * HW, l.vm, H, W, lane, p.stream_stores);
+    if (h == w) l.vm[plane + lane] = l.vm[lane];
+    else any |= window_mask_row(mine, l.vm + plane, H, W, w, h, lane);
+    if (m) emit_plane2<WW>(m + HW, m + 3 * HW, l.vm + plane, H, W, lane, p.stream_stores);
+    emit_marginals<KIND, WW>(p, l, row, lane);
+    STAMP(23);
+    lds_sync();
+    if (KIND == PCBENV_SPATIAL) emit_pin_grid<WW>(p, l, row, lane, 0, H);
+    STAMP(4);
+    return episode_done<KIND>(next, any);
+}
+
 // One transition of environment e with action (o, x, y): validate_action, update_grid, place_component, features,
 // legal mask + observation stream, done, terminal reward, and -- PCBENV_FLAG_AUTO_RESET -- the reset that follows a
 // terminal transition.  State is in LDS (l); outputs go to row `row` of the bound tensors.
@@ -76,7 +136,17 @@ static __device__ __forceinline__ void transition(const DevParams &p, Lds &l, in
     if (NT > WAVE) lds_sync();  // every wavefront has read the cursor before wavefront 0 advances it (one wavefront: program order)
 
     bool done = true;  // an invalid action is a terminal transition with state and observations unchanged (quirk Q8 iii)
-    if (valid && !(helpers_route && auto_reset)) {
+    // The geometry-fixed builds take their plain transition -- the planes first, pins and features behind them -- in
+    // plain_transition_from_rows (above); every other case, there and in all other builds, is the text below.
+    constexpr bool ROWS_ARM = PCB_GEO64_UNIT && !TRAJ && NT == WAVE && WW == 1 && pcb_layout::is_pin_kind(KIND);
+    bool rows_arm = false;
+    if constexpr (ROWS_ARM) {
+        rows_arm = valid && mode == MODE_ALL && H == WAVE && next_component(cur, ncomp) >= 0 && !(p.flags & PCBENV_FLAG_INCREMENTAL_OBS);
+        if (rows_arm) done = plain_transition_from_rows<KIND, WW>(p, l, row, lane, o, x, y, cur, npins);
+    }
+    if (rows_arm) {
+        // (done above)
+    } else if (valid && !(helpers_route && auto_reset)) {
         int ph, pw;
         CompRec cr = CompRec();
         if (KIND == PCBENV_SQUARE) ph = pw = p.component_n;

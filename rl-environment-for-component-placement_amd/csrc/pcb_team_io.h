@@ -139,3 +139,12 @@ static __device__ inline bool window_mask(const u64 *occ, u64 *hf, u64 *vm, int 
     }
     return block_any(any, flag);
 }
+// The one-row-per-lane arm above for a caller that holds the lane's occupancy row as a value (`row`: row `lane` of the
+// grid, 0 for lane >= H): nothing is read from LDS, so the fold need not wait for the rows to be written there.
+// pcb_layout::fold_across_lanes(1, NT, H) holds.  The pieces are pcb_transition.h's, checked on the CPU against the window's definition.
+static __device__ inline bool window_mask_row(u64 row, u64 *vm, int H, int W, int ph, int pw, int lane) {
+    const u64 a = rows_vfold(row1_hfold(row, pw), ph, [lane](u64 v, int s) { return lane_down(v, s, lane); });
+    const u64 v = (lane + ph <= H) ? row1_free_below(a, W - pw + 1) : 0ull;
+    if (lane < H) vm[lane] = v;
+    return __any(v != 0ull);
+}

@@ -1,5 +1,6 @@
 // pcb_transition.h -- the scalar core of one transition, stated once: the flat action code, validate_action's range and
-// bit test, update_grid's extent and row fill, place_component's pin rotation with its inverse, the cursor and `done`.
+// bit test, update_grid's extent and row fill (in LDS words, and for one 64-column row held as a value, with the legal-mask
+// window folded from such rows), place_component's pin rotation with its inverse, the cursor and `done`.
 // This is the arithmetic that must match the reference bit for bit.  Plain C++17 behind PCB_HD (it includes only
 // pcb_records.h): the step, playout and policy kernels and tools/transition_check.cpp, which replays the recorded reference
 // transitions of tests/golden on the CPU, compile the same text.  Nothing here knows a team size: the loops over rows and
@@ -49,6 +50,32 @@ PCB_HD inline void placed_extent(int ch, int cw, int o, int *ph, int *pw) { *ph 
         if (hi_ > lo_) (words)[(first) + w_] |= ((hi_ - lo_) >= 64 ? ~0ull : ((1ull << (hi_ - lo_)) - 1ull)) << lo_; \
     }
 PCB_HD inline void occupy_row(u64 *row_words, int WW, int y, int pw) { PCB_OCCUPY_ROW(row_words, 0, WW, y, pw) }
+// The same for WW == 1 with the row held as a value: `row` after columns y..y+pw-1 are filled, 0 <= y, 1 <= pw, y + pw <= 64
+// (what a valid action gives).  pw == 64 forces y == 0, and y + pw == 64 shifts by y < 64: no shift by 64 either way.
+#define PCB_OCCUPIED_ROW1(row, y, pw) ((row) | (((pw) >= 64 ? ~0ull : ((1ull << (pw)) - 1ull)) << (y)))
+PCB_HD inline u64 occupied_row1(u64 row, int y, int pw) { return PCB_OCCUPIED_ROW1(row, y, pw); }
+// row r of the grid, `row` before, after update_grid has placed ph x pw cells at (x, y)
+#define PCB_ROW_AFTER_UPDATE1(row, r, x, ph, y, pw) (((r) >= (x) && (r) < (x) + (ph)) ? PCB_OCCUPIED_ROW1(row, y, pw) : (row))
+PCB_HD inline u64 row_after_update1(u64 row, int r, int x, int ph, int y, int pw) { return PCB_ROW_AFTER_UPDATE1(row, r, x, ph, y, pw); }
+
+// ---- the legal-mask window on rows held as values, one 64-column row per lane (WW == 1; R:526-567, S:1792-1835) -------
+// Team<>::window_mask's one-row-per-lane arm in three pieces that know no lane: the horizontal OR over pw columns, the
+// vertical OR over ph rows by log-step doubling -- `down(a, s)` is the value `a` of the lane s further on, 0 beyond the
+// last; V is one lane's u64 on the device and all 64 of them in tools/step_dataflow_check.cpp -- and the cut to the
+// columns where the window fits.  Team<>::window_mask_row (pcb_team_io.h) puts them together.
+PCB_HD inline u64 row1_hfold(u64 f, int pw) {
+    int s = 1;
+    while (2 * s <= pw) { f |= f >> s; s *= 2; }
+    if (s < pw) f |= f >> (pw - s);
+    return f;
+}
+template <class V, class Down> PCB_HD inline V rows_vfold(V a, int ph, Down down) {
+    int s = 1;
+    while (2 * s <= ph) { a = a | down(a, s); s *= 2; }
+    if (s < ph) a = a | down(a, ph - s);
+    return a;
+}
+PCB_HD inline u64 row1_free_below(u64 a, int n) { return n <= 0 ? 0ull : (~a & (n >= 64 ? ~0ull : ((1ull << n) - 1ull))); }
 
 // ---- place_component (S:149-190): pin pr of the ch x cw component placed at (x, y) with orientation o.  The rotation
 // is kept in rel_x / rel_y (in place, as the reference does); PCB_UNROTATE_REL, just below, undoes it. ------------------
