@@ -45,7 +45,8 @@ class AlphaZeroConfig:
     # Gumbel root search (puct_selfplay's gumbel): every move is a search of `iterations` simulations spent by Sequential
     # Halving over gumbel_considered candidates, and the policy target is softmax(logit + sigma(completed q)) in the place of
     # the visit counts; sigma(q) = (gumbel_c_visit + the most visits of a root child) * gumbel_c_scale * q.  `mode` is then not
-    # read.  None: PUCT at the root.  Not together with noise_alpha or leaves > 1.
+    # read.  None: PUCT at the root.  Not together with noise_alpha; with leaves = L > 1 a move is ceil(iterations / L) + 1 evaluations
+    # of P * L rows (pcbenv_gumbel_advance_leaves).
     gumbel_considered: Optional[int] = None
     gumbel_c_visit: float = 50.0
     gumbel_c_scale: float = 1.0
@@ -116,7 +117,10 @@ class AlphaZeroTrainer:
                            root_noise=None if self.cfg.noise_alpha is None else (self.cfg.noise_alpha, self.cfg.noise_eps),
                            gumbel=None if self.cfg.gumbel_considered is None else (self.cfg.gumbel_considered, self.cfg.gumbel_c_visit, self.cfg.gumbel_c_scale))
         from .batched_env import default_max_steps
-        self.step_index += M * (self.cfg.iterations + (self.cfg.gumbel_considered is not None)) * default_max_steps(root.cfg)
+        evaluations = self.cfg.iterations + (self.cfg.gumbel_considered is not None)
+        if self.cfg.gumbel_considered is not None and self.cfg.leaves != 1:
+            evaluations = -(-self.cfg.iterations // self.cfg.leaves) + 1
+        self.step_index += M * evaluations * default_max_steps(root.cfg)
         z, weight = value_targets(sp.reward.float(), sp.done)
         return {"obs": obs, "mask_bits": bits, "child_visits": sp.child_visits, "child_actions": sp.child_actions, "z": z, "weight": weight,
                 "reward": sp.reward, "done": sp.done, "errors": sp.errors}

@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _gumbel_lib, _leaves_lib, _lib, _move_lib, _noise_lib, _priors_lib, _search_lib, _train_lib
+from . import _gumbel_leaves_lib, _gumbel_lib, _leaves_lib, _lib, _move_lib, _noise_lib, _priors_lib, _search_lib, _train_lib
 from .config import EnvConfig, KIND_PIN, KIND_RECT, KIND_SPATIAL, KIND_SQUARE
 from .instances import Instance, InstanceStream, env_seed, pack_instances
 
@@ -169,7 +169,7 @@ class BatchedPlacementEnv:
             raise RuntimeError("BatchedPlacementEnv needs a GPU device (there is no CPU fallback)")
         # the device the handle lives on, index included: one named without an index is the current device, now and for good
         self.device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
-        self._L = _gumbel_lib.bind(_noise_lib.bind(_leaves_lib.bind(_train_lib.bind(_move_lib.bind(_priors_lib.bind(_search_lib.bind(_lib.load())))))))
+        self._L = _gumbel_leaves_lib.bind(_gumbel_lib.bind(_noise_lib.bind(_leaves_lib.bind(_train_lib.bind(_move_lib.bind(_priors_lib.bind(_search_lib.bind(_lib.load()))))))))
         # per-environment spaces (the reference constructors' declarations); every tensor adds a leading batch dim
         from .spaces import action_space_for, observation_space_for
         self.action_space = self.single_action_space = action_space_for(cfg)
@@ -1051,6 +1051,49 @@ class BatchedPlacementEnv:
         req.seed = (self.run_seed if seed is None else int(seed)) & (2 ** 64 - 1)
         req.step_index, req.first_root = int(step_index) & (2 ** 64 - 1), self.first_env_index
         self._puct_absorb(self._L.pcbenv_gumbel_advance, req, P, phases, value, leaf_terminal, cand_count, cand_actions, cand_prior)
+
+    def gumbel_leaves_request(self, tree: Dict[str, torch.Tensor], c_puct: float = 1.0, max_children: int = 16, c_visit: float = 50.0,
+                              c_scale: float = 1.0, leaves: int = 1) -> "_gumbel_leaves_lib.PcbenvGumbelLeavesRequest":
+        """The request of `gumbel_advance_leaves` for the tensors in `tree`: the tensors of `gumbel_request` and `pending`
+        [P, N], the exchange tensors with the leaf extent of `puct_leaves_request` -- `selected`, `path_len` [P * L], `paths`
+        [T, P * L, 3] -- the members of pcbenv_gumbel_leaves_request (include/pcbenv_gumbel_leaves.h);
+        `pcbenv.search.new_puct_tree(leaves=L)` and `new_gumbel_tensors` have a set of the right shapes.  P, N and T are read
+        off `parent` and `paths`, Mc and n off `considered`; C = max_children and L = leaves are arguments.  The request
+        holds addresses only: the caller keeps the tensors alive."""
+        i32, f64 = torch.int32, torch.float64
+        par, paths, table, L = tree["parent"], tree["paths"], tree["considered"], int(leaves)
+        if L < 1 or L > _leaves_lib.MAX_PUCT_LEAVES:
+            raise ValueError(f"leaves must be in [1, {_leaves_lib.MAX_PUCT_LEAVES}], got {L}")
+        if par.dim() != 2 or paths.dim() != 3 or paths.shape[1:] != (par.shape[0] * L, 3):
+            raise ValueError(f"parent must be [P, N] and paths [T, P * {L}, 3], got {tuple(par.shape)} and {tuple(paths.shape)}")
+        if table.dim() != 2 or table.shape[0] < 2 or table.shape[0] > _gumbel_lib.MAX_CONSIDERED + 1 or table.shape[1] < 1:
+            raise ValueError(f"considered must be [Mc + 1, n] with Mc in [1, {_gumbel_lib.MAX_CONSIDERED}] and n >= 1, got {tuple(table.shape)}")
+        (P, N), T, Cn, (rows, n) = par.shape, paths.shape[0], int(max_children), table.shape
+        own = {**_exchange_want(T, P * L), "sim_index": (i32, (P,)), "sim_visits": (i32, (P, Cn)), "considered": (i32, (rows, n)), "move_slot": (i32, (P,)),
+               "move_action": (i32, (P, 3)), "child_weights": (i32, (P, Cn)), "child_policy": (torch.float32, (P, Cn)),
+               "child_actions": (i32, (P, Cn, 3)), "root_value": (f64, (P,))}
+        return self._tree_request(_gumbel_leaves_lib.PcbenvGumbelLeavesRequest, tree, _puct_tree_want(P, N, own, slots=("pending",)), num_roots=P,
+                                  capacity=N, max_children=Cn, max_steps=T, num_simulations=n, max_considered=rows - 1, c_puct=float(c_puct),
+                                  c_visit=float(c_visit), c_scale=float(c_scale), num_leaves=L)
+
+    def gumbel_advance_leaves(self, req: "_gumbel_leaves_lib.PcbenvGumbelLeavesRequest", phases: int, value: Optional[torch.Tensor] = None,
+                              leaf_terminal: Optional[torch.Tensor] = None, cand_count: Optional[torch.Tensor] = None,
+                              cand_actions: Optional[torch.Tensor] = None, cand_prior: Optional[torch.Tensor] = None, seed: Optional[int] = None,
+                              step_index: int = 0) -> None:
+        """`gumbel_advance` with L = req.num_leaves descents per root and launch (`pcbenv_gumbel_advance_leaves`, one kernel
+        launch on the current stream, nothing else): the same phases and key.  SELECT takes up to L scheduled simulations
+        of every root, one after the other along the schedule, each descent leaving a pending visit on its path, and
+        writes `selected`, `path_len` [P * L] and `paths` [T, P * L, 3], row p * L + l the leaf l of root p, -1 in `selected`
+        and `path_len` where there is no leaf: behind a repeat, which consumes no simulation, and behind the end of the
+        budget.  ABSORB is `puct_advance_leaves`', with the same inputs of P * L rows.  BEGIN and CHOOSE are
+        `gumbel_advance`'s.  `req`: `gumbel_leaves_request(tree, ...)`, reusable for every call on the same tensors."""
+        P = req.num_roots
+        if P == 0:  # torch gives empty tensors a null pointer
+            return
+        req.seed = (self.run_seed if seed is None else int(seed)) & (2 ** 64 - 1)
+        req.step_index, req.first_root = int(step_index) & (2 ** 64 - 1), self.first_env_index
+        self._puct_absorb(self._L.pcbenv_gumbel_advance_leaves, req, P * req.num_leaves, phases, value, leaf_terminal, cand_count, cand_actions,
+                          cand_prior)
 
     def top_priors(self, logits: torch.Tensor, K: int, mask_bits: Optional[torch.Tensor] = None,
                    out: Optional[Sequence[torch.Tensor]] = None, errors: Optional[torch.Tensor] = None):

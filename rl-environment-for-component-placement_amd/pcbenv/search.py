@@ -519,7 +519,7 @@ def _puct_arguments(root, iterations, max_children, max_steps, capacity, tree=No
 
 def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float = 1.0, max_children: int = 16, max_steps=None,
                 capacity=None, tree=None, leaves: int = 1, root_noise=None, noise_seed=None, noise_first_root=None,
-                noise_step_index=None, root_select=None) -> PuctSearch:
+                noise_step_index=None, root_select=None, leaf_begin=None, leaf_end=None) -> PuctSearch:
     """Batched PUCT (the AlphaZero search) over all P = root.num_envs roots in lock-step, the tree in tensors, one
     `evaluate` per iteration and no host synchronisation inside the loop: the specification of pcbenv_puct_advance
     (include/pcbenv_search.h), in tensor code for any device.  Iteration m:
@@ -556,13 +556,17 @@ def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float 
     search.  noise_seed defaults to root.run_seed ^ 0x6e6f6973 and noise_first_root to root.first_env_index; a root that
     is no BatchedPlacementEnv gives the seed explicitly (the first root then defaults to 0).  noise_step_index: the step
     index of the key where it is not the search's own (move j of `puct_selfplay` has step_index + j).  None: no noise.
-    root_select: another rule for level 0 (`gumbel_search`'s), leaves == 1 only: root_select(tree, stopped, nxt) -> the node
-    every root goes to from slot 0, given the tree as it stands (a dict of views that must not be modified), the roots
-    that stop at slot 0 and the node PUCT would go to.  None: PUCT at every level."""
+    root_select: another rule for level 0 (`gumbel_search`'s): root_select(tree, stopped, nxt) -> the node every root goes to
+    from slot 0, given the tree as it stands (a dict of views that must not be modified), the roots that stop at slot 0 and
+    the node PUCT would go to; it is called once per leaf.  None: PUCT at every level.  With leaves > 1 such a rule has a
+    budget to keep, so it comes with two more hooks: leaf_begin(l, tree, alive) -> alive, called before the descent of leaf l
+    with the roots that have had no repeat so far, returns those that take this leaf -- the others get no leaf from here on,
+    as behind a repeat, and add no pending visit -- and leaf_end(l, alive), called behind the descent with the roots whose
+    leaf l is a leaf: a repeat is not among them, so what root_select proposed for it is not committed."""
     P, C, M, T, N = _puct_arguments(root, iterations, max_children, max_steps, capacity, tree, leaves)
     L = int(leaves)
-    if root_select is not None and L != 1:
-        raise ValueError("root_select needs leaves == 1")
+    if root_select is not None and L != 1 and (leaf_begin is None or leaf_end is None):
+        raise ValueError("root_select with leaves > 1 needs leaf_begin and leaf_end")
     noise = _noise_arguments(root, root_noise, noise_seed, noise_first_root)
     dev = getattr(root, "device", "cpu")
     i64, f64 = dict(dtype=torch.int64, device=dev), dict(dtype=torch.float64, device=dev)
@@ -592,6 +596,11 @@ def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float 
     none = torch.full((P,), -1, **i64)
     noised = torch.zeros(P, dtype=torch.int32, device=dev)
 
+    def view():  # the tree as it stands, for a hook
+        return dict(num_nodes=count, parent=parent[:, :N], depth=depth[:, :N], visits=visits[:, :N], num_children=nchild[:, :N],
+                    first_child=first_child[:, :N], node_action=node_action[:, :N], prior=prior[:, :N], value_sum=vsum[:, :N],
+                    value_max=vmax[:, :N], terminal=terminal[:, :N], reward_lo=lo, reward_hi=hi)
+
     def add_noise(noised, errors):
         now = dict(num_children=nchild[:, :N], first_child=first_child[:, :N], prior=prior[:, :N])
         prior[:, :N], done = puct_root_noise(now, noised, C, noise[0], noise[1], noise[2], step_index if noise_step_index is None else noise_step_index,
@@ -607,6 +616,8 @@ def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float 
         alive = torch.ones(P, dtype=torch.bool, device=dev)  # no repeat so far
         chosen, levels = [], []
         for l in range(L):
+            if leaf_begin is not None:
+                alive = leaf_begin(l, view(), alive)
             node = torch.zeros(P, **i64)
             plen = torch.zeros(P, **i64)
             stopped = ~alive
@@ -626,9 +637,7 @@ def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float 
                 score = torch.where(mine, q + u, torch.full_like(q, float("-inf")))
                 nxt = fc + score.argmax(dim=1)                         # the first maximum: the lowest child
                 if root_select is not None and d == 0:
-                    nxt = root_select(dict(num_nodes=count, parent=parent[:, :N], depth=depth[:, :N], visits=visits[:, :N], num_children=nchild[:, :N],
-                                           first_child=first_child[:, :N], node_action=node_action[:, :N], prior=prior[:, :N], value_sum=vsum[:, :N],
-                                           value_max=vmax[:, :N], terminal=terminal[:, :N], reward_lo=lo, reward_hi=hi), stopped, nxt)
+                    nxt = root_select(view(), stopped, nxt)
                 pending[rows, torch.where(stopped, trash, node)] += 1  # the node the descent leaves
                 node = torch.where(stopped, node, nxt)
                 paths[torch.where(stopped, torch.full_like(node, T), torch.full_like(node, d)), rows, l] = node_action[rows, node]
@@ -642,6 +651,8 @@ def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float 
                 pending[rows, idx] -= on.to(torch.int64)
                 cur = torch.where(on, parent[rows, idx], none)
             alive = alive & ~repeat
+            if leaf_end is not None:
+                leaf_end(l, alive)
             pending[rows, torch.where(alive, node, trash)] += 1
             chosen.append(torch.where(alive, node, none))
             levels.append(torch.where(alive, plen, none))
@@ -1213,28 +1224,74 @@ def _gumbel_arguments(root, simulations, max_considered, seed, first_root):
     return n, Mc, (int(root.run_seed) ^ 0x67756d62) if seed is None else int(seed), int(getattr(root, "first_env_index", 0) if first_root is None else first_root)
 
 
+def _gumbel_launches(simulations, leaves, launches):
+    """(L, the evaluations of a Gumbel search of n simulations with L leaves per launch): `launches`, or ceil(n / L) + 1 --
+    n + 1 with one leaf, one evaluation per simulation and the root's own."""
+    L = int(leaves)
+    if L < 1 or L > 64:
+        raise ValueError("a Gumbel search needs leaves in [1, 64]")
+    E = -(-int(simulations) // L) + 1 if launches is None else int(launches)
+    if E < 1:
+        raise ValueError("a Gumbel search needs launches >= 1")
+    return L, E
+
+
 def gumbel_search(root, simulations: int, step_index: int, evaluate, max_considered: int = 16, c_visit: float = 50.0, c_scale: float = 1.0,
                   c_puct: float = 1.0, max_children: int = 16, max_steps=None, capacity=None, tree=None, seed=None, first_root=None,
-                  gumbel_step_index=None) -> GumbelSearch:
+                  gumbel_step_index=None, leaves: int = 1, launches=None) -> GumbelSearch:
     """The search of one move under the Gumbel rule, the whole of it as specification: `puct_search` with n + 1 =
     simulations + 1 evaluations whose level 0 is `gumbel_select_root`'s while the budget lasts, then `gumbel_choose`.  A fresh
     root spends evaluation 0 on its own expansion and then makes exactly n scheduled simulations; a kept root (tree=) makes n
     scheduled simulations and one PUCT descent.  Below the root every level is PUCT's.  The draws have the key (seed,
     first_root + p, gumbel_step_index), defaulting to root.run_seed ^ 0x67756d62, root.first_env_index and step_index;
-    capacity defaults to 1 + (n + 1) * max_children."""
+    capacity defaults to 1 + (n + 1) * max_children.
+    leaves = L > 1: several simulations per evaluation, the specification of pcbenv_gumbel_advance_leaves
+    (include/pcbenv_gumbel_leaves.h): `puct_search(leaves=L)` with `launches` evaluations of P * L rows, default ceil(n / L) + 1.
+    Leaf after leaf a root takes the next simulation of its schedule -- `gumbel_select_root` on the counters as the leaves
+    before left them; its scores read no pending visit, so they are the same for every leaf -- and descends from the child
+    by the pending-visit score.  A repeat consumes no simulation and ends the root's leaves of this evaluation, as does the
+    end of the budget at a leaf behind the first; with the budget spent, the first leaf is one PUCT descent.  A root that is
+    terminal or has no children has one leaf, itself.  A root whose repeats left sim_index < n when the launches are over
+    is chosen as it stands: `sim_index` tells the share of the budget spent.  capacity defaults to 1 + launches * L *
+    max_children."""
     n, Mc, seed, first = _gumbel_arguments(root, simulations, max_considered, seed, first_root)
     C, c_visit, c_scale = _gumbel_rule(max_children, c_visit, c_scale)
     key = int(step_index if gumbel_step_index is None else gumbel_step_index)
     P, dev = int(root.num_envs), getattr(root, "device", "cpu")
     table = considered_visits(Mc, n).to(dev)
     state = dict(sim_index=torch.zeros(P, dtype=torch.int32, device=dev), sim_visits=torch.zeros((P, C), dtype=torch.int32, device=dev))
+    L, E = _gumbel_launches(n, leaves, launches)
 
     def root_select(now, stopped, nxt):
         sel = gumbel_select_root(now, state["sim_index"], state["sim_visits"], table, C, c_visit, c_scale, seed, key, first)
         state.update(sim_index=sel["sim_index"], sim_visits=sel["sim_visits"])
         return torch.where(sel["scheduled"], now["first_child"][:, 0].to(torch.int64) + sel["child"], nxt)
-    ps = puct_search(root, n + 1, step_index, evaluate, c_puct=c_puct, max_children=C, max_steps=max_steps, capacity=capacity, tree=tree,
-                     root_select=root_select)
+    if L == 1 and launches is None:
+        ps = puct_search(root, n + 1, step_index, evaluate, c_puct=c_puct, max_children=C, max_steps=max_steps, capacity=capacity, tree=tree,
+                         root_select=root_select)
+    else:
+        proposed = {}
+
+        def leaf_begin(l, now, alive):  # a root that takes no descent, or has no simulation left, has its one leaf and no more
+            proposed.clear()
+            if l == 0:
+                return alive
+            k, fc, t = now["num_children"][:, 0], now["first_child"][:, 0], state["sim_index"].to(torch.int64)
+            ok = (k >= 1) & (k <= C) & (fc >= 1) & (fc <= int(now["prior"].shape[1]) - k)
+            return alive & ~(now["terminal"][:, 0] != 0) & ok & (t >= 0) & (t < n)
+
+        def propose(now, stopped, nxt):  # the counters move when the leaf has turned out to be one
+            sel = proposed["sel"] = gumbel_select_root(now, state["sim_index"], state["sim_visits"], table, C, c_visit, c_scale, seed, key, first)
+            return torch.where(sel["scheduled"], now["first_child"][:, 0].to(torch.int64) + sel["child"], nxt)
+
+        def leaf_end(l, alive):
+            sel = proposed.get("sel")
+            if sel is not None:
+                keep = alive & sel["scheduled"]
+                state.update(sim_index=torch.where(keep, sel["sim_index"], state["sim_index"]),
+                             sim_visits=torch.where(keep[:, None], sel["sim_visits"], state["sim_visits"]))
+        ps = puct_search(root, E, step_index, evaluate, c_puct=c_puct, max_children=C, max_steps=max_steps, capacity=capacity, tree=tree, leaves=L,
+                         root_select=propose, leaf_begin=leaf_begin, leaf_end=leaf_end)
     ch = gumbel_choose(search_tree(ps), state["sim_visits"], C, c_visit, c_scale, seed, key, first)
     return GumbelSearch(ps, state["sim_index"], state["sim_visits"], ch["move_slot"], ch["move_action"], ch["child_weights"], ch["child_policy"],
                         ch["child_actions"], ch["root_value"])
@@ -1251,21 +1308,49 @@ def _gumbel_iterations(root, greq, tree, n, T, evaluate, step_index, seed, key):
                             seed=seed, step_index=key)
 
 
+def _gumbel_leaves_iterations(root, greq, tree, E, T, evaluate, step_index, seed, key):
+    """The launches of one device Gumbel search with leaves on `tree`: BEGIN | SELECT, then E times `evaluate` followed by
+    ABSORB | SELECT, the last time by ABSORB alone -- pcbenv_gumbel_advance_leaves every one."""
+    root.gumbel_advance_leaves(greq, GUMBEL_BEGIN | GUMBEL_SELECT, seed=seed, step_index=key)
+    for m in range(E):
+        ev = evaluate(tree["paths"], tree["path_len"], int(step_index) + m * T)
+        over = ev.terminal.view(torch.uint8) if ev.terminal.dtype == torch.bool else ev.terminal
+        root.gumbel_advance_leaves(greq, GUMBEL_ABSORB | (GUMBEL_SELECT if m + 1 < E else 0), ev.value, over, ev.cand_count, ev.cand_actions,
+                                   ev.cand_prior, seed=seed, step_index=key)
+
+
 def gumbel_search_device(root, simulations: int, step_index: int, evaluate, max_considered: int = 16, c_visit: float = 50.0, c_scale: float = 1.0,
                          c_puct: float = 1.0, max_children: int = 16, max_steps=None, capacity=None, tree=None, seed=None,
-                         gumbel_step_index=None) -> GumbelSearch:
+                         gumbel_step_index=None, leaves: int = 1, launches=None) -> GumbelSearch:
     """`gumbel_search` with the tree kept by the device: `root.gumbel_advance` (pcbenv_gumbel_advance) is the one launch per
     evaluation, with no tensor operation between them: BEGIN | SELECT first -- a fresh tree gets `puct_advance(INIT)` before
     it -- then n + 1 times `evaluate(tree paths, path_len, step_index + m * max_steps)` followed by ABSORB | SELECT, the last
     time by ABSORB alone, then CHOOSE.  The same search as `gumbel_search` with the same arguments: the same evaluations, the
     same tree, counters, move and target, field by field, floats by their bits.
     tree: the search continues in this tree, in place -- the tensors of `new_puct_tree` and `new_gumbel_tensors` (for this
-    max_considered and simulations) as an earlier search or `puct_move(MOVE_REROOT)` left them."""
+    max_considered and simulations) as an earlier search or `puct_move(MOVE_REROOT)` left them.
+    leaves = L > 1, launches: `gumbel_search(leaves=L, launches=)` with `root.gumbel_advance_leaves`
+    (pcbenv_gumbel_advance_leaves, include/pcbenv_gumbel_leaves.h) as the one launch per evaluation: BEGIN | SELECT first -- a
+    fresh tree gets `puct_advance_leaves(INIT)` before it, so that `pending` is zero -- then `launches` times `evaluate` and
+    ABSORB | SELECT, the last time ABSORB alone, then CHOOSE; `evaluate` sees P * L rows, path_len -1 where there is no leaf.  A
+    tree that is kept is one of `new_puct_tree(leaves=L)`."""
     from . import _lib
     n, Mc, seed, _ = _gumbel_arguments(root, simulations, max_considered, seed, None)
-    P, C, M, T, N = _puct_arguments(root, n + 1, max_children, max_steps, capacity, tree)
+    L, E = _gumbel_launches(n, leaves, launches)
     key = int(step_index if gumbel_step_index is None else gumbel_step_index)
     kept = tree is not None
+    if L != 1 or launches is not None:
+        P, C, M, T, N = _puct_arguments(root, E, max_children, max_steps, capacity, tree, L)
+        if not kept:
+            tree = new_puct_tree(P, N, T, root.device, L)
+            tree.update(new_gumbel_tensors(P, C, Mc, n, root.device))
+            root.puct_advance_leaves(root.puct_leaves_request(tree, c_puct, C, L), _lib.TREE_INIT)
+        greq = root.gumbel_leaves_request(tree, c_puct, C, c_visit, c_scale, L)
+        _gumbel_leaves_iterations(root, greq, tree, E, T, evaluate, step_index, seed, key)
+        root.gumbel_advance_leaves(greq, GUMBEL_CHOOSE, seed=seed, step_index=key)
+        return GumbelSearch(puct_result(tree, C), tree["sim_index"], tree["sim_visits"], tree["move_slot"], tree["move_action"], tree["child_weights"],
+                            tree["child_policy"], tree["child_actions"], tree["root_value"])
+    P, C, M, T, N = _puct_arguments(root, n + 1, max_children, max_steps, capacity, tree)
     if not kept:
         tree = new_puct_tree(P, N, T, root.device)
         tree.update(new_gumbel_tensors(P, C, Mc, n, root.device))
@@ -1321,13 +1406,20 @@ def puct_selfplay(root, evaluate, moves: int, iterations: int, step_index: int =
     of the most-simulated root children, `child_visits` holds `child_weights`, the policy target softmax(logit +
     sigma(completed q)) in units of 2^-24, which `visit_targets.cross_entropy` takes as it takes visit counts.  `mode` is not
     read: the choice is the sample.  The draws of move j have the key (gumbel_seed, first_env_index + p, step_index + j),
-    gumbel_seed defaulting to run_seed ^ 0x67756d62.  The default capacity is 1 + 2 * (n + 1) * max_children; leaves must be
-    1, and together with root_noise it raises ValueError."""
+    gumbel_seed defaulting to run_seed ^ 0x67756d62.  The default capacity is 1 + 2 * (n + 1) * max_children; together with
+    root_noise it raises ValueError.  With leaves = L > 1 every move is `gumbel_search_device(leaves=L)`: ceil(n / L) + 1
+    evaluations of P * L rows and pcbenv_gumbel_advance_leaves launches, the default capacity 1 + 2 * (ceil(n / L) + 1) * L *
+    max_children; `pending` is zero after the last ABSORB, so REROOT takes the tree as it is.
+    `evaluate` must be callable: ValueError otherwise, before anything is allocated."""
     from . import _lib, _move_lib
     L = int(leaves)
-    if gumbel is not None and (root_noise is not None or L != 1):
-        raise ValueError("gumbel= goes with neither root_noise nor leaves > 1")
-    E = int(iterations) + (1 if gumbel is not None else 0)  # evaluations per move
+    if not callable(evaluate):
+        raise ValueError("puct_selfplay needs an evaluate(paths, path_len, step_index0) to call")
+    if gumbel is not None and root_noise is not None:
+        raise ValueError("gumbel= does not go with root_noise")
+    E = int(iterations) + 1 if gumbel is not None else int(iterations)  # evaluations per move
+    if gumbel is not None and L != 1:
+        E = _gumbel_launches(_gumbel_arguments(root, iterations, gumbel[0], gumbel_seed, None)[0], L, None)[1]
     P, C, M, T, N = _puct_arguments(root, E, max_children, max_steps, 1 + 2 * E * L * int(max_children) if capacity is None else capacity, leaves=L)
     J = int(moves)
     if J < 1:
@@ -1339,10 +1431,10 @@ def puct_selfplay(root, evaluate, moves: int, iterations: int, step_index: int =
     if gumbel is not None:
         n, Mc, gseed, _ = _gumbel_arguments(root, iterations, gumbel[0], gumbel_seed, None)
         tree.update(new_gumbel_tensors(P, C, Mc, n, dev))
-        greq = root.gumbel_request(tree, c_puct, C, gumbel[1], gumbel[2])
+        greq = root.gumbel_request(tree, c_puct, C, gumbel[1], gumbel[2]) if L == 1 else root.gumbel_leaves_request(tree, c_puct, C, gumbel[1], gumbel[2], L)
     req, mreq = root.puct_request(tree, c_puct, C) if L == 1 else root.puct_leaves_request(tree, c_puct, C, L), root.puct_move_request(tree, C)
     if gumbel is not None:
-        root.puct_advance(req, _lib.TREE_INIT)
+        (root.puct_advance if L == 1 else root.puct_advance_leaves)(req, _lib.TREE_INIT)
     seed = (root.run_seed ^ 0x6d6f7665) if seed is None else int(seed)
     noise = _noise_arguments(root, root_noise, noise_seed, None)
     nreq = root.puct_noise_request(tree, C) if noise is not None else None
@@ -1351,7 +1443,10 @@ def puct_selfplay(root, evaluate, moves: int, iterations: int, step_index: int =
                    torch.empty((J, P), dtype=torch.float64, device=dev), torch.empty((J, P), dtype=torch.float64, device=dev),
                    torch.empty((J, P), dtype=torch.uint8, device=dev), torch.empty((J, P), **i32), tree["errors_dev"][0], tree)
     for j in range(J):
-        if gumbel is not None:
+        if gumbel is not None and L != 1:
+            _gumbel_leaves_iterations(root, greq, tree, M, T, evaluate, int(step_index) + j * M * T, gseed, int(step_index) + j)
+            root.gumbel_advance_leaves(greq, GUMBEL_CHOOSE, seed=gseed, step_index=int(step_index) + j)
+        elif gumbel is not None:
             _gumbel_iterations(root, greq, tree, n, T, evaluate, int(step_index) + j * M * T, gseed, int(step_index) + j)
             root.gumbel_advance(greq, GUMBEL_CHOOSE, seed=gseed, step_index=int(step_index) + j)
         else:

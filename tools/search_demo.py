@@ -1,5 +1,5 @@
 """Receding-horizon Monte-Carlo lookahead with pcbenv.search.best_of_k against the plain uniform-random policy, c3.
-python tools/search_demo.py [--roots 256] [--k 16] [--playouts | --tree [--device-tree] [--policy] | --puct [--device-priors] [--reuse] [--leaves L] [--noise ALPHA EPS | --gumbel M] [--train N [--moves M] [--torch-loss]]]
+python tools/search_demo.py [--roots 256] [--k 16] [--playouts | --tree [--device-tree] [--policy] | --puct [--device-priors] [--reuse] [--leaves L] [--noise ALPHA EPS | --gumbel M [--leaves L]] [--train N [--moves M] [--torch-loss]]]
 
 Both play the same instances (one episode per root environment).  The search forks every root k times into a planner
 batch (one device-side gather), plays every child to its end with the on-device sampler, and applies the best child's
@@ -25,6 +25,10 @@ the 16 child entries of a move's root that got no visit (entries behind the root
 the root level of every search is a Gumbel search (pcbenv_gumbel_advance): k simulations per move, k + 1 evaluations, spent by
 Sequential Halving over M candidates, c_visit 50 and c_scale 1; the move is the best of the most-simulated children, and with
 --reuse the policy target is softmax(logit + sigma(completed q)), whose entries without weight zero_visit_share then counts.
+--puct --gumbel M --leaves L: up to L simulations of a root per launch (pcbenv_gumbel_advance_leaves): a move is k simulations in
+ceil(k / L) + 1 evaluations of roots x L rows; the line then also reports the rows that were leaves, their cost, the share of
+rows that were none (-1: behind a repeat or the end of the budget) and, with --reuse, the share of searched roots that finished
+their schedule (sim_index == k).
 --puct --train N (a spatial configuration: --config
 c4): N rounds of pcbenv.alphazero.AlphaZeroTrainer -- collect() plays --moves moves of every root with puct_selfplay, k
 iterations each, pcbenv/policy.py's model behind network_evaluator(priors="device"); update() trains the model on the visit
@@ -124,8 +128,8 @@ def main():
         ap.error("--leaves goes with --puct")
     if a.noise and not a.puct:
         ap.error("--noise goes with --puct")
-    if a.gumbel is not None and (not a.puct or a.noise or a.leaves != 1):
-        ap.error("--gumbel goes with --puct, without --noise and --leaves")
+    if a.gumbel is not None and (not a.puct or a.noise):
+        ap.error("--gumbel goes with --puct, without --noise")
     if a.puct and (a.tree or a.playouts):
         ap.error("--puct goes alone")
     if a.device_tree and not a.tree:
@@ -152,6 +156,14 @@ def main():
     if a.puct:
         zeros = torch.zeros((P * a.leaves, cfg.num_orientations * cfg.height * cfg.width), dtype=torch.float32, device=search_root.device)
         evaluate = network_evaluator(search_root, planner, lambda obs: zeros, max_children=16, priors="device" if a.device_priors else "torch", leaves=a.leaves)
+        leaf_rows, all_rows = torch.zeros((), dtype=torch.int64, device=search_root.device), [0]  # rows evaluated that were leaves, rows in all
+        counted = evaluate
+
+        def evaluate(paths, path_len, step_index0):
+            all_rows[0] += path_len.numel()
+            if a.leaves != 1:  # with one leaf every row is one: nothing is counted on the device
+                leaf_rows.add_((path_len >= 0).sum())
+            return counted(paths, path_len, step_index0)
     if a.policy:
         from pcbenv.policy import SpatialPolicy
         torch.manual_seed(0)
@@ -171,8 +183,8 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if a.puct and a.gumbel is not None:
-            first = gumbel_search_device(search_root, k, 1000 + t * T * (k + 1), evaluate, max_considered=a.gumbel, max_children=16,
-                                         gumbel_step_index=1000 + t).move_action
+            first = gumbel_search_device(search_root, k, 1000 + t * T * (-(-k // a.leaves) + 1), evaluate, max_considered=a.gumbel, max_children=16,
+                                         gumbel_step_index=1000 + t, leaves=a.leaves).move_action
         elif a.puct:
             first = puct_search_device(search_root, k, 1000 + t * T * k, evaluate, max_children=16, leaves=a.leaves, root_noise=a.noise).action
         elif a.tree:
@@ -188,16 +200,24 @@ def main():
         return r, d
     kept = None
     if a.reuse:
+        finished = torch.zeros(2, dtype=torch.int64, device=search_root.device)  # searched roots that finished their schedule, searched roots
+
+        def on_move(j, tree):
+            if a.gumbel is not None:
+                finished[0] += (tree["sim_index"] == k).sum()
+                finished[1] += (tree["sim_index"] > 0).sum()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         sp = puct_selfplay(search_root, evaluate, T, k, step_index=1000, max_children=16, leaves=a.leaves, root_noise=a.noise,
-                           gumbel=None if a.gumbel is None else (a.gumbel, 50.0, 1.0))
+                           gumbel=None if a.gumbel is None else (a.gumbel, 50.0, 1.0), on_move=on_move)
         torch.cuda.synchronize()
         spent, planner_steps = time.perf_counter() - t0, P * k * a.leaves * T * T
         search_final = final_rewards(search_root, lambda t: (sp.reward[t], sp.done[t]), T)
         kept = {"mean_visits_kept_per_move": round(float(sp.kept_visits[:-1].double().mean()), 2), "tree_errors": int(sp.errors)}
         searched = sp.child_visits.sum(dim=2) > 0
         kept["zero_visit_share"] = round(float((sp.child_visits[searched] == 0).double().mean()), 4)
+        if a.gumbel is not None:
+            kept["finished_schedule_share"] = round(int(finished[0]) / max(int(finished[1]), 1), 4)
     else:
         search_final = final_rewards(search_root, search_step, T)
     out = {"config": a.config, "roots": P, "k": k, "search": ("puct_selfplay" if a.reuse else "puct_search_device") + "+network_evaluator" + ("(priors=device)" if a.device_priors else "") if a.puct else ("tree_search_device" if a.device_tree else "tree_search") + ("+policy_backend" if a.policy else "") if a.tree else "best_of_k_playouts" if a.playouts else "best_of_k",
@@ -211,6 +231,10 @@ def main():
         out["noise"] = a.noise
     if a.gumbel is not None:
         out["gumbel"] = a.gumbel
+    if a.puct:
+        total = all_rows[0]
+        leaves = int(leaf_rows) if a.leaves != 1 else total
+        out.update(evaluated_leaves=leaves, us_per_evaluated_leaf=round(1e6 * spent / max(leaves, 1), 3), no_leaf_share=round(1.0 - leaves / max(total, 1), 4))
     out["seconds_per_move"] = round(spent / T, 4)
     print(json.dumps(out), flush=True)
     for e in (rand_root, search_root, planner):
