@@ -50,6 +50,9 @@ class AlphaZeroConfig:
     gumbel_considered: Optional[int] = None
     gumbel_c_visit: float = 50.0
     gumbel_c_scale: float = 1.0
+    # the full Gumbel rule (puct_selfplay's gumbel_full, pcbenv_gumbel_tree_advance): below the root the search goes to the
+    # argmax of pi' - n / (1 + sum n) and a child without a visit is completed with v_mix; needs gumbel_considered and leaves = 1
+    gumbel_full: bool = False
 
 
 def value_targets(reward: torch.Tensor, done: torch.Tensor):
@@ -115,7 +118,8 @@ class AlphaZeroTrainer:
                            max_children=self.cfg.max_children, capacity=self.cfg.capacity, mode=self.cfg.mode,
                            on_move=lambda j, tree: keep_root(j + 1) if j + 1 < M else None, leaves=self.cfg.leaves,
                            root_noise=None if self.cfg.noise_alpha is None else (self.cfg.noise_alpha, self.cfg.noise_eps),
-                           gumbel=None if self.cfg.gumbel_considered is None else (self.cfg.gumbel_considered, self.cfg.gumbel_c_visit, self.cfg.gumbel_c_scale))
+                           gumbel=None if self.cfg.gumbel_considered is None else (self.cfg.gumbel_considered, self.cfg.gumbel_c_visit, self.cfg.gumbel_c_scale),
+                           gumbel_full=self.cfg.gumbel_full)
         from .batched_env import default_max_steps
         evaluations = self.cfg.iterations + (self.cfg.gumbel_considered is not None)
         if self.cfg.gumbel_considered is not None and self.cfg.leaves != 1:

@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _gumbel_leaves_lib, _gumbel_lib, _leaves_lib, _lib, _move_lib, _noise_lib, _priors_lib, _search_lib, _train_lib
+from . import _gumbel_leaves_lib, _gumbel_lib, _gumbel_tree_lib, _leaves_lib, _lib, _move_lib, _noise_lib, _priors_lib, _search_lib, _train_lib
 from .config import EnvConfig, KIND_PIN, KIND_RECT, KIND_SPATIAL, KIND_SQUARE
 from .instances import Instance, InstanceStream, env_seed, pack_instances
 
@@ -169,7 +169,7 @@ class BatchedPlacementEnv:
             raise RuntimeError("BatchedPlacementEnv needs a GPU device (there is no CPU fallback)")
         # the device the handle lives on, index included: one named without an index is the current device, now and for good
         self.device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
-        self._L = _gumbel_leaves_lib.bind(_gumbel_lib.bind(_noise_lib.bind(_leaves_lib.bind(_train_lib.bind(_move_lib.bind(_priors_lib.bind(_search_lib.bind(_lib.load()))))))))
+        self._L = _gumbel_tree_lib.bind(_gumbel_leaves_lib.bind(_gumbel_lib.bind(_noise_lib.bind(_leaves_lib.bind(_train_lib.bind(_move_lib.bind(_priors_lib.bind(_search_lib.bind(_lib.load())))))))))
         # per-environment spaces (the reference constructors' declarations); every tensor adds a leading batch dim
         from .spaces import action_space_for, observation_space_for
         self.action_space = self.single_action_space = action_space_for(cfg)
@@ -1051,6 +1051,23 @@ class BatchedPlacementEnv:
         req.seed = (self.run_seed if seed is None else int(seed)) & (2 ** 64 - 1)
         req.step_index, req.first_root = int(step_index) & (2 ** 64 - 1), self.first_env_index
         self._puct_absorb(self._L.pcbenv_gumbel_advance, req, P, phases, value, leaf_terminal, cand_count, cand_actions, cand_prior)
+
+    def gumbel_tree_advance(self, req: "_gumbel_lib.PcbenvGumbelRequest", phases: int, value: Optional[torch.Tensor] = None,
+                            leaf_terminal: Optional[torch.Tensor] = None, cand_count: Optional[torch.Tensor] = None,
+                            cand_actions: Optional[torch.Tensor] = None, cand_prior: Optional[torch.Tensor] = None, seed: Optional[int] = None,
+                            step_index: int = 0) -> None:
+        """`gumbel_advance` under the full Gumbel rule (`pcbenv_gumbel_tree_advance`, include/pcbenv_gumbel_tree.h, one
+        kernel launch on the current stream, nothing else): the same request -- `gumbel_request(tree, ...)` -- phases,
+        tensors and key.  SELECT goes, at level 0 once the budget is spent and at every level below the root, to the child
+        with the largest pi'(c) - n_c / (1 + sum n), pi' = softmax(logit + sigma(completed q)) over the node's children; a
+        child without a visit is completed with v_mix, the node's value under its prior, at the root too -- in SELECT's
+        scores and in CHOOSE's policy target.  `req.c_puct` is not read."""
+        P = req.num_roots
+        if P == 0:  # torch gives empty tensors a null pointer
+            return
+        req.seed = (self.run_seed if seed is None else int(seed)) & (2 ** 64 - 1)
+        req.step_index, req.first_root = int(step_index) & (2 ** 64 - 1), self.first_env_index
+        self._puct_absorb(self._L.pcbenv_gumbel_tree_advance, req, P, phases, value, leaf_terminal, cand_count, cand_actions, cand_prior)
 
     def gumbel_leaves_request(self, tree: Dict[str, torch.Tensor], c_puct: float = 1.0, max_children: int = 16, c_visit: float = 50.0,
                               c_scale: float = 1.0, leaves: int = 1) -> "_gumbel_leaves_lib.PcbenvGumbelLeavesRequest":

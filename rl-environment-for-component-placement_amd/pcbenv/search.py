@@ -519,7 +519,7 @@ def _puct_arguments(root, iterations, max_children, max_steps, capacity, tree=No
 
 def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float = 1.0, max_children: int = 16, max_steps=None,
                 capacity=None, tree=None, leaves: int = 1, root_noise=None, noise_seed=None, noise_first_root=None,
-                noise_step_index=None, root_select=None, leaf_begin=None, leaf_end=None) -> PuctSearch:
+                noise_step_index=None, root_select=None, leaf_begin=None, leaf_end=None, level_select=None) -> PuctSearch:
     """Batched PUCT (the AlphaZero search) over all P = root.num_envs roots in lock-step, the tree in tensors, one
     `evaluate` per iteration and no host synchronisation inside the loop: the specification of pcbenv_puct_advance
     (include/pcbenv_search.h), in tensor code for any device.  Iteration m:
@@ -562,9 +562,15 @@ def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float 
     budget to keep, so it comes with two more hooks: leaf_begin(l, tree, alive) -> alive, called before the descent of leaf l
     with the roots that have had no repeat so far, returns those that take this leaf -- the others get no leaf from here on,
     as behind a repeat, and add no pending visit -- and leaf_end(l, alive), called behind the descent with the roots whose
-    leaf l is a leaf: a repeat is not among them, so what root_select proposed for it is not committed."""
+    leaf l is a leaf: a repeat is not among them, so what root_select proposed for it is not committed.
+    level_select: another rule for every level (`gumbel_search(full=True)`'s): level_select(d, tree, node, stopped, nxt) -> the
+    node every root goes to from `node` [P] at level d, given the tree as it stands (views, not to be modified), the roots
+    that stop there and the node PUCT would go to; at level 0 root_select is asked after it.  None: PUCT.  Such a rule reads
+    no pending visit: with leaves > 1 it raises ValueError."""
     P, C, M, T, N = _puct_arguments(root, iterations, max_children, max_steps, capacity, tree, leaves)
     L = int(leaves)
+    if level_select is not None and L != 1:
+        raise ValueError("level_select does not go with leaves > 1")
     if root_select is not None and L != 1 and (leaf_begin is None or leaf_end is None):
         raise ValueError("root_select with leaves > 1 needs leaf_begin and leaf_end")
     noise = _noise_arguments(root, root_noise, noise_seed, noise_first_root)
@@ -636,6 +642,8 @@ def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float 
                 u = c_puct * prior[rows[:, None], ch] * sqrt_rn(n_p)[:, None] / (1.0 + n_cf)
                 score = torch.where(mine, q + u, torch.full_like(q, float("-inf")))
                 nxt = fc + score.argmax(dim=1)                         # the first maximum: the lowest child
+                if level_select is not None:
+                    nxt = level_select(d, view(), node, stopped, nxt)
                 if root_select is not None and d == 0:
                     nxt = root_select(view(), stopped, nxt)
                 pending[rows, torch.where(stopped, trash, node)] += 1  # the node the descent leaves
@@ -1079,7 +1087,8 @@ def _gumbel_rule(max_children, c_visit, c_scale):
     return C, c_visit, c_scale
 
 
-def gumbel_scores(tree: dict, max_children: int, c_visit: float, c_scale: float, seed: int, step_index: int, first_root: int = 0) -> dict:
+def gumbel_scores(tree: dict, max_children: int, c_visit: float, c_scale: float, seed: int, step_index: int, first_root: int = 0,
+                  full: bool = False) -> dict:
     """The quantities of every root's children under the Gumbel rule: the specification of include/pcbenv_gumbel.h's
     "quantities of a root" in tensor code for any device, no host synchronisation, which csrc/pcb_gumbel.h and the kernel
     match bit for bit.  tree: a dict with `num_children`, `first_child`, `visits` (integers of any width), `prior`,
@@ -1090,7 +1099,9 @@ def gumbel_scores(tree: dict, max_children: int, c_visit: float, c_scale: float,
     `noise_uniform`'s; logit_c = ln(min(prior, 1)), a prior that is not above 2^-149 at that floor; qhat_c = the child's mean
     value -- the root's where the child has no visit, reward_lo where the root has none either -- normalised by
     [reward_lo, reward_hi], 0 while that is no range; sigma_c = ((c_visit + the most visits among the children) * c_scale)
-    * qhat_c.  ln is `ieee_ln`."""
+    * qhat_c.  ln is `ieee_ln`.
+    full=True: the quantities of include/pcbenv_gumbel_tree.h -- qhat, sigma, x and score are `gumbel_node_scores`' at slot 0,
+    where a child without a visit is completed with v_mix in the place of the root's mean; g and logit are the same."""
     C, c_visit, c_scale = _gumbel_rule(max_children, c_visit, c_scale)
     prior, vsum = tree["prior"], tree["value_sum"]
     dev = prior.device
@@ -1116,6 +1127,9 @@ def gumbel_scores(tree: dict, max_children: int, c_visit: float, c_scale: float,
     floor = torch.full_like(pr, GUMBEL_PRIOR_FLOOR)
     logit = ieee_ln(torch.where(pr > floor, torch.where(pr < 1.0, pr, torch.ones_like(pr)), floor))
     sigma = ((c_visit + most.to(torch.float64)) * c_scale)[:, None] * qhat
+    if full:
+        at_root = gumbel_node_scores(tree, torch.zeros(P, **i64), C, c_visit, c_scale)
+        qhat, sigma = at_root["qhat"], at_root["sigma"]
     u = noise_uniform(noise_base(seed, rows + int(first_root), step_index)[:, None], lane[None, :], GUMBEL_DRAW)
     g = -ieee_ln(-ieee_ln(u))
     na = tree.get("node_action")
@@ -1129,7 +1143,7 @@ def _best_of(score, within):
 
 
 def gumbel_select_root(tree: dict, sim_index: torch.Tensor, sim_visits: torch.Tensor, considered: torch.Tensor, max_children: int,
-                       c_visit: float, c_scale: float, seed: int, step_index: int, first_root: int = 0) -> dict:
+                       c_visit: float, c_scale: float, seed: int, step_index: int, first_root: int = 0, full: bool = False) -> dict:
     """Level 0 of pcbenv_gumbel_advance's SELECT: its specification in tensor code for any device, no host synchronisation.
     tree: `gumbel_scores`' and `terminal` [P, N]; sim_index [P], sim_visits [P, C] integers; considered int32 [Mc + 1, n]
     (`considered_visits`) on the tree's device.  Nothing is modified.  -> dict(scheduled bool [P]: the root makes a scheduled
@@ -1138,8 +1152,10 @@ def gumbel_select_root(tree: dict, sim_index: torch.Tensor, sim_visits: torch.Te
     the tree or a negative sim_index).  A root stops at slot 0 if it is terminal or has no children.  With t = sim_index,
     0 <= t < n: v = considered[min(Mc, k), t], S = the children with sim_visits == v, or all k if there is none, the child
     is the argmax of `gumbel_scores`' score over S, ties to the lowest; its counter and sim_index go up by one.  With t >= n
-    the root level is PUCT's and the counters stay."""
-    sc = gumbel_scores(tree, max_children, c_visit, c_scale, seed, step_index, first_root)
+    the root level is PUCT's and the counters stay.
+    full=True: level 0 of pcbenv_gumbel_tree_advance's SELECT -- `gumbel_scores(full=True)`; with t >= n the root level is
+    `gumbel_select_node`'s."""
+    sc = gumbel_scores(tree, max_children, c_visit, c_scale, seed, step_index, first_root, full)
     Mc, n = int(considered.shape[0]) - 1, int(considered.shape[1])
     k, ok, mine = sc["k"], sc["ok"], sc["mine"]
     dev = k.device
@@ -1159,7 +1175,7 @@ def gumbel_select_root(tree: dict, sim_index: torch.Tensor, sim_visits: torch.Te
 
 
 def gumbel_choose(tree: dict, sim_visits: torch.Tensor, max_children: int, c_visit: float, c_scale: float, seed: int, step_index: int,
-                  first_root: int = 0) -> dict:
+                  first_root: int = 0, full: bool = False) -> dict:
     """The move and the policy target of every root under the Gumbel rule: the specification of pcbenv_gumbel_advance's
     CHOOSE (include/pcbenv_gumbel.h) in tensor code for any device, no host synchronisation.  tree: `gumbel_scores`' and
     `node_action`; sim_visits [P, C] integers.  Nothing is modified.  -> dict(move_slot int32 [P], move_action int32 [P, 3],
@@ -1167,8 +1183,9 @@ def gumbel_choose(tree: dict, sim_visits: torch.Tensor, max_children: int, c_vis
     int32 [1]).  The move is the best score among the children with the most scheduled simulations, ties to the lowest.
     The target is pi = softmax(logit + sigma) over the k children: e_c = `ieee_exp`(x_c - max x), Z their sum in child
     order, pi_c = e_c / Z; child_policy = float32(pi), child_weights = int32(pi * 2^24 + 0.5), zero behind k.  A root
-    without children, or with a child range outside the tree (bit 1 of errors): move_slot -1 and zeros."""
-    sc = gumbel_scores(tree, max_children, c_visit, c_scale, seed, step_index, first_root)
+    without children, or with a child range outside the tree (bit 1 of errors): move_slot -1 and zeros.
+    full=True: pcbenv_gumbel_tree_advance's CHOOSE -- `gumbel_scores(full=True)`."""
+    sc = gumbel_scores(tree, max_children, c_visit, c_scale, seed, step_index, first_root, full)
     k, fc, ok, mine, x = sc["k"], sc["fc"], sc["ok"], sc["mine"], sc["x"]
     dev = k.device
     P, C = mine.shape
@@ -1188,6 +1205,86 @@ def gumbel_choose(tree: dict, sim_visits: torch.Tensor, max_children: int, c_vis
     return dict(move_slot=slot.to(torch.int32), move_action=action, child_weights=(pi * GUMBEL_WEIGHT_ONE + 0.5).to(torch.int32),
                 child_policy=pi.to(torch.float32), child_actions=sc["actions"],
                 root_value=tree["value_sum"][:, 0] / tree["visits"][:, 0].to(torch.float64), errors=errors)
+
+
+def gumbel_node_scores(tree: dict, node: torch.Tensor, max_children: int, c_visit: float, c_scale: float) -> dict:
+    """The quantities of one node per root under the full Gumbel rule: the specification of include/pcbenv_gumbel_tree.h's
+    "quantities of a node" in tensor code for any device, no host synchronisation, which csrc/pcb_gumbel_tree.h and the
+    kernel match bit for bit.  tree: `gumbel_scores`'; node [P]: a slot of every root, integers; not modified.  -> dict(k, fc
+    int64 [P]; ok bool [P]: the node has children in a healthy range; mine bool [P, C]: child c exists; n int64 [P, C]: its
+    visits; Nsum int64 [P]; vhat, vmix float64 [P]; logit, qhat, sigma, x, pi, t float64 [P, C], meaningless where mine is
+    False).  With ch the children of the node and n_c their visits: S = the sum of value_sum(ch), Wv and Qv the sums of pr_c
+    and pr_c * q_c over the children with a visit, pr_c the prior clamped to [2^-149, 1] and q_c = value_sum(ch) / n_c; vhat =
+    (value_sum(node) - S) / own with own = visits(node) - Nsum, the node's mean where own <= 0 and reward_lo where it has no
+    visit either; vmix = (vhat + (Nsum / Wv) * Qv) / (1 + Nsum), vhat while no child has a visit; qhat_c = q_c, or vmix for a
+    child without a visit, normalised by [reward_lo, reward_hi], 0 while that is no range; sigma_c = ((c_visit + the most
+    visits among the children) * c_scale) * qhat_c; pi = softmax(logit + sigma) as `gumbel_choose` forms it; t_c = pi_c - n_c /
+    (1 + Nsum).  Every sum is formed in child order from 0.0.  ln and exp are `ieee_ln` and `ieee_exp`."""
+    C, c_visit, c_scale = _gumbel_rule(max_children, c_visit, c_scale)
+    prior, vsum = tree["prior"], tree["value_sum"]
+    dev = prior.device
+    P, N = prior.shape
+    i64 = dict(dtype=torch.int64, device=dev)
+    visits = tree["visits"].to(torch.int64)
+    rows, lane = torch.arange(P, **i64), torch.arange(C, **i64)
+    a = node.to(**i64)
+    k, fc = tree["num_children"].to(torch.int64)[rows, a], tree["first_child"].to(torch.int64)[rows, a]
+    ok = (k >= 1) & (k <= C) & (fc >= 1) & (fc <= N - k)
+    mine = ok[:, None] & (lane[None, :] < k[:, None])
+    ch = torch.where(mine, fc[:, None] + lane[None, :], torch.zeros((), **i64))
+    n_c = visits[rows[:, None], ch]
+    seen = mine & (n_c > 0)
+    zero_i = torch.zeros((), **i64)
+    Nsum = torch.where(mine, n_c, zero_i).sum(dim=1)
+    most = torch.where(mine, n_c, torch.full((), -2 ** 31, **i64)).max(dim=1).values
+    pr = prior[rows[:, None], ch]
+    floor = torch.full_like(pr, GUMBEL_PRIOR_FLOOR)
+    pr = torch.where(pr > floor, torch.where(pr < 1.0, pr, torch.ones_like(pr)), floor)
+    vs = vsum[rows[:, None], ch]
+    q_c = vs / torch.where(seen, n_c, torch.ones((), **i64)).to(torch.float64)
+    wq = pr * q_c
+    S = torch.zeros(P, dtype=torch.float64, device=dev)
+    Wv, Qv = torch.zeros_like(S), torch.zeros_like(S)
+    for b in range(C):  # in this order: it is the contract
+        S = torch.where(mine[:, b], S + vs[:, b], S)
+        Wv = torch.where(seen[:, b], Wv + pr[:, b], Wv)
+        Qv = torch.where(seen[:, b], Qv + wq[:, b], Qv)
+    lo, hi = tree["reward_lo"], tree["reward_hi"]
+    n_a, sum_a = visits[rows, a], vsum[rows, a]
+    own = n_a - Nsum
+    Nf = Nsum.to(torch.float64)
+    vhat = torch.where(own > 0, (sum_a - S) / own.clamp(min=1).to(torch.float64), torch.where(n_a > 0, sum_a / n_a.clamp(min=1).to(torch.float64), lo))
+    mixes = (Nsum > 0) & (Wv > 0.0)
+    vmix = torch.where(mixes, (vhat + (Nf / torch.where(mixes, Wv, torch.ones_like(Wv))) * Qv) / (1.0 + Nf), vhat)
+    wide = hi > lo
+    span = torch.where(wide, hi - lo, torch.ones_like(hi))
+    lo_ = torch.where(wide, lo, torch.zeros_like(lo))
+    qhat = torch.where(wide[:, None], (torch.where(seen, q_c, vmix[:, None]) - lo_[:, None]) / span[:, None], torch.zeros_like(q_c))
+    logit = ieee_ln(pr)
+    sigma = ((c_visit + most.to(torch.float64)) * c_scale)[:, None] * qhat
+    x = logit + sigma
+    mx = torch.where(mine, x, torch.full_like(x, float("-inf"))).max(dim=1).values
+    e = torch.where(mine, ieee_exp(torch.where(mine, x - mx[:, None], torch.zeros_like(x))), torch.zeros_like(x))
+    Z = torch.zeros(P, dtype=torch.float64, device=dev)
+    for b in range(C):  # in this order: it is the contract
+        Z = torch.where(mine[:, b], Z + e[:, b], Z)
+    pi = torch.where(mine, e / torch.where(ok, Z, torch.ones_like(Z))[:, None], torch.zeros_like(e))
+    t = pi - n_c.to(torch.float64) / (1.0 + Nf)[:, None]
+    return dict(k=k, fc=fc, ok=ok, mine=mine, n=n_c, Nsum=Nsum, vhat=vhat, vmix=vmix, logit=logit, qhat=qhat, sigma=sigma, x=x, pi=pi, t=t)
+
+
+def gumbel_select_node(tree: dict, node: torch.Tensor, max_children: int, c_visit: float, c_scale: float) -> dict:
+    """The non-root rule of pcbenv_gumbel_tree_advance's SELECT at one node per root, in tensor code for any device, no host
+    synchronisation: -> dict(child int64 [P]: the argmax of `gumbel_node_scores`' t over the node's children, ties to the
+    lowest, 0 where the node has none in a healthy range; ok bool [P]: it has; errors int32 [1]: bit 1 (value 2) if a node
+    that does not stop -- it is not terminal and num_children != 0 -- has a child range outside the tree).  The rule is
+    deterministic and has no exploration constant; the visit counts it produces track pi."""
+    ns = gumbel_node_scores(tree, node, max_children, c_visit, c_scale)
+    rows = torch.arange(node.shape[0], dtype=torch.int64, device=ns["k"].device)
+    a = node.to(device=rows.device, dtype=torch.int64)
+    goes = ~((tree["terminal"][rows, a] != 0) | (ns["k"] == 0))
+    child = torch.where(ns["ok"], _best_of(ns["t"], ns["mine"]), torch.zeros_like(ns["k"]))
+    return dict(child=child, ok=ns["ok"], errors=((goes & ~ns["ok"]).any().to(torch.int32) * 2).reshape(1))
 
 
 def new_gumbel_tensors(P: int, C: int, max_considered: int, simulations: int, device) -> dict:
@@ -1238,7 +1335,7 @@ def _gumbel_launches(simulations, leaves, launches):
 
 def gumbel_search(root, simulations: int, step_index: int, evaluate, max_considered: int = 16, c_visit: float = 50.0, c_scale: float = 1.0,
                   c_puct: float = 1.0, max_children: int = 16, max_steps=None, capacity=None, tree=None, seed=None, first_root=None,
-                  gumbel_step_index=None, leaves: int = 1, launches=None) -> GumbelSearch:
+                  gumbel_step_index=None, leaves: int = 1, launches=None, full: bool = False) -> GumbelSearch:
     """The search of one move under the Gumbel rule, the whole of it as specification: `puct_search` with n + 1 =
     simulations + 1 evaluations whose level 0 is `gumbel_select_root`'s while the budget lasts, then `gumbel_choose`.  A fresh
     root spends evaluation 0 on its own expansion and then makes exactly n scheduled simulations; a kept root (tree=) makes n
@@ -1253,8 +1350,14 @@ def gumbel_search(root, simulations: int, step_index: int, evaluate, max_conside
     end of the budget at a leaf behind the first; with the budget spent, the first leaf is one PUCT descent.  A root that is
     terminal or has no children has one leaf, itself.  A root whose repeats left sim_index < n when the launches are over
     is chosen as it stands: `sim_index` tells the share of the budget spent.  capacity defaults to 1 + launches * L *
-    max_children."""
+    max_children.
+    full=True: the specification of pcbenv_gumbel_tree_advance (include/pcbenv_gumbel_tree.h) -- level 0 once the budget is
+    spent and every level below the root are `gumbel_select_node`'s, and `gumbel_select_root` and `gumbel_choose` complete a
+    child without a visit with v_mix (full=True); c_puct is not read.  With leaves > 1 or launches= it raises ValueError: the
+    rule reads no pending visit."""
     n, Mc, seed, first = _gumbel_arguments(root, simulations, max_considered, seed, first_root)
+    if full and (int(leaves) != 1 or launches is not None):
+        raise ValueError("full=True does not go with leaves > 1 or launches=")
     C, c_visit, c_scale = _gumbel_rule(max_children, c_visit, c_scale)
     key = int(step_index if gumbel_step_index is None else gumbel_step_index)
     P, dev = int(root.num_envs), getattr(root, "device", "cpu")
@@ -1263,12 +1366,16 @@ def gumbel_search(root, simulations: int, step_index: int, evaluate, max_conside
     L, E = _gumbel_launches(n, leaves, launches)
 
     def root_select(now, stopped, nxt):
-        sel = gumbel_select_root(now, state["sim_index"], state["sim_visits"], table, C, c_visit, c_scale, seed, key, first)
+        sel = gumbel_select_root(now, state["sim_index"], state["sim_visits"], table, C, c_visit, c_scale, seed, key, first, full)
         state.update(sim_index=sel["sim_index"], sim_visits=sel["sim_visits"])
         return torch.where(sel["scheduled"], now["first_child"][:, 0].to(torch.int64) + sel["child"], nxt)
+
+    def level_select(d, now, node, stopped, nxt):
+        rows = torch.arange(P, dtype=torch.int64, device=node.device)
+        return now["first_child"][rows, node].to(torch.int64) + gumbel_select_node(now, node, C, c_visit, c_scale)["child"]
     if L == 1 and launches is None:
         ps = puct_search(root, n + 1, step_index, evaluate, c_puct=c_puct, max_children=C, max_steps=max_steps, capacity=capacity, tree=tree,
-                         root_select=root_select)
+                         root_select=root_select, level_select=level_select if full else None)
     else:
         proposed = {}
 
@@ -1292,20 +1399,21 @@ def gumbel_search(root, simulations: int, step_index: int, evaluate, max_conside
                              sim_visits=torch.where(keep[:, None], sel["sim_visits"], state["sim_visits"]))
         ps = puct_search(root, E, step_index, evaluate, c_puct=c_puct, max_children=C, max_steps=max_steps, capacity=capacity, tree=tree, leaves=L,
                          root_select=propose, leaf_begin=leaf_begin, leaf_end=leaf_end)
-    ch = gumbel_choose(search_tree(ps), state["sim_visits"], C, c_visit, c_scale, seed, key, first)
+    ch = gumbel_choose(search_tree(ps), state["sim_visits"], C, c_visit, c_scale, seed, key, first, full)
     return GumbelSearch(ps, state["sim_index"], state["sim_visits"], ch["move_slot"], ch["move_action"], ch["child_weights"], ch["child_policy"],
                         ch["child_actions"], ch["root_value"])
 
 
-def _gumbel_iterations(root, greq, tree, n, T, evaluate, step_index, seed, key):
+def _gumbel_iterations(root, greq, tree, n, T, evaluate, step_index, seed, key, full=False):
     """The launches of one device Gumbel search on `tree`: BEGIN | SELECT, then n + 1 times `evaluate` followed by ABSORB |
-    SELECT, the last time by ABSORB alone."""
-    root.gumbel_advance(greq, GUMBEL_BEGIN | GUMBEL_SELECT, seed=seed, step_index=key)
+    SELECT, the last time by ABSORB alone -- pcbenv_gumbel_advance every one, pcbenv_gumbel_tree_advance with full."""
+    advance = root.gumbel_tree_advance if full else root.gumbel_advance
+    advance(greq, GUMBEL_BEGIN | GUMBEL_SELECT, seed=seed, step_index=key)
     for m in range(n + 1):
         ev = evaluate(tree["paths"], tree["path_len"], int(step_index) + m * T)
         over = ev.terminal.view(torch.uint8) if ev.terminal.dtype == torch.bool else ev.terminal
-        root.gumbel_advance(greq, GUMBEL_ABSORB | (GUMBEL_SELECT if m < n else 0), ev.value, over, ev.cand_count, ev.cand_actions, ev.cand_prior,
-                            seed=seed, step_index=key)
+        advance(greq, GUMBEL_ABSORB | (GUMBEL_SELECT if m < n else 0), ev.value, over, ev.cand_count, ev.cand_actions, ev.cand_prior,
+                seed=seed, step_index=key)
 
 
 def _gumbel_leaves_iterations(root, greq, tree, E, T, evaluate, step_index, seed, key):
@@ -1321,7 +1429,7 @@ def _gumbel_leaves_iterations(root, greq, tree, E, T, evaluate, step_index, seed
 
 def gumbel_search_device(root, simulations: int, step_index: int, evaluate, max_considered: int = 16, c_visit: float = 50.0, c_scale: float = 1.0,
                          c_puct: float = 1.0, max_children: int = 16, max_steps=None, capacity=None, tree=None, seed=None,
-                         gumbel_step_index=None, leaves: int = 1, launches=None) -> GumbelSearch:
+                         gumbel_step_index=None, leaves: int = 1, launches=None, full: bool = False) -> GumbelSearch:
     """`gumbel_search` with the tree kept by the device: `root.gumbel_advance` (pcbenv_gumbel_advance) is the one launch per
     evaluation, with no tensor operation between them: BEGIN | SELECT first -- a fresh tree gets `puct_advance(INIT)` before
     it -- then n + 1 times `evaluate(tree paths, path_len, step_index + m * max_steps)` followed by ABSORB | SELECT, the last
@@ -1333,9 +1441,14 @@ def gumbel_search_device(root, simulations: int, step_index: int, evaluate, max_
     (pcbenv_gumbel_advance_leaves, include/pcbenv_gumbel_leaves.h) as the one launch per evaluation: BEGIN | SELECT first -- a
     fresh tree gets `puct_advance_leaves(INIT)` before it, so that `pending` is zero -- then `launches` times `evaluate` and
     ABSORB | SELECT, the last time ABSORB alone, then CHOOSE; `evaluate` sees P * L rows, path_len -1 where there is no leaf.  A
-    tree that is kept is one of `new_puct_tree(leaves=L)`."""
+    tree that is kept is one of `new_puct_tree(leaves=L)`.
+    full=True: `gumbel_search(full=True)` with `root.gumbel_tree_advance` (pcbenv_gumbel_tree_advance,
+    include/pcbenv_gumbel_tree.h) as the one launch per evaluation and as CHOOSE, on the same tensors; not with leaves > 1 or
+    launches= (ValueError).  Without it the launches are what they are without this argument."""
     from . import _lib
     n, Mc, seed, _ = _gumbel_arguments(root, simulations, max_considered, seed, None)
+    if full and (int(leaves) != 1 or launches is not None):
+        raise ValueError("full=True does not go with leaves > 1 or launches=")
     L, E = _gumbel_launches(n, leaves, launches)
     key = int(step_index if gumbel_step_index is None else gumbel_step_index)
     kept = tree is not None
@@ -1356,8 +1469,8 @@ def gumbel_search_device(root, simulations: int, step_index: int, evaluate, max_
         tree.update(new_gumbel_tensors(P, C, Mc, n, root.device))
         root.puct_advance(root.puct_request(tree, c_puct, C), _lib.TREE_INIT)
     greq = root.gumbel_request(tree, c_puct, C, c_visit, c_scale)
-    _gumbel_iterations(root, greq, tree, n, T, evaluate, step_index, seed, key)
-    root.gumbel_advance(greq, GUMBEL_CHOOSE, seed=seed, step_index=key)
+    _gumbel_iterations(root, greq, tree, n, T, evaluate, step_index, seed, key, full)
+    (root.gumbel_tree_advance if full else root.gumbel_advance)(greq, GUMBEL_CHOOSE, seed=seed, step_index=key)
     return GumbelSearch(puct_result(tree, C), tree["sim_index"], tree["sim_visits"], tree["move_slot"], tree["move_action"], tree["child_weights"],
                         tree["child_policy"], tree["child_actions"], tree["root_value"])
 
@@ -1378,7 +1491,7 @@ class SelfPlay:
 
 def puct_selfplay(root, evaluate, moves: int, iterations: int, step_index: int = 0, c_puct: float = 1.0, max_children: int = 16,
                   max_steps=None, capacity=None, mode: int = MOVE_GREEDY, seed=None, on_move=None, leaves: int = 1, root_noise=None,
-                  noise_seed=None, gumbel=None, gumbel_seed=None) -> SelfPlay:
+                  noise_seed=None, gumbel=None, gumbel_seed=None, gumbel_full: bool = False) -> SelfPlay:
     """Plays `moves` moves of every root environment with a PUCT search whose tree stays on the device and is kept from
     move to move.  Per move: `iterations` of search on the kept tree (`evaluate` and one pcbenv_puct_advance launch each,
     as `puct_search_device(tree=)`); `root.puct_move(MOVE_CHOOSE)` -- the visit distribution of the root and the move,
@@ -1410,9 +1523,13 @@ def puct_selfplay(root, evaluate, moves: int, iterations: int, step_index: int =
     root_noise it raises ValueError.  With leaves = L > 1 every move is `gumbel_search_device(leaves=L)`: ceil(n / L) + 1
     evaluations of P * L rows and pcbenv_gumbel_advance_leaves launches, the default capacity 1 + 2 * (ceil(n / L) + 1) * L *
     max_children; `pending` is zero after the last ABSORB, so REROOT takes the tree as it is.
+    gumbel_full=True: every move is `gumbel_search_device(full=True)`, the launches pcbenv_gumbel_tree_advance's
+    (include/pcbenv_gumbel_tree.h) on the same tensors; it needs gumbel= and leaves = 1 (ValueError otherwise).
     `evaluate` must be callable: ValueError otherwise, before anything is allocated."""
     from . import _lib, _move_lib
     L = int(leaves)
+    if gumbel_full and (gumbel is None or L != 1):
+        raise ValueError("gumbel_full=True needs gumbel= and leaves = 1")
     if not callable(evaluate):
         raise ValueError("puct_selfplay needs an evaluate(paths, path_len, step_index0) to call")
     if gumbel is not None and root_noise is not None:
@@ -1447,8 +1564,8 @@ def puct_selfplay(root, evaluate, moves: int, iterations: int, step_index: int =
             _gumbel_leaves_iterations(root, greq, tree, M, T, evaluate, int(step_index) + j * M * T, gseed, int(step_index) + j)
             root.gumbel_advance_leaves(greq, GUMBEL_CHOOSE, seed=gseed, step_index=int(step_index) + j)
         elif gumbel is not None:
-            _gumbel_iterations(root, greq, tree, n, T, evaluate, int(step_index) + j * M * T, gseed, int(step_index) + j)
-            root.gumbel_advance(greq, GUMBEL_CHOOSE, seed=gseed, step_index=int(step_index) + j)
+            _gumbel_iterations(root, greq, tree, n, T, evaluate, int(step_index) + j * M * T, gseed, int(step_index) + j, gumbel_full)
+            (root.gumbel_tree_advance if gumbel_full else root.gumbel_advance)(greq, GUMBEL_CHOOSE, seed=gseed, step_index=int(step_index) + j)
         else:
             _puct_iterations(root, req, tree, M, T, evaluate, int(step_index) + j * M * T, _lib.TREE_SELECT if j else _lib.TREE_INIT | _lib.TREE_SELECT, L,
                              None if noise is None else (nreq, noise[0], noise[1], noise[2], int(step_index) + j))
