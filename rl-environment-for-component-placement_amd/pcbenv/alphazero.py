@@ -53,6 +53,9 @@ class AlphaZeroConfig:
     # the full Gumbel rule (puct_selfplay's gumbel_full, pcbenv_gumbel_tree_advance): below the root the search goes to the
     # argmax of pi' - n / (1 + sum n) and a child without a visit is completed with v_mix; needs gumbel_considered and leaves = 1
     gumbel_full: bool = False
+    # "gumbel": the full Gumbel rule with any leaves (puct_selfplay's gumbel_node_rule): gumbel_full's launches with leaves = 1,
+    # pcbenv_gumbel_tree_advance_leaves' with more, where a pending visit counts as a visit of the child; needs gumbel_considered
+    gumbel_node_rule: str = "puct"
 
 
 def value_targets(reward: torch.Tensor, done: torch.Tensor):
@@ -119,7 +122,7 @@ class AlphaZeroTrainer:
                            on_move=lambda j, tree: keep_root(j + 1) if j + 1 < M else None, leaves=self.cfg.leaves,
                            root_noise=None if self.cfg.noise_alpha is None else (self.cfg.noise_alpha, self.cfg.noise_eps),
                            gumbel=None if self.cfg.gumbel_considered is None else (self.cfg.gumbel_considered, self.cfg.gumbel_c_visit, self.cfg.gumbel_c_scale),
-                           gumbel_full=self.cfg.gumbel_full)
+                           gumbel_full=self.cfg.gumbel_full, gumbel_node_rule=self.cfg.gumbel_node_rule)
         from .batched_env import default_max_steps
         evaluations = self.cfg.iterations + (self.cfg.gumbel_considered is not None)
         if self.cfg.gumbel_considered is not None and self.cfg.leaves != 1:

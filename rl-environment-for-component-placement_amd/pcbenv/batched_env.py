@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _gumbel_leaves_lib, _gumbel_lib, _gumbel_tree_lib, _leaves_lib, _lib, _move_lib, _noise_lib, _priors_lib, _search_lib, _train_lib
+from . import _gumbel_leaves_lib, _gumbel_lib, _gumbel_tree_leaves_lib, _gumbel_tree_lib, _leaves_lib, _lib, _move_lib, _noise_lib, _priors_lib, _search_lib, _train_lib
 from .config import EnvConfig, KIND_PIN, KIND_RECT, KIND_SPATIAL, KIND_SQUARE
 from .instances import Instance, InstanceStream, env_seed, pack_instances
 
@@ -169,7 +169,7 @@ class BatchedPlacementEnv:
             raise RuntimeError("BatchedPlacementEnv needs a GPU device (there is no CPU fallback)")
         # the device the handle lives on, index included: one named without an index is the current device, now and for good
         self.device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
-        self._L = _gumbel_tree_lib.bind(_gumbel_leaves_lib.bind(_gumbel_lib.bind(_noise_lib.bind(_leaves_lib.bind(_train_lib.bind(_move_lib.bind(_priors_lib.bind(_search_lib.bind(_lib.load())))))))))
+        self._L = _gumbel_tree_leaves_lib.bind(_gumbel_tree_lib.bind(_gumbel_leaves_lib.bind(_gumbel_lib.bind(_noise_lib.bind(_leaves_lib.bind(_train_lib.bind(_move_lib.bind(_priors_lib.bind(_search_lib.bind(_lib.load()))))))))))
         # per-environment spaces (the reference constructors' declarations); every tensor adds a leading batch dim
         from .spaces import action_space_for, observation_space_for
         self.action_space = self.single_action_space = action_space_for(cfg)
@@ -1110,6 +1110,25 @@ class BatchedPlacementEnv:
         req.seed = (self.run_seed if seed is None else int(seed)) & (2 ** 64 - 1)
         req.step_index, req.first_root = int(step_index) & (2 ** 64 - 1), self.first_env_index
         self._puct_absorb(self._L.pcbenv_gumbel_advance_leaves, req, P * req.num_leaves, phases, value, leaf_terminal, cand_count, cand_actions,
+                          cand_prior)
+
+    def gumbel_tree_advance_leaves(self, req: "_gumbel_leaves_lib.PcbenvGumbelLeavesRequest", phases: int, value: Optional[torch.Tensor] = None,
+                                   leaf_terminal: Optional[torch.Tensor] = None, cand_count: Optional[torch.Tensor] = None,
+                                   cand_actions: Optional[torch.Tensor] = None, cand_prior: Optional[torch.Tensor] = None, seed: Optional[int] = None,
+                                   step_index: int = 0) -> None:
+        """`gumbel_advance_leaves` under the full Gumbel rule (`pcbenv_gumbel_tree_advance_leaves`,
+        include/pcbenv_gumbel_tree_leaves.h, one kernel launch on the current stream, nothing else): the same request --
+        `gumbel_leaves_request(tree, ...)` -- phases, tensors and key.  The scores of the root's children and CHOOSE's policy
+        target are `gumbel_tree_advance`'s (v_mix completes a child without a visit); below the root, and at the root once
+        the budget is spent, every descent goes to the child with the largest pi'(c) - (n_c + pending_c) / (1 + sum (n +
+        pending)): a pending visit counts as a visit and enters nothing else, so pi' of a node is the same for all L leaves
+        of a launch.  Repeats, the end of the budget and ABSORB are `gumbel_advance_leaves`'.  `req.c_puct` is not read."""
+        P = req.num_roots
+        if P == 0:  # torch gives empty tensors a null pointer
+            return
+        req.seed = (self.run_seed if seed is None else int(seed)) & (2 ** 64 - 1)
+        req.step_index, req.first_root = int(step_index) & (2 ** 64 - 1), self.first_env_index
+        self._puct_absorb(self._L.pcbenv_gumbel_tree_advance_leaves, req, P * req.num_leaves, phases, value, leaf_terminal, cand_count, cand_actions,
                           cand_prior)
 
     def top_priors(self, logits: torch.Tensor, K: int, mask_bits: Optional[torch.Tensor] = None,

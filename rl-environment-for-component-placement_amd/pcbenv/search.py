@@ -519,7 +519,7 @@ def _puct_arguments(root, iterations, max_children, max_steps, capacity, tree=No
 
 def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float = 1.0, max_children: int = 16, max_steps=None,
                 capacity=None, tree=None, leaves: int = 1, root_noise=None, noise_seed=None, noise_first_root=None,
-                noise_step_index=None, root_select=None, leaf_begin=None, leaf_end=None, level_select=None) -> PuctSearch:
+                noise_step_index=None, root_select=None, leaf_begin=None, leaf_end=None, level_select=None, pending_select=None) -> PuctSearch:
     """Batched PUCT (the AlphaZero search) over all P = root.num_envs roots in lock-step, the tree in tensors, one
     `evaluate` per iteration and no host synchronisation inside the loop: the specification of pcbenv_puct_advance
     (include/pcbenv_search.h), in tensor code for any device.  Iteration m:
@@ -566,7 +566,10 @@ def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float 
     level_select: another rule for every level (`gumbel_search(full=True)`'s): level_select(d, tree, node, stopped, nxt) -> the
     node every root goes to from `node` [P] at level d, given the tree as it stands (views, not to be modified), the roots
     that stop there and the node PUCT would go to; at level 0 root_select is asked after it.  None: PUCT.  Such a rule reads
-    no pending visit: with leaves > 1 it raises ValueError."""
+    no pending visit: with leaves > 1 it raises ValueError.
+    pending_select: `level_select` for a rule that counts pending visits (`gumbel_search(node_rule="gumbel", leaves=L)`'s):
+    pending_select(d, tree, node, stopped, nxt), where `tree` also has `pending` [P, N] as the leaves before this one left it.
+    It goes with any leaves; at level 0 root_select is asked after it.  None: PUCT."""
     P, C, M, T, N = _puct_arguments(root, iterations, max_children, max_steps, capacity, tree, leaves)
     L = int(leaves)
     if level_select is not None and L != 1:
@@ -644,6 +647,8 @@ def puct_search(root, iterations: int, step_index: int, evaluate, c_puct: float 
                 nxt = fc + score.argmax(dim=1)                         # the first maximum: the lowest child
                 if level_select is not None:
                     nxt = level_select(d, view(), node, stopped, nxt)
+                if pending_select is not None:
+                    nxt = pending_select(d, dict(view(), pending=pending[:, :N]), node, stopped, nxt)
                 if root_select is not None and d == 0:
                     nxt = root_select(view(), stopped, nxt)
                 pending[rows, torch.where(stopped, trash, node)] += 1  # the node the descent leaves
@@ -1207,7 +1212,7 @@ def gumbel_choose(tree: dict, sim_visits: torch.Tensor, max_children: int, c_vis
                 root_value=tree["value_sum"][:, 0] / tree["visits"][:, 0].to(torch.float64), errors=errors)
 
 
-def gumbel_node_scores(tree: dict, node: torch.Tensor, max_children: int, c_visit: float, c_scale: float) -> dict:
+def gumbel_node_scores(tree: dict, node: torch.Tensor, max_children: int, c_visit: float, c_scale: float, pending=None) -> dict:
     """The quantities of one node per root under the full Gumbel rule: the specification of include/pcbenv_gumbel_tree.h's
     "quantities of a node" in tensor code for any device, no host synchronisation, which csrc/pcb_gumbel_tree.h and the
     kernel match bit for bit.  tree: `gumbel_scores`'; node [P]: a slot of every root, integers; not modified.  -> dict(k, fc
@@ -1219,7 +1224,11 @@ def gumbel_node_scores(tree: dict, node: torch.Tensor, max_children: int, c_visi
     visit either; vmix = (vhat + (Nsum / Wv) * Qv) / (1 + Nsum), vhat while no child has a visit; qhat_c = q_c, or vmix for a
     child without a visit, normalised by [reward_lo, reward_hi], 0 while that is no range; sigma_c = ((c_visit + the most
     visits among the children) * c_scale) * qhat_c; pi = softmax(logit + sigma) as `gumbel_choose` forms it; t_c = pi_c - n_c /
-    (1 + Nsum).  Every sum is formed in child order from 0.0.  ln and exp are `ieee_ln` and `ieee_exp`."""
+    (1 + Nsum).  Every sum is formed in child order from 0.0.  ln and exp are `ieee_ln` and `ieee_exp`.
+    pending [P, N] integers (not modified): the rule of include/pcbenv_gumbel_tree_leaves.h -- a pending visit counts as a visit
+    in t and enters nothing else: with m_c = n_c + pending(ch) and Msum their sum, t_c = pi_c - m_c / (1 + Msum), a NaN (Msum ==
+    -1: damaged counts only) counting as -inf; the dict also has m int64 [P, C] and Msum int64 [P].  pi and everything before
+    it read no pending visit.  None: what the function returns without the argument."""
     C, c_visit, c_scale = _gumbel_rule(max_children, c_visit, c_scale)
     prior, vsum = tree["prior"], tree["value_sum"]
     dev = prior.device
@@ -1269,17 +1278,26 @@ def gumbel_node_scores(tree: dict, node: torch.Tensor, max_children: int, c_visi
     for b in range(C):  # in this order: it is the contract
         Z = torch.where(mine[:, b], Z + e[:, b], Z)
     pi = torch.where(mine, e / torch.where(ok, Z, torch.ones_like(Z))[:, None], torch.zeros_like(e))
-    t = pi - n_c.to(torch.float64) / (1.0 + Nf)[:, None]
-    return dict(k=k, fc=fc, ok=ok, mine=mine, n=n_c, Nsum=Nsum, vhat=vhat, vmix=vmix, logit=logit, qhat=qhat, sigma=sigma, x=x, pi=pi, t=t)
+    out = dict(k=k, fc=fc, ok=ok, mine=mine, n=n_c, Nsum=Nsum, vhat=vhat, vmix=vmix, logit=logit, qhat=qhat, sigma=sigma, x=x, pi=pi)
+    if pending is None:
+        out["t"] = pi - n_c.to(torch.float64) / (1.0 + Nf)[:, None]
+        return out
+    m_c = n_c + pending.to(**i64)[rows[:, None], ch]
+    Msum = torch.where(mine, m_c, zero_i).sum(dim=1)
+    t = pi - m_c.to(torch.float64) / (1.0 + Msum.to(torch.float64))[:, None]
+    out.update(m=m_c, Msum=Msum, t=torch.where(t == t, t, torch.full_like(t, float("-inf"))))
+    return out
 
 
-def gumbel_select_node(tree: dict, node: torch.Tensor, max_children: int, c_visit: float, c_scale: float) -> dict:
+def gumbel_select_node(tree: dict, node: torch.Tensor, max_children: int, c_visit: float, c_scale: float, pending=None) -> dict:
     """The non-root rule of pcbenv_gumbel_tree_advance's SELECT at one node per root, in tensor code for any device, no host
     synchronisation: -> dict(child int64 [P]: the argmax of `gumbel_node_scores`' t over the node's children, ties to the
     lowest, 0 where the node has none in a healthy range; ok bool [P]: it has; errors int32 [1]: bit 1 (value 2) if a node
     that does not stop -- it is not terminal and num_children != 0 -- has a child range outside the tree).  The rule is
-    deterministic and has no exploration constant; the visit counts it produces track pi."""
-    ns = gumbel_node_scores(tree, node, max_children, c_visit, c_scale)
+    deterministic and has no exploration constant; the visit counts it produces track pi.
+    pending [P, N]: pcbenv_gumbel_tree_advance_leaves' rule -- `gumbel_node_scores(pending=)`'s t, in which a pending visit
+    counts as a visit, so that the descents of one launch track pi as visits do.  None: as without the argument."""
+    ns = gumbel_node_scores(tree, node, max_children, c_visit, c_scale, pending)
     rows = torch.arange(node.shape[0], dtype=torch.int64, device=ns["k"].device)
     a = node.to(device=rows.device, dtype=torch.int64)
     goes = ~((tree["terminal"][rows, a] != 0) | (ns["k"] == 0))
@@ -1333,9 +1351,19 @@ def _gumbel_launches(simulations, leaves, launches):
     return L, E
 
 
+def _gumbel_node_rule(node_rule, full, leaves, launches):
+    """True if every level below the root is the Gumbel node rule: full=True, which does not go with leaves > 1 or launches=,
+    or node_rule="gumbel", which goes with any."""
+    if node_rule not in ("puct", "gumbel"):
+        raise ValueError('node_rule must be "puct" or "gumbel"')
+    if full and (int(leaves) != 1 or launches is not None):
+        raise ValueError("full=True does not go with leaves > 1 or launches=")
+    return bool(full) or node_rule == "gumbel"
+
+
 def gumbel_search(root, simulations: int, step_index: int, evaluate, max_considered: int = 16, c_visit: float = 50.0, c_scale: float = 1.0,
                   c_puct: float = 1.0, max_children: int = 16, max_steps=None, capacity=None, tree=None, seed=None, first_root=None,
-                  gumbel_step_index=None, leaves: int = 1, launches=None, full: bool = False) -> GumbelSearch:
+                  gumbel_step_index=None, leaves: int = 1, launches=None, full: bool = False, node_rule: str = "puct") -> GumbelSearch:
     """The search of one move under the Gumbel rule, the whole of it as specification: `puct_search` with n + 1 =
     simulations + 1 evaluations whose level 0 is `gumbel_select_root`'s while the budget lasts, then `gumbel_choose`.  A fresh
     root spends evaluation 0 on its own expansion and then makes exactly n scheduled simulations; a kept root (tree=) makes n
@@ -1354,10 +1382,14 @@ def gumbel_search(root, simulations: int, step_index: int, evaluate, max_conside
     full=True: the specification of pcbenv_gumbel_tree_advance (include/pcbenv_gumbel_tree.h) -- level 0 once the budget is
     spent and every level below the root are `gumbel_select_node`'s, and `gumbel_select_root` and `gumbel_choose` complete a
     child without a visit with v_mix (full=True); c_puct is not read.  With leaves > 1 or launches= it raises ValueError: the
-    rule reads no pending visit."""
+    rule reads no pending visit.
+    node_rule="gumbel": the full rule with any leaves and launches.  With leaves = 1 and no launches= it is full=True, bit for
+    bit.  Otherwise it is the specification of pcbenv_gumbel_tree_advance_leaves (include/pcbenv_gumbel_tree_leaves.h): the
+    leaf loop above with `gumbel_select_root(full=True)` at the root and, at every level below it and at level 0 once the
+    budget is spent, `gumbel_select_node(pending=)` -- a pending visit counts as a visit of the child and enters nothing else;
+    `gumbel_choose(full=True)`; c_puct is not read.  "puct", the default: the search is what it is without this argument."""
     n, Mc, seed, first = _gumbel_arguments(root, simulations, max_considered, seed, first_root)
-    if full and (int(leaves) != 1 or launches is not None):
-        raise ValueError("full=True does not go with leaves > 1 or launches=")
+    full = _gumbel_node_rule(node_rule, full, leaves, launches)
     C, c_visit, c_scale = _gumbel_rule(max_children, c_visit, c_scale)
     key = int(step_index if gumbel_step_index is None else gumbel_step_index)
     P, dev = int(root.num_envs), getattr(root, "device", "cpu")
@@ -1388,7 +1420,7 @@ def gumbel_search(root, simulations: int, step_index: int, evaluate, max_conside
             return alive & ~(now["terminal"][:, 0] != 0) & ok & (t >= 0) & (t < n)
 
         def propose(now, stopped, nxt):  # the counters move when the leaf has turned out to be one
-            sel = proposed["sel"] = gumbel_select_root(now, state["sim_index"], state["sim_visits"], table, C, c_visit, c_scale, seed, key, first)
+            sel = proposed["sel"] = gumbel_select_root(now, state["sim_index"], state["sim_visits"], table, C, c_visit, c_scale, seed, key, first, full)
             return torch.where(sel["scheduled"], now["first_child"][:, 0].to(torch.int64) + sel["child"], nxt)
 
         def leaf_end(l, alive):
@@ -1397,8 +1429,12 @@ def gumbel_search(root, simulations: int, step_index: int, evaluate, max_conside
                 keep = alive & sel["scheduled"]
                 state.update(sim_index=torch.where(keep, sel["sim_index"], state["sim_index"]),
                              sim_visits=torch.where(keep[:, None], sel["sim_visits"], state["sim_visits"]))
+
+        def pending_select(d, now, node, stopped, nxt):
+            rows = torch.arange(P, dtype=torch.int64, device=node.device)
+            return now["first_child"][rows, node].to(torch.int64) + gumbel_select_node(now, node, C, c_visit, c_scale, now["pending"])["child"]
         ps = puct_search(root, E, step_index, evaluate, c_puct=c_puct, max_children=C, max_steps=max_steps, capacity=capacity, tree=tree, leaves=L,
-                         root_select=propose, leaf_begin=leaf_begin, leaf_end=leaf_end)
+                         root_select=propose, leaf_begin=leaf_begin, leaf_end=leaf_end, pending_select=pending_select if full else None)
     ch = gumbel_choose(search_tree(ps), state["sim_visits"], C, c_visit, c_scale, seed, key, first, full)
     return GumbelSearch(ps, state["sim_index"], state["sim_visits"], ch["move_slot"], ch["move_action"], ch["child_weights"], ch["child_policy"],
                         ch["child_actions"], ch["root_value"])
@@ -1416,20 +1452,22 @@ def _gumbel_iterations(root, greq, tree, n, T, evaluate, step_index, seed, key, 
                 seed=seed, step_index=key)
 
 
-def _gumbel_leaves_iterations(root, greq, tree, E, T, evaluate, step_index, seed, key):
+def _gumbel_leaves_iterations(root, greq, tree, E, T, evaluate, step_index, seed, key, full=False):
     """The launches of one device Gumbel search with leaves on `tree`: BEGIN | SELECT, then E times `evaluate` followed by
-    ABSORB | SELECT, the last time by ABSORB alone -- pcbenv_gumbel_advance_leaves every one."""
-    root.gumbel_advance_leaves(greq, GUMBEL_BEGIN | GUMBEL_SELECT, seed=seed, step_index=key)
+    ABSORB | SELECT, the last time by ABSORB alone -- pcbenv_gumbel_advance_leaves every one, pcbenv_gumbel_tree_advance_leaves
+    with full."""
+    advance = root.gumbel_tree_advance_leaves if full else root.gumbel_advance_leaves
+    advance(greq, GUMBEL_BEGIN | GUMBEL_SELECT, seed=seed, step_index=key)
     for m in range(E):
         ev = evaluate(tree["paths"], tree["path_len"], int(step_index) + m * T)
         over = ev.terminal.view(torch.uint8) if ev.terminal.dtype == torch.bool else ev.terminal
-        root.gumbel_advance_leaves(greq, GUMBEL_ABSORB | (GUMBEL_SELECT if m + 1 < E else 0), ev.value, over, ev.cand_count, ev.cand_actions,
-                                   ev.cand_prior, seed=seed, step_index=key)
+        advance(greq, GUMBEL_ABSORB | (GUMBEL_SELECT if m + 1 < E else 0), ev.value, over, ev.cand_count, ev.cand_actions, ev.cand_prior, seed=seed,
+                step_index=key)
 
 
 def gumbel_search_device(root, simulations: int, step_index: int, evaluate, max_considered: int = 16, c_visit: float = 50.0, c_scale: float = 1.0,
                          c_puct: float = 1.0, max_children: int = 16, max_steps=None, capacity=None, tree=None, seed=None,
-                         gumbel_step_index=None, leaves: int = 1, launches=None, full: bool = False) -> GumbelSearch:
+                         gumbel_step_index=None, leaves: int = 1, launches=None, full: bool = False, node_rule: str = "puct") -> GumbelSearch:
     """`gumbel_search` with the tree kept by the device: `root.gumbel_advance` (pcbenv_gumbel_advance) is the one launch per
     evaluation, with no tensor operation between them: BEGIN | SELECT first -- a fresh tree gets `puct_advance(INIT)` before
     it -- then n + 1 times `evaluate(tree paths, path_len, step_index + m * max_steps)` followed by ABSORB | SELECT, the last
@@ -1444,11 +1482,14 @@ def gumbel_search_device(root, simulations: int, step_index: int, evaluate, max_
     tree that is kept is one of `new_puct_tree(leaves=L)`.
     full=True: `gumbel_search(full=True)` with `root.gumbel_tree_advance` (pcbenv_gumbel_tree_advance,
     include/pcbenv_gumbel_tree.h) as the one launch per evaluation and as CHOOSE, on the same tensors; not with leaves > 1 or
-    launches= (ValueError).  Without it the launches are what they are without this argument."""
+    launches= (ValueError).  Without it the launches are what they are without this argument.
+    node_rule="gumbel": `gumbel_search(node_rule="gumbel")`.  With leaves = 1 and no launches= the launches are full=True's,
+    pcbenv_gumbel_tree_advance; otherwise every launch, CHOOSE included, is `root.gumbel_tree_advance_leaves`
+    (pcbenv_gumbel_tree_advance_leaves, include/pcbenv_gumbel_tree_leaves.h) on the tensors of leaves = L.  Without it the
+    launches are what they are without this argument."""
     from . import _lib
     n, Mc, seed, _ = _gumbel_arguments(root, simulations, max_considered, seed, None)
-    if full and (int(leaves) != 1 or launches is not None):
-        raise ValueError("full=True does not go with leaves > 1 or launches=")
+    full = _gumbel_node_rule(node_rule, full, leaves, launches)
     L, E = _gumbel_launches(n, leaves, launches)
     key = int(step_index if gumbel_step_index is None else gumbel_step_index)
     kept = tree is not None
@@ -1459,8 +1500,8 @@ def gumbel_search_device(root, simulations: int, step_index: int, evaluate, max_
             tree.update(new_gumbel_tensors(P, C, Mc, n, root.device))
             root.puct_advance_leaves(root.puct_leaves_request(tree, c_puct, C, L), _lib.TREE_INIT)
         greq = root.gumbel_leaves_request(tree, c_puct, C, c_visit, c_scale, L)
-        _gumbel_leaves_iterations(root, greq, tree, E, T, evaluate, step_index, seed, key)
-        root.gumbel_advance_leaves(greq, GUMBEL_CHOOSE, seed=seed, step_index=key)
+        _gumbel_leaves_iterations(root, greq, tree, E, T, evaluate, step_index, seed, key, full)
+        (root.gumbel_tree_advance_leaves if full else root.gumbel_advance_leaves)(greq, GUMBEL_CHOOSE, seed=seed, step_index=key)
         return GumbelSearch(puct_result(tree, C), tree["sim_index"], tree["sim_visits"], tree["move_slot"], tree["move_action"], tree["child_weights"],
                             tree["child_policy"], tree["child_actions"], tree["root_value"])
     P, C, M, T, N = _puct_arguments(root, n + 1, max_children, max_steps, capacity, tree)
@@ -1491,7 +1532,7 @@ class SelfPlay:
 
 def puct_selfplay(root, evaluate, moves: int, iterations: int, step_index: int = 0, c_puct: float = 1.0, max_children: int = 16,
                   max_steps=None, capacity=None, mode: int = MOVE_GREEDY, seed=None, on_move=None, leaves: int = 1, root_noise=None,
-                  noise_seed=None, gumbel=None, gumbel_seed=None, gumbel_full: bool = False) -> SelfPlay:
+                  noise_seed=None, gumbel=None, gumbel_seed=None, gumbel_full: bool = False, gumbel_node_rule: str = "puct") -> SelfPlay:
     """Plays `moves` moves of every root environment with a PUCT search whose tree stays on the device and is kept from
     move to move.  Per move: `iterations` of search on the kept tree (`evaluate` and one pcbenv_puct_advance launch each,
     as `puct_search_device(tree=)`); `root.puct_move(MOVE_CHOOSE)` -- the visit distribution of the root and the move,
@@ -1525,11 +1566,17 @@ def puct_selfplay(root, evaluate, moves: int, iterations: int, step_index: int =
     max_children; `pending` is zero after the last ABSORB, so REROOT takes the tree as it is.
     gumbel_full=True: every move is `gumbel_search_device(full=True)`, the launches pcbenv_gumbel_tree_advance's
     (include/pcbenv_gumbel_tree.h) on the same tensors; it needs gumbel= and leaves = 1 (ValueError otherwise).
+    gumbel_node_rule="gumbel": every move is `gumbel_search_device(node_rule="gumbel", leaves=L)` -- gumbel_full=True's launches
+    with leaves = 1, pcbenv_gumbel_tree_advance_leaves' (include/pcbenv_gumbel_tree_leaves.h) with more; it needs gumbel=
+    (ValueError otherwise).  "puct", the default: the game is what it is without this argument.
     `evaluate` must be callable: ValueError otherwise, before anything is allocated."""
     from . import _lib, _move_lib
     L = int(leaves)
     if gumbel_full and (gumbel is None or L != 1):
         raise ValueError("gumbel_full=True needs gumbel= and leaves = 1")
+    if gumbel_node_rule not in ("puct", "gumbel") or (gumbel_node_rule == "gumbel" and gumbel is None):
+        raise ValueError('gumbel_node_rule must be "puct" or "gumbel", and "gumbel" needs gumbel=')
+    gumbel_full = bool(gumbel_full) or gumbel_node_rule == "gumbel"
     if not callable(evaluate):
         raise ValueError("puct_selfplay needs an evaluate(paths, path_len, step_index0) to call")
     if gumbel is not None and root_noise is not None:
@@ -1561,8 +1608,8 @@ def puct_selfplay(root, evaluate, moves: int, iterations: int, step_index: int =
                    torch.empty((J, P), dtype=torch.uint8, device=dev), torch.empty((J, P), **i32), tree["errors_dev"][0], tree)
     for j in range(J):
         if gumbel is not None and L != 1:
-            _gumbel_leaves_iterations(root, greq, tree, M, T, evaluate, int(step_index) + j * M * T, gseed, int(step_index) + j)
-            root.gumbel_advance_leaves(greq, GUMBEL_CHOOSE, seed=gseed, step_index=int(step_index) + j)
+            _gumbel_leaves_iterations(root, greq, tree, M, T, evaluate, int(step_index) + j * M * T, gseed, int(step_index) + j, gumbel_full)
+            (root.gumbel_tree_advance_leaves if gumbel_full else root.gumbel_advance_leaves)(greq, GUMBEL_CHOOSE, seed=gseed, step_index=int(step_index) + j)
         elif gumbel is not None:
             _gumbel_iterations(root, greq, tree, n, T, evaluate, int(step_index) + j * M * T, gseed, int(step_index) + j, gumbel_full)
             (root.gumbel_tree_advance if gumbel_full else root.gumbel_advance)(greq, GUMBEL_CHOOSE, seed=gseed, step_index=int(step_index) + j)

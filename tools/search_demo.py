@@ -1,5 +1,5 @@
 """Receding-horizon Monte-Carlo lookahead with pcbenv.search.best_of_k against the plain uniform-random policy, c3.
-python tools/search_demo.py [--roots 256] [--k 16] [--seed 11] [--playouts | --tree [--device-tree] [--policy] | --puct [--device-priors] [--reuse] [--leaves L] [--noise ALPHA EPS | --gumbel M [--leaves L | --gumbel-full]] [--train N [--moves M] [--torch-loss]]]
+python tools/search_demo.py [--roots 256] [--k 16] [--seed 11] [--playouts | --tree [--device-tree] [--policy] | --puct [--device-priors] [--reuse] [--leaves L] [--noise ALPHA EPS | --gumbel M [--leaves L] [--gumbel-full]] [--capacity N] [--train N [--moves M] [--torch-loss]]]
 
 Both play the same instances (one episode per root environment).  The search forks every root k times into a planner
 batch (one device-side gather), plays every child to its end with the on-device sampler, and applies the best child's
@@ -30,7 +30,10 @@ ceil(k / L) + 1 evaluations of roots x L rows; the line then also reports the ro
 rows that were none (-1: behind a repeat or the end of the budget) and, with --reuse, the share of searched roots that finished
 their schedule (sim_index == k).
 --puct --gumbel M --gumbel-full: the full Gumbel rule (pcbenv_gumbel_tree_advance): below the root the search goes to the argmax of
-pi' - n / (1 + sum n) in the place of PUCT, and a child without a visit is completed with v_mix; not with --leaves.
+pi' - n / (1 + sum n) in the place of PUCT, and a child without a visit is completed with v_mix.  With --leaves L the launches
+are pcbenv_gumbel_tree_advance_leaves' (node_rule="gumbel"): the same rule with a pending visit counted as a visit.
+--puct --capacity N: node slots per root in the place of the search's default; tree_errors (with --reuse) has bit 0 set if some
+expansion found no room (ERR_FULL), so 0 says that no root met it.
 --puct --train N (a spatial configuration: --config
 c4): N rounds of pcbenv.alphazero.AlphaZeroTrainer -- collect() plays --moves moves of every root with puct_selfplay, k
 iterations each, pcbenv/policy.py's model behind network_evaluator(priors="device"); update() trains the model on the visit
@@ -81,7 +84,7 @@ def train(a, cfg):
     trainer = AlphaZeroTrainer(root, planner, SpatialPolicy(cfg).to(root.device),
                                AlphaZeroConfig(moves=moves, iterations=a.k, max_children=16, capacity=1 + moves * (a.k + 1) * a.leaves * 16, device_loss=not a.torch_loss,
                                                leaves=a.leaves, noise_alpha=a.noise[0] if a.noise else None, noise_eps=a.noise[1] if a.noise else 0.25,
-                                               gumbel_considered=a.gumbel, gumbel_full=a.gumbel_full))
+                                               gumbel_considered=a.gumbel, gumbel_node_rule="gumbel" if a.gumbel_full else "puct"))
     for it in range(a.train):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -117,7 +120,8 @@ def main():
     ap.add_argument("--leaves", type=int, default=1, metavar="L", help="with --puct: L leaves per root and iteration (pcbenv_puct_advance_leaves); k stays the iterations per move")
     ap.add_argument("--noise", type=float, nargs=2, default=None, metavar=("ALPHA", "EPS"), help="with --puct: Dir(ALPHA) noise of weight EPS on the root's priors (pcbenv_puct_root_noise)")
     ap.add_argument("--gumbel", type=int, default=None, metavar="M", help="with --puct: Gumbel root search, Sequential Halving over M candidates (pcbenv_gumbel_advance)")
-    ap.add_argument("--gumbel-full", action="store_true", help="with --gumbel: the non-root rule and v_mix of the paper as well (pcbenv_gumbel_tree_advance)")
+    ap.add_argument("--gumbel-full", action="store_true", help="with --gumbel: the non-root rule and v_mix of the paper as well (pcbenv_gumbel_tree_advance; with --leaves pcbenv_gumbel_tree_advance_leaves)")
+    ap.add_argument("--capacity", type=int, default=None, metavar="N", help="with --puct: node slots per root (default: the search's own)")
     ap.add_argument("--train", type=int, default=0, metavar="N", help="with --puct: N collect/update rounds of pcbenv.alphazero.AlphaZeroTrainer")
     ap.add_argument("--moves", type=int, default=0, help="with --train: moves of every root per round (default: one episode)")
     ap.add_argument("--torch-loss", action="store_true", help="with --train: the policy loss through the torch chain (device_loss off)")
@@ -132,8 +136,10 @@ def main():
         ap.error("--leaves goes with --puct")
     if a.noise and not a.puct:
         ap.error("--noise goes with --puct")
-    if a.gumbel_full and (a.gumbel is None or a.leaves != 1):
-        ap.error("--gumbel-full goes with --gumbel, without --leaves")
+    if a.gumbel_full and a.gumbel is None:
+        ap.error("--gumbel-full goes with --gumbel")
+    if a.capacity is not None and not a.puct:
+        ap.error("--capacity goes with --puct")
     if a.gumbel is not None and (not a.puct or a.noise):
         ap.error("--gumbel goes with --puct, without --noise")
     if a.puct and (a.tree or a.playouts):
@@ -190,9 +196,9 @@ def main():
         t0 = time.perf_counter()
         if a.puct and a.gumbel is not None:
             first = gumbel_search_device(search_root, k, 1000 + t * T * (-(-k // a.leaves) + 1), evaluate, max_considered=a.gumbel, max_children=16,
-                                         gumbel_step_index=1000 + t, leaves=a.leaves, full=a.gumbel_full).move_action
+                                         gumbel_step_index=1000 + t, leaves=a.leaves, node_rule="gumbel" if a.gumbel_full else "puct", capacity=a.capacity).move_action
         elif a.puct:
-            first = puct_search_device(search_root, k, 1000 + t * T * k, evaluate, max_children=16, leaves=a.leaves, root_noise=a.noise).action
+            first = puct_search_device(search_root, k, 1000 + t * T * k, evaluate, max_children=16, leaves=a.leaves, root_noise=a.noise, capacity=a.capacity).action
         elif a.tree:
             first = (tree_search_device if a.device_tree else tree_search)(search_root, k, step_index=1000 + t * T * k, backend=backend).action
         elif a.playouts:
@@ -215,7 +221,7 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         sp = puct_selfplay(search_root, evaluate, T, k, step_index=1000, max_children=16, leaves=a.leaves, root_noise=a.noise,
-                           gumbel=None if a.gumbel is None else (a.gumbel, 50.0, 1.0), on_move=on_move, gumbel_full=a.gumbel_full)
+                           gumbel=None if a.gumbel is None else (a.gumbel, 50.0, 1.0), on_move=on_move, gumbel_node_rule="gumbel" if a.gumbel_full else "puct", capacity=a.capacity)
         torch.cuda.synchronize()
         spent, planner_steps = time.perf_counter() - t0, P * k * a.leaves * T * T
         search_final = final_rewards(search_root, lambda t: (sp.reward[t], sp.done[t]), T)
@@ -241,6 +247,8 @@ def main():
         out["gumbel_full"] = True
     if a.seed != 11:
         out["seed"] = a.seed
+    if a.capacity is not None:
+        out["capacity"] = a.capacity
     if a.puct:
         total = all_rows[0]
         leaves = int(leaf_rows) if a.leaves != 1 else total
