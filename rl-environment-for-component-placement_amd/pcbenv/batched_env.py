@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _gumbel_leaves_lib, _gumbel_lib, _gumbel_tree_leaves_lib, _gumbel_tree_lib, _leaves_lib, _lib, _move_lib, _noise_lib, _priors_lib, _search_lib, _train_lib
+from . import _frontier_lib, _gumbel_leaves_lib, _gumbel_lib, _gumbel_tree_leaves_lib, _gumbel_tree_lib, _leaves_lib, _lib, _move_lib, _noise_lib, _priors_lib, _search_lib, _train_lib
 from .config import EnvConfig, KIND_PIN, KIND_RECT, KIND_SPATIAL, KIND_SQUARE
 from .instances import Instance, InstanceStream, env_seed, pack_instances
 
@@ -169,7 +169,7 @@ class BatchedPlacementEnv:
             raise RuntimeError("BatchedPlacementEnv needs a GPU device (there is no CPU fallback)")
         # the device the handle lives on, index included: one named without an index is the current device, now and for good
         self.device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
-        self._L = _gumbel_tree_leaves_lib.bind(_gumbel_tree_lib.bind(_gumbel_leaves_lib.bind(_gumbel_lib.bind(_noise_lib.bind(_leaves_lib.bind(_train_lib.bind(_move_lib.bind(_priors_lib.bind(_search_lib.bind(_lib.load()))))))))))
+        self._L = _frontier_lib.bind(_gumbel_tree_leaves_lib.bind(_gumbel_tree_lib.bind(_gumbel_leaves_lib.bind(_gumbel_lib.bind(_noise_lib.bind(_leaves_lib.bind(_train_lib.bind(_move_lib.bind(_priors_lib.bind(_search_lib.bind(_lib.load())))))))))))
         # per-environment spaces (the reference constructors' declarations); every tensor adds a leading batch dim
         from .spaces import action_space_for, observation_space_for
         self.action_space = self.single_action_space = action_space_for(cfg)
@@ -944,6 +944,57 @@ class BatchedPlacementEnv:
             return
         self._puct_absorb(self._L.pcbenv_puct_advance_leaves, req, P * req.num_leaves, phases, value, leaf_terminal, cand_count, cand_actions,
                           cand_prior)
+
+    def frontier_request(self, tensors: Dict[str, torch.Tensor], width: int, num_candidates: int,
+                         prior_weight: float = 0.0) -> "_frontier_lib.PcbenvFrontierRequest":
+        """The request of `frontier_advance` for the tensors in `tensors` (see `pcbenv.search.new_frontier_tensors` for a set
+        of the right shapes): the two sets of rows `paths_0`, `path_len_0`, `cum_logp_0` and `paths_1`, `path_len_1`,
+        `cum_logp_1`, the members `parent_row`, `live`, `best_value`, `best_len`, `best_path` of pcbenv_frontier_request
+        (include/pcbenv_frontier.h) and optionally `errors_dev` -- on this device, contiguous, of the dtypes and shapes the
+        header gives; P and T are read off `best_path` [T, P, 3], W = width and K = num_candidates are arguments.  The
+        request holds addresses only: the caller keeps the tensors alive."""
+        W, K, best = int(width), int(num_candidates), tensors["best_path"]
+        if W < 1 or W > _frontier_lib.MAX_FRONTIER_WIDTH or K < 1 or K > _frontier_lib.MAX_FRONTIER_CANDIDATES or W * K > _frontier_lib.MAX_FRONTIER_ROWS:
+            raise ValueError(f"width and num_candidates must be in [1, 64] and their product at most {_frontier_lib.MAX_FRONTIER_ROWS}, got {W} and {K}")
+        if best.dim() != 3 or best.shape[2] != 3:
+            raise ValueError(f"best_path must be [T, P, 3], got {tuple(best.shape)}")
+        T, P = int(best.shape[0]), int(best.shape[1])
+        i32, f64, R = torch.int32, torch.float64, P * W * K
+        want = {"parent_row": (i32, (R,)), "live": (i32, (P,)), "best_value": (f64, (P,)), "best_len": (i32, (P,)), "best_path": (i32, (T, P, 3))}
+        req = self._tree_request(_frontier_lib.PcbenvFrontierRequest, tensors, want, num_roots=P, width=W, num_candidates=K, max_steps=T,
+                                 prior_weight=float(prior_weight))
+        sets = []
+        for s in (0, 1):
+            for name, (dtype, shape) in (("paths", (i32, (T, R, 3))), ("path_len", (i32, (R,))), ("cum_logp", (f64, (R,)))):
+                check_tensor(self.device, f"{name}_{s}", tensors[f"{name}_{s}"], dtype, shape)
+            sets.append({name: _ptr(tensors[f"{name}_{s}"]) for name in _frontier_lib.FRONTIER_SET})
+        req.sets = sets  # the addresses of set 0 and set 1: `frontier_advance` names one `in` and the other `out`
+        return req
+
+    def frontier_advance(self, req: "_frontier_lib.PcbenvFrontierRequest", phases: int, evaluation=None, swap: bool = False) -> None:
+        """One depth of P beam searches over placements on the device (`pcbenv_frontier_advance`, one kernel launch on the
+        current stream, nothing else).  `phases` is `_frontier_lib.FRONTIER_INIT` or `FRONTIER_ADVANCE`.  swap=False reads
+        set 0 of the request's tensors as `in` and writes set 1 as `out`; swap=True the other way round.  INIT writes the
+        root row into the out set; ADVANCE takes `evaluation`, the `pcbenv.search.Evaluation` of the in rows -- `value`
+        [P * W * K] float64, `terminal` uint8 or bool, `cand_count` int32, `cand_actions` [P * W * K, K, 3] int32,
+        `cand_prior` [P * W * K, K] float32 -- records the best finished row per root in `best_value`, `best_len` and
+        `best_path`, keeps the W best expandable rows and writes their children, at most W * K per root, into the out
+        set: the `paths=` / `path_len=` of the next `gather_` or `playout(k=W * K)` call.  `req`: `frontier_request(...)`,
+        reusable for every call on the same tensors."""
+        P, K = req.num_roots, req.num_candidates
+        if P == 0:  # torch gives empty tensors a null pointer
+            return
+        R = P * req.width * K
+        for name in _frontier_lib.FRONTIER_SET:
+            setattr(req, name + "_in", req.sets[1 if swap else 0][name])
+            setattr(req, name + "_out", req.sets[0 if swap else 1][name])
+        ev = evaluation
+        over = None if ev is None else ev.terminal.view(torch.uint8) if ev.terminal.dtype == torch.bool else ev.terminal
+        self._advance(self._L.pcbenv_frontier_advance, req, phases,
+                      (("value", None if ev is None else ev.value, torch.float64, (R,)), ("leaf_terminal", over, torch.uint8, (R,)),
+                       ("cand_count", None if ev is None else ev.cand_count, torch.int32, (R,)),
+                       ("cand_actions", None if ev is None else ev.cand_actions, torch.int32, (R, K, 3)),
+                       ("cand_prior", None if ev is None else ev.cand_prior, torch.float32, (R, K))))
 
     def puct_move_request(self, tree: Dict[str, torch.Tensor], max_children: int = 16) -> "_move_lib.PcbenvPuctMoveRequest":
         """The request of `puct_move` for the tensors in `tree`: the tree tensors of `puct_request` (`num_nodes` ...

@@ -29,6 +29,11 @@ anything is evaluated, each descent leaving a pending visit on its path, the eva
 launch backs them up (pcbenv_puct_advance_leaves, include/pcbenv_leaves.h).  With leaves == 1 each of them does what it
 did before that keyword existed.
 
+`frontier_search` is a beam search over placements -- per root a frontier of W partial placements, each expanded by an
+evaluator's K best legal actions, the W best of the W * K children kept per depth, the best finished placement the
+result -- on `frontier_advance`, the specification in tensor code of pcbenv_frontier_advance
+(include/pcbenv_frontier.h); `frontier_search_device` is the same search with one launch per depth.
+
 `policy_backend` replaces the uniform rollout of either search by a policy's: the node a path names is materialised
 in a planner batch by `gather_(paths=...)` (pcbenv_gather_paths, one launch), and the rollout behind it draws from the
 logits a network gives for the planner's observations.
@@ -1708,3 +1713,215 @@ def network_evaluator(root, planner, logits_fn, value_fn=None, max_children: int
         value = torch.where(over, planner.reward.to(torch.float64), leaf)
         return Evaluation(value, over.to(torch.uint8), count, actions, prior)
     return evaluate
+
+
+# ---- the frontier: a beam search over placements ---------------------------------------------------------------------
+FRONTIER_INIT, FRONTIER_ADVANCE = 1, 2  # include/pcbenv_frontier.h
+MAX_FRONTIER_WIDTH, MAX_FRONTIER_CANDIDATES, MAX_FRONTIER_ROWS = 64, 64, 1024
+FRONTIER_ERR_ROW = 2  # bit 1 of the error word: a path_len outside [-1, T] in the rows read
+
+
+def new_frontier_tensors(P: int, W: int, K: int, T: int, device) -> dict:
+    """The tensors of P frontiers of W * K rows and T steps, as `BatchedPlacementEnv.frontier_request` takes them: the two
+    sets of rows `paths_s` [T, P * W * K, 3], `path_len_s` and `cum_logp_s` [P * W * K], s = 0, 1, which a search swaps
+    between depths, `parent_row`, `live`, the accumulators `best_value`, `best_len`, `best_path` and `errors_dev`.
+    Uninitialised but for the paths, `best_path`, `cum_logp_s` and `errors_dev`: FRONTIER_INIT fills the rest."""
+    i32, f64 = dict(dtype=torch.int32, device=device), dict(dtype=torch.float64, device=device)
+    R = int(P) * int(W) * int(K)
+    ft = {}
+    for s in (0, 1):
+        ft.update({f"paths_{s}": torch.zeros((T, R, 3), **i32), f"path_len_{s}": torch.empty(R, **i32), f"cum_logp_{s}": torch.zeros(R, **f64)})
+    ft.update(parent_row=torch.empty(R, **i32), live=torch.empty(P, **i32), best_value=torch.empty(P, **f64), best_len=torch.empty(P, **i32),
+              best_path=torch.zeros((T, P, 3), **i32), errors_dev=torch.zeros(1, **i32))
+    return ft
+
+
+def log_prior(prior: torch.Tensor) -> torch.Tensor:
+    """float64 ln of float32 priors as csrc/pcb_frontier.h:log_prior gives it: `ieee_ln` of a prior that is a positive,
+    finite, normal float32 -- read off its bits -- and -inf of any other."""
+    b = prior.contiguous().view(torch.int32)
+    e = (b >> 23) & 0xff
+    ok = (b >= 0) & (e >= 1) & (e <= 254)
+    x = torch.where(ok, prior, torch.ones_like(prior)).to(torch.float64)
+    return torch.where(ok, ieee_ln(x), torch.full_like(x, float("-inf")))
+
+
+def frontier_advance(ft: dict, phases: int, width: int, num_candidates: int, prior_weight: float = 0.0, evaluation=None, swap: bool = False) -> None:
+    """One depth of a beam search over placements, in tensor code for any device and without a host synchronisation: the
+    specification of pcbenv_frontier_advance (include/pcbenv_frontier.h), on the tensors of `new_frontier_tensors`, in
+    place.  swap=False reads set 0 as `in` and writes set 1 as `out`; swap=True the other way round.  W = width, K =
+    num_candidates, F = W * K rows per root, row p * F + i the slot i of root p.
+    FRONTIER_INIT writes the out set and nothing else: path_len 0 for slot 0 of every root and -1 for the others, cum_logp
+    of slot 0 = 0.0, parent_row = -1, live = 1, best_len = -1 and best_value = -inf; the paths and best_path are untouched.
+    FRONTIER_ADVANCE takes `evaluation`, the `Evaluation` of the in rows, in four steps per root.
+      live rows        path_len in [0, T]; a value outside [-1, T] is no row and sets bit 1 of `errors_dev`.
+      finished rows    live rows the evaluation calls terminal, taken in increasing i with v = value, a NaN counted as -inf:
+                       one with best_len == -1 or v > best_value becomes the root's best -- best_value = v, best_len = its
+                       length, best_path rows d < that length = its path.  A finished row is never expanded.
+      the order        live, unfinished rows with path_len < T and k = clamp(cand_count, 0, K) > 0 are expandable, the
+                       others are dropped.  Their score is value if prior_weight == 0, and value + prior_weight * cum_logp
+                       otherwise (two operations), a NaN counted as -inf; the order is the score descending, ties -- -0.0
+                       with +0.0 among them -- to the lower i; the first n = min(W, expandable) rows are kept.
+      the children     child c < k of the kept row of rank w goes to slot w * K + c of the out set: the parent's path and
+                       cand_actions[parent, c] behind it, path_len + 1, cum_logp of the parent + `log_prior` of the
+                       candidate's prior, parent_row = the parent's slot i.  Every other slot gets path_len = parent_row =
+                       -1 and nothing else; live = the child rows written."""
+    W, K, ph = int(width), int(num_candidates), int(phases)
+    if ph not in (FRONTIER_INIT, FRONTIER_ADVANCE):
+        raise ValueError("phases must be FRONTIER_INIT or FRONTIER_ADVANCE")
+    if W < 1 or W > MAX_FRONTIER_WIDTH or K < 1 or K > MAX_FRONTIER_CANDIDATES or W * K > MAX_FRONTIER_ROWS:
+        raise ValueError(f"width and num_candidates must be in [1, 64] and their product at most {MAX_FRONTIER_ROWS}, got {W} and {K}")
+    F = W * K
+    T, P = int(ft["best_path"].shape[0]), int(ft["best_path"].shape[1])
+    a, b = (1, 0) if swap else (0, 1)
+    paths_in, len_in, cum_in = ft[f"paths_{a}"], ft[f"path_len_{a}"], ft[f"cum_logp_{a}"]
+    paths_out, len_out, cum_out = ft[f"paths_{b}"], ft[f"path_len_{b}"], ft[f"cum_logp_{b}"]
+    dev = len_in.device
+    if P == 0:
+        return
+    slot = torch.arange(F, dtype=torch.int64, device=dev)
+    if ph == FRONTIER_INIT:
+        first = (slot == 0)[None, :].expand(P, F)
+        len_out.view(P, F).copy_(torch.where(first, 0, -1))
+        cum_out.view(P, F)[:, 0] = 0.0
+        ft["parent_row"].fill_(-1)
+        ft["live"].fill_(1)
+        ft["best_len"].fill_(-1)
+        ft["best_value"].fill_(float("-inf"))
+        return
+    ev = evaluation
+    f64 = dict(dtype=torch.float64, device=dev)
+    ninf = torch.full((), float("-inf"), **f64)
+    length = len_in.view(P, F).to(torch.int64)
+    live = (length >= 0) & (length <= T)
+    damaged = (length < -1) | (length > T)
+    if ft.get("errors_dev") is not None:
+        ft["errors_dev"] |= (damaged.any().to(torch.int32) * FRONTIER_ERR_ROW)
+    value = ev.value.to(**f64).view(P, F)
+    over = ev.terminal.to(dev).view(P, F) != 0
+    k = ev.cand_count.to(device=dev, dtype=torch.int64).view(P, F).clamp(0, K)
+    cand_actions = ev.cand_actions.to(device=dev, dtype=torch.int32).view(P, F, K, 3)
+    cand_prior = ev.cand_prior.to(device=dev, dtype=torch.float32).view(P, F, K)
+    rows = torch.arange(P, dtype=torch.int64, device=dev)
+    pin = paths_in.view(T, P, F, 3)
+    # finished rows: the first of those with the largest value is the one a walk in increasing i ends with
+    fin = live & over
+    v = torch.where(fin & ~torch.isnan(value), value, ninf)
+    top = v.max(dim=1, keepdim=True).values
+    first = torch.where(fin & (v == top), slot[None, :], F).min(dim=1).values.clamp(max=F - 1)
+    v_first, len_first = v[rows, first], length[rows, first]
+    better = fin.any(dim=1) & ((ft["best_len"] == -1) | (v_first > ft["best_value"]))
+    ft["best_value"].copy_(torch.where(better, v_first, ft["best_value"]))
+    ft["best_len"].copy_(torch.where(better, len_first.to(torch.int32), ft["best_len"]))
+    step = torch.arange(T, dtype=torch.int64, device=dev)
+    taken = better[None, :] & (step[:, None] < len_first[None, :])                                    # [T, P]
+    ft["best_path"].copy_(torch.where(taken[:, :, None], pin[:, rows, first], ft["best_path"]))
+    # the order of the expandable rows
+    expandable = live & ~over & (length < T) & (k > 0)
+    cum = cum_in.view(P, F)
+    score = value if float(prior_weight) == 0.0 else value + float(prior_weight) * torch.where(expandable, cum, torch.zeros_like(cum))
+    score = torch.where(expandable & ~torch.isnan(score), score, ninf) + 0.0  # + 0.0: -0.0 and +0.0 are one key to any sort
+    by_score = torch.sort(score, dim=1, descending=True, stable=True).indices
+    behind = (~expandable).gather(1, by_score).to(torch.int8)
+    order = by_score.gather(1, torch.sort(behind, dim=1, stable=True).indices)  # the expandable rows first, each part in the order it had
+    n = expandable.sum(dim=1).clamp(max=W)
+    # the children
+    w, c = torch.div(slot, K, rounding_mode="floor"), slot % K
+    parent = order[:, :W][:, w]                                                                        # [P, F]
+    child = (w[None, :] < n[:, None]) & (c[None, :] < k.gather(1, parent))
+    plen = length.gather(1, parent)
+    len_out.view(P, F).copy_(torch.where(child, plen + 1, -1))
+    ft["parent_row"].view(P, F).copy_(torch.where(child, parent, -1))
+    lp = log_prior(cand_prior[rows[:, None], parent, c[None, :]])
+    cum_out.view(P, F).copy_(torch.where(child, cum.gather(1, parent) + lp, cum_out.view(P, F)))
+    pout = paths_out.view(T, P, F, 3)
+    inherited = pin.gather(2, parent[None, :, :, None].expand(T, P, F, 3))
+    own = cand_actions[rows[:, None], parent, c[None, :]]                                              # [P, F, 3]
+    at = step[:, None, None]
+    new = torch.where((child[None] & (at < plen[None]))[..., None], inherited,
+                      torch.where((child[None] & (at == plen[None]))[..., None], own[None].expand(T, P, F, 3), pout))
+    pout.copy_(new)
+    ft["live"].copy_(child.sum(dim=1))
+
+
+@dataclass
+class FrontierSearch:
+    """What `frontier_search` and `frontier_search_device` return.  P roots, F = width * max_children rows per root."""
+    best_path: torch.Tensor   # [T, P, 3] int32: the path of the best finished placement (rows >= best_len: don't care)
+    best_len: torch.Tensor    # [P] int32: its length, -1 if no row of the root finished
+    best_value: torch.Tensor  # [P] float64: its value, -inf if none
+    action: torch.Tensor      # [P, 3] int32: best_path[0], zero where best_len < 1
+    live: torch.Tensor        # [P] int32: the rows of the final frontier
+    errors: torch.Tensor      # 0-dim int32: bit 1 = a path_len outside [-1, T] was read
+    paths: torch.Tensor       # [T, P * F, 3] int32: the final frontier, as the last ADVANCE wrote it
+    path_len: torch.Tensor    # [P * F] int32, -1 = no row
+    cum_logp: torch.Tensor    # [P * F] float64
+    parent_row: torch.Tensor  # [P * F] int32: the slot of a row's parent in the frontier before, -1 = no row
+
+
+def _frontier_arguments(root, evaluate, width, max_children, prior_weight, max_steps, depth):
+    from .batched_env import default_max_steps
+    P, W, K = int(root.num_envs), int(width), int(max_children)
+    if W < 1 or W > MAX_FRONTIER_WIDTH or K < 1 or K > MAX_FRONTIER_CANDIDATES or W * K > MAX_FRONTIER_ROWS:
+        raise ValueError(f"a frontier search needs width and max_children in [1, 64] and their product at most {MAX_FRONTIER_ROWS}")
+    if P * W * K > 2 ** 31 - 1:
+        raise ValueError("a frontier search needs num_envs * width * max_children <= 2^31 - 1")
+    if not callable(evaluate):
+        raise ValueError("evaluate must be callable: (paths, path_len, step_index0) -> Evaluation")
+    pw = float(prior_weight)
+    if pw != pw or pw in (float("inf"), float("-inf")):
+        raise ValueError("prior_weight must be finite")
+    T = default_max_steps(root.cfg) if max_steps is None else int(max_steps)
+    D = T + 1 if depth is None else int(depth)
+    if T < 1 or D < 1 or D > T + 1:
+        raise ValueError("a frontier search needs max_steps >= 1 and depth in [1, max_steps + 1]")
+    return P, W, K, pw, T, D
+
+
+def frontier_result(ft: dict, last: int) -> FrontierSearch:
+    """The tensors of a frontier search in the form the searches report; `last`: the set the last ADVANCE wrote."""
+    best_path, best_len = ft["best_path"], ft["best_len"]
+    action = torch.where((best_len >= 1)[:, None], best_path[0], torch.zeros_like(best_path[0]))
+    return FrontierSearch(best_path, best_len, ft["best_value"], action, ft["live"], ft["errors_dev"][0], ft[f"paths_{last}"], ft[f"path_len_{last}"],
+                          ft[f"cum_logp_{last}"], ft["parent_row"])
+
+
+def frontier_search(root, evaluate, width: int, max_children: int, step_index: int, prior_weight: float = 0.0, max_steps=None,
+                    depth=None) -> FrontierSearch:
+    """A beam search over placements for all P = root.num_envs roots in lock-step, on the specification `frontier_advance`:
+    tensor code for any device, one `evaluate` per depth and no host synchronisation.  Per root a frontier of at most W =
+    width partial placements is kept; INIT makes it the root alone, and depth d = 0, 1, ... is
+      evaluate   evaluate(paths, path_len, step_index + d * max_steps) -> `Evaluation` of the P * W * K rows of the frontier's
+                 children (K = max_children; path_len -1: no row, what comes back for it is not looked at);
+      advance    `frontier_advance`: the finished rows compete for best_path, the W best of the others by value +
+                 prior_weight * cum_logp are kept, and each gives its k <= K candidates as the next rows.
+    depth: the number of depths, default and at most max_steps + 1 (then every row has finished or was dropped).
+    max_steps: the most transitions of an episode (default: that of root.cfg).  With prior_weight = 0 the search orders
+    by the evaluator's value alone -- a network's value head, or a uniform rollout from the node -- and with a constant
+    value and prior_weight = 1 by the cumulative log-prior.  `network_evaluator(..., leaves=W * K)` is such an `evaluate`."""
+    P, W, K, pw, T, D = _frontier_arguments(root, evaluate, width, max_children, prior_weight, max_steps, depth)
+    ft = new_frontier_tensors(P, W, K, T, getattr(root, "device", "cpu"))
+    frontier_advance(ft, FRONTIER_INIT, W, K, pw, swap=True)  # writes set 0
+    for d in range(D):
+        cur = d % 2
+        ev = evaluate(ft[f"paths_{cur}"], ft[f"path_len_{cur}"], int(step_index) + d * T)
+        frontier_advance(ft, FRONTIER_ADVANCE, W, K, pw, ev, swap=cur == 1)
+    return frontier_result(ft, D % 2)
+
+
+def frontier_search_device(root, evaluate, width: int, max_children: int, step_index: int, prior_weight: float = 0.0, max_steps=None,
+                           depth=None) -> FrontierSearch:
+    """`frontier_search` with the frontier step on the device: a depth is `evaluate` and one kernel launch,
+    `root.frontier_advance` (pcbenv_frontier_advance, include/pcbenv_frontier.h), with no tensor operation between them.
+    The same search as `frontier_search` with the same arguments, field by field, floats by their bits: the score is two
+    IEEE operations and the logarithm is `ieee_ln` on either side.  The evaluation's tensors must be on the root's device,
+    contiguous, of the dtypes `Evaluation` names (`terminal` may be bool)."""
+    P, W, K, pw, T, D = _frontier_arguments(root, evaluate, width, max_children, prior_weight, max_steps, depth)
+    ft = new_frontier_tensors(P, W, K, T, root.device)
+    req = root.frontier_request(ft, W, K, pw)
+    root.frontier_advance(req, FRONTIER_INIT, swap=True)  # writes set 0
+    for d in range(D):
+        cur = d % 2
+        ev = evaluate(ft[f"paths_{cur}"], ft[f"path_len_{cur}"], int(step_index) + d * T)
+        root.frontier_advance(req, FRONTIER_ADVANCE, ev, swap=cur == 1)
+    return frontier_result(ft, D % 2)

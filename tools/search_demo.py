@@ -1,5 +1,5 @@
 """Receding-horizon Monte-Carlo lookahead with pcbenv.search.best_of_k against the plain uniform-random policy, c3.
-python tools/search_demo.py [--roots 256] [--k 16] [--seed 11] [--playouts | --tree [--device-tree] [--policy] | --puct [--device-priors] [--reuse] [--leaves L] [--noise ALPHA EPS | --gumbel M [--leaves L] [--gumbel-full]] [--capacity N] [--train N [--moves M] [--torch-loss]]]
+python tools/search_demo.py [--roots 256] [--k 16] [--seed 11] [--playouts | --tree [--device-tree] [--policy] | --puct [--device-priors] [--reuse] [--leaves L] [--noise ALPHA EPS | --gumbel M [--leaves L] [--gumbel-full]] [--capacity N] [--train N [--moves M] [--torch-loss]] | --frontier W [--prior-weight X] [--device-priors]]
 
 Both play the same instances (one episode per root environment).  The search forks every root k times into a planner
 batch (one device-side gather), plays every child to its end with the on-device sampler, and applies the best child's
@@ -38,7 +38,13 @@ expansion found no room (ERR_FULL), so 0 says that no root met it.
 c4): N rounds of pcbenv.alphazero.AlphaZeroTrainer -- collect() plays --moves moves of every root with puct_selfplay, k
 iterations each, pcbenv/policy.py's model behind network_evaluator(priors="device"); update() trains the model on the visit
 counts with pcbenv_evaluate_visits (--torch-loss: the torch chain instead) -- and one line per round: the mean final reward
-of the episodes that ended in the round and the mean cross entropy of the update."""
+of the episodes that ended in the round and the mean cross entropy of the update.
+--frontier W: a beam search over placements (pcbenv.search.frontier_search_device: one pcbenv_frontier_advance launch per depth next
+to the evaluation), ONE search per episode: a frontier of W partial placements per root, each expanded by the k most probable
+legal actions of network_evaluator (constant logits; --device-priors: pcbenv_top_priors) and scored by one uniform rollout from
+it, plus --prior-weight X times its cumulative log-prior.  The plan found, best_path, is then played with `step`.  The line
+reports the mean final reward, the rows evaluated and the time per episode, and that every played plan ended with the
+best_value the search reported for it."""
 import argparse
 import json
 import os
@@ -51,7 +57,7 @@ import torch  # noqa: E402
 from pcbenv import named_config  # noqa: E402
 from pcbenv.batched_env import BatchedPlacementEnv  # noqa: E402
 from pcbenv.config import KIND_SPATIAL  # noqa: E402
-from pcbenv.search import (best_of_k, best_of_k_playouts, gumbel_search_device, network_evaluator, policy_backend, puct_search_device, puct_selfplay, tree_search,  # noqa: E402
+from pcbenv.search import (best_of_k, best_of_k_playouts, frontier_search_device, gumbel_search_device, network_evaluator, policy_backend, puct_search_device, puct_selfplay, tree_search,  # noqa: E402
                            tree_search_device)
 
 
@@ -104,6 +110,50 @@ def train(a, cfg):
     planner.close()
 
 
+def frontier(a, cfg):
+    """--frontier W: one search per episode and its plan played; one JSON line."""
+    P, W, K, T = a.roots, a.frontier, a.k, cfg.max_num_components
+
+    def make(n):
+        e = BatchedPlacementEnv(cfg, n, queue_depth=1, run_seed=a.seed)
+        e.generate_instances()
+        e.reset()
+        return e
+    rand_root, root, planner = make(P), make(P), make(P * W * K)
+    dev = root.device
+    zeros = torch.zeros((P * W * K, cfg.num_orientations * cfg.height * cfg.width), dtype=torch.float32, device=dev)
+    scored = network_evaluator(root, planner, lambda obs: zeros, max_children=K, priors="device" if a.device_priors else "torch", leaves=W * K)
+    rows = torch.zeros((), dtype=torch.int64, device=dev)
+
+    def evaluate(paths, path_len, step_index0):
+        rows.add_((path_len >= 0).sum())
+        return scored(paths, path_len, step_index0)
+    random_final = final_rewards(rand_root, lambda t: rand_root.rollout_step(t)[1:3], T)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fs = frontier_search_device(root, evaluate, W, K, 1000, prior_weight=a.prior_weight)
+    torch.cuda.synchronize()
+    spent = time.perf_counter() - t0
+    no_action = torch.full((P, 3), -1, dtype=torch.int32, device=dev)
+
+    def play(t):  # past its plan, or without one: an action that is no action ends the episode as it stands
+        _, r, d, _ = root.step(torch.where((fs.best_len <= t)[:, None], no_action, fs.best_path[t]))
+        return r, d
+    final = final_rewards(root, play, T)
+    planned = fs.best_len >= 1
+    out = {"config": a.config, "roots": P, "frontier": W, "k": K, "prior_weight": a.prior_weight,
+           "search": "frontier_search_device+network_evaluator" + ("(priors=device)" if a.device_priors else ""),
+           "random_policy_mean_final_reward": float(random_final.mean()), "frontier_mean_final_reward": float(final.mean()),
+           "roots_with_a_plan": int(planned.sum()), "every_plan_reproduced_its_best_value": bool((final[planned] == fs.best_value[planned]).all()),
+           "evaluated_rows_per_episode": round(int(rows) / P, 2), "us_per_evaluated_row": round(1e6 * spent / max(int(rows), 1), 3),
+           "search_seconds": round(spent, 3), "seconds_per_episode": round(spent / P, 6), "frontier_errors": int(fs.errors)}
+    if a.seed != 11:
+        out["seed"] = a.seed
+    print(json.dumps(out), flush=True)
+    for e in (rand_root, root, planner):
+        e.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--roots", type=int, default=256)
@@ -125,11 +175,17 @@ def main():
     ap.add_argument("--train", type=int, default=0, metavar="N", help="with --puct: N collect/update rounds of pcbenv.alphazero.AlphaZeroTrainer")
     ap.add_argument("--moves", type=int, default=0, help="with --train: moves of every root per round (default: one episode)")
     ap.add_argument("--torch-loss", action="store_true", help="with --train: the policy loss through the torch chain (device_loss off)")
+    ap.add_argument("--frontier", type=int, default=None, metavar="W", help="a beam search over placements, W rows per root and k candidates per row, one search per episode (frontier_search_device)")
+    ap.add_argument("--prior-weight", type=float, default=0.0, metavar="X", help="with --frontier: the weight of a row's cumulative log-prior in its score")
     a = ap.parse_args()
     if a.train and not a.puct:
         ap.error("--train goes with --puct")
-    if a.device_priors and not a.puct:
-        ap.error("--device-priors goes with --puct")
+    if a.frontier is not None and (a.puct or a.tree or a.playouts or a.train):
+        ap.error("--frontier goes alone")
+    if a.prior_weight != 0.0 and a.frontier is None:
+        ap.error("--prior-weight goes with --frontier")
+    if a.device_priors and not a.puct and a.frontier is None:
+        ap.error("--device-priors goes with --puct or --frontier")
     if a.reuse and not a.puct:
         ap.error("--reuse goes with --puct")
     if a.leaves != 1 and not a.puct:
@@ -152,6 +208,8 @@ def main():
     if a.policy and cfg.kind != KIND_SPATIAL:
         ap.error("--policy needs a spatial configuration, the one pcbenv/policy.py's model reads (--config c4)")
     P, k, T = a.roots, a.k, cfg.max_num_components
+    if a.frontier is not None:
+        return frontier(a, cfg)
     if a.train:
         if cfg.kind != KIND_SPATIAL:
             ap.error("--train needs a spatial configuration, the one pcbenv/policy.py's model reads (--config c4)")
