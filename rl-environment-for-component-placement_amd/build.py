@@ -11,7 +11,7 @@ the host side -- the C ABI
 (csrc/pcb_gen.hip), which share csrc/pcb_host.h -- the two kernels every kind uses (csrc/pcb_sample.hip), the policy kernels
 (csrc/pcb_policy*.hip), the tree steps with their entry points (csrc/pcb_tree.hip, and csrc/pcb_puct.hip
 for include/pcbenv_search.h, csrc/pcb_puct_leaves.hip for include/pcbenv_leaves.h, csrc/pcb_puct_move.hip for include/pcbenv_move.h,
-csrc/pcb_puct_noise.hip for include/pcbenv_noise.h, csrc/pcb_gumbel.hip for include/pcbenv_gumbel.h, csrc/pcb_gumbel_leaves.hip for include/pcbenv_gumbel_leaves.h, csrc/pcb_gumbel_tree.hip for include/pcbenv_gumbel_tree.h, csrc/pcb_gumbel_tree_leaves.hip for include/pcbenv_gumbel_tree_leaves.h, csrc/pcb_frontier.hip for include/pcbenv_frontier.h;
+csrc/pcb_puct_noise.hip for include/pcbenv_noise.h, csrc/pcb_gumbel.hip for include/pcbenv_gumbel.h, csrc/pcb_gumbel_leaves.hip for include/pcbenv_gumbel_leaves.h, csrc/pcb_gumbel_tree.hip for include/pcbenv_gumbel_tree.h, csrc/pcb_gumbel_tree_leaves.hip for include/pcbenv_gumbel_tree_leaves.h, csrc/pcb_frontier.hip for include/pcbenv_frontier.h, csrc/pcb_frontier_sample.hip for include/pcbenv_frontier_sample.h;
 what they share is csrc/pcb_group.h, the lane-group kernel skeleton and its launch, csrc/pcb_puct_group.h, the PUCT absorb
 and descent of pcb_puct.hip and pcb_gumbel.hip, and csrc/pcb_tree_host.h, the argument checks of their entry points), the masked top-K of a policy's logits (csrc/pcb_top_priors.hip for include/pcbenv_priors.h)
 and the host instance generator
@@ -45,9 +45,9 @@ UNITS = ([unit("pcb_kind", "pcb_kind.inc", k) for k in FLAT_KINDS[::-1]]
          + [unit("pcb_playout_paths", "pcb_playout.inc", k, paths=True) for k in FLAT_KINDS]
          + [unit("pcb_gather_paths", "pcb_gather_paths.inc", k, p) for p in (2, 1, 0) for k in PIN_KINDS]
          + [unit("pcb_gather_paths", "pcb_gather_paths.inc", k) for k in FLAT_KINDS]
-         + [(u + ".o", u, []) for u in ("pcb_policy.hip", "pcb_policy_eval.hip", "pcb_policy_visits.hip", "pcb_policy_axis.hip", "pcb_tree.hip", "pcb_puct.hip", "pcb_puct_leaves.hip", "pcb_puct_move.hip", "pcb_puct_noise.hip", "pcb_gumbel.hip", "pcb_gumbel_leaves.hip", "pcb_gumbel_tree.hip", "pcb_gumbel_tree_leaves.hip", "pcb_frontier.hip", "pcb_top_priors.hip", "pcb_gen.hip", "pcb_sample.hip",
+         + [(u + ".o", u, []) for u in ("pcb_policy.hip", "pcb_policy_eval.hip", "pcb_policy_visits.hip", "pcb_policy_axis.hip", "pcb_tree.hip", "pcb_puct.hip", "pcb_puct_leaves.hip", "pcb_puct_move.hip", "pcb_puct_noise.hip", "pcb_gumbel.hip", "pcb_gumbel_leaves.hip", "pcb_gumbel_tree.hip", "pcb_gumbel_tree_leaves.hip", "pcb_frontier.hip", "pcb_frontier_sample.hip", "pcb_top_priors.hip", "pcb_gen.hip", "pcb_sample.hip",
                                         "pcbenv_api.hip", "pcb_config.hip", "instance_gen.cpp")])
-DEPS = [os.path.join(REPO, "include", h) for h in ("pcbenv.h", "pcbenv_search.h", "pcbenv_priors.h", "pcbenv_move.h", "pcbenv_train.h", "pcbenv_leaves.h", "pcbenv_noise.h", "pcbenv_gumbel.h", "pcbenv_gumbel_leaves.h", "pcbenv_gumbel_tree.h", "pcbenv_gumbel_tree_leaves.h", "pcbenv_frontier.h")] + sorted(
+DEPS = [os.path.join(REPO, "include", h) for h in ("pcbenv.h", "pcbenv_search.h", "pcbenv_priors.h", "pcbenv_move.h", "pcbenv_train.h", "pcbenv_leaves.h", "pcbenv_noise.h", "pcbenv_gumbel.h", "pcbenv_gumbel_leaves.h", "pcbenv_gumbel_tree.h", "pcbenv_gumbel_tree_leaves.h", "pcbenv_frontier.h", "pcbenv_frontier_sample.h")] + sorted(
     os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc", ".hip", ".cpp")))
 OUT = os.path.join(HERE, "libpcbenv.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17", "-Wno-unused-value", "-pthread"]

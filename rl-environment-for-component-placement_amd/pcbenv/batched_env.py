@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _frontier_lib, _gumbel_leaves_lib, _gumbel_lib, _gumbel_tree_leaves_lib, _gumbel_tree_lib, _leaves_lib, _lib, _move_lib, _noise_lib, _priors_lib, _search_lib, _train_lib
+from . import _frontier_lib, _frontier_sample_lib, _gumbel_leaves_lib, _gumbel_lib, _gumbel_tree_leaves_lib, _gumbel_tree_lib, _leaves_lib, _lib, _move_lib, _noise_lib, _priors_lib, _search_lib, _train_lib
 from .config import EnvConfig, KIND_PIN, KIND_RECT, KIND_SPATIAL, KIND_SQUARE
 from .instances import Instance, InstanceStream, env_seed, pack_instances
 
@@ -169,7 +169,7 @@ class BatchedPlacementEnv:
             raise RuntimeError("BatchedPlacementEnv needs a GPU device (there is no CPU fallback)")
         # the device the handle lives on, index included: one named without an index is the current device, now and for good
         self.device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
-        self._L = _frontier_lib.bind(_gumbel_tree_leaves_lib.bind(_gumbel_tree_lib.bind(_gumbel_leaves_lib.bind(_gumbel_lib.bind(_noise_lib.bind(_leaves_lib.bind(_train_lib.bind(_move_lib.bind(_priors_lib.bind(_search_lib.bind(_lib.load())))))))))))
+        self._L = _frontier_sample_lib.bind(_frontier_lib.bind(_gumbel_tree_leaves_lib.bind(_gumbel_tree_lib.bind(_gumbel_leaves_lib.bind(_gumbel_lib.bind(_noise_lib.bind(_leaves_lib.bind(_train_lib.bind(_move_lib.bind(_priors_lib.bind(_search_lib.bind(_lib.load()))))))))))))
         # per-environment spaces (the reference constructors' declarations); every tensor adds a leading batch dim
         from .spaces import action_space_for, observation_space_for
         self.action_space = self.single_action_space = action_space_for(cfg)
@@ -991,6 +991,57 @@ class BatchedPlacementEnv:
         ev = evaluation
         over = None if ev is None else ev.terminal.view(torch.uint8) if ev.terminal.dtype == torch.bool else ev.terminal
         self._advance(self._L.pcbenv_frontier_advance, req, phases,
+                      (("value", None if ev is None else ev.value, torch.float64, (R,)), ("leaf_terminal", over, torch.uint8, (R,)),
+                       ("cand_count", None if ev is None else ev.cand_count, torch.int32, (R,)),
+                       ("cand_actions", None if ev is None else ev.cand_actions, torch.int32, (R, K, 3)),
+                       ("cand_prior", None if ev is None else ev.cand_prior, torch.float32, (R, K))))
+
+    def frontier_sample_request(self, tensors: Dict[str, torch.Tensor], width: int, num_candidates: int, seed: int,
+                                first_root: int = 0) -> "_frontier_sample_lib.PcbenvFrontierSampleRequest":
+        """The request of `frontier_sample` for the tensors in `tensors` (see `pcbenv.search.new_frontier_sample_tensors` for
+        a set of the right shapes): the tensors `frontier_request` takes, `gumbel_0` and `gumbel_1` float64 [P * W * K], the
+        third member of the two sets of rows, and the sample set `set_len` [P * W], `set_gumbel`, `set_logp`, `set_value`
+        float64 [P * W] and `set_path` [T, P * W, 3] of pcbenv_frontier_sample_request (include/pcbenv_frontier_sample.h)
+        -- on this device, contiguous.  P and T are read off `best_path` [T, P, 3]; `seed` and `first_root`, the global
+        index of root 0, name the draws.  The request holds addresses only: the caller keeps the tensors alive."""
+        W, K, best = int(width), int(num_candidates), tensors["best_path"]
+        if W < 1 or W > _frontier_lib.MAX_FRONTIER_WIDTH or K < 1 or K > _frontier_lib.MAX_FRONTIER_CANDIDATES or W * K > _frontier_lib.MAX_FRONTIER_ROWS:
+            raise ValueError(f"width and num_candidates must be in [1, 64] and their product at most {_frontier_lib.MAX_FRONTIER_ROWS}, got {W} and {K}")
+        if best.dim() != 3 or best.shape[2] != 3:
+            raise ValueError(f"best_path must be [T, P, 3], got {tuple(best.shape)}")
+        T, P = int(best.shape[0]), int(best.shape[1])
+        i32, f64, R, S = torch.int32, torch.float64, P * W * K, P * W
+        want = {"parent_row": (i32, (R,)), "live": (i32, (P,)), "best_value": (f64, (P,)), "best_len": (i32, (P,)), "best_path": (i32, (T, P, 3)),
+                "set_len": (i32, (S,)), "set_gumbel": (f64, (S,)), "set_logp": (f64, (S,)), "set_value": (f64, (S,)), "set_path": (i32, (T, S, 3))}
+        req = self._tree_request(_frontier_sample_lib.PcbenvFrontierSampleRequest, tensors, want, num_roots=P, width=W, num_candidates=K, max_steps=T,
+                                 seed=int(seed) & (2 ** 64 - 1), first_root=int(first_root))
+        sets = []
+        for s in (0, 1):
+            for name, (dtype, shape) in (("paths", (i32, (T, R, 3))), ("path_len", (i32, (R,))), ("cum_logp", (f64, (R,))), ("gumbel", (f64, (R,)))):
+                check_tensor(self.device, f"{name}_{s}", tensors[f"{name}_{s}"], dtype, shape)
+            sets.append({name: _ptr(tensors[f"{name}_{s}"]) for name in _frontier_sample_lib.SAMPLE_SET})
+        req.sets = sets  # the addresses of set 0 and set 1: `frontier_sample` names one `in` and the other `out`
+        return req
+
+    def frontier_sample(self, req: "_frontier_sample_lib.PcbenvFrontierSampleRequest", phases: int, step_index: int, evaluation=None,
+                        swap: bool = False) -> None:
+        """One depth of P stochastic beam searches over placements on the device (`pcbenv_frontier_sample`, one kernel launch
+        on the current stream, nothing else).  As `frontier_advance`, with the rows ordered by their perturbed
+        log-probability `gumbel` in place of their value: ADVANCE keeps the W contenders with the largest one among the set
+        entries, the finished rows -- which enter the sample set `set_*` -- and the expandable rows, whose children are
+        written with a Gumbel of their own, drawn for (seed, first_root + p, `step_index`).  `req`:
+        `frontier_sample_request(...)`, reusable for every call on the same tensors."""
+        P, K = req.num_roots, req.num_candidates
+        if P == 0:  # torch gives empty tensors a null pointer
+            return
+        R = P * req.width * K
+        for name in _frontier_sample_lib.SAMPLE_SET:
+            setattr(req, name + "_in", req.sets[1 if swap else 0][name])
+            setattr(req, name + "_out", req.sets[0 if swap else 1][name])
+        req.step_index = int(step_index) & (2 ** 64 - 1)
+        ev = evaluation
+        over = None if ev is None else ev.terminal.view(torch.uint8) if ev.terminal.dtype == torch.bool else ev.terminal
+        self._advance(self._L.pcbenv_frontier_sample, req, phases,
                       (("value", None if ev is None else ev.value, torch.float64, (R,)), ("leaf_terminal", over, torch.uint8, (R,)),
                        ("cand_count", None if ev is None else ev.cand_count, torch.int32, (R,)),
                        ("cand_actions", None if ev is None else ev.cand_actions, torch.int32, (R, K, 3)),

@@ -33,6 +33,9 @@ did before that keyword existed.
 evaluator's K best legal actions, the W best of the W * K children kept per depth, the best finished placement the
 result -- on `frontier_advance`, the specification in tensor code of pcbenv_frontier_advance
 (include/pcbenv_frontier.h); `frontier_search_device` is the same search with one launch per depth.
+`frontier_sample_search` is that search with the rows ordered by Gumbel-perturbed log-probabilities -- stochastic beam search,
+W placements per root sampled without replacement -- on `frontier_sample_advance`, the specification of
+pcbenv_frontier_sample (include/pcbenv_frontier_sample.h); `frontier_sample_search_device` has one launch per depth.
 
 `policy_backend` replaces the uniform rollout of either search by a policy's: the node a path names is materialised
 in a planner batch by `gather_(paths=...)` (pcbenv_gather_paths, one launch), and the rollout behind it draws from the
@@ -41,6 +44,7 @@ logits a network gives for the planner's observations.
 from __future__ import annotations
 
 from dataclasses import dataclass
+from types import SimpleNamespace
 
 import torch
 
@@ -1746,6 +1750,74 @@ def log_prior(prior: torch.Tensor) -> torch.Tensor:
     return torch.where(ok, ieee_ln(x), torch.full_like(x, float("-inf")))
 
 
+def _frontier_rows(ft: dict, width: int, num_candidates: int, evaluation, swap: bool):
+    """Steps 1 and 2 of `frontier_advance` -- the live rows, bit 1 of the error word and the best finished row -- and the
+    tensors the later steps read, as a namespace."""
+    W, K = int(width), int(num_candidates)
+    F = W * K
+    T, P = int(ft["best_path"].shape[0]), int(ft["best_path"].shape[1])
+    a, b = (1, 0) if swap else (0, 1)
+    paths_in, len_in, cum_in = ft[f"paths_{a}"], ft[f"path_len_{a}"], ft[f"cum_logp_{a}"]
+    paths_out, len_out, cum_out = ft[f"paths_{b}"], ft[f"path_len_{b}"], ft[f"cum_logp_{b}"]
+    dev = len_in.device
+    slot = torch.arange(F, dtype=torch.int64, device=dev)
+    ev = evaluation
+    f64 = dict(dtype=torch.float64, device=dev)
+    ninf = torch.full((), float("-inf"), **f64)
+    length = len_in.view(P, F).to(torch.int64)
+    live = (length >= 0) & (length <= T)
+    damaged = (length < -1) | (length > T)
+    if ft.get("errors_dev") is not None:
+        ft["errors_dev"] |= (damaged.any().to(torch.int32) * FRONTIER_ERR_ROW)
+    value = ev.value.to(**f64).view(P, F)
+    over = ev.terminal.to(dev).view(P, F) != 0
+    k = ev.cand_count.to(device=dev, dtype=torch.int64).view(P, F).clamp(0, K)
+    cand_actions = ev.cand_actions.to(device=dev, dtype=torch.int32).view(P, F, K, 3)
+    cand_prior = ev.cand_prior.to(device=dev, dtype=torch.float32).view(P, F, K)
+    rows = torch.arange(P, dtype=torch.int64, device=dev)
+    pin = paths_in.view(T, P, F, 3)
+    # finished rows: the first of those with the largest value is the one a walk in increasing i ends with
+    fin = live & over
+    v = torch.where(fin & ~torch.isnan(value), value, ninf)
+    top = v.max(dim=1, keepdim=True).values
+    first = torch.where(fin & (v == top), slot[None, :], F).min(dim=1).values.clamp(max=F - 1)
+    v_first, len_first = v[rows, first], length[rows, first]
+    better = fin.any(dim=1) & ((ft["best_len"] == -1) | (v_first > ft["best_value"]))
+    ft["best_value"].copy_(torch.where(better, v_first, ft["best_value"]))
+    ft["best_len"].copy_(torch.where(better, len_first.to(torch.int32), ft["best_len"]))
+    step = torch.arange(T, dtype=torch.int64, device=dev)
+    taken = better[None, :] & (step[:, None] < len_first[None, :])                                    # [T, P]
+    ft["best_path"].copy_(torch.where(taken[:, :, None], pin[:, rows, first], ft["best_path"]))
+    expandable = live & ~over & (length < T) & (k > 0)
+    cum = cum_in.view(P, F)
+    return SimpleNamespace(**locals())
+
+
+def _frontier_children(ft: dict, x, kept: torch.Tensor, n: torch.Tensor):
+    """Step 4 of `frontier_advance` for the rows and tensors `x` of `_frontier_rows`: the children of the kept rows `kept`
+    [P, W] (slots of the in set, in rank order), of which the first `n` [P] count, into the out set.  -> (child, parent, c),
+    [P, F] bool, [P, F] and [F]: which out slots hold a child, the in slot of their parent, and their candidate."""
+    W, K, F, T, P, dev, slot, length, k, cum, rows, pin, step = x.W, x.K, x.F, x.T, x.P, x.dev, x.slot, x.length, x.k, x.cum, x.rows, x.pin, x.step
+    len_out, cum_out, paths_out, cand_prior, cand_actions = x.len_out, x.cum_out, x.paths_out, x.cand_prior, x.cand_actions
+    w, c = torch.div(slot, K, rounding_mode="floor"), slot % K
+    parent = kept[:, w]                                                                                # [P, F]
+    child = (w[None, :] < n[:, None]) & (c[None, :] < k.gather(1, parent))
+    plen = length.gather(1, parent)
+    len_out.view(P, F).copy_(torch.where(child, plen + 1, -1))
+    ft["parent_row"].view(P, F).copy_(torch.where(child, parent, -1))
+    lp = log_prior(cand_prior[rows[:, None], parent, c[None, :]])
+    cum_out.view(P, F).copy_(torch.where(child, cum.gather(1, parent) + lp, cum_out.view(P, F)))
+    pout = paths_out.view(T, P, F, 3)
+    inherited = pin.gather(2, parent[None, :, :, None].expand(T, P, F, 3))
+    own = cand_actions[rows[:, None], parent, c[None, :]]                                              # [P, F, 3]
+    at = step[:, None, None]
+    new = torch.where((child[None] & (at < plen[None]))[..., None], inherited,
+                      torch.where((child[None] & (at == plen[None]))[..., None], own[None].expand(T, P, F, 3), pout))
+    pout.copy_(new)
+    ft["live"].copy_(child.sum(dim=1))
+    return child, parent, c
+
+
 def frontier_advance(ft: dict, phases: int, width: int, num_candidates: int, prior_weight: float = 0.0, evaluation=None, swap: bool = False) -> None:
     """One depth of a beam search over placements, in tensor code for any device and without a host synchronisation: the
     specification of pcbenv_frontier_advance (include/pcbenv_frontier.h), on the tensors of `new_frontier_tensors`, in
@@ -1789,59 +1861,15 @@ def frontier_advance(ft: dict, phases: int, width: int, num_candidates: int, pri
         ft["best_len"].fill_(-1)
         ft["best_value"].fill_(float("-inf"))
         return
-    ev = evaluation
-    f64 = dict(dtype=torch.float64, device=dev)
-    ninf = torch.full((), float("-inf"), **f64)
-    length = len_in.view(P, F).to(torch.int64)
-    live = (length >= 0) & (length <= T)
-    damaged = (length < -1) | (length > T)
-    if ft.get("errors_dev") is not None:
-        ft["errors_dev"] |= (damaged.any().to(torch.int32) * FRONTIER_ERR_ROW)
-    value = ev.value.to(**f64).view(P, F)
-    over = ev.terminal.to(dev).view(P, F) != 0
-    k = ev.cand_count.to(device=dev, dtype=torch.int64).view(P, F).clamp(0, K)
-    cand_actions = ev.cand_actions.to(device=dev, dtype=torch.int32).view(P, F, K, 3)
-    cand_prior = ev.cand_prior.to(device=dev, dtype=torch.float32).view(P, F, K)
-    rows = torch.arange(P, dtype=torch.int64, device=dev)
-    pin = paths_in.view(T, P, F, 3)
-    # finished rows: the first of those with the largest value is the one a walk in increasing i ends with
-    fin = live & over
-    v = torch.where(fin & ~torch.isnan(value), value, ninf)
-    top = v.max(dim=1, keepdim=True).values
-    first = torch.where(fin & (v == top), slot[None, :], F).min(dim=1).values.clamp(max=F - 1)
-    v_first, len_first = v[rows, first], length[rows, first]
-    better = fin.any(dim=1) & ((ft["best_len"] == -1) | (v_first > ft["best_value"]))
-    ft["best_value"].copy_(torch.where(better, v_first, ft["best_value"]))
-    ft["best_len"].copy_(torch.where(better, len_first.to(torch.int32), ft["best_len"]))
-    step = torch.arange(T, dtype=torch.int64, device=dev)
-    taken = better[None, :] & (step[:, None] < len_first[None, :])                                    # [T, P]
-    ft["best_path"].copy_(torch.where(taken[:, :, None], pin[:, rows, first], ft["best_path"]))
+    x = _frontier_rows(ft, W, K, evaluation, swap)
     # the order of the expandable rows
-    expandable = live & ~over & (length < T) & (k > 0)
-    cum = cum_in.view(P, F)
-    score = value if float(prior_weight) == 0.0 else value + float(prior_weight) * torch.where(expandable, cum, torch.zeros_like(cum))
-    score = torch.where(expandable & ~torch.isnan(score), score, ninf) + 0.0  # + 0.0: -0.0 and +0.0 are one key to any sort
+    score = x.value if float(prior_weight) == 0.0 else x.value + float(prior_weight) * torch.where(x.expandable, x.cum, torch.zeros_like(x.cum))
+    score = torch.where(x.expandable & ~torch.isnan(score), score, x.ninf) + 0.0  # + 0.0: -0.0 and +0.0 are one key to any sort
     by_score = torch.sort(score, dim=1, descending=True, stable=True).indices
-    behind = (~expandable).gather(1, by_score).to(torch.int8)
+    behind = (~x.expandable).gather(1, by_score).to(torch.int8)
     order = by_score.gather(1, torch.sort(behind, dim=1, stable=True).indices)  # the expandable rows first, each part in the order it had
-    n = expandable.sum(dim=1).clamp(max=W)
-    # the children
-    w, c = torch.div(slot, K, rounding_mode="floor"), slot % K
-    parent = order[:, :W][:, w]                                                                        # [P, F]
-    child = (w[None, :] < n[:, None]) & (c[None, :] < k.gather(1, parent))
-    plen = length.gather(1, parent)
-    len_out.view(P, F).copy_(torch.where(child, plen + 1, -1))
-    ft["parent_row"].view(P, F).copy_(torch.where(child, parent, -1))
-    lp = log_prior(cand_prior[rows[:, None], parent, c[None, :]])
-    cum_out.view(P, F).copy_(torch.where(child, cum.gather(1, parent) + lp, cum_out.view(P, F)))
-    pout = paths_out.view(T, P, F, 3)
-    inherited = pin.gather(2, parent[None, :, :, None].expand(T, P, F, 3))
-    own = cand_actions[rows[:, None], parent, c[None, :]]                                              # [P, F, 3]
-    at = step[:, None, None]
-    new = torch.where((child[None] & (at < plen[None]))[..., None], inherited,
-                      torch.where((child[None] & (at == plen[None]))[..., None], own[None].expand(T, P, F, 3), pout))
-    pout.copy_(new)
-    ft["live"].copy_(child.sum(dim=1))
+    n = x.expandable.sum(dim=1).clamp(max=W)
+    _frontier_children(ft, x, order[:, :W], n)
 
 
 @dataclass
@@ -1925,3 +1953,194 @@ def frontier_search_device(root, evaluate, width: int, max_children: int, step_i
         ev = evaluate(ft[f"paths_{cur}"], ft[f"path_len_{cur}"], int(step_index) + d * T)
         root.frontier_advance(req, FRONTIER_ADVANCE, ev, swap=cur == 1)
     return frontier_result(ft, D % 2)
+
+
+# ---- the stochastic frontier: sampling placements without replacement ------------------------------------------------
+FRONTIER_ERR_SET = 4          # bit 2 of the error word: a set_len outside [-1, T]
+FRONTIER_SAMPLE_DRAWS = 256   # csrc/pcb_frontier_sample.h:GUMBEL_DRAWS: draw 256 + i of child c is the Gumbel of child c of the parent in slot i
+FRONTIER_SAMPLE_SET = ("set_len", "set_gumbel", "set_logp", "set_value", "set_path")
+
+
+def new_frontier_sample_tensors(P: int, W: int, K: int, T: int, device) -> dict:
+    """The tensors of `new_frontier_tensors` and what `BatchedPlacementEnv.frontier_sample_request` takes beside them:
+    `gumbel_s` float64 [P * W * K], s = 0, 1, the third member of the two sets of rows, and the sample set of W slots per
+    root, `set_len` [P * W], `set_gumbel`, `set_logp`, `set_value` float64 [P * W] and `set_path` [T, P * W, 3]."""
+    i32, f64 = dict(dtype=torch.int32, device=device), dict(dtype=torch.float64, device=device)
+    R, S = int(P) * int(W) * int(K), int(P) * int(W)
+    ft = new_frontier_tensors(P, W, K, T, device)
+    ft.update(gumbel_0=torch.zeros(R, **f64), gumbel_1=torch.zeros(R, **f64), set_len=torch.empty(S, **i32), set_gumbel=torch.zeros(S, **f64),
+              set_logp=torch.zeros(S, **f64), set_value=torch.zeros(S, **f64), set_path=torch.zeros((T, S, 3), **i32))
+    return ft
+
+
+def _is_finite(x: torch.Tensor) -> torch.Tensor:
+    return (x - x) == 0.0
+
+
+def truncated_gumbel(G_S: torch.Tensor, phi: torch.Tensor, G_c: torch.Tensor, Z: torch.Tensor) -> torch.Tensor:
+    """csrc/pcb_frontier_sample.h:child_gumbel, the same operations: the perturbed log-probability of a child with
+    log-probability phi and G_c = phi + g_c, given its parent's G_S and Z, the largest G_c among its siblings."""
+    zero, one = torch.zeros_like(G_c), torch.ones_like(G_c)
+    ok = _is_finite(phi) & _is_finite(G_S)
+    gs, gc = torch.where(ok, G_S, zero), torch.where(ok, G_c, zero)
+    a = torch.where(ok, G_c - Z, zero)
+    d = 1.0 - ieee_exp(a)
+    same = (a == 0.0) | (d <= 0.0)
+    v = (gs - gc) + ieee_ln(torch.where(same, one, d))
+    top, mag = torch.where(v > 0.0, v, zero), torch.where(v < 0.0, -v, v)
+    out = (gs - top) - ieee_ln(1.0 + ieee_exp(-mag))
+    ninf = torch.full_like(G_c, float("-inf"))
+    return torch.where(_is_finite(phi), torch.where(_is_finite(G_S) & ~same, out, G_S), ninf)
+
+
+def _ranked(mask: torch.Tensor, values: torch.Tensor):
+    """Along dim 1: the `values` where `mask` holds, moved to the front in their order -> (those, how many)."""
+    P, W = mask.shape
+    rank = mask.to(torch.int64).cumsum(dim=1) - 1
+    front = torch.zeros((P, W + 1), dtype=values.dtype, device=values.device)
+    front.scatter_(1, torch.where(mask, rank, W), values)
+    return front[:, :W], mask.sum(dim=1)
+
+
+def frontier_sample_advance(ft: dict, phases: int, width: int, num_candidates: int, seed: int, step_index: int, first_root: int = 0,
+                            evaluation=None, swap: bool = False) -> None:
+    """One depth of a stochastic beam search over placements (Kool, van Hoof and Welling, ICML 2019), in tensor code for any
+    device and without a host synchronisation: the specification of pcbenv_frontier_sample
+    (include/pcbenv_frontier_sample.h), on the tensors of `new_frontier_sample_tensors`, in place; swap as in
+    `frontier_advance`.
+    FRONTIER_INIT is `frontier_advance`'s, and gumbel of slot 0 = 0.0 and set_len = -1 everywhere.
+    FRONTIER_ADVANCE: the live rows and the best finished row as in `frontier_advance`.  Then
+      the contenders   set slots with set_len in [0, T] (outside [-1, T]: bit 2 of `errors_dev`), id j, key set_gumbel; live
+                       rows that are finished or expandable, id W + i, key gumbel; a NaN key counts as -inf.
+      the winners      the first min(W, contenders) by key descending, ties -- -0.0 with +0.0 among them -- to the lower id.
+                       A set entry that did not win gets set_len -1.  The m-th finished winner goes into the m-th lowest
+                       slot without a surviving entry: set_len, set_gumbel = its key, set_logp = its cum_logp, set_value =
+                       its value, set_path = its path.  The expandable winners are the kept rows, in rank order.
+      the children     as in `frontier_advance`, and gumbel = `truncated_gumbel` of the parent's key, the child's cum_logp
+                       phi, phi + g with g = -ln(-ln u), u draw number 256 + the parent's slot of child c under (seed,
+                       first_root + p, step_index), and Z, the largest phi + g over the parent's children with finite phi."""
+    W, K, ph = int(width), int(num_candidates), int(phases)
+    if ph not in (FRONTIER_INIT, FRONTIER_ADVANCE):
+        raise ValueError("phases must be FRONTIER_INIT or FRONTIER_ADVANCE")
+    if W < 1 or W > MAX_FRONTIER_WIDTH or K < 1 or K > MAX_FRONTIER_CANDIDATES or W * K > MAX_FRONTIER_ROWS:
+        raise ValueError(f"width and num_candidates must be in [1, 64] and their product at most {MAX_FRONTIER_ROWS}, got {W} and {K}")
+    F = W * K
+    T, P = int(ft["best_path"].shape[0]), int(ft["best_path"].shape[1])
+    if P == 0:
+        return
+    a, b = (1, 0) if swap else (0, 1)
+    gum_in, gum_out = ft[f"gumbel_{a}"].view(P, F), ft[f"gumbel_{b}"].view(P, F)
+    if ph == FRONTIER_INIT:
+        frontier_advance(ft, FRONTIER_INIT, W, K, swap=swap)
+        gum_out[:, 0] = 0.0
+        ft["set_len"].fill_(-1)
+        return
+    x = _frontier_rows(ft, W, K, evaluation, swap)
+    dev, ninf, length = x.dev, x.ninf, x.length
+    # the contenders
+    set_len = ft["set_len"].view(P, W).to(torch.int64)
+    entry = (set_len >= 0) & (set_len <= T)
+    if ft.get("errors_dev") is not None:
+        ft["errors_dev"] |= (((set_len < -1) | (set_len > T)).any().to(torch.int32) * FRONTIER_ERR_SET)
+    set_gumbel = ft["set_gumbel"].view(P, W)
+    key_set = torch.where(entry & ~torch.isnan(set_gumbel), set_gumbel, ninf)
+    contender = x.fin | x.expandable
+    key_row = torch.where(contender & ~torch.isnan(gum_in), gum_in, ninf)
+    key = torch.cat([key_set, key_row], dim=1) + 0.0  # + 0.0: -0.0 and +0.0 are one key to any sort
+    valid = torch.cat([entry, contender], dim=1)
+    by_key = torch.sort(key, dim=1, descending=True, stable=True).indices
+    behind = (~valid).gather(1, by_key).to(torch.int8)
+    order = by_key.gather(1, torch.sort(behind, dim=1, stable=True).indices)  # the contenders first, each part in the order it had
+    # the winners
+    won = order[:, :W]
+    is_winner = torch.arange(W, dtype=torch.int64, device=dev)[None, :] < valid.sum(dim=1).clamp(max=W)[:, None]
+    from_set = is_winner & (won < W)
+    row = (won - W).clamp(min=0)
+    finished = is_winner & ~from_set & x.fin.gather(1, row)
+    survivor = torch.zeros((P, W + 1), dtype=torch.bool, device=dev)
+    survivor.scatter_(1, torch.where(from_set, won, W), torch.ones_like(from_set))
+    survivor = survivor[:, :W]
+    entered, count = _ranked(finished, row)
+    vacant = ~survivor
+    rank = vacant.to(torch.int64).cumsum(dim=1) - 1
+    takes = vacant & (rank < count[:, None])
+    src = entered.gather(1, rank.clamp(min=0))                                                        # [P, W]
+    src_len = length.gather(1, src)
+    ft["set_len"].view(P, W).copy_(torch.where(takes, src_len, torch.where(entry & ~survivor, -1, set_len)))
+    set_gumbel.copy_(torch.where(takes, key_row.gather(1, src), set_gumbel))
+    ft["set_logp"].view(P, W).copy_(torch.where(takes, x.cum.gather(1, src), ft["set_logp"].view(P, W)))
+    ft["set_value"].view(P, W).copy_(torch.where(takes, x.value.gather(1, src), ft["set_value"].view(P, W)))
+    set_path = ft["set_path"].view(T, P, W, 3)
+    moved = x.pin.gather(2, src[None, :, :, None].expand(T, P, W, 3))
+    set_path.copy_(torch.where((takes[None] & (x.step[:, None, None] < src_len[None]))[..., None], moved, set_path))
+    # the children
+    kept, n = _ranked(is_winner & ~from_set & ~finished, row)
+    child, parent, c = _frontier_children(ft, x, kept, n)
+    phi = x.cum_out.view(P, F)
+    genv = int(first_root) + torch.arange(P, dtype=torch.int64, device=dev)
+    base = noise_base(int(seed), genv, int(step_index))[:, None]
+    word = _mix64(base + (64 * (FRONTIER_SAMPLE_DRAWS + parent) + c[None, :] + 1) * _i64(_GOLDEN))
+    u = (_shr(word, 12).to(torch.float64) + 0.5) * (1.0 / 4503599627370496.0)
+    G_c = phi + -ieee_ln(-ieee_ln(u))
+    counts = child & _is_finite(phi)
+    Z = torch.where(counts, G_c, ninf).view(P, W, K).max(dim=2, keepdim=True).values.expand(P, W, K).reshape(P, F)
+    G = truncated_gumbel(key_row.gather(1, parent), torch.where(child, phi, ninf), G_c, Z)
+    gum_out.copy_(torch.where(child, G, gum_out))
+
+
+@dataclass
+class FrontierSampleSearch:
+    """What `frontier_sample_search` and `frontier_sample_search_device` return.  P roots, W = width slots per root, slot
+    p * W + j; the entries of a root in descending `set_gumbel` are its sample, in the order they were drawn."""
+    best_path: torch.Tensor   # [T, P, 3] int32: the path of the finished placement with the largest value (rows >= best_len: don't care)
+    best_len: torch.Tensor    # [P] int32: its length, -1 if no row of the root finished
+    best_value: torch.Tensor  # [P] float64: its value, -inf if none
+    action: torch.Tensor      # [P, 3] int32: best_path[0], zero where best_len < 1
+    live: torch.Tensor        # [P] int32: the rows of the final frontier (0: the set is complete)
+    errors: torch.Tensor      # 0-dim int32: bit 1 = a path_len, bit 2 = a set_len out of range was read
+    set_len: torch.Tensor     # [P * W] int32: the length of the placement in a slot, -1 = free
+    set_gumbel: torch.Tensor  # [P * W] float64: its perturbed log-probability
+    set_logp: torch.Tensor    # [P * W] float64: its log-probability under the policy restricted to the candidates
+    set_value: torch.Tensor   # [P * W] float64: its value
+    set_path: torch.Tensor    # [T, P * W, 3] int32: its path (rows >= set_len: don't care)
+
+
+def frontier_sample_result(ft: dict) -> FrontierSampleSearch:
+    """The tensors of a stochastic frontier search in the form the searches report."""
+    r = frontier_result(ft, 0)
+    return FrontierSampleSearch(r.best_path, r.best_len, r.best_value, r.action, r.live, r.errors, *(ft[n] for n in FRONTIER_SAMPLE_SET))
+
+
+def frontier_sample_search(root, evaluate, width: int, max_children: int, step_index: int, seed: int, first_root: int = 0, max_steps=None,
+                           depth=None) -> FrontierSampleSearch:
+    """A stochastic beam search over placements for all P = root.num_envs roots in lock-step, on the specification
+    `frontier_sample_advance`: `frontier_search` with the rows ordered by Gumbel-perturbed log-probabilities, which returns
+    W = width complete placements per root sampled without replacement from the policy `evaluate` gives (its K =
+    max_children candidates per node), each with its value and its log-probability, next to the best of them by value.
+    Depth d is `evaluate(paths, path_len, step_index + d * max_steps)` and one step with that step index; the draws depend
+    on (seed, first_root + p, step index) alone.  depth: the number of depths, default and at most max_steps + 1 (then
+    live == 0 and the set is complete)."""
+    P, W, K, _, T, D = _frontier_arguments(root, evaluate, width, max_children, 0.0, max_steps, depth)
+    ft = new_frontier_sample_tensors(P, W, K, T, getattr(root, "device", "cpu"))
+    frontier_sample_advance(ft, FRONTIER_INIT, W, K, seed, int(step_index), first_root, swap=True)  # writes set 0
+    for d in range(D):
+        cur = d % 2
+        ev = evaluate(ft[f"paths_{cur}"], ft[f"path_len_{cur}"], int(step_index) + d * T)
+        frontier_sample_advance(ft, FRONTIER_ADVANCE, W, K, seed, int(step_index) + d * T, first_root, ev, swap=cur == 1)
+    return frontier_sample_result(ft)
+
+
+def frontier_sample_search_device(root, evaluate, width: int, max_children: int, step_index: int, seed: int, first_root: int = 0, max_steps=None,
+                                  depth=None) -> FrontierSampleSearch:
+    """`frontier_sample_search` with the frontier step on the device: a depth is `evaluate` and one kernel launch,
+    `root.frontier_sample` (pcbenv_frontier_sample, include/pcbenv_frontier_sample.h), with no tensor operation between
+    them.  The same search as `frontier_sample_search` with the same arguments, field by field, floats by their bits."""
+    P, W, K, _, T, D = _frontier_arguments(root, evaluate, width, max_children, 0.0, max_steps, depth)
+    ft = new_frontier_sample_tensors(P, W, K, T, root.device)
+    req = root.frontier_sample_request(ft, W, K, seed, first_root)
+    root.frontier_sample(req, FRONTIER_INIT, int(step_index), swap=True)  # writes set 0
+    for d in range(D):
+        cur = d % 2
+        ev = evaluate(ft[f"paths_{cur}"], ft[f"path_len_{cur}"], int(step_index) + d * T)
+        root.frontier_sample(req, FRONTIER_ADVANCE, int(step_index) + d * T, ev, swap=cur == 1)
+    return frontier_sample_result(ft)

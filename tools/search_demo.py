@@ -1,5 +1,5 @@
 """Receding-horizon Monte-Carlo lookahead with pcbenv.search.best_of_k against the plain uniform-random policy, c3.
-python tools/search_demo.py [--roots 256] [--k 16] [--seed 11] [--playouts | --tree [--device-tree] [--policy] | --puct [--device-priors] [--reuse] [--leaves L] [--noise ALPHA EPS | --gumbel M [--leaves L] [--gumbel-full]] [--capacity N] [--train N [--moves M] [--torch-loss]] | --frontier W [--prior-weight X] [--device-priors]]
+python tools/search_demo.py [--roots 256] [--k 16] [--seed 11] [--playouts | --tree [--device-tree] [--policy] | --puct [--device-priors] [--reuse] [--leaves L] [--noise ALPHA EPS | --gumbel M [--leaves L] [--gumbel-full]] [--capacity N] [--train N [--moves M] [--torch-loss]] | --frontier W [--prior-weight X | --stochastic] [--device-priors]]
 
 Both play the same instances (one episode per root environment).  The search forks every root k times into a planner
 batch (one device-side gather), plays every child to its end with the on-device sampler, and applies the best child's
@@ -44,7 +44,12 @@ to the evaluation), ONE search per episode: a frontier of W partial placements p
 legal actions of network_evaluator (constant logits; --device-priors: pcbenv_top_priors) and scored by one uniform rollout from
 it, plus --prior-weight X times its cumulative log-prior.  The plan found, best_path, is then played with `step`.  The line
 reports the mean final reward, the rows evaluated and the time per episode, and that every played plan ended with the
-best_value the search reported for it."""
+best_value the search reported for it.
+--frontier W --stochastic: the same search with the rows ordered by Gumbel-perturbed log-probabilities
+(pcbenv.search.frontier_sample_search_device, one pcbenv_frontier_sample launch per depth): W complete placements per root
+sampled without replacement from the evaluator's priors under --seed.  The entry with the largest value is played; the line
+reports its mean reward, the mean reward over all entries and the distinct plans per root.
+"""
 import argparse
 import json
 import os
@@ -57,7 +62,7 @@ import torch  # noqa: E402
 from pcbenv import named_config  # noqa: E402
 from pcbenv.batched_env import BatchedPlacementEnv  # noqa: E402
 from pcbenv.config import KIND_SPATIAL  # noqa: E402
-from pcbenv.search import (best_of_k, best_of_k_playouts, frontier_search_device, gumbel_search_device, network_evaluator, policy_backend, puct_search_device, puct_selfplay, tree_search,  # noqa: E402
+from pcbenv.search import (best_of_k, best_of_k_playouts, frontier_sample_search_device, frontier_search_device, gumbel_search_device, network_evaluator, policy_backend, puct_search_device, puct_selfplay, tree_search,  # noqa: E402
                            tree_search_device)
 
 
@@ -110,6 +115,39 @@ def train(a, cfg):
     planner.close()
 
 
+def stochastic_frontier(a, root, fs, rows, spent, random_final, no_action, envs):
+    """--frontier W --stochastic: the entry of a root's sample with the largest value is played; one JSON line."""
+    P, W, T = a.roots, a.frontier, fs.set_path.shape[0]
+    n, value = fs.set_len.view(P, W), fs.set_value.view(P, W)
+    held = n >= 1
+    ninf = torch.full_like(value, float("-inf"))
+    best = torch.where(held, value, ninf).argmax(dim=1)                                  # [P]: the slot played
+    at = torch.arange(P, device=n.device)
+    plan_len, plan = n[at, best], fs.set_path.view(T, P, W, 3)[:, at, best]              # [P], [T, P, 3]
+
+    def play(t):
+        _, r, d, _ = root.step(torch.where((plan_len <= t)[:, None], no_action, plan[t]))
+        return r, d
+    final = final_rewards(root, play, T)
+    planned = plan_len >= 1
+    paths = fs.set_path.view(T, P, W, 3).permute(1, 2, 0, 3).cpu().numpy()
+    lens = n.cpu().numpy()
+    distinct = [len({paths[p, j, :lens[p, j]].tobytes() for j in range(W) if lens[p, j] >= 1}) for p in range(P)]
+    entries = int(held.sum())
+    out = {"config": a.config, "roots": P, "frontier": W, "k": a.k, "stochastic": True, "seed": a.seed,
+           "search": "frontier_sample_search_device+network_evaluator" + ("(priors=device)" if a.device_priors else ""),
+           "random_policy_mean_final_reward": float(random_final.mean()), "frontier_mean_final_reward": float(final.mean()),
+           "mean_best_reward": float(torch.where(held, value, ninf).max(dim=1).values[planned].mean()) if bool(planned.any()) else None,
+           "mean_set_reward": float(value[held].mean()) if entries else None, "set_entries_per_root": round(entries / P, 3),
+           "distinct_plans_per_root": round(sum(distinct) / P, 3), "every_entry_is_a_distinct_plan": sum(distinct) == entries,
+           "roots_with_a_plan": int(planned.sum()), "every_plan_reproduced_its_value": bool((final[planned] == value[at, best][planned]).all()),
+           "evaluated_rows_per_episode": round(int(rows) / P, 2), "us_per_evaluated_row": round(1e6 * spent / max(int(rows), 1), 3),
+           "search_seconds": round(spent, 3), "seconds_per_episode": round(spent / P, 6), "frontier_errors": int(fs.errors)}
+    print(json.dumps(out), flush=True)
+    for e in envs:
+        e.close()
+
+
 def frontier(a, cfg):
     """--frontier W: one search per episode and its plan played; one JSON line."""
     P, W, K, T = a.roots, a.frontier, a.k, cfg.max_num_components
@@ -131,10 +169,15 @@ def frontier(a, cfg):
     random_final = final_rewards(rand_root, lambda t: rand_root.rollout_step(t)[1:3], T)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    fs = frontier_search_device(root, evaluate, W, K, 1000, prior_weight=a.prior_weight)
+    if a.stochastic:
+        fs = frontier_sample_search_device(root, evaluate, W, K, 1000, seed=a.seed)
+    else:
+        fs = frontier_search_device(root, evaluate, W, K, 1000, prior_weight=a.prior_weight)
     torch.cuda.synchronize()
     spent = time.perf_counter() - t0
     no_action = torch.full((P, 3), -1, dtype=torch.int32, device=dev)
+    if a.stochastic:
+        return stochastic_frontier(a, root, fs, rows, spent, random_final, no_action, (rand_root, root, planner))
 
     def play(t):  # past its plan, or without one: an action that is no action ends the episode as it stands
         _, r, d, _ = root.step(torch.where((fs.best_len <= t)[:, None], no_action, fs.best_path[t]))
@@ -177,7 +220,10 @@ def main():
     ap.add_argument("--torch-loss", action="store_true", help="with --train: the policy loss through the torch chain (device_loss off)")
     ap.add_argument("--frontier", type=int, default=None, metavar="W", help="a beam search over placements, W rows per root and k candidates per row, one search per episode (frontier_search_device)")
     ap.add_argument("--prior-weight", type=float, default=0.0, metavar="X", help="with --frontier: the weight of a row's cumulative log-prior in its score")
+    ap.add_argument("--stochastic", action="store_true", help="with --frontier: a stochastic beam search (frontier_sample_search_device), W plans per root sampled without replacement under --seed; the best of them is played")
     a = ap.parse_args()
+    if a.stochastic and (a.frontier is None or a.prior_weight != 0.0):
+        ap.error("--stochastic goes with --frontier and without --prior-weight")
     if a.train and not a.puct:
         ap.error("--train goes with --puct")
     if a.frontier is not None and (a.puct or a.tree or a.playouts or a.train):
